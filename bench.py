@@ -16,13 +16,14 @@ Multi-GPU (--gpus N, launched by torch.distributed.run), two modes:
   --scaling strong: the FIXED 8192-bin x 62.5 M-row index (S-IBF-8192, 64 GB) cut into N column shards; value =
       k-mers / time = probes of the whole index per second; bytes_per_probe is the per-GPU share (4104 B at N = 1,
       520 B at N = 8).
-The default line also carries `roofline_hbm`: the same probe kernel on an 8 GB matrix (the 8192-bin config's
-per-GPU shard), which does not fit the 256 MB Infinity Cache that the 160 MB S-IBF-1024 matrix lives in.
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if given and prints its line; every other leg
+below runs only with --full.  The --full line also carries `roofline_hbm`: the same probe kernel on an 8 GB matrix (the
+8192-bin config's per-GPU shard), which does not fit the 256 MB Infinity Cache that the 160 MB S-IBF-1024 matrix lives in.
 
 Output: ONE JSON line on rank 0 (contract in the task description), including
   roofline     — algorithmic bytes of the probe kernel / its HIP-event duration vs 8 TB/s HBM,
-  cpu_baseline — the CPU oracle (oracle/, a port of the reference path) timed on this host.
-Two further legs report the other BASELINE figures without touching `value`:
+  cpu_baseline — (--full) the CPU oracle (oracle/, a port of the reference path) timed on this host.
+Two further legs (--full) report the other BASELINE figures without touching `value`:
   end_to_end   — queries/s, regex -> candidate-bin mask, on the same index, with its own cpu_baseline
                  (the oracle's single-threaded query(), ~10 s, masks compared bit for bit); at N = 1 also
                  end_to_end.hibf_batch: the same motif batch on a 1024-user-bin HIBF (BASELINE configs[2]);
@@ -42,6 +43,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
+DUMP_SAMPLE_BYTES = 32 << 20  # --dump-outputs: sampled mask rows of all ranks together (the files stay well under 64 MB)
 
 
 def usable_cpus():
@@ -174,8 +176,29 @@ def timed_probe_steps(torch, dist, ix, d_kmers, n, d_masks, stream, steps, warmu
     return elapsed, float(np.mean([a.elapsed_time(b) for a, b in evs])) / 1e3
 
 
+def dump_outputs(torch, d_masks, n, W, rank, world, outdir):
+    """--dump-outputs DIR: what the timed path returned in its last step — one row of W u64 mask words per k-mer — as float64
+    .npy files, for output-for-output comparisons of two builds (the inputs depend on the arguments alone):
+      kmer_index.npy   (S,)       a fixed sample of the batch (splitmix64, seed 9), sorted, duplicates dropped;
+      masks.npy        (S, W, 2)  the mask rows of those k-mers, each word as [low 32 bits, high 32 bits] (exact in float64);
+      column_sums.npy  (W, 4)     over ALL n k-mers: the sum of each word's 16-bit pieces, lowest first (exact below 2^37
+                                  k-mers), so that a row outside the sample cannot change unseen.
+    At N > 1 every rank writes its own column shard as masks_rank<r>.npy and column_sums_rank<r>.npy."""
+    os.makedirs(outdir, exist_ok=True)
+    s = min(n, max(1, DUMP_SAMPLE_BYTES // (world * W * 16)))
+    idx = np.unique(splitmix64(9, s) % np.uint64(n)).astype(np.int64)
+    rows = d_masks[torch.from_numpy(idx).to(d_masks.device)].cpu().numpy().view(np.uint64)
+    masks = np.stack([rows & np.uint64(0xFFFFFFFF), rows >> np.uint64(32)], axis=-1).astype(np.float64)
+    sums = np.stack([((d_masks >> (16 * j)) & 0xFFFF).sum(dim=0).cpu().numpy() for j in range(4)], axis=-1).astype(np.float64)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    if rank == 0:
+        np.save(os.path.join(outdir, "kmer_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(outdir, "masks%s.npy" % suffix), masks)
+    np.save(os.path.join(outdir, "column_sums%s.npy" % suffix), sums)
+
+
 def hbm_leg(capi, torch, args, h):
-    """The out-of-cache leg of the default line: the SAME probe kernel on the 8192-bin config's per-GPU shard — 1024
+    """The out-of-cache leg of the --full line: the SAME probe kernel on the 8192-bin config's per-GPU shard — 1024
     bins x 62.5 M rows = 8 GB, 30x the Infinity Cache — with uniform 40-bit k-mers, so every row gather goes to HBM.
     Rank-local, after the timed region; does not touch `value`."""
     rows, bits, per_bin = 62500000, 40, 20000
@@ -1178,7 +1201,15 @@ def main():
     ap.add_argument("--rehearse-single-device", action="store_true",
                     help="N>1 rehearsal on a one-GPU box: every rank uses cuda:0 and the collectives run over gloo on host "
                          "tensors (RCCL refuses two ranks on one device); numbers from such a run are not bench results")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the timed probe steps: CPU baselines and parity checks, end-to-end query batches, "
+                         "HIBF legs, the out-of-cache roofline_hbm leg, the one-process N-device legs (the --no-* options pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the masks of the last step (a fixed sample plus column sums) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run does what its headline figure needs and nothing else
+        args.no_cpu = args.no_queries = args.no_hibf = args.no_hbm_leg = args.no_dna_batch = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as a CHILD process (never an exec: nothing
@@ -1248,6 +1279,8 @@ def main():
     d_masks = torch.empty((n, W), dtype=torch.int64, device="cuda")
     stream = torch.cuda.current_stream()
     elapsed, avg_kernel_s = timed_probe_steps(torch, dist, ix, d_kmers, n, d_masks, stream, args.steps, args.warmup, world, args.coll_device)
+    if args.dump_outputs:
+        dump_outputs(torch, d_masks, n, W, rank, world, args.dump_outputs)
 
     bytes_per_probe = h * W * 8 + W * 8 + 8  # rows + mask write + k-mer read (per GPU: its share of the index)
     achieved = bytes_per_probe * n / avg_kernel_s / 1e9

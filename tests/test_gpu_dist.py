@@ -93,7 +93,7 @@ def test_bench_two_rank_rehearsal_prints_one_contract_line():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--kmers", str(1 << 18), "--per-bin", "2000", "--motifs", "40", "--hibf-kmers", str(1 << 16), "--cpu-query-seconds", "2",
-           "--rehearse-single-device", "--rehearse-one-process"] + SMALL_DNA
+           "--rehearse-single-device", "--rehearse-one-process", "--full"] + SMALL_DNA
     out = _contract_line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline"):
@@ -139,7 +139,7 @@ def test_bench_strong_scaling_rehearsal():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--scaling", "strong", "--rows", "2000003", "--per-bin", "500", "--kmers", str(1 << 18), "--hibf-kmers", str(1 << 16),
-           "--cpu-query-seconds", "2", "--rehearse-single-device", "--rehearse-one-process"] + SMALL_DNA
+           "--cpu-query-seconds", "2", "--rehearse-single-device", "--rehearse-one-process", "--full"] + SMALL_DNA
     out = _contract_line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT))
     assert out["scaling"] == "strong" and out["unit"] == "probes/s" and out["n_gpus"] == 2
     cfg = out["config"]
@@ -158,12 +158,12 @@ def test_bench_refuses_a_rank_count_that_is_not_gpus():
 
 
 def test_bench_single_gpu_contract_line_with_all_legs():
-    """`python bench.py` at N=1 (small sizes): one JSON line with the contract keys, the roofline and
+    """`python bench.py --full` at N=1 (small sizes): one JSON line with the contract keys, the roofline and
     cpu_baseline objects, and the two extra legs without errors."""
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--kmers", str(1 << 18), "--per-bin", "2000",
-           "--motifs", "40", "--hibf-kmers", str(1 << 16), "--cpu-query-seconds", "1"] + SMALL_DNA
+           "--motifs", "40", "--hibf-kmers", str(1 << 16), "--cpu-query-seconds", "1", "--full"] + SMALL_DNA
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -188,3 +188,41 @@ def test_bench_single_gpu_contract_line_with_all_legs():
     dna = e2e["dna_batch_8192"]
     assert "error" not in dna and dna["failed"] == 0 and dna["motifs_found_in_their_home_bin"] == 300 and dna["cpu_oracle"]["masks_compared"] > 0
     assert "error" not in out["hibf"]["query_batch"] and out["hibf"]["query_batch"]["cpu_oracle"]["masks_compared"] > 0
+
+
+def test_bench_plain_run_times_the_probe_steps_alone_and_dumps_its_outputs(tmp_path, oracle):
+    """`python bench.py` without --full: the probe steps and the contract line, no other leg.  --dump-outputs writes the masks
+    of the last timed step (a fixed sample of rows, column sums over the whole batch): the same in two runs, and the CPU
+    oracle's masks on the same bits."""
+    import subprocess
+    import bench
+    n, per_bin, bins, steps = 1 << 18, 2000, 1024, 4
+    runs = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--kmers", str(n),
+               "--per-bin", str(per_bin), "--dump-outputs", str(d)]
+        out = _contract_line(subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT))
+        assert out["metric"] == "k-mer IBF probes/sec" and out["unit"] == "probes/s" and out["higher_is_better"] is True and out["dtype"] == "u64"
+        assert out["steps"] == steps and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0 and "roofline" in out
+        for leg in ("cpu_baseline", "cpu_baseline_all_cores", "parity_checked_probes", "end_to_end", "roofline_hbm", "hibf", "hibf_1024",
+                    "hibf_irregular"):
+            assert leg not in out, leg
+        assert sorted(f.name for f in d.iterdir()) == ["column_sums.npy", "kmer_index.npy", "masks.npy"]
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert all(a.dtype == np.float64 for a in files.values())
+        runs.append(files)
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
+    m = bench.compute_bitcount(per_bin, 0.05)
+    ox = oracle.Index.ibf(bins, m, 3, dna=False, k=4)
+    ox.emplace_pairs(bench.splitmix64(1, bins * per_bin) >> np.uint64(44), np.repeat(np.arange(bins, dtype=np.uint32), per_bin))
+    want = ox.probe(bench.splitmix64(2, n) >> np.uint64(44))
+    idx = runs[0]["kmer_index.npy"].astype(np.int64)
+    masks = runs[0]["masks.npy"]
+    assert idx.size > 1000 and np.all(np.diff(idx) > 0) and masks.shape == (idx.size, 16, 2)
+    got = (masks[..., 1].astype(np.uint64) << np.uint64(32)) | masks[..., 0].astype(np.uint64)
+    assert want[idx].any() and np.array_equal(got, want[idx])
+    sums = np.stack([((want >> np.uint64(16 * j)) & np.uint64(0xFFFF)).sum(axis=0) for j in range(4)], axis=-1).astype(np.float64)
+    assert np.array_equal(runs[0]["column_sums.npy"], sums)

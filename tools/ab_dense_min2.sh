@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 for kn in "TETREX_DENSE_MIN=32 TETREX_DENSE_SPARSE_BELOW=16" "TETREX_DENSE_MIN=8 TETREX_DENSE_SPARSE_BELOW=4" "TETREX_DENSE_MIN=16 TETREX_DENSE_SPARSE_BELOW=8"; do
   echo "== $kn"
-  env $kn timeout -k 10 400 python3 bench.py --no-cpu --no-verification 2>/dev/null | python3 -c "
+  env $kn timeout -k 10 400 python3 bench.py --full --no-cpu --no-verification 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); e=d['end_to_end']
 for k in ('batch','batch_10x','hibf_batch','k6_batch'):

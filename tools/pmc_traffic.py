@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """HBM traffic per kernel launch from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE: separate runs, with
 --kernel-trace only — MI355X_MICROARCH.md §HBM) of one command.  Usage (on the GPU box):
-    tools/pmc_traffic.py <out.json> <tag> -- python3 bench.py --steps 5 --warmup 1 --no-cpu --no-queries --no-hibf
+    tools/pmc_traffic.py <out.json> <tag> -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu --no-queries --no-hibf
 FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports 1/2 of the bytes of 16-B/lane coalesced reads
 (calibrated here on emplace_kernel, whose input is a known 12 bytes per value) -> corrected = 2 x FETCH + WRITE.
 Launches are grouped by kernel name, grid size and BUILD PHASE (a phase starts whenever emplace_kernel launches resume after

@@ -5,9 +5,9 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r2_final
 mkdir -p $O
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_probe -o probe -- python3 bench.py --no-queries --no-hibf --no-cpu > $O/bench_probe_legs.json 2> /dev/null
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_all -o all -- python3 bench.py --no-cpu > $O/bench_all_legs_under_rocprof.json 2> /dev/null
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_probe -o probe -- python3 bench.py --full --no-queries --no-hibf --no-cpu > $O/bench_probe_legs.json 2> /dev/null
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_all -o all -- python3 bench.py --full --no-cpu > $O/bench_all_legs_under_rocprof.json 2> /dev/null
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -o c3 -- python3 tests/perf_config3_queries.py > $O/config3.json 2> /dev/null
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_e2e -o e2e -- python3 tools/e2e_profile.py > $O/e2e_1k.txt 2>&1
 python tools/trace_timeline.py $O/prof_e2e/e2e_kernel_trace.csv > $O/e2e_timeline.txt
