@@ -157,6 +157,142 @@ def layout_hibf(O, seed, user_bins, tmax=64, h=2, n_values=20, value_bits=20, di
     return ox, descs, values
 
 
+AMINO = "ACDEFGHIKLMNPQRSTVWY"
+
+
+def kmer_values(motif, k):
+    """The packed k-mers of a literal protein string (5 bits per residue, first residue highest)."""
+    return [sum(AMINO.index(c) << (5 * (k - 1 - j)) for j, c in enumerate(motif[i:i + k])) for i in range(len(motif) - k + 1)]
+
+
+def layout_split_chunks(descs):
+    """Mirror of the upload rule for split user bins in layout order (csrc/txq_hibf.hip build_layout_order): the chunk width
+    (8-byte chunks when padding every IBF to 16 bytes would widen the row by more than 30 %), then per chunk of every IBF the
+    non-representative parts of each split user bin whose representative — its lowest technical bin — lies in that chunk,
+    ordered by the representative's bit and then by technical bin, and the chunk's first side bit (`bit0`: a chunk that does not
+    fit after the bits already used in a side word starts a fresh word).  Entry e of a chunk is side bit bit0 + e.
+    Returns (chunk words, [dict(ibf, chunk, bit0, entries=[(user bin, technical bin)])] for the chunks that have entries)."""
+    exact = sum((d["bins"] + 63) // 64 for d in descs)
+    padded2 = sum(((d["bins"] + 63) // 64 + 1) & ~1 for d in descs)
+    cwords = 1 if padded2 * 10 > exact * 13 else 2
+    out = []
+    for i, d in enumerate(descs):
+        tbs_of = {}
+        for tb, ub in enumerate(int(u) for u in d["tb_to_user"]):
+            if ub != MERGED:
+                tbs_of.setdefault(ub, []).append(tb)
+        per = {}
+        for ub in sorted(tbs_of):
+            rep, *parts = tbs_of[ub]
+            for tb in parts:
+                per.setdefault(rep // (64 * cwords), []).append((rep % (64 * cwords), ub, tb))
+        used = 0
+        for c in sorted(per):
+            ents = sorted(per[c], key=lambda e: e[0])  # (stable: technical-bin order within one user bin)
+            if used and used + len(ents) > 64:
+                used = 0
+            out.append(dict(ibf=i, chunk=c, bit0=used, entries=[(ub, tb) for _, ub, tb in ents]))
+            used = (used + len(ents)) % 64
+    return cwords, out
+
+
+def split_heavy_hibf(O, seed, k=4, narrow=False, h=2, n_values=6, part_values=2, rows=2048):
+    """An explicit HIBF whose layout-order chunks carry MANY parts of split user bins (reference include/index_hibf.h:114-147: a
+    layout with tmax = 256 splits large user bins that far).  Tree (technical bins; "X/n": user bin X split over n of them):
+      root R (256): A/200 (representative in the first chunk, parts over all four words), merged bins to C1, C2, C3 and to
+                    small one-word leaves (2, or 16 with `narrow`: enough that the row takes 8-byte chunks), single user bins;
+      C1 (256): B/129 -> a chunk of 128 entries; merged bin to G1 —  G1 (256): H/70 and I/65 with representatives in one chunk
+                (133 entries, I's from side bit 69 on), merged bin to K1 —  K1 (256): L/200 at depth 3 (kMaxVDepth ancestors);
+      C2 (256): D/66 (65 entries) and E/65 (64 entries) in two chunks; merged bin to G2 —  G2 (256): J/128 (127 entries);
+      C3 (192): F/3 and G/4 in two chunks that share a side word (G's chunk has bit0 = 2).
+    Every user bin that is not split holds `n_values` random k-mers, every part `part_values`.  Planted: a literal motif of k + 2
+    residues per split bin, its k-mers spread over LATE parts only — side entries >= 128 where the chunk has that many (A, I,
+    L), >= 64 for B, J and D, the last entry for E, F and G — and a control motif in H's parts below entry 64.  Rows are many
+    (`rows`), so that no early part answers a planted k-mer by a false positive.
+    Returns (oracle index, upload descriptors, values per user bin, planted: {motif: [user bins]})."""
+    rng = np.random.default_rng(seed)
+    n_leaves = 16 if narrow else 2
+    # IBF specs: (technical bins, [(split name, representative, parts)], children)
+    spec = {"R": (256, [("A", 5, 200)], ["C1", "C2", "C3"] + ["S%d" % j for j in range(n_leaves)]),
+            "C1": (256, [("B", 0, 129)], ["G1"]), "G1": (256, [("H", 0, 70), ("I", 1, 65)], ["K1"]), "K1": (256, [("L", 0, 200)], []),
+            "C2": (256, [("D", 0, 66), ("E", 128, 65)], ["G2"]), "G2": (256, [("J", 0, 128)], []),
+            "C3": (192, [("F", 0, 3), ("G", 128, 4)], [])}
+    spec.update({"S%d" % j: (40, [], []) for j in range(n_leaves)})
+    order = ["R", "C1", "C2", "C3"] + ["S%d" % j for j in range(n_leaves)] + ["G1", "G2", "K1"]  # (parents first; R is IBF 0)
+    ident = {name: i for i, name in enumerate(order)}
+    tbs = {}  # IBF -> per technical bin: ("M", child IBF name) or ("U", user-bin name)
+    n_single = 0
+    for name in order:
+        bins, splits, children = spec[name]
+        slot = [None] * bins
+        for sname, rep, n in sorted(splits, key=lambda s: -s[1]):  # (higher representatives first: their parts lie above them)
+            free = [tb for tb in range(rep + 1, bins) if slot[tb] is None]
+            slot[rep] = ("U", sname)
+            for tb in rng.choice(free, size=n - 1, replace=False):
+                slot[int(tb)] = ("U", sname)
+        free = [tb for tb in range(bins) if slot[tb] is None]
+        for child, tb in zip(children, rng.choice(free, size=len(children), replace=False)):
+            slot[int(tb)] = ("M", child)
+        for tb in range(bins):
+            if slot[tb] is None:
+                slot[tb] = ("U", "u%d" % n_single)
+                n_single += 1
+        tbs[name] = slot
+    names = sorted({t[1] for s in tbs.values() for t in s if t[0] == "U"})
+    user_of = {nm: int(u) for nm, u in zip(names, rng.permutation(len(names)))}
+    user_bins = len(names)
+    descs = [dict(bins=spec[nm][0], bin_size=rows, hash_funs=h, words=None,
+                  next_ibf_id=np.array([ident[t[1]] if t[0] == "M" else 0 for t in tbs[nm]], dtype=np.uint64),
+                  tb_to_user=np.array([MERGED if t[0] == "M" else user_of[t[1]] for t in tbs[nm]], dtype=np.uint64)) for nm in order]
+    # the planted k-mers, by the mirror's side entries
+    _, chunks = layout_split_chunks(descs)
+    entry_of = {}  # (IBF, technical bin) -> side entry
+    for ch in chunks:
+        for e, (_, tb) in enumerate(ch["entries"]):
+            entry_of[(ch["ibf"], tb)] = e
+    late = {"A": 128, "I": 128, "L": 128, "B": 64, "J": 64, "D": 64, "E": 63, "F": 1, "G": 2}
+    motifs = set()
+    while len(motifs) < len(late) + 1:
+        motifs.add("".join(rng.choice(list(AMINO), size=k + 2)))
+    motifs = sorted(motifs)
+    planted, plant_at = {}, {}  # motif -> user bins; (IBF, technical bin) -> k-mers
+    for (sname, lo), motif in zip(sorted(late.items()) + [("H", None)], motifs):
+        nm = next(n for n in order if any(s[0] == sname for s in spec[n][1]))
+        parts = [tb for tb, t in enumerate(tbs[nm]) if t == ("U", sname) and (ident[nm], tb) in entry_of]
+        at = [tb for tb in parts if (entry_of[(ident[nm], tb)] < 64 if lo is None else entry_of[(ident[nm], tb)] >= lo)]
+        assert at, sname
+        for j, v in enumerate(kmer_values(motif, k)):
+            plant_at.setdefault((ident[nm], at[j % len(at)]), []).append(v)
+        planted[motif] = [user_of[sname]]
+    taken = {v for m in motifs for v in kmer_values(m, k)}
+
+    def fresh(n):
+        v = rng.integers(0, 1 << (5 * k), size=n, dtype=np.uint64)
+        return v[[int(x) not in taken for x in v]]
+    content = {}  # (IBF, technical bin) -> values, merged bins: everything below them
+    for nm in reversed(order):
+        i = ident[nm]
+        for tb, t in enumerate(tbs[nm]):
+            if t[0] == "M":
+                c = ident[t[1]]
+                content[(i, tb)] = np.concatenate([content[(c, b)] for b in range(spec[t[1]][0])])
+            else:
+                split = sum(1 for x in tbs[nm] if x == t) > 1
+                content[(i, tb)] = np.concatenate([fresh(part_values if split else n_values),
+                                                   np.array(plant_at.get((i, tb), []), dtype=np.uint64)])
+    values = [[] for _ in range(user_bins)]
+    ox = O.Index.hibf(user_bins, dna=False, k=k)
+    for nm, d in zip(order, descs):
+        i = ox.add_ibf(d["bins"], d["bin_size"], d["hash_funs"], d["next_ibf_id"], d["tb_to_user"])
+        for tb in range(d["bins"]):
+            ox.hibf_emplace(i, content[(i, tb)], tb)
+            if int(d["tb_to_user"][tb]) != MERGED:
+                values[int(d["tb_to_user"][tb])].append(content[(i, tb)])
+    for i, d in enumerate(descs):
+        d["words"] = ox.hibf_words(i)
+    return ox, descs, [np.concatenate(v) for v in values], planted
+
+
 NO_KMER = 0xFFFFFFFF
 
 

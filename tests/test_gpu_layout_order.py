@@ -148,19 +148,23 @@ def test_a_motif_whose_kmers_lie_in_different_parts_of_a_split_user_bin(capi, or
         split |= {u for u in ubs if ubs.count(u) > 1}
     assert len([u for u in range(0, 900, 7) if u in split]) >= 10
     env = {"enumerated": {"TETREX_DENSE": "0"}, "level-kernels": {"TXQ_HIBF_LAYOUT_FUSED": "0"}, "tracked": {"TETREX_DENSE_TRACKED": "1"},
-           "untracked": {"TETREX_DENSE_TRACKED": "-1"}}.get(way, {})
+           "untracked": {"TETREX_DENSE_TRACKED": "0"}}.get(way, {})
     for k_, v_ in env.items():
         monkeypatch.setenv(k_, v_)
     qs = ["LMKAC", "LMKACD", "MKACD", "L.KAC", "LMKA[CD]D", "LM..CD", "L.{1,2}KACD", "((...){2,3})+", "(LMKA|A)C.?D"]
     if way == "two-shards":
         shards = [capi.Index.upload_hibf(900, descs, shard_rank=r, n_shards=2, subtrees=True) for r in range(2)]
-        got, status, _ = capi.query_masks_sharded(shards, qs, False, 4)
+        got, status, stats = capi.query_masks_sharded(shards, qs, False, 4)
         for ix in shards:
             ix.free()
     else:
         ix = capi.Index.upload_hibf(900, descs)
-        got, status, _ = ix.query_masks(qs, False, 4)
+        got, status, stats = ix.query_masks(qs, False, 4)
         ix.free()
+    if way == "tracked":
+        assert stats["tracked_queries"] > 0
+    if way == "untracked":  # (TETREX_DENSE_TRACKED=0: no query tracked — the way must not run the tracked path again)
+        assert stats["tracked_queries"] == 0
     planted = 0
     for q, g, st in zip(qs, got, status):
         want = ox.expected_mask(q)[0]

@@ -320,7 +320,7 @@ static int check_desc(const txq_index_desc* desc, int shard_rank, int n_shards, 
 }
 
 // the upload itself: the index goes to the device of `device_rank`; it keeps mask columns `range_rank` of `range_shards`
-static int upload_impl(const txq_index_desc* desc, bool hibf, int device_rank, int range_rank, int range_shards, txq_index** out) {
+static int upload_impl(const txq_index_desc* desc, bool hibf, int device_rank, int range_rank, int range_shards, txq_index** out, bool cleared_ok = false) {
     const int shard_rank = range_rank, n_shards = range_shards;
     txq_index* ix = new (std::nothrow) txq_index();
     if (!ix) return fail(TXQ_ERR_NOMEM, "out of host memory");
@@ -342,7 +342,7 @@ static int upload_impl(const txq_index_desc* desc, bool hibf, int device_rank, i
         rc = alloc_ibf(desc->ibf[0], lo, hi, &f, &bytes);
         if (rc == TXQ_OK) { ix->ibf.push_back(f); ix->device_bytes += bytes; }
     } else {
-        rc = hibf_upload(*ix, *desc);
+        rc = hibf_upload(*ix, *desc, cleared_ok);
     }
     if (rc != TXQ_OK) {
         ix->release();
@@ -435,7 +435,7 @@ int txq_index_upload_subtrees(const txq_index_desc* desc, int shard_rank, int n_
         load[best] += weight[b];
     }
     // this shard's tree: the root and its own sub-trees, renumbered in the original order; in its copy of the root the columns of
-    // everybody else's technical bins are cleared and those bins become plain technical bins that never fire
+    // everybody else's technical bins are cleared and those bins become kClearedBin: no user bin, never firing
     std::vector<uint64_t> new_id(n, UINT64_MAX), kept;
     for (uint64_t i = 0; i < n; ++i)
         if (i == 0 || shard_of_bin[owner_of_ibf[i]] == shard_rank) { new_id[i] = kept.size(); kept.push_back(i); }
@@ -458,14 +458,14 @@ int txq_index_upload_subtrees(const txq_index_desc* desc, int shard_rank, int n_
         user[j].assign(desc->ibf[i].bins, 0);
         for (uint64_t b = 0; b < desc->ibf[i].bins; ++b) {
             const uint64_t ub = desc->tb_to_user_bin[i][b];
-            if (i == 0 && shard_of_bin[b] != shard_rank) { user[j][b] = 0; continue; }  // (cleared column: user bin 0 is never reported through it)
+            if (i == 0 && shard_of_bin[b] != shard_rank) { user[j][b] = kClearedBin; continue; }  // (cleared column: no user bin, never reported)
             user[j][b] = ub;
             if (ub == TXQ_MERGED_BIN) next[j][b] = new_id[desc->next_ibf_id[i][b]];
         }
     }
     for (size_t j = 0; j < kept.size(); ++j) { next_p.push_back(next[j].data()); user_p.push_back(user[j].data()); }
     const txq_index_desc pruned{kept.size(), ibfs.data(), next_p.data(), user_p.data(), desc->user_bins};
-    if (int rc = upload_impl(&pruned, true, shard_rank, 0, 1, out)) return rc;
+    if (int rc = upload_impl(&pruned, true, shard_rank, 0, 1, out, true)) return rc;
     (*out)->join_or = true;
     (*out)->n_shards = n_shards;
     return TXQ_OK;

@@ -597,31 +597,55 @@ struct PathRows {
     // session's form — a split bin is its representative's bit.  A representative that is set in `mask` also stays when ANOTHER
     // part of its bin holds the k-mer: the k-mer's h rows of the IBF's side matrix, ANDed, are those parts' hits — one word per
     // row for the whole chunk, asked only when a representative is open; a hit names its representative through the chunk's
-    // entries (the other parts' own bits are zero in `mask`, so they vanish from y by themselves).
+    // entries (the other parts' own bits are zero in `mask`, so they vanish from y by themselves).  A chunk's entries are side
+    // bits [bit0, bit0 + count) from its first word on: one or two words for up to 128 of them (the common case, in registers),
+    // as many words as it takes beyond — one user bin split 200 ways gives its representative's chunk 199 entries.
+    static __device__ __forceinline__ uint64_t low_bits(uint32_t n) { return n >= 64u ? ~0ULL : (1ULL << n) - 1ULL; }
     __device__ __forceinline__ T pull_split(const Loads& l, T mask, T y) const {
         if (!sp_count || !l.hit) return y;
         const T open = mask & sp_reps & ~y;  // representatives that are asked for and that their own part does not answer
         if (!L::any(open)) return y;
         const uint32_t shift = (c_packed >> 20) & 63u, hf = (c_packed >> 26) & 7u;
-        const bool two = sp_bit0 + sp_count > 64u;  // (more parts than the first word has room for: they go on in the next)
-        uint64_t lo = ~0ULL, hi = two ? ~0ULL : 0ULL;
+        const uint32_t end = sp_bit0 + sp_count;  // (one past the chunk's last side bit, counted from its first word)
+        if (end <= 128u) {
+            const bool two = end > 64u;  // (more parts than the first word has room for: they go on in the next)
+            uint64_t lo = ~0ULL, hi = two ? ~0ULL : 0ULL;
 #pragma unroll
-        for (int i = 0; i < H; ++i)
-            if ((uint32_t)i < hf) {
-                const uint64_t* p = sp_side + (size_t)hash_row_seeded32(l.sv[i], shift, c_rows) * sp_stride;
-                lo &= p[0];
-                if (two) hi &= p[1];
+            for (int i = 0; i < H; ++i)
+                if ((uint32_t)i < hf) {
+                    const uint64_t* p = sp_side + (size_t)hash_row_seeded32(l.sv[i], shift, c_rows) * sp_stride;
+                    lo &= p[0];
+                    if (two) hi &= p[1];
+                }
+            const uint32_t in_lo = two ? 64u - sp_bit0 : sp_count;
+            lo = (lo >> sp_bit0) & low_bits(in_lo);
+            if (two) hi &= low_bits(sp_count - in_lo);  // (up to 64 there)
+            for (; lo; lo &= lo - 1) {
+                const uint32_t rep = splits[sp_first + (uint32_t)__builtin_ctzll(lo)].rep_bit;
+                if (L::test(open, rep)) y = L::with_bit(y, rep);
             }
-        const uint32_t in_lo = two ? 64u - sp_bit0 : sp_count;
-        lo = (lo >> sp_bit0) & (in_lo >= 64u ? ~0ULL : ((1ULL << in_lo) - 1ULL));
-        if (two) hi &= (1ULL << (sp_count - in_lo)) - 1ULL;  // (fewer than 64 there: a chunk has at most 127 parts)
-        for (; lo; lo &= lo - 1) {
-            const uint32_t rep = splits[sp_first + (uint32_t)__builtin_ctzll(lo)].rep_bit;
-            if (L::test(open, rep)) y = L::with_bit(y, rep);
+            for (; hi; hi &= hi - 1) {
+                const uint32_t rep = splits[sp_first + in_lo + (uint32_t)__builtin_ctzll(hi)].rep_bit;
+                if (L::test(open, rep)) y = L::with_bit(y, rep);
+            }
+            return y;
         }
-        for (; hi; hi &= hi - 1) {
-            const uint32_t rep = splits[sp_first + in_lo + (uint32_t)__builtin_ctzll(hi)].rep_bit;
-            if (L::test(open, rep)) y = L::with_bit(y, rep);
+        // more than two words: word by word, bit b of word w is entry w * 64 + b - bit0
+        const uint64_t* p[H];
+#pragma unroll
+        for (int i = 0; i < H; ++i) p[i] = sp_side + (size_t)hash_row_seeded32(l.sv[i], shift, c_rows) * sp_stride;
+        const uint32_t n_words = (end + 63u) >> 6;
+        for (uint32_t w = 0; w < n_words; ++w) {
+            uint64_t v = ~0ULL;
+#pragma unroll
+            for (int i = 0; i < H; ++i)
+                if ((uint32_t)i < hf) v &= p[i][w];
+            v &= low_bits(end - w * 64u);  // (the last word: only its first end % 64 bits are the chunk's)
+            if (!w) v &= ~low_bits(sp_bit0);
+            for (; v; v &= v - 1) {
+                const uint32_t rep = splits[sp_first + w * 64u + (uint32_t)__builtin_ctzll(v) - sp_bit0].rep_bit;
+                if (L::test(open, rep)) y = L::with_bit(y, rep);
+            }
         }
         return y;
     }

@@ -840,7 +840,7 @@ static int build_layout_order(Index& ix, const txq_index_desc& desc, const std::
                 chunks.push_back(r);
             }
             for (uint64_t b = 0; b < desc.ibf[i].bins; ++b)
-                if (tbu[off[i] + b] != TXQ_MERGED_BIN) {
+                if (tbu[off[i] + b] != TXQ_MERGED_BIN && tbu[off[i] + b] != kClearedBin) {  // (a cleared root bin is no user bin)
                     leaf[seg[i] + (b >> 6)] |= 1ULL << (b & 63);
                     vuser[(seg[i] + (b >> 6)) * 64 + (b & 63)] = (uint32_t)tbu[off[i] + b];
                 }
@@ -906,7 +906,7 @@ static int build_layout_order(Index& ix, const txq_index_desc& desc, const std::
         for (uint64_t i = 0; i < n; ++i) {
             bins_of.clear();
             for (uint64_t b = 0; b < desc.ibf[i].bins; ++b)
-                if (tbu[off[i] + b] != TXQ_MERGED_BIN) bins_of.emplace_back(tbu[off[i] + b], b);
+                if (tbu[off[i] + b] != TXQ_MERGED_BIN && tbu[off[i] + b] != kClearedBin) bins_of.emplace_back(tbu[off[i] + b], b);
             std::sort(bins_of.begin(), bins_of.end());
             for (size_t at = 0; at < bins_of.size();) {
                 size_t end = at + 1;
@@ -942,7 +942,9 @@ static int build_layout_order(Index& ix, const txq_index_desc& desc, const std::
                     ranges[c] = VSplitRange{(uint32_t)flat.size(), cnt, {0, 0, 0, 0}, 0, 0, 0};
                     if (!cnt) continue;
                     has = true;
-                    // a chunk's parts (at most 127) are consecutive side bits from bit0 of one word on, into the next word if need be
+                    // a chunk's parts are consecutive side bits from bit0 of one word on, into as many further words as they need (no
+                    // bound: one user bin split 200 ways gives its representative's chunk 199 parts); a chunk that does not fit after
+                    // `used` starts a fresh word, so only chunks of more than 64 parts span words, and those start at bit 0
                     if (used && used + cnt > 64) { ++word; used = 0; }
                     ranges[c].bit0 = used;
                     ranges[c].side = word;  // (the word for now; the pointer once the matrices have their place)
@@ -1164,7 +1166,7 @@ int hibf_layout_to_user(const Index& ix, const uint64_t* d_rows, size_t n, uint6
     return TXQ_OK;
 }
 
-int hibf_upload(Index& ix, const txq_index_desc& desc) {
+int hibf_upload(Index& ix, const txq_index_desc& desc, bool cleared_ok) {
     const uint64_t n = desc.n_ibf;
     if (n >> 31) return fail(TXQ_ERR_ARG, "too many IBFs");
     // validate the tree on the host before anything reaches the GPU
@@ -1191,8 +1193,8 @@ int hibf_upload(Index& ix, const txq_index_desc& desc) {
                 if ((size_t)level[nx] >= width.size()) width.push_back(0);
                 ++width[level[nx]];
                 q.push_back(nx);
-            } else {
-                if (ub >= desc.user_bins) return fail(TXQ_ERR_ARG, "IBF %llu bin %llu: user bin %llu out of range", (unsigned long long)i, (unsigned long long)b, (unsigned long long)ub);
+            } else {  // (a sub-tree shard's cleared root bins carry kClearedBin)
+                if (ub >= desc.user_bins && !(ub == kClearedBin && cleared_ok && i == 0)) return fail(TXQ_ERR_ARG, "IBF %llu bin %llu: user bin %llu out of range", (unsigned long long)i, (unsigned long long)b, (unsigned long long)ub);
                 nx = 0;
             }
             next[off[i] + b] = nx;
@@ -1253,6 +1255,7 @@ int hibf_upload(Index& ix, const txq_index_desc& desc) {
             const uint64_t i = order[at];
             for (uint64_t b = 0; b < desc.ibf[i].bins; ++b) {
                 const uint64_t ub = tbu[off[i] + b];
+                if (ub == kClearedBin) continue;
                 std::pair<uint64_t, uint64_t> r = ub == TXQ_MERGED_BIN ? span[next[off[i] + b]] : std::make_pair(ub >> 6, ub >> 6);
                 if (r.first < span[i].first) span[i].first = r.first;
                 if (r.first != UINT64_MAX && r.second > span[i].second) span[i].second = r.second;

@@ -114,7 +114,7 @@ struct VPath {           // the ancestors of an IBF, root first: whose merged bi
 // representative) is side bit `bit0 + e`.
 struct VSplit { uint32_t part_word; uint16_t rep_bit, part_bit; };  // word column and bit of the part in the IBF's row; its representative's bit in the chunk
 struct VSplitRange {
-    uint32_t first, count;   // the chunk's entries in Index::d_vsplits (fewer than the chunk has bits)
+    uint32_t first, count;   // the chunk's entries in Index::d_vsplits (any number: every part of a split bin whose representative is in the chunk)
     uint32_t reps[4];        // the chunk's bits that are representatives (bit b of the 128: reps[b >> 5] >> (b & 31))
     uint64_t side;           // device pointer: row 0 of the chunk's (first) word in the IBF's side matrix — entry e is bit bit0 + e from there
     uint32_t side_stride;    // words per side row
@@ -369,7 +369,10 @@ hipError_t launch_probe_interleaved(const IbfDev& interleaved, const HibfNode& r
 hipError_t launch_emplace(const IbfDev& f, const uint64_t* values, const uint32_t* bins_of, size_t n, hipStream_t s);
 
 // txq_hibf.hip
-int hibf_upload(Index& ix, const txq_index_desc& desc);
+// A technical bin of a sub-tree shard's root whose column was cleared because another shard owns it (txq_index_upload_subtrees):
+// internal only, accepted by hibf_upload with `cleared_ok`; it is no user bin and no merged bin, and it never fires.
+static constexpr uint64_t kClearedBin = 0xFFFFFFFFFFFFFFFEull;
+int hibf_upload(Index& ix, const txq_index_desc& desc, bool cleared_ok = false);
 int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, uint64_t* d_masks, uint64_t* d_alive, hipStream_t s);
 // layout-order rows of n k-mers: d_rows[n][v_words]
 int hibf_probe_layout_order(Index& ix, const uint64_t* d_kmers, size_t n, uint64_t* d_rows, hipStream_t s);

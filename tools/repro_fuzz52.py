@@ -41,7 +41,7 @@ i = qs.index("((...){2,3})+")
 batch = qs[i - i % 7: i - i % 7 + 7]
 print("batch:", batch)
 for label, env in [("defaults", {}), ("alone", {"ALONE": "1"}), ("TETREX_DENSE=0", {"TETREX_DENSE": "0"}), ("user order", {"TXQ_HIBF_LAYOUT_ORDER": "0"}),
-                   ("untracked", {"TETREX_DENSE_TRACKED": "-1"}), ("tracked", {"TETREX_DENSE_TRACKED": "1"}), ("table", {"TXQ_KMER_TABLE_MIN": "1"}),
+                   ("untracked", {"TETREX_DENSE_TRACKED": "0"}), ("tracked", {"TETREX_DENSE_TRACKED": "1"}), ("table", {"TXQ_KMER_TABLE_MIN": "1"}),
                    ("one stream", {"TXQ_ONE_STREAM": "1"}), ("no fused rows", {"TXQ_HIBF_LAYOUT_FUSED": "0"}), ("threads 1", {"TETREX_THREADS": "1"}),
                    ("one wave", {"TETREX_WAVE_OPS": "0"}), ("final via device", {"TXQ_FINAL_PINNED": "0"})]:
     e = dict(os.environ, **env)
