@@ -144,6 +144,43 @@ int64_t txh_index_maps(const txh_index* ix, uint64_t ibf_id, uint64_t* next_ibf_
 const void* txh_index_serialise(txh_index* ix, size_t* bytes);
 void txh_index_free(txh_index* ix);
 
+/* ---- size-aware HIBF layout (host/layout.hpp; `tetrex index --layout sized`) ----
+ * A pure function: counts[user_bins] = each user bin's k-mer count estimate (by user bin id); unions[user_bins x window] =
+ * union estimates over runs of the bins in layout order (estimate descending, ties by id): unions[s * window + L - 1] for
+ * the bins at sorted positions s .. s+L-1, window = min(B, 4 * ceil(B / t_max)).  params NULL: the defaults below. */
+typedef struct {
+    uint64_t tmax;       /* technical bins per IBF at most, a multiple of 64; 0: 64 * ceil(ceil(sqrt(B)) / 64) */
+    float fpr;           /* of the user bins (0.05) */
+    float relaxed_fpr;   /* of merged bins (0.3) */
+    unsigned hash_count; /* 3 */
+    double alpha;        /* weight of lower levels' bits (1.2) */
+} txh_layout_params;
+typedef struct txh_layout txh_layout;
+int txh_hibf_layout(const double* counts, uint64_t user_bins, const double* unions, uint64_t window, const txh_layout_params* params,
+                    txh_layout** out);
+int64_t txh_layout_ibf_count(const txh_layout* l);
+/* IBF `ibf` of the layout (0 = root, then depth-first pre-order): its bin_size and maps (as txh_index_maps); returns its
+ * technical bins (nothing written past cap) */
+int64_t txh_layout_ibf(const txh_layout* l, uint64_t ibf, uint64_t* bin_size, uint64_t* next_ibf_id, uint64_t* tb_to_user, size_t cap);
+/* the layout order (user bin at each sorted position); returns B */
+int64_t txh_layout_order(const txh_layout* l, uint64_t* order, size_t cap);
+void txh_layout_free(txh_layout* l);
+
+/* The whole `tetrex index` build (FASTA files -> index image, bits set on the GPU), without the CLI.  Exported by
+ * libtetrex_query.so (it needs libtxq.so); errors via txe_last_error().  The handle is an ordinary txh_index
+ * (txh_index_describe / _words / _maps / _serialise / _free of libtetrex_host.so).  options NULL: the CLI's defaults. */
+typedef struct {
+    unsigned k;          /* 6 */
+    int dna;             /* -n */
+    unsigned reduction;  /* 0 none, 1 murphy, 2 li (-r) */
+    unsigned hash_count; /* 3 (-c) */
+    float fpr;           /* 0.05 (-p) */
+    int flavour;         /* 0 HIBF, uniform layout (default); 1 HIBF, sized layout (--layout sized); 2 flat IBF (-i) */
+    uint64_t tmax;       /* --tmax (sized only; 0: the default) */
+    int device;          /* -D */
+} txh_build_options;
+int txh_index_build(const char* const* paths, size_t n, const txh_build_options* options, txh_index** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,37 @@ int txq_probe_device(txq_index* ix, const uint64_t* d_kmers, size_t n, uint64_t*
  * shard's columns are skipped). */
 int txq_emplace_device(txq_index* ix, const uint64_t* d_values, const uint32_t* d_bins_of, size_t n, void* stream);
 
+/* Index construction of a size-aware HIBF (`tetrex index --layout sized`, tetrex_amd/csrc/host/layout.hpp).  The input is
+ * the k-mer values of every user bin as one CSR array on the device: bin b holds d_values[d_offsets[b] .. d_offsets[b+1]),
+ * offsets ascending, n_bins + 1 of them; n_values bounds every index.  A library too large for the device is streamed as
+ * chunks (each chunk with offsets of its own over all n_bins bins): both the sketch and the insertion combine with what
+ * earlier chunks left (max / OR), so the result does not depend on the chunking.
+ *
+ * HyperLogLog sketches, TXQ_HLL_REGISTERS u8 registers per bin (d_registers: n_bins x 4096, zeroed by the caller before
+ * the first chunk).  With x the splitmix64 finaliser of a value
+ *     x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31
+ * the value sets register x >> 52 to at least min(clz(x << 12), 52) + 1.  The result is the same whatever the scheduling. */
+#define TXQ_HLL_BITS 12
+#define TXQ_HLL_REGISTERS 4096
+int txq_sketch_device(const uint64_t* d_values, size_t n_values, const uint64_t* d_offsets, uint64_t n_bins, uint8_t* d_registers,
+                      void* stream);
+/* Union estimates over runs of the bins in the order d_order (n_bins bin ids): d_estimates[s * window + L - 1] = the
+ * estimate of the union of bins d_order[s .. s+L-1] for L = 1 .. window (0.0 where s + L > n_bins).  The estimate of
+ * registers M[0..m), m = 4096: E = alpha_m * m^2 / Z, alpha_m = 0.7213 / (1 + 1.079 / m), Z = sum 2^-M[r] (computed as the
+ * exact integer sum of 2^(53 - M[r]), rounded once to a double and scaled by 2^-53); where E <= 2.5 m and V > 0 registers
+ * are zero, linear counting m * ln(m / V) replaces it (ln of the host's libm).  window = 1 with the identity order gives
+ * each bin's own estimate. */
+int txq_union_estimates_device(const uint8_t* d_registers, const uint32_t* d_order, uint64_t n_bins, uint64_t window,
+                               double* d_estimates, void* stream);
+/* Insertion into every IBF of a tree.  d_ibfs[n_ibf]: the IBFs' shapes, each .words a DEVICE pointer to its zeroed
+ * [bin_size][bin_words] matrix.  User bin b's path from the root is d_path[3 * e .. 3 * e + 2] = (ibf, first technical bin,
+ * parts) for e in [d_path_offsets[b], d_path_offsets[b+1]); only the leaf entry may have parts > 1.  Each value sets, in each
+ * IBF on its bin's path, the hash_funs bits of technical bin first + (parts > 1 ? mulhi64(fmix(v ^ 0x9e3779b97f4a7c15), parts)
+ * : 0) (fmix: the finaliser above), so a value always lands in the same part.  Entries outside an IBF's bins are skipped. */
+int txq_tree_insert_device(const uint64_t* d_values, size_t n_values, const uint64_t* d_offsets, uint64_t n_bins,
+                           const uint64_t* d_path_offsets, const uint64_t* d_path, const txq_ibf_desc* d_ibfs, uint64_t n_ibf,
+                           void* stream);
+
 /* Mask-DAG programs (format: include/txq_program.h).  Runs n_programs programs found in
  * `blob`; final_masks receives n_programs x shard_words words (host buffer, synchronous). */
 int txq_run_programs(txq_index* ix, const void* blob, size_t blob_bytes, size_t n_programs, uint64_t* final_masks);

@@ -1,0 +1,132 @@
+"""numpy restatements for the size-aware HIBF layout (include/txq.h txq_sketch_device / txq_union_estimates_device /
+txq_tree_insert_device, tetrex_amd/csrc/host/layout.hpp): the hash, the HyperLogLog registers and estimator, the part rule
+of split bins, and checks of a layout's structure."""
+import math
+
+import numpy as np
+
+M = 4096
+ALPHA_MM = 0.7213 / (1.0 + 1.079 / M) * M * M
+MERGED = 0xFFFFFFFFFFFFFFFF
+_U = np.uint64
+
+
+def fmix(x):
+    """splitmix64's finaliser."""
+    x = np.array(x, dtype=np.uint64, copy=True)
+    with np.errstate(over="ignore"):
+        x ^= x >> _U(30)
+        x *= _U(0xbf58476d1ce4e5b9)
+        x ^= x >> _U(27)
+        x *= _U(0x94d049bb133111eb)
+        x ^= x >> _U(31)
+    return x
+
+
+def _clz64(w):
+    w = np.array(w, dtype=np.uint64, copy=True)
+    zero = w == 0
+    n = np.zeros(w.shape, dtype=np.uint64)
+    for s in (32, 16, 8, 4, 2, 1):
+        m = (w >> _U(64 - s)) == 0
+        n[m] += _U(s)
+        w[m] <<= _U(s)
+    n[zero] = 64
+    return n
+
+
+def registers(values):
+    """4096 u8 registers of one bin: register x >> 52 of x = fmix(v) holds the max of min(clz(x << 12), 52) + 1."""
+    regs = np.zeros(M, dtype=np.uint8)
+    v = np.asarray(values, dtype=np.uint64)
+    if v.size:
+        x = fmix(v)
+        rank = np.minimum(_clz64(x << _U(12)), _U(52)) + _U(1)
+        np.maximum.at(regs, (x >> _U(52)).astype(np.int64), rank.astype(np.uint8))
+    return regs
+
+
+def estimate(regs):
+    """alpha_m m^2 / sum 2^-M (the sum exact, rounded once), linear counting m ln(m / V) where E <= 2.5 m and V > 0."""
+    r = np.minimum(np.asarray(regs, dtype=np.int64), 53)
+    counts = np.bincount(r, minlength=54)
+    total = sum(int(c) << (53 - i) for i, c in enumerate(counts) if c)
+    e = ALPHA_MM / (float(total) * 2.0 ** -53)
+    zeros = int(counts[0])
+    if e <= 2.5 * M and zeros > 0:
+        e = float(M) * math.log(float(M) / float(zeros))
+    return e
+
+
+def union_table(regs, order, window):
+    """[s, L-1] = estimate of the union of bins order[s .. s+L-1]; 0.0 past the end."""
+    B = regs.shape[0]
+    out = np.zeros((B, window), dtype=np.float64)
+    for s in range(B):
+        acc = np.zeros(M, dtype=np.uint8)
+        for L in range(1, window + 1):
+            if s + L > B:
+                break
+            acc = np.maximum(acc, regs[int(order[s + L - 1])])
+            out[s, L - 1] = estimate(acc)
+    return out
+
+
+def part_of(values, parts):
+    """The part of a split bin that holds each value: mulhi64(fmix(v ^ 0x9e3779b97f4a7c15), parts)."""
+    x = fmix(np.asarray(values, dtype=np.uint64) ^ _U(0x9e3779b97f4a7c15))
+    hi, lo = x >> _U(32), x & _U(0xFFFFFFFF)
+    p = _U(parts)
+    # (hi * 2^32 + lo) * p >> 64 with p < 2^32: hi * p + (lo * p >> 32), then >> 32
+    return (hi * p + ((lo * p) >> _U(32))) >> _U(32)
+
+
+def paths(ibfs):
+    """Each user bin's path from the root: [(ibf, first technical bin, parts)], from the maps alone.  Asserts that every
+    user bin is exactly one run of technical bins in exactly one IBF and every IBF but the root has exactly one parent."""
+    out = {}
+    parent = {}
+
+    def walk(i, stack):
+        tbu, nxt = ibfs[i]["tb_to_user_bin"], ibfs[i]["next_ibf_id"]
+        t, T = 0, len(tbu)
+        while t < T:
+            if int(tbu[t]) == MERGED:
+                c = int(nxt[t])
+                assert 0 < c < len(ibfs) and c not in parent, (i, t, c)
+                parent[c] = (i, t)
+                walk(c, stack + [(i, t, 1)])
+                t += 1
+                continue
+            ub = int(tbu[t])
+            e = t
+            while e < T and int(tbu[e]) == ub:
+                e += 1
+            assert ub not in out, "user bin %d placed twice" % ub
+            out[ub] = stack + [(i, t, e - t)]
+            t = e
+
+    walk(0, [])
+    assert len(parent) == len(ibfs) - 1
+    return out
+
+
+def total_bits(ibfs):
+    return sum(64 * ((f["bins"] + 63) // 64) * f["bin_size"] for f in ibfs)
+
+
+def uniform_bits(counts, fpr=0.05):
+    """Bits of the uniform two-level tree `tetrex index` writes by default (device_index.cpp build_index) for bins of
+    these sizes: a child of 64 * ceil(ceil(B / t_max) / 64) user bins each, every child with the rows of the largest
+    bin, the root sized by its largest merged bin."""
+    def bitcount(n):
+        return int(math.ceil(-n * math.log(np.float32(fpr)) / math.log(2) ** 2))
+    B = len(counts)
+    tmax = 64 * ((int(math.ceil(math.sqrt(B))) + 63) // 64)
+    if B <= tmax:
+        return 64 * ((B + 63) // 64) * max(1, bitcount(max(counts)))
+    per_child = 64 * (((B + tmax - 1) // tmax + 63) // 64)
+    n_child = (B + per_child - 1) // per_child
+    child_rows = max(1, bitcount(max(counts)))
+    merged = [sum(counts[c * per_child:(c + 1) * per_child]) for c in range(n_child)]
+    return n_child * per_child * child_rows + 64 * ((n_child + 63) // 64) * max(1, bitcount(max(merged)))

@@ -22,6 +22,7 @@ SYMBOLS = [
     "txq_init", "txq_shutdown", "txq_last_error", "txq_device_count",
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device",
+    "txq_sketch_device", "txq_union_estimates_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
     "txq_malloc", "txq_free", "txq_memcpy_h2d", "txq_memcpy_d2h", "txq_synchronize", "txq_host_alloc", "txq_host_free",
 ]
@@ -444,3 +445,48 @@ class Session:
                 self._h = None
         except Exception:
             pass
+
+
+HLL_REGISTERS = 4096
+
+
+def _csr(values_per_bin):
+    offsets = np.zeros(len(values_per_bin) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(v) for v in values_per_bin])
+    flat = np.concatenate([np.asarray(v, dtype=np.uint64) for v in values_per_bin]) if len(values_per_bin) else np.zeros(0, np.uint64)
+    return flat, offsets
+
+
+def sketch(values_per_bin):
+    """HyperLogLog registers of every bin (txq_sketch_device): uint8 array (B, 4096)."""
+    L = lib()
+    L.txq_sketch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    flat, offsets = _csr(values_per_bin)
+    B = len(values_per_bin)
+    dv, do = DeviceBuffer.from_numpy(flat if flat.size else np.zeros(1, np.uint64)), DeviceBuffer.from_numpy(offsets)
+    dr = DeviceBuffer.from_numpy(np.zeros(B * HLL_REGISTERS, dtype=np.uint8))
+    try:
+        check(L.txq_sketch_device(dv.ptr, flat.size, do.ptr, B, dr.ptr, None))
+        check(L.txq_synchronize())
+        return dr.to_numpy(np.uint8, (B, HLL_REGISTERS))
+    finally:
+        for b in (dv, do, dr):
+            b.free()
+
+
+def union_estimates(registers, order, window):
+    """d_estimates[s, L-1] = estimate of the union of bins order[s .. s+L-1] (txq_union_estimates_device): (B, window)."""
+    L = lib()
+    L.txq_union_estimates_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    regs = np.ascontiguousarray(registers, dtype=np.uint8)
+    B = regs.shape[0]
+    dr, do = DeviceBuffer.from_numpy(regs), DeviceBuffer.from_numpy(np.asarray(order, dtype=np.uint32))
+    de = DeviceBuffer(B * window * 8)
+    try:
+        check(L.txq_union_estimates_device(dr.ptr, do.ptr, B, window, de.ptr, None))
+        check(L.txq_synchronize())
+        return de.to_numpy(np.float64, (B, window))
+    finally:
+        for b in (dr, do, de):
+            b.free()
+

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <future>
+#include <memory>
 #include <stdexcept>
 
 namespace tetrex {
@@ -305,12 +306,6 @@ std::vector<uint64_t> set_bins(const uint64_t* mask, uint64_t bins) {
     return out;
 }
 
-uint64_t compute_bitcount(uint64_t n, float fpr) {
-    const double num = -static_cast<double>(n) * std::log(fpr);  // float log, as in the reference
-    const double den = std::pow(std::log(2), 2);
-    return static_cast<uint64_t>(std::ceil(num / den));
-}
-
 namespace {
 
 struct DevBuf {
@@ -352,6 +347,124 @@ IbfImage build_flat(const std::vector<const std::vector<uint64_t>*>& per_bin, ui
     return img;
 }
 
+// The size-aware tree (`--layout sized`, host/layout.hpp) built on the device: the k-mer values of all bins go up as one CSR
+// array (streamed in chunks of at most kBuildChunk values when the library is larger), are sketched, the union table
+// is estimated for the layout DP, and one pass inserts every value into each IBF on its user bin's path.
+constexpr uint64_t kBuildChunk = uint64_t(1) << 27;  // values per chunk (1 GiB)
+
+HibfImage build_sized_hibf(const std::vector<std::vector<uint64_t>>& values, const BuildOptions& opt) {
+    using clock = std::chrono::steady_clock;
+    const bool trace = std::getenv("TETREX_TRACE") != nullptr;
+    auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const uint64_t B = values.size();
+    std::vector<uint64_t> offsets(B + 1, 0);
+    for (uint64_t b = 0; b < B; ++b) offsets[b + 1] = offsets[b] + values[b].size();
+    const uint64_t total = offsets[B];
+    const uint64_t chunk = std::max<uint64_t>(1, std::min(total, kBuildChunk));
+    const uint64_t n_chunks = std::max<uint64_t>(1, (total + chunk - 1) / chunk);
+    DevBuf d_vals(chunk * 8), d_offs((B + 1) * 8);
+    std::vector<uint64_t> chunk_offs(B + 1);
+    // chunk c = values [c * chunk, ...) of the concatenation; every bin's slice of it is copied from the bin's own vector
+    auto upload_chunk = [&](uint64_t c) -> uint64_t {
+        const uint64_t g0 = c * chunk, g1 = std::min(total, g0 + chunk);
+        for (uint64_t b = 0; b <= B; ++b) chunk_offs[b] = std::min(std::max(offsets[b], g0), g1) - g0;
+        for (uint64_t b = 0; b < B; ++b) {
+            const uint64_t lo = chunk_offs[b], hi = chunk_offs[b + 1];
+            if (hi > lo)
+                txq_check(txq_memcpy_h2d((uint64_t*)d_vals.p + lo, values[b].data() + (g0 + lo - offsets[b]), (hi - lo) * 8), "h2d values");
+        }
+        txq_check(txq_memcpy_h2d(d_offs.p, chunk_offs.data(), (B + 1) * 8), "h2d offsets");
+        return g1 - g0;
+    };
+    const auto t0 = clock::now();
+    // sketches
+    DevBuf d_regs(B * TXQ_HLL_REGISTERS);
+    {
+        const std::vector<uint8_t> zero(B * TXQ_HLL_REGISTERS, 0);
+        txq_check(txq_memcpy_h2d(d_regs.p, zero.data(), zero.size()), "h2d registers");
+    }
+    uint64_t resident = UINT64_MAX;  // the chunk now on the device
+    for (uint64_t c = 0; c < n_chunks; ++c) {
+        const uint64_t n = upload_chunk(c);
+        resident = c;
+        txq_check(txq_sketch_device((const uint64_t*)d_vals.p, n, (const uint64_t*)d_offs.p, B, (uint8_t*)d_regs.p, nullptr), "txq_sketch_device");
+    }
+    txq_check(txq_synchronize(), "sketch");
+    const auto t1 = clock::now();
+    // each bin's estimate (identity order, window 1), the layout order, the union table
+    LayoutParams lp;
+    lp.tmax = opt.tmax ? opt.tmax : default_tmax(B);
+    lp.fpr = opt.fpr;
+    lp.hash_count = opt.hash_count;
+    const uint64_t W = union_window(B, lp.tmax);
+    std::vector<double> counts(B), unions(B * W);
+    {
+        std::vector<uint32_t> order(B);
+        for (uint64_t b = 0; b < B; ++b) order[b] = (uint32_t)b;
+        DevBuf d_order(B * 4), d_est(B * W * 8);
+        txq_check(txq_memcpy_h2d(d_order.p, order.data(), B * 4), "h2d order");
+        txq_check(txq_union_estimates_device((const uint8_t*)d_regs.p, (const uint32_t*)d_order.p, B, 1, (double*)d_est.p, nullptr), "txq_union_estimates_device");
+        txq_check(txq_memcpy_d2h(counts.data(), d_est.p, B * 8), "d2h estimates");
+        const std::vector<uint64_t> sorted = layout_order(counts.data(), B);
+        for (uint64_t s = 0; s < B; ++s) order[s] = (uint32_t)sorted[s];
+        txq_check(txq_memcpy_h2d(d_order.p, order.data(), B * 4), "h2d order");
+        txq_check(txq_union_estimates_device((const uint8_t*)d_regs.p, (const uint32_t*)d_order.p, B, W, (double*)d_est.p, nullptr), "txq_union_estimates_device");
+        txq_check(txq_memcpy_d2h(unions.data(), d_est.p, B * W * 8), "d2h unions");
+    }
+    const auto t2 = clock::now();
+    const HibfLayout layout = hibf_layout(counts.data(), B, unions.data(), W, lp);
+    const auto paths = layout_paths(layout, B);
+    const auto t3 = clock::now();
+    // the tree on the device
+    HibfImage h;
+    h.user_bins = B;
+    const uint64_t n_ibf = layout.ibfs.size();
+    h.ibfs.resize(n_ibf);
+    std::vector<std::unique_ptr<DevBuf>> d_words;
+    std::vector<txq_ibf_desc> descs(n_ibf);
+    for (uint64_t i = 0; i < n_ibf; ++i) {
+        const LayoutIbf& f = layout.ibfs[i];
+        IbfImage& img = h.ibfs[i];
+        img.shape(f.tb_to_user_bin.size(), f.bin_size, opt.hash_count);
+        h.next_ibf_id.push_back(f.next_ibf_id);
+        h.tb_to_user_bin.push_back(f.tb_to_user_bin);
+        d_words.push_back(std::make_unique<DevBuf>(img.words.size() * 8));
+        txq_check(txq_memcpy_h2d(d_words.back()->p, img.words.data(), img.words.size() * 8), "h2d zero words");
+        descs[i] = txq_ibf_desc{img.bins, img.tech_bins, img.bin_size, img.hash_shift, img.bin_words, img.hash_funs, (const uint64_t*)d_words.back()->p};
+    }
+    std::vector<uint64_t> path_offsets(B + 1, 0), path;
+    for (uint64_t b = 0; b < B; ++b) {
+        for (const PathStep& st : paths[b]) { path.push_back(st.ibf); path.push_back(st.tb); path.push_back(st.parts); }
+        path_offsets[b + 1] = path.size() / 3;
+    }
+    DevBuf d_descs(n_ibf * sizeof(txq_ibf_desc)), d_poff((B + 1) * 8), d_path(path.size() * 8);
+    txq_check(txq_memcpy_h2d(d_descs.p, descs.data(), n_ibf * sizeof(txq_ibf_desc)), "h2d descriptors");
+    txq_check(txq_memcpy_h2d(d_poff.p, path_offsets.data(), (B + 1) * 8), "h2d path offsets");
+    txq_check(txq_memcpy_h2d(d_path.p, path.data(), path.size() * 8), "h2d paths");
+    for (uint64_t c = 0; c < n_chunks; ++c) {
+        // the last chunk the sketch pass uploaded is still resident (values and offsets)
+        const uint64_t n = resident == c ? std::min(total - c * chunk, chunk) : upload_chunk(c);
+        resident = c;
+        txq_check(txq_tree_insert_device((const uint64_t*)d_vals.p, n, (const uint64_t*)d_offs.p, B, (const uint64_t*)d_poff.p,
+                                         (const uint64_t*)d_path.p, (const txq_ibf_desc*)d_descs.p, n_ibf, nullptr), "txq_tree_insert_device");
+    }
+    txq_check(txq_synchronize(), "tree insert");
+    const auto t4 = clock::now();
+    for (uint64_t i = 0; i < n_ibf; ++i)
+        txq_check(txq_memcpy_d2h(h.ibfs[i].words.data(), d_words[i]->p, h.ibfs[i].words.size() * 8), "d2h words");
+    const auto t5 = clock::now();
+    if (trace) {
+        uint64_t bits = 0;
+        for (const IbfImage& f : h.ibfs) bits += f.tech_bins * f.bin_size;
+        std::fprintf(stderr, "[tetrex] sized layout: %llu user bins, %llu IBFs, %llu bits, t_max %llu, window %llu, %llu values in %llu chunk(s)\n",
+                     (unsigned long long)B, (unsigned long long)n_ibf, (unsigned long long)bits, (unsigned long long)lp.tmax,
+                     (unsigned long long)W, (unsigned long long)total, (unsigned long long)n_chunks);
+        std::fprintf(stderr, "[tetrex] build ms: upload+sketch %.3f union %.3f layout %.3f insert %.3f download %.3f\n", ms(t0, t1),
+                     ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, t5));
+    }
+    return h;
+}
+
 }  // namespace
 
 IndexImage build_index(const std::vector<std::string>& bin_files, const BuildOptions& opt, size_t* n_sequences) {
@@ -359,6 +472,9 @@ IndexImage build_index(const std::vector<std::string>& bin_files, const BuildOpt
     if (!opt.dna && opt.k > 12) throw std::runtime_error("Max kmer size for amino acids is 12");
     if (opt.dna && opt.k > 32) throw std::runtime_error("Max kmer size for nucleic acids is 32");
     ensure_device(opt.device);
+    if (opt.layout == BuildOptions::kSized && !opt.hibf) throw std::runtime_error("a sized layout is an HIBF layout (not with -i)");
+    if (opt.layout == BuildOptions::kSized && (opt.tmax % 64 != 0)) throw std::runtime_error("t_max must be a positive multiple of 64");
+    const auto t_encode = std::chrono::steady_clock::now();
     const KmerEncoder enc(opt.dna ? Molecule::DNA : Molecule::Peptide, opt.k, (Alphabet)opt.reduction);
     std::vector<std::vector<uint64_t>> values(bin_files.size());
     size_t seqs = 0;
@@ -369,6 +485,9 @@ IndexImage build_index(const std::vector<std::string>& bin_files, const BuildOpt
             enc.record_values(r.seq, opt.dna_wraparound, values[b]);
         });
     if (n_sequences) *n_sequences = seqs;
+    if (std::getenv("TETREX_TRACE"))
+        std::fprintf(stderr, "[tetrex] build ms: encode %.3f\n",
+                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_encode).count());
 
     IndexImage img;
     img.k = (uint8_t)opt.k;
@@ -399,6 +518,11 @@ IndexImage build_index(const std::vector<std::string>& bin_files, const BuildOpt
     // have the rows of the largest user bin (as the flat IBF sizes its bins): the device keeps such a tree's children
     // side by side and probes them like one flat IBF (csrc/txq_hibf.hip: regular trees, uniform children).
     img.is_hibf = true;
+    if (opt.layout == BuildOptions::kSized) {
+        img.hibf = build_sized_hibf(values, opt);
+        img.format = "hibf";
+        return img;
+    }
     HibfImage& h = img.hibf;
     const uint64_t B = bin_files.size();
     h.user_bins = B;

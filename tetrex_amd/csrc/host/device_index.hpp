@@ -6,6 +6,7 @@
 #include "compiler.hpp"
 #include "encoder.hpp"
 #include "index_file.hpp"
+#include "layout.hpp"
 #include "../../../include/txq.h"
 
 #include <string>
@@ -108,9 +109,6 @@ class DeviceIndex {
 // ascending ids of the set bits (compute_set_bins, reference src/query.cpp:40-75)
 std::vector<uint64_t> set_bins(const uint64_t* mask, uint64_t bins);
 
-// IBFIndex::compute_bitcount (reference include/index_ibf.h:133-139)
-uint64_t compute_bitcount(uint64_t n, float fpr);
-
 struct BuildOptions {
     unsigned k = 6;
     float fpr = 0.05f;
@@ -120,6 +118,11 @@ struct BuildOptions {
     unsigned reduction = 0; // 0 None, 1 murphy, 2 li
     bool dna_wraparound = true;  // reproduce include/nucleotide_decomposer.h:106-110
     int device = 0;
+    // HIBF layout: kUniform, this project's two-level tree (the default); kSized, host/layout.hpp with t_max = tmax
+    // (0: default_tmax(B)), built by the kernels of txq_build.hip
+    enum Layout { kUniform = 0, kSized = 1 };
+    int layout = kUniform;
+    uint64_t tmax = 0;
 };
 // `tetrex index`: FASTA files -> index image, bits set on the GPU (txq_emplace_device).
 IndexImage build_index(const std::vector<std::string>& bin_files, const BuildOptions& opt, size_t* n_sequences = nullptr);

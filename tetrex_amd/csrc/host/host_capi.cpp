@@ -4,6 +4,7 @@
 #include "encoder.hpp"
 #include "index_file.hpp"
 #include "kgraph.hpp"
+#include "layout.hpp"
 #include "matcher.hpp"
 #include "regex_front.hpp"
 
@@ -31,9 +32,8 @@ struct txh_blob {
     std::vector<uint64_t> stats;
 };
 
-struct txh_index {
-    IndexImage image;
-    std::vector<uint8_t> file;
+struct txh_layout {
+    HibfLayout layout;
 };
 
 extern "C" {
@@ -353,5 +353,46 @@ const void* txh_index_serialise(txh_index* ix, size_t* bytes) {
 }
 
 void txh_index_free(txh_index* ix) { delete ix; }
+
+int txh_hibf_layout(const double* counts, uint64_t user_bins, const double* unions, uint64_t window, const txh_layout_params* params,
+                    txh_layout** out) {
+    try {
+        if (!out) return fail("null argument");
+        LayoutParams p;
+        if (params) {
+            p.tmax = params->tmax;
+            p.fpr = params->fpr;
+            p.relaxed_fpr = params->relaxed_fpr;
+            p.hash_count = params->hash_count;
+            p.alpha = params->alpha;
+        }
+        auto l = std::make_unique<txh_layout>();
+        l->layout = hibf_layout(counts, user_bins, unions, window, p);
+        *out = l.release();
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+
+int64_t txh_layout_ibf_count(const txh_layout* l) { return l ? (int64_t)l->layout.ibfs.size() : fail("null argument"); }
+
+int64_t txh_layout_ibf(const txh_layout* l, uint64_t ibf, uint64_t* bin_size, uint64_t* next_ibf_id, uint64_t* tb_to_user, size_t cap) {
+    if (!l || ibf >= l->layout.ibfs.size()) return fail("no such IBF");
+    const LayoutIbf& f = l->layout.ibfs[ibf];
+    const size_t n = f.tb_to_user_bin.size();
+    if (bin_size) *bin_size = f.bin_size;
+    for (size_t t = 0; t < n && t < cap; ++t) {
+        if (next_ibf_id) next_ibf_id[t] = f.next_ibf_id[t];
+        if (tb_to_user) tb_to_user[t] = f.tb_to_user_bin[t];
+    }
+    return (int64_t)n;
+}
+
+int64_t txh_layout_order(const txh_layout* l, uint64_t* order, size_t cap) {
+    if (!l) return fail("null argument");
+    for (size_t s = 0; s < l->layout.order.size() && s < cap; ++s) order[s] = l->layout.order[s];
+    return (int64_t)l->layout.order.size();
+}
+
+void txh_layout_free(txh_layout* l) { delete l; }
 
 }  // extern "C"

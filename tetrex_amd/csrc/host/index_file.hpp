@@ -89,3 +89,9 @@ void write_index_file(const std::string& path, const IndexImage& ix);
 void peek_index_params(const std::vector<uint8_t>& bytes, uint8_t& k, std::string& molecule, bool& is_hibf);
 
 }  // namespace tetrex
+
+// the handle behind include/txh.h's txh_index (host_capi.cpp; txh_index_build of query_capi.cpp makes one too)
+struct txh_index {
+    tetrex::IndexImage image;
+    std::vector<uint8_t> file;
+};

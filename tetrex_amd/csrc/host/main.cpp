@@ -1,7 +1,7 @@
 // `tetrex` command line — product code.  Keeps the reference's surface for the query path:
 //   tetrex query [-d] [-v] [-f] [-c] [-a] [-t N] [-o dest] [-g dibf] <index.ibf> <regex|->
 //     (include/arg_parse.h:57-71, src/main.cpp:36-59, src/query.cpp:477-498)
-//   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] <name> <libs...>
+//   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] [--layout uniform|sized [--tmax N]] <name> <libs...>
 //     (include/arg_parse.h:10-38, src/index_base.cpp:73-117)
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
@@ -292,7 +292,7 @@ int cmd_query(int argc, char** argv) {
 int cmd_index(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'k', "ksize", true}, {'p', "fpr", true}, {'c', "hash_count", true}, {'t', "threads", true},
                                        {'n', "nucleic_acid", false}, {'i', "ibf", false}, {'r', "reduce", true}, {'D', "device", true},
-                                       {'W', "no-wraparound", false}};
+                                       {'W', "no-wraparound", false}, {'\0', "layout", true}, {'\0', "tmax", true}};
     Args a;
     try {
         a = parse(argc, argv, 2, spec);
@@ -313,6 +313,19 @@ int cmd_index(int argc, char** argv) {
     if (red == "murphy") opt.reduction = 1;
     else if (red == "li") opt.reduction = 2;
     else if (red != "None") { std::cerr << "[Indexing Parser Error] reduce must be murphy or li\n"; return 0; }
+    // --layout uniform|sized [--tmax N] (not in the reference): the HIBF's layout, host/layout.hpp
+    const std::string layout = a.get("layout", "uniform");
+    if (a.has("layout") && a.has("ibf")) { std::cerr << "[Indexing Parser Error] --layout is an HIBF option: not with -i\n"; return 0; }
+    if (layout == "sized") opt.layout = BuildOptions::kSized;
+    else if (layout != "uniform") { std::cerr << "[Indexing Parser Error] --layout must be uniform or sized\n"; return 0; }
+    if (a.has("tmax")) {
+        const std::string t = a.get("tmax", "");
+        char* end = nullptr;
+        const unsigned long long v = std::strtoull(t.c_str(), &end, 10);
+        if (opt.layout != BuildOptions::kSized) { std::cerr << "[Indexing Parser Error] --tmax needs --layout sized\n"; return 0; }
+        if (t.empty() || *end || v == 0 || v % 64) { std::cerr << "[Indexing Parser Error] --tmax must be a positive multiple of 64\n"; return 0; }
+        opt.tmax = v;
+    }
     if (!opt.dna && opt.k > 12) { std::cerr << "[Indexing Parser Error] Max kmer size for amino acids is 12" << "\n"; return 0; }
     std::vector<std::string> files;
     for (size_t i = 1; i < a.pos.size(); ++i) {

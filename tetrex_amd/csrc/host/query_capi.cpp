@@ -113,4 +113,33 @@ int txe_query_masks_sharded(void* const* handles, void* const* aux_handles, size
     }
 }
 
+int txh_index_build(const char* const* paths, size_t n, const txh_build_options* options, txh_index** out) {
+    try {
+        if (!paths || !out) throw std::invalid_argument("null argument");
+        std::vector<std::string> files;
+        for (size_t i = 0; i < n; ++i) files.emplace_back(paths[i]);
+        BuildOptions opt;
+        if (options) {
+            opt.k = options->k;
+            opt.dna = options->dna != 0;
+            opt.reduction = options->reduction;
+            opt.hash_count = options->hash_count;
+            opt.fpr = options->fpr;
+            if (options->flavour < 0 || options->flavour > 2) throw std::invalid_argument("flavour must be 0, 1 or 2");
+            opt.hibf = options->flavour != 2;
+            opt.layout = options->flavour == 1 ? BuildOptions::kSized : BuildOptions::kUniform;
+            if (options->tmax && options->flavour != 1) throw std::invalid_argument("tmax is an option of the sized layout");
+            opt.tmax = options->tmax;
+            opt.device = options->device;
+        }
+        auto ix = std::make_unique<txh_index>();
+        ix->image = build_index(files, opt);
+        *out = ix.release();
+        return 0;
+    } catch (const std::exception& e) {
+        g_qerr = e.what();
+        return -1;
+    }
+}
+
 }  // extern "C"

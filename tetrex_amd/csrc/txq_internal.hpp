@@ -357,6 +357,7 @@ void preload_hibf_kernels();
 
 hipStream_t take_spare_stream(int device);  // a non-blocking stream made at txq_init, or null (txq_api.hip)
 
+int require_init();  // txq_init has run; binds the calling thread to the first device
 int fail(int code, const char* fmt, ...);
 int fail_hip(hipError_t e, const char* what);
 int ensure(void** p, size_t* cap, size_t bytes);

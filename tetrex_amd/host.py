@@ -313,6 +313,76 @@ def _index_api():
     return L
 
 
+class LayoutParams(C.Structure):
+    _fields_ = [("tmax", C.c_uint64), ("fpr", C.c_float), ("relaxed_fpr", C.c_float), ("hash_count", C.c_uint),
+                ("alpha", C.c_double)]
+
+
+class BuildOptions(C.Structure):
+    _fields_ = [("k", C.c_uint), ("dna", C.c_int), ("reduction", C.c_uint), ("hash_count", C.c_uint), ("fpr", C.c_float),
+                ("flavour", C.c_int), ("tmax", C.c_uint64), ("device", C.c_int)]
+
+
+def default_tmax(user_bins):
+    """64 * ceil(ceil(sqrt(B)) / 64): the technical bins of one IBF at most, as the uniform builder chooses them."""
+    return 64 * ((int(np.ceil(np.sqrt(float(user_bins)))) + 63) // 64)
+
+
+def union_window(user_bins, tmax):
+    """W = min(B, 4 * ceil(B / t_max)): the longest run of user bins one merged bin may take."""
+    return min(user_bins, 4 * ((user_bins + tmax - 1) // tmax))
+
+
+def layout_order(counts):
+    """User bins by estimate descending, ties by id (the order of the union table's rows)."""
+    counts = np.asarray(counts, dtype=np.float64)
+    return np.lexsort((np.arange(counts.size), -counts)).astype(np.uint64)
+
+
+def hibf_layout(counts, unions, tmax=None, fpr=0.05, relaxed_fpr=0.3, hash_count=3, alpha=1.2):
+    """The size-aware HIBF layout (host/layout.hpp, include/txh.h txh_hibf_layout), a pure function.
+
+    counts: each user bin's estimate, by user bin id; unions: B x W union estimates over runs in layout_order(counts)
+    (W = union_window(B, tmax)).  Returns dict(order, tmax, window, ibfs=[dict(bins, bin_size, next_ibf_id,
+    tb_to_user_bin)]), the root first and the children in depth-first pre-order."""
+    L = lib()
+    if not hasattr(L, "_layout_ready"):
+        L.txh_hibf_layout.argtypes = [C.POINTER(C.c_double), C.c_uint64, C.POINTER(C.c_double), C.c_uint64,
+                                      C.POINTER(LayoutParams), C.POINTER(C.c_void_p)]
+        L.txh_layout_ibf_count.restype = C.c_int64
+        L.txh_layout_ibf_count.argtypes = [C.c_void_p]
+        L.txh_layout_ibf.restype = C.c_int64
+        L.txh_layout_ibf.argtypes = [C.c_void_p, C.c_uint64, u64p, u64p, u64p, C.c_size_t]
+        L.txh_layout_order.restype = C.c_int64
+        L.txh_layout_order.argtypes = [C.c_void_p, u64p, C.c_size_t]
+        L.txh_layout_free.argtypes = [C.c_void_p]
+        L._layout_ready = True
+    c = np.ascontiguousarray(counts, dtype=np.float64)
+    B = c.size
+    tmax = int(tmax) if tmax else default_tmax(B)
+    u = np.ascontiguousarray(unions, dtype=np.float64).reshape(-1)
+    W = u.size // B if B else 0
+    p = LayoutParams(tmax, fpr, relaxed_fpr, hash_count, alpha)
+    h = C.c_void_p()
+    dp = C.POINTER(C.c_double)
+    if L.txh_hibf_layout(c.ctypes.data_as(dp), B, u.ctypes.data_as(dp), W, C.byref(p), C.byref(h)) != 0:
+        raise _err()
+    try:
+        ibfs = []
+        for i in range(L.txh_layout_ibf_count(h)):
+            n = L.txh_layout_ibf(h, i, None, None, None, 0)
+            size = C.c_uint64()
+            nxt = np.zeros(n, dtype=np.uint64)
+            tbu = np.zeros(n, dtype=np.uint64)
+            L.txh_layout_ibf(h, i, C.byref(size), nxt.ctypes.data_as(u64p), tbu.ctypes.data_as(u64p), n)
+            ibfs.append(dict(bins=int(n), bin_size=int(size.value), next_ibf_id=nxt, tb_to_user_bin=tbu))
+        order = np.zeros(B, dtype=np.uint64)
+        L.txh_layout_order(h, order.ctypes.data_as(u64p), B)
+    finally:
+        L.txh_layout_free(h)
+    return dict(order=order, tmax=tmax, window=W, ibfs=ibfs)
+
+
 class IndexFile:
     """A parsed / constructed TetRex index image (host/index_file.hpp)."""
 
@@ -335,6 +405,24 @@ class IndexFile:
         h = C.c_void_p()
         if L.txh_index_load(str(path).encode(), C.byref(h)) != 0:
             raise _err()
+        return cls(h.value)
+
+    @classmethod
+    def build(cls, paths, k=6, dna=False, reduction=0, layout="sized", tmax=None, fpr=0.05, hash_count=3, device=0):
+        """`tetrex index` without the CLI (txh_index_build of libtetrex_query.so; needs a GPU): layout "sized" (the
+        size-aware HIBF), "uniform" (the default HIBF of the CLI) or "ibf" (a flat IBF, -i)."""
+        from tetrex_amd import capi
+        flavours = {"uniform": 0, "sized": 1, "ibf": 2}
+        if layout not in flavours:
+            raise ValueError("layout must be one of %s" % sorted(flavours))
+        Q = capi._query_lib()
+        Q.txh_index_build.argtypes = [C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(BuildOptions), C.POINTER(C.c_void_p)]
+        arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
+        opt = BuildOptions(k, int(dna), reduction, hash_count, fpr, flavours[layout], int(tmax or 0), device)
+        _index_api()  # the handle is freed through libtetrex_host.so
+        h = C.c_void_p()
+        if Q.txh_index_build(arr, len(paths), C.byref(opt), C.byref(h)) != 0:
+            raise HostError(Q.txe_last_error().decode(errors="replace"))
         return cls(h.value)
 
     @classmethod
