@@ -56,6 +56,8 @@ extern "C" {
  *   TXQ_HIBF_LAYOUT_ORDER=0, TXQ_HIBF_LAYOUT_FUSED=0, TXQ_HIBF_LANE_HASH, TXQ_HIBF_STEPS_PER_GROUP, TXQ_HIBF_TILE, TXQ_HIBF_UNROLL, TXQ_HIBF_STORE_KIND, TXQ_HIBF_WAVES, TXQ_HIBF_STACK_LDS, TXQ_HIBF_LAYOUT_DIRECT=0
  *                                                     which HIBF descent kernel runs, and its tiling
  *   TXQ_PROBE_BLOCKS_PER_CU, TXQ_PROBE_UNROLL, TXQ_PROBE_NT   grid and variant of the flat probe kernel
+ *   TXQ_PROBE_TABLE=0|1                               a flat probe's table of its batch's k-mer domain: never | whenever it fits
+ *                                                     (unset: where the batch repeats its values often enough to pay for it)
  * (tests/test_gpu_knobs.py runs a workload under each of them against the oracle.) */
 
 typedef enum {

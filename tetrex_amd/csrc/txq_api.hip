@@ -81,6 +81,7 @@ void read_knobs() {
     k.probe_blocks_per_cu = (int)std::max(1LL, num("TXQ_PROBE_BLOCKS_PER_CU", 256));
     k.probe_unroll = (int)num("TXQ_PROBE_UNROLL", 2);
     k.probe_nt = flag("TXQ_PROBE_NT");
+    k.probe_table = is("TXQ_PROBE_TABLE", '0') ? 0 : is("TXQ_PROBE_TABLE", '1') ? 1 : -1;
     std::lock_guard<std::mutex> lock(g_knobs_mutex);
     g_knobs = k;
 }
@@ -191,6 +192,11 @@ void Index::release() {
         if (host_pipe.bounce[i]) (void)hipHostFree(host_pipe.bounce[i]);
     }
     host_pipe = HostPipe{};
+    if (probe_table.rows) (void)hipFree(probe_table.rows);
+    if (probe_table.dom) (void)hipFree(probe_table.dom);
+    if (probe_table.done) (void)hipEventDestroy(probe_table.done);
+    probe_table.rows = nullptr; probe_table.dom = nullptr; probe_table.done = nullptr;
+    probe_table.cap_rows = 0; probe_table.recorded = probe_table.refused = false;
     for (const ArenaChunk& c : session_cache.chunks) (void)hipFree(c.p);
     for (const ArenaChunk& c : session_cache.block_chunks) (void)hipFree(c.p);
     for (StagingSet& t : session_cache.set)
@@ -584,7 +590,7 @@ int txq_probe_device(txq_index* ix, const uint64_t* d_kmers, size_t n, uint64_t*
     if (n >> 32) return fail(TXQ_ERR_ARG, "at most 2^32-1 k-mers per call");
     hipStream_t s = (hipStream_t)stream;
     if (ix->is_hibf) return hibf_probe(*ix, knobs(), d_kmers, n, d_masks, d_alive, s);
-    hipError_t e = launch_probe(ix->ibf[0], d_kmers, n, d_masks, d_alive, s);
+    hipError_t e = probe_flat(*ix, knobs(), d_kmers, n, d_masks, d_alive, s);
     if (e != hipSuccess) return fail_hip(e, "probe kernel launch");
     return TXQ_OK;
 }

@@ -45,6 +45,7 @@ struct Knobs {
     // probe (txq_probe.hip)
     int probe_blocks_per_cu = 256, probe_unroll = 2;  // TXQ_PROBE_BLOCKS_PER_CU, TXQ_PROBE_UNROLL
     bool probe_nt = false;                            // TXQ_PROBE_NT
+    int probe_table = -1;  // TXQ_PROBE_TABLE: 0 never the domain table of a flat probe, 1 whenever it fits (tests), unset: where it pays
 };
 Knobs knobs();      // a copy of the snapshot taken at the last entry point (published under a lock: entry points run on several threads)
 void read_knobs();  // take it (txq_api.hip)
@@ -199,6 +200,15 @@ struct Index {
     uint64_t* kmer_table = nullptr; uint32_t kmer_table_bits = 0;  // bits = bits per residue * k of the table that is built
     bool kmer_table_refused = false;                               // (the allocation failed once: not tried again)
     std::mutex table_mutex;                                        // building / dropping the table (sessions of one index may run on several threads)
+    // The flat probe's scratch table of a call's k-mer domain (txq_probe.hip probe_flat): rebuilt on every call, so nothing in
+    // it outlives the call; `done` is recorded behind the call's last kernel and the next call, on whatever stream, waits for it.
+    struct ProbeTable {
+        uint64_t* rows = nullptr; size_t cap_rows = 0;  // [cap_rows][stride]
+        uint32_t* dom = nullptr;                        // the domain pass's answer: D, k-mers below the capacity
+        hipEvent_t done = nullptr;
+        bool recorded = false, refused = false;         // (refused: the allocation failed once, not tried again)
+        std::mutex mutex;
+    } probe_table;
 
     // Device buffers of the last session, kept for the next one: a single query must not pay
     // hipMalloc/hipFree (they cost more than its kernels).  One session at a time may hold them.
@@ -365,6 +375,8 @@ int alloc_ibf(const txq_ibf_desc& d, uint64_t w0, uint64_t w1, IbfDev* out, uint
 
 // txq_probe.hip
 hipError_t launch_probe(const IbfDev& f, const uint64_t* kmers, size_t n, uint64_t* masks, uint64_t* alive, hipStream_t s);
+// txq_probe_device on a flat index: launch_probe, or the domain-table path where the batch's k-mer domain is small
+hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* kmers, size_t n, uint64_t* masks, uint64_t* alive, hipStream_t s);
 hipError_t launch_probe_interleaved(const IbfDev& interleaved, const HibfNode& root, const void* children, uint32_t wpr_log2, const uint64_t* kmers,
                                     size_t n, uint64_t* masks, uint64_t* alive, hipStream_t s);
 hipError_t launch_emplace(const IbfDev& f, const uint64_t* values, const uint32_t* bins_of, size_t n, hipStream_t s);

@@ -14,7 +14,18 @@
 //     first AND, 94 VGPRs = 5 waves/SIMD); output rows of one step are contiguous (coalesced 1-KiB stores),
 //   * `alive` (mask != 0, the collector's path_.none() test) falls out of one __ballot per step.
 // Algorithmic HBM bytes per probe: h*W*8 (rows) + W*8 (mask) + 8 (k-mer); W = shard_words.
+//
+// Domain table (probe_flat, the path of txq_probe_device on a flat IBF): a batch whose values lie in a domain [0, D)
+// several times smaller than the batch holds each value n/D times, and every repeat gathers the same h rows again.  Per call:
+//   1. probe_domain_kernel: a 1/16 sample of the k-mers -> D = 1 + the largest value below the table's capacity, and how
+//      many values lie below it (device word; the host gets no answer back, the call stays stream-ordered),
+//   2. probe_kernel<..., kBuild>: every value of [0, D) probed into a scratch table T[v] (row pitch = stride),
+//   3. probe_kernel<..., kAnswer>: the same lane layout; a k-mer v < D reads ONE row T[v], any other k-mer (and every
+//      k-mer when the domain does not pay, count < ratio * D) gathers its h rows as above.
+// The table is rebuilt on every call (no answer survives a call; emplace needs no invalidation).  Per probe of the
+// answer: 8 (k-mer) + W*8 (table row) + W*8 (mask); per call D * (h*W*8 + W*8) to build and n/2 bytes of sample.
 #include "txq_internal.hpp"
+#include <algorithm>
 #include <cstdlib>
 
 namespace txq {
@@ -44,25 +55,52 @@ struct TreeRoot {
     uint32_t wpr_log2;         // log2(mask words per child)
 };
 
+// The domain table of one call (see the header): dom[0] = D = 1 + the largest k-mer value below `cap` in a sample of the
+// batch (0: none), dom[1] = how many k-mers of the sample lie below `cap`.  The table is used when the batch holds about
+// ratio * D k-mers below D, dom[1] * sample >= ratio * D (ratio 0: always).
+struct TableArgs {
+    uint64_t* table;        // T[v] at table + v * stride, v < D
+    const uint32_t* dom;
+    uint32_t ratio, sample;
+};
+__device__ __forceinline__ uint32_t table_rows(const TableArgs& T) {
+    const uint32_t d = T.dom[0], c = T.dom[1];
+    return d && (uint64_t)c * T.sample >= (uint64_t)T.ratio * d ? d : 0u;
+}
+enum ProbeMode { kPlain = 0, kBuild = 1, kAnswer = 2 };
+
 // LPK lanes per k-mer, H hash functions, U steps in flight.  Requires bin_size < 2^32 and an even
 // stride.  U*H independent 16-byte gathers per lane are issued before the first AND.
-template <int LPK, int H, int U, bool NT, class ROOT = NoRoot>
+// MODE kBuild: the k-mers are 0 .. D-1 (no input), written to T.table at row pitch stride (whole 16-byte chunks, plain
+// stores: the answer reads them back); MODE kAnswer: k-mers below D read their row of T.table instead of gathering.
+template <int LPK, int H, int U, bool NT, class ROOT = NoRoot, int MODE = kPlain>
 __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __restrict__ kmers, size_t n,
-                                                    uint64_t* __restrict__ masks, uint64_t* __restrict__ alive, ROOT R = ROOT{}) {
+                                                    uint64_t* __restrict__ masks, uint64_t* __restrict__ alive, ROOT R = ROOT{},
+                                                    TableArgs T = TableArgs{}) {
     constexpr int KPS = 64 / LPK;          // k-mers per step
     constexpr int UU = U < LPK ? U : LPK;  // a tile has LPK steps
     const int lane = threadIdx.x & 63;
     const int sub = lane % LPK, grp = lane / LPK;
     const uint32_t chunks = f.stride >> 1;
+    const uint32_t tab_rows = MODE == kPlain ? 0u : table_rows(T);
+    if constexpr (MODE == kBuild) n = tab_rows;
     const size_t n_tiles = (n + 63) >> 6;
     const size_t n_waves = (size_t)gridDim.x * (blockDim.x >> 6);
     for (size_t tile = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); tile < n_tiles; tile += n_waves) {
         const size_t base = tile << 6;
         const size_t mine = base + lane;
-        const uint64_t v = mine < n ? __builtin_nontemporal_load(kmers + mine) : 0;
+        const uint64_t v = MODE == kBuild ? (uint64_t)mine : mine < n ? __builtin_nontemporal_load(kmers + mine) : 0;
+        const bool tab = MODE == kAnswer && mine < n && v < tab_rows;  // my k-mer's mask is row v of the table
         uint32_t row[H];
+        if (tab) {
+            row[0] = (uint32_t)v;
 #pragma unroll
-        for (int i = 0; i < H; ++i) row[i] = (uint32_t)hash_row(v, kSeeds[i], f.hash_shift, f.bin_size);
+            for (int i = 1; i < H; ++i) row[i] = 0;
+        } else {
+#pragma unroll
+            for (int i = 0; i < H; ++i) row[i] = (uint32_t)hash_row(v, kSeeds[i], f.hash_shift, f.bin_size);
+        }
+        const uint64_t tab_lanes = MODE == kAnswer ? __ballot(tab) : 0;
         uint32_t root_lo = ~0u, root_hi = ~0u;  // the root's verdict on my k-mer: bit b = it may be in the child behind merged bin b
         if constexpr (ROOT::kActive) {
             const uint64_t* rw = (const uint64_t*)R.root.words;
@@ -96,12 +134,18 @@ __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __
                 }
                 u32x4 x[UU][H];
 #pragma unroll
-                for (int u = 0; u < UU; ++u)
+                for (int u = 0; u < UU; ++u) {
+                    const bool t = MODE == kAnswer && ((tab_lanes >> ((s + u) * KPS + grp)) & 1ULL);
 #pragma unroll
                     for (int i = 0; i < H; ++i) {
-                        const uint64_t* p = f.words + (size_t)r[u][i] * f.stride + 2u * c;
+                        if (MODE == kAnswer && t && i > 0) {
+                            x[u][i] = u32x4{~0u, ~0u, ~0u, ~0u};
+                            continue;
+                        }
+                        const uint64_t* p = (MODE == kAnswer && t ? T.table : f.words) + (size_t)r[u][i] * f.stride + 2u * c;
                         x[u][i] = NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)) : ld16(p);
                     }
+                }
 #pragma unroll
                 for (int u = 0; u < UU; ++u) {
                     u32x4 acc = x[u][0];
@@ -112,7 +156,9 @@ __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __
                         acc.x &= m0; acc.y &= m0; acc.z &= m1; acc.w &= m1;
                     }
                     const size_t kidx = base + (s + u) * KPS + grp;
-                    if (kidx < n) store_chunk(f, masks, kidx, c, acc);
+                    if (MODE == kBuild) {
+                        if (kidx < n) *reinterpret_cast<u32x4*>(masks + kidx * f.stride + 2u * c) = acc;
+                    } else if (kidx < n) store_chunk(f, masks, kidx, c, acc);
                     nz[u] |= nonzero(acc);
                 }
             }
@@ -201,6 +247,44 @@ __global__ __launch_bounds__(256) void emplace_kernel(IbfDev f, const uint64_t* 
     }
 }
 
+// The domain pass of the table path: dom[0] = max(v + 1), dom[1] = count over the k-mers v < cap of a SAMPLE (dom zeroed
+// before): block b reads the head of the b-th of gridDim.x equal segments of the batch, 1 / kDomainSample of it in all.
+// The gate does not decide correctness (a k-mer the sample missed, v >= D, gathers its rows), so a sample is enough, and
+// a batch whose domain does not pay costs a few microseconds rather than a pass over all its k-mers.
+static constexpr uint32_t kDomainSample = 16;
+__global__ __launch_bounds__(256) void probe_domain_kernel(const uint64_t* __restrict__ kmers, size_t n, uint32_t cap, uint32_t* __restrict__ dom) {
+    uint32_t top = 0, count = 0;
+    const size_t lo = n * blockIdx.x / gridDim.x, hi = n * (blockIdx.x + 1) / gridDim.x;
+    const size_t end = lo + (hi - lo + kDomainSample - 1) / kDomainSample;
+    for (size_t i = lo + threadIdx.x; i < end; i += blockDim.x) {
+        const uint64_t v = kmers[i];
+        if (v < cap) {
+            top = max(top, (uint32_t)v + 1u);
+            ++count;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        top = max(top, (uint32_t)__shfl_xor((int)top, o));
+        count += (uint32_t)__shfl_xor((int)count, o);
+    }
+    __shared__ uint32_t s_top[4], s_count[4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        s_top[wave] = top;
+        s_count[wave] = count;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int waves = blockDim.x >> 6;
+        for (int w = 1; w < waves; ++w) {
+            top = max(top, s_top[w]);
+            count += s_count[w];
+        }
+        if (top) atomicMax(dom, top);
+        if (count) atomicAdd(dom + 1, count);
+    }
+}
+
 // ---- launchers --------------------------------------------------------------------------
 
 static inline unsigned grid_for(size_t work_items, unsigned per_block) {
@@ -285,6 +369,91 @@ hipError_t launch_probe(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* 
     if (chunks <= 16) return launch_lpk<16>(f, k, n, m, a, s);
     if (chunks <= 32) return launch_lpk<32>(f, k, n, m, a, s);
     return launch_lpk<64>(f, k, n, m, a, s);
+}
+
+// The domain-table path (header comment).  ratio: the table is used when at least ratio * D k-mers of the batch lie below D
+// (0: whenever D fits the table).  The table must hold `cap` rows; the caller keeps other calls off it until the answer ran.
+template <int LPK>
+static hipError_t launch_table_lpk(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* m, uint64_t* a, uint64_t* table, uint32_t* dom,
+                                   uint32_t cap, uint32_t ratio, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(dom, 0, 2 * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    const unsigned dgrid = (unsigned)std::min<size_t>(std::max<size_t>(n / 1024, 1), 512);  // segments of the sample
+    probe_domain_kernel<<<dgrid, 256, 0, s>>>(k, n, cap, dom);
+    const TableArgs T{table, dom, ratio, kDomainSample};
+    // the build's grid covers the capacity (D is not known on the host); waves past D leave at once
+    const unsigned bgrid = (unsigned)std::min<size_t>(((size_t)cap + 255) / 256, 2048);
+    const unsigned grid = grid_for((n + 63) / 64, 4);
+    switch (f.hash_funs) {
+#define TXQ_TABLE_H(H)                                                                                                  \
+        case H:                                                                                                           \
+            probe_kernel<LPK, H, 2, false, NoRoot, kBuild><<<bgrid, 256, 0, s>>>(f, nullptr, 0, table, nullptr, NoRoot{}, T); \
+            probe_kernel<LPK, H, 2, false, NoRoot, kAnswer><<<grid, 256, 0, s>>>(f, k, n, m, a, NoRoot{}, T);             \
+            break;
+        TXQ_TABLE_H(2) TXQ_TABLE_H(3) TXQ_TABLE_H(4) TXQ_TABLE_H(5)
+#undef TXQ_TABLE_H
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// Rows a call of n k-mers may give the table, 0: the plain path (the host's half of the gate; the device decides from D).
+static constexpr uint32_t kTableRatio = 4;  // n / D at which the table pays: (h + 1) / (h - 1) = 2 at h = 3, with margin
+static size_t table_capacity(const IbfDev& f, const Knobs& kn, size_t n) {
+    if (kn.probe_table == 0 || kn.kmer_table_mb <= 0 || (f.bin_size >> 32) || f.stride < 2 || (f.stride & 1) || f.hash_funs < 2)
+        return 0;
+    const size_t budget = ((size_t)kn.kmer_table_mb << 20) / ((size_t)f.stride * 8);
+    size_t cap = kn.probe_table == 1 ? std::max<size_t>(n, 1 << 16) : n / kTableRatio;
+    cap = std::min(cap, budget) & ~(size_t)63;
+    if (kn.probe_table != 1 && cap < (1 << 14)) return 0;  // a batch this small does not pay for three launches
+    return cap;
+}
+
+hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* k, size_t n, uint64_t* m, uint64_t* a, hipStream_t s) {
+    const IbfDev& f = ix.ibf[0];
+    const size_t cap = n && f.shard_words ? table_capacity(f, kn, n) : 0;
+    if (!cap) return launch_probe(f, k, n, m, a, s);
+    Index::ProbeTable& pt = ix.probe_table;
+    // one table per index: a call on another stream (txq_probe's second stream, another host thread) waits for the
+    // answer of the call before it; the lock keeps (wait, launches, record) of two host threads apart
+    std::lock_guard<std::mutex> lock(pt.mutex);
+    if (pt.refused) return launch_probe(f, k, n, m, a, s);
+    if (pt.cap_rows < cap) {
+        if (pt.rows) {  // growing: the kernels of an earlier call may still read the old table
+            if (pt.recorded) (void)hipEventSynchronize(pt.done);
+            (void)hipFree(pt.rows);
+            pt.rows = nullptr;
+            pt.cap_rows = 0;
+        }
+        if (!pt.dom && hipMalloc((void**)&pt.dom, 2 * sizeof(uint32_t)) != hipSuccess) pt.dom = nullptr;
+        if (!pt.done && hipEventCreateWithFlags(&pt.done, hipEventDisableTiming) != hipSuccess) pt.done = nullptr;
+        if (!pt.dom || !pt.done || hipMalloc((void**)&pt.rows, cap * f.stride * 8) != hipSuccess) {
+            (void)hipGetLastError();  // (out of memory is not an error of this call: the rows are gathered as before)
+            pt.rows = nullptr;
+            pt.refused = true;
+            return launch_probe(f, k, n, m, a, s);
+        }
+        pt.cap_rows = cap;
+    }
+    if (pt.recorded) {
+        hipError_t e = hipStreamWaitEvent(s, pt.done, 0);
+        if (e != hipSuccess) return e;
+    }
+    const uint32_t ratio = kn.probe_table == 1 ? 0u : kTableRatio;
+    const uint32_t chunks = f.stride >> 1;
+    hipError_t e;
+    if (chunks <= 1) e = launch_table_lpk<1>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
+    else if (chunks <= 2) e = launch_table_lpk<2>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
+    else if (chunks <= 4) e = launch_table_lpk<4>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
+    else if (chunks <= 8) e = launch_table_lpk<8>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
+    else if (chunks <= 16) e = launch_table_lpk<16>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
+    else if (chunks <= 32) e = launch_table_lpk<32>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
+    else e = launch_table_lpk<64>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
+    if (e != hipSuccess) return e;
+    e = hipEventRecord(pt.done, s);
+    if (e != hipSuccess) return e;
+    pt.recorded = true;
+    return hipSuccess;
 }
 
 // the interleaved children of a small regular HIBF (even stride, rows < 2^32, root of at most 64 merged bins)
