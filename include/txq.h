@@ -16,6 +16,8 @@
  *                              (the mask algebra of the collector — path_ &= hits, absorb |=, Match |= —
  *                               compiled by the host into mask-DAG programs, see txq_program.h)
  *   txq_emplace_device      <- interleaved_bloom_filter::emplace     include/index_ibf.h:94-98 (index build, "next")
+ *   txq_count / _device     <- seqan::hibf membership_for(values, threshold) / counting_agent::bulk_count, the general form of
+ *                              the one-value, threshold-1 call at include/index_hibf.h:142-147 (`tetrex search`)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every function returns 0 on success or a
  * negative txq_status; txq_last_error() gives the message for the calling thread.  Host buffers are
@@ -172,6 +174,25 @@ int txq_probe(txq_index* ix, const uint64_t* kmers, size_t n, uint64_t* masks);
  * (bitvector::none() of include/otf_collector.h:383, per shard). */
 int txq_probe_device(txq_index* ix, const uint64_t* d_kmers, size_t n, uint64_t* d_masks, uint64_t* d_alive,
                      void* stream);
+
+/* Threshold membership of value sets (seqan::hibf membership_for(values, threshold); counting_agent::bulk_count on a
+ * flat IBF).  Query q owns d_values[d_offsets[q] .. d_offsets[q+1]) (n_queries + 1 ascending offsets, at most 2^32-1
+ * values per call).  d_hits: n_queries x shard_words words.  d_counts: NULL, or n_queries x (64 * shard_words) u32.
+ * Flat IBF: counts[q][b] = how many values of q have bit b in bulk_contains, hits[q][b] = counts[q][b] >= thresholds[q].
+ * HIBF: every visited IBF counts the values per technical bin; a run of technical bins of one user bin is summed (a split
+ * bin's parts add up), a merged bin whose count reaches the threshold is visited, a run whose sum reaches it is a hit;
+ * counts[q][u] is the run's sum (the largest, where a user bin's parts form several runs; 0 for a user bin whose IBF is not
+ * visited), so hits[q][u] == (counts[q][u] >= thresholds[q]) on every kind of index.  Threshold 0 selects every bin; one value at
+ * threshold 1 gives txq_probe's mask.  A column shard answers for its own columns; sub-tree shards are refused (TXQ_ERR_ARG).
+ * txq_count checks its host offsets before anything is launched; txq_count_device trusts the device offsets it is given.
+ * Neither can check that the offsets stay within the values (no value count is passed): that is the caller's part.
+ * Limits: on an HIBF every IBF may have at most 8192 technical bins (a wider one: TXQ_ERR_ARG).  On a flat IBF a long query is
+ * spread over many workgroups; on an HIBF each (query, IBF) pair is counted by one wave, so a very long query (10^5 values and
+ * more) is slow there, though exact. */
+int txq_count_device(txq_index* ix, const uint64_t* d_values, const uint64_t* d_offsets, size_t n_queries,
+                     const uint32_t* d_thresholds, uint64_t* d_hits, uint32_t* d_counts, void* stream);
+int txq_count(txq_index* ix, const uint64_t* values, const uint64_t* offsets, size_t n_queries,
+              const uint32_t* thresholds, uint64_t* hits, uint32_t* counts);  /* host buffers, synchronous */
 
 /* Device-side emplace: value i is inserted into bin bins_of[i] (flat IBF only; bins outside this
  * shard's columns are skipped). */

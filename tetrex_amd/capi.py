@@ -21,7 +21,7 @@ TXQ_MERGED_BIN = 0xFFFFFFFFFFFFFFFF
 SYMBOLS = [
     "txq_init", "txq_shutdown", "txq_last_error", "txq_device_count",
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
-    "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device",
+    "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
     "txq_malloc", "txq_free", "txq_memcpy_h2d", "txq_memcpy_d2h", "txq_synchronize", "txq_host_alloc", "txq_host_free",
@@ -75,6 +75,8 @@ def lib():
         L.txq_probe.argtypes = [C.c_void_p, u64p, C.c_size_t, u64p]
         L.txq_probe_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.txq_emplace_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.txq_count.argtypes = [C.c_void_p, u64p, u64p, C.c_size_t, u32p, u64p, u32p]
+        L.txq_count_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.txq_run_programs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, u64p]
         L.txq_run_programs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         L.txq_session_begin.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
@@ -305,6 +307,26 @@ class Index:
 
     def probe_device(self, d_kmers, n, d_masks, d_alive=None, stream=None):
         check(lib().txq_probe_device(self._h, d_kmers, n, d_masks, d_alive, stream))
+
+    def count(self, values, offsets, thresholds, counts=False):
+        """Threshold membership of value sets (txq_count): query q owns values[offsets[q]:offsets[q+1]] and thresholds[q].
+        Returns hits (n_queries, shard_words) uint64, and with counts=True also counts (n_queries, 64 * shard_words) uint32."""
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        t = np.ascontiguousarray(thresholds, dtype=np.uint32)
+        nq = o.size - 1
+        if nq < 0 or t.size != nq:
+            raise TxqError(-1, "count: %d offsets and %d thresholds" % (o.size, t.size))
+        if nq and int(o.max()) > v.size:
+            raise TxqError(-1, "count: offsets run past the %d values" % v.size)
+        hits = np.zeros((max(nq, 0), self.shard_words), dtype=np.uint64)
+        cnt = np.zeros((max(nq, 0), 64 * self.shard_words), dtype=np.uint32) if counts else None
+        check(lib().txq_count(self._h, v.ctypes.data_as(u64p), o.ctypes.data_as(u64p), nq, t.ctypes.data_as(u32p),
+                              hits.ctypes.data_as(u64p), cnt.ctypes.data_as(u32p) if counts else None))
+        return (hits, cnt) if counts else hits
+
+    def count_device(self, d_values, d_offsets, n_queries, d_thresholds, d_hits, d_counts=None, stream=None):
+        check(lib().txq_count_device(self._h, d_values, d_offsets, n_queries, d_thresholds, d_hits, d_counts, stream))
 
     def emplace_device(self, d_values, d_bins_of, n, stream=None):
         check(lib().txq_emplace_device(self._h, d_values, d_bins_of, n, stream))

@@ -284,6 +284,17 @@ std::vector<uint64_t> run_queries(txq_index* ix, const KmerEncoder& enc, const s
     return masks;
 }
 
+void DeviceIndex::count(const std::vector<uint64_t>& values, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& thresholds,
+                        std::vector<uint64_t>& hits, std::vector<uint32_t>* counts) {
+    if (!ix_) throw std::runtime_error("index not uploaded");
+    if (shards_.size() > 1) throw std::runtime_error("count: one shard only");
+    if (offsets.empty() || thresholds.size() + 1 != offsets.size()) throw std::runtime_error("count: offsets and thresholds disagree");
+    const size_t n = thresholds.size(), W = info_.shard_words;
+    hits.assign(n * W, 0);
+    if (counts) counts->assign(n * W * 64, 0);
+    txq_check(txq_count(ix_, values.data(), offsets.data(), n, thresholds.data(), hits.data(), counts ? counts->data() : nullptr), "txq_count");
+}
+
 std::vector<uint64_t> DeviceIndex::query_masks(const std::vector<std::string>& regexes, std::vector<int>* status,
                                                std::vector<std::string>* messages, StagedStats* stats, const StagedOptions* options) {
     if (!ix_) throw std::runtime_error("index not uploaded");

@@ -88,6 +88,11 @@ class DeviceIndex {
     std::vector<uint64_t> query_masks(const std::vector<std::string>& regexes, std::vector<int>* status = nullptr,
                                       std::vector<std::string>* messages = nullptr, StagedStats* stats = nullptr,
                                       const StagedOptions* options = nullptr);
+    // threshold membership of value sets (txq_count, `tetrex search`) on the uploaded shard: query q owns
+    // values[offsets[q] .. offsets[q+1]) and thresholds[q]; hits: n x result_words() words, counts (if not null):
+    // n x 64 * result_words() u32.  One shard only (upload()).
+    void count(const std::vector<uint64_t>& values, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& thresholds,
+               std::vector<uint64_t>& hits, std::vector<uint32_t>* counts);
     // `tetrex query -g`: upload the d-gram index next to the main index (same device, same shard)
     void attach_dgram(const DgramImage& dgram);
     bool has_dgram() const { return aux_ != nullptr; }

@@ -3,15 +3,19 @@
 //     (include/arg_parse.h:57-71, src/main.cpp:36-59, src/query.cpp:477-498)
 //   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] [--layout uniform|sized [--tmax N]] <name> <libs...>
 //     (include/arg_parse.h:10-38, src/index_base.cpp:73-117)
+//   tetrex search [-e E | --threshold F] [--counts] [-o dest] [-v] <index.ibf> <queries.fa[.gz]>
+//     (not in the reference: every FASTA record a query, answered by seqan::hibf membership_for(values, threshold))
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
 #include "device_index.hpp"
+#include "fasta.hpp"
 #include "index_file.hpp"
 #include "kgraph.hpp"
 #include "regex_front.hpp"
 #include "verify.hpp"
 
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <filesystem>
@@ -375,6 +379,106 @@ int cmd_track(int argc, char** argv) {
     return 0;
 }
 
+// tetrex search: each record of the query file is a query; its values are the index's k-mers of the record (n of them) and a
+// bin is reported when at least t of them are in it (txq_count).  -e E: t = max(n - k E, 0) — a record within E edits of a
+// substring of a bin shares at least n - k E k-mer positions with it (q-gram lemma), and a Bloom filter drops none of them,
+// so that bin is always reported.  --threshold F (0 < F <= 1): t = ceil(F n).  Rows: name \t bin path [\t count/n].
+int cmd_search(int argc, char** argv) {
+    const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
+                                       {'v', "verbose", false}, {'D', "device", true}};
+    Args a;
+    unsigned long long errors = 0;
+    double fraction = 0;
+    try {
+        a = parse(argc, argv, 2, spec);
+        if (a.pos.size() != 2) throw std::runtime_error("expected <index> <queries.fa>");
+        if (a.has("errors") && a.has("threshold")) throw std::runtime_error("-e and --threshold exclude each other");
+        if (a.has("errors")) {
+            const std::string e = a.get("errors", "");
+            char* end = nullptr;
+            errors = std::strtoull(e.c_str(), &end, 10);
+            if (e.empty() || *end || e[0] == '-') throw std::runtime_error("-e must be a number of errors >= 0");
+        }
+        if (a.has("threshold")) {
+            const std::string f = a.get("threshold", "");
+            char* end = nullptr;
+            fraction = std::strtod(f.c_str(), &end);
+            if (f.empty() || *end || !(fraction > 0.0 && fraction <= 1.0)) throw std::runtime_error("--threshold must be a fraction in (0, 1]");
+        }
+    } catch (const std::exception& e) {
+        std::cerr << "[Search Parser Error] " << e.what() << "\n";
+        return 1;
+    }
+    const bool verbose = a.has("verbose"), with_counts = a.has("counts");
+    const std::string dest = a.get("output", "-");
+    const double t_start = now();
+    IndexImage image;
+    try {
+        image = read_index_file(a.pos[0]);
+    } catch (const std::exception& e) {
+        std::cerr << "Filepath to (H)IBF Index not valid" << std::endl;
+        std::cerr << e.what() << '\n';
+        return 1;
+    }
+    DeviceIndex dev;
+    dev.upload(image, std::atoi(a.get("device", "0").c_str()));
+    const KmerEncoder enc = dev.encoder();
+    const uint64_t bins = dev.bins(), W = dev.result_words();
+    std::ofstream file;
+    if (dest != "-") {
+        file.open(dest);
+        if (!file) throw std::runtime_error("Failed to open output file: " + dest);
+    }
+    std::ostream& out = dest == "-" ? std::cout : file;
+    // queries go to the device in batches: at most 2^24 values, and at most 256 MiB of counts
+    const size_t max_values = (size_t)1 << 24, max_queries = std::max<size_t>(1, ((size_t)256 << 20) / (W * 64 * 4));
+    std::vector<std::string> names;
+    std::vector<uint64_t> values, offsets{0}, n_of;
+    std::vector<uint32_t> thresholds, counts;
+    std::vector<uint64_t> hits;
+    std::string row;
+    auto flush = [&]() {
+        if (names.empty()) return;
+        dev.count(values, offsets, thresholds, hits, with_counts ? &counts : nullptr);
+        for (size_t q = 0; q < names.size(); ++q) {
+            for (uint64_t u : set_bins(hits.data() + q * W, bins)) {
+                row.assign(names[q]).append("\t").append(image.bin_paths[u]);
+                if (with_counts) row.append("\t").append(std::to_string(counts[q * W * 64 + u])).append("/").append(std::to_string(n_of[q]));
+                out << row << '\n';
+            }
+        }
+        names.clear();
+        values.clear();
+        offsets.assign(1, 0);
+        n_of.clear();
+        thresholds.clear();
+    };
+    std::vector<uint64_t> v;
+    for_each_record(a.pos[1], [&](const FastaRecord& r) {
+        v.clear();
+        enc.record_values(r.seq, false, v);
+        const uint64_t n = v.size();
+        if (n == 0) {
+            std::cerr << "[tetrex search] " << r.name << ": no k-mer of length " << enc.k() << ", skipped" << std::endl;
+            return;
+        }
+        uint64_t t;
+        if (a.has("threshold")) t = (uint64_t)std::ceil(fraction * (double)n);
+        else t = n > (uint64_t)enc.k() * errors ? n - (uint64_t)enc.k() * errors : 0;
+        if (t == 0) std::cerr << "[tetrex search] " << r.name << ": threshold 0, every bin is reported" << std::endl;
+        if (values.size() + n > max_values || names.size() >= max_queries) flush();
+        names.push_back(r.name);
+        values.insert(values.end(), v.begin(), v.end());
+        offsets.push_back(values.size());
+        n_of.push_back(n);
+        thresholds.push_back((uint32_t)std::min<uint64_t>(t, 0xFFFFFFFFull));
+    });
+    flush();
+    out.flush();
+    if (verbose) std::cerr << "Search time: " << (now() - t_start) << " s" << std::endl;
+    return 0;
+}
+
 int cmd_inspect(int argc, char** argv) {
     if (argc != 3) { std::cerr << "[Error TetRex Index Inspection module expected <index>\n"; return 0; }
     std::cerr << "Reading Index from Disk... ";
@@ -406,10 +510,11 @@ int cmd_inspect(int argc, char** argv) {
 
 int main(int argc, char** argv) {
     try {
-        if (argc < 2) { std::cerr << "[Error] usage: tetrex {index|query|inspect} ...\n"; return -1; }
+        if (argc < 2) { std::cerr << "[Error] usage: tetrex {index|query|search|inspect} ...\n"; return -1; }
         const std::string sub = argv[1];
         if (sub == "query") return cmd_query(argc, argv);
         if (sub == "index") return cmd_index(argc, argv);
+        if (sub == "search") return cmd_search(argc, argv);
         if (sub == "inspect") return cmd_inspect(argc, argv);
         if (sub == "track") return cmd_track(argc, argv);
         std::cerr << "[Error] unknown sub-command " << sub << "\n";

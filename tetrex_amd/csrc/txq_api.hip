@@ -228,8 +228,11 @@ void Index::release() {
     if (d_merged_off) (void)hipFree(d_merged_off);
     d_merged = d_merged_off = nullptr;
     for (void* p : {(void*)scratch_kmers, (void*)scratch_masks, (void*)frontier[0], (void*)frontier[1], (void*)d_counts,
-                    (void*)scratch_blob, (void*)scratch_slots, (void*)scratch_final, (void*)scratch_dense_kmers, (void*)scratch_dense_masks, (void*)kmer_table})
+                    (void*)scratch_blob, (void*)scratch_slots, (void*)scratch_final, (void*)scratch_dense_kmers, (void*)scratch_dense_masks, (void*)kmer_table,
+                    (void*)scratch_count_acc, (void*)scratch_count_io})
         if (p) (void)hipFree(p);
+    scratch_count_acc = nullptr; cap_count_acc = 0;
+    scratch_count_io = nullptr; cap_count_io = 0;
     kmer_table = nullptr; kmer_table_bits = 0;
     d_ibf = nullptr; d_next = d_tb_user = nullptr; d_map_off = nullptr;
     scratch_kmers = scratch_masks = nullptr; frontier[0] = frontier[1] = nullptr; d_counts = nullptr;
@@ -653,6 +656,60 @@ int txq_probe(txq_index* ix, const uint64_t* kmers, size_t n, uint64_t* masks) {
     }
     if (int rc = drain(b)) return rc;
     if (int rc = drain(b ^ 1)) return rc;
+    return TXQ_OK;
+}
+
+int txq_count_device(txq_index* ix, const uint64_t* d_values, const uint64_t* d_offsets, size_t n_queries, const uint32_t* d_thresholds,
+                     uint64_t* d_hits, uint32_t* d_counts, void* stream) {
+    if (!ix) return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = bind_index(ix)) return rc;
+    if (n_queries && (!d_values || !d_offsets || !d_thresholds || !d_hits)) return fail(TXQ_ERR_ARG, "null argument");
+    if (ix->join_or) return fail(TXQ_ERR_ARG, "txq_count does not support sub-tree shards (txq_index_upload_subtrees)");
+    if (n_queries >= 0xFFFFFFFFull) return fail(TXQ_ERR_ARG, "at most 2^32-2 queries per call");
+    return count_device(*ix, d_values, d_offsets, n_queries, d_thresholds, d_hits, d_counts, (hipStream_t)stream);
+}
+
+// Host buffers: the offsets are checked here, then the call's values, offsets (rebased to 0), thresholds and results go through
+// one device buffer of the index, on the index's first host-pipe stream.
+int txq_count(txq_index* ix, const uint64_t* values, const uint64_t* offsets, size_t n_queries, const uint32_t* thresholds, uint64_t* hits,
+              uint32_t* counts) {
+    if (!ix) return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = bind_index(ix)) return rc;
+    if (!offsets || (n_queries && (!thresholds || !hits))) return fail(TXQ_ERR_ARG, "null argument");
+    if (ix->join_or) return fail(TXQ_ERR_ARG, "txq_count does not support sub-tree shards (txq_index_upload_subtrees)");
+    if (n_queries >= 0xFFFFFFFFull) return fail(TXQ_ERR_ARG, "at most 2^32-2 queries per call");
+    for (size_t q = 0; q < n_queries; ++q)
+        if (offsets[q + 1] < offsets[q]) return fail(TXQ_ERR_ARG, "offsets are not ascending at query %zu", q);
+    const uint64_t n_values = n_queries ? offsets[n_queries] - offsets[0] : 0;
+    if (n_values >> 32) return fail(TXQ_ERR_ARG, "%llu values: at most 2^32-1 per call", (unsigned long long)n_values);
+    if (n_values && !values) return fail(TXQ_ERR_ARG, "null argument");
+    const size_t W = ix->shard_words;
+    if (n_queries == 0 || W == 0) return TXQ_OK;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_val = up(n_values * 8), b_off = up((n_queries + 1) * 8), b_thr = up(n_queries * 4), b_hit = up(n_queries * W * 8);
+    const size_t b_cnt = counts ? up(n_queries * W * 64 * 4) : 0;
+    if (int rc = ensure((void**)&ix->scratch_count_io, &ix->cap_count_io, b_val + b_off + b_thr + b_hit + b_cnt)) return rc;
+    unsigned char* base = ix->scratch_count_io;
+    uint64_t* d_val = (uint64_t*)base;
+    uint64_t* d_off = (uint64_t*)(base + b_val);
+    uint32_t* d_thr = (uint32_t*)(base + b_val + b_off);
+    uint64_t* d_hit = (uint64_t*)(base + b_val + b_off + b_thr);
+    uint32_t* d_cnt = counts ? (uint32_t*)(base + b_val + b_off + b_thr + b_hit) : nullptr;
+    std::vector<uint64_t> rebased(offsets, offsets + n_queries + 1);
+    for (uint64_t& o : rebased) o -= offsets[0];
+    Index::HostPipe& hp = ix->host_pipe;
+    if (!hp.stream[0]) TXQ_HIP(hipStreamCreateWithFlags(&hp.stream[0], hipStreamNonBlocking));
+    hipStream_t st = hp.stream[0];
+    if (n_values) TXQ_HIP(hipMemcpyAsync(d_val, values + offsets[0], n_values * 8, hipMemcpyHostToDevice, st));
+    TXQ_HIP(hipMemcpyAsync(d_off, rebased.data(), rebased.size() * 8, hipMemcpyHostToDevice, st));
+    TXQ_HIP(hipMemcpyAsync(d_thr, thresholds, n_queries * 4, hipMemcpyHostToDevice, st));
+    if (int rc = count_device(*ix, d_val, d_off, n_queries, d_thr, d_hit, d_cnt, st)) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    TXQ_HIP(hipMemcpyAsync(hits, d_hit, n_queries * W * 8, hipMemcpyDeviceToHost, st));
+    if (counts) TXQ_HIP(hipMemcpyAsync(counts, d_cnt, n_queries * W * 64 * 4, hipMemcpyDeviceToHost, st));
+    TXQ_HIP(hipStreamSynchronize(st));
     return TXQ_OK;
 }
 

@@ -1,0 +1,398 @@
+// Threshold membership of value sets on gfx950 (txq_count / txq_count_device): seqan::hibf
+// membership_agent::membership_for(values, threshold) on an HIBF, counting_agent::bulk_count plus a threshold on a flat IBF.
+// The reference only ever asks for one value at threshold 1 (include/index_hibf.h:142-147); this is the general query.
+//
+// Query q owns values [offsets[q], offsets[q+1]) and a threshold t_q.  count[q][b] = how many of its values have bit b in
+// bulk_contains; hit[q][b] = count[q][b] >= t_q.  On an HIBF the count of a technical bin steers the descent exactly as
+// Hibf::descend walks it (oracle/txo_ibf.hpp), with counts in place of one bit: runs of technical bins of one user bin are
+// summed, a merged bin is visited when its count reaches t_q, a run whose sum reaches t_q is a hit.
+//
+// Mapping to the machine:
+//   * the row gather is the probe's (txq_probe.hip): LPK lanes x 16-byte loads per value, LPK = pow2 >= the row's 16-byte
+//     chunks (<= 64; wider rows are cut into column tiles of 64 chunks), 64 / LPK values per step, two steps in flight;
+//   * every set bit of a lane's ANDed 128 bits is one LDS atomic add to the workgroup's u32 counters (chunk c, bin b at
+//     c * 129 + b: lanes of different chunks hit different banks; lanes of one chunk in different values may add to the same
+//     counter, which the LDS serialises).  Bit-sliced counters in VGPRs were measured and dropped: on
+//     300-value queries their flushes cost more than the atomics they save;
+//   * at the end of a query the counters are thresholded and written once per (query, word): a hit word by ballot, and the
+//     64 u32 counts of the word as one coalesced 256-byte store.  No per-value mask is written; bytes per value h*W*8 + 8.
+// Flat IBF: the value array is cut into units of `seg` values (seg_len); a unit starts at a query boundary unless the query
+// is longer than `seg`, so a short query is counted by ONE workgroup (four waves that share its LDS counters) and written
+// directly, and a long one (10^6 values) is spread over many workgroups that add their partial counts to a per-query row of
+// u32 accumulators (one global atomic per non-zero bin and workgroup); count_finish_kernel thresholds those rows and answers
+// the empty queries.
+// HIBF: level-synchronous work items (query, IBF) as in hibf_level_kernel; one wave counts all values of the query on the
+// IBF, walks its technical bins (one lane per bin; a run's last lane sums the run), writes the user bins of this shard's
+// columns and appends (query, child) for merged bins that pass.  Each level reads its item count from HBM: no host
+// synchronisation inside a call.
+#include "txq_internal.hpp"
+#include <algorithm>
+
+namespace txq {
+
+typedef uint32_t cx4 __attribute__((ext_vector_type(4)));
+
+static constexpr uint32_t kLdsPitch = 129;      // u32 counters of chunk c at lds[c * 129 + b], b < 128
+static constexpr uint32_t kTileChunks = 64;     // 16-byte chunks per column tile (8192 bins)
+static constexpr uint64_t kSegMin = 512;        // values per unit of the flat kernel, at least ...
+static constexpr uint64_t kTargetUnits = 8192;  // ... and about this many units per call
+static constexpr int kFlatWaves = 4;            // waves of a flat workgroup: they share one unit and its LDS counters
+
+__device__ __forceinline__ uint64_t seg_len(uint64_t n) { return max(kSegMin, (n + kTargetUnits - 1) / kTargetUnits); }
+
+// the query that holds value index x (offsets[0] <= x < offsets[nq]): the last q with offsets[q] <= x < offsets[q+1]
+__device__ __forceinline__ uint32_t query_of(const uint64_t* off, uint32_t nq, uint64_t x) {
+    uint32_t lo = 1, hi = nq;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (off[mid] > x) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo - 1;
+}
+
+// where the unit that nominally starts at x really starts: x, unless x falls inside a query of at most `seg` values (that
+// query is left whole to the unit before)
+__device__ __forceinline__ uint64_t unit_start(const uint64_t* off, uint32_t nq, uint64_t end, uint64_t seg, uint64_t x) {
+    if (x >= end) return end;
+    const uint32_t q = query_of(off, nq, x);
+    const uint64_t a = off[q], b = off[q + 1];
+    return a == x || b - a > seg ? x : b;
+}
+
+struct CountOut {
+    const uint64_t* values;
+    const uint64_t* offsets;  // nq + 1
+    const uint32_t* thr;      // nq
+    uint64_t* hits;           // [nq][W]
+    uint32_t* counts;         // [nq][64 W] or null
+    uint32_t* acc;            // flat: long queries' accumulators [nq][64 W] (== counts when counts are asked for)
+    uint64_t user_bins;       // bits of a full mask (t = 0 selects only these)
+    uint32_t nq, W, word0;
+};
+
+// Count values [lo, hi) on the column tile of chunks [c0, c0 + 2^lpk_log2) of IBF f into the workgroup's LDS counters: wave
+// `wave` of `n_waves` takes every n_waves-th pair of steps.  H: hash functions loaded per value (an IBF with fewer repeats its
+// last row).  lo, hi are workgroup-uniform.
+template <int H>
+__device__ __forceinline__ void count_values(const IbfDev& f, uint32_t lpk_log2, uint32_t c0, uint32_t chunks, const uint64_t* __restrict__ values,
+                                             uint64_t lo, uint64_t hi, uint32_t* lds, uint32_t wave = 0, uint32_t n_waves = 1) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t sub = lane & ((1u << lpk_log2) - 1u), grp = lane >> lpk_log2, kps = 64u >> lpk_log2;
+    const uint32_t c = c0 + sub;
+    const bool mine = c < chunks;
+    const bool w1 = f.stride == 1;  // rows of one word: 8-byte loads
+    uint32_t* cnt = lds + sub * kLdsPitch;
+    for (uint64_t i0 = lo + (uint64_t)wave * 2u * kps; i0 < hi; i0 += (uint64_t)n_waves * 2u * kps) {
+        cx4 x[2][H];
+        bool ok[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const uint64_t i = i0 + u * kps + grp;
+            ok[u] = i < hi && mine;
+            const uint64_t v = i < hi ? values[i] : 0;
+            uint64_t row = 0;
+#pragma unroll
+            for (int j = 0; j < H; ++j) {
+                if (j == 0 || (uint32_t)j < f.hash_funs) row = hash_row(v, kSeeds[j], f.hash_shift, f.bin_size);
+                const uint64_t* p = f.words + row * f.stride + 2u * c;
+                if (!ok[u]) x[u][j] = cx4{0u, 0u, 0u, 0u};
+                else if (w1) {
+                    const uint64_t w = *p;
+                    x[u][j] = cx4{(uint32_t)w, (uint32_t)(w >> 32), 0u, 0u};
+                } else x[u][j] = *reinterpret_cast<const cx4*>(p);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            cx4 a = x[u][0];
+#pragma unroll
+            for (int j = 1; j < H; ++j) a &= x[u][j];
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                uint32_t m = a[d];
+                while (m) {
+                    atomicAdd(cnt + d * 32 + (uint32_t)__builtin_ctz(m), 1u);
+                    m &= m - 1u;
+                }
+            }
+        }
+    }
+}
+
+// ---- flat IBF -----------------------------------------------------------------------------------------------------------
+
+// Units of `seg` values (grid-stride over units x column tiles), kFlatWaves waves per unit.  Dynamic LDS: min(chunks, 64) * 129 u32.
+template <int H>
+__global__ __launch_bounds__(64 * kFlatWaves) void count_flat_kernel(IbfDev f, CountOut o, uint32_t lpk_log2, uint32_t n_tiles) {
+    extern __shared__ uint32_t lds[];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t chunks = f.stride == 1 ? 1u : f.stride >> 1;
+    const uint32_t tile = 1u << lpk_log2;
+    for (uint32_t i = threadIdx.x; i < (chunks < tile ? chunks : tile) * kLdsPitch; i += blockDim.x) lds[i] = 0;
+    __syncthreads();
+    const uint64_t base = o.offsets[0], end = o.offsets[o.nq];
+    if (end <= base) return;
+    const uint64_t seg = seg_len(end - base), n_units = (end - base + seg - 1) / seg;
+    const size_t W = o.W;
+    for (uint64_t work = blockIdx.x; work < n_units * n_tiles; work += gridDim.x) {
+        const uint64_t u = work / n_tiles;
+        const uint32_t c0 = (uint32_t)(work % n_tiles) << lpk_log2;
+        const uint32_t tcn = chunks - c0 < tile ? chunks - c0 : tile;  // chunks of this tile
+        const uint64_t lo = unit_start(o.offsets, o.nq, end, seg, base + u * seg);
+        const uint64_t hi = u + 1 == n_units ? end : unit_start(o.offsets, o.nq, end, seg, base + (u + 1) * seg);
+        if (lo >= hi) continue;
+        uint32_t q = query_of(o.offsets, o.nq, lo);
+        uint64_t pos = lo;
+        while (pos < hi) {
+            const uint64_t qb = o.offsets[q], qe = o.offsets[q + 1];
+            const uint64_t stop = qe < hi ? qe : hi;
+            count_values<H>(f, lpk_log2, c0, chunks, o.values, pos, stop, lds, wave, kFlatWaves);
+            __syncthreads();
+            const bool whole = qe - qb <= seg;  // (then the whole query lies in this unit)
+            const uint32_t t = o.thr[q];
+            for (uint32_t wl = wave; wl < 2u * tcn; wl += kFlatWaves) {
+                const uint32_t w = 2u * c0 + wl;
+                if (w >= o.W) break;
+                const uint32_t at = (wl >> 1) * kLdsPitch + (wl & 1u) * 64u + lane;
+                const uint32_t n = lds[at];
+                lds[at] = 0;
+                const size_t ci = ((size_t)q * W + w) * 64 + lane;
+                if (whole) {
+                    const bool valid = ((uint64_t)(o.word0 + w) << 6) + lane < o.user_bins;
+                    const uint64_t hit = __ballot(valid && n >= t);
+                    if (lane == 0) o.hits[(size_t)q * W + w] = hit;
+                    if (o.counts) o.counts[ci] = n;
+                } else if (n) {
+                    atomicAdd(o.acc + ci, n);
+                }
+            }
+            __syncthreads();
+            pos = stop;
+            if (pos < hi) {
+                ++q;
+                while (o.offsets[q + 1] <= pos) ++q;  // (empty queries: count_finish_kernel answers them)
+            }
+        }
+    }
+}
+
+// Zero the accumulator rows of the queries longer than a unit (before count_flat_kernel adds to them).
+__global__ __launch_bounds__(64) void count_zero_long_kernel(CountOut o) {
+    const uint64_t base = o.offsets[0], end = o.offsets[o.nq];
+    if (end <= base) return;
+    const uint64_t seg = seg_len(end - base);
+    const size_t row = (size_t)o.W * 64;
+    for (uint32_t q = blockIdx.x; q < o.nq; q += gridDim.x)
+        if (o.offsets[q + 1] - o.offsets[q] > seg)
+            for (size_t i = threadIdx.x; i < row; i += 64) o.acc[(size_t)q * row + i] = 0;
+}
+
+// Answer the queries count_flat_kernel did not write: empty ones (count 0) and long ones (from their accumulators).
+__global__ __launch_bounds__(64) void count_finish_kernel(CountOut o) {
+    const uint32_t lane = threadIdx.x;
+    const uint64_t base = o.offsets[0], end = o.offsets[o.nq];
+    const uint64_t seg = end > base ? seg_len(end - base) : 0;
+    const size_t W = o.W;
+    for (uint32_t q = blockIdx.x; q < o.nq; q += gridDim.x) {
+        const uint64_t len = o.offsets[q + 1] - o.offsets[q];
+        if (len && len <= seg) continue;
+        const uint32_t t = o.thr[q];
+        for (uint32_t w = 0; w < o.W; ++w) {
+            const size_t ci = ((size_t)q * W + w) * 64 + lane;
+            const uint32_t n = len ? o.acc[ci] : 0u;
+            const bool valid = ((uint64_t)(o.word0 + w) << 6) + lane < o.user_bins;
+            const uint64_t hit = __ballot(valid && n >= t);
+            if (lane == 0) o.hits[(size_t)q * W + w] = hit;
+            if (o.counts && !len) o.counts[ci] = 0;  // (a long query's counts are its accumulators: acc == counts)
+        }
+    }
+}
+
+// ---- HIBF ---------------------------------------------------------------------------------------------------------------
+
+struct HibfCountView {
+    const IbfDev* ibf;
+    const uint64_t* next;
+    const uint64_t* tb_user;
+    const uint64_t* map_off;
+    const uint64_t* descend;     // merged bins whose sub-tree holds user bins of this shard's columns
+    const uint64_t* merged_off;
+};
+
+// One level: work item (query, IBF) per wave.  Level 0 (in == null): (q, root) for q < n_level0.  Every IBF has at most
+// 64 chunks (checked at the call), so its whole row of counters is in LDS: max chunks * 129 u32.
+template <int H>
+__global__ __launch_bounds__(64) void count_hibf_level_kernel(HibfCountView t, CountOut o, const WorkItem* __restrict__ in,
+                                                              const uint32_t* __restrict__ in_count, uint32_t in_cap, uint32_t n_level0,
+                                                              WorkItem* __restrict__ out, uint32_t* __restrict__ out_count, uint32_t out_cap,
+                                                              uint32_t lds_words) {
+    extern __shared__ uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t i = lane; i < lds_words; i += 64) lds[i] = 0;
+    __syncthreads();
+    const uint32_t count = in ? min(*in_count, in_cap) : n_level0;
+    const size_t W = o.W;
+    for (uint32_t item = blockIdx.x; item < count; item += gridDim.x) {
+        const uint32_t q = in ? in[item].kmer : item;
+        const uint32_t id = in ? in[item].ibf : 0u;
+        const IbfDev f = t.ibf[id];
+        const uint64_t off = t.map_off[id], moff = t.merged_off[id];
+        const uint32_t chunks = f.stride == 1 ? 1u : f.stride >> 1;
+        uint32_t lpk_log2 = 0;
+        while ((1u << lpk_log2) < chunks) ++lpk_log2;
+        count_values<H>(f, lpk_log2, 0, chunks, o.values, o.offsets[q], o.offsets[q + 1], lds);
+        __syncthreads();
+        const uint32_t thr = o.thr[q];
+        for (uint32_t b0 = 0; b0 < f.bins; b0 += 64) {
+            const uint32_t tb = b0 + lane;
+            const bool live = tb < f.bins;
+            const uint32_t n = live ? lds[(tb >> 7) * kLdsPitch + (tb & 127u)] : 0u;
+            const uint64_t ub = live ? t.tb_user[off + tb] : 0;
+            const bool merged = live && ub == TXQ_MERGED_BIN;
+            const bool kid = merged && n >= thr && ((t.descend[moff + (tb >> 6)] >> (tb & 63u)) & 1ULL);
+            const uint64_t kids = __ballot(kid);
+            if (kids) {  // (query, child) -> next level, one atomic per wave and 64 bins
+                uint32_t at = 0;
+                if (lane == 0) at = atomicAdd(out_count, (uint32_t)__builtin_popcountll(kids));
+                at = __shfl(at, 0) + (uint32_t)__builtin_popcountll(kids & ((1ULL << lane) - 1ULL));
+                if (kid && at < out_cap) out[at] = WorkItem{q, (uint32_t)t.next[off + tb]};
+            }
+            if (live && !merged && (tb + 1 == f.bins || t.tb_user[off + tb + 1] != ub)) {  // the last technical bin of a user bin's run
+                uint32_t sum = n;
+                for (uint32_t s = tb; s > 0 && t.tb_user[off + s - 1] == ub; --s) sum += lds[((s - 1) >> 7) * kLdsPitch + ((s - 1) & 127u)];
+                const uint64_t w = ub >> 6;
+                if (ub < o.user_bins && w >= o.word0 && w < (uint64_t)o.word0 + o.W) {
+                    const size_t wl = (size_t)(w - o.word0);
+                    // (a user bin whose parts are not adjacent has several runs: a hit if any passes, its count the largest)
+                    if (o.counts) atomicMax(o.counts + ((size_t)q * W + wl) * 64 + (ub & 63), sum);
+                    if (sum >= thr) atomicOr((unsigned long long*)(o.hits + (size_t)q * W + wl), 1ULL << (ub & 63));
+                }
+            }
+        }
+        __syncthreads();
+        for (uint32_t i = lane; i < chunks * kLdsPitch; i += 64) lds[i] = 0;
+        __syncthreads();
+    }
+}
+
+// ---- launchers ----------------------------------------------------------------------------------------------------------
+
+#define TXQ_HIP(call)                                        \
+    do {                                                     \
+        hipError_t e_ = (call);                              \
+        if (e_ != hipSuccess) return fail_hip(e_, #call);    \
+    } while (0)
+
+static constexpr unsigned kCountGrid = 4096;  // waves of a call (persistent: the work is only known on the device)
+
+#define TXQ_COUNT_H_SWITCH(H_, LAUNCH)                      \
+    switch (H_) {                                          \
+        case 1: LAUNCH(1); break;                          \
+        case 2: LAUNCH(2); break;                          \
+        case 3: LAUNCH(3); break;                          \
+        case 4: LAUNCH(4); break;                          \
+        case 5: LAUNCH(5); break;                          \
+        default: return fail(TXQ_ERR_ARG, "hash_funs outside 1..5"); \
+    }
+
+static int count_flat(Index& ix, CountOut o, hipStream_t s) {
+    const IbfDev& f = ix.ibf[0];
+    const uint32_t chunks = f.stride == 1 ? 1u : f.stride >> 1;
+    uint32_t lpk_log2 = 0;
+    while ((1u << lpk_log2) < std::min(chunks, kTileChunks)) ++lpk_log2;
+    const uint32_t n_tiles = (chunks + kTileChunks - 1) / kTileChunks;
+    const size_t lds = (size_t)std::min(chunks, 1u << lpk_log2) * kLdsPitch * 4;
+    const size_t row = (size_t)o.W * 64;
+    // long queries add their partial counts to a row of u32 per query: the caller's counts, or scratch of a bounded number
+    // of queries at a time
+    size_t per_call = o.nq;
+    if (!o.counts) per_call = std::max<size_t>(1, std::min<size_t>(o.nq, ((size_t)256 << 20) / (row * 4)));
+    if (!o.counts)
+        if (int rc = ensure((void**)&ix.scratch_count_acc, &ix.cap_count_acc, per_call * row * 4)) return rc;
+    for (size_t q0 = 0; q0 < o.nq; q0 += per_call) {
+        CountOut c = o;
+        c.nq = (uint32_t)std::min(per_call, (size_t)o.nq - q0);
+        c.offsets = o.offsets + q0;
+        c.thr = o.thr + q0;
+        c.hits = o.hits + q0 * o.W;
+        c.counts = o.counts ? o.counts + q0 * row : nullptr;
+        c.acc = o.counts ? c.counts : ix.scratch_count_acc;
+        const unsigned qgrid = (unsigned)std::min<size_t>(c.nq, kCountGrid);
+        count_zero_long_kernel<<<qgrid, 64, 0, s>>>(c);
+#define TXQ_FLAT(H) count_flat_kernel<H><<<kCountGrid, 64 * kFlatWaves, lds, s>>>(f, c, lpk_log2, n_tiles)
+        TXQ_COUNT_H_SWITCH(f.hash_funs, TXQ_FLAT)
+#undef TXQ_FLAT
+        count_finish_kernel<<<qgrid, 64, 0, s>>>(c);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail_hip(e, "count kernel launch");
+    }
+    return TXQ_OK;
+}
+
+static int count_hibf(Index& ix, CountOut o, hipStream_t s) {
+    uint32_t max_chunks = 1, h_max = 1;
+    for (const IbfDev& f : ix.ibf) {
+        const uint32_t chunks = f.stride == 1 ? 1u : f.stride >> 1;
+        if (chunks > kTileChunks) return fail(TXQ_ERR_ARG, "txq_count: an IBF of the tree has more than %u technical bins", kTileChunks * 128);
+        max_chunks = std::max(max_chunks, chunks);
+        h_max = std::max(h_max, f.hash_funs);
+    }
+    const size_t row = (size_t)o.W * 64;
+    TXQ_HIP(hipMemsetAsync(o.hits, 0, (size_t)o.nq * o.W * 8, s));
+    if (o.counts) TXQ_HIP(hipMemsetAsync(o.counts, 0, (size_t)o.nq * row * 4, s));
+    // a (query, IBF) pair occurs at most once: level l holds at most chunk * (IBFs on level l) items
+    const size_t cap_items = (size_t)1 << 24;
+    size_t chunk = std::max<size_t>(1, cap_items / ix.max_level_width);
+    chunk = std::min<size_t>(chunk, o.nq);
+    const size_t cap = chunk * ix.max_level_width;
+    if (ix.depth > 1)
+        for (int i = 0; i < 2; ++i)
+            if (int rc = ensure((void**)&ix.frontier[i], &ix.cap_frontier[i], cap * sizeof(WorkItem))) return rc;
+    if (int rc = ensure((void**)&ix.d_counts, &ix.cap_counts, ((size_t)ix.depth + 2) * 4)) return rc;
+    const HibfCountView t{ix.d_ibf, ix.d_next, ix.d_tb_user, ix.d_map_off, ix.d_descend, ix.d_merged_off};
+    const uint32_t lds_words = max_chunks * kLdsPitch;
+    for (size_t q0 = 0; q0 < o.nq; q0 += chunk) {
+        CountOut c = o;
+        c.nq = (uint32_t)std::min(chunk, (size_t)o.nq - q0);
+        c.offsets = o.offsets + q0;
+        c.thr = o.thr + q0;
+        c.hits = o.hits + q0 * o.W;
+        c.counts = o.counts ? o.counts + q0 * row : nullptr;
+        TXQ_HIP(hipMemsetAsync(ix.d_counts, 0, ((size_t)ix.depth + 2) * 4, s));
+        for (uint32_t lvl = 0; lvl < ix.depth; ++lvl) {
+            const WorkItem* in = lvl ? ix.frontier[(lvl - 1) & 1] : nullptr;
+            const uint32_t* in_count = lvl ? ix.d_counts + (lvl - 1) : nullptr;
+            WorkItem* out = ix.frontier[lvl & 1];
+            const uint32_t out_cap = ix.depth > 1 && lvl + 1 < ix.depth ? (uint32_t)cap : 0u;
+            const unsigned grid = lvl ? kCountGrid : (unsigned)std::min<size_t>(c.nq, kCountGrid);
+#define TXQ_LEVEL(H)                                                                                                  \
+            count_hibf_level_kernel<H><<<grid, 64, lds_words * 4, s>>>(t, c, in, in_count, (uint32_t)cap, c.nq, out, ix.d_counts + lvl, \
+                                                                       out_cap, lds_words)
+            TXQ_COUNT_H_SWITCH(h_max, TXQ_LEVEL)
+#undef TXQ_LEVEL
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return fail_hip(e, "hibf count kernel launch");
+        }
+    }
+    return TXQ_OK;
+}
+
+int count_device(Index& ix, const uint64_t* d_values, const uint64_t* d_offsets, size_t n_queries, const uint32_t* d_thr,
+                 uint64_t* d_hits, uint32_t* d_counts, hipStream_t s) {
+    if (n_queries == 0 || ix.shard_words == 0) return TXQ_OK;
+    CountOut o{};
+    o.values = d_values;
+    o.offsets = d_offsets;
+    o.thr = d_thr;
+    o.hits = d_hits;
+    o.counts = d_counts;
+    o.acc = d_counts;
+    o.user_bins = ix.user_bins;
+    o.nq = (uint32_t)n_queries;
+    o.W = (uint32_t)ix.shard_words;
+    o.word0 = (uint32_t)ix.shard_word0;
+    return ix.is_hibf ? count_hibf(ix, o, s) : count_flat(ix, o, s);
+}
+
+}  // namespace txq

@@ -195,6 +195,8 @@ struct Index {
     uint64_t* host_final = nullptr; size_t cap_host_final = 0;  // pinned: a session's final masks are gathered straight into host memory
     uint64_t* scratch_dense_kmers = nullptr; size_t cap_dense_kmers = 0;  // dense steps on an HIBF: the pairs' k-mers ...
     uint64_t* scratch_dense_masks = nullptr; size_t cap_dense_masks = 0;  // ... and their descended masks
+    uint32_t* scratch_count_acc = nullptr; size_t cap_count_acc = 0;      // txq_count on a flat index: long queries' partial counts
+    unsigned char* scratch_count_io = nullptr; size_t cap_count_io = 0;   // txq_count (host buffers): the call's inputs and results
     // A flat index's masks of ALL k-mers, M[v] at kmer_table + v * shard_words for every packed value v < 2^(bits * k) (txq_exec.hip
     // ensure_kmer_table): where that fits TXQ_KMER_TABLE_MB, a dense step reads ONE row per k-mer instead of gathering hash_funs.
     uint64_t* kmer_table = nullptr; uint32_t kmer_table_bits = 0;  // bits = bits per residue * k of the table that is built
@@ -391,6 +393,10 @@ int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, ui
 int hibf_probe_layout_order(Index& ix, const uint64_t* d_kmers, size_t n, uint64_t* d_rows, hipStream_t s);
 // final masks of a layout-order session -> user-bin order: d_out[n][shard_words] (zeroed here)
 int hibf_layout_to_user(const Index& ix, const uint64_t* d_rows, size_t n, uint64_t* d_out, hipStream_t s);
+
+// txq_count.hip: threshold membership of n_queries value sets (include/txq.h txq_count_device; arguments checked by the caller)
+int count_device(Index& ix, const uint64_t* d_values, const uint64_t* d_offsets, size_t n_queries, const uint32_t* d_thr,
+                 uint64_t* d_hits, uint32_t* d_counts, hipStream_t s);
 
 // txq_exec.hip
 int run_programs(Index& ix, const void* blob, size_t blob_bytes, size_t n_programs, uint64_t* d_final, hipStream_t s);
