@@ -165,6 +165,23 @@ int64_t txh_layout_ibf(const txh_layout* l, uint64_t ibf, uint64_t* bin_size, ui
 /* the layout order (user bin at each sorted position); returns B */
 int64_t txh_layout_order(const txh_layout* l, uint64_t* order, size_t cap);
 void txh_layout_free(txh_layout* l);
+/* The same over a given order: order[user_bins] must be a permutation of 0 .. B-1 (anything else is refused), and
+ * unions[s * window + L - 1] is the union of the bins order[s .. s+L-1].  With the layout order of counts this is
+ * txh_hibf_layout, field for field.  txh_layout_order returns the order given. */
+int txh_hibf_layout_ordered(const double* counts, uint64_t user_bins, const uint64_t* order, const double* unions, uint64_t window,
+                            const txh_layout_params* params, txh_layout** out);
+
+/* ---- similarity rearrangement of the user bins before the layout (host/layout.hpp; `tetrex index --layout sized --rearrange`) ----
+ * Intervals of the layout order: an interval starts at sorted position s and takes the following positions e while
+ * counts[order[e]] >= ratio * counts[order[s]] (ratio in (0, 1]) and while it is shorter than max_len (1 .. 4096; 0: 4096).
+ * starts receives the first sorted position of every interval, ascending; returns their number (nothing written past cap). */
+#define TXH_REARRANGE_MAX_LEN 4096
+int64_t txh_rearrange_intervals(const double* counts, uint64_t user_bins, double ratio, uint64_t max_len, uint64_t* starts, size_t cap);
+/* The chain inside one interval of n bins: counts[n] by position in the interval, unions[n x n] their pairwise union
+ * estimates.  Position 0 stays; then the bin not yet placed with the largest J = (c_last + c_j - u[last][j]) / u[last][j]
+ * (in double, in this order; u == 0: J = 0; ties: the smaller position) follows the bin placed last.  n <= 2: the identity.
+ * chain[n] receives the positions in their new order. */
+int txh_rearrange_chain(const double* counts, const double* unions, uint64_t n, uint64_t* chain);
 
 /* The whole `tetrex index` build (FASTA files -> index image, bits set on the GPU), without the CLI.  Exported by
  * libtetrex_query.so (it needs libtxq.so); errors via txe_last_error().  The handle is an ordinary txh_index
@@ -178,6 +195,7 @@ typedef struct {
     int flavour;         /* 0 HIBF, uniform layout (default); 1 HIBF, sized layout (--layout sized); 2 flat IBF (-i) */
     uint64_t tmax;       /* --tmax (sized only; 0: the default) */
     int device;          /* -D */
+    double rearrange_ratio; /* --rearrange [--rearrange-ratio R] (sized only): 0 off (the default), else the ratio in (0, 1] */
 } txh_build_options;
 int txh_index_build(const char* const* paths, size_t n, const txh_build_options* options, txh_index** out);
 

@@ -220,6 +220,11 @@ int txq_sketch_device(const uint64_t* d_values, size_t n_values, const uint64_t*
  * each bin's own estimate. */
 int txq_union_estimates_device(const uint8_t* d_registers, const uint32_t* d_order, uint64_t n_bins, uint64_t window,
                                double* d_estimates, void* stream);
+/* Pairwise union estimates (`tetrex index --layout sized --rearrange`, host/layout.hpp): d_estimates[i * n + j] = the
+ * estimate of the union of bins d_ids[i] and d_ids[j] (bin ids into d_registers; they may repeat), by the estimator above, so
+ * the diagonal holds each bin's own estimate and the matrix is symmetric.  n = 0 is a no-op; null pointers and n > 4096
+ * (one table: 4096^2 doubles at most) are TXQ_ERR_ARG. */
+int txq_pair_unions_device(const uint8_t* d_registers, const uint32_t* d_ids, uint64_t n, double* d_estimates, void* stream);
 /* Insertion into every IBF of a tree.  d_ibfs[n_ibf]: the IBFs' shapes, each .words a DEVICE pointer to its zeroed
  * [bin_size][bin_words] matrix.  User bin b's path from the root is d_path[3 * e .. 3 * e + 2] = (ibf, first technical bin,
  * parts) for e in [d_path_offsets[b], d_path_offsets[b+1]); only the leaf entry may have parts > 1.  Each value sets, in each

@@ -22,7 +22,7 @@ SYMBOLS = [
     "txq_init", "txq_shutdown", "txq_last_error", "txq_device_count",
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
-    "txq_sketch_device", "txq_union_estimates_device", "txq_tree_insert_device",
+    "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
     "txq_malloc", "txq_free", "txq_memcpy_h2d", "txq_memcpy_d2h", "txq_synchronize", "txq_host_alloc", "txq_host_free",
 ]
@@ -512,3 +512,26 @@ def union_estimates(registers, order, window):
         for b in (dr, do, de):
             b.free()
 
+
+
+def pair_unions(registers, ids):
+    """estimates[i, j] = estimate of the union of bins ids[i] and ids[j] (txq_pair_unions_device): (n, n) float64."""
+    L = lib()
+    L.txq_pair_unions_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    regs = np.ascontiguousarray(registers, dtype=np.uint8)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    n = int(ids.size)
+    if n and (regs.ndim != 2 or regs.shape[1] != HLL_REGISTERS or int(ids.max()) >= regs.shape[0]):
+        raise ValueError("registers must be (B, %d) and every id below B" % HLL_REGISTERS)
+    if n == 0:
+        check(L.txq_pair_unions_device(None, None, 0, None, None))
+        return np.zeros((0, 0), dtype=np.float64)
+    dr, di = DeviceBuffer.from_numpy(regs), DeviceBuffer.from_numpy(ids)
+    de = DeviceBuffer(min(n, 4096) ** 2 * 8)  # n > 4096 is refused by the library
+    try:
+        check(L.txq_pair_unions_device(dr.ptr, di.ptr, n, de.ptr, None))
+        check(L.txq_synchronize())
+        return de.to_numpy(np.float64, (n, n))
+    finally:
+        for b in (dr, di, de):
+            b.free()

@@ -409,6 +409,9 @@ HibfImage build_sized_hibf(const std::vector<std::vector<uint64_t>>& values, con
     lp.hash_count = opt.hash_count;
     const uint64_t W = union_window(B, lp.tmax);
     std::vector<double> counts(B), unions(B * W);
+    std::vector<uint64_t> final_order;
+    uint64_t n_intervals = 0, longest_interval = 0;
+    double rearrange_ms = 0;
     {
         std::vector<uint32_t> order(B);
         for (uint64_t b = 0; b < B; ++b) order[b] = (uint32_t)b;
@@ -416,14 +419,42 @@ HibfImage build_sized_hibf(const std::vector<std::vector<uint64_t>>& values, con
         txq_check(txq_memcpy_h2d(d_order.p, order.data(), B * 4), "h2d order");
         txq_check(txq_union_estimates_device((const uint8_t*)d_regs.p, (const uint32_t*)d_order.p, B, 1, (double*)d_est.p, nullptr), "txq_union_estimates_device");
         txq_check(txq_memcpy_d2h(counts.data(), d_est.p, B * 8), "d2h estimates");
-        const std::vector<uint64_t> sorted = layout_order(counts.data(), B);
-        for (uint64_t s = 0; s < B; ++s) order[s] = (uint32_t)sorted[s];
+        final_order = layout_order(counts.data(), B);
+        if (opt.rearrange_ratio != 0) {
+            // inside each interval of the sorted order: the pairwise unions from the device, the chain on the host
+            const auto r0 = clock::now();
+            const std::vector<uint64_t> sorted = final_order;
+            const std::vector<uint64_t> starts = rearrange_intervals(counts.data(), sorted.data(), B, opt.rearrange_ratio);
+            n_intervals = starts.size();
+            for (uint64_t i = 0; i < n_intervals; ++i)
+                longest_interval = std::max(longest_interval, (i + 1 < n_intervals ? starts[i + 1] : B) - starts[i]);
+            if (longest_interval >= 3) {
+                DevBuf d_ids(longest_interval * 4), d_pairs(longest_interval * longest_interval * 8);
+                std::vector<uint32_t> ids;
+                std::vector<double> pairs, c;
+                for (uint64_t i = 0; i < n_intervals; ++i) {
+                    const uint64_t s = starts[i], n = (i + 1 < n_intervals ? starts[i + 1] : B) - s;
+                    if (n < 3) continue;
+                    ids.resize(n);
+                    c.resize(n);
+                    pairs.resize(n * n);
+                    for (uint64_t j = 0; j < n; ++j) { ids[j] = (uint32_t)sorted[s + j]; c[j] = counts[sorted[s + j]]; }
+                    txq_check(txq_memcpy_h2d(d_ids.p, ids.data(), n * 4), "h2d interval");
+                    txq_check(txq_pair_unions_device((const uint8_t*)d_regs.p, (const uint32_t*)d_ids.p, n, (double*)d_pairs.p, nullptr), "txq_pair_unions_device");
+                    txq_check(txq_memcpy_d2h(pairs.data(), d_pairs.p, n * n * 8), "d2h pair unions");
+                    const std::vector<uint64_t> chain = rearrange_chain(c.data(), pairs.data(), n);
+                    for (uint64_t j = 0; j < n; ++j) final_order[s + j] = sorted[s + chain[j]];
+                }
+            }
+            rearrange_ms = ms(r0, clock::now());
+        }
+        for (uint64_t s = 0; s < B; ++s) order[s] = (uint32_t)final_order[s];
         txq_check(txq_memcpy_h2d(d_order.p, order.data(), B * 4), "h2d order");
         txq_check(txq_union_estimates_device((const uint8_t*)d_regs.p, (const uint32_t*)d_order.p, B, W, (double*)d_est.p, nullptr), "txq_union_estimates_device");
         txq_check(txq_memcpy_d2h(unions.data(), d_est.p, B * W * 8), "d2h unions");
     }
     const auto t2 = clock::now();
-    const HibfLayout layout = hibf_layout(counts.data(), B, unions.data(), W, lp);
+    const HibfLayout layout = hibf_layout_ordered(counts.data(), B, final_order.data(), unions.data(), W, lp);
     const auto paths = layout_paths(layout, B);
     const auto t3 = clock::now();
     // the tree on the device
@@ -470,8 +501,14 @@ HibfImage build_sized_hibf(const std::vector<std::vector<uint64_t>>& values, con
         std::fprintf(stderr, "[tetrex] sized layout: %llu user bins, %llu IBFs, %llu bits, t_max %llu, window %llu, %llu values in %llu chunk(s)\n",
                      (unsigned long long)B, (unsigned long long)n_ibf, (unsigned long long)bits, (unsigned long long)lp.tmax,
                      (unsigned long long)W, (unsigned long long)total, (unsigned long long)n_chunks);
-        std::fprintf(stderr, "[tetrex] build ms: upload+sketch %.3f union %.3f layout %.3f insert %.3f download %.3f\n", ms(t0, t1),
-                     ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, t5));
+        if (opt.rearrange_ratio != 0) {
+            std::fprintf(stderr, "[tetrex] sized layout: rearranged in %llu interval(s), the longest of %llu bins (ratio %g)\n",
+                         (unsigned long long)n_intervals, (unsigned long long)longest_interval, opt.rearrange_ratio);
+            std::fprintf(stderr, "[tetrex] build ms: upload+sketch %.3f union %.3f rearrange %.3f layout %.3f insert %.3f download %.3f\n",
+                         ms(t0, t1), ms(t1, t2) - rearrange_ms, rearrange_ms, ms(t2, t3), ms(t3, t4), ms(t4, t5));
+        } else
+            std::fprintf(stderr, "[tetrex] build ms: upload+sketch %.3f union %.3f layout %.3f insert %.3f download %.3f\n", ms(t0, t1),
+                         ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, t5));
     }
     return h;
 }
@@ -485,6 +522,9 @@ IndexImage build_index(const std::vector<std::string>& bin_files, const BuildOpt
     ensure_device(opt.device);
     if (opt.layout == BuildOptions::kSized && !opt.hibf) throw std::runtime_error("a sized layout is an HIBF layout (not with -i)");
     if (opt.layout == BuildOptions::kSized && (opt.tmax % 64 != 0)) throw std::runtime_error("t_max must be a positive multiple of 64");
+    if (opt.rearrange_ratio != 0 && opt.layout != BuildOptions::kSized) throw std::runtime_error("rearrangement is an option of the sized layout");
+    if (opt.rearrange_ratio != 0 && !(opt.rearrange_ratio > 0 && opt.rearrange_ratio <= 1))
+        throw std::runtime_error("the rearrangement ratio must lie in (0, 1]");
     const auto t_encode = std::chrono::steady_clock::now();
     const KmerEncoder enc(opt.dna ? Molecule::DNA : Molecule::Peptide, opt.k, (Alphabet)opt.reduction);
     std::vector<std::vector<uint64_t>> values(bin_files.size());

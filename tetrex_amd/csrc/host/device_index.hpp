@@ -128,6 +128,9 @@ struct BuildOptions {
     enum Layout { kUniform = 0, kSized = 1 };
     int layout = kUniform;
     uint64_t tmax = 0;
+    // kSized only: before the layout, chain similar bins inside intervals of the sorted order (host/layout.hpp
+    // rearrange_intervals / rearrange_chain, txq_pair_unions_device).  0: off; else the interval ratio in (0, 1].
+    double rearrange_ratio = 0;
 };
 // `tetrex index`: FASTA files -> index image, bits set on the GPU (txq_emplace_device).
 IndexImage build_index(const std::vector<std::string>& bin_files, const BuildOptions& opt, size_t* n_sequences = nullptr);

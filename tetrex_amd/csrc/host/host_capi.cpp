@@ -8,6 +8,8 @@
 #include "matcher.hpp"
 #include "regex_front.hpp"
 
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -369,6 +371,46 @@ int txh_hibf_layout(const double* counts, uint64_t user_bins, const double* unio
         auto l = std::make_unique<txh_layout>();
         l->layout = hibf_layout(counts, user_bins, unions, window, p);
         *out = l.release();
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+
+int txh_hibf_layout_ordered(const double* counts, uint64_t user_bins, const uint64_t* order, const double* unions, uint64_t window,
+                            const txh_layout_params* params, txh_layout** out) {
+    try {
+        if (!out) return fail("null argument");
+        LayoutParams p;
+        if (params) {
+            p.tmax = params->tmax;
+            p.fpr = params->fpr;
+            p.relaxed_fpr = params->relaxed_fpr;
+            p.hash_count = params->hash_count;
+            p.alpha = params->alpha;
+        }
+        auto l = std::make_unique<txh_layout>();
+        l->layout = hibf_layout_ordered(counts, user_bins, order, unions, window, p);
+        *out = l.release();
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+
+int64_t txh_rearrange_intervals(const double* counts, uint64_t user_bins, double ratio, uint64_t max_len, uint64_t* starts, size_t cap) {
+    try {
+        if (user_bins && !counts) return fail("null argument");
+        for (uint64_t b = 0; b < user_bins; ++b)
+            if (!(counts[b] >= 0) || !std::isfinite(counts[b])) return fail("counts must be finite and >= 0");
+        const std::vector<uint64_t> order = layout_order(counts, user_bins);
+        const std::vector<uint64_t> s = rearrange_intervals(counts, order.data(), user_bins, ratio, max_len ? max_len : kRearrangeMaxLen);
+        for (size_t i = 0; i < s.size() && i < cap; ++i) starts[i] = s[i];
+        return (int64_t)s.size();
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+
+int txh_rearrange_chain(const double* counts, const double* unions, uint64_t n, uint64_t* chain) {
+    try {
+        if (n && !chain) return fail("null argument");
+        const std::vector<uint64_t> c = rearrange_chain(counts, unions, n);
+        std::copy(c.begin(), c.end(), chain);
         return 0;
     } catch (const std::exception& e) { return fail(e.what()); }
 }

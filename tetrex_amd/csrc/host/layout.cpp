@@ -148,8 +148,56 @@ struct Ctx {
 
 }  // namespace
 
+std::vector<uint64_t> rearrange_intervals(const double* counts, const uint64_t* order, uint64_t user_bins, double ratio, uint64_t max_len) {
+    if (!(ratio > 0 && ratio <= 1)) throw std::invalid_argument("the rearrangement ratio must lie in (0, 1]");
+    if (max_len < 1 || max_len > kRearrangeMaxLen)
+        throw std::invalid_argument("an interval holds 1 .. " + std::to_string(kRearrangeMaxLen) + " bins at most");
+    if (user_bins && (!counts || !order)) throw std::invalid_argument("null argument");
+    std::vector<uint64_t> starts;
+    for (uint64_t s = 0; s < user_bins;) {
+        starts.push_back(s);
+        const double floor = ratio * counts[order[s]];
+        uint64_t e = s + 1;
+        while (e < user_bins && e - s < max_len && counts[order[e]] >= floor) ++e;
+        s = e;
+    }
+    return starts;
+}
+
+std::vector<uint64_t> rearrange_chain(const double* counts, const double* unions, uint64_t n) {
+    if (n && (!counts || !unions)) throw std::invalid_argument("null argument");
+    std::vector<uint64_t> chain(n);
+    std::iota(chain.begin(), chain.end(), 0);
+    if (n < 3) return chain;
+    std::vector<uint8_t> placed(n, 0);
+    placed[0] = 1;
+    for (uint64_t k = 1; k < n; ++k) {
+        const uint64_t last = chain[k - 1];
+        uint64_t best = n;
+        double best_j = 0;
+        for (uint64_t j = 0; j < n; ++j) {
+            if (placed[j]) continue;
+            const double u = unions[last * n + j];
+            const double jac = u == 0 ? 0.0 : (counts[last] + counts[j] - u) / u;
+            if (best == n || jac > best_j) { best = j; best_j = jac; }  // ascending j: the smaller position keeps a tie
+        }
+        chain[k] = best;
+        placed[best] = 1;
+    }
+    return chain;
+}
+
 HibfLayout hibf_layout(const double* counts, uint64_t user_bins, const double* unions, uint64_t window, const LayoutParams& params) {
     if (user_bins == 0 || !counts || !unions) throw std::invalid_argument("no user bins");
+    for (uint64_t b = 0; b < user_bins; ++b)  // before they are sorted
+        if (!(counts[b] >= 0) || !std::isfinite(counts[b])) throw std::invalid_argument("counts must be finite and >= 0");
+    const std::vector<uint64_t> order = layout_order(counts, user_bins);
+    return hibf_layout_ordered(counts, user_bins, order.data(), unions, window, params);
+}
+
+HibfLayout hibf_layout_ordered(const double* counts, uint64_t user_bins, const uint64_t* order, const double* unions, uint64_t window,
+                               const LayoutParams& params) {
+    if (user_bins == 0 || !counts || !unions || !order) throw std::invalid_argument("no user bins");
     const uint64_t tmax = params.tmax ? params.tmax : default_tmax(user_bins);
     if (tmax % 64) throw std::invalid_argument("t_max must be a multiple of 64");
     if (window != union_window(user_bins, tmax))
@@ -160,10 +208,18 @@ HibfLayout hibf_layout(const double* counts, uint64_t user_bins, const double* u
         throw std::invalid_argument("fpr and relaxed_fpr must lie in (0, 1), hash_count in 1..5, alpha >= 0");
     for (uint64_t b = 0; b < user_bins; ++b)
         if (!(counts[b] >= 0) || !std::isfinite(counts[b])) throw std::invalid_argument("counts must be finite and >= 0");
+    {
+        std::vector<uint8_t> seen(user_bins, 0);
+        for (uint64_t s = 0; s < user_bins; ++s) {
+            if (order[s] >= user_bins || seen[order[s]])
+                throw std::invalid_argument("the order must be a permutation of the user bins 0 .. " + std::to_string(user_bins - 1));
+            seen[order[s]] = 1;
+        }
+    }
     HibfLayout out;
     out.tmax = tmax;
     out.window = window;
-    out.order = layout_order(counts, user_bins);
+    out.order.assign(order, order + user_bins);
     Ctx ctx{counts, unions, window, tmax, &out.order, split_corrections(tmax, params.fpr, params.hash_count), params, &out};
     ctx.p.tmax = tmax;
     ctx.layout(0, user_bins);

@@ -66,6 +66,28 @@ std::vector<uint64_t> layout_order(const double* counts, uint64_t user_bins);
 std::vector<double> split_corrections(uint64_t max_parts, double fpr, unsigned hash_count);
 // counts: by user bin id; unions: user_bins x window (see above).  Throws std::invalid_argument on a bad input.
 HibfLayout hibf_layout(const double* counts, uint64_t user_bins, const double* unions, uint64_t window, const LayoutParams& params);
+// The same over a GIVEN order (a permutation of 0 .. B-1, anything else is refused): unions[s * window + L - 1] is then the
+// union of the bins order[s .. s+L-1].  The DP reads counts[order[pos]] and that table, nothing else, so it never needs the
+// order to be sorted; with layout_order(counts) this is hibf_layout.  HibfLayout::order holds the order used.
+HibfLayout hibf_layout_ordered(const double* counts, uint64_t user_bins, const uint64_t* order, const double* unions, uint64_t window,
+                               const LayoutParams& params);
+
+// Similarity rearrangement (`tetrex index --layout sized --rearrange`): before the layout, user bins that share k-mers are
+// moved next to each other, so that a merged bin (a run of the order, sized by its union) covers bins that overlap.
+// Two pure steps; the pairwise union estimates between them come from the device (include/txq.h txq_pair_unions_device).
+//   intervals: walk the sorted order from position 0; an interval starts at position s and takes the following positions e
+//     while counts[order[e]] >= ratio * counts[order[s]] and while it is shorter than max_len; then the next one starts.
+//     Bins only move inside their interval, so the order stays "large bins first" up to the factor ratio (in (0, 1]).
+//   chain: inside an interval of n bins with pairwise union estimates u[i * n + j] (i, j: positions in the interval), position
+//     0 stays; then, n - 1 times, the bin not yet placed with the largest J = (c_last + c_j - u[last][j]) / u[last][j] to the
+//     bin placed last follows it (u == 0: J = 0; ties: the smaller position).  Intervals of one or two bins are left alone.
+// This is a greedy nearest-neighbour chain, O(n^2), not seqan::hibf's agglomerative clustering.
+constexpr uint64_t kRearrangeMaxLen = 4096;  // one interval's pairwise table: at most 4096^2 doubles (128 MiB)
+// first sorted position of every interval, ascending (interval i ends where i + 1 starts, the last one at B)
+std::vector<uint64_t> rearrange_intervals(const double* counts, const uint64_t* order, uint64_t user_bins, double ratio,
+                                          uint64_t max_len = kRearrangeMaxLen);
+// counts[n]: the interval's estimates by position; returns the chain as positions of the interval
+std::vector<uint64_t> rearrange_chain(const double* counts, const double* unions, uint64_t n);
 // each user bin's path, root first
 std::vector<std::vector<PathStep>> layout_paths(const HibfLayout& layout, uint64_t user_bins);
 

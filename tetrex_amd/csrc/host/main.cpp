@@ -1,7 +1,7 @@
 // `tetrex` command line — product code.  Keeps the reference's surface for the query path:
 //   tetrex query [-d] [-v] [-f] [-c] [-a] [-t N] [-o dest] [-g dibf] <index.ibf> <regex|->
 //     (include/arg_parse.h:57-71, src/main.cpp:36-59, src/query.cpp:477-498)
-//   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] [--layout uniform|sized [--tmax N]] <name> <libs...>
+//   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] [--layout uniform|sized [--tmax N] [--rearrange [--rearrange-ratio R]]] <name> <libs...>
 //     (include/arg_parse.h:10-38, src/index_base.cpp:73-117)
 //   tetrex search [-e E | --threshold F] [--counts] [-o dest] [-v] <index.ibf> <queries.fa[.gz]>
 //     (not in the reference: every FASTA record a query, answered by seqan::hibf membership_for(values, threshold))
@@ -296,7 +296,8 @@ int cmd_query(int argc, char** argv) {
 int cmd_index(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'k', "ksize", true}, {'p', "fpr", true}, {'c', "hash_count", true}, {'t', "threads", true},
                                        {'n', "nucleic_acid", false}, {'i', "ibf", false}, {'r', "reduce", true}, {'D', "device", true},
-                                       {'W', "no-wraparound", false}, {'\0', "layout", true}, {'\0', "tmax", true}};
+                                       {'W', "no-wraparound", false}, {'\0', "layout", true}, {'\0', "tmax", true},
+                                       {'\0', "rearrange", false}, {'\0', "rearrange-ratio", true}};
     Args a;
     try {
         a = parse(argc, argv, 2, spec);
@@ -329,6 +330,17 @@ int cmd_index(int argc, char** argv) {
         if (opt.layout != BuildOptions::kSized) { std::cerr << "[Indexing Parser Error] --tmax needs --layout sized\n"; return 0; }
         if (t.empty() || *end || v == 0 || v % 64) { std::cerr << "[Indexing Parser Error] --tmax must be a positive multiple of 64\n"; return 0; }
         opt.tmax = v;
+    }
+    // --rearrange [--rearrange-ratio R]: similar bins side by side before the sized layout (host/layout.hpp).  The flag takes
+    // no value of its own: an optional one would swallow the index name that follows it.
+    if (a.has("rearrange") && opt.layout != BuildOptions::kSized) { std::cerr << "[Indexing Parser Error] --rearrange needs --layout sized\n"; return 0; }
+    if (a.has("rearrange-ratio") && !a.has("rearrange")) { std::cerr << "[Indexing Parser Error] --rearrange-ratio needs --rearrange\n"; return 0; }
+    if (a.has("rearrange")) {
+        const std::string t = a.get("rearrange-ratio", "0.5");
+        char* end = nullptr;
+        const double v = std::strtod(t.c_str(), &end);
+        if (t.empty() || *end || !(v > 0 && v <= 1)) { std::cerr << "[Indexing Parser Error] --rearrange-ratio must be a number in (0, 1]\n"; return 0; }
+        opt.rearrange_ratio = v;
     }
     if (!opt.dna && opt.k > 12) { std::cerr << "[Indexing Parser Error] Max kmer size for amino acids is 12" << "\n"; return 0; }
     std::vector<std::string> files;

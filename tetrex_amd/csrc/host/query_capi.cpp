@@ -131,6 +131,8 @@ int txh_index_build(const char* const* paths, size_t n, const txh_build_options*
             if (options->tmax && options->flavour != 1) throw std::invalid_argument("tmax is an option of the sized layout");
             opt.tmax = options->tmax;
             opt.device = options->device;
+            if (options->rearrange_ratio != 0 && options->flavour != 1) throw std::invalid_argument("rearrangement is an option of the sized layout");
+            opt.rearrange_ratio = options->rearrange_ratio;
         }
         auto ix = std::make_unique<txh_index>();
         ix->image = build_index(files, opt);

@@ -18,6 +18,11 @@ constexpr uint32_t kSketchSlices = 16;        // workgroups per bin at most ...
 constexpr uint64_t kSketchMinSlice = 16384;   // ... each with at least this many values (small bins: one workgroup)
 constexpr uint32_t kUnionThreads = 256;       // 16 registers per lane
 constexpr uint32_t kRegsPerLane = kRegs / kUnionThreads;
+constexpr uint32_t kPairThreads = 256;        // pair unions: four waves, each with whole bins (64 registers per lane)
+constexpr uint32_t kPairTile = 16;            // a workgroup's tile: 16 x 16 pairs
+constexpr uint32_t kPairRows = kPairTile / (kPairThreads / 64);  // row bins a wave keeps in VGPRs (4 x 16 u32)
+constexpr uint32_t kPairQuads = kRegs / 16 / 64;                 // uint4 per lane and bin (4)
+constexpr uint64_t kPairMaxBins = 4096;
 
 // linear counting m * ln(m / V), V = 0 .. m, filled on the host (one libm for the device and for restatements)
 __constant__ double kLinearCount[kRegs + 1];
@@ -109,6 +114,76 @@ __global__ __launch_bounds__(kUnionThreads) void union_kernel(const uint8_t* __r
             est[s * window + L - 1] = e;
         }
         __syncthreads();
+    }
+}
+
+// Pair unions: one workgroup per 16 x 16 tile of pairs (i, j) with tile column >= tile row; both halves of the matrix are
+// written.  A lane only ever needs its own 64 registers of a bin (uint4 q * 64 + lane, q = 0 .. 3, coalesced), so the tile's
+// 16 row bins live in VGPRs, four per wave, and its 16 column bins are staged once in LDS (64 KiB: two workgroups per
+// CU) where all four waves read them: 256 B of global reads per pair.  Per pair a wave takes the byte-wise max of its
+// lanes' registers, sums 2^(53 - M) exactly as union_kernel does, and reduces with shuffles; no cross-wave step.
+__global__ __launch_bounds__(kPairThreads) void pair_union_kernel(const uint8_t* __restrict__ regs, const uint32_t* __restrict__ ids,
+                                                                   uint32_t n, double alpha_mm, double* __restrict__ est) {
+    __shared__ uint4 cols[kPairTile][kRegs / 16];
+    const uint32_t ti = blockIdx.y, tj = blockIdx.x;
+    if (tj < ti) return;  // uniform: the lower triangle is written by its mirror tile
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // bins past n are never computed (the loops below stop at n): their slots load bin n - 1, a valid address
+#pragma unroll 4
+    for (uint32_t jj = 0; jj < kPairTile; ++jj) {
+        const uint32_t gj = min(tj * kPairTile + jj, n - 1);
+        cols[jj][threadIdx.x] = reinterpret_cast<const uint4*>(regs + (uint64_t)ids[gj] * kRegs)[threadIdx.x];
+    }
+    uint32_t a[kPairRows][kPairQuads * 4];
+#pragma unroll
+    for (uint32_t ii = 0; ii < kPairRows; ++ii) {
+        const uint32_t gi = min(ti * kPairTile + wave * kPairRows + ii, n - 1);
+#pragma unroll
+        for (uint32_t q = 0; q < kPairQuads; ++q) {
+            const uint4 v = reinterpret_cast<const uint4*>(regs + (uint64_t)ids[gi] * kRegs)[q * 64 + lane];
+            a[ii][4 * q] = v.x; a[ii][4 * q + 1] = v.y; a[ii][4 * q + 2] = v.z; a[ii][4 * q + 3] = v.w;
+        }
+    }
+    __syncthreads();
+    for (uint32_t jj = 0; jj < kPairTile; ++jj) {
+        const uint32_t gj = tj * kPairTile + jj;
+        if (gj >= n) break;  // uniform
+        uint32_t b[kPairQuads * 4];
+#pragma unroll
+        for (uint32_t q = 0; q < kPairQuads; ++q) {
+            const uint4 v = cols[jj][q * 64 + lane];
+            b[4 * q] = v.x; b[4 * q + 1] = v.y; b[4 * q + 2] = v.z; b[4 * q + 3] = v.w;
+        }
+#pragma unroll
+        for (uint32_t ii = 0; ii < kPairRows; ++ii) {
+            const uint32_t gi = ti * kPairTile + wave * kPairRows + ii;
+            if (gi >= n) continue;  // uniform over the wave
+            uint64_t sum = 0;
+            uint32_t zeros = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < kPairQuads * 4; ++w) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t r = max((a[ii][w] >> (8 * k)) & 0xFFu, (b[w] >> (8 * k)) & 0xFFu);
+                    sum += 1ULL << (53 - min(r, 53u));
+                    zeros += r == 0;
+                }
+            }
+            uint32_t lo = (uint32_t)sum, hi = (uint32_t)(sum >> 32);  // a lane's 64 registers: sum < 2^60
+            uint64_t tl = lo, th = hi;
+            for (int o = 32; o > 0; o >>= 1) {
+                tl += __shfl_xor(tl, o);
+                th += __shfl_xor(th, o);
+                zeros += __shfl_xor(zeros, o);
+            }
+            if (lane == 0) {
+                const double z = ((double)th * 4294967296.0 + (double)tl) * 0x1p-53;
+                double e = alpha_mm / z;
+                if (e <= 2.5 * kRegs && zeros > 0) e = kLinearCount[zeros];
+                est[(uint64_t)gi * n + gj] = e;
+                if (ti != tj) est[(uint64_t)gj * n + gi] = e;
+            }
+        }
     }
 }
 
@@ -209,6 +284,21 @@ int txq_union_estimates_device(const uint8_t* d_registers, const uint32_t* d_ord
     union_kernel<<<(unsigned)n_bins, kUnionThreads, 0, st>>>(d_registers, d_order, n_bins, (uint32_t)window, alpha_mm, d_estimates);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "union estimate kernel launch");
+    return TXQ_OK;
+}
+
+int txq_pair_unions_device(const uint8_t* d_registers, const uint32_t* d_ids, uint64_t n, double* d_estimates, void* stream) {
+    if (int rc = require_init()) return rc;
+    if (n == 0) return TXQ_OK;
+    if (!d_registers || !d_ids || !d_estimates) return fail(TXQ_ERR_ARG, "null argument");
+    if (n > kPairMaxBins) return fail(TXQ_ERR_ARG, "at most 4096 bins per pair table");
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = upload_linear_count(st)) return rc;
+    const double m = kRegs, alpha_mm = 0.7213 / (1.0 + 1.079 / m) * m * m;
+    const unsigned tiles = (unsigned)((n + kPairTile - 1) / kPairTile);
+    pair_union_kernel<<<dim3(tiles, tiles), kPairThreads, 0, st>>>(d_registers, d_ids, (uint32_t)n, alpha_mm, d_estimates);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "pair union kernel launch");
     return TXQ_OK;
 }
 

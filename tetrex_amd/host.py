@@ -320,7 +320,7 @@ class LayoutParams(C.Structure):
 
 class BuildOptions(C.Structure):
     _fields_ = [("k", C.c_uint), ("dna", C.c_int), ("reduction", C.c_uint), ("hash_count", C.c_uint), ("fpr", C.c_float),
-                ("flavour", C.c_int), ("tmax", C.c_uint64), ("device", C.c_int)]
+                ("flavour", C.c_int), ("tmax", C.c_uint64), ("device", C.c_int), ("rearrange_ratio", C.c_double)]
 
 
 def default_tmax(user_bins):
@@ -339,14 +339,54 @@ def layout_order(counts):
     return np.lexsort((np.arange(counts.size), -counts)).astype(np.uint64)
 
 
-def hibf_layout(counts, unions, tmax=None, fpr=0.05, relaxed_fpr=0.3, hash_count=3, alpha=1.2):
+REARRANGE_MAX_LEN = 4096  # TXH_REARRANGE_MAX_LEN
+
+
+def rearrange_intervals(counts, ratio=0.5, max_len=None):
+    """Intervals of layout_order(counts) inside which `--rearrange` moves bins (include/txh.h txh_rearrange_intervals): the
+    first sorted position of every interval, ascending.  max_len: 1 .. 4096 bins per interval at most (None: 4096)."""
+    L = lib()
+    L.txh_rearrange_intervals.restype = C.c_int64
+    L.txh_rearrange_intervals.argtypes = [C.POINTER(C.c_double), C.c_uint64, C.c_double, C.c_uint64, u64p, C.c_size_t]
+    c = np.ascontiguousarray(counts, dtype=np.float64)
+    if max_len is not None and int(max_len) < 1:
+        raise HostError("an interval holds at least one bin")
+    starts = np.zeros(max(1, c.size), dtype=np.uint64)
+    n = L.txh_rearrange_intervals(c.ctypes.data_as(C.POINTER(C.c_double)), c.size, float(ratio), int(max_len or 0),
+                                  starts.ctypes.data_as(u64p), starts.size)
+    if n < 0:
+        raise _err()
+    return starts[:n]
+
+
+def rearrange_chain(counts, unions):
+    """The nearest-neighbour chain inside one interval (include/txh.h txh_rearrange_chain): counts[n] by position in the
+    interval, unions (n, n) pairwise union estimates; returns the positions in their new order (position 0 first)."""
+    L = lib()
+    L.txh_rearrange_chain.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint64, u64p]
+    c = np.ascontiguousarray(counts, dtype=np.float64)
+    u = np.ascontiguousarray(unions, dtype=np.float64)
+    n = c.size
+    if u.size != n * n:
+        raise HostError("unions must be n x n")
+    chain = np.zeros(n, dtype=np.uint64)
+    dp = C.POINTER(C.c_double)
+    if L.txh_rearrange_chain(c.ctypes.data_as(dp), u.ctypes.data_as(dp), n, chain.ctypes.data_as(u64p)) != 0:
+        raise _err()
+    return chain
+
+
+def hibf_layout(counts, unions, tmax=None, fpr=0.05, relaxed_fpr=0.3, hash_count=3, alpha=1.2, order=None):
     """The size-aware HIBF layout (host/layout.hpp, include/txh.h txh_hibf_layout), a pure function.
 
     counts: each user bin's estimate, by user bin id; unions: B x W union estimates over runs in layout_order(counts)
-    (W = union_window(B, tmax)).  Returns dict(order, tmax, window, ibfs=[dict(bins, bin_size, next_ibf_id,
-    tb_to_user_bin)]), the root first and the children in depth-first pre-order."""
+    (W = union_window(B, tmax)).  order (optional): lay the bins out in this order instead (a permutation of 0 .. B-1;
+    unions then over runs of it; txh_hibf_layout_ordered).  Returns dict(order, tmax, window, ibfs=[dict(bins, bin_size,
+    next_ibf_id, tb_to_user_bin)]), the root first and the children in depth-first pre-order."""
     L = lib()
     if not hasattr(L, "_layout_ready"):
+        L.txh_hibf_layout_ordered.argtypes = [C.POINTER(C.c_double), C.c_uint64, u64p, C.POINTER(C.c_double), C.c_uint64,
+                                              C.POINTER(LayoutParams), C.POINTER(C.c_void_p)]
         L.txh_hibf_layout.argtypes = [C.POINTER(C.c_double), C.c_uint64, C.POINTER(C.c_double), C.c_uint64,
                                       C.POINTER(LayoutParams), C.POINTER(C.c_void_p)]
         L.txh_layout_ibf_count.restype = C.c_int64
@@ -365,7 +405,14 @@ def hibf_layout(counts, unions, tmax=None, fpr=0.05, relaxed_fpr=0.3, hash_count
     p = LayoutParams(tmax, fpr, relaxed_fpr, hash_count, alpha)
     h = C.c_void_p()
     dp = C.POINTER(C.c_double)
-    if L.txh_hibf_layout(c.ctypes.data_as(dp), B, u.ctypes.data_as(dp), W, C.byref(p), C.byref(h)) != 0:
+    if order is None:
+        rc = L.txh_hibf_layout(c.ctypes.data_as(dp), B, u.ctypes.data_as(dp), W, C.byref(p), C.byref(h))
+    else:
+        o = np.ascontiguousarray(order, dtype=np.uint64)
+        if o.size != B:
+            raise HostError("the order must be a permutation of the user bins")
+        rc = L.txh_hibf_layout_ordered(c.ctypes.data_as(dp), B, o.ctypes.data_as(u64p), u.ctypes.data_as(dp), W, C.byref(p), C.byref(h))
+    if rc != 0:
         raise _err()
     try:
         ibfs = []
@@ -408,9 +455,10 @@ class IndexFile:
         return cls(h.value)
 
     @classmethod
-    def build(cls, paths, k=6, dna=False, reduction=0, layout="sized", tmax=None, fpr=0.05, hash_count=3, device=0):
+    def build(cls, paths, k=6, dna=False, reduction=0, layout="sized", tmax=None, fpr=0.05, hash_count=3, device=0, rearrange=None):
         """`tetrex index` without the CLI (txh_index_build of libtetrex_query.so; needs a GPU): layout "sized" (the
-        size-aware HIBF), "uniform" (the default HIBF of the CLI) or "ibf" (a flat IBF, -i)."""
+        size-aware HIBF), "uniform" (the default HIBF of the CLI) or "ibf" (a flat IBF, -i).  rearrange (sized only):
+        None / 0 off, True the default ratio 0.5, or the interval ratio in (0, 1] (`--rearrange [--rearrange-ratio R]`)."""
         from tetrex_amd import capi
         flavours = {"uniform": 0, "sized": 1, "ibf": 2}
         if layout not in flavours:
@@ -418,7 +466,8 @@ class IndexFile:
         Q = capi._query_lib()
         Q.txh_index_build.argtypes = [C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(BuildOptions), C.POINTER(C.c_void_p)]
         arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
-        opt = BuildOptions(k, int(dna), reduction, hash_count, fpr, flavours[layout], int(tmax or 0), device)
+        ratio = 0.5 if rearrange is True else float(rearrange or 0)
+        opt = BuildOptions(k, int(dna), reduction, hash_count, fpr, flavours[layout], int(tmax or 0), device, ratio)
         _index_api()  # the handle is freed through libtetrex_host.so
         h = C.c_void_p()
         if Q.txh_index_build(arr, len(paths), C.byref(opt), C.byref(h)) != 0:
