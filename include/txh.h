@@ -126,6 +126,17 @@ int64_t txh_regex_required_literal(const char* pattern, int posix, char* out, si
 int64_t txh_record_values(int dna, unsigned k, unsigned reduction, const char* seq, size_t len, int wraparound,
                           uint64_t* out, size_t cap);
 
+/* Six-frame translation of one nucleotide record into the k-mer values of a peptide index (the CPU restatement of
+ * txq_translate_device, include/txq.h, where the semantics are spelled out): frames +1 +2 +3 -1 -2 -3 one after the other,
+ * offsets[f] .. offsets[f+1] the values of frame f.  Returns the number of values (may exceed cap; nothing written past cap),
+ * or a negative number where k is outside 1..12 or the reduction unknown. */
+int64_t txh_translated_values(unsigned k, unsigned reduction, const char* seq, size_t len, uint64_t* out, size_t cap,
+                              uint64_t offsets[7]);
+/* one frame (0..5) as residue letters, X for an ambiguous codon and * for a stop; returns the length (may exceed cap) */
+int64_t txh_translate_frame(const char* seq, size_t len, unsigned frame, char* out, size_t cap);
+/* the 256-byte residue code table of the peptide encoder of a reduction (what txq_translate takes as `codes`) */
+int txh_peptide_codes(unsigned reduction, uint8_t out[256]);
+
 /* ---- .ibf index files (include/index_base.h:160-202 layout; see host/index_file.hpp) ---- */
 typedef struct txh_index txh_index;
 int txh_index_parse(const void* bytes, size_t n, txh_index** out);

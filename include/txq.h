@@ -194,6 +194,33 @@ int txq_count_device(txq_index* ix, const uint64_t* d_values, const uint64_t* d_
 int txq_count(txq_index* ix, const uint64_t* values, const uint64_t* offsets, size_t n_queries,
               const uint32_t* thresholds, uint64_t* hits, uint32_t* counts);  /* host buffers, synchronous */
 
+/* Six-frame translation of nucleotide records into the k-mer values of a peptide index (`tetrex search --translate`; not in
+ * the reference).  Record r is the bytes d_seq[d_rec_offsets[r] .. d_rec_offsets[r+1]) (n_records + 1 ascending offsets).
+ * Letters A C G T U in either case (U reads as T); any other byte is ambiguous.  Frame f = 0..5 is +1 +2 +3 -1 -2 -3: frames
+ * +1..+3 read the record from offset 0, 1, 2, frames -1..-3 its reverse complement from offset 0, 1, 2; trailing bytes that
+ * do not fill a codon are dropped.  Codons translate by NCBI table 1, a codon with an ambiguous byte is X, a stop is *.
+ * The values of a frame: every window of k residues without a stop, in ascending position, folded as the index's encoder
+ * does it: value = sum of d_codes[residue j] << 5 (k - 1 - j), d_codes the encoder's 256-byte table (so reduced alphabets
+ * work unchanged).  Query 6 r + f owns d_values[d_offsets[6 r + f] .. d_offsets[6 r + f + 1]); d_offsets has 6 n_records + 1
+ * entries, d_offsets[0] = 0, and is in the form txq_count_device takes.  d_values must hold txq_translate_bound values:
+ * the sum over records and offsets o = 0, 1, 2 of 2 max(0, floor((L_r - o) / 3) - k + 1) (UINT64_MAX: bad arguments).
+ * The call is deterministic and does not synchronise with the host; its scratch is the library's, in stream order.
+ * txq_translate is the synchronous twin on host buffers (it checks the record offsets).  k outside 1..12 and null
+ * pointers: TXQ_ERR_ARG. */
+uint64_t txq_translate_bound(const uint64_t* rec_offsets, size_t n_records, unsigned k);
+int txq_translate_device(const uint8_t* d_seq, const uint64_t* d_rec_offsets, size_t n_records, unsigned k, const uint8_t* d_codes,
+                         uint64_t* d_values, uint64_t* d_offsets, void* stream);
+int txq_translate(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_records, unsigned k, const uint8_t* codes,
+                  uint64_t* values, uint64_t* offsets);
+
+/* The set bits of a hit matrix (n_queries x words words, as txq_count_device writes it) as a list of (query, bin, count)
+ * u32 triples in (query, bin) order: bin = 64 * word + bit — on a column shard the column within the shard —, count =
+ * d_counts[query * 64 * words + bin], or 0 where d_counts is NULL.  *d_total receives the number of set bits whatever
+ * the capacity; at most `capacity` triples are written (the caller retries with a larger list).  No atomic append: the
+ * order does not depend on scheduling.  Asynchronous on `stream`. */
+int txq_hit_list_device(const uint64_t* d_hits, const uint32_t* d_counts, size_t n_queries, size_t words, uint32_t* d_list,
+                        size_t capacity, uint64_t* d_total, void* stream);
+
 /* Device-side emplace: value i is inserted into bin bins_of[i] (flat IBF only; bins outside this
  * shard's columns are skipped). */
 int txq_emplace_device(txq_index* ix, const uint64_t* d_values, const uint32_t* d_bins_of, size_t n, void* stream);

@@ -22,6 +22,7 @@ SYMBOLS = [
     "txq_init", "txq_shutdown", "txq_last_error", "txq_device_count",
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
+    "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_hit_list_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
     "txq_malloc", "txq_free", "txq_memcpy_h2d", "txq_memcpy_d2h", "txq_synchronize", "txq_host_alloc", "txq_host_free",
@@ -77,6 +78,11 @@ def lib():
         L.txq_emplace_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.txq_count.argtypes = [C.c_void_p, u64p, u64p, C.c_size_t, u32p, u64p, u32p]
         L.txq_count_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.txq_translate_bound.restype = C.c_uint64
+        L.txq_translate_bound.argtypes = [u64p, C.c_size_t, C.c_uint]
+        L.txq_translate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.txq_translate.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_uint, C.c_void_p, u64p, u64p]
+        L.txq_hit_list_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.txq_run_programs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, u64p]
         L.txq_run_programs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         L.txq_session_begin.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
@@ -467,6 +473,64 @@ class Session:
                 self._h = None
         except Exception:
             pass
+
+
+def _records(records):
+    """list of bytes/str records -> (uint8 bytes back to back, uint64 offsets)"""
+    recs = [r.encode() if isinstance(r, str) else bytes(r) for r in records]
+    offsets = np.zeros(len(recs) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(r) for r in recs])
+    return np.frombuffer(b"".join(recs), dtype=np.uint8), offsets
+
+
+def translate_bound(rec_offsets, k):
+    """txq_translate_bound: how many values txq_translate* may produce for these record offsets (no GPU needed)."""
+    o = np.ascontiguousarray(rec_offsets, dtype=np.uint64)
+    b = lib().txq_translate_bound(o.ctypes.data_as(u64p), max(o.size - 1, 0), k)
+    if b == 0xFFFFFFFFFFFFFFFF:
+        raise TxqError(-1, lib().txq_last_error().decode(errors="replace"))
+    return int(b)
+
+
+def translate(records, k, codes):
+    """Six-frame translation of nucleotide records into the k-mer values of a peptide index on the GPU (txq_translate).
+    records: list of bytes/str, or (uint8 array, uint64 offsets).  codes: the encoder's 256-byte table (host.peptide_codes).
+    Returns (values uint64[], offsets uint64[6 n + 1]): query 6 r + f owns values[offsets[6 r + f]:offsets[6 r + f + 1]]."""
+    seq, rec = records if isinstance(records, tuple) else _records(records)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    rec = np.ascontiguousarray(rec, dtype=np.uint64)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    n = rec.size - 1
+    if n < 0 or codes.size != 256 or (n and int(rec[-1]) > seq.size):
+        raise TxqError(-1, "translate: offsets, bytes and code table disagree")
+    bound = lib().txq_translate_bound(rec.ctypes.data_as(u64p), n, k)
+    values = np.zeros(0 if bound == 0xFFFFFFFFFFFFFFFF else bound, dtype=np.uint64)
+    offsets = np.zeros(6 * n + 1, dtype=np.uint64)
+    check(lib().txq_translate(seq.ctypes.data, rec.ctypes.data_as(u64p), n, k, codes.ctypes.data, values.ctypes.data_as(u64p),
+                              offsets.ctypes.data_as(u64p)))
+    return values[:int(offsets[-1])], offsets
+
+
+def hit_list(hits, counts=None, capacity=None, guard=0):
+    """txq_hit_list_device on a host hit matrix (n, words) uint64 (and counts (n, 64 words) uint32): returns (rows, total),
+    rows a (capacity + guard, 3) uint32 array of (query, bin, count) whose first min(total, capacity) rows are the list; the
+    `guard` rows behind the capacity keep the 0xFFFFFFFF they were filled with unless the library wrote past the capacity."""
+    h = np.ascontiguousarray(hits, dtype=np.uint64)
+    n, words = h.shape
+    if capacity is None:
+        capacity = int(np.unpackbits(h.view(np.uint8)).sum())
+    dh = DeviceBuffer.from_numpy(h if h.size else np.zeros(1, np.uint64))
+    dc = DeviceBuffer.from_numpy(np.ascontiguousarray(counts, dtype=np.uint32)) if counts is not None else None
+    dl = DeviceBuffer.from_numpy(np.full((capacity + guard + 1, 3), 0xFFFFFFFF, dtype=np.uint32))
+    dt = DeviceBuffer.from_numpy(np.full(1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64))
+    try:
+        check(lib().txq_hit_list_device(dh.ptr, dc.ptr if dc else None, n, words, dl.ptr, capacity, dt.ptr, None))
+        check(lib().txq_synchronize())
+        return dl.to_numpy(np.uint32, (capacity + guard, 3)), int(dt.to_numpy(np.uint64, (1,))[0])
+    finally:
+        for b in (dh, dc, dl, dt):
+            if b is not None:
+                b.free()
 
 
 HLL_REGISTERS = 4096

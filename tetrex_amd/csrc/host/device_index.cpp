@@ -637,4 +637,99 @@ DgramImage build_dgram_index(const std::vector<std::string>& bin_files, uint64_t
     return d;
 }
 
+namespace {
+// a device buffer that only grows (one per kind for all batches of a call)
+struct GrowBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    void* reserve(size_t bytes) {
+        if (bytes > cap || !p) {
+            if (p) txq_free(p);
+            p = nullptr;
+            cap = 0;
+            txq_check(txq_malloc(&p, std::max<size_t>(bytes, 256)), "txq_malloc");
+            cap = std::max<size_t>(bytes, 256);
+        }
+        return p;
+    }
+    ~GrowBuf() { if (p) txq_free(p); }
+};
+}  // namespace
+
+void DeviceIndex::search_translated(std::string_view seq, const std::vector<uint64_t>& rec_offsets,
+                                    const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& n_of,
+                                    std::vector<uint64_t>& thresholds, std::vector<TranslatedHit>& hits) {
+    if (!ix_) throw std::runtime_error("index not uploaded");
+    if (shards_.size() > 1) throw std::runtime_error("search_translated: one shard only");
+    if (enc_.molecule() != Molecule::Peptide) throw std::runtime_error("search_translated: a peptide index is needed");
+    if (rec_offsets.empty() || rec_offsets.back() > seq.size()) throw std::runtime_error("search_translated: record offsets run past the bytes");
+    const unsigned k = enc_.k();
+    const size_t R = rec_offsets.size() - 1, W = info_.shard_words;
+    n_of.assign(6 * R, 0);
+    thresholds.assign(6 * R, 0);
+    hits.clear();
+    if (R == 0 || W == 0) return;
+    // a batch: at most 2^24 values (by their bound), and at most 256 MiB of hit words / counts
+    const uint64_t max_values = (uint64_t)1 << 24;
+    const size_t max_queries = std::max<size_t>(6, ((size_t)256 << 20) / (W * (with_counts ? 64 * 4 : 8)));
+    GrowBuf d_codes, d_seq, d_rec, d_val, d_off, d_thr, d_hit, d_cnt, d_list, d_total;
+    txq_check(txq_memcpy_h2d(d_codes.reserve(256), enc_.aa_table().data(), 256), "h2d");
+    d_total.reserve(8);
+    size_t list_cap = (size_t)1 << 20;
+    std::vector<uint64_t> rebased, off;
+    std::vector<uint32_t> thr, list;
+    for (size_t r0 = 0; r0 < R;) {
+        size_t r1 = r0;
+        uint64_t bound = 0;
+        while (r1 < R) {
+            const uint64_t b = txq_translate_bound(rec_offsets.data() + r1, 1, k);
+            if (b == UINT64_MAX) txq_check(TXQ_ERR_ARG, "txq_translate_bound");
+            if (r1 > r0 && (bound + b > max_values || 6 * (r1 - r0 + 1) > max_queries)) break;
+            bound += b;
+            ++r1;
+        }
+        const size_t nr = r1 - r0, nq = 6 * nr;
+        const uint64_t first = rec_offsets[r0], bytes = rec_offsets[r1] - first;
+        rebased.assign(rec_offsets.begin() + r0, rec_offsets.begin() + r1 + 1);
+        for (uint64_t& o : rebased) o -= first;
+        if (bytes) txq_check(txq_memcpy_h2d(d_seq.reserve(bytes), seq.data() + first, bytes), "h2d");
+        else d_seq.reserve(1);
+        txq_check(txq_memcpy_h2d(d_rec.reserve(rebased.size() * 8), rebased.data(), rebased.size() * 8), "h2d");
+        d_val.reserve(bound * 8 + 8);
+        d_off.reserve((nq + 1) * 8);
+        txq_check(txq_translate_device((const uint8_t*)d_seq.p, (const uint64_t*)d_rec.p, nr, k, (const uint8_t*)d_codes.p, (uint64_t*)d_val.p,
+                                       (uint64_t*)d_off.p, nullptr), "txq_translate_device");
+        off.resize(nq + 1);
+        txq_check(txq_memcpy_d2h(off.data(), d_off.p, off.size() * 8), "d2h");
+        thr.assign(nq, 0xFFFFFFFFu);  // (no count reaches it: a query that is not searched has no hits)
+        bool any = false;
+        for (size_t q = 0; q < nq; ++q) {
+            const uint64_t n = off[q + 1] - off[q], t = n ? threshold_of(n) : 0;
+            n_of[6 * r0 + q] = n;
+            thresholds[6 * r0 + q] = t;
+            if (t) thr[q] = (uint32_t)std::min<uint64_t>(t, 0xFFFFFFFEull), any = true;
+        }
+        r0 = r1;
+        if (!any) continue;
+        txq_check(txq_memcpy_h2d(d_thr.reserve(nq * 4), thr.data(), nq * 4), "h2d");
+        d_hit.reserve(nq * W * 8);
+        if (with_counts) d_cnt.reserve(nq * W * 64 * 4);
+        txq_check(txq_count_device(ix_, (const uint64_t*)d_val.p, (const uint64_t*)d_off.p, nq, (const uint32_t*)d_thr.p, (uint64_t*)d_hit.p,
+                                   with_counts ? (uint32_t*)d_cnt.p : nullptr, nullptr), "txq_count_device");
+        uint64_t total = 0;
+        for (;;) {
+            d_list.reserve(list_cap * 12);
+            txq_check(txq_hit_list_device((const uint64_t*)d_hit.p, with_counts ? (const uint32_t*)d_cnt.p : nullptr, nq, W, (uint32_t*)d_list.p,
+                                          list_cap, (uint64_t*)d_total.p, nullptr), "txq_hit_list_device");
+            txq_check(txq_memcpy_d2h(&total, d_total.p, 8), "d2h");
+            if (total <= list_cap) break;
+            list_cap = total;  // (the list did not fit: once more with room for all of it)
+        }
+        list.resize(3 * total);
+        if (total) txq_check(txq_memcpy_d2h(list.data(), d_list.p, total * 12), "d2h");
+        const uint32_t q0 = (uint32_t)(6 * (r1 - nr)), bin0 = (uint32_t)(info_.shard_word0 * 64);
+        for (uint64_t i = 0; i < total; ++i) hits.push_back(TranslatedHit{q0 + list[3 * i], bin0 + list[3 * i + 1], list[3 * i + 2]});
+    }
+}
+
 }  // namespace tetrex

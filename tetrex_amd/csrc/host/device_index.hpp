@@ -9,6 +9,7 @@
 #include "layout.hpp"
 #include "../../../include/txq.h"
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -93,6 +94,16 @@ class DeviceIndex {
     // n x 64 * result_words() u32.  One shard only (upload()).
     void count(const std::vector<uint64_t>& values, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& thresholds,
                std::vector<uint64_t>& hits, std::vector<uint32_t>* counts);
+    // `tetrex search --translate`: nucleotide records against this peptide index, all on the device.  Record r is
+    // seq[rec_offsets[r] .. rec_offsets[r+1]); its six frames are queries 6 r + f (f = 0..5: +1 +2 +3 -1 -2 -3).  The bytes
+    // are uploaded and translated there (txq_translate_device), n_of[q] comes back, thresholds[q] = threshold_of(n_of[q]) (0
+    // where n_of[q] = 0), a query with threshold 0 is not searched, the others are counted (txq_count_device on the device's
+    // values) and only the list of their hits comes back (txq_hit_list_device), in (query, bin) order.  Records are batched
+    // by txq_translate_bound to at most 2^24 values a batch (one larger record: a batch of its own).  One shard only.
+    struct TranslatedHit { uint32_t query, bin, count; };  // count: 0 unless with_counts
+    void search_translated(std::string_view seq, const std::vector<uint64_t>& rec_offsets,
+                           const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& n_of,
+                           std::vector<uint64_t>& thresholds, std::vector<TranslatedHit>& hits);
     // `tetrex query -g`: upload the d-gram index next to the main index (same device, same shard)
     void attach_dgram(const DgramImage& dgram);
     bool has_dgram() const { return aux_ != nullptr; }

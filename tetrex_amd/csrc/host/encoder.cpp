@@ -1,5 +1,7 @@
 #include "encoder.hpp"
 
+#include <stdexcept>
+
 namespace tetrex {
 
 namespace {
@@ -55,6 +57,56 @@ void KmerEncoder::record_values(std::string_view seq, bool wraparound, std::vect
     for (size_t i = wraparound ? 0 : k_; i < seq.size(); ++i) {
         fwd = ((fwd << 2) & kmer_mask_) | (((unsigned char)seq[i] >> 1) & 3u);
         out.push_back(canonical(fwd));
+    }
+}
+
+namespace {
+// NCBI translation table 1, codon index 16 a + 4 b + c with T = 0, C = 1, A = 2, G = 3
+constexpr char kTable1[65] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
+
+unsigned nucleotide(unsigned char c) {
+    switch (c) {
+        case 'T': case 't': case 'U': case 'u': return 0;
+        case 'C': case 'c': return 1;
+        case 'A': case 'a': return 2;
+        case 'G': case 'g': return 3;
+        default: return 4;
+    }
+}
+}  // namespace
+
+std::string translate_frame(std::string_view seq, unsigned frame) {
+    if (frame > 5) throw std::invalid_argument("frame must be 0..5");
+    const size_t L = seq.size(), o = frame % 3;
+    std::string out;
+    // base i of the strand that is read: S[i], or the complement (code ^ 2) of S[L - 1 - i]; an ambiguous byte stays ambiguous
+    auto base = [&](size_t i) {
+        if (frame < 3) return nucleotide((unsigned char)seq[i]);
+        const unsigned n = nucleotide((unsigned char)seq[L - 1 - i]);
+        return n < 4 ? n ^ 2u : n;
+    };
+    for (size_t p = o; p + 3 <= L; p += 3) {
+        const unsigned c[3] = {base(p), base(p + 1), base(p + 2)};
+        out.push_back((c[0] | c[1] | c[2]) & 4u ? 'X' : kTable1[16 * c[0] + 4 * c[1] + c[2]]);
+    }
+    return out;
+}
+
+void translated_values(const KmerEncoder& enc, std::string_view seq, std::vector<uint64_t>& out, std::array<uint64_t, 7>& offsets) {
+    if (enc.molecule() != Molecule::Peptide || enc.k() < 1 || enc.k() > 12)
+        throw std::invalid_argument("translated k-mers need a peptide encoder with k in 1..12");
+    const size_t start = out.size();
+    offsets[0] = 0;
+    for (unsigned f = 0; f < 6; ++f) {
+        const std::string residues = translate_frame(seq, f);
+        size_t a = 0;
+        while (a <= residues.size()) {  // maximal stop-free runs
+            size_t b = residues.find('*', a);
+            if (b == std::string::npos) b = residues.size();
+            enc.record_values(std::string_view(residues).substr(a, b - a), false, out);
+            a = b + 1;
+        }
+        offsets[f + 1] = out.size() - start;
     }
 }
 

@@ -57,4 +57,14 @@ class KmerEncoder {
     std::array<char, 256> reduce_{};
 };
 
+// Six-frame translation of a nucleotide record for a peptide index (`tetrex search --translate`; the CPU
+// restatement of libtxq's txq_translate_device).  Letters A C G T U in either case, any other byte ambiguous; frame f = 0..5
+// is +1 +2 +3 -1 -2 -3 (the record from offset 0, 1, 2, then its reverse complement from offset 0, 1, 2); NCBI table 1,
+// a codon with an ambiguous byte is X, a stop is *.
+std::string translate_frame(std::string_view seq, unsigned frame);
+// The values of all six frames, frame after frame: for each frame, record_values of every maximal stop-free run of at least k
+// residues, in order.  offsets[f] .. offsets[f+1] are frame f's values in `out` (appended to; offsets count from out's old size
+// as 0).  `enc` must be a peptide encoder with k in 1..12.
+void translated_values(const KmerEncoder& enc, std::string_view seq, std::vector<uint64_t>& out, std::array<uint64_t, 7>& offsets);
+
 }  // namespace tetrex

@@ -249,6 +249,39 @@ int64_t txh_record_values(int dna, unsigned k, unsigned reduction, const char* s
     return (int64_t)v.size();
 }
 
+int64_t txh_translated_values(unsigned k, unsigned reduction, const char* seq, size_t len, uint64_t* out, size_t cap,
+                              uint64_t offsets[7]) {
+    try {
+        if (reduction > 2) return fail("unknown reduction");
+        if (!offsets || (len && !seq)) return fail("null argument");
+        std::vector<uint64_t> v;
+        std::array<uint64_t, 7> off{};
+        translated_values(encoder(0, k, reduction), std::string_view(seq ? seq : "", len), v, off);
+        for (size_t i = 0; i < v.size() && i < cap; ++i) out[i] = v[i];
+        for (size_t f = 0; f < 7; ++f) offsets[f] = off[f];
+        return (int64_t)v.size();
+    } catch (const std::exception& e) {
+        return fail(e.what());
+    }
+}
+
+int64_t txh_translate_frame(const char* seq, size_t len, unsigned frame, char* out, size_t cap) {
+    try {
+        const std::string r = translate_frame(std::string_view(seq ? seq : "", len), frame);
+        for (size_t i = 0; i < r.size() && i < cap; ++i) out[i] = r[i];
+        return (int64_t)r.size();
+    } catch (const std::exception& e) {
+        return fail(e.what());
+    }
+}
+
+int txh_peptide_codes(unsigned reduction, uint8_t out[256]) {
+    if (reduction > 2 || !out) return fail("unknown reduction");
+    const auto& t = encoder(0, 1, reduction).aa_table();
+    std::memcpy(out, t.data(), 256);
+    return 0;
+}
+
 int txh_index_parse(const void* bytes, size_t n, txh_index** out) {
     try {
         std::vector<uint8_t> v((const uint8_t*)bytes, (const uint8_t*)bytes + n);

@@ -3,8 +3,9 @@
 //     (include/arg_parse.h:57-71, src/main.cpp:36-59, src/query.cpp:477-498)
 //   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] [--layout uniform|sized [--tmax N] [--rearrange [--rearrange-ratio R]]] <name> <libs...>
 //     (include/arg_parse.h:10-38, src/index_base.cpp:73-117)
-//   tetrex search [-e E | --threshold F] [--counts] [-o dest] [-v] <index.ibf> <queries.fa[.gz]>
-//     (not in the reference: every FASTA record a query, answered by seqan::hibf membership_for(values, threshold))
+//   tetrex search [-e E | --threshold F] [--counts] [--translate] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//     (not in the reference: every FASTA record a query, answered by seqan::hibf membership_for(values, threshold);
+//      --translate: nucleotide records on a peptide index, every record's six frames a query of their own)
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
 #include "device_index.hpp"
@@ -391,13 +392,75 @@ int cmd_track(int argc, char** argv) {
     return 0;
 }
 
+// tetrex search --translate: nucleotide records on a peptide index.  Every record is translated in its six
+// frames on the device; frame f of a record is a query of its own with n_f values (the k-mers of the frame without a stop)
+// and the plain rules with n = n_f: -e E gives t = max(n_f - k E, 0), --threshold F gives t = ceil(F n_f).  A frame with
+// n_f = 0 or t = 0 reports nothing (a wrong frame is short and full of stops: "every bin" for it would be noise); a record
+// none of whose frames is searched gets a note.  Rows: name \t bin path \t frame [\t count/n_f], by record, frame
+// (+1 +2 +3 -1 -2 -3) and bin.
+int search_translated(const Args& a, const IndexImage& image, unsigned long long errors, double fraction) {
+    const bool verbose = a.has("verbose"), with_counts = a.has("counts"), by_fraction = a.has("threshold");
+    const std::string dest = a.get("output", "-");
+    const double t_start = now();
+    DeviceIndex dev;
+    dev.upload(image, std::atoi(a.get("device", "0").c_str()));
+    const uint64_t k = dev.encoder().k();
+    std::ofstream file;
+    if (dest != "-") {
+        file.open(dest);
+        if (!file) throw std::runtime_error("Failed to open output file: " + dest);
+    }
+    std::ostream& out = dest == "-" ? std::cout : file;
+    static const char* const kFrames[6] = {"+1", "+2", "+3", "-1", "-2", "-3"};
+    const auto threshold_of = [&](uint64_t n) -> uint64_t {
+        if (by_fraction) return (uint64_t)std::ceil(fraction * (double)n);
+        return n > k * errors ? n - k * errors : 0;
+    };
+    // records go to the device in chunks of their bytes (search_translated cuts a chunk into batches of values)
+    const size_t max_bytes = (size_t)64 << 20, max_records = (size_t)1 << 20;
+    std::vector<std::string> names;
+    std::string seq, row;
+    std::vector<uint64_t> rec_offsets{0}, n_of, thresholds;
+    std::vector<DeviceIndex::TranslatedHit> hits;
+    auto flush = [&]() {
+        if (names.empty()) return;
+        dev.search_translated(seq, rec_offsets, threshold_of, with_counts, n_of, thresholds, hits);
+        size_t h = 0;
+        for (size_t r = 0; r < names.size(); ++r) {
+            bool searched = false;
+            for (size_t f = 0; f < 6; ++f) searched = searched || thresholds[6 * r + f] > 0;
+            if (!searched)
+                std::cerr << "[tetrex search] " << names[r] << ": no frame with " << k << "-mers enough for a threshold above 0, skipped" << std::endl;
+            for (; h < hits.size() && hits[h].query < 6 * (r + 1); ++h) {
+                const DeviceIndex::TranslatedHit& x = hits[h];
+                row.assign(names[r]).append("\t").append(image.bin_paths[x.bin]).append("\t").append(kFrames[x.query % 6]);
+                if (with_counts) row.append("\t").append(std::to_string(x.count)).append("/").append(std::to_string(n_of[x.query]));
+                out << row << '\n';
+            }
+        }
+        names.clear();
+        seq.clear();
+        rec_offsets.assign(1, 0);
+    };
+    for_each_record(a.pos[1], [&](const FastaRecord& r) {
+        if (!names.empty() && (seq.size() + r.seq.size() > max_bytes || names.size() >= max_records)) flush();
+        names.push_back(r.name);
+        seq.append(r.seq);
+        rec_offsets.push_back(seq.size());
+    });
+    flush();
+    out.flush();
+    if (verbose) std::cerr << "Search time: " << (now() - t_start) << " s" << std::endl;
+    return 0;
+}
+
 // tetrex search: each record of the query file is a query; its values are the index's k-mers of the record (n of them) and a
 // bin is reported when at least t of them are in it (txq_count).  -e E: t = max(n - k E, 0) — a record within E edits of a
 // substring of a bin shares at least n - k E k-mer positions with it (q-gram lemma), and a Bloom filter drops none of them,
 // so that bin is always reported.  --threshold F (0 < F <= 1): t = ceil(F n).  Rows: name \t bin path [\t count/n].
 int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
-                                       {'v', "verbose", false}, {'D', "device", true}};
+                                       {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}};
     Args a;
     unsigned long long errors = 0;
     double fraction = 0;
@@ -431,6 +494,14 @@ int cmd_search(int argc, char** argv) {
         std::cerr << "Filepath to (H)IBF Index not valid" << std::endl;
         std::cerr << e.what() << '\n';
         return 1;
+    }
+    if (a.has("translate")) {
+        if (image.molecule == "na" || image.k < 1 || image.k > 12) {
+            std::cerr << "[tetrex search] --translate needs a peptide index with k in 1..12: " << a.pos[0] << " is a "
+                      << (image.molecule == "na" ? "nucleotide index" : "peptide index with k = " + std::to_string(image.k)) << std::endl;
+            return 1;
+        }
+        return search_translated(a, image, errors, fraction);
     }
     DeviceIndex dev;
     dev.upload(image, std::atoi(a.get("device", "0").c_str()));

@@ -1,0 +1,451 @@
+// Six-frame translation of nucleotide records into the k-mer values of a peptide index, and the compact list of a hit
+// matrix, on gfx950 (txq_translate / txq_translate_device, txq_hit_list_device; `tetrex search --translate`).
+// The reference has no counterpart: it never asks an index about a sequence.
+//
+// Translation.  Record r is seq[rec[r] .. rec[r+1]), L bytes.  The window S[p, p + 3k) of the record is at once
+//   * the forward k-mer at codon p / 3 of frame +(p mod 3 + 1), and
+//   * reverse-complemented, the k-mer at codon (L - p - 3k) / 3 of frame -((L - p - 3k) mod 3 + 1),
+// so one pass over the start positions p serves all six frames.  A k-mer is a value when none of its k residues is a stop;
+// query 6 r + f owns the values of frame f in ascending codon order, which for a forward frame is ascending p and for a
+// reverse frame descending p.  This is stream compaction: count, scan, fill.
+//
+// Mapping to the machine:
+//   * the bytes rec[0] .. rec[n] are cut into at most kUnits units of `chunk` start positions (a multiple of kTile, known
+//     only on the device: no host synchronisation), one wave each, so a record of 2 x 10^6 bytes is spread over thousands
+//     of waves and a unit of short reads walks the records that start in it;
+//   * a step takes kTile = 192 start positions of one record, aligned to the record's codons: lane l owns p = t0 + 3 l + j,
+//     j = 0, 1, 2, so j is the forward frame.  The step's bytes are staged with 16-byte loads into LDS, every codon is
+//     translated once in both directions into the index's residue codes (LDS), and a lane folds the k codes of each of
+//     its windows;
+//   * the rank of a value inside its frame is (valid windows of the frame before this step) + (valid lanes below, from one
+//     ballot per frame and direction): consecutive lanes write consecutive 8-byte values, a 512-byte store per wave;
+//   * count_kernel adds each record's six counts into offsets[] and leaves, per unit, the counts of the record that runs
+//     past the unit's end; scan_kernel turns the counts into offsets; fill_kernel recomputes the windows and, for a record
+//     that began in an earlier unit, first sums those units' counts.
+// Scratch (6 u32 per unit; the hit list's tile sums) is allocated and freed in stream order by the library.
+#include "../../include/txq.h"
+#include "txq_internal.hpp"
+
+#include <vector>
+
+namespace txq {
+namespace {
+
+constexpr uint32_t kUnits = 8192;            // waves of a translation call
+constexpr uint32_t kTile = 192;              // start positions per step: 64 lanes x 3 frames
+constexpr uint64_t kMinChunk = 4 * kTile;    // start positions per unit, at least
+constexpr uint32_t kMaxK = 12;               // 5 bits per residue in 64 (and the staging buffers below)
+constexpr uint32_t kRawBytes = 256;          // 15 (alignment) + kTile + 3 kMaxK - 1 = 242 bytes at most
+constexpr uint32_t kResidues = 256;          // kTile + 3 (kMaxK - 1) = 225 residues at most
+constexpr uint8_t kStop = 0xFF;
+
+// NCBI translation table 1, codon index 16 a + 4 b + c with T = 0, C = 1, A = 2, G = 3
+__constant__ char kTable1[65] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
+
+typedef uint32_t tx4 __attribute__((ext_vector_type(4)));
+
+struct TrArgs {
+    const uint8_t* seq;
+    const uint64_t* rec;  // n + 1
+    uint64_t n;
+    uint32_t k;
+    const uint8_t* codes;  // 256
+    uint64_t* values;
+    uint64_t* offsets;  // 6 n + 1
+    uint32_t* tails;    // kUnits x 6: per unit, the counts (forward j, reverse j) of the record that runs past the unit's end
+};
+
+__device__ __forceinline__ uint64_t chunk_len(uint64_t total) {
+    const uint64_t c = (total + kUnits - 1) / kUnits;
+    const uint64_t tiles = (c + kTile - 1) / kTile;
+    return tiles * kTile < kMinChunk ? kMinChunk : tiles * kTile;
+}
+
+// the record that holds byte x (rec[0] <= x < rec[n]): the last r with rec[r] <= x
+__device__ __forceinline__ uint64_t record_of(const uint64_t* rec, uint64_t n, uint64_t x) {
+    uint64_t lo = 1, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (rec[mid] > x) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo - 1;
+}
+
+// T/U = 0, C = 1, A = 2, G = 3 in either case; anything else is ambiguous (4).  The complement is code ^ 2.
+__device__ __forceinline__ uint32_t nucleotide(uint8_t c) {
+    switch (c & 0xDFu) {
+        case 'T': case 'U': return 0u;
+        case 'C': return 1u;
+        case 'A': return 2u;
+        case 'G': return 3u;
+        default: return 4u;
+    }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t raw[kRawBytes];
+    __shared__ uint8_t res[2][kResidues];  // residue codes of the codon at t0 + i: forward, reverse-complemented
+    __shared__ uint8_t lut[64];            // codon -> residue code of this index, kStop for a stop
+    const uint32_t lane = threadIdx.x;
+    const uint64_t base = a.rec[0], end = a.rec[a.n];
+    if (end <= base) return;
+    const uint64_t chunk = chunk_len(end - base);
+    const uint64_t ua = base + (uint64_t)blockIdx.x * chunk;
+    if (ua >= end) return;
+    const uint64_t ub = ua + chunk < end ? ua + chunk : end;
+    {
+        const char aa = kTable1[lane];
+        lut[lane] = aa == '*' ? kStop : (uint8_t)(a.codes[(uint8_t)aa] & 31u);
+    }
+    const uint8_t code_x = (uint8_t)(a.codes[(uint8_t)'X'] & 31u);
+    const uint32_t k = a.k, span = 3u * k;
+    const uint64_t below = (1ULL << lane) - 1ULL;
+    const uintptr_t seq_lo = (uintptr_t)(a.seq + base), seq_hi = (uintptr_t)(a.seq + end);
+    __syncthreads();
+
+    uint32_t cnt[6] = {0u, 0u, 0u, 0u, 0u, 0u};  // (count) windows of the current record in this unit: forward j, reverse j
+    bool runs_on = false;                        // the current record runs past the unit's end
+    for (uint64_t r = record_of(a.rec, a.n, ua); r < a.n; ++r) {
+        const uint64_t rs = a.rec[r];
+        if (rs >= ub) break;
+        const uint64_t re = a.rec[r + 1], L = re - rs;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) cnt[c] = 0u;
+        runs_on = re > ub;
+        if (L < span) continue;
+        const uint64_t lo = (ua > rs ? ua : rs) - rs;                         // start positions [lo, hi) of this record are this unit's
+        const uint64_t fit = L - span + 1, cut = (ub < re ? ub : re) - rs;
+        const uint64_t hi = cut < fit ? cut : fit;
+        if (lo >= hi) continue;
+        // frame of the reverse windows at p = j (mod 3), and where the frames' values go
+        uint32_t rframe[3];
+        uint64_t fbase[3], rlast[3], run[6];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            rframe[j] = 3u + (uint32_t)((L - span + 3u - (uint32_t)j) % 3u);  // (L - 3k - p) mod 3 for every p = j (mod 3) that fits
+            run[j] = run[3 + j] = 0;
+            if (FILL) {
+                fbase[j] = a.offsets[6 * r + j];
+                rlast[j] = a.offsets[6 * r + rframe[j] + 1] - 1;  // the frame's first codon is its last start position
+            }
+        }
+        if (FILL && lo > 0) {  // the record began in an earlier unit: the windows those units found
+            const uint64_t u0 = (rs - base) / chunk;
+            uint64_t part[6] = {0, 0, 0, 0, 0, 0};
+            for (uint64_t u = u0 + lane; u < blockIdx.x; u += 64)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) part[c] += a.tails[u * 6 + c];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                uint64_t v = part[c];
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+                run[c] = v;
+            }
+        }
+        for (uint64_t t0 = lo / 3 * 3; t0 < hi; t0 += kTile) {
+            // stage the step's bytes: 16-byte loads where the whole chunk lies inside the sequence buffer
+            const uintptr_t first = (uintptr_t)(a.seq + rs + t0);
+            const uint32_t shift = (uint32_t)(first & 15u);
+            const uint64_t left = L - t0;
+            const uint32_t nbytes = left < kTile + span - 1 ? (uint32_t)left : kTile + span - 1;
+            if (lane < (shift + nbytes + 15u) / 16u) {
+                const uintptr_t p = first - shift + 16u * lane;
+                if (p >= seq_lo && p + 16 <= seq_hi) {
+                    *reinterpret_cast<tx4*>(raw + 16u * lane) = *reinterpret_cast<const tx4*>(p);
+                } else {
+                    for (uint32_t b = 0; b < 16; ++b)
+                        raw[16u * lane + b] = p + b >= seq_lo && p + b < seq_hi ? *reinterpret_cast<const uint8_t*>(p + b) : (uint8_t)'N';
+                }
+            }
+            __syncthreads();
+            for (uint32_t i = lane; i < kTile + span - 3; i += 64) {
+                uint8_t f = kStop, g = kStop;  // (a codon that does not fit is never part of a window that fits)
+                if (t0 + i + 3 <= L) {
+                    const uint32_t x = nucleotide(raw[shift + i]), y = nucleotide(raw[shift + i + 1]), z = nucleotide(raw[shift + i + 2]);
+                    if ((x | y | z) & 4u) f = g = code_x;
+                    else {
+                        f = lut[16u * x + 4u * y + z];
+                        g = lut[16u * (z ^ 2u) + 4u * (y ^ 2u) + (x ^ 2u)];
+                    }
+                }
+                res[0][i] = f;
+                res[1][i] = g;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const uint64_t p = t0 + 3u * lane + (uint32_t)j;
+                const bool mine = p >= lo && p < hi;
+                uint64_t vf = 0, vr = 0;
+                bool okf = mine, okr = mine;
+                if (mine) {
+                    const uint32_t at = 3u * lane + (uint32_t)j;
+                    for (uint32_t q = 0; q < k; ++q) {
+                        const uint8_t f = res[0][at + 3u * q], g = res[1][at + 3u * q];
+                        okf = okf && f != kStop;
+                        okr = okr && g != kStop;
+                        vf = (vf << 5) | (uint64_t)(f & 31u);
+                        vr |= (uint64_t)(g & 31u) << (5u * q);  // the window's last codon is the reverse k-mer's first residue
+                    }
+                }
+                const uint64_t bf = __ballot(okf), br = __ballot(okr);
+                if (FILL) {
+                    if (okf) a.values[fbase[j] + run[j] + (uint64_t)__builtin_popcountll(bf & below)] = vf;
+                    if (okr) a.values[rlast[j] - run[3 + j] - (uint64_t)__builtin_popcountll(br & below)] = vr;
+                    run[j] += (uint64_t)__builtin_popcountll(bf);
+                    run[3 + j] += (uint64_t)__builtin_popcountll(br);
+                } else {
+                    cnt[j] += (uint32_t)__builtin_popcountll(bf);
+                    cnt[3 + j] += (uint32_t)__builtin_popcountll(br);
+                }
+            }
+            __syncthreads();
+        }
+        if (!FILL && lane == 0) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                if (cnt[j]) atomicAdd((unsigned long long*)(a.offsets + 1 + 6 * r + j), (unsigned long long)cnt[j]);
+                if (cnt[3 + j]) atomicAdd((unsigned long long*)(a.offsets + 1 + 6 * r + rframe[j]), (unsigned long long)cnt[3 + j]);
+            }
+        }
+    }
+    if (!FILL && lane < 6) {
+        uint32_t mine = 0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+            if (lane == (uint32_t)c) mine = cnt[c];
+        a.tails[(uint64_t)blockIdx.x * 6 + lane] = runs_on ? mine : 0u;
+    }
+}
+
+// Inclusive scan of x[0 .. m) in place by one workgroup: 8 entries per thread and round.
+__global__ __launch_bounds__(1024) void scan_kernel(uint64_t* x, uint64_t m) {
+    __shared__ uint64_t wsum[16];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t carry = 0;
+    for (uint64_t t0 = 0; t0 < m; t0 += 8192) {
+        const uint64_t i0 = t0 + (uint64_t)threadIdx.x * 8;
+        uint64_t v[8], sum = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            v[e] = i0 + e < m ? x[i0 + e] : 0;
+            sum += v[e];
+        }
+        uint64_t incl = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t up = __shfl_up(incl, d);
+            if ((int)lane >= d) incl += up;
+        }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        uint64_t before = 0, total = 0;
+        for (uint32_t w = 0; w < 16; ++w) {
+            if (w < wave) before += wsum[w];
+            total += wsum[w];
+        }
+        uint64_t run = carry + before + incl - sum;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            run += v[e];
+            if (i0 + e < m) x[i0 + e] = run;
+        }
+        carry += total;
+        __syncthreads();
+    }
+}
+
+// ---- hit list -----------------------------------------------------------------------------------------------------------
+// Tiles of kHitTile words of the hit matrix, 4 consecutive words per thread: the tiles' bit counts, their scan (scan_kernel),
+// then every thread writes the triples of its words from its rank.  The order is (word index, bit) = (query, bin).
+
+constexpr uint32_t kHitThreads = 256, kHitTile = 4 * kHitThreads;
+
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d);
+        if ((int)lane >= d) incl += up;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (uint32_t w = 0; w < kHitThreads / 64; ++w) {
+        if (w < wave) before += wsum[w];
+        all += wsum[w];
+    }
+    *total = all;
+    return before + incl - v;
+}
+
+__global__ __launch_bounds__(kHitThreads) void hit_count_kernel(const uint64_t* __restrict__ hits, uint64_t m, uint64_t* tile_pref) {
+    __shared__ uint32_t wsum[kHitThreads / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * kHitTile + threadIdx.x * 4u;
+    uint32_t c = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (i0 + e < m) c += (uint32_t)__builtin_popcountll(hits[i0 + e]);
+    uint32_t total;
+    (void)block_exclusive_scan(c, wsum, &total);
+    if (threadIdx.x == 0) {
+        tile_pref[(uint64_t)blockIdx.x + 1] = total;
+        if (blockIdx.x == 0) tile_pref[0] = 0;
+    }
+}
+
+__global__ __launch_bounds__(kHitThreads) void hit_fill_kernel(const uint64_t* __restrict__ hits, const uint32_t* __restrict__ counts, uint64_t m,
+                                                               uint64_t words, const uint64_t* __restrict__ tile_pref, uint64_t n_tiles,
+                                                               uint32_t* __restrict__ list, uint64_t capacity, uint64_t* total_out) {
+    __shared__ uint32_t wsum[kHitThreads / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * kHitTile + threadIdx.x * 4u;
+    uint64_t w[4];
+    uint32_t c = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        w[e] = i0 + e < m ? hits[i0 + e] : 0;
+        c += (uint32_t)__builtin_popcountll(w[e]);
+    }
+    uint32_t total;
+    uint64_t at = tile_pref[blockIdx.x] + block_exclusive_scan(c, wsum, &total);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *total_out = tile_pref[n_tiles];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        uint64_t bits = w[e];
+        if (!bits) continue;
+        const uint64_t q = (i0 + e) / words, word = (i0 + e) % words;
+        while (bits && at < capacity) {
+            const uint32_t bin = (uint32_t)(word * 64) + (uint32_t)__builtin_ctzll(bits);
+            bits &= bits - 1;
+            list[3 * at] = (uint32_t)q;
+            list[3 * at + 1] = bin;
+            list[3 * at + 2] = counts ? counts[q * words * 64 + bin] : 0u;
+            ++at;
+        }
+        at += (uint64_t)__builtin_popcountll(bits);  // (what did not fit still counts towards the ranks that follow)
+    }
+}
+
+int translate_args(const void* seq, const void* rec, size_t n, unsigned k, const void* codes, const void* values, const void* offsets) {
+    if (k < 1 || k > kMaxK) return fail(TXQ_ERR_ARG, "k = %u: translated k-mers need k in 1..12", k);
+    if (!offsets || (n && (!rec || !codes))) return fail(TXQ_ERR_ARG, "null argument");
+    (void)seq; (void)values;  // (may be null where there are no bytes / no values: only the caller knows)
+    if (n > 0x7FFFFFFFull / 6) return fail(TXQ_ERR_ARG, "at most 2^31 / 6 records per call");
+    return TXQ_OK;
+}
+
+}  // namespace
+}  // namespace txq
+
+using namespace txq;
+
+extern "C" {
+
+uint64_t txq_translate_bound(const uint64_t* rec_offsets, size_t n_records, unsigned k) {
+    if (k < 1 || k > kMaxK || (n_records && !rec_offsets)) {
+        (void)fail(TXQ_ERR_ARG, "txq_translate_bound: null offsets or k outside 1..12");
+        return UINT64_MAX;
+    }
+    uint64_t bound = 0;
+    for (size_t r = 0; r < n_records; ++r) {
+        if (rec_offsets[r + 1] < rec_offsets[r]) {
+            (void)fail(TXQ_ERR_ARG, "record offsets are not ascending at record %zu", r);
+            return UINT64_MAX;
+        }
+        const uint64_t L = rec_offsets[r + 1] - rec_offsets[r];
+        for (uint64_t o = 0; o < 3; ++o) {
+            const uint64_t codons = L >= o ? (L - o) / 3 : 0;
+            if (codons >= k) bound += 2 * (codons - k + 1);
+        }
+    }
+    return bound;
+}
+
+int txq_translate_device(const uint8_t* d_seq, const uint64_t* d_rec_offsets, size_t n_records, unsigned k, const uint8_t* d_codes,
+                         uint64_t* d_values, uint64_t* d_offsets, void* stream) {
+    if (int rc = translate_args(d_seq, d_rec_offsets, n_records, k, d_codes, d_values, d_offsets)) return rc;
+    if (int rc = require_init()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t m = 6 * n_records;
+    hipError_t e = hipMemsetAsync(d_offsets, 0, (m + 1) * 8, st);
+    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
+    if (n_records == 0) return TXQ_OK;
+    void* tails = nullptr;
+    if (e = hipMallocAsync(&tails, (size_t)kUnits * 6 * 4, st); e != hipSuccess) return fail_hip(e, "hipMallocAsync");
+    const TrArgs a{d_seq, d_rec_offsets, (uint64_t)n_records, k, d_codes, d_values, d_offsets, (uint32_t*)tails};
+    translate_kernel<false><<<kUnits, 64, 0, st>>>(a);
+    scan_kernel<<<1, 1024, 0, st>>>(d_offsets + 1, m);
+    translate_kernel<true><<<kUnits, 64, 0, st>>>(a);
+    e = hipGetLastError();
+    const hipError_t ef = hipFreeAsync(tails, st);
+    if (e != hipSuccess) return fail_hip(e, "translate kernel launch");
+    if (ef != hipSuccess) return fail_hip(ef, "hipFreeAsync");
+    return TXQ_OK;
+}
+
+int txq_translate(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_records, unsigned k, const uint8_t* codes, uint64_t* values,
+                  uint64_t* offsets) {
+    if (int rc = translate_args(seq, rec_offsets, n_records, k, codes, values, offsets)) return rc;
+    const uint64_t bound = txq_translate_bound(rec_offsets, n_records, k);
+    if (bound == UINT64_MAX) return TXQ_ERR_ARG;
+    const uint64_t first = n_records ? rec_offsets[0] : 0, bytes = n_records ? rec_offsets[n_records] - first : 0;
+    if ((bytes && !seq) || (bound && !values)) return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = require_init()) return rc;
+    const size_t m = 6 * n_records;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_seq = up(bytes + 16), b_rec = up((n_records + 1) * 8), b_codes = 256, b_off = up((m + 1) * 8), b_val = up(bound * 8 + 8);
+    unsigned char* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, b_seq + b_rec + b_codes + b_off + b_val);
+    if (e != hipSuccess) return fail_hip(e, "hipMalloc");
+    uint8_t* d_seq = d;
+    uint64_t* d_rec = (uint64_t*)(d + b_seq);
+    uint8_t* d_codes = d + b_seq + b_rec;
+    uint64_t* d_off = (uint64_t*)(d + b_seq + b_rec + b_codes);
+    uint64_t* d_val = (uint64_t*)(d + b_seq + b_rec + b_codes + b_off);
+    std::vector<uint64_t> rebased(rec_offsets, rec_offsets + n_records + 1);
+    for (uint64_t& o : rebased) o -= first;
+    int rc = TXQ_OK;
+    if (bytes) e = hipMemcpy(d_seq, seq + first, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rec, rebased.data(), rebased.size() * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_records) e = hipMemcpy(d_codes, codes, 256, hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = txq_translate_device(d_seq, d_rec, n_records, k, d_codes, d_val, d_off, nullptr);
+    if (e == hipSuccess && rc == TXQ_OK) e = hipMemcpy(offsets, d_off, (m + 1) * 8, hipMemcpyDeviceToHost);  // (waits for the kernels)
+    if (e == hipSuccess && rc == TXQ_OK && offsets[m]) {
+        if (offsets[m] > bound) rc = fail(TXQ_ERR_OVERFLOW, "translation produced more values than its bound");
+        else e = hipMemcpy(values, d_val, offsets[m] * 8, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail_hip(e, "txq_translate copies");
+    return rc;
+}
+
+int txq_hit_list_device(const uint64_t* d_hits, const uint32_t* d_counts, size_t n_queries, size_t words, uint32_t* d_list,
+                        size_t capacity, uint64_t* d_total, void* stream) {
+    if (!d_total || (n_queries && words && !d_hits) || (capacity && !d_list)) return fail(TXQ_ERR_ARG, "null argument");
+    if (n_queries >= 0xFFFFFFFFull || words > 0x3FFFFFFull) return fail(TXQ_ERR_ARG, "queries and bins must fit 32 bits");
+    if (int rc = require_init()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t m = (uint64_t)n_queries * words;
+    if (m == 0) {
+        const hipError_t e = hipMemsetAsync(d_total, 0, 8, st);
+        return e == hipSuccess ? TXQ_OK : fail_hip(e, "hipMemsetAsync");
+    }
+    const uint64_t n_tiles = (m + kHitTile - 1) / kHitTile;
+    if (n_tiles > 0x7FFFFFFFull) return fail(TXQ_ERR_ARG, "hit matrix too large for one call");
+    void* pref = nullptr;
+    if (hipError_t e = hipMallocAsync(&pref, (n_tiles + 1) * 8, st); e != hipSuccess) return fail_hip(e, "hipMallocAsync");
+    hit_count_kernel<<<(unsigned)n_tiles, kHitThreads, 0, st>>>(d_hits, m, (uint64_t*)pref);
+    scan_kernel<<<1, 1024, 0, st>>>((uint64_t*)pref + 1, n_tiles);
+    hit_fill_kernel<<<(unsigned)n_tiles, kHitThreads, 0, st>>>(d_hits, d_counts, m, words, (const uint64_t*)pref, n_tiles, d_list, capacity, d_total);
+    const hipError_t e = hipGetLastError();
+    const hipError_t ef = hipFreeAsync(pref, st);
+    if (e != hipSuccess) return fail_hip(e, "hit list kernel launch");
+    if (ef != hipSuccess) return fail_hip(ef, "hipFreeAsync");
+    return TXQ_OK;
+}
+
+}  // extern "C"

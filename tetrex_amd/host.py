@@ -239,6 +239,50 @@ def record_values_array(seq, k, dna=True, reduction=0, wraparound=False):
     return out[:n].copy()
 
 
+FRAMES = ("+1", "+2", "+3", "-1", "-2", "-3")
+
+
+def translate_frame(seq, frame):
+    """One of the six frames (0..5 = +1 +2 +3 -1 -2 -3) of a nucleotide record as residue letters (NCBI table 1; X for a codon
+    with an ambiguous byte, * for a stop)."""
+    L = lib()
+    L.txh_translate_frame.restype = C.c_int64
+    L.txh_translate_frame.argtypes = [C.c_char_p, C.c_size_t, C.c_uint, C.c_char_p, C.c_size_t]
+    s = seq.encode() if isinstance(seq, str) else bytes(seq)
+    buf = C.create_string_buffer(len(s) // 3 + 1)
+    n = L.txh_translate_frame(s, len(s), frame, buf, len(buf))
+    if n < 0:
+        raise _err()
+    return buf.raw[:n].decode()
+
+
+def translated_values(seq, k, reduction=0):
+    """txh_translated_values: the k-mer values of the six frames of one nucleotide record for a peptide index, frame after
+    frame.  Returns (values uint64[], offsets uint64[7])."""
+    L = lib()
+    L.txh_translated_values.restype = C.c_int64
+    L.txh_translated_values.argtypes = [C.c_uint, C.c_uint, C.c_char_p, C.c_size_t, u64p, C.c_size_t, u64p]
+    s = seq.encode() if isinstance(seq, str) else bytes(seq)
+    cap = 2 * len(s) + 8
+    out = np.zeros(cap, dtype=np.uint64)
+    off = np.zeros(7, dtype=np.uint64)
+    n = L.txh_translated_values(k, reduction, s, len(s), out.ctypes.data_as(u64p), cap, off.ctypes.data_as(u64p))
+    if n < 0:
+        raise _err()
+    assert n <= cap
+    return out[:n].copy(), off
+
+
+def peptide_codes(reduction=0):
+    """The 256-byte residue code table of the peptide encoder (what capi.translate takes as `codes`)."""
+    L = lib()
+    L.txh_peptide_codes.argtypes = [C.c_uint, C.POINTER(C.c_uint8)]
+    out = np.zeros(256, dtype=np.uint8)
+    if L.txh_peptide_codes(reduction, out.ctypes.data_as(C.POINTER(C.c_uint8))) < 0:
+        raise _err()
+    return out
+
+
 def parse_blob(blob):
     """Decode a txq_program.h blob (version 1, 2 or 4): (kmers uint64[], [(n_slots, ops array [n,4] =
     kmer,dst,a,b)]).  Version-2/4 ops are in level order, which is also a valid sequential order.
