@@ -700,3 +700,69 @@ def test_blocks_are_pooled_with_the_index_from_batch_to_batch(capi, oracle, monk
             elif w is not None:
                 assert st == 0 and np.array_equal(g, w), (q, which, tracked)
     ix.free()
+
+
+def test_every_hash_count_and_lane_width_of_every_row_source(capi, oracle, monkeypatch):
+    """The host-side dispatch of dense_kernel / sparse_kernel / sparse_units_kernel (csrc/txq_exec.hip with_rows) has one arm
+    per row source, hash count (1 .. 5) and lane width; the other tests take them at h = 2, 3 (and 4 on one flat index).
+    Here every arm is walked on the smallest indexes that take it: DNA k = 3 (a table of 64 rows), masks of one word, of three
+    (8-byte lanes) and of four (16-byte lanes); flat indexes through their rows and through the table of all k-mers' masks,
+    full and tracked blocks; regular trees through the interleaved children, TreeRows and TreeRowsByLane.  Bit-equal to the
+    oracle, and only on masks that say something: neither empty nor full."""
+    from helpers import regular_hibf
+    monkeypatch.setenv("TETREX_DENSE_MIN", "1")
+    monkeypatch.setenv("TETREX_DENSE_SPARSE_BELOW", "0")
+    monkeypatch.setenv("TXQ_KMER_TABLE_MIN", "1")
+    qs = ["ACG..T.GA", "A.{2,4}CGT.A", "AC[GT]..[AC]CGT", "ACGTTGCA", "T.G.C.A.T", "GG(A|C)T.{1,2}CA"]
+
+    def informative(want, bins):
+        n = int(sum(bin(int(w)).count("1") for w in want))
+        assert 0 < n < bins, (n, bins)
+
+    compared = 0
+    for h in (1, 2, 3, 4, 5):
+        for bins in (40, 187, 256):
+            rng = np.random.default_rng(1000 * h + bins)
+            ox = oracle.Index.ibf(bins, 257, h, dna=True, k=3)
+            for b in range(bins):
+                ox.emplace(rng.choice(64, 44, replace=False).astype(np.uint64), b)
+            wants = _wants(ox, qs)
+            for w in wants:
+                informative(w, bins)
+            for table_mb in ("512", "0"):
+                for tracked in (None, "1"):
+                    monkeypatch.setenv("TXQ_KMER_TABLE_MB", table_mb)
+                    if tracked:
+                        monkeypatch.setenv("TETREX_DENSE_TRACKED", tracked)
+                    else:
+                        monkeypatch.delenv("TETREX_DENSE_TRACKED", raising=False)
+                    checked, dense_ops = _check(capi, ox, qs, True, 3, wants=wants)
+                    assert checked == len(qs) and dense_ops > 0, (h, bins, table_mb, tracked)
+                    assert not tracked or TRACKED[0] > 0, (h, bins, table_mb)
+            compared += len(wants)
+    assert compared == 90
+    monkeypatch.delenv("TETREX_DENSE_TRACKED", raising=False)
+
+    monkeypatch.setenv("TXQ_KMER_TABLE_MB", "0")
+    compared = 0
+    for ub, children in ((256, 4), (300, 5)):
+        for h in (1, 3, 5):
+            rng = np.random.default_rng(7 * h + ub)
+            ox, descs, _ = regular_hibf(oracle, ub, children, 44, lambda b: rng.choice(64, 44, replace=False).astype(np.uint64), h=h, dna=True, k=3)
+            wants = [ox.expected_mask(q)[0] for q in qs]
+            for w in wants:
+                informative(w, ub)
+            ix = capi.Index.upload_hibf(ub, descs)
+            for dense_tree in (None, "1", "2"):
+                if dense_tree:
+                    monkeypatch.setenv("TXQ_DENSE_TREE", dense_tree)
+                else:
+                    monkeypatch.delenv("TXQ_DENSE_TREE", raising=False)
+                got, status, stats = ix.query_masks(qs, True, 3)
+                assert stats["dense_ops"] > 0, (ub, h, dense_tree)
+                for q, g, st, w in zip(qs, got, status, wants):
+                    assert st == 0, q
+                    assert np.array_equal(g, w), (q, ub, h, dense_tree)
+            ix.free()
+            compared += len(wants)
+    assert compared == 36

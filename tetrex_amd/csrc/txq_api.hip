@@ -119,12 +119,6 @@ static int bind_index(const Index* ix) {
     return bind_device(ix ? ix->device : g_devices[0]);
 }
 
-#define TXQ_HIP(call)                                        \
-    do {                                                     \
-        hipError_t e_ = (call);                              \
-        if (e_ != hipSuccess) return fail_hip(e_, #call);    \
-    } while (0)
-
 // shard r of R owns mask words [lo, hi): as even as possible, earlier shards get the remainder
 static void shard_range(uint64_t words, int r, int R, uint64_t* lo, uint64_t* hi) {
     uint64_t base = words / R, rem = words % R;

@@ -278,23 +278,7 @@ __global__ __launch_bounds__(64) void count_hibf_level_kernel(HibfCountView t, C
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------
 
-#define TXQ_HIP(call)                                        \
-    do {                                                     \
-        hipError_t e_ = (call);                              \
-        if (e_ != hipSuccess) return fail_hip(e_, #call);    \
-    } while (0)
-
 static constexpr unsigned kCountGrid = 4096;  // waves of a call (persistent: the work is only known on the device)
-
-#define TXQ_COUNT_H_SWITCH(H_, LAUNCH)                      \
-    switch (H_) {                                          \
-        case 1: LAUNCH(1); break;                          \
-        case 2: LAUNCH(2); break;                          \
-        case 3: LAUNCH(3); break;                          \
-        case 4: LAUNCH(4); break;                          \
-        case 5: LAUNCH(5); break;                          \
-        default: return fail(TXQ_ERR_ARG, "hash_funs outside 1..5"); \
-    }
 
 static int count_flat(Index& ix, CountOut o, hipStream_t s) {
     const IbfDev& f = ix.ibf[0];
@@ -320,9 +304,8 @@ static int count_flat(Index& ix, CountOut o, hipStream_t s) {
         c.acc = o.counts ? c.counts : ix.scratch_count_acc;
         const unsigned qgrid = (unsigned)std::min<size_t>(c.nq, kCountGrid);
         count_zero_long_kernel<<<qgrid, 64, 0, s>>>(c);
-#define TXQ_FLAT(H) count_flat_kernel<H><<<kCountGrid, 64 * kFlatWaves, lds, s>>>(f, c, lpk_log2, n_tiles)
-        TXQ_COUNT_H_SWITCH(f.hash_funs, TXQ_FLAT)
-#undef TXQ_FLAT
+        if (!with_hash_funs(f.hash_funs, [&](auto h) { count_flat_kernel<decltype(h)::value><<<kCountGrid, 64 * kFlatWaves, lds, s>>>(f, c, lpk_log2, n_tiles); }))
+            return fail(TXQ_ERR_ARG, "hash_funs outside 1..5");
         count_finish_kernel<<<qgrid, 64, 0, s>>>(c);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail_hip(e, "count kernel launch");
@@ -366,11 +349,11 @@ static int count_hibf(Index& ix, CountOut o, hipStream_t s) {
             WorkItem* out = ix.frontier[lvl & 1];
             const uint32_t out_cap = ix.depth > 1 && lvl + 1 < ix.depth ? (uint32_t)cap : 0u;
             const unsigned grid = lvl ? kCountGrid : (unsigned)std::min<size_t>(c.nq, kCountGrid);
-#define TXQ_LEVEL(H)                                                                                                  \
-            count_hibf_level_kernel<H><<<grid, 64, lds_words * 4, s>>>(t, c, in, in_count, (uint32_t)cap, c.nq, out, ix.d_counts + lvl, \
-                                                                       out_cap, lds_words)
-            TXQ_COUNT_H_SWITCH(h_max, TXQ_LEVEL)
-#undef TXQ_LEVEL
+            if (!with_hash_funs(h_max, [&](auto h) {
+                    count_hibf_level_kernel<decltype(h)::value><<<grid, 64, lds_words * 4, s>>>(t, c, in, in_count, (uint32_t)cap, c.nq, out, ix.d_counts + lvl,
+                                                                                                out_cap, lds_words);
+                }))
+                return fail(TXQ_ERR_ARG, "hash_funs outside 1..5");
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return fail_hip(e, "hibf count kernel launch");
         }

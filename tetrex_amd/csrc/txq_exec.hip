@@ -1544,12 +1544,6 @@ __global__ __launch_bounds__(256) void gather_result_kernel(uint64_t* const* __r
     }
 }
 
-#define TXQ_HIP(call)                                        \
-    do {                                                     \
-        hipError_t e_ = (call);                              \
-        if (e_ != hipSuccess) return fail_hip(e_, #call);    \
-    } while (0)
-
 // Host-side validation: nothing malformed may reach the GPU (a stray slot or k-mer index would
 // be an out-of-bounds access there).  Accepts version 1 (op order), 2 (levels) and 3 (levels + dense
 // ops) blobs and normalises the program table.
@@ -2014,29 +2008,43 @@ static int grow_slot_regions(Session& s, const BlobView& bv, const unsigned char
 // Big level-scheduled programs, and every program with dense ops, leave the one-workgroup-per-program kernel:
 // their ops are cut into units per dependency level (units of level l, all programs, are contiguous in `units`),
 // their dense ops into tiles, and every level becomes one launch of each kind over the whole GPU.
-// Returns the number of programs left to exec_kernel.
 struct LevelPlan {
     size_t units = 0, tiles = 0, hsteps = 0, sparse = 0, sparse_chunks = 0;
-    // split_steps (flat indexes, tables of k-mer masks): the level's sparse groups are ordered [others | STEPs]; the first
-    // sparse_misc go to the sparse_kernel without step code, the STEPs to the one with it (sparse_chunks counts the others' chunks then)
+    // the level's sparse groups are ordered [others | STEPs]: the first sparse_misc go to the sparse_kernel without step code,
+    // the STEPs to the one with it (sparse_chunks counts the others' chunks)
     size_t sparse_misc = 0, step_chunks = 0;
+};
+// What plan_units makes of a stage's programs: the lists a stage uploads and the launches of its levels.
+struct StagePlan {
+    std::vector<ExecUnit> units;          // ordinary ops, level by level
+    std::vector<TileGroup> tile_groups;   // untracked dense ops; make_tiles_kernel cuts them into n_tiles tiles
+    size_t n_tiles = 0;
+    std::vector<DenseTile> hsteps;        // HIBF descent: the STEP tiles ...
+    std::vector<uint32_t> hstep_na;       // ... and their predecessors per suffix
+    std::vector<SparseGroup> sparse_groups;
+    std::vector<DenseOpPtr> optr;         // every dense op's blocks, indexed like the stage's dense table
+    std::vector<LevelPlan> levels;
+    size_t n_small = 0;                   // programs left to exec_kernel
+    uint64_t work[4] = {0, 0, 0, 0};      // step pairs, step suffixes, slots zeroed or filled, entries reduced (TXQ_TRACE)
+    // chunk_hibf_steps: chunk c = hsteps [chunk_first[c], chunk_first[c + 1]), pair_base[tile] = first pair of the tile within its chunk
+    std::vector<uint32_t> pair_base, chunk_pairs;
+    std::vector<size_t> chunk_first;
+    size_t most_pairs = 0;
 };
 // hibf: STEP tiles go to their own list (`hsteps`, with the number of predecessors per suffix in `hstep_na`): on an
 // HIBF a step is three launches (dense_hibf_*), not a tile of dense_kernel.
 // The dense ops of tracked programs become sparse groups (one per op; sparse_kernel), and every dense op's blocks are
 // resolved to pointers here (`optr`, indexed like the stage's dense table).
-static size_t plan_units(const Session& s, BlobView& bv, const unsigned char* blob, uint32_t W, uint32_t G_dense, bool hibf, bool split_steps, std::vector<ExecUnit>* units,
-                         std::vector<TileGroup>* groups, size_t* n_tiles, uint64_t (*work)[4], std::vector<DenseTile>* hsteps, std::vector<uint32_t>* hstep_na,
-                         std::vector<SparseGroup>* sparse, std::vector<DenseOpPtr>* optr, std::vector<LevelPlan>* plan) {
+static int plan_units(const Session& s, BlobView& bv, const unsigned char* blob, uint32_t W, uint32_t G_dense, bool hibf, StagePlan* out) {
     const uint32_t per_unit = unit_ops(W);
     const uint32_t* levels_host = bv.n_levels ? (const uint32_t*)(blob + bv.levels_offset) : nullptr;
     const txq_op* ops = (const txq_op*)(blob + bv.ops_offset);
     const txq_dense_op* dops = bv.n_dense ? (const txq_dense_op*)(blob + bv.dense_offset) : nullptr;
-    optr->assign(bv.n_dense, DenseOpPtr{nullptr, nullptr, 0, 0});
+    out->optr.assign(bv.n_dense, DenseOpPtr{nullptr, nullptr, 0, 0});
     std::vector<std::vector<ExecUnit>> per_level;
     std::vector<std::vector<TileGroup>> groups_level;
     std::vector<std::vector<DenseTile>> hsteps_level;
-    std::vector<std::vector<SparseGroup>> sparse_level, step_level;  // (step_level: the STEP groups when split_steps)
+    std::vector<std::vector<SparseGroup>> sparse_level, step_level;  // (step_level: the STEP groups)
     std::vector<size_t> sparse_chunks, step_chunks;
     // entries per tile: every lane-group set of the workgroup gets two destination suffixes of a step (TXQ_DENSE_TILE_ROUNDS)
     const uint32_t step_tile = (uint32_t)s.kn.dense_tile_rounds * (256 / (G_dense ? G_dense : 1));
@@ -2087,7 +2095,7 @@ static size_t plan_units(const Session& s, BlobView& bv, const unsigned char* bl
                     cut(run, i);
                     run = i + 1;
                     const txq_dense_op& x = dops[o.dst];
-                    DenseOpPtr& q = (*optr)[o.dst];
+                    DenseOpPtr& q = out->optr[o.dst];
                     if (x.kind == TXQ_DENSE_REDUCE) q.dst = slot_of(x.dst);
                     else { const Session::DenseBlock& b = block_of(x.dst); q.dst = b.p; q.dst_cap = b.cap; }
                     if (x.kind == TXQ_DENSE_STEP || x.kind == TXQ_DENSE_REDUCE) { const Session::DenseBlock& b = block_of(x.src); q.src = b.p; q.src_cap = b.cap; }
@@ -2097,7 +2105,7 @@ static size_t plan_units(const Session& s, BlobView& bv, const unsigned char* bl
                     if (x.reserved & TXQ_DENSE_TRACKED) {  // work follows the block's live list (FILL: its shape)
                         const bool fixed = x.kind == TXQ_DENSE_FILL;
                         if (fixed && !shape_entries) continue;
-                        const bool to_steps = split_steps && x.kind == TXQ_DENSE_STEP;
+                        const bool to_steps = x.kind == TXQ_DENSE_STEP;
                         (to_steps ? step_level : sparse_level)[l].push_back(SparseGroup{o.dst, fixed ? (uint32_t)shape_entries : kNotFixed});
                         // most chunks this group can turn out to have: a list never outgrows its block
                         const uint64_t most = fixed ? shape_entries : x.kind == TXQ_DENSE_ZERO ? q.dst_cap : q.src_cap;
@@ -2113,9 +2121,9 @@ static size_t plan_units(const Session& s, BlobView& bv, const unsigned char* bl
                         if (x.kind == TXQ_DENSE_STEP) entries *= (uint64_t)__builtin_popcount(x.r_mask) * (__builtin_popcount(x.shape[0]) ? 1 : 0);
                         else per_tile = 1024;
                     }
-                    if (x.kind == TXQ_DENSE_STEP) { (*work)[0] += entries * (uint64_t)__builtin_popcount(x.shape[0]); (*work)[1] += entries; }
-                    else if (x.kind == TXQ_DENSE_REDUCE) (*work)[3] += entries;
-                    else (*work)[2] += entries;
+                    if (x.kind == TXQ_DENSE_STEP) { out->work[0] += entries * (uint64_t)__builtin_popcount(x.shape[0]); out->work[1] += entries; }
+                    else if (x.kind == TXQ_DENSE_REDUCE) out->work[3] += entries;
+                    else out->work[2] += entries;
                     const bool hstep = hibf && x.kind == TXQ_DENSE_STEP;
                     if (hstep) per_tile = 256;  // 256 suffixes x up to 32 predecessors: at most 8192 k-mers per tile
                     if (!hstep) {
@@ -2131,113 +2139,61 @@ static size_t plan_units(const Session& s, BlobView& bv, const unsigned char* bl
         }
         d.n_ops = 0;  // the per-program kernel skips it
     }
-    if (bad_program >= 0) {
-        (void)fail(TXQ_ERR_PROGRAM, "program %d: an op on a dense block that no ZERO has created, or beyond its capacity", bad_program);
-        return (size_t)-1;
-    }
-    plan->resize(per_level.size());
+    if (bad_program >= 0)
+        return fail(TXQ_ERR_PROGRAM, "program %d: an op on a dense block that no ZERO has created, or beyond its capacity", bad_program);
+    out->levels.resize(per_level.size());
     for (size_t l = 0; l < per_level.size(); ++l) {
-        (*plan)[l].units = per_level[l].size();
+        out->levels[l].units = per_level[l].size();
         size_t level_tiles = 0;
         for (TileGroup& g : groups_level[l]) {
-            g.first_tile = *n_tiles + level_tiles;
+            g.first_tile = out->n_tiles + level_tiles;
             level_tiles += (g.entries + g.per_tile - 1) / g.per_tile;
         }
-        (*plan)[l].tiles = level_tiles;
-        *n_tiles += level_tiles;
-        groups->insert(groups->end(), groups_level[l].begin(), groups_level[l].end());
-        (*plan)[l].hsteps = hsteps_level[l].size();
-        (*plan)[l].sparse = sparse_level[l].size() + step_level[l].size();
-        (*plan)[l].sparse_misc = sparse_level[l].size();
-        (*plan)[l].sparse_chunks = sparse_chunks[l];
-        (*plan)[l].step_chunks = step_chunks[l];
-        sparse->insert(sparse->end(), sparse_level[l].begin(), sparse_level[l].end());
-        sparse->insert(sparse->end(), step_level[l].begin(), step_level[l].end());
-        units->insert(units->end(), per_level[l].begin(), per_level[l].end());
+        out->levels[l].tiles = level_tiles;
+        out->n_tiles += level_tiles;
+        out->tile_groups.insert(out->tile_groups.end(), groups_level[l].begin(), groups_level[l].end());
+        out->levels[l].hsteps = hsteps_level[l].size();
+        out->levels[l].sparse = sparse_level[l].size() + step_level[l].size();
+        out->levels[l].sparse_misc = sparse_level[l].size();
+        out->levels[l].sparse_chunks = sparse_chunks[l];
+        out->levels[l].step_chunks = step_chunks[l];
+        out->sparse_groups.insert(out->sparse_groups.end(), sparse_level[l].begin(), sparse_level[l].end());
+        out->sparse_groups.insert(out->sparse_groups.end(), step_level[l].begin(), step_level[l].end());
+        out->units.insert(out->units.end(), per_level[l].begin(), per_level[l].end());
         for (const DenseTile& t : hsteps_level[l]) {
-            hsteps->push_back(t);
-            hstep_na->push_back((uint32_t)__builtin_popcount(dops[t.op].shape[0]));
+            out->hsteps.push_back(t);
+            out->hstep_na.push_back((uint32_t)__builtin_popcount(dops[t.op].shape[0]));
         }
     }
-    return n_small;
+    out->n_small = n_small;
+    return TXQ_OK;
 }
 
-// rows_of(H) makes the kernel's row source for H hash functions (FlatRows / TreeRows)
-template <bool WIDE, template <int, bool> class ROWS, class MAKE>
-static hipError_t launch_dense(int ua, uint32_t hash_funs, MAKE rows_of, const DenseTile* tiles, size_t n_tiles, const txq_dense_op* dops, const DenseOpPtr* optr,
-                               uint64_t* const* base, uint32_t n_programs, uint32_t W, uint32_t G, uint32_t SL, const DenseParams& P, const LevelUnits& U, hipStream_t st) {
-    const size_t grid = n_tiles + U.n_units;
-    // ua: predecessors in flight per lane (TXQ_DENSE_UNROLL: A/B knob)
-#define TXQ_DENSE(H) \
-    do { \
-        ROWS<H, WIDE> rows{}; \
-        rows_of(rows); \
-        if (ua >= 5) dense_kernel<H, WIDE, 5, ROWS<H, WIDE>><<<(unsigned)grid, 256, 0, st>>>(rows, tiles, dops, optr, base, n_programs, W, G, SL, P, U); \
-        else if (ua <= 2) dense_kernel<H, WIDE, 2, ROWS<H, WIDE>><<<(unsigned)grid, 256, 0, st>>>(rows, tiles, dops, optr, base, n_programs, W, G, SL, P, U); \
-        else dense_kernel<H, WIDE, 3, ROWS<H, WIDE>><<<(unsigned)grid, 256, 0, st>>>(rows, tiles, dops, optr, base, n_programs, W, G, SL, P, U); \
-    } while (0)
-    switch (hash_funs) {
-        case 1: TXQ_DENSE(1); break;
-        case 2: TXQ_DENSE(2); break;
-        case 3: TXQ_DENSE(3); break;
-        case 4: TXQ_DENSE(4); break;
-        case 5: TXQ_DENSE(5); break;
-        default: return hipErrorInvalidValue;
+// HIBF steps run in chunks of tiles whose masks fit the scratch (2 GiB), never across a level.
+static void chunk_hibf_steps(StagePlan& plan, uint32_t W) {
+    plan.pair_base.assign(plan.hsteps.size(), 0);
+    const uint64_t budget = std::max<uint64_t>(((uint64_t)2 << 30) / ((uint64_t)W * 8), 8192);
+    size_t at = 0;
+    for (const LevelPlan& lp : plan.levels) {
+        uint64_t pairs = 0;
+        for (size_t i = 0; i < lp.hsteps; ++i, ++at) {
+            const uint64_t mine = (uint64_t)plan.hsteps[at].count * plan.hstep_na[at];
+            if (i == 0 || pairs + mine > budget) {
+                plan.chunk_first.push_back(at);
+                plan.chunk_pairs.push_back(0);
+                pairs = 0;
+            }
+            plan.pair_base[at] = (uint32_t)pairs;
+            pairs += mine;
+            plan.chunk_pairs.back() = (uint32_t)pairs;
+        }
     }
-#undef TXQ_DENSE
-    return hipGetLastError();
-}
-
-// the level's sparse groups [groups, groups + n_groups) (n_groups <= kMaxSparseGroups): `grid` workgroups share their chunks out
-template <bool WIDE, template <int, bool> class ROWS, class MAKE>
-static hipError_t launch_sparse(uint32_t hash_funs, MAKE rows_of, const SparseGroup* groups, uint32_t n_groups, const uint32_t* counts, const uint32_t* prefix,
-                                size_t grid, const txq_dense_op* dops, const DenseOpPtr* optr, uint64_t* const* base, uint32_t n_programs, uint32_t W, uint32_t G,
-                                const DenseParams& P, const LevelUnits& U, uint32_t chunk, hipStream_t st) {
-#define TXQ_SPARSE(H) \
-    do { \
-        ROWS<H, WIDE> rows{}; \
-        rows_of(rows); \
-        sparse_kernel<H, WIDE, ROWS<H, WIDE>><<<(unsigned)grid, 256, 0, st>>>(rows, groups, n_groups, counts, prefix, dops, optr, base, n_programs, W, G, P, U, chunk); \
-    } while (0)
-    switch (hash_funs) {
-        case 1: TXQ_SPARSE(1); break;
-        case 2: TXQ_SPARSE(2); break;
-        case 3: TXQ_SPARSE(3); break;
-        case 4: TXQ_SPARSE(4); break;
-        case 5: TXQ_SPARSE(5); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef TXQ_SPARSE
-    return hipGetLastError();
+    for (uint32_t c : plan.chunk_pairs) plan.most_pairs = std::max<size_t>(plan.most_pairs, c);
+    plan.chunk_first.push_back(plan.hsteps.size());
 }
 
 __global__ __launch_bounds__(256) void iota_kernel(uint64_t* __restrict__ v, uint64_t n) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) v[i] = i;
-}
-
-// the STEP groups of a level on narrow masks (sparse_units_kernel)
-template <bool WIDE, template <int, bool> class ROWS, class MAKE>
-static hipError_t launch_sparse_units(uint32_t hash_funs, MAKE rows_of, const SparseGroup* groups, uint32_t n_groups, const uint32_t* counts, const uint32_t* prefix,
-                                      size_t grid, const txq_dense_op* dops, const DenseOpPtr* optr, uint64_t* const* base, uint32_t n_programs, uint32_t W, uint32_t G,
-                                      const StepParams& P, const LevelUnits& U, unsigned long long* ctr, int ua, hipStream_t st) {
-    // ua: units in flight per lane group (TXQ_SPARSE_UNROLL: A/B knob; 3 fits the 128 VGPRs of four waves per SIMD up to h = 3)
-#define TXQ_UNITS(H) \
-    do { \
-        ROWS<H, WIDE> rows{}; \
-        rows_of(rows); \
-        if (ua <= 2 || H >= 4) sparse_units_kernel<H, WIDE, 2, ROWS<H, WIDE>><<<(unsigned)grid, 256, 0, st>>>(rows, groups, n_groups, counts, prefix, dops, optr, base, n_programs, W, G, P, U, ctr); \
-        else sparse_units_kernel<H, WIDE, 3, ROWS<H, WIDE>><<<(unsigned)grid, 256, 0, st>>>(rows, groups, n_groups, counts, prefix, dops, optr, base, n_programs, W, G, P, U, ctr); \
-    } while (0)
-    switch (hash_funs) {
-        case 1: TXQ_UNITS(1); break;
-        case 2: TXQ_UNITS(2); break;
-        case 3: TXQ_UNITS(3); break;
-        case 4: TXQ_UNITS(4); break;
-        case 5: TXQ_UNITS(5); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef TXQ_UNITS
-    return hipGetLastError();
 }
 
 // The table of all k-mers' masks of an index (Index::kmer_table), built once per index when the first stage with dense steps
@@ -2281,181 +2237,398 @@ static bool ensure_kmer_table(Index& ix, const Knobs& kn, const DenseParams& P, 
     return true;
 }
 
-int session_stage(Session& s, const void* blob_v, size_t bytes, const uint32_t* q_prog, const uint32_t* q_slot, size_t n_q,
-                  uint8_t* alive, hipStream_t caller_stream) {
-    Index& ix = *s.ix;
-    const unsigned char* blob = (const unsigned char*)blob_v;
+// Where the dense ops of a stage take M[k-mer] from and how its lanes are grouped: decided once per stage (decide_rows);
+// everything after it asks this value.
+struct RowSource {
+    enum Kind : uint8_t {
+        Flat,         // FlatRows: the flat IBF's hash_funs rows
+        Table,        // TableRows: one row of the index's table of all k-mers' masks (flat index or any HIBF)
+        Tree,         // TreeRows: a regular two-level HIBF, root and child per lane
+        TreeByLane,   // TreeRowsByLane in dense_kernel (root words by lane, through LDS); TreeRows in sparse_kernel
+        Interleaved,  // InterleavedRows: the interleaved copy of a small regular tree's uniform children
+        Path,         // PathRows: a general HIBF, masks in layout order
+        Descent       // any other HIBF: a step is k-mers -> hibf_probe -> combine (StagePlan::hsteps); its other dense ops use FlatRows' kernels, which never ask for a row
+    };
+    Kind kind = Flat;
+    bool wide = false;           // 16-byte lanes: masks and rows are whole pairs of words
+    uint32_t hash_funs = 0;      // the kernels' H
+    uint32_t wpr_log2 = 0;       // tree kinds: log2 of a child's row words
+    uint32_t g = 1, slices = 1;  // lanes per destination suffix; lane groups that share the predecessors of one suffix (TXQ_DENSE_SLICES)
+    const char* name = "none";   // TXQ_TRACE
+    // dense steps run inside dense_kernel / the sparse kernels, so a level's ordinary units may ride in those launches
+    bool fused() const { return kind != Descent; }
+    // narrow masks of a flat index or a table: a level's tracked STEPs are shared out by units (sparse_units_kernel)
+    bool by_units(const Knobs& kn, uint32_t W) const { return kn.sparse_steps && W <= kUnitStepWords && (kind == Flat || kind == Table); }
+};
+
+static RowSource decide_rows(const Index& ix, const Session& s, bool table) {
+    const Knobs& kn = s.kn;
+    const uint32_t W = s.W;
+    RowSource r;
+    bool even_rows = false;  // a lane may read 16 bytes of a row
+    // dense steps on a regular two-level HIBF run fused, too (TXQ_DENSE_TREE=0 sends them through the generic HIBF path)
+    const bool tree = !table && index_fuses_tree_steps(ix, kn);
+    if (s.vspace) {
+        r.kind = RowSource::Path, r.hash_funs = ix.tree_hash_max, even_rows = ix.v_chunk_words == 2;
+        r.name = "general tree in layout order, fused";
+    } else if (table) {
+        r.kind = RowSource::Table, r.hash_funs = 1, even_rows = true;
+        r.name = ix.is_hibf ? "HIBF through its table of all k-mers' masks" : "flat IBF through its table of all k-mers' masks";
+    } else if (tree) {
+        r.hash_funs = ix.tree_hash_max;
+        while ((1u << r.wpr_log2) < ix.child_row_words) ++r.wpr_log2;
+        if (ix.interleaved.words && ix.interleaved.shard_words == W && ix.root_node.bins <= 64 && kn.dense_tree < 0) {
+            r.kind = RowSource::Interleaved, even_rows = ix.interleaved.stride % 2 == 0;
+            r.name = "regular tree, interleaved children, fused";
+        } else {
+            r.kind = RowSource::Tree, even_rows = ix.child_row_words >= 2;  // (or TreeByLane, below)
+            r.name = "regular tree, fused";
+        }
+    } else if (ix.is_hibf) {
+        r.kind = RowSource::Descent, r.hash_funs = ix.ibf[0].hash_funs;
+        r.name = "HIBF descent";
+    } else {
+        r.kind = RowSource::Flat, r.hash_funs = ix.ibf[0].hash_funs, even_rows = ix.ibf[0].stride % 2 == 0;
+        r.name = "flat IBF, fused";
+    }
+    // 16-byte lanes where masks and rows allow it, g lanes per destination suffix ...
+    r.wide = W % 2 == 0 && even_rows;
+    while (r.g < 64 && r.g < (r.wide ? W / 2 : W)) r.g <<= 1;
+    // ... and two such lane groups share the predecessors of one suffix (TXQ_DENSE_SLICES: A/B knob; on the bench batch
+    // 1 / 2 / 4 / 8 slices took 34 / 30 / 34 / 44+ ms end to end: more slices shorten a tile's load chain but multiply the tiles)
+    while (r.slices * 2 <= (uint32_t)kn.dense_slices && r.g * r.slices * 2 <= 64) r.slices <<= 1;
+    // root of <= 64 merged bins and the suffix's lanes cover the mask: root words by lane (TXQ_DENSE_TREE=1: the general variant)
+    if (r.kind == RowSource::Tree && (256u / (r.g * r.slices)) * 32u * ix.root_node.stride() <= kRootWordsLds && kn.dense_tree != 1)
+        r.kind = RowSource::TreeByLane;
+    return r;
+}
+
+// The one place that knows how each policy's fields are set from the index: f(rows, tag) with the filled-in ROWS<H, WIDE>
+// object and tag = RowsTag<its kind, H, WIDE>.  False: hash_funs outside 1..5, f not called.  A launcher's f leaves the
+// combinations its kernel is never launched with out with `if constexpr` on the tag.
+template <RowSource::Kind K, int H_, bool WIDE_>
+struct RowsTag {
+    static constexpr RowSource::Kind kind = K;
+    static constexpr int H = H_;
+    static constexpr bool WIDE = WIDE_;
+};
+template <class F>
+static bool with_rows(const RowSource& rs, const Index& ix, uint32_t W, F&& f) {
+    bool ok = true;
+    with_bool(rs.wide, [&](auto wide) {
+        constexpr bool WIDE = decltype(wide)::value;
+        if (rs.kind == RowSource::Table) {  // one row per k-mer: H = 1, whatever the index's hash count
+            TableRows<1, WIDE> r{};
+            r.table = ix.kmer_table, r.stride = W;
+            f(r, RowsTag<RowSource::Table, 1, WIDE>{});
+            return;
+        }
+        ok = with_hash_funs(rs.hash_funs, [&](auto h) {
+            constexpr int H = decltype(h)::value;
+            auto tree = [&](auto& r) { r.root = ix.root_node, r.children = (const ChildRec*)ix.d_children, r.wpr_log2 = rs.wpr_log2; };
+            switch (rs.kind) {
+                case RowSource::Tree: { TreeRows<H, WIDE> r{}; tree(r); f(r, RowsTag<RowSource::Tree, H, WIDE>{}); break; }
+                case RowSource::TreeByLane: { TreeRowsByLane<H, WIDE> r{}; tree(r); f(r, RowsTag<RowSource::TreeByLane, H, WIDE>{}); break; }
+                case RowSource::Interleaved: { InterleavedRows<H, WIDE> r{}; r.f = ix.interleaved; tree(r); f(r, RowsTag<RowSource::Interleaved, H, WIDE>{}); break; }
+                case RowSource::Path: {
+                    PathRows<H, WIDE> r{};
+                    r.chunks = ix.d_vchunks, r.paths = ix.d_vpaths, r.split_range = ix.d_vsplit_range, r.splits = ix.d_vsplits;
+                    f(r, RowsTag<RowSource::Path, H, WIDE>{});
+                    break;
+                }
+                default: { FlatRows<H, WIDE> r{}; r.f = ix.ibf[0]; f(r, RowsTag<RowSource::Flat, H, WIDE>{}); break; }  // Flat, Descent
+            }
+        });
+    });
+    return ok;
+}
+
+// The tables a stage sends to the device next to its blob, in the order they lie in the staging set's `aux` buffer (every one
+// 16-byte aligned) and in which they are copied.  The list is built once per stage (stage_tables); both ways of sending it walk
+// it (send_tables), and the kernels' typed pointers are taken from it (Stage::dev).
+enum StageTable {
+    kProgs, kFresh, kQueryProg, kQuerySlot,
+    kAlive,  // written by the device
+    kUnits,
+    kTiles,  // written by the device (make_tiles_kernel)
+    kTileGroups, kHsteps, kPairBase, kMoves, kBase, kOptr, kBlockTable, kSparseGroups,
+    kSparseCounts, kSparsePrefix,  // written by the device (sparse_plan_kernel)
+    kClears,
+    kBlob,  // a packed stage only: the blob rides last
+    kStageTables
+};
+struct StageTables {
+    struct Segment { const void* src; size_t bytes, at; };  // src == nullptr: nothing to send (the device writes it)
+    Segment seg[kStageTables] = {};
+    size_t bytes = 0;
+    // a small stage (a single query: a few hundred bytes of blob, a dozen small tables) travels as ONE copy
+    bool packed = false;
+    void add(StageTable t, const void* src, size_t n) {  // (in the order of the enum)
+        seg[t] = Segment{src, n, bytes};
+        bytes = (bytes + n + 15) & ~(size_t)15;
+    }
+};
+
+// What the phases of session_stage share.
+struct Stage {
+    Session& s;
+    Index& ix;
+    const unsigned char* blob; size_t bytes;                       // the call's arguments
+    const uint32_t *q_prog, *q_slot; size_t n_q; uint8_t* alive;
+    hipStream_t caller_stream;
+    // stage_decide
     BlobView bv;
-    double t0 = now_s();
-    if (int rc = validate_blob(blob, bytes, s.n_programs, s.kn, &bv)) return rc;
-    s.t_validate += now_s() - t0;
-    t0 = now_s();
+    bool any_dense = false, table = false, continues = false;
+    uint32_t W = 0;
+    RowSource rows;
+    // stage_regions
+    std::vector<uint32_t> fresh;  // programs that got their first region: ZERO/ONES/RESULT need initialising
+    std::vector<RegionMove> moves, clears;
+    // stage_plan
+    StagePlan plan;
+    size_t n_sparse_launches = 0;
+    std::vector<uint64_t*> block_table;  // per program with blocks a row [flags | block 0 | its capacity | block 1 | ..] (DenseRow)
+    std::vector<size_t> row_of;
+    // stage_upload
+    Index::StagingSet* set = nullptr;
+    StageTables tables;
+    const unsigned char* d_blob = nullptr;
+    uint64_t* d_masks = nullptr;
+    template <class T>
+    T* dev(StageTable t) const { return reinterpret_cast<T*>(set->d_aux + tables.seg[t].at); }
+    // stage_prologue
+    hipStream_t st = nullptr;
+    // the levels: what every launch takes ...
+    const txq_op* d_ops = nullptr;
+    const txq_dense_op* d_dops = nullptr;
+    const DenseOpPtr* d_optr = nullptr;
+    const ExecUnit* d_units = nullptr;
+    uint32_t np = 0, g_units_log2 = 0;
+    // ... and how far the lists have been worked off
+    size_t first_unit = 0, first_tile = 0, first_hstep = 0, chunk = 0, first_sparse = 0, sparse_launch = 0;
+    // where the host's time goes (Session::t_*; TXQ_TRACE_STAGES)
+    double t0 = 0, t_begin = 0, t_mark[6] = {0, 0, 0, 0, 0, 0};
+};
+
+// The launchers instantiate only what can be launched: TableRows at H = 1 (with_rows), and per kernel what is said there.
+// ua: predecessors in flight per lane (TXQ_DENSE_UNROLL: A/B knob).  U: the level's ordinary units, where they ride along.
+static hipError_t launch_dense(const Stage& g, const DenseTile* tiles, size_t n_tiles, const LevelUnits& U) {
+    const size_t grid = n_tiles + U.n_units;
+    const int ua = g.s.kn.dense_unroll >= 5 ? 5 : g.s.kn.dense_unroll <= 2 ? 2 : 3;
+    const bool ok = with_rows(g.rows, g.ix, g.W, [&](const auto& rows, auto tag) {
+        using T = decltype(tag);
+        using R = std::decay_t<decltype(rows)>;
+        auto go = [&](auto u) {
+            dense_kernel<T::H, T::WIDE, decltype(u)::value, R><<<(unsigned)grid, 256, 0, g.st>>>(rows, tiles, g.d_dops, g.d_optr, g.s.d_base, g.np, g.W, g.rows.g,
+                                                                                                g.rows.slices, g.bv.dense, U);
+        };
+        // layout order: always two predecessors in flight — a lane keeps its ancestors' gates in registers
+        if constexpr (T::kind == RowSource::Path) go(std::integral_constant<int, 2>{});
+        else with_value<2, 3, 5>(ua, go);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// the level's sparse groups [groups, groups + n_groups) (n_groups <= kMaxSparseGroups): `grid` workgroups share their chunks out
+static hipError_t launch_sparse(const Stage& g, const SparseGroup* groups, uint32_t n_groups, const uint32_t* counts, const uint32_t* prefix, size_t grid,
+                                const LevelUnits& U, uint32_t chunk) {
+    const bool ok = with_rows(g.rows, g.ix, g.W, [&](const auto& rows, auto tag) {
+        using T = decltype(tag);
+        // (sparse_kernel has no by-lane variant: a TreeRowsByLane is a TreeRows)
+        using R = std::conditional_t<T::kind == RowSource::TreeByLane, TreeRows<T::H, T::WIDE>, std::decay_t<decltype(rows)>>;
+        sparse_kernel<T::H, T::WIDE, R><<<(unsigned)grid, 256, 0, g.st>>>(rows, groups, n_groups, counts, prefix, g.d_dops, g.d_optr, g.s.d_base, g.np, g.W, g.rows.g,
+                                                                          g.bv.dense, U, chunk);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// ZERO / REDUCE / FILL groups only: the variant without the step code (its row source is not used)
+static hipError_t launch_sparse_misc(const Stage& g, const SparseGroup* groups, uint32_t n_groups, const uint32_t* counts, const uint32_t* prefix, size_t grid,
+                                     const LevelUnits& U) {
+    with_bool(g.rows.wide, [&](auto wide) {
+        constexpr bool WIDE = decltype(wide)::value;
+        sparse_kernel<1, WIDE, FlatRows<1, WIDE>, false><<<(unsigned)grid, 256, 0, g.st>>>(FlatRows<1, WIDE>{}, groups, n_groups, counts, prefix, g.d_dops, g.d_optr,
+                                                                                           g.s.d_base, g.np, g.W, g.rows.g, g.bv.dense, U, kSparseChunk);
+    });
+    return hipGetLastError();
+}
+
+// the STEP groups of a level on narrow masks (RowSource::by_units: flat index or table)
+static hipError_t launch_sparse_units(const Stage& g, const SparseGroup* groups, uint32_t n_groups, const uint32_t* counts, const uint32_t* prefix, size_t grid,
+                                      const StepParams& P, const LevelUnits& U) {
+    // units in flight per lane group (TXQ_SPARSE_UNROLL: A/B knob; 3 fits the 128 VGPRs of four waves per SIMD up to h = 3)
+    const int ua = g.s.kn.sparse_unroll <= 2 ? 2 : 3;
+    bool ok = with_rows(g.rows, g.ix, g.W, [&](const auto& rows, auto tag) {
+        using T = decltype(tag);
+        if constexpr (T::kind == RowSource::Flat || T::kind == RowSource::Table) {
+            using R = std::decay_t<decltype(rows)>;
+            auto go = [&](auto u) {
+                sparse_units_kernel<T::H, T::WIDE, decltype(u)::value, R><<<(unsigned)grid, 256, 0, g.st>>>(rows, groups, n_groups, counts, prefix, g.d_dops, g.d_optr,
+                                                                                                           g.s.d_base, g.np, g.W, g.rows.g, P, U, g.s.d_step_ctr);
+            };
+            if constexpr (T::H >= 4) go(std::integral_constant<int, 2>{});
+            else with_value<2, 3>(ua, go);
+        }
+    });
+    ok = ok && (g.rows.kind == RowSource::Flat || g.rows.kind == RowSource::Table);
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// Phase 1: the blob is well formed, the questions are in range; does the index's table of all k-mers' masks serve the stage,
+// what is its row source, and does it continue the previous stage?  *empty: there is nothing to run.
+static int stage_decide(Stage& g, bool* empty) {
+    Session& s = g.s;
+    Index& ix = g.ix;
+    BlobView& bv = g.bv;
+    g.t0 = now_s();
+    if (int rc = validate_blob(g.blob, g.bytes, s.n_programs, s.kn, &bv)) return rc;
+    s.t_validate += now_s() - g.t0;
+    g.t0 = g.t_begin = now_s();
     ++s.n_stages;
-    s.bytes_uploaded += bytes;
-    const BlobView* h = &bv;
-    bool any_dense = false;
-    for (uint8_t d : bv.has_dense) any_dense |= d != 0;
+    s.bytes_uploaded += g.bytes;
+    for (uint8_t d : bv.has_dense) g.any_dense |= d != 0;
     // Dense steps through the index's table of all k-mers' masks, where it fits (TXQ_DENSE_TREE set: the tree paths are asked for).
     // A session on a general HIBF that would keep its masks in layout order goes back to user-bin order for it — in its first
     // stage, before anything has been laid out.
     // A session of a few queries does not build it (0.4-1 ms: more than a single query's steps cost); it uses one that is there.
-    bool table = false;
-    if (any_dense && (!ix.is_hibf || s.kn.dense_tree < 0) && (ix.kmer_table || (long long)s.n_programs >= s.kn.kmer_table_min)) {
-        if (!s.vspace) table = ensure_kmer_table(ix, s.kn, bv.dense, s.W, s.upload);
+    if (g.any_dense && (!ix.is_hibf || s.kn.dense_tree < 0) && (ix.kmer_table || (long long)s.n_programs >= s.kn.kmer_table_min)) {
+        if (!s.vspace) g.table = ensure_kmer_table(ix, s.kn, bv.dense, s.W, s.upload);
         else if (s.n_stages == 1 && !s.aux && ensure_kmer_table(ix, s.kn, bv.dense, (uint32_t)ix.shard_words, s.upload)) {
             s.vspace = false;
             s.W = (uint32_t)ix.shard_words;
-            table = true;
+            g.table = true;
         }
     }
-    const uint32_t W = s.W;
-    for (size_t i = 0; i < n_q; ++i) {
-        if (q_prog[i] >= s.n_programs) return fail(TXQ_ERR_ARG, "feedback query %zu: program out of range", i);
-        if (q_slot[i] >= bv.n_slots[q_prog[i]]) return fail(TXQ_ERR_ARG, "feedback query %zu: slot out of range", i);
+    g.W = s.W;
+    for (size_t i = 0; i < g.n_q; ++i) {
+        if (g.q_prog[i] >= s.n_programs) return fail(TXQ_ERR_ARG, "feedback query %zu: program out of range", i);
+        if (g.q_slot[i] >= bv.n_slots[g.q_prog[i]]) return fail(TXQ_ERR_ARG, "feedback query %zu: slot out of range", i);
     }
-    if (W == 0 || s.n_programs == 0) {
-        for (size_t i = 0; i < n_q; ++i) alive[i] = 0;
+    if (g.W == 0 || s.n_programs == 0) {
+        for (size_t i = 0; i < g.n_q; ++i) g.alive[i] = 0;
+        *empty = true;
         return TXQ_OK;
     }
-    if (any_dense && !ix.is_hibf && (ix.ibf[0].bin_size >> 32))
+    if (g.any_dense && !ix.is_hibf && (ix.ibf[0].bin_size >> 32))
         return fail(TXQ_ERR_PROGRAM, "dense ops need fewer than 2^32 rows");
     // Does this stage continue anything the previous stage — possibly still running — works on?  Programs with ops in both,
     // feedback questions, grown regions (moves), an HIBF that is descended or a d-gram index (scratch of the index) tie it
     // to the previous stage's stream; a stage of other programs only (the next wave of queries) runs beside it.
-    bool continues = n_q != 0 || (ix.is_hibf && !ix.probes_interleaved(s.kn) && !s.vspace) || s.aux != nullptr;
+    g.continues = g.n_q != 0 || (ix.is_hibf && !ix.probes_interleaved(s.kn) && !s.vspace) || s.aux != nullptr;
     for (size_t p = 0; p < s.n_programs; ++p)
         if (bv.programs[p].n_ops) {
-            continues = continues || s.last_stage[p] + 1 == s.n_stages;
+            g.continues = g.continues || s.last_stage[p] + 1 == s.n_stages;
             s.last_stage[p] = (uint32_t)s.n_stages;
         }
-    // dense steps on a regular two-level HIBF run fused, too (TreeRows; TXQ_DENSE_TREE=0 sends them through the generic HIBF path)
-    const bool tree = !table && index_fuses_tree_steps(ix, s.kn);
+    g.rows = decide_rows(ix, s, g.table);
     bool any_tracked = false;
     for (size_t p = 0; p < s.n_programs; ++p) any_tracked |= bv.tracked[p] != 0 && bv.has_dense[p] != 0;
-    const bool vspace = s.vspace;
-    if (any_tracked && ix.is_hibf && !tree && !vspace && !table)
+    if (any_tracked && !g.rows.fused())
         return fail(TXQ_ERR_PROGRAM, "tracked blocks need an index whose dense steps run fused (txq_index_supports_dense() == 2)");
-    std::vector<uint32_t> fresh;  // programs that got their first region: ZERO/ONES/RESULT need initialising
-    std::vector<RegionMove> moves;
-    std::vector<std::pair<uint64_t*, size_t>> to_clear;
-    const double t_begin = t0;
-    double t_mark[6] = {0, 0, 0, 0, 0, 0};  // (TXQ_TRACE_STAGES) where the host's time of this stage goes
-    if (int rc = grow_slot_regions(s, bv, blob, &fresh, &moves, &to_clear)) return rc;
-    s.t_grow += now_s() - t0;
-    t_mark[0] = now_s();
-    for (size_t i = 0; i < n_q; ++i)
-        if (!s.base[q_prog[i]]) return fail(TXQ_ERR_ARG, "feedback query %zu: program %u has not run an op yet", i, q_prog[i]);
+    return TXQ_OK;
+}
 
-    // dense steps: 16-byte lanes where masks and rows allow it, G lanes per destination suffix
-    if (any_dense) s.row_source = tree ? "regular tree, fused" : vspace ? "general tree in layout order, fused" : ix.is_hibf ? "HIBF descent" : "flat IBF, fused";
-    if (any_dense && tree && ix.interleaved.words && ix.interleaved.shard_words == W && ix.root_node.bins <= 64 && s.kn.dense_tree < 0)
-        s.row_source = "regular tree, interleaved children, fused";
-    const int tree_knob = s.kn.dense_tree;  // 0: generic HIBF steps, 1: TreeRows, 2: TreeRowsByLane where it applies; -1 (default): best fit
-    const bool interleaved = tree && ix.interleaved.words && ix.interleaved.shard_words == W && ix.root_node.bins <= 64 && tree_knob < 0;
-    if (table) s.row_source = ix.is_hibf ? "HIBF through its table of all k-mers' masks" : "flat IBF through its table of all k-mers' masks";
-    const bool wide = W % 2 == 0 && (vspace ? ix.v_chunk_words == 2 : table ? true : (interleaved ? ix.interleaved.stride % 2 == 0 : tree ? ix.child_row_words >= 2 : !ix.is_hibf && ix.ibf[0].stride % 2 == 0));
-    uint32_t g_dense = 1;
-    while (g_dense < 64 && g_dense < (wide ? W / 2 : W)) g_dense <<= 1;
-    // ... and two such lane groups share the predecessors of one suffix (TXQ_DENSE_SLICES: A/B knob; on the bench batch
-    // 1 / 2 / 4 / 8 slices took 34 / 30 / 34 / 44+ ms end to end: more slices shorten a tile's load chain but multiply the tiles)
-    const uint32_t want_slices = (uint32_t)s.kn.dense_slices;
-    uint32_t sl_dense = 1;
-    while (sl_dense * 2 <= want_slices && g_dense * sl_dense * 2 <= 64) sl_dense <<= 1;
-    std::vector<ExecUnit> units;
-    std::vector<TileGroup> tile_groups;
-    size_t n_tiles = 0;
-    uint64_t work[4] = {0, 0, 0, 0};
-    std::vector<DenseTile> hsteps;
-    std::vector<uint32_t> hstep_na;
-    std::vector<LevelPlan> plan;
-    std::vector<SparseGroup> sparse_groups;
-    std::vector<DenseOpPtr> optr;
-    double t1 = now_s();
-    // a level's STEP groups get a launch of their own (chunked by work, below); the ZERO / REDUCE / FILL groups run in the
-    // sparse_kernel variant without step code (66 VGPRs)
-    const bool split_steps = true;
-    // ... and where a mask is a cache line or two, that launch shares the steps out by units (sparse_units_kernel; TXQ_SPARSE_STEPS=0:
-    // sparse_kernel's rounds of entries, A/B and tests)
-    const bool by_units = s.kn.sparse_steps && W <= kUnitStepWords && !vspace && !tree && (table || !ix.is_hibf);
-    const size_t n_small = plan_units(s, bv, blob, W, g_dense * sl_dense, ix.is_hibf && !tree && !vspace && !table, split_steps, &units, &tile_groups, &n_tiles, &work, &hsteps, &hstep_na,
-                                      &sparse_groups, &optr, &plan);
-    if (n_small == (size_t)-1) return TXQ_ERR_PROGRAM;
-    size_t n_sparse_launches = 0;
-    for (const LevelPlan& lp : plan)
-        n_sparse_launches += (lp.sparse_misc + kMaxSparseGroups - 1) / kMaxSparseGroups + (lp.sparse - lp.sparse_misc + kMaxSparseGroups - 1) / kMaxSparseGroups;
-    // the stage's block table: per program with blocks a row [flags | block 0 | its capacity | block 1 | ..] (DenseRow)
-    std::vector<uint64_t*> block_table;
-    std::vector<size_t> row_of(s.n_programs, 0);
+// Phase 2: every program has its slot region and its dense blocks.
+static int stage_regions(Stage& g) {
+    Session& s = g.s;
+    std::vector<std::pair<uint64_t*, size_t>> to_clear;
+    if (int rc = grow_slot_regions(s, g.bv, g.blob, &g.fresh, &g.moves, &to_clear)) return rc;
+    for (const auto& b : to_clear) g.clears.push_back(RegionMove{b.first, nullptr, b.second / 8});
+    s.t_grow += now_s() - g.t0;
+    g.t_mark[0] = now_s();
+    for (size_t i = 0; i < g.n_q; ++i)
+        if (!s.base[g.q_prog[i]]) return fail(TXQ_ERR_ARG, "feedback query %zu: program %u has not run an op yet", i, g.q_prog[i]);
+    if (g.any_dense) s.row_source = g.rows.name;
+    return TXQ_OK;
+}
+
+// Phase 3: units, tiles, sparse groups and HIBF steps of every level; the stage's block table.
+static int stage_plan(Stage& g) {
+    Session& s = g.s;
+    const double t1 = now_s();
+    if (int rc = plan_units(s, g.bv, g.blob, g.W, g.rows.g * g.rows.slices, !g.rows.fused(), &g.plan)) return rc;
+    for (const LevelPlan& lp : g.plan.levels)
+        g.n_sparse_launches += (lp.sparse_misc + kMaxSparseGroups - 1) / kMaxSparseGroups + (lp.sparse - lp.sparse_misc + kMaxSparseGroups - 1) / kMaxSparseGroups;
+    g.row_of.assign(s.n_programs, 0);
     for (size_t p = 0; p < s.n_programs; ++p)
         if (!s.blocks[p].empty()) {
-            row_of[p] = block_table.size();
-            block_table.push_back(reinterpret_cast<uint64_t*>((uintptr_t)(s.tracked[p] ? 1 : 0)));
+            g.row_of[p] = g.block_table.size();
+            g.block_table.push_back(reinterpret_cast<uint64_t*>((uintptr_t)(s.tracked[p] ? 1 : 0)));
             for (const Session::DenseBlock& b : s.blocks[p]) {
-                block_table.push_back(b.p);
-                block_table.push_back(reinterpret_cast<uint64_t*>((uintptr_t)b.cap));
+                g.block_table.push_back(b.p);
+                g.block_table.push_back(reinterpret_cast<uint64_t*>((uintptr_t)b.cap));
             }
         }
+    const uint64_t* work = g.plan.work;
     s.n_step_pairs += work[0]; s.n_step_suffixes += work[1]; s.n_zero_slots += work[2]; s.n_reduce_entries += work[3];
-    // HIBF steps run in chunks of tiles whose masks fit the scratch (2 GiB): chunk c = tiles [chunk_first[c], chunk_first[c+1]),
-    // never across a level; pair_base[tile] = first pair of the tile within its chunk
-    std::vector<uint32_t> pair_base(hsteps.size(), 0);
-    std::vector<size_t> chunk_first;
-    std::vector<uint32_t> chunk_pairs;
-    size_t most_pairs = 0;
-    {
-        const uint64_t budget = std::max<uint64_t>(((uint64_t)2 << 30) / ((uint64_t)W * 8), 8192);
-        size_t at = 0;
-        for (const LevelPlan& lp : plan) {
-            uint64_t pairs = 0;
-            for (size_t i = 0; i < lp.hsteps; ++i, ++at) {
-                const uint64_t mine = (uint64_t)hsteps[at].count * hstep_na[at];
-                if (i == 0 || pairs + mine > budget) {
-                    if (!chunk_first.empty() && !chunk_pairs.empty()) most_pairs = std::max<size_t>(most_pairs, chunk_pairs.back());
-                    chunk_first.push_back(at);
-                    chunk_pairs.push_back(0);
-                    pairs = 0;
-                }
-                pair_base[at] = (uint32_t)pairs;
-                pairs += mine;
-                chunk_pairs.back() = (uint32_t)pairs;
-            }
-        }
-        for (uint32_t c : chunk_pairs) most_pairs = std::max<size_t>(most_pairs, c);
-        chunk_first.push_back(hsteps.size());
-    }
-
-    // Staging set of this stage (the other one may still be read by the previous stage's kernels; this one was last used
-    // two stages ago): blob, and aux = program table | fresh-program list | feedback queries | alive bytes | units | tiles |
-    // HIBF steps | their pair bases | region moves | region bases.  Everything is copied on the upload stream and the host
-    // waits for THOSE copies only (pageable sources, some of them locals) — not for the kernels of the previous stage.
+    chunk_hibf_steps(g.plan, g.W);
     s.t_plan += now_s() - t1;
-    t1 = now_s();
-    t_mark[1] = t1;
+    return TXQ_OK;
+}
+
+static void stage_tables(Stage& g) {
+    const Session& s = g.s;
+    const StagePlan& P = g.plan;
+    StageTables& T = g.tables;
+    T.add(kProgs, g.bv.programs.data(), s.n_programs * sizeof(DevProgram));
+    T.add(kFresh, g.fresh.data(), g.fresh.size() * 4);
+    T.add(kQueryProg, g.q_prog, g.n_q * 4);
+    T.add(kQuerySlot, g.q_slot, g.n_q * 4);
+    T.add(kAlive, nullptr, g.n_q);
+    T.add(kUnits, P.units.data(), P.units.size() * sizeof(ExecUnit));
+    T.add(kTiles, nullptr, P.n_tiles * sizeof(DenseTile));
+    T.add(kTileGroups, P.tile_groups.data(), P.tile_groups.size() * sizeof(TileGroup));
+    T.add(kHsteps, P.hsteps.data(), P.hsteps.size() * sizeof(DenseTile));
+    T.add(kPairBase, P.pair_base.data(), P.hsteps.size() * 4);
+    T.add(kMoves, g.moves.data(), g.moves.size() * sizeof(RegionMove));
+    T.add(kBase, s.base.data(), 2 * s.n_programs * sizeof(uint64_t*));  // (its second half is filled in once `aux` has its address)
+    T.add(kOptr, P.optr.data(), P.optr.size() * sizeof(DenseOpPtr));
+    T.add(kBlockTable, g.block_table.data(), g.block_table.size() * sizeof(uint64_t*));
+    T.add(kSparseGroups, P.sparse_groups.data(), P.sparse_groups.size() * sizeof(SparseGroup));
+    T.add(kSparseCounts, nullptr, P.sparse_groups.size() * 4);
+    T.add(kSparsePrefix, nullptr, (P.sparse_groups.size() + g.n_sparse_launches) * 4);
+    T.add(kClears, g.clears.data(), g.clears.size() * sizeof(RegionMove));
+    T.packed = T.bytes + g.bytes <= ((size_t)256 << 10);
+    T.add(kBlob, g.blob, T.packed ? g.bytes : 0);  // the blob rides behind the tables in `aux`
+}
+
+// Everything is copied on the upload stream: one copy of the packed tables, or the blob and every table that has a source.
+static int send_tables(Stage& g) {
+    Session& s = g.s;
+    const StageTables& T = g.tables;
+    const Index::StagingSet& S = *g.set;
+    if (T.packed) {
+        s.host_aux.resize(T.bytes);
+        for (const StageTables::Segment& t : T.seg)
+            if (t.src && t.bytes) std::memcpy(s.host_aux.data() + t.at, t.src, t.bytes);
+        TXQ_HIP(hipMemcpyAsync(S.d_aux, s.host_aux.data(), T.bytes, hipMemcpyHostToDevice, s.upload));
+        return TXQ_OK;
+    }
+    TXQ_HIP(hipMemcpyAsync(S.d_blob, g.blob, g.bytes, hipMemcpyHostToDevice, s.upload));
+    for (const StageTables::Segment& t : T.seg)
+        if (t.src && t.bytes) TXQ_HIP(hipMemcpyAsync(S.d_aux + t.at, t.src, t.bytes, hipMemcpyHostToDevice, s.upload));
+    return TXQ_OK;
+}
+
+// Phase 4: the staging set of this stage (the other one may still be read by the previous stage's kernels; this one was last
+// used two stages ago) takes the blob and the tables.  The host waits for THOSE copies only (pageable sources, some of them
+// this stage's own) — not for the kernels of the previous stage.
+static int stage_upload(Stage& g) {
+    Session& s = g.s;
+    Index& ix = g.ix;
+    double t1 = now_s();
+    g.t_mark[1] = t1;
     Index::StagingSet& S = s.set[(s.n_stages - 1) & 1];
+    g.set = &S;
     if (S.pending) {
         TXQ_HIP(hipEventSynchronize(S.done));
         S.pending = false;
     }
     s.t_wait += now_s() - t1;
     t1 = now_s();
-    t_mark[2] = t1;
-    size_t aux_bytes = 0;
-    auto place = [&](size_t bytes) { const size_t at = aux_bytes; aux_bytes = (aux_bytes + bytes + 15) & ~(size_t)15; return at; };
-    const size_t prog_bytes = s.n_programs * sizeof(DevProgram);
-    const size_t at_progs = place(prog_bytes), at_fresh = place(fresh.size() * 4), at_qp = place(n_q * 4), at_qs = place(n_q * 4), at_alive = place(n_q);
-    const size_t at_units = place(units.size() * sizeof(ExecUnit)), at_tiles = place(n_tiles * sizeof(DenseTile)), at_groups = place(tile_groups.size() * sizeof(TileGroup));
-    const size_t at_hsteps = place(hsteps.size() * sizeof(DenseTile)), at_pair_base = place(hsteps.size() * 4);
-    const size_t at_moves = place(moves.size() * sizeof(RegionMove)), at_base = place(2 * s.n_programs * sizeof(uint64_t*));
-    const size_t at_optr = place(optr.size() * sizeof(DenseOpPtr)), at_bt = place(block_table.size() * sizeof(uint64_t*));
-    const size_t at_sgroups = place(sparse_groups.size() * sizeof(SparseGroup)), at_scounts = place(sparse_groups.size() * 4);
-    const size_t at_sprefix = place((sparse_groups.size() + n_sparse_launches) * 4);
-    std::vector<RegionMove> clears;
-    for (const auto& b : to_clear) clears.push_back(RegionMove{b.first, nullptr, b.second / 8});
-    const size_t at_clears = place(clears.size() * sizeof(RegionMove));
-    // a small stage (a single query: a few hundred bytes of blob, a dozen small tables) travels as ONE copy: the blob
-    // rides behind the tables in `aux`
-    const bool packed = aux_bytes + bytes <= ((size_t)256 << 10);
-    const size_t at_blob = packed ? place(bytes) : 0;
+    g.t_mark[2] = t1;
+    stage_tables(g);
+    const StageTables& T = g.tables;
     // The set's buffers are idle (S.done was waited for), but hipFree drains the WHOLE device — the previous stage, which this
     // stage may want to run beside: a buffer that has to grow (how the queries fall into waves depends on the host's timing, so
     // stage sizes differ from batch to batch) is replaced generously and the old one freed with the session.
@@ -2469,342 +2642,280 @@ int session_stage(Session& s, const void* blob_v, size_t bytes, const uint32_t* 
         *cap = want;
         return TXQ_OK;
     };
-    if (!packed)
-        if (int rc = ensure_idle((void**)&S.d_blob, &S.cap_blob, (bytes + 7) & ~(size_t)7)) return rc;
-    if (int rc = ensure_idle((void**)&S.d_aux, &S.cap_aux, aux_bytes + 16)) return rc;
-    const unsigned char* dblob = packed ? S.d_aux + at_blob : S.d_blob;
+    if (!T.packed)
+        if (int rc = ensure_idle((void**)&S.d_blob, &S.cap_blob, (g.bytes + 7) & ~(size_t)7)) return rc;
+    if (int rc = ensure_idle((void**)&S.d_aux, &S.cap_aux, T.bytes + 16)) return rc;
+    g.d_blob = T.packed ? g.dev<const unsigned char>(kBlob) : S.d_blob;
     for (size_t p = 0; p < s.n_programs; ++p)  // (the aux buffer has its final address now)
-        s.base[s.n_programs + p] = s.blocks[p].empty() ? nullptr : reinterpret_cast<uint64_t*>(reinterpret_cast<uint64_t**>(S.d_aux + at_bt) + row_of[p]);
-    const size_t nk = h->n_kmers;
-    // scratch of the INDEX that kernels in flight may still use: replacing it drains the device (ensure), so replace it generously
-    auto ensure_scratch = [&](uint64_t** p, size_t* cap, size_t need) -> int {
-        if (*p && *cap >= need) return TXQ_OK;
-        return ensure((void**)p, cap, std::max(need + need / 2, (size_t)64 << 20));
-    };
-    if (int rc = ensure_idle((void**)&S.d_masks, &S.cap_masks, std::max((nk ? nk : 1) * (size_t)W * 8, (size_t)16 << 20))) return rc;
-    uint64_t* const d_masks = S.d_masks;
+        s.base[s.n_programs + p] = s.blocks[p].empty() ? nullptr : reinterpret_cast<uint64_t*>(g.dev<uint64_t*>(kBlockTable) + g.row_of[p]);
+    const size_t nk = g.bv.n_kmers;
+    if (int rc = ensure_idle((void**)&S.d_masks, &S.cap_masks, std::max((nk ? nk : 1) * (size_t)g.W * 8, (size_t)16 << 20))) return rc;
+    g.d_masks = S.d_masks;
     s.t_alloc += now_s() - t1;
-    t_mark[3] = now_s();
-    hipStream_t up = s.upload;
-    if (packed) {
-        s.host_aux.resize(aux_bytes);
-        unsigned char* hb = s.host_aux.data();
-        auto put = [&](size_t at, const void* src, size_t n) { if (n) std::memcpy(hb + at, src, n); };
-        put(at_progs, bv.programs.data(), prog_bytes);
-        put(at_fresh, fresh.data(), fresh.size() * 4);
-        put(at_qp, q_prog, n_q * 4);
-        put(at_qs, q_slot, n_q * 4);
-        put(at_units, units.data(), units.size() * sizeof(ExecUnit));
-        put(at_groups, tile_groups.data(), tile_groups.size() * sizeof(TileGroup));
-        put(at_hsteps, hsteps.data(), hsteps.size() * sizeof(DenseTile));
-        put(at_pair_base, pair_base.data(), hsteps.size() * 4);
-        put(at_moves, moves.data(), moves.size() * sizeof(RegionMove));
-        put(at_base, s.base.data(), 2 * s.n_programs * sizeof(uint64_t*));
-        put(at_optr, optr.data(), optr.size() * sizeof(DenseOpPtr));
-        put(at_bt, block_table.data(), block_table.size() * sizeof(uint64_t*));
-        put(at_sgroups, sparse_groups.data(), sparse_groups.size() * sizeof(SparseGroup));
-        put(at_clears, clears.data(), clears.size() * sizeof(RegionMove));
-        put(at_blob, blob, bytes);
-        TXQ_HIP(hipMemcpyAsync(S.d_aux, hb, aux_bytes, hipMemcpyHostToDevice, up));
-    } else {
-        auto send = [&](size_t at, const void* src, size_t n) -> hipError_t {
-            return n ? hipMemcpyAsync(S.d_aux + at, src, n, hipMemcpyHostToDevice, up) : hipSuccess;
+    g.t_mark[3] = now_s();
+    if (int rc = send_tables(g)) return rc;
+    s.d_base = g.dev<uint64_t*>(kBase);
+    if (!g.plan.hsteps.empty()) {
+        // scratch of the INDEX that kernels in flight may still use: replacing it drains the device (ensure), so replace it generously
+        auto ensure_scratch = [&](uint64_t** p, size_t* cap, size_t need) -> int {
+            if (*p && *cap >= need) return TXQ_OK;
+            return ensure((void**)p, cap, std::max(need + need / 2, (size_t)64 << 20));
         };
-        TXQ_HIP(hipMemcpyAsync(S.d_blob, blob, bytes, hipMemcpyHostToDevice, up));
-        TXQ_HIP(send(at_progs, bv.programs.data(), prog_bytes));
-        TXQ_HIP(send(at_fresh, fresh.data(), fresh.size() * 4));
-        TXQ_HIP(send(at_qp, q_prog, n_q * 4));
-        TXQ_HIP(send(at_qs, q_slot, n_q * 4));
-        TXQ_HIP(send(at_units, units.data(), units.size() * sizeof(ExecUnit)));
-        TXQ_HIP(send(at_groups, tile_groups.data(), tile_groups.size() * sizeof(TileGroup)));
-        TXQ_HIP(send(at_hsteps, hsteps.data(), hsteps.size() * sizeof(DenseTile)));
-        TXQ_HIP(send(at_pair_base, pair_base.data(), hsteps.size() * 4));
-        TXQ_HIP(send(at_moves, moves.data(), moves.size() * sizeof(RegionMove)));
-        TXQ_HIP(send(at_base, s.base.data(), 2 * s.n_programs * sizeof(uint64_t*)));
-        TXQ_HIP(send(at_optr, optr.data(), optr.size() * sizeof(DenseOpPtr)));
-        TXQ_HIP(send(at_bt, block_table.data(), block_table.size() * sizeof(uint64_t*)));
-        TXQ_HIP(send(at_sgroups, sparse_groups.data(), sparse_groups.size() * sizeof(SparseGroup)));
-        TXQ_HIP(send(at_clears, clears.data(), clears.size() * sizeof(RegionMove)));
+        if (int rc = ensure_scratch(&ix.scratch_dense_kmers, &ix.cap_dense_kmers, g.plan.most_pairs * 8)) return rc;
+        if (int rc = ensure_scratch(&ix.scratch_dense_masks, &ix.cap_dense_masks, g.plan.most_pairs * (size_t)g.W * 8)) return rc;
     }
-    DevProgram* d_progs = (DevProgram*)(S.d_aux + at_progs);
-    uint32_t* d_fresh = (uint32_t*)(S.d_aux + at_fresh);
-    uint32_t* d_qp = (uint32_t*)(S.d_aux + at_qp);
-    uint32_t* d_qs = (uint32_t*)(S.d_aux + at_qs);
-    uint8_t* d_alive = S.d_aux + at_alive;
-    ExecUnit* d_units = (ExecUnit*)(S.d_aux + at_units);
-    DenseTile* d_tiles = (DenseTile*)(S.d_aux + at_tiles);
-    DenseTile* d_hsteps = (DenseTile*)(S.d_aux + at_hsteps);
-    uint32_t* d_pair_base = (uint32_t*)(S.d_aux + at_pair_base);
-    const DenseOpPtr* d_optr = (const DenseOpPtr*)(S.d_aux + at_optr);
-    const SparseGroup* d_sgroups = (const SparseGroup*)(S.d_aux + at_sgroups);
-    uint32_t* d_scounts = (uint32_t*)(S.d_aux + at_scounts);
-    uint32_t* d_sprefix = (uint32_t*)(S.d_aux + at_sprefix);
-    s.d_base = (uint64_t**)(S.d_aux + at_base);
-    if (!hsteps.empty()) {
-        if (int rc = ensure_scratch(&ix.scratch_dense_kmers, &ix.cap_dense_kmers, most_pairs * 8)) return rc;
-        if (int rc = ensure_scratch(&ix.scratch_dense_masks, &ix.cap_dense_masks, most_pairs * (size_t)W * 8)) return rc;
-    }
-    t_mark[4] = now_s();
-    TXQ_HIP(hipStreamSynchronize(up));
-    s.t_upload += now_s() - t0;
-    t0 = now_s();
-    t_mark[5] = t0;
+    g.t_mark[4] = now_s();
+    TXQ_HIP(hipStreamSynchronize(s.upload));
+    s.t_upload += now_s() - g.t0;
+    g.t0 = now_s();
+    g.t_mark[5] = g.t0;
+    return TXQ_OK;
+}
 
-    const bool one_stream = s.kn.one_stream;  // A/B knob
+// Phase 5: the stage's stream; tiles, cleared blocks, moved and fresh regions; M[k-mer] of the stage's k-mers.
+static int stage_prologue(Stage& g) {
+    Session& s = g.s;
+    Index& ix = g.ix;
+    const uint32_t W = g.W;
     const Index::StagingSet& prev = s.set[s.n_stages & 1];
-    const bool beside = !continues && moves.empty() && hsteps.empty() && prev.pending && s.n_stages > 1 && !one_stream;
+    const bool beside = !g.continues && g.moves.empty() && g.plan.hsteps.empty() && prev.pending && s.n_stages > 1 && !s.kn.one_stream;
     const int which = beside ? 1 - s.stream_of_last : s.stream_of_last;
     s.stream_of_last = which;
     if (beside) ++s.n_beside;
     if (s.kn.trace_stages)
-        fprintf(stderr, "[txq] stage %zu: continues %d (questions %zu), moves %zu, previous pending %d -> stream %d\n", s.n_stages, (int)continues, n_q, moves.size(),
-                (int)prev.pending, which);
-    hipStream_t st = which ? s.side : caller_stream;
-    if (!tile_groups.empty()) {
-        make_tiles_kernel<<<(unsigned)tile_groups.size(), 256, 0, st>>>((const TileGroup*)(S.d_aux + at_groups), d_tiles);
+        fprintf(stderr, "[txq] stage %zu: continues %d (questions %zu), moves %zu, previous pending %d -> stream %d\n", s.n_stages, (int)g.continues, g.n_q,
+                g.moves.size(), (int)prev.pending, which);
+    hipStream_t st = g.st = which ? s.side : g.caller_stream;
+    if (!g.plan.tile_groups.empty()) {
+        make_tiles_kernel<<<(unsigned)g.plan.tile_groups.size(), 256, 0, st>>>(g.dev<const TileGroup>(kTileGroups), g.dev<DenseTile>(kTiles));
         TXQ_HIP(hipGetLastError());
     }
-    if (!clears.empty()) {  // blocks a tracked program takes over: all zero, list empty
-        clear_blocks_kernel<<<dim3((unsigned)clears.size(), 16), 256, 0, st>>>((const RegionMove*)(S.d_aux + at_clears));
+    if (!g.clears.empty()) {  // blocks a tracked program takes over: all zero, list empty
+        clear_blocks_kernel<<<dim3((unsigned)g.clears.size(), 16), 256, 0, st>>>(g.dev<const RegionMove>(kClears));
         TXQ_HIP(hipGetLastError());
-        s.n_block_memsets += clears.size();
+        s.n_block_memsets += g.clears.size();
     }
-    if (!moves.empty()) {  // after everything earlier stages launched on the regions, before anything of this stage
-        move_regions_kernel<<<dim3((unsigned)moves.size(), 16), 256, 0, st>>>((const RegionMove*)(S.d_aux + at_moves));
+    if (!g.moves.empty()) {  // after everything earlier stages launched on the regions, before anything of this stage
+        move_regions_kernel<<<dim3((unsigned)g.moves.size(), 16), 256, 0, st>>>(g.dev<const RegionMove>(kMoves));
         TXQ_HIP(hipGetLastError());
     }
-    if (!fresh.empty()) {
-        size_t blocks = (fresh.size() * W + 255) / 256;
+    if (!g.fresh.empty()) {
+        size_t blocks = (g.fresh.size() * W + 255) / 256;
         if (blocks > 2048) blocks = 2048;
-        init_slots_kernel<<<(unsigned)blocks, 256, 0, st>>>(s.d_base, d_fresh, (uint32_t)fresh.size(), W, ix.user_bins, ix.shard_word0, s.vspace ? ix.d_vleaf : nullptr);
+        init_slots_kernel<<<(unsigned)blocks, 256, 0, st>>>(s.d_base, g.dev<const uint32_t>(kFresh), (uint32_t)g.fresh.size(), W, ix.user_bins, ix.shard_word0,
+                                                            s.vspace ? ix.d_vleaf : nullptr);
     }
-    const uint64_t* d_kmers = (const uint64_t*)(dblob + h->kmers_offset);
-    const size_t n_aux = (size_t)h->n_aux_kmers, n_main = nk - n_aux;
+    const uint64_t* d_kmers = (const uint64_t*)(g.d_blob + g.bv.kmers_offset);
+    const size_t n_aux = (size_t)g.bv.n_aux_kmers, n_main = g.bv.n_kmers - n_aux;
     if (n_aux && !s.aux) return fail(TXQ_ERR_STATE, "the blob has auxiliary (d-gram) k-mers but the session has no auxiliary index");
     if (n_main) {
-        if (vspace) {
-            if (int rc = hibf_probe_layout_order(ix, d_kmers, n_main, d_masks, st)) return rc;
+        if (s.vspace) {
+            if (int rc = hibf_probe_layout_order(ix, d_kmers, n_main, g.d_masks, st)) return rc;
         } else if (ix.is_hibf) {
-            if (int rc = hibf_probe(ix, s.kn, d_kmers, n_main, d_masks, nullptr, st)) return rc;
+            if (int rc = hibf_probe(ix, s.kn, d_kmers, n_main, g.d_masks, nullptr, st)) return rc;
         } else {
-            hipError_t e = launch_probe(ix.ibf[0], d_kmers, n_main, d_masks, nullptr, st);
+            hipError_t e = launch_probe(ix.ibf[0], d_kmers, n_main, g.d_masks, nullptr, st);
             if (e != hipSuccess) return fail_hip(e, "probe kernel launch");
         }
     }
     if (n_aux) {  // d-grams: same bins, same column shard, their own flat IBF
-        hipError_t e = launch_probe(s.aux->ibf[0], d_kmers + n_main, n_aux, d_masks + n_main * (size_t)W, nullptr, st);
+        hipError_t e = launch_probe(s.aux->ibf[0], d_kmers + n_main, n_aux, g.d_masks + n_main * (size_t)W, nullptr, st);
         if (e != hipSuccess) return fail_hip(e, "d-gram probe kernel launch");
     }
-    if (h->n_ops) {
-        // lanes per op: the mask width rounded up to a power of two, at most the whole workgroup
-        // (a 65536-bin mask is 1024 words: one word per thread of exec_kernel, four per thread of a unit)
-        int g = 1;
-        while (g < 1024 && (uint32_t)g < W) g <<= 1;
-        const int g_units = g < 256 ? g : 256;
-        uint32_t g_units_log2 = 0;
-        while ((1 << g_units_log2) < g_units) ++g_units_log2;
-        const bool fuse_units = s.kn.fuse_units;  // A/B knob
-        const txq_op* d_ops = (const txq_op*)(dblob + h->ops_offset);
-        const uint32_t* d_levels = h->n_levels ? (const uint32_t*)(dblob + h->levels_offset) : nullptr;
-        const txq_dense_op* d_dops = h->n_dense ? (const txq_dense_op*)(dblob + h->dense_offset) : nullptr;
-        const uint32_t np = (uint32_t)s.n_programs;
-        if (n_small) {
-            size_t blocks = s.n_programs < 4096 ? s.n_programs : 4096;
-#define TXQ_EXEC(G) exec_kernel<G><<<(unsigned)blocks, 1024, 0, st>>>(d_progs, d_ops, d_levels, s.d_base, np, d_masks, W)
-            switch (g) {
-                case 1: TXQ_EXEC(1); break;
-                case 2: TXQ_EXEC(2); break;
-                case 4: TXQ_EXEC(4); break;
-                case 8: TXQ_EXEC(8); break;
-                case 16: TXQ_EXEC(16); break;
-                case 32: TXQ_EXEC(32); break;
-                case 64: TXQ_EXEC(64); break;
-                case 128: TXQ_EXEC(128); break;
-                case 256: TXQ_EXEC(256); break;
-                case 512: TXQ_EXEC(512); break;
-                default: TXQ_EXEC(1024); break;
-            }
-#undef TXQ_EXEC
+    return TXQ_OK;
+}
+
+// The programs that plan_units left whole: one workgroup per program, all levels in one launch.
+static void launch_small_programs(const Stage& g) {
+    // lanes per op: the mask width rounded up to a power of two, at most the whole workgroup
+    // (a 65536-bin mask is 1024 words: one word per thread of exec_kernel, four per thread of a unit)
+    int lanes = 1;
+    while (lanes < 1024 && (uint32_t)lanes < g.W) lanes <<= 1;
+    const size_t blocks = g.s.n_programs < 4096 ? g.s.n_programs : 4096;
+    const uint32_t* d_levels = g.bv.n_levels ? (const uint32_t*)(g.d_blob + g.bv.levels_offset) : nullptr;
+    with_value<1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024>(lanes, [&](auto l) {
+        exec_kernel<decltype(l)::value><<<(unsigned)blocks, 1024, 0, g.st>>>(g.dev<const DevProgram>(kProgs), g.d_ops, d_levels, g.s.d_base, g.np, g.d_masks, g.W);
+    });
+}
+
+// HIBF descent: the level's steps, chunk by chunk: k-mers of all (suffix, predecessor) pairs -> tree descent -> combine
+static int run_hibf_steps(Stage& g, const LevelPlan& lp) {
+    Session& s = g.s;
+    Index& ix = g.ix;
+    const DenseTile* d_hsteps = g.dev<const DenseTile>(kHsteps);
+    const uint32_t* d_pair_base = g.dev<const uint32_t>(kPairBase);
+    for (const size_t level_end = g.first_hstep + lp.hsteps; g.first_hstep < level_end; ++g.chunk) {
+        const size_t c0 = g.plan.chunk_first[g.chunk], c1 = g.plan.chunk_first[g.chunk + 1];
+        const uint32_t pairs = g.plan.chunk_pairs[g.chunk];
+        if (pairs) {
+            dense_hibf_kmers_kernel<<<(unsigned)(c1 - c0), 256, 0, g.st>>>(d_hsteps + c0, d_pair_base + c0, g.d_dops, g.bv.dense, ix.scratch_dense_kmers);
+            TXQ_HIP(hipGetLastError());
+            if (int rc = hibf_probe(ix, s.kn, ix.scratch_dense_kmers, pairs, ix.scratch_dense_masks, nullptr, g.st)) return rc;
+            dense_hibf_combine_kernel<<<(unsigned)(c1 - c0), 256, 0, g.st>>>(d_hsteps + c0, d_pair_base + c0, g.d_dops, g.d_optr, g.W, g.bv.dense, ix.scratch_dense_masks);
+            TXQ_HIP(hipGetLastError());
         }
-        size_t first = 0, first_tile = 0, first_hstep = 0, chunk = 0, first_sparse = 0, sparse_launch = 0;
-        uint32_t wpr_log2 = 0;
-        while (tree && (1u << wpr_log2) < ix.child_row_words) ++wpr_log2;
-        for (size_t l = 0; l < plan.size(); ++l) {
-            const size_t cnt = plan[l].units;
-            ++s.n_levels;
-            // a flat index runs the level's units inside its dense launch (below), or its sparse launch when it has no tiles;
-            // otherwise they are a launch of their own
-            const bool ride = fuse_units && cnt && plan[l].tiles && (!ix.is_hibf || tree || vspace || table);
-            const bool ride_sparse = fuse_units && cnt && !ride && plan[l].sparse && (!ix.is_hibf || tree || vspace || table);
-            if (cnt && !ride && !ride_sparse) {
-                ++s.n_unit_launches;
-                exec_units_kernel<<<(unsigned)cnt, 256, 0, st>>>(d_units + first, d_ops, s.d_base, np, d_masks, W, g_units_log2);
-            }
-            s.n_units += cnt;
-            // HIBF: the level's steps, chunk by chunk: k-mers of all (suffix, predecessor) pairs -> tree descent -> combine
-            for (const size_t level_end = first_hstep + plan[l].hsteps; first_hstep < level_end; ++chunk) {
-                const size_t c0 = chunk_first[chunk], c1 = chunk_first[chunk + 1];
-                const uint32_t pairs = chunk_pairs[chunk];
-                if (pairs) {
-                    dense_hibf_kmers_kernel<<<(unsigned)(c1 - c0), 256, 0, st>>>(d_hsteps + c0, d_pair_base + c0, d_dops, bv.dense, ix.scratch_dense_kmers);
-                    TXQ_HIP(hipGetLastError());
-                    if (int rc = hibf_probe(ix, s.kn, ix.scratch_dense_kmers, pairs, ix.scratch_dense_masks, nullptr, st)) return rc;
-                    dense_hibf_combine_kernel<<<(unsigned)(c1 - c0), 256, 0, st>>>(d_hsteps + c0, d_pair_base + c0, d_dops, d_optr, W, bv.dense, ix.scratch_dense_masks);
-                    TXQ_HIP(hipGetLastError());
-                }
-                first_hstep = c1;
-                s.n_dense_tiles += c1 - c0;
-            }
-            if (plan[l].tiles) {  // ordinary and dense ops of one level are independent of each other: no order implied
-                const LevelUnits lu{d_units + first, d_ops, d_masks, ride ? (uint32_t)cnt : 0u, g_units_log2};
-                hipError_t e;
-                if (vspace) {  // (rows are whole 16-byte chunks: WIDE; two predecessors in flight — a lane keeps its ancestors' gates in registers)
-                    auto rows_path = [&](auto& r) { r.chunks = ix.d_vchunks; r.paths = ix.d_vpaths; r.split_range = ix.d_vsplit_range; r.splits = ix.d_vsplits; };
-                    e = wide ? launch_dense<true, PathRows>(2, ix.tree_hash_max, rows_path, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st)
-                             : launch_dense<false, PathRows>(2, ix.tree_hash_max, rows_path, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st);
-                } else if (tree) {
-                    auto rows_of = [&](auto& r) { r.root = ix.root_node; r.children = (const ChildRec*)ix.d_children; r.wpr_log2 = wpr_log2; };
-                    // root of <= 64 merged bins and the suffix's lanes cover the mask: root words by lane (TXQ_DENSE_TREE=1: the general variant)
-                    const bool by_lane = (256u / (g_dense * sl_dense)) * 32u * ix.root_node.stride() <= kRootWordsLds && tree_knob != 1;
-                    if (interleaved) {
-                        auto rows_il = [&](auto& r) { r.f = ix.interleaved; r.root = ix.root_node; r.children = (const ChildRec*)ix.d_children; r.wpr_log2 = wpr_log2; };
-                        e = wide ? launch_dense<true, InterleavedRows>(s.kn.dense_unroll, ix.tree_hash_max, rows_il, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st)
-                                 : launch_dense<false, InterleavedRows>(s.kn.dense_unroll, ix.tree_hash_max, rows_il, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st);
-                    } else if (by_lane)
-                        e = wide ? launch_dense<true, TreeRowsByLane>(s.kn.dense_unroll, ix.tree_hash_max, rows_of, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st)
-                                 : launch_dense<false, TreeRowsByLane>(s.kn.dense_unroll, ix.tree_hash_max, rows_of, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st);
-                    else
-                        e = wide ? launch_dense<true, TreeRows>(s.kn.dense_unroll, ix.tree_hash_max, rows_of, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st)
-                                 : launch_dense<false, TreeRows>(s.kn.dense_unroll, ix.tree_hash_max, rows_of, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st);
-                } else if (table) {  // a flat index whose masks of all k-mers are tabulated: one row per k-mer
-                    auto rows_tab = [&](auto& r) { r.table = ix.kmer_table; r.stride = W; };
-                    e = wide ? launch_dense<true, TableRows>(s.kn.dense_unroll, 1, rows_tab, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st)
-                             : launch_dense<false, TableRows>(s.kn.dense_unroll, 1, rows_tab, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st);
-                } else {  // (an irregular HIBF only has ZERO / REDUCE tiles here: its steps are `hsteps`)
-                    auto rows_of = [&](auto& r) { r.f = ix.ibf[0]; };
-                    e = wide ? launch_dense<true, FlatRows>(s.kn.dense_unroll, ix.ibf[0].hash_funs, rows_of, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st)
-                             : launch_dense<false, FlatRows>(s.kn.dense_unroll, ix.ibf[0].hash_funs, rows_of, d_tiles + first_tile, plan[l].tiles, d_dops, d_optr, s.d_base, np, W, g_dense, sl_dense, bv.dense, lu, st);
-                }
-                if (e != hipSuccess) return fail_hip(e, "dense kernel launch");
-                first_tile += plan[l].tiles;
-                s.n_dense_tiles += plan[l].tiles;
-                ++s.n_dense_launches;
-            }
-            // the level's sparse groups (dense ops of tracked programs): plan (counts -> chunks), then the chunks.  split_steps: the
-            // groups are ordered [others | STEPs] and the STEPs go to the compacted step kernel (two ranges, each in segments of
-            // at most kMaxSparseGroups groups); otherwise sparse_kernel takes all of them
-            const size_t n_misc = split_steps ? plan[l].sparse_misc : plan[l].sparse;
-            bool rode = false;  // the level's ordinary ops ride in its first sparse launch
-            for (int range = 0; range < 2; ++range) {
-                const size_t r_lo = range == 0 ? 0 : n_misc, r_hi = range == 0 ? n_misc : plan[l].sparse;
-                const bool steps = range == 1;
-                size_t range_chunks = steps ? plan[l].step_chunks : plan[l].sparse_chunks;
-                if (steps && by_units) range_chunks = range_chunks * (kSparseChunk / 16);  // (counted in chunks of kSparseChunk entries; a chunk by units holds 16 at least)
-                // The STEPs of sparse_kernel (trees; masks wider than kUnitStepWords): a chunk is ONE round of the workgroup's lane groups
-                // on wide masks — the live lists of a layout-order session are short (thousands of entries of 19.8 KB), and a
-                // chunk of 64 of them was sixteen rounds of dozens of dependent trips in one workgroup while most of the device
-                // idled (level 2 of the 200-motif batch: 2900 entries, 6.1 ms) — and kSparseChunk entries where a round holds that many
-                const uint32_t step_chunk = steps && !by_units && W > kUnitStepWords ? std::max<uint32_t>(1u, std::min<uint32_t>(kSparseChunk, 256u / g_dense)) : kSparseChunk;
-                if (steps && !by_units) range_chunks = range_chunks * (kSparseChunk / step_chunk);
-                for (size_t off = r_lo; off < r_hi; off += kMaxSparseGroups, ++sparse_launch) {
-                    const uint32_t ng = (uint32_t)std::min<size_t>(kMaxSparseGroups, r_hi - off);
-                    const SparseGroup* gr = d_sgroups + first_sparse + off;
-                    uint32_t* counts = d_scounts + first_sparse + off;
-                    uint32_t* prefix = d_sprefix + first_sparse + off + sparse_launch;
-                    sparse_plan_kernel<<<1, 1024, 0, st>>>(gr, ng, d_dops, d_optr, W, bv.dense.pos, steps && by_units ? (0x80000000u | (uint32_t)s.kn.sparse_units) : step_chunk, counts, prefix);
-                    TXQ_HIP(hipGetLastError());
-                    const LevelUnits lu{d_units + first, d_ops, d_masks, ride_sparse && !rode ? (uint32_t)cnt : 0u, g_units_log2};
-                    rode = true;
-                    // as many workgroups as the chunks could be at most, within what the device holds at a time
-                    const size_t grid = lu.n_units + std::max<size_t>(1, std::min<size_t>(range_chunks, 2048));
-                    hipError_t e;
-                    if (steps && by_units) {
-                        StepParams sp{bv.dense.k, bv.dense.bits, bv.dense.pos, bv.dense.canonical, (uint32_t)s.kn.sparse_units, 0u};
+        g.first_hstep = c1;
+        s.n_dense_tiles += c1 - c0;
+    }
+    return TXQ_OK;
+}
+
+// (profiling aid: TXQ_TRACE_SYNC + TXQ_TRACE_STAGES) what a sparse launch amounted to
+static void trace_sparse_launch(const Stage& g, size_t level, bool steps, size_t first_group, uint32_t ng, const uint32_t* counts) {
+    const double t_l = now_s();
+    (void)hipStreamSynchronize(g.st);
+    const double dt = now_s() - t_l;
+    std::vector<uint32_t> cnts(ng);
+    (void)hipMemcpy(cnts.data(), counts, (size_t)ng * 4, hipMemcpyDeviceToHost);
+    const txq_dense_op* hd = (const txq_dense_op*)(g.blob + g.bv.dense_offset);
+    uint64_t by_kind[5] = {0, 0, 0, 0, 0};  // entries: ZERO, STEP, REDUCE, FILL, STEP without probe
+    uint64_t visits = 0;
+    for (uint32_t gi = 0; gi < ng; ++gi) {
+        const txq_dense_op& x = hd[g.plan.sparse_groups[first_group + gi].op];
+        const bool np_ = x.kind == TXQ_DENSE_STEP && (x.reserved & TXQ_DENSE_NOPROBE);
+        by_kind[np_ ? 4 : x.kind] += cnts[gi];
+        if (x.kind == TXQ_DENSE_STEP) visits += (uint64_t)cnts[gi] * (uint64_t)__builtin_popcount(x.r_mask);
+    }
+    fprintf(stderr, "[txq]   sparse launch%s: level %zu, %u groups, %.1f us; entries: zero %llu, step %llu (+ %llu without probe; %llu visits), reduce %llu, fill %llu\n",
+            steps ? " (steps)" : "", level, ng, dt * 1e6, (unsigned long long)by_kind[0], (unsigned long long)by_kind[1], (unsigned long long)by_kind[4],
+            (unsigned long long)visits, (unsigned long long)by_kind[2], (unsigned long long)by_kind[3]);
+}
+
+// The level's sparse groups (dense ops of tracked programs): plan (counts -> chunks), then the chunks.  The groups are ordered
+// [others | STEPs]: ZERO / REDUCE / FILL run in the sparse_kernel variant without step code (66 VGPRs), the STEPs get launches
+// of their own, chunked by work — two ranges, each in segments of at most kMaxSparseGroups groups.  ride: the level's ordinary
+// units run in the first of these launches.
+static int run_sparse_groups(Stage& g, size_t l, bool ride) {
+    Session& s = g.s;
+    const LevelPlan& lp = g.plan.levels[l];
+    const uint32_t W = g.W;
+    const bool by_units = g.rows.by_units(s.kn, W);
+    const SparseGroup* d_sgroups = g.dev<const SparseGroup>(kSparseGroups);
+    uint32_t *d_scounts = g.dev<uint32_t>(kSparseCounts), *d_sprefix = g.dev<uint32_t>(kSparsePrefix);
+    const size_t n_misc = lp.sparse_misc;
+    bool rode = false;
+    for (int range = 0; range < 2; ++range) {
+        const size_t r_lo = range == 0 ? 0 : n_misc, r_hi = range == 0 ? n_misc : lp.sparse;
+        const bool steps = range == 1;
+        size_t range_chunks = steps ? lp.step_chunks : lp.sparse_chunks;
+        if (steps && by_units) range_chunks = range_chunks * (kSparseChunk / 16);  // (counted in chunks of kSparseChunk entries; a chunk by units holds 16 at least)
+        // The STEPs of sparse_kernel (trees; masks wider than kUnitStepWords): a chunk is ONE round of the workgroup's lane groups
+        // on wide masks — the live lists of a layout-order session are short (thousands of entries of 19.8 KB), and a
+        // chunk of 64 of them was sixteen rounds of dozens of dependent trips in one workgroup while most of the device
+        // idled (level 2 of the 200-motif batch: 2900 entries, 6.1 ms) — and kSparseChunk entries where a round holds that many
+        const uint32_t step_chunk = steps && !by_units && W > kUnitStepWords ? std::max<uint32_t>(1u, std::min<uint32_t>(kSparseChunk, 256u / g.rows.g)) : kSparseChunk;
+        if (steps && !by_units) range_chunks = range_chunks * (kSparseChunk / step_chunk);
+        for (size_t off = r_lo; off < r_hi; off += kMaxSparseGroups, ++g.sparse_launch) {
+            const uint32_t ng = (uint32_t)std::min<size_t>(kMaxSparseGroups, r_hi - off);
+            const SparseGroup* gr = d_sgroups + g.first_sparse + off;
+            uint32_t* counts = d_scounts + g.first_sparse + off;
+            uint32_t* prefix = d_sprefix + g.first_sparse + off + g.sparse_launch;
+            sparse_plan_kernel<<<1, 1024, 0, g.st>>>(gr, ng, g.d_dops, g.d_optr, W, g.bv.dense.pos, steps && by_units ? (0x80000000u | (uint32_t)s.kn.sparse_units) : step_chunk,
+                                                     counts, prefix);
+            TXQ_HIP(hipGetLastError());
+            const LevelUnits lu{g.d_units + g.first_unit, g.d_ops, g.d_masks, ride && !rode ? (uint32_t)lp.units : 0u, g.g_units_log2};
+            rode = true;
+            // as many workgroups as the chunks could be at most, within what the device holds at a time
+            const size_t grid = lu.n_units + std::max<size_t>(1, std::min<size_t>(range_chunks, 2048));
+            hipError_t e;
+            if (steps && by_units) {
+                StepParams sp{g.bv.dense.k, g.bv.dense.bits, g.bv.dense.pos, g.bv.dense.canonical, (uint32_t)s.kn.sparse_units, 0u};
 #ifdef TXQ_EXPERIMENTS
-                        if (const char* ex = std::getenv("TXQ_STEP_EXPERIMENT")) sp.experiment = (uint32_t)std::atoi(ex);  // 1: destination atomics twice, 2: bitmap atomics twice, 4: row gathers twice
+                if (const char* ex = std::getenv("TXQ_STEP_EXPERIMENT")) sp.experiment = (uint32_t)std::atoi(ex);  // 1: destination atomics twice, 2: bitmap atomics twice, 4: row gathers twice
 #endif
-                        if (table) {
-                            auto rows_tab = [&](auto& r) { r.table = ix.kmer_table; r.stride = W; };
-                            e = wide ? launch_sparse_units<true, TableRows>(1, rows_tab, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, sp, lu, s.d_step_ctr, s.kn.sparse_unroll, st)
-                                     : launch_sparse_units<false, TableRows>(1, rows_tab, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, sp, lu, s.d_step_ctr, s.kn.sparse_unroll, st);
-                        } else {
-                            auto rows_of = [&](auto& r) { r.f = ix.ibf[0]; };
-                            e = wide ? launch_sparse_units<true, FlatRows>(ix.ibf[0].hash_funs, rows_of, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, sp, lu, s.d_step_ctr, s.kn.sparse_unroll, st)
-                                     : launch_sparse_units<false, FlatRows>(ix.ibf[0].hash_funs, rows_of, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, sp, lu, s.d_step_ctr, s.kn.sparse_unroll, st);
-                        }
-                    } else if (split_steps && !steps) {  // ZERO / REDUCE / FILL only: the variant without the step code (its row source is not used)
-                        FlatRows<1, true> none{};
-                        if (wide) sparse_kernel<1, true, FlatRows<1, true>, false><<<(unsigned)grid, 256, 0, st>>>(none, gr, ng, counts, prefix, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, kSparseChunk);
-                        else { FlatRows<1, false> none1{}; sparse_kernel<1, false, FlatRows<1, false>, false><<<(unsigned)grid, 256, 0, st>>>(none1, gr, ng, counts, prefix, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, kSparseChunk); }
-                        e = hipGetLastError();
-                    } else if (vspace) {
-                        auto rows_path = [&](auto& r) { r.chunks = ix.d_vchunks; r.paths = ix.d_vpaths; r.split_range = ix.d_vsplit_range; r.splits = ix.d_vsplits; };
-                        e = wide ? launch_sparse<true, PathRows>(ix.tree_hash_max, rows_path, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, step_chunk, st)
-                                 : launch_sparse<false, PathRows>(ix.tree_hash_max, rows_path, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, step_chunk, st);
-                    } else if (interleaved) {
-                        auto rows_il = [&](auto& r) { r.f = ix.interleaved; r.root = ix.root_node; r.children = (const ChildRec*)ix.d_children; r.wpr_log2 = wpr_log2; };
-                        e = wide ? launch_sparse<true, InterleavedRows>(ix.tree_hash_max, rows_il, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, step_chunk, st)
-                                 : launch_sparse<false, InterleavedRows>(ix.tree_hash_max, rows_il, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, step_chunk, st);
-                    } else if (tree) {
-                        auto rows_of = [&](auto& r) { r.root = ix.root_node; r.children = (const ChildRec*)ix.d_children; r.wpr_log2 = wpr_log2; };
-                        e = wide ? launch_sparse<true, TreeRows>(ix.tree_hash_max, rows_of, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, step_chunk, st)
-                                 : launch_sparse<false, TreeRows>(ix.tree_hash_max, rows_of, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, step_chunk, st);
-                    } else if (table) {
-                        auto rows_tab = [&](auto& r) { r.table = ix.kmer_table; r.stride = W; };
-                        e = wide ? launch_sparse<true, TableRows>(1, rows_tab, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, step_chunk, st)
-                                 : launch_sparse<false, TableRows>(1, rows_tab, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, step_chunk, st);
-                    } else {
-                        auto rows_of = [&](auto& r) { r.f = ix.ibf[0]; };
-                        e = wide ? launch_sparse<true, FlatRows>(ix.ibf[0].hash_funs, rows_of, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, step_chunk, st)
-                                 : launch_sparse<false, FlatRows>(ix.ibf[0].hash_funs, rows_of, gr, ng, counts, prefix, grid, d_dops, d_optr, s.d_base, np, W, g_dense, bv.dense, lu, step_chunk, st);
-                    }
-                    if (e != hipSuccess) return fail_hip(e, "sparse kernel launch");
-                    if (s.kn.trace_sync && s.kn.trace_stages) {  // (profiling aid: TXQ_TRACE_SYNC + TXQ_TRACE_STAGES) what each sparse launch amounted to
-                        const double t_l = now_s();
-                        (void)hipStreamSynchronize(st);
-                        const double dt = now_s() - t_l;
-                        std::vector<uint32_t> cnts(ng);
-                        (void)hipMemcpy(cnts.data(), counts, (size_t)ng * 4, hipMemcpyDeviceToHost);
-                        const txq_dense_op* hd = (const txq_dense_op*)(blob + bv.dense_offset);
-                        uint64_t by_kind[5] = {0, 0, 0, 0, 0};  // entries: ZERO, STEP, REDUCE, FILL, STEP without probe
-                        uint64_t visits = 0;
-                        for (uint32_t gi = 0; gi < ng; ++gi) {
-                            const txq_dense_op& x = hd[sparse_groups[first_sparse + off + gi].op];
-                            const bool np_ = x.kind == TXQ_DENSE_STEP && (x.reserved & TXQ_DENSE_NOPROBE);
-                            by_kind[np_ ? 4 : x.kind] += cnts[gi];
-                            if (x.kind == TXQ_DENSE_STEP) visits += (uint64_t)cnts[gi] * (uint64_t)__builtin_popcount(x.r_mask);
-                        }
-                        fprintf(stderr, "[txq]   sparse launch%s: level %zu, %u groups, %.1f us; entries: zero %llu, step %llu (+ %llu without probe; %llu visits), reduce %llu, fill %llu\n",
-                                steps ? " (steps)" : "", l, ng, dt * 1e6, (unsigned long long)by_kind[0], (unsigned long long)by_kind[1], (unsigned long long)by_kind[4],
-                                (unsigned long long)visits, (unsigned long long)by_kind[2], (unsigned long long)by_kind[3]);
-                    }
-                    ++s.n_sparse_launches;
-                    s.n_sparse_groups += ng;
-                }
-            }
-            first_sparse += plan[l].sparse;
-            first += cnt;
+                e = launch_sparse_units(g, gr, ng, counts, prefix, grid, sp, lu);
+            } else if (!steps) e = launch_sparse_misc(g, gr, ng, counts, prefix, grid, lu);
+            else e = launch_sparse(g, gr, ng, counts, prefix, grid, lu, step_chunk);
+            if (e != hipSuccess) return fail_hip(e, "sparse kernel launch");
+            if (s.kn.trace_sync && s.kn.trace_stages) trace_sparse_launch(g, l, steps, g.first_sparse + off, ng, counts);
+            ++s.n_sparse_launches;
+            s.n_sparse_groups += ng;
         }
     }
+    return TXQ_OK;
+}
+
+// Phase 6, per dependency level: ordinary units, HIBF steps, dense tiles, sparse groups.  Ordinary and dense ops of one level
+// are independent of each other: no order implied.
+static int run_level(Stage& g, size_t l) {
+    Session& s = g.s;
+    const LevelPlan& lp = g.plan.levels[l];
+    const size_t cnt = lp.units;
+    ++s.n_levels;
+    // where the dense steps run fused, the level's units run inside its dense launch, or its sparse launch when it has no tiles;
+    // otherwise they are a launch of their own
+    const bool ride = s.kn.fuse_units && cnt && lp.tiles && g.rows.fused();
+    const bool ride_sparse = s.kn.fuse_units && cnt && !ride && lp.sparse && g.rows.fused();
+    if (cnt && !ride && !ride_sparse) {
+        ++s.n_unit_launches;
+        exec_units_kernel<<<(unsigned)cnt, 256, 0, g.st>>>(g.d_units + g.first_unit, g.d_ops, s.d_base, g.np, g.d_masks, g.W, g.g_units_log2);
+    }
+    s.n_units += cnt;
+    if (int rc = run_hibf_steps(g, lp)) return rc;
+    if (lp.tiles) {
+        const LevelUnits lu{g.d_units + g.first_unit, g.d_ops, g.d_masks, ride ? (uint32_t)cnt : 0u, g.g_units_log2};
+        hipError_t e = launch_dense(g, g.dev<const DenseTile>(kTiles) + g.first_tile, lp.tiles, lu);
+        if (e != hipSuccess) return fail_hip(e, "dense kernel launch");
+        g.first_tile += lp.tiles;
+        s.n_dense_tiles += lp.tiles;
+        ++s.n_dense_launches;
+    }
+    if (int rc = run_sparse_groups(g, l, ride_sparse)) return rc;
+    g.first_sparse += lp.sparse;
+    g.first_unit += cnt;
+    return TXQ_OK;
+}
+
+// Phase 7: the answers to the feedback questions; the staging set is busy until the stage's last kernel has run.
+static int stage_epilogue(Stage& g) {
+    Session& s = g.s;
+    Index::StagingSet& S = *g.set;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "exec kernel launch");
-    if (n_q) {
-        size_t blocks = (n_q + 3) / 4;
+    if (g.n_q) {
+        size_t blocks = (g.n_q + 3) / 4;
         if (blocks > 2048) blocks = 2048;
-        slot_alive_kernel<<<(unsigned)blocks, 256, 0, st>>>(s.d_base, d_qp, d_qs, (uint32_t)n_q, W, d_alive);
+        uint8_t* d_alive = g.dev<uint8_t>(kAlive);
+        slot_alive_kernel<<<(unsigned)blocks, 256, 0, g.st>>>(s.d_base, g.dev<const uint32_t>(kQueryProg), g.dev<const uint32_t>(kQuerySlot), (uint32_t)g.n_q, g.W, d_alive);
         TXQ_HIP(hipGetLastError());
-        TXQ_HIP(hipMemcpyAsync(alive, d_alive, n_q, hipMemcpyDeviceToHost, st));
-        TXQ_HIP(hipStreamSynchronize(st));
+        TXQ_HIP(hipMemcpyAsync(g.alive, d_alive, g.n_q, hipMemcpyDeviceToHost, g.st));
+        TXQ_HIP(hipStreamSynchronize(g.st));
     }
-    TXQ_HIP(hipEventRecord(S.done, st));
+    TXQ_HIP(hipEventRecord(S.done, g.st));
     S.pending = true;
-    if (s.kn.trace_sync) (void)hipStreamSynchronize(st);  // charges the device time to the stage that caused it
-    s.t_device += now_s() - t0;
+    if (s.kn.trace_sync) (void)hipStreamSynchronize(g.st);  // charges the device time to the stage that caused it
+    s.t_device += now_s() - g.t0;
+    const double* m = g.t_mark;
     if (s.kn.trace_stages)
         fprintf(stderr, "[txq] stage %zu: regions %.0f us, plan %.0f us, staging set %.0f us, buffers %.0f us, copies issued %.0f us, copies done %.0f us, launches %.0f us\n", s.n_stages,
-                (t_mark[0] - t_begin) * 1e6, (t_mark[1] - t_mark[0]) * 1e6, (t_mark[2] - t_mark[1]) * 1e6, (t_mark[3] - t_mark[2]) * 1e6, (t_mark[4] - t_mark[3]) * 1e6,
-                (t_mark[5] - t_mark[4]) * 1e6, (now_s() - t_mark[5]) * 1e6);
+                (m[0] - g.t_begin) * 1e6, (m[1] - m[0]) * 1e6, (m[2] - m[1]) * 1e6, (m[3] - m[2]) * 1e6, (m[4] - m[3]) * 1e6, (m[5] - m[4]) * 1e6, (now_s() - m[5]) * 1e6);
     return TXQ_OK;
+}
+
+// One stage of a session, phase by phase.  A failure after stage_upload may leave kernels running: the caller drains the
+// device and closes the session (txq_session_stage).
+int session_stage(Session& s, const void* blob, size_t bytes, const uint32_t* q_prog, const uint32_t* q_slot, size_t n_q, uint8_t* alive,
+                  hipStream_t caller_stream) {
+    Stage g{s, *s.ix, (const unsigned char*)blob, bytes, q_prog, q_slot, n_q, alive, caller_stream};
+    bool empty = false;
+    if (int rc = stage_decide(g, &empty)) return rc;
+    if (empty) return TXQ_OK;
+    if (int rc = stage_regions(g)) return rc;
+    if (int rc = stage_plan(g)) return rc;
+    if (int rc = stage_upload(g)) return rc;
+    if (int rc = stage_prologue(g)) return rc;
+    if (g.bv.n_ops) {
+        g.d_ops = (const txq_op*)(g.d_blob + g.bv.ops_offset);
+        g.d_dops = g.bv.n_dense ? (const txq_dense_op*)(g.d_blob + g.bv.dense_offset) : nullptr;
+        g.d_optr = g.dev<const DenseOpPtr>(kOptr);
+        g.d_units = g.dev<const ExecUnit>(kUnits);
+        g.np = (uint32_t)s.n_programs;
+        while ((1u << g.g_units_log2) < 256 && (1u << g.g_units_log2) < g.W) ++g.g_units_log2;  // lanes per op of a unit: the mask width rounded up to a power of two, at most 256
+        if (g.plan.n_small) launch_small_programs(g);
+        for (size_t l = 0; l < g.plan.levels.size(); ++l)
+            if (int rc = run_level(g, l)) return rc;
+    }
+    return stage_epilogue(g);
 }
 
 int session_finish(Session& s, uint64_t* d_final, hipStream_t st) {

@@ -757,12 +757,6 @@ __global__ __launch_bounds__(256) void hibf_layout_to_user_kernel(const uint64_t
     }
 }
 
-#define TXQ_HIP(call)                                        \
-    do {                                                     \
-        hipError_t e_ = (call);                              \
-        if (e_ != hipSuccess) return fail_hip(e_, #call);    \
-    } while (0)
-
 // Layout order for a tree that is not regular (txq_internal.hpp VChunk): the rows of all IBFs, levels ascending, each IBF
 // padded to whole 16-byte chunks; per chunk its record, per IBF its ancestors, which bits are user bins, and the user
 // bin behind every bit.  Single shard only (a column shard of the USER bins does not cut the layout-order row in one piece).
@@ -1074,18 +1068,11 @@ static bool layout_order_fused(Index& ix, const uint64_t* d_kmers, size_t n, uin
     while (g < 64 && (uint32_t)g < quads) g <<= 1;
     const uint32_t w_iters = (quads + (uint32_t)g - 1) / (uint32_t)g;
     if (w_iters > 1 && ix.d_vnonrep) return false;  // (split bins are unified for one pass of words per lane: the level kernels then)
-    hipError_t e;
-#define TXQ_FUSED(G) e = launch_fused<G, true>(grid, waves * 64, wave_bytes * waves, s, t, d_kmers, n, d_rows, w_out, 0u, w_iters, stack_cap, (uint32_t)wave_words, h_max, nullptr, stack_lds, row_lds_words)
-    switch (g) {
-        case 1: TXQ_FUSED(1); break;
-        case 2: TXQ_FUSED(2); break;
-        case 4: TXQ_FUSED(4); break;
-        case 8: TXQ_FUSED(8); break;
-        case 16: TXQ_FUSED(16); break;
-        case 32: TXQ_FUSED(32); break;
-        default: TXQ_FUSED(64); break;
-    }
-#undef TXQ_FUSED
+    hipError_t e = hipErrorInvalidValue;
+    with_value<1, 2, 4, 8, 16, 32, 64>(g, [&](auto G) {  // (g is a power of two)
+        e = launch_fused<decltype(G)::value, true>(grid, waves * 64, wave_bytes * waves, s, t, d_kmers, n, d_rows, w_out, 0u, w_iters, stack_cap, (uint32_t)wave_words, h_max,
+                                                   nullptr, stack_lds, row_lds_words);
+    });
     *rc = e == hipSuccess ? TXQ_OK : fail_hip(e, "layout-order fused kernel launch");
     return true;
 }
@@ -1141,13 +1128,13 @@ int hibf_probe_layout_order(Index& ix, const uint64_t* d_kmers_all, size_t n_all
             const uint32_t at = L.group_first[0], ng = L.group_first[1];
             const uint32_t phases = (ng + 7) / 8;
             if ((uint64_t)phases * n_tiles * 8 >= ((uint64_t)1 << 31)) return fail(TXQ_ERR_ARG, "too many k-mers for one layout-order probe");
-#define TXQ_LEVEL(CW, H) hibf_layout_level_kernel<CW, H><<<phases * n_tiles * 8, 256, 0, s>>>(ix.d_vchunks, ix.d_vgroups + at, ng, d_kmers, n, d_rows, ix.v_words, n_tiles, tile, (uint32_t)knobs().hibf_store & 112u)
-            if (ix.v_chunk_words == 1) {
-                switch (ix.tree_hash_max) { case 1: TXQ_LEVEL(1, 1); break; case 2: TXQ_LEVEL(1, 2); break; case 3: TXQ_LEVEL(1, 3); break; case 4: TXQ_LEVEL(1, 4); break; default: TXQ_LEVEL(1, 5); break; }
-            } else {
-                switch (ix.tree_hash_max) { case 1: TXQ_LEVEL(2, 1); break; case 2: TXQ_LEVEL(2, 2); break; case 3: TXQ_LEVEL(2, 3); break; case 4: TXQ_LEVEL(2, 4); break; default: TXQ_LEVEL(2, 5); break; }
-            }
-#undef TXQ_LEVEL
+            // (chunks of one or two row words; a hash count outside 1..4 means 5, the most an IBF has)
+            with_value<1, 2>(ix.v_chunk_words == 1 ? 1 : 2, [&](auto cw) {
+                with_hash_funs(ix.tree_hash_max >= 1 && ix.tree_hash_max <= 4 ? ix.tree_hash_max : 5u, [&](auto h) {
+                    hibf_layout_level_kernel<decltype(cw)::value, decltype(h)::value><<<phases * n_tiles * 8, 256, 0, s>>>(
+                        ix.d_vchunks, ix.d_vgroups + at, ng, d_kmers, n, d_rows, ix.v_words, n_tiles, tile, (uint32_t)knobs().hibf_store & 112u);
+                });
+            });
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return fail_hip(e, "layout-order level kernel launch");
         }
@@ -1493,19 +1480,11 @@ static bool hibf_probe_fused(Index& ix, const Knobs& kn, const uint64_t* d_kmers
         hipError_t e = hipMemsetAsync(d_alive, 0, ((n + 63) / 64) * 8, s);
         if (e != hipSuccess) { *rc = fail_hip(e, "hipMemsetAsync(alive)"); return true; }
     }
-    hipError_t e;
-#define TXQ_FUSED(G) e = launch_fused<G>(grid, waves * 64, wave_bytes * waves, s, t, d_kmers, n, d_masks, w_out, (uint32_t)ix.shard_word0, w_iters, \
-                                         stack_cap, (uint32_t)wave_words, h_max, d_alive, stack_lds, w_out)
-    switch (g) {
-        case 1: TXQ_FUSED(1); break;
-        case 2: TXQ_FUSED(2); break;
-        case 4: TXQ_FUSED(4); break;
-        case 8: TXQ_FUSED(8); break;
-        case 16: TXQ_FUSED(16); break;
-        case 32: TXQ_FUSED(32); break;
-        default: TXQ_FUSED(64); break;
-    }
-#undef TXQ_FUSED
+    hipError_t e = hipErrorInvalidValue;
+    with_value<1, 2, 4, 8, 16, 32, 64>(g, [&](auto G) {  // (g is a power of two)
+        e = launch_fused<decltype(G)::value>(grid, waves * 64, wave_bytes * waves, s, t, d_kmers, n, d_masks, w_out, (uint32_t)ix.shard_word0, w_iters, stack_cap,
+                                             (uint32_t)wave_words, h_max, d_alive, stack_lds, w_out);
+    });
     if (e != hipSuccess) *rc = fail_hip(e, "hibf fused kernel launch");
     return true;
 }
@@ -1563,19 +1542,11 @@ int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, ui
             size_t blocks = (groups * g + 255) / 256;
             if (blocks > 2048) blocks = 2048;
             if (blocks == 0) blocks = 1;
-            hipError_t e;
-#define TXQ_LVL(G) e = launch_level<G>((unsigned)blocks, s, t, d_kmers + off, in, in_count, (uint32_t)m, out, ix.d_counts + lvl, \
-                                       (uint32_t)(ix.depth > 1 ? cap : 0), overflow, d_masks + off * w_out, w_out, (uint32_t)ix.shard_word0, w_iters)
-            switch (g) {
-                case 1: TXQ_LVL(1); break;
-                case 2: TXQ_LVL(2); break;
-                case 4: TXQ_LVL(4); break;
-                case 8: TXQ_LVL(8); break;
-                case 16: TXQ_LVL(16); break;
-                case 32: TXQ_LVL(32); break;
-                default: TXQ_LVL(64); break;
-            }
-#undef TXQ_LVL
+            hipError_t e = hipErrorInvalidValue;
+            with_value<1, 2, 4, 8, 16, 32, 64>(g, [&](auto G) {  // (g is a power of two)
+                e = launch_level<decltype(G)::value>((unsigned)blocks, s, t, d_kmers + off, in, in_count, (uint32_t)m, out, ix.d_counts + lvl,
+                                                     (uint32_t)(ix.depth > 1 ? cap : 0), overflow, d_masks + off * w_out, w_out, (uint32_t)ix.shard_word0, w_iters);
+            });
             if (e != hipSuccess) return fail_hip(e, "hibf level kernel launch");
             hibf_clamp_kernel<<<1, 64, 0, s>>>(ix.d_counts + lvl, (uint32_t)cap);
         }

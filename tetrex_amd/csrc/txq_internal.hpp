@@ -5,9 +5,35 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
+// a HIP call whose failure ends the calling function with TXQ_ERR_HIP (functions that return a TXQ_* code)
+#define TXQ_HIP(call)                                        \
+    do {                                                     \
+        hipError_t e_ = (call);                              \
+        if (e_ != hipSuccess) return fail_hip(e_, #call);    \
+    } while (0)
+
 namespace txq {
+
+// A run-time value as a compile-time constant: f(std::integral_constant<int, V>{}) for the V of the list that equals v.
+// Returns false, with f not called, when v is none of them.  Kernel templates are instantiated for exactly the listed values
+// (fewer where f itself leaves combinations out with `if constexpr`).
+template <int... Vs, class F>
+inline bool with_value(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// the number of hash functions of an IBF: 1 .. 5; false: outside that range
+template <class F>
+inline bool with_hash_funs(uint32_t h, F&& f) {
+    return h <= 5 && with_value<1, 2, 3, 4, 5>((int)h, f);
+}
+template <class F>
+inline void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // Every environment variable libtxq.so reads (all of them A/B and test switches between code paths that give the
 // SAME results; listed in include/txq.h).  They are parsed in ONE place (txq_api.hip read_knobs) at the library's entry

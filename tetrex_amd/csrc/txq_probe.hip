@@ -318,26 +318,10 @@ static hipError_t launch_lpk(const IbfDev& f, const uint64_t* k, size_t n, uint6
         else return hipErrorInvalidValue;
         return hipGetLastError();
     }
-    switch (f.hash_funs) {
-        case 1: probe_kernel<LPK, 1, 2, false><<<grid, 256, 0, s>>>(f, k, n, m, a); break;
-        case 2: probe_kernel<LPK, 2, 2, false><<<grid, 256, 0, s>>>(f, k, n, m, a); break;
-        case 3: probe_kernel<LPK, 3, 2, false><<<grid, 256, 0, s>>>(f, k, n, m, a); break;
-        case 4: probe_kernel<LPK, 4, 2, false><<<grid, 256, 0, s>>>(f, k, n, m, a); break;
-        case 5: probe_kernel<LPK, 5, 2, false><<<grid, 256, 0, s>>>(f, k, n, m, a); break;
-        default: return hipErrorInvalidValue;
-    }
+    if (!with_hash_funs(f.hash_funs, [&](auto h) { probe_kernel<LPK, decltype(h)::value, 2, false><<<grid, 256, 0, s>>>(f, k, n, m, a); }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
-
-#define TXQ_H_SWITCH(KERNEL, GRID)                                         \
-    switch (f.hash_funs) {                                                 \
-        case 1: KERNEL<1><<<GRID, 256, 0, s>>>(f, k, n, m, a); break;      \
-        case 2: KERNEL<2><<<GRID, 256, 0, s>>>(f, k, n, m, a); break;      \
-        case 3: KERNEL<3><<<GRID, 256, 0, s>>>(f, k, n, m, a); break;      \
-        case 4: KERNEL<4><<<GRID, 256, 0, s>>>(f, k, n, m, a); break;      \
-        case 5: KERNEL<5><<<GRID, 256, 0, s>>>(f, k, n, m, a); break;      \
-        default: return hipErrorInvalidValue;                              \
-    }
 
 void preload_probe_kernels() {
     hipFuncAttributes a;
@@ -353,12 +337,14 @@ hipError_t launch_probe(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* 
             if (e != hipSuccess) return e;
         }
         const unsigned grid = grid_for(n, 4);
-        TXQ_H_SWITCH(probe_bigrows_kernel, grid);
+        if (!with_hash_funs(f.hash_funs, [&](auto h) { probe_bigrows_kernel<decltype(h)::value><<<grid, 256, 0, s>>>(f, k, n, m, a); }))
+            return hipErrorInvalidValue;
         return hipGetLastError();
     }
     if (f.stride == 1) {
         const unsigned grid = grid_for((n + 63) & ~(size_t)63, 256);
-        TXQ_H_SWITCH(probe_w1_kernel, grid);
+        if (!with_hash_funs(f.hash_funs, [&](auto h) { probe_w1_kernel<decltype(h)::value><<<grid, 256, 0, s>>>(f, k, n, m, a); }))
+            return hipErrorInvalidValue;
         return hipGetLastError();
     }
     const uint32_t chunks = f.stride >> 1;
@@ -384,16 +370,15 @@ static hipError_t launch_table_lpk(const IbfDev& f, const uint64_t* k, size_t n,
     // the build's grid covers the capacity (D is not known on the host); waves past D leave at once
     const unsigned bgrid = (unsigned)std::min<size_t>(((size_t)cap + 255) / 256, 2048);
     const unsigned grid = grid_for((n + 63) / 64, 4);
-    switch (f.hash_funs) {
-#define TXQ_TABLE_H(H)                                                                                                  \
-        case H:                                                                                                           \
-            probe_kernel<LPK, H, 2, false, NoRoot, kBuild><<<bgrid, 256, 0, s>>>(f, nullptr, 0, table, nullptr, NoRoot{}, T); \
-            probe_kernel<LPK, H, 2, false, NoRoot, kAnswer><<<grid, 256, 0, s>>>(f, k, n, m, a, NoRoot{}, T);             \
-            break;
-        TXQ_TABLE_H(2) TXQ_TABLE_H(3) TXQ_TABLE_H(4) TXQ_TABLE_H(5)
-#undef TXQ_TABLE_H
-        default: return hipErrorInvalidValue;
-    }
+    // (one hash function: a table row would be the IBF's own row — table_capacity never sends such an index here)
+    if (f.hash_funs < 2 || !with_hash_funs(f.hash_funs, [&](auto h) {
+            constexpr int H = decltype(h)::value;
+            if constexpr (H >= 2) {
+                probe_kernel<LPK, H, 2, false, NoRoot, kBuild><<<bgrid, 256, 0, s>>>(f, nullptr, 0, table, nullptr, NoRoot{}, T);
+                probe_kernel<LPK, H, 2, false, NoRoot, kAnswer><<<grid, 256, 0, s>>>(f, k, n, m, a, NoRoot{}, T);
+            }
+        }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -460,14 +445,8 @@ hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* k, size_t n, u
 template <int LPK>
 static hipError_t launch_tree_lpk(const IbfDev& f, const TreeRoot& root, const uint64_t* k, size_t n, uint64_t* m, uint64_t* a, hipStream_t s) {
     const unsigned grid = grid_for((n + 63) / 64, 4);
-    switch (f.hash_funs) {
-        case 1: probe_kernel<LPK, 1, 2, false, TreeRoot><<<grid, 256, 0, s>>>(f, k, n, m, a, root); break;
-        case 2: probe_kernel<LPK, 2, 2, false, TreeRoot><<<grid, 256, 0, s>>>(f, k, n, m, a, root); break;
-        case 3: probe_kernel<LPK, 3, 2, false, TreeRoot><<<grid, 256, 0, s>>>(f, k, n, m, a, root); break;
-        case 4: probe_kernel<LPK, 4, 2, false, TreeRoot><<<grid, 256, 0, s>>>(f, k, n, m, a, root); break;
-        case 5: probe_kernel<LPK, 5, 2, false, TreeRoot><<<grid, 256, 0, s>>>(f, k, n, m, a, root); break;
-        default: return hipErrorInvalidValue;
-    }
+    if (!with_hash_funs(f.hash_funs, [&](auto h) { probe_kernel<LPK, decltype(h)::value, 2, false, TreeRoot><<<grid, 256, 0, s>>>(f, k, n, m, a, root); }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 hipError_t launch_probe_interleaved(const IbfDev& f, const HibfNode& root, const void* children, uint32_t wpr_log2, const uint64_t* k, size_t n,
