@@ -166,7 +166,7 @@ def kmer_values(motif, k):
 
 
 def layout_split_chunks(descs):
-    """Mirror of the upload rule for split user bins in layout order (csrc/txq_hibf.hip build_layout_order): the chunk width
+    """Mirror of the upload rule for split user bins in layout order (csrc/txq_hibf_plan.hpp plan_layout_order, plan_split_bins): the chunk width
     (8-byte chunks when padding every IBF to 16 bytes would widen the row by more than 30 %), then per chunk of every IBF the
     non-representative parts of each split user bin whose representative — its lowest technical bin — lies in that chunk,
     ordered by the representative's bit and then by technical bin, and the chunk's first side bit (`bit0`: a chunk that does not

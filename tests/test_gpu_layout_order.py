@@ -1,6 +1,6 @@
 """Sessions on GENERAL HIBFs — three and more levels, user bins next to merged bins, split bins, user bins in any order:
 what seqan::hibf's layout produces (reference include/index_hibf.h:114-129,132-147) — work in LAYOUT ORDER
-(csrc/txq_internal.hpp VChunk; csrc/txq_hibf.hip hibf_layout_level_kernel; csrc/txq_exec.hip PathRows): masks are the rows
+(csrc/txq_records.hpp VChunk; csrc/txq_hibf.hip hibf_layout_level_kernel; csrc/txq_exec.hip PathRows): masks are the rows
 of the tree's own technical bins, written segment by segment, dense steps gather a lane's bytes from one IBF behind its
 ancestors' gates, and only the final masks are converted to user-bin order.  Every mask must equal the CPU oracle's
 collect() over membership_for — and the masks of the same queries in user-bin order (TXQ_HIBF_LAYOUT_ORDER=0: the descent

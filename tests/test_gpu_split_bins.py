@@ -1,4 +1,4 @@
-"""Split user bins with MANY parts in layout order (csrc/txq_internal.hpp VSplit): a fused step (csrc/txq_exec.hip PathRows) sees a
+"""Split user bins with MANY parts in layout order (csrc/txq_records.hpp VSplit): a fused step (csrc/txq_exec.hip PathRows) sees a
 split bin only through its representative's chunk and learns of the other parts from the IBF's side matrix, whose entries for
 one chunk are as many consecutive bits as the chunk has parts — 199 for a user bin split 200 ways, as seqan::hibf's layouts
 with tmax = 256 produce.  Every mask must equal the CPU oracle's, on every way a session can take; the planted k-mers of each

@@ -3,6 +3,7 @@
 // that needs one fails with TXQ_ERR_STATE.
 #include "../../include/txq.h"
 #include "txq_internal.hpp"
+#include "txq_hibf_plan.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -119,13 +120,6 @@ static int bind_index(const Index* ix) {
     return bind_device(ix ? ix->device : g_devices[0]);
 }
 
-// shard r of R owns mask words [lo, hi): as even as possible, earlier shards get the remainder
-static void shard_range(uint64_t words, int r, int R, uint64_t* lo, uint64_t* hi) {
-    uint64_t base = words / R, rem = words % R;
-    *lo = base * r + (r < (int)rem ? r : rem);
-    *hi = *lo + base + (r < (int)rem ? 1 : 0);
-}
-
 static int validate_ibf(const txq_ibf_desc& d, bool need_words) {
     if (d.bins == 0 || d.bin_size == 0) return fail(TXQ_ERR_ARG, "IBF with zero bins or rows");
     if (d.hash_funs < 1 || d.hash_funs > 5) return fail(TXQ_ERR_ARG, "hash_funs %llu outside 1..5", (unsigned long long)d.hash_funs);
@@ -141,20 +135,10 @@ static int validate_ibf(const txq_ibf_desc& d, bool need_words) {
 
 // Allocate one IBF (column slice [w0, w1) of its rows) in HBM; copies from `src` when given.
 int alloc_ibf(const txq_ibf_desc& d, uint64_t w0, uint64_t w1, IbfDev* out, uint64_t* bytes) {
-    IbfDev f{};
-    f.bin_size = d.bin_size;
-    f.hash_shift = (uint32_t)d.hash_shift;
-    f.hash_funs = (uint32_t)d.hash_funs;
-    f.bins = (uint32_t)d.bins;
-    f.word0 = (uint32_t)w0;
-    f.ident_word = kNoIdent;
-    f.reserved = 0;
-    f.shard_words = (uint32_t)(w1 - w0);
-    f.stride = f.shard_words <= 1 ? 1u : ((f.shard_words + 1u) & ~1u);
-    f.words = nullptr;
+    IbfDev f = ibf_shape(d, w0, w1);
     *bytes = 0;
     if (f.shard_words) {
-        const size_t nbytes = (size_t)d.bin_size * f.stride * 8;
+        const size_t nbytes = ibf_bytes(f);
         TXQ_HIP(hipMalloc((void**)&f.words, nbytes));
         *bytes = nbytes;
         hipError_t e = hipSuccess;
@@ -174,10 +158,8 @@ int alloc_ibf(const txq_ibf_desc& d, uint64_t w0, uint64_t w1, IbfDev* out, uint
 void Index::release() {
     for (auto& f : ibf) if (f.words) (void)hipFree(f.words);
     ibf.clear();
-    if (d_ibf) (void)hipFree(d_ibf);
-    if (d_next) (void)hipFree(d_next);
-    if (d_tb_user) (void)hipFree(d_tb_user);
-    if (d_map_off) (void)hipFree(d_map_off);
+    for (void* p : uploaded) (void)hipFree(p);  // every array of an HIBF upload; the fields that point at them die with the index
+    uploaded.clear();
     for (int i = 0; i < 2; ++i) {
         if (host_pipe.stream[i]) (void)hipStreamDestroy(host_pipe.stream[i]);
         if (host_pipe.done[i]) (void)hipEventDestroy(host_pipe.done[i]);
@@ -201,26 +183,11 @@ void Index::release() {
                     (void*)session_cache.set[0].d_masks, (void*)session_cache.set[1].d_masks})
         if (p) (void)hipFree(p);
     session_cache = SessionCache{};
-    for (void* p : {(void*)d_vchunks, (void*)d_vpaths, (void*)d_vleaf, (void*)d_vuser, (void*)d_vgroups, (void*)d_vnodes, (void*)d_vnonrep, (void*)d_vrep, (void*)d_vsplit_range, (void*)d_vsplits, (void*)d_vside})
-        if (p) (void)hipFree(p);
-    d_vchunks = nullptr; d_vpaths = nullptr; d_vleaf = nullptr; d_vuser = nullptr; d_vgroups = nullptr; d_vnodes = nullptr;
-    d_vnonrep = nullptr; d_vrep = nullptr; d_vsplit_range = nullptr; d_vsplits = nullptr; d_vside = nullptr;
-    v_words = n_vchunks = 0;
-    vlevels.clear();
-    if (d_children) (void)hipFree(d_children);
-    if (interleaved.words) (void)hipFree(interleaved.words);
     interleaved = IbfDev{};
     if (scratch_cm) (void)hipFree(scratch_cm);
     if (scratch_crows) (void)hipFree(scratch_crows);
     scratch_crows = nullptr; cap_crows = 0;
-    d_children = nullptr; scratch_cm = nullptr; cap_cm = 0; n_children = 0;
-    if (d_merged) (void)hipFree(d_merged);
-    if (d_descend) (void)hipFree(d_descend);
-    if (d_nodes) (void)hipFree(d_nodes);
-    d_nodes = nullptr;
-    d_descend = nullptr;
-    if (d_merged_off) (void)hipFree(d_merged_off);
-    d_merged = d_merged_off = nullptr;
+    scratch_cm = nullptr; cap_cm = 0;
     for (void* p : {(void*)scratch_kmers, (void*)scratch_masks, (void*)frontier[0], (void*)frontier[1], (void*)d_counts,
                     (void*)scratch_blob, (void*)scratch_slots, (void*)scratch_final, (void*)scratch_dense_kmers, (void*)scratch_dense_masks, (void*)kmer_table,
                     (void*)scratch_count_acc, (void*)scratch_count_io})
@@ -228,7 +195,6 @@ void Index::release() {
     scratch_count_acc = nullptr; cap_count_acc = 0;
     scratch_count_io = nullptr; cap_count_io = 0;
     kmer_table = nullptr; kmer_table_bits = 0;
-    d_ibf = nullptr; d_next = d_tb_user = nullptr; d_map_off = nullptr;
     scratch_kmers = scratch_masks = nullptr; frontier[0] = frontier[1] = nullptr; d_counts = nullptr;
     scratch_blob = nullptr; scratch_slots = scratch_final = nullptr;
     if (host_final) { (void)hipHostFree(host_final); host_final = nullptr; cap_host_final = 0; }
@@ -364,33 +330,6 @@ int txq_index_upload(const txq_index_desc* desc, int shard_rank, int n_shards, t
     return upload_impl(desc, hibf, shard_rank, shard_rank, n_shards, out);
 }
 
-// Is the tree what hibf_upload recognises as a regular two-level one (root of merged bins only over leaf IBFs that each map an
-// aligned run of user bins, all of one power-of-two row width, tiling the mask)?  Those shard by mask columns.
-static bool regular_two_level(const txq_index_desc& d) {
-    const uint64_t n = d.n_ibf;
-    if (n < 2 || d.ibf[0].bins != n - 1) return false;
-    const uint64_t wpr = d.ibf[1].bin_words;
-    if (wpr < 1 || (wpr & (wpr - 1)) || wpr > 128 || (d.user_bins + 63) / 64 != wpr * (n - 1)) return false;
-    std::vector<uint8_t> seen(n, 0), column(n - 1, 0);
-    for (uint64_t b = 0; b < d.ibf[0].bins; ++b) {
-        if (d.tb_to_user_bin[0][b] != TXQ_MERGED_BIN) return false;
-        const uint64_t c = d.next_ibf_id[0][b];
-        if (c == 0 || c >= n || seen[c]) return false;
-        seen[c] = 1;
-    }
-    for (uint64_t i = 1; i < n; ++i) {
-        if (d.ibf[i].bin_words != wpr) return false;
-        const uint64_t base = d.tb_to_user_bin[i][0];
-        if (base == TXQ_MERGED_BIN || base % (wpr * 64)) return false;
-        for (uint64_t b = 0; b < d.ibf[i].bins; ++b)
-            if (d.tb_to_user_bin[i][b] != base + b) return false;
-        const uint64_t col = base / (wpr * 64);
-        if (col >= n - 1 || column[col]) return false;
-        column[col] = 1;
-    }
-    return true;
-}
-
 int txq_index_upload_subtrees(const txq_index_desc* desc, int shard_rank, int n_shards, txq_index** out) {
     read_knobs();
     if (int rc = require_init()) return rc;
@@ -401,72 +340,28 @@ int txq_index_upload_subtrees(const txq_index_desc* desc, int shard_rank, int n_
     for (uint64_t i = 0; i < n; ++i)
         if (!desc->next_ibf_id[i] || !desc->tb_to_user_bin[i]) return fail(TXQ_ERR_ARG, "HIBF map %llu is null", (unsigned long long)i);
     if (regular_two_level(*desc)) return upload_impl(desc, hibf, shard_rank, shard_rank, n_shards, out);
-    // the sub-trees under the root's merged bins and the row words under each (the whole tree is checked by hibf_upload below;
-    // here only what the walk itself needs: children in range, no IBF reached twice)
-    std::vector<int> owner_of_ibf(n, -1);  // which root bin's sub-tree an IBF belongs to (-1: the root)
-    std::vector<uint64_t> weight(desc->ibf[0].bins, 0);
-    std::vector<uint8_t> reached(n, 0);
-    reached[0] = 1;
-    for (uint64_t b = 0; b < desc->ibf[0].bins; ++b) {
-        if (desc->tb_to_user_bin[0][b] != TXQ_MERGED_BIN) continue;
-        std::vector<uint64_t> stack{desc->next_ibf_id[0][b]};
-        while (!stack.empty()) {
-            const uint64_t i = stack.back();
-            stack.pop_back();
-            if (i >= n || reached[i]) return fail(TXQ_ERR_ARG, "HIBF: bad child %llu (out of range or reached twice)", (unsigned long long)i);
-            reached[i] = 1;
-            owner_of_ibf[i] = (int)b;
-            weight[b] += desc->ibf[i].bin_words;
-            for (uint64_t c = 0; c < desc->ibf[i].bins; ++c)
-                if (desc->tb_to_user_bin[i][c] == TXQ_MERGED_BIN) stack.push_back(desc->next_ibf_id[i][c]);
-        }
+    // this shard's tree (txq_hibf_plan.hpp plan_subtree_shard); user bins are checked by the upload of the IBFs the shard keeps
+    HibfTree tree;
+    if (PlanError e = read_tree(*desc, false, &tree, false)) {
+        if (e.kind == PlanError::kBadChild || e.kind == PlanError::kTwoParents)
+            return fail(TXQ_ERR_ARG, "HIBF: bad child %llu (out of range or reached twice)", (unsigned long long)e.ibf);
+        return fail(e.code, "%s", e.text.c_str());
     }
-    for (uint64_t i = 0; i < n; ++i)
-        if (!reached[i]) return fail(TXQ_ERR_ARG, "IBF %llu is unreachable from the root", (unsigned long long)i);
-    // largest sub-tree first, to the shard that holds least (ties: the lower shard) — the same deal on every rank
-    std::vector<uint64_t> order;
-    for (uint64_t b = 0; b < desc->ibf[0].bins; ++b)
-        if (desc->tb_to_user_bin[0][b] == TXQ_MERGED_BIN) order.push_back(b);
-    std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return weight[a] > weight[b]; });
-    std::vector<uint64_t> load(n_shards, 0);
-    std::vector<int> shard_of_bin(desc->ibf[0].bins, 0);  // (the root's own user bins: shard 0)
-    for (uint64_t b : order) {
-        int best = 0;
-        for (int r = 1; r < n_shards; ++r)
-            if (load[r] < load[best]) best = r;
-        shard_of_bin[b] = best;
-        load[best] += weight[b];
-    }
-    // this shard's tree: the root and its own sub-trees, renumbered in the original order; in its copy of the root the columns of
-    // everybody else's technical bins are cleared and those bins become kClearedBin: no user bin, never firing
-    std::vector<uint64_t> new_id(n, UINT64_MAX), kept;
-    for (uint64_t i = 0; i < n; ++i)
-        if (i == 0 || shard_of_bin[owner_of_ibf[i]] == shard_rank) { new_id[i] = kept.size(); kept.push_back(i); }
+    const SubtreeShard shard = plan_subtree_shard(tree, *desc, shard_rank, n_shards);
+    const std::vector<uint64_t>& kept = shard.kept;
     const txq_ibf_desc& root = desc->ibf[0];
-    std::vector<uint64_t> keep_mask(root.bin_words, 0);
-    for (uint64_t b = 0; b < root.bins; ++b)
-        if (shard_of_bin[b] == shard_rank) keep_mask[b >> 6] |= 1ULL << (b & 63);
     std::vector<uint64_t> root_words((size_t)root.bin_size * root.bin_words);
     for (uint64_t r = 0; r < root.bin_size; ++r)
-        for (uint64_t w = 0; w < root.bin_words; ++w) root_words[r * root.bin_words + w] = root.words[r * root.bin_words + w] & keep_mask[w];
+        for (uint64_t w = 0; w < root.bin_words; ++w) root_words[r * root.bin_words + w] = root.words[r * root.bin_words + w] & shard.keep_mask[w];
     std::vector<txq_ibf_desc> ibfs;
-    std::vector<std::vector<uint64_t>> next(kept.size()), user(kept.size());
     std::vector<const uint64_t*> next_p, user_p;
     for (size_t j = 0; j < kept.size(); ++j) {
-        const uint64_t i = kept[j];
-        txq_ibf_desc d = desc->ibf[i];
-        if (i == 0) d.words = root_words.data();
+        txq_ibf_desc d = desc->ibf[kept[j]];
+        if (kept[j] == 0) d.words = root_words.data();
         ibfs.push_back(d);
-        next[j].assign(desc->ibf[i].bins, 0);
-        user[j].assign(desc->ibf[i].bins, 0);
-        for (uint64_t b = 0; b < desc->ibf[i].bins; ++b) {
-            const uint64_t ub = desc->tb_to_user_bin[i][b];
-            if (i == 0 && shard_of_bin[b] != shard_rank) { user[j][b] = kClearedBin; continue; }  // (cleared column: no user bin, never reported)
-            user[j][b] = ub;
-            if (ub == TXQ_MERGED_BIN) next[j][b] = new_id[desc->next_ibf_id[i][b]];
-        }
+        next_p.push_back(shard.next[j].data());
+        user_p.push_back(shard.user[j].data());
     }
-    for (size_t j = 0; j < kept.size(); ++j) { next_p.push_back(next[j].data()); user_p.push_back(user[j].data()); }
     const txq_index_desc pruned{kept.size(), ibfs.data(), next_p.data(), user_p.data(), desc->user_bins};
     if (int rc = upload_impl(&pruned, true, shard_rank, 0, 1, out, true)) return rc;
     (*out)->join_or = true;

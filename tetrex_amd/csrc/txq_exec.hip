@@ -490,7 +490,7 @@ struct TreeRowsByLane : TreeRows<H, WIDE> {
     static constexpr bool kPullsSplit = false;
 };
 
-// A general HIBF in layout order (txq_internal.hpp VChunk): the lane's 16 bytes are two row words of ONE IBF of the tree, and
+// A general HIBF in layout order (txq_records.hpp VChunk): the lane's 16 bytes are two row words of ONE IBF of the tree, and
 // M[k-mer] there = that IBF's rows ANDed, if the k-mer gets that far — if, in every ancestor from the root down, the rows
 // ANDed have the bit of the merged bin that leads towards it (membership_for(·, 1), reference include/index_hibf.h:132-147,
 // restated per technical bin).  Two rounds of loads like TreeRows: the gate words of all ancestors (8 bytes each; the lanes
@@ -593,7 +593,7 @@ struct PathRows {
         for (int h = 0; h < H; ++h) y &= l.x[h];
         return y;
     }
-    // Split user bins (txq_internal.hpp VSplit).  y = mask & M[k-mer] of this chunk as the IBF's rows give it, `mask` in the
+    // Split user bins (txq_records.hpp VSplit).  y = mask & M[k-mer] of this chunk as the IBF's rows give it, `mask` in the
     // session's form — a split bin is its representative's bit.  A representative that is set in `mask` also stays when ANOTHER
     // part of its bin holds the k-mer: the k-mer's h rows of the IBF's side matrix, ANDed, are those parts' hits — one word per
     // row for the whole chunk, asked only when a representative is open; a hit names its representative through the chunk's
@@ -1842,7 +1842,7 @@ int session_begin(Index& ix, size_t n_programs, Session** out) {
     s->kn = knobs();
     ++ix.open_sessions;
     s->n_programs = n_programs;
-    s->vspace = ix.layout_order(s->kn);  // a general HIBF: the session's masks are rows in layout order (txq_internal.hpp VChunk)
+    s->vspace = ix.layout_order(s->kn);  // a general HIBF: the session's masks are rows in layout order (txq_records.hpp VChunk)
     s->W = s->vspace ? ix.v_words : (uint32_t)ix.shard_words;
     s->base.assign(2 * n_programs, nullptr);
     s->cap.assign(n_programs, 0);

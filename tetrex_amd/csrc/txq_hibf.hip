@@ -10,9 +10,9 @@
 // "any bit of the run is set", so every set technical bin can be handled independently.
 // No host round trip between levels: each level kernel reads its item count from HBM.
 #include "txq_internal.hpp"
+#include "txq_hibf_plan.hpp"
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <utility>
 
 namespace txq {
@@ -29,7 +29,7 @@ struct HibfView {
     // record, nodes[e] (no next_ibf_id -> descriptor chain); nodes[total technical bins] is the root
     const struct HibfNode* nodes;
     uint32_t root_entry;
-    // LAYOUT rows of trees with split user bins (txq_internal.hpp VSplit): per row word the bits that are not their bin's
+    // LAYOUT rows of trees with split user bins (txq_records.hpp VSplit): per row word the bits that are not their bin's
     // representative, and for such a bit the representative's position in the row (null: no split bins)
     const uint64_t* nonrep = nullptr;
     const uint32_t* rep_pos = nullptr;
@@ -137,8 +137,6 @@ __global__ __launch_bounds__(256) void hibf_level_kernel(HibfView t, const uint6
     }
 }
 
-constexpr uint32_t kRootEntry = 0xFFFFFFFFu;  // stack entry of the root IBF (every other entry is a technical-bin index)
-
 // value of `v` in lane `src` (wave-uniform src)
 __device__ __forceinline__ uint64_t read_lane(uint64_t v, int src) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
@@ -167,7 +165,7 @@ __device__ __forceinline__ void wave_sync() {
 // EVERY IBF of the tree): entries beyond them go into the k-mer's own output row in HBM, which is this wave's alone until it
 // writes the finished row over it (the host checks that the row has the room: stack_cap - stack_lds <= 2 * w_out entries) —
 // the LDS the never-used tail of the stack took is worth one to four more resident waves per CU.
-// LAYOUT: the row is the tree's layout-order row (txq_internal.hpp VChunk) — t.nodes are then the records whose ident_word is
+// LAYOUT: the row is the tree's layout-order row (txq_records.hpp VChunk) — t.nodes are then the records whose ident_word is
 // the IBF's first word IN THAT ROW (Index::d_vnodes), t.descend = t.merged, and an IBF's ANDed row words go into its segment
 // as they are, merged bins' bits included (one lane owns a word: plain LDS stores; no technical-bin -> user-bin mapping).
 template <int G, bool LAYOUT = false>
@@ -328,7 +326,7 @@ __global__ __launch_bounds__(256) void hibf_fused_kernel(HibfView t, const uint6
                 }
             }
             if constexpr (LAYOUT) {
-                // Split user bins (txq_internal.hpp VSplit): a bin is its representative — the bits of its other parts were held
+                // Split user bins (txq_records.hpp VSplit): a bin is its representative — the bits of its other parts were held
                 // back from the row above (their mask came with the rows' loads) and go to the representative now that all of the
                 // round's words are in the row (plain stores, every IBF by its own lanes): LDS atomics for the rare word that has any.
                 // (w_iters == 1 wherever this kernel runs in layout order: an IBF of more than 256 * G technical bins would need
@@ -661,7 +659,7 @@ __global__ __launch_bounds__(256) void mask_alive_kernel(const uint64_t* __restr
     }
 }
 
-// ---- layout order (txq_internal.hpp VChunk): the rows of a general HIBF, level by level, child-stationary ----------
+// ---- layout order (txq_records.hpp VChunk): the rows of a general HIBF, level by level, child-stationary ----------
 // One launch per level of the tree.  A workgroup = a tile of k-mers x one GROUP of the level's chunks (consecutive
 // chunks whose IBFs' rows fit an XCD's L2: workgroup b takes group b % 8 of its phase, and the dispatcher deals
 // workgroups round-robin over the 8 XCDs, so an XCD keeps probing the same few MB — a speed assumption only).
@@ -757,10 +755,7 @@ __global__ __launch_bounds__(256) void hibf_layout_to_user_kernel(const uint64_t
     }
 }
 
-// Layout order for a tree that is not regular (txq_internal.hpp VChunk): the rows of all IBFs, levels ascending, each IBF
-// padded to whole 16-byte chunks; per chunk its record, per IBF its ancestors, which bits are user bins, and the user
-// bin behind every bit.  Single shard only (a column shard of the USER bins does not cut the layout-order row in one piece).
-// The side matrix of an IBF with split user bins (txq_internal.hpp VSplit): one thread per row copies the bits of the IBF's
+// The side matrix of an IBF with split user bins (txq_records.hpp VSplit): one thread per row copies the bits of the IBF's
 // non-representative parts (`entries`) to their places in the side row (`pos`: word * 64 + bit).
 __global__ __launch_bounds__(256) void build_side_matrix_kernel(const uint64_t* __restrict__ words, uint32_t stride, uint64_t rows, const VSplit* __restrict__ entries,
                                                                 const uint32_t* __restrict__ pos, uint32_t n_entries, uint64_t* __restrict__ side, uint32_t side_stride) {
@@ -777,243 +772,6 @@ __global__ __launch_bounds__(256) void build_side_matrix_kernel(const uint64_t* 
         acc |= ((row[sp.part_word] >> sp.part_bit) & 1ULL) << (p & 63);
     }
     out[word] = acc;
-}
-
-static int build_layout_order(Index& ix, const txq_index_desc& desc, const std::vector<int>& level, const std::vector<uint64_t>& next,
-                              const std::vector<uint64_t>& tbu, const std::vector<uint64_t>& off, const std::vector<HibfNode>* nodes) {
-    const uint64_t n = desc.n_ibf;
-    if (ix.shard_words != ix.mask_words || ix.shard_word0 != 0 || ix.depth > kMaxVDepth + 1 || desc.user_bins >= kNoGate) return TXQ_OK;
-    for (const IbfDev& f : ix.ibf)
-        if ((f.bin_size >> 32) || f.stride >= (1u << 20) || f.hash_funs > 5) return TXQ_OK;
-    // IBFs by level (BFS order within a level), their segments in the row
-    std::vector<std::vector<uint64_t>> by_level(ix.depth);
-    for (uint64_t i = 0; i < n; ++i) by_level[level[i]].push_back(i);
-    std::vector<uint64_t> seg(n, 0), parent(n, UINT64_MAX), parent_tb(n, 0);
-    for (uint64_t i = 0; i < n; ++i)
-        for (uint64_t b = 0; b < desc.ibf[i].bins; ++b)
-            if (tbu[off[i] + b] == TXQ_MERGED_BIN) { parent[next[off[i] + b]] = i; parent_tb[next[off[i] + b]] = b; }
-    // 16-byte chunks (every IBF padded to an even number of words) unless that widens the row by more than 30 % — trees of
-    // many one-word IBFs —: then 8-byte chunks
-    uint64_t exact = 0, padded2 = 0;
-    for (uint64_t i = 0; i < n; ++i) { exact += desc.ibf[i].bin_words; padded2 += (desc.ibf[i].bin_words + 1) & ~(uint64_t)1; }
-    const uint64_t cwords = padded2 * 10 > exact * 13 ? 1 : 2;
-    uint64_t words = 0;
-    for (auto& lv : by_level)
-        for (uint64_t i : lv) { seg[i] = words; words += (desc.ibf[i].bin_words + cwords - 1) / cwords * cwords; }
-    const bool pad_word = (words & 1) != 0;  // (slot masks of an even number of words: one word that belongs to no IBF)
-    if (pad_word) ++words;
-    if (words >= (1u << 26)) return TXQ_OK;
-    std::vector<VChunk> chunks;
-    std::vector<uint32_t> chunk0(n, 0);  // an IBF's first chunk
-    std::vector<VPath> paths(n);
-    std::vector<uint64_t> leaf(words, 0);
-    std::vector<uint32_t> vuser(words * 64, kNoGate);
-    std::vector<uint32_t> groups;  // per level: first chunk of each group, then the level's end
-    ix.vlevels.clear();
-    auto packed_of = [](const IbfDev& f) { return f.stride | (f.hash_shift << 20) | (f.hash_funs << 26) | ((uint32_t)(f.stride == 1) << 29); };
-    for (auto& lv : by_level) {
-        VLevel L;
-        L.first_chunk = (uint32_t)chunks.size();
-        uint64_t group_bytes = 0;
-        for (uint64_t i : lv) {
-            const IbfDev& f = ix.ibf[i];
-            const uint64_t bytes = f.bin_size * (uint64_t)f.stride * 8;
-            if (L.group_first.empty() || group_bytes + bytes > ((uint64_t)2 << 20)) { L.group_first.push_back((uint32_t)chunks.size()); group_bytes = 0; }
-            group_bytes += bytes;
-            const uint64_t padded = (desc.ibf[i].bin_words + cwords - 1) / cwords * cwords;
-            chunk0[i] = (uint32_t)chunks.size();
-            for (uint64_t c = 0; c < padded; c += cwords) {
-                VChunk r{};
-                r.words = (uint64_t)(uintptr_t)f.words;
-                r.bin_size = (uint32_t)f.bin_size;
-                r.packed = packed_of(f);
-                r.col = (uint32_t)c;
-                r.gate_word = parent[i] == UINT64_MAX ? kNoGate : (uint32_t)(seg[parent[i]] + (parent_tb[i] >> 6));
-                r.gate_bit = (uint32_t)(parent_tb[i] & 63);
-                r.ibf = (uint32_t)i;
-                chunks.push_back(r);
-            }
-            for (uint64_t b = 0; b < desc.ibf[i].bins; ++b)
-                if (tbu[off[i] + b] != TXQ_MERGED_BIN && tbu[off[i] + b] != kClearedBin) {  // (a cleared root bin is no user bin)
-                    leaf[seg[i] + (b >> 6)] |= 1ULL << (b & 63);
-                    vuser[(seg[i] + (b >> 6)) * 64 + (b & 63)] = (uint32_t)tbu[off[i] + b];
-                }
-            VPath& p = paths[i];
-            p.depth = 0;
-            std::vector<uint64_t> chain;  // i's ancestors, nearest first
-            for (uint64_t a = i; parent[a] != UINT64_MAX; a = parent[a]) chain.push_back(a);
-            for (size_t at = chain.size(); at-- > 0;) {  // root first
-                const uint64_t child = chain[at], a = parent[child];
-                const IbfDev& fa = ix.ibf[a];
-                auto& slot = p.anc[p.depth++];
-                slot.words = (uint64_t)(uintptr_t)fa.words;
-                slot.bin_size = (uint32_t)fa.bin_size;
-                slot.packed = packed_of(fa);
-                slot.word = (uint32_t)(parent_tb[child] >> 6);
-                slot.bit = (uint32_t)(parent_tb[child] & 63);
-            }
-        }
-        if (pad_word && &lv == &by_level.back()) {  // the padding word: a chunk without hash functions — always zero
-            VChunk r{};
-            r.words = (uint64_t)(uintptr_t)ix.ibf[0].words;
-            r.bin_size = 1;
-            r.packed = 1;  // stride 1, no hash function
-            r.gate_word = kNoGate;
-            chunks.push_back(r);
-        }
-        L.n_chunks = (uint32_t)chunks.size() - L.first_chunk;
-        L.group_first.push_back((uint32_t)chunks.size());
-        ix.vlevels.push_back(L);
-    }
-    for (VLevel& L : ix.vlevels) {  // the groups of all levels in one device array; group_first becomes offsets into it
-        const uint32_t at = (uint32_t)groups.size();
-        groups.insert(groups.end(), L.group_first.begin(), L.group_first.end());
-        const uint32_t ng = (uint32_t)L.group_first.size() - 1;
-        L.group_first.assign({at, ng});
-    }
-    if (nodes) {  // the fused kernel's node records with every IBF's place in the layout-order row (hibf_fused_kernel<G, LAYOUT>)
-        std::vector<HibfNode> vn(*nodes);
-        for (uint64_t i = 0; i < n; ++i)
-            for (uint64_t b = 0; b < desc.ibf[i].bins; ++b)
-                if (tbu[off[i] + b] == TXQ_MERGED_BIN) vn[off[i] + b].ident_word = (uint32_t)seg[next[off[i] + b]];
-        vn[off[n]].ident_word = (uint32_t)seg[0];
-        TXQ_HIP(hipMalloc((void**)&ix.d_vnodes, vn.size() * sizeof(HibfNode)));
-        TXQ_HIP(hipMemcpy(ix.d_vnodes, vn.data(), vn.size() * sizeof(HibfNode), hipMemcpyHostToDevice));
-        ix.device_bytes += vn.size() * sizeof(HibfNode);
-    }
-    TXQ_HIP(hipMalloc((void**)&ix.d_vchunks, chunks.size() * sizeof(VChunk)));
-    TXQ_HIP(hipMalloc((void**)&ix.d_vpaths, paths.size() * sizeof(VPath)));
-    TXQ_HIP(hipMalloc((void**)&ix.d_vleaf, leaf.size() * 8));
-    TXQ_HIP(hipMalloc((void**)&ix.d_vuser, vuser.size() * 4));
-    TXQ_HIP(hipMalloc((void**)&ix.d_vgroups, groups.size() * 4));
-    TXQ_HIP(hipMemcpy(ix.d_vchunks, chunks.data(), chunks.size() * sizeof(VChunk), hipMemcpyHostToDevice));
-    TXQ_HIP(hipMemcpy(ix.d_vpaths, paths.data(), paths.size() * sizeof(VPath), hipMemcpyHostToDevice));
-    TXQ_HIP(hipMemcpy(ix.d_vleaf, leaf.data(), leaf.size() * 8, hipMemcpyHostToDevice));
-    TXQ_HIP(hipMemcpy(ix.d_vuser, vuser.data(), vuser.size() * 4, hipMemcpyHostToDevice));
-    TXQ_HIP(hipMemcpy(ix.d_vgroups, groups.data(), groups.size() * 4, hipMemcpyHostToDevice));
-    {   // split user bins (txq_internal.hpp VSplit): per IBF the technical bins by user bin; the lowest part represents the bin
-        std::vector<uint64_t> nonrep(words, 0);
-        std::vector<uint32_t> rep_pos;
-        std::vector<std::vector<VSplit>> per_chunk(chunks.size());
-        bool any = false;
-        std::vector<std::pair<uint64_t, uint64_t>> bins_of;  // (user bin, technical bin) of one IBF
-        for (uint64_t i = 0; i < n; ++i) {
-            bins_of.clear();
-            for (uint64_t b = 0; b < desc.ibf[i].bins; ++b)
-                if (tbu[off[i] + b] != TXQ_MERGED_BIN && tbu[off[i] + b] != kClearedBin) bins_of.emplace_back(tbu[off[i] + b], b);
-            std::sort(bins_of.begin(), bins_of.end());
-            for (size_t at = 0; at < bins_of.size();) {
-                size_t end = at + 1;
-                while (end < bins_of.size() && bins_of[end].first == bins_of[at].first) ++end;
-                if (end - at > 1) {
-                    if (!any) { any = true; rep_pos.assign(words * 64, kNoGate); }
-                    const uint64_t rep = bins_of[at].second;  // (sorted: the lowest technical bin)
-                    const uint32_t chunk = chunk0[i] + (uint32_t)((rep >> 6) / cwords);
-                    const uint16_t rep_bit = (uint16_t)(rep - (uint64_t)((rep >> 6) / cwords) * cwords * 64);
-                    for (size_t j = at + 1; j < end; ++j) {
-                        const uint64_t part = bins_of[j].second;
-                        nonrep[seg[i] + (part >> 6)] |= 1ULL << (part & 63);
-                        rep_pos[(seg[i] + (part >> 6)) * 64 + (part & 63)] = (uint32_t)((seg[i] + (rep >> 6)) * 64 + (rep & 63));
-                        per_chunk[chunk].push_back(VSplit{(uint32_t)(part >> 6), rep_bit, (uint16_t)(part & 63)});
-                    }
-                }
-                at = end;
-            }
-        }
-        if (any) {
-            std::vector<VSplitRange> ranges(chunks.size());
-            std::vector<VSplit> flat;
-            std::vector<uint32_t> side_pos;             // per entry: its bit in its IBF's side row (word * 64 + bit)
-            std::vector<uint64_t> side_off(n + 1, 0);   // per IBF: first word of its side matrix in d_vside
-            std::vector<uint32_t> side_stride(n, 0);
-            for (uint64_t i = 0; i < n; ++i) {
-                uint32_t word = 0, used = 0, last_word = 0;
-                bool has = false;
-                const uint64_t padded = (desc.ibf[i].bin_words + cwords - 1) / cwords * cwords;
-                for (uint32_t c = chunk0[i]; c < chunk0[i] + padded / cwords; ++c) {
-                    std::stable_sort(per_chunk[c].begin(), per_chunk[c].end(), [](const VSplit& x, const VSplit& y) { return x.rep_bit < y.rep_bit; });
-                    const uint32_t cnt = (uint32_t)per_chunk[c].size();
-                    ranges[c] = VSplitRange{(uint32_t)flat.size(), cnt, {0, 0, 0, 0}, 0, 0, 0};
-                    if (!cnt) continue;
-                    has = true;
-                    // a chunk's parts are consecutive side bits from bit0 of one word on, into as many further words as they need (no
-                    // bound: one user bin split 200 ways gives its representative's chunk 199 parts); a chunk that does not fit after
-                    // `used` starts a fresh word, so only chunks of more than 64 parts span words, and those start at bit 0
-                    if (used && used + cnt > 64) { ++word; used = 0; }
-                    ranges[c].bit0 = used;
-                    ranges[c].side = word;  // (the word for now; the pointer once the matrices have their place)
-                    for (uint32_t e = 0; e < cnt; ++e) {
-                        ranges[c].reps[per_chunk[c][e].rep_bit >> 5] |= 1u << (per_chunk[c][e].rep_bit & 31);
-                        side_pos.push_back(word * 64 + used + e);
-                    }
-                    used += cnt;
-                    last_word = word + (used - 1) / 64;
-                    while (used >= 64) { used -= 64; ++word; }
-                    flat.insert(flat.end(), per_chunk[c].begin(), per_chunk[c].end());
-                }
-                side_stride[i] = has ? last_word + 1 : 0;
-                side_off[i + 1] = side_off[i] + (uint64_t)side_stride[i] * ix.ibf[i].bin_size;
-            }
-            TXQ_HIP(hipMalloc((void**)&ix.d_vside, std::max<uint64_t>(side_off[n], 1) * 8));
-            TXQ_HIP(hipMemset(ix.d_vside, 0, std::max<uint64_t>(side_off[n], 1) * 8));
-            for (uint64_t i = 0; i < n; ++i) {
-                const uint64_t padded = (desc.ibf[i].bin_words + cwords - 1) / cwords * cwords;
-                for (uint32_t c = chunk0[i]; c < chunk0[i] + padded / cwords; ++c) {
-                    ranges[c].side_stride = side_stride[i];
-                    ranges[c].side = (uint64_t)(uintptr_t)(ix.d_vside + side_off[i] + ranges[c].side);
-                }
-            }
-            // a chunk that holds representatives says so in its record (VChunk::packed bit 30): the others never look at their range
-            for (size_t c = 0; c < chunks.size(); ++c)
-                if (ranges[c].count) chunks[c].packed |= 1u << 30;
-            TXQ_HIP(hipMemcpy(ix.d_vchunks, chunks.data(), chunks.size() * sizeof(VChunk), hipMemcpyHostToDevice));
-            TXQ_HIP(hipMalloc((void**)&ix.d_vnonrep, nonrep.size() * 8));
-            TXQ_HIP(hipMalloc((void**)&ix.d_vrep, rep_pos.size() * 4));
-            TXQ_HIP(hipMalloc((void**)&ix.d_vsplit_range, ranges.size() * sizeof(VSplitRange)));
-            TXQ_HIP(hipMalloc((void**)&ix.d_vsplits, flat.size() * sizeof(VSplit)));
-            TXQ_HIP(hipMemcpy(ix.d_vnonrep, nonrep.data(), nonrep.size() * 8, hipMemcpyHostToDevice));
-            TXQ_HIP(hipMemcpy(ix.d_vrep, rep_pos.data(), rep_pos.size() * 4, hipMemcpyHostToDevice));
-            TXQ_HIP(hipMemcpy(ix.d_vsplit_range, ranges.data(), ranges.size() * sizeof(VSplitRange), hipMemcpyHostToDevice));
-            TXQ_HIP(hipMemcpy(ix.d_vsplits, flat.data(), flat.size() * sizeof(VSplit), hipMemcpyHostToDevice));
-            {   // the side matrices: every IBF's entries are consecutive in `flat` (its chunks are)
-                uint32_t* d_pos = nullptr;
-                TXQ_HIP(hipMalloc((void**)&d_pos, std::max<size_t>(side_pos.size(), 1) * 4));
-                TXQ_HIP(hipMemcpy(d_pos, side_pos.data(), side_pos.size() * 4, hipMemcpyHostToDevice));
-                for (uint64_t i = 0; i < n; ++i) {
-                    if (!side_stride[i]) continue;
-                    const uint64_t padded = (desc.ibf[i].bin_words + cwords - 1) / cwords * cwords;
-                    const uint32_t e0 = ranges[chunk0[i]].first;
-                    const VSplitRange& last = ranges[chunk0[i] + padded / cwords - 1];
-                    const uint32_t e1 = last.first + last.count;
-                    const IbfDev& f = ix.ibf[i];
-                    build_side_matrix_kernel<<<(unsigned)((f.bin_size + 255) / 256), 256>>>(f.words, f.stride, f.bin_size, ix.d_vsplits + e0, d_pos + e0, e1 - e0,
-                                                                                       ix.d_vside + side_off[i], side_stride[i]);
-                }
-                hipError_t e = hipDeviceSynchronize();
-                (void)hipFree(d_pos);
-                if (e != hipSuccess) return fail_hip(e, "building the side matrices of split bins");
-            }
-            ix.device_bytes += side_off[n] * 8;
-            ix.device_bytes += nonrep.size() * 8 + rep_pos.size() * 4 + ranges.size() * sizeof(VSplitRange) + flat.size() * sizeof(VSplit);
-            // the ONES of a layout-order session: a split bin is its representative
-            for (size_t w = 0; w < leaf.size(); ++w) leaf[w] &= ~nonrep[w];
-            TXQ_HIP(hipMemcpy(ix.d_vleaf, leaf.data(), leaf.size() * 8, hipMemcpyHostToDevice));
-        }
-    }
-    ix.v_words = (uint32_t)words;
-    ix.v_inner_words = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        bool inner = false;
-        for (uint64_t b = 0; b < desc.ibf[i].bins && !inner; ++b) inner = tbu[off[i] + b] == TXQ_MERGED_BIN;
-        if (inner) ix.v_inner_words += (uint32_t)((desc.ibf[i].bin_words + cwords - 1) / cwords * cwords);
-    }
-    ix.v_chunk_words = (uint32_t)cwords;
-    ix.n_vchunks = (uint32_t)chunks.size();
-    ix.v_depth = ix.depth - 1;
-    ix.tree_hash_max = 1;
-    for (const IbfDev& f : ix.ibf) ix.tree_hash_max = std::max(ix.tree_hash_max, f.hash_funs);
-    ix.device_bytes += chunks.size() * sizeof(VChunk) + paths.size() * sizeof(VPath) + leaf.size() * 8 + vuser.size() * 4;
-    return TXQ_OK;
 }
 
 // Waves per workgroup of hibf_fused_kernel: its waves share nothing (a wave's row and stack are its own piece of the LDS, only
@@ -1054,8 +812,7 @@ static bool layout_order_fused(Index& ix, const uint64_t* d_kmers, size_t n, uin
     const uint32_t row_lds_words = direct ? 0 : w_out;
     const size_t wave_words = (size_t)row_lds_words + stack_lds / 2, wave_bytes = wave_words * 8;
     if (wave_bytes > (64u << 10)) return false;
-    uint32_t h_max = 1;
-    for (const IbfDev& f : ix.ibf) if (f.hash_funs > h_max) h_max = f.hash_funs;
+    uint32_t h_max = ix.tree_hash_max;
     HibfView t{ix.d_ibf, ix.d_next, ix.d_tb_user, ix.d_map_off, ix.d_merged, ix.d_merged, ix.d_merged_off, (const HibfNode*)ix.d_vnodes, (uint32_t)ix.hibf_total_tbs};
     t.nonrep = ix.d_vnonrep;
     t.rep_pos = ix.d_vrep;
@@ -1078,7 +835,7 @@ static bool layout_order_fused(Index& ix, const uint64_t* d_kmers, size_t n, uin
 }
 
 // Rows of plain k-mers as the kernels above write them hold every technical bin's own bit; a split user bin becomes its
-// representative here (txq_internal.hpp VSplit): one thread per row word, the rare word with a set non-representative bit moves it.
+// representative here (txq_records.hpp VSplit): one thread per row word, the rare word with a set non-representative bit moves it.
 __global__ __launch_bounds__(256) void unify_split_rows_kernel(uint64_t* __restrict__ rows, size_t n_words, uint32_t w_out,
                                                                const uint64_t* __restrict__ nonrep, const uint32_t* __restrict__ rep_pos) {
     for (size_t at = (size_t)blockIdx.x * blockDim.x + threadIdx.x; at < n_words; at += (size_t)gridDim.x * blockDim.x) {
@@ -1153,48 +910,113 @@ int hibf_layout_to_user(const Index& ix, const uint64_t* d_rows, size_t n, uint6
     return TXQ_OK;
 }
 
-int hibf_upload(Index& ix, const txq_index_desc& desc, bool cleared_ok) {
-    const uint64_t n = desc.n_ibf;
-    if (n >> 31) return fail(TXQ_ERR_ARG, "too many IBFs");
-    // validate the tree on the host before anything reaches the GPU
-    std::vector<uint64_t> off(n + 1, 0);
-    for (uint64_t i = 0; i < n; ++i) {
-        if (!desc.next_ibf_id[i] || !desc.tb_to_user_bin[i]) return fail(TXQ_ERR_ARG, "HIBF map %llu is null", (unsigned long long)i);
-        off[i + 1] = off[i] + desc.ibf[i].bins;
-    }
-    std::vector<uint64_t> next(off[n]), tbu(off[n]);
-    std::vector<int> level(n, -1);
-    std::deque<uint64_t> q{0};
-    level[0] = 0;
-    std::vector<uint64_t> width(1, 1);
-    while (!q.empty()) {
-        const uint64_t i = q.front();
-        q.pop_front();
-        for (uint64_t b = 0; b < desc.ibf[i].bins; ++b) {
-            const uint64_t ub = desc.tb_to_user_bin[i][b];
-            uint64_t nx = desc.next_ibf_id[i][b];
-            if (ub == TXQ_MERGED_BIN) {
-                if (nx >= n || nx == i) return fail(TXQ_ERR_ARG, "IBF %llu bin %llu: bad child %llu", (unsigned long long)i, (unsigned long long)b, (unsigned long long)nx);
-                if (level[nx] >= 0) return fail(TXQ_ERR_ARG, "IBF %llu has two parents: not a tree", (unsigned long long)nx);
-                level[nx] = level[i] + 1;
-                if ((size_t)level[nx] >= width.size()) width.push_back(0);
-                ++width[level[nx]];
-                q.push_back(nx);
-            } else {  // (a sub-tree shard's cleared root bins carry kClearedBin)
-                if (ub >= desc.user_bins && !(ub == kClearedBin && cleared_ok && i == 0)) return fail(TXQ_ERR_ARG, "IBF %llu bin %llu: user bin %llu out of range", (unsigned long long)i, (unsigned long long)b, (unsigned long long)ub);
-                nx = 0;
-            }
-            next[off[i] + b] = nx;
-            tbu[off[i] + b] = ub;
-        }
-    }
-    for (uint64_t i = 0; i < n; ++i)
-        if (level[i] < 0) return fail(TXQ_ERR_ARG, "IBF %llu is unreachable from the root", (unsigned long long)i);
-    ix.depth = (uint32_t)width.size();
-    ix.hibf_total_tbs = off[n];
-    ix.max_level_width = 1;
-    for (uint64_t w : width) if (w > ix.max_level_width) ix.max_level_width = w;
+// ---- upload: the plans of txq_hibf_plan.hpp go to the device ----------------------------------------------------------------
+// Every array of an upload goes through device_array: allocated (at least one element), copied, recorded in Index::uploaded —
+// which Index::release frees — and, where `counted`, added to device_bytes.
+// KNOWN GAP: d_merged, d_descend, d_merged_off and d_vgroups are not counted (they never were).  Counting them changes what
+// txq_index_get_info reports, so it is left to a change of its own.
+enum Counted : bool { kUncounted = false, kCounted = true };
 
+static int device_alloc(Index& ix, void** out, size_t bytes, Counted counted) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+    if (e != hipSuccess) return fail_hip(e, "hipMalloc(index array)");
+    ix.uploaded.push_back(p);
+    if (counted) ix.device_bytes += bytes;
+    *out = p;
+    return TXQ_OK;
+}
+// the first `count` elements of v (all of them by default)
+template <class T>
+static int device_array(Index& ix, T** dst, const std::vector<T>& v, Counted counted, size_t count = SIZE_MAX) {
+    count = std::min(count, v.size());
+    if (int rc = device_alloc(ix, (void**)dst, std::max<size_t>(count, 1) * sizeof(T), kUncounted)) return rc;
+    if (counted) ix.device_bytes += count * sizeof(T);
+    hipError_t e = count ? hipMemcpy(*dst, v.data(), count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+    return e == hipSuccess ? TXQ_OK : fail_hip(e, "hipMemcpy(index array)");
+}
+
+static int upload_regular(Index& ix, const RegularPlan& r) {
+    if (int rc = device_array(ix, &ix.d_children, r.children, kCounted)) return rc;
+    ix.n_children = (uint32_t)r.children.size();
+    ix.children_uniform = r.children_uniform;
+    ix.child_row_words = r.child_row_words;
+    ix.children_bytes = r.children_bytes;
+    ix.root_node = r.root;
+    if (!r.interleave || !knobs().hibf_interleave) return TXQ_OK;  // (TXQ_HIBF_INTERLEAVE=0: never)
+    IbfDev f = r.interleaved;
+    const size_t nbytes = ibf_bytes(f);
+    if (int rc = device_alloc(ix, (void**)&f.words, nbytes, kCounted)) return rc;
+    ix.interleaved = f;
+    TXQ_HIP(hipMemset(f.words, 0, nbytes));
+    const uint64_t total = f.bin_size * ix.shard_words;
+    const unsigned grid = (unsigned)std::min<uint64_t>((total + 255) / 256, 256 * 64);
+    interleave_children_kernel<<<grid ? grid : 1, 256, 0, nullptr>>>(ix.d_children, ix.n_children, r.child_row_words, f.bin_size, f.words, f.stride);
+    TXQ_HIP(hipGetLastError());
+    TXQ_HIP(hipDeviceSynchronize());
+    return TXQ_OK;
+}
+
+// The side matrices of the IBFs with split user bins, built on the device from the IBFs' own columns (build_side_matrix_kernel);
+// the chunks' ranges get their addresses in it.
+static int upload_split_bins(Index& ix, const LayoutPlan& p) {
+    SplitPlan s = p.split;  // (a copy: the ranges' offsets become addresses)
+    const uint64_t n = ix.ibf.size(), side_words = s.side_off[n];
+    if (int rc = device_alloc(ix, (void**)&ix.d_vside, std::max<uint64_t>(side_words, 1) * 8, kUncounted)) return rc;
+    ix.device_bytes += side_words * 8;
+    TXQ_HIP(hipMemset(ix.d_vside, 0, std::max<uint64_t>(side_words, 1) * 8));
+    for (uint64_t i = 0; i < n; ++i)
+        for (uint32_t c = p.chunk0[i]; c < p.chunk0[i] + p.padded[i] / p.cwords; ++c) s.ranges[c].side = (uint64_t)(uintptr_t)(ix.d_vside + s.ranges[c].side);
+    if (int rc = device_array(ix, &ix.d_vnonrep, s.nonrep, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_vrep, s.rep_pos, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_vsplit_range, s.ranges, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_vsplits, s.flat, kCounted)) return rc;
+    struct Temporary {  // the entries' side bits: only the kernel below reads them
+        uint32_t* p = nullptr;
+        ~Temporary() { if (p) (void)hipFree(p); }
+    } pos;
+    TXQ_HIP(hipMalloc((void**)&pos.p, std::max<size_t>(s.side_pos.size(), 1) * 4));
+    TXQ_HIP(hipMemcpy(pos.p, s.side_pos.data(), s.side_pos.size() * 4, hipMemcpyHostToDevice));
+    for (uint64_t i = 0; i < n; ++i) {  // every IBF's entries are consecutive in `flat` (its chunks are)
+        if (!s.side_stride[i]) continue;
+        const uint32_t e0 = s.ranges[p.chunk0[i]].first;
+        const VSplitRange& last = s.ranges[p.chunk0[i] + p.padded[i] / p.cwords - 1];
+        const uint32_t e1 = last.first + last.count;
+        const IbfDev& f = ix.ibf[i];
+        build_side_matrix_kernel<<<(unsigned)((f.bin_size + 255) / 256), 256>>>(f.words, f.stride, f.bin_size, ix.d_vsplits + e0, pos.p + e0, e1 - e0,
+                                                                           ix.d_vside + s.side_off[i], s.side_stride[i]);
+    }
+    hipError_t e = hipDeviceSynchronize();
+    return e == hipSuccess ? TXQ_OK : fail_hip(e, "building the side matrices of split bins");
+}
+
+static int upload_layout_order(Index& ix, const LayoutPlan& p) {
+    if (!p.vnodes.empty())
+        if (int rc = device_array(ix, &ix.d_vnodes, p.vnodes, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_vchunks, p.chunks, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_vpaths, p.paths, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_vleaf, p.leaf, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_vuser, p.vuser, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_vgroups, p.groups, kUncounted)) return rc;
+    if (p.split.any)
+        if (int rc = upload_split_bins(ix, p)) return rc;
+    ix.vlevels = p.levels;
+    ix.v_words = (uint32_t)p.words;
+    ix.v_inner_words = p.v_inner_words;
+    ix.v_chunk_words = (uint32_t)p.cwords;
+    ix.n_vchunks = (uint32_t)p.chunks.size();
+    ix.v_depth = ix.depth - 1;
+    return TXQ_OK;
+}
+
+int hibf_upload(Index& ix, const txq_index_desc& desc, bool cleared_ok) {
+    HibfTree tree;  // validated on the host before anything reaches the GPU
+    if (PlanError e = read_tree(desc, cleared_ok, &tree)) return fail(e.code, "%s", e.text.c_str());
+    const uint64_t n = tree.n;
+    ix.depth = tree.depth;
+    ix.hibf_total_tbs = tree.total_tbs();
+    ix.max_level_width = tree.max_level_width;
+    ix.tree_hash_max = tree.hash_max;
     ix.ibf.reserve(n);
     ix.max_stride = 1;
     for (uint64_t i = 0; i < n; ++i) {
@@ -1202,170 +1024,24 @@ int hibf_upload(Index& ix, const txq_index_desc& desc, bool cleared_ok) {
         uint64_t bytes;
         // every IBF of the tree is kept whole; only the user-bin mask columns are sharded
         if (int rc = alloc_ibf(desc.ibf[i], 0, desc.ibf[i].bin_words, &f, &bytes)) return rc;
-        {   // identity-mapped leaf?
-            const uint64_t base = tbu[off[i]];
-            bool ident = base != TXQ_MERGED_BIN && base % 64 == 0 && (base >> 6) + desc.ibf[i].bin_words < kNoIdent;
-            for (uint64_t b = 0; ident && b < desc.ibf[i].bins; ++b) ident = tbu[off[i] + b] == base + b;
-            if (ident) f.ident_word = (uint32_t)(base >> 6);
-        }
         ix.ibf.push_back(f);
         ix.device_bytes += bytes;
         if (f.stride > ix.max_stride) ix.max_stride = f.stride;
     }
-    TXQ_HIP(hipMalloc((void**)&ix.d_ibf, n * sizeof(IbfDev)));
-    TXQ_HIP(hipMalloc((void**)&ix.d_next, (off[n] ? off[n] : 1) * 8));
-    TXQ_HIP(hipMalloc((void**)&ix.d_tb_user, (off[n] ? off[n] : 1) * 8));
-    TXQ_HIP(hipMalloc((void**)&ix.d_map_off, n * 8));
-    // merged-bin bitmasks, one 64-bit word per row word of every IBF
-    std::vector<uint64_t> moff(n + 1, 0);
-    // (padded to 4 words per IBF: the fused kernel reads them as two 16-byte loads)
-    for (uint64_t i = 0; i < n; ++i) moff[i + 1] = moff[i] + ((desc.ibf[i].bin_words + 3) & ~(uint64_t)3);
-    std::vector<uint64_t> merged(moff[n], 0);
-    for (uint64_t i = 0; i < n; ++i)
-        for (uint64_t b = 0; b < desc.ibf[i].bins; ++b)
-            if (desc.tb_to_user_bin[i][b] == TXQ_MERGED_BIN) merged[moff[i] + (b >> 6)] |= 1ULL << (b & 63);
-    // Sub-tree pruning for column shards: a merged bin is only descended into when its sub-tree
-    // holds a user bin whose mask word belongs to this shard (span[i] = mask-word range under IBF i).
-    std::vector<std::pair<uint64_t, uint64_t>> span(n, {UINT64_MAX, 0});
-    {
-        std::vector<uint64_t> order;  // parents before children (BFS order from the tree walk above)
-        order.reserve(n);
-        std::deque<uint64_t> bfs{0};
-        while (!bfs.empty()) {
-            const uint64_t i = bfs.front();
-            bfs.pop_front();
-            order.push_back(i);
-            for (uint64_t b = 0; b < desc.ibf[i].bins; ++b)
-                if (tbu[off[i] + b] == TXQ_MERGED_BIN) bfs.push_back(next[off[i] + b]);
-        }
-        for (size_t at = order.size(); at-- > 0;) {
-            const uint64_t i = order[at];
-            for (uint64_t b = 0; b < desc.ibf[i].bins; ++b) {
-                const uint64_t ub = tbu[off[i] + b];
-                if (ub == kClearedBin) continue;
-                std::pair<uint64_t, uint64_t> r = ub == TXQ_MERGED_BIN ? span[next[off[i] + b]] : std::make_pair(ub >> 6, ub >> 6);
-                if (r.first < span[i].first) span[i].first = r.first;
-                if (r.first != UINT64_MAX && r.second > span[i].second) span[i].second = r.second;
-            }
-        }
-    }
-    std::vector<uint64_t> descend(moff[n], 0);
-    const uint64_t shard_lo = ix.shard_word0, shard_hi = ix.shard_word0 + ix.shard_words;  // [lo, hi)
-    for (uint64_t i = 0; i < n; ++i)
-        for (uint64_t b = 0; b < desc.ibf[i].bins; ++b) {
-            if (tbu[off[i] + b] != TXQ_MERGED_BIN) continue;
-            const auto& r = span[next[off[i] + b]];
-            if (r.first != UINT64_MAX && r.first < shard_hi && r.second >= shard_lo) descend[moff[i] + (b >> 6)] |= 1ULL << (b & 63);
-        }
-    TXQ_HIP(hipMalloc((void**)&ix.d_descend, (moff[n] ? moff[n] : 1) * 8));
-    TXQ_HIP(hipMemcpy(ix.d_descend, descend.data(), moff[n] * 8, hipMemcpyHostToDevice));
-    TXQ_HIP(hipMalloc((void**)&ix.d_merged, (moff[n] ? moff[n] : 1) * 8));
-    TXQ_HIP(hipMalloc((void**)&ix.d_merged_off, n * 8));
-    TXQ_HIP(hipMemcpy(ix.d_merged, merged.data(), moff[n] * 8, hipMemcpyHostToDevice));
-    TXQ_HIP(hipMemcpy(ix.d_merged_off, moff.data(), n * 8, hipMemcpyHostToDevice));
-    TXQ_HIP(hipMemcpy(ix.d_ibf, ix.ibf.data(), n * sizeof(IbfDev), hipMemcpyHostToDevice));
-    TXQ_HIP(hipMemcpy(ix.d_next, next.data(), off[n] * 8, hipMemcpyHostToDevice));
-    TXQ_HIP(hipMemcpy(ix.d_tb_user, tbu.data(), off[n] * 8, hipMemcpyHostToDevice));
-    TXQ_HIP(hipMemcpy(ix.d_map_off, off.data(), n * 8, hipMemcpyHostToDevice));
-    ix.device_bytes += n * sizeof(IbfDev) + off[n] * 16 + n * 8;
-    // node records by technical bin for the fused kernel (skipped for trees too large for it)
-    bool compact = off[n] < kRootEntry && moff[n] < 0xFFFFFFFFull && off[n] <= ((size_t)256 << 20) / sizeof(HibfNode);
-    for (const IbfDev& f : ix.ibf) compact = compact && !(f.bin_size >> 32) && f.stride < (1u << 20) && f.hash_shift < 64 && f.hash_funs < 8;
-    std::vector<HibfNode> nodes;
-    if (compact) {
-        nodes.resize(off[n] + 1);
-        std::memset(nodes.data(), 0, nodes.size() * sizeof(HibfNode));
-        auto node_of = [&](uint64_t i) {
-            const IbfDev& f = ix.ibf[i];
-            bool has_merged = false;
-            for (uint64_t w = moff[i]; w < moff[i + 1]; ++w) has_merged = has_merged || merged[w] != 0;
-            HibfNode nd{};
-            nd.words = (uint64_t)(uintptr_t)f.words;
-            nd.bin_size = (uint32_t)f.bin_size;
-            nd.packed = f.stride | (f.hash_shift << 20) | (f.hash_funs << 26) | ((uint32_t)has_merged << 29);
-            nd.off = (uint32_t)off[i];
-            nd.moff = (uint32_t)moff[i];
-            nd.ident_word = f.ident_word;
-            nd.bins = f.bins;
-            return nd;
-        };
-        for (uint64_t i = 0; i < n; ++i)
-            for (uint64_t b = 0; b < desc.ibf[i].bins; ++b)
-                if (tbu[off[i] + b] == TXQ_MERGED_BIN) nodes[off[i] + b] = node_of(next[off[i] + b]);
-        nodes[off[n]] = node_of(0);
-        TXQ_HIP(hipMalloc((void**)&ix.d_nodes, nodes.size() * sizeof(HibfNode)));
-        TXQ_HIP(hipMemcpy(ix.d_nodes, nodes.data(), nodes.size() * sizeof(HibfNode), hipMemcpyHostToDevice));
-        ix.device_bytes += nodes.size() * sizeof(HibfNode);
-    }
-
-    // Regular two-level tree?  (root: only merged bins; every child: a leaf whose technical bins are an aligned run of
-    // user bins, all children of one power-of-two row width, tiling the mask columns in order; this shard's
-    // column range starts and ends on child boundaries)  -> ChildRec table for the child-stationary descent.
-    if (compact && ix.depth == 2 && n >= 2 && desc.ibf[0].bins < (1u << 20)) {
-        const uint32_t wpr = (uint32_t)desc.ibf[1].bin_words;
-        bool regular = wpr >= 1 && (wpr & (wpr - 1)) == 0 && wpr <= 128;
-        std::vector<uint64_t> by_column(n - 1, UINT64_MAX), root_tb(n, 0);
-        for (uint64_t b = 0; regular && b < desc.ibf[0].bins; ++b) {
-            if (tbu[off[0] + b] != TXQ_MERGED_BIN) { regular = false; break; }
-            root_tb[next[off[0] + b]] = b;
-        }
-        for (uint64_t i = 1; regular && i < n; ++i) {
-            const IbfDev& f = ix.ibf[i];
-            regular = f.ident_word != kNoIdent && desc.ibf[i].bin_words == wpr && f.stride == wpr && f.ident_word % wpr == 0 &&
-                      f.ident_word / wpr < n - 1 && by_column[f.ident_word / wpr] == UINT64_MAX && f.hash_funs <= 5;
-            if (regular) by_column[f.ident_word / wpr] = i;
-        }
-        regular = regular && ix.mask_words == (uint64_t)wpr * (n - 1) && ix.shard_word0 % wpr == 0 && ix.shard_words % wpr == 0 && ix.shard_words > 0;
-        if (regular) {
-            std::vector<ChildRec> recs;
-            uint64_t bytes = 0;
-            for (uint64_t c = ix.shard_word0 / wpr; c < (ix.shard_word0 + ix.shard_words) / wpr; ++c) {
-                const IbfDev& f = ix.ibf[by_column[c]];
-                recs.push_back(ChildRec{(uint64_t)(uintptr_t)f.words, (uint32_t)f.bin_size, f.hash_shift | (f.hash_funs << 8) | ((uint32_t)root_tb[by_column[c]] << 12)});
-                bytes += f.bin_size * (uint64_t)f.stride * 8;
-            }
-            TXQ_HIP(hipMalloc((void**)&ix.d_children, recs.size() * sizeof(ChildRec)));
-            TXQ_HIP(hipMemcpy(ix.d_children, recs.data(), recs.size() * sizeof(ChildRec), hipMemcpyHostToDevice));
-            ix.n_children = (uint32_t)recs.size();
-            ix.children_uniform = true;
-            for (const ChildRec& c : recs) ix.children_uniform = ix.children_uniform && c.bin_size == recs[0].bin_size && (c.packed & 0xFFFu) == (recs[0].packed & 0xFFFu);
-            ix.child_row_words = wpr;
-            ix.children_bytes = bytes;
-            const IbfDev& root = ix.ibf[0];
-            ix.root_node = HibfNode{};
-            ix.root_node.words = (uint64_t)(uintptr_t)root.words;
-            ix.root_node.bin_size = (uint32_t)root.bin_size;
-            ix.root_node.packed = root.stride | (root.hash_shift << 20) | (root.hash_funs << 26);
-            ix.root_node.bins = root.bins;
-            ix.tree_hash_max = 1;
-            for (const IbfDev& f : ix.ibf) ix.tree_hash_max = std::max(ix.tree_hash_max, f.hash_funs);
-            if (ix.children_uniform && root.bins <= 64 && ix.shard_words <= 32 && knobs().hibf_interleave) {  // (TXQ_HIBF_INTERLEAVE=0: never)
-                const IbfDev& c0 = ix.ibf[by_column[ix.shard_word0 / wpr]];
-                IbfDev f{};
-                f.bin_size = c0.bin_size;
-                f.hash_shift = c0.hash_shift;
-                f.hash_funs = c0.hash_funs;
-                f.shard_words = (uint32_t)ix.shard_words;
-                f.stride = f.shard_words <= 1 ? 1u : ((f.shard_words + 1u) & ~1u);
-                f.bins = (uint32_t)ix.shard_words * 64u;
-                f.ident_word = kNoIdent;
-                const size_t nbytes = (size_t)f.bin_size * f.stride * 8;
-                TXQ_HIP(hipMalloc((void**)&f.words, nbytes));
-                ix.interleaved = f;  // released with the index from here on
-                TXQ_HIP(hipMemset(f.words, 0, nbytes));
-                const uint64_t total = f.bin_size * ix.shard_words;
-                const unsigned grid = (unsigned)std::min<uint64_t>((total + 255) / 256, 256 * 64);
-                interleave_children_kernel<<<grid ? grid : 1, 256, 0, nullptr>>>((const ChildRec*)ix.d_children, ix.n_children, wpr, f.bin_size, f.words, f.stride);
-                TXQ_HIP(hipGetLastError());
-                TXQ_HIP(hipDeviceSynchronize());
-                ix.device_bytes += nbytes;
-            }
-            ix.device_bytes += recs.size() * sizeof(ChildRec);
-        }
-    }
-    // any other tree: sessions work in layout order
-    if (!ix.d_children)
-        if (int rc = build_layout_order(ix, desc, level, next, tbu, off, compact ? &nodes : nullptr)) return rc;
+    const MapsPlan maps = plan_maps(tree, desc, ix.ibf, ix.shard_word0, ix.shard_words);
+    if (int rc = device_array(ix, &ix.d_ibf, ix.ibf, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_next, tree.next, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_tb_user, tree.tbu, kCounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_map_off, tree.off, kCounted, n)) return rc;
+    if (int rc = device_array(ix, &ix.d_merged, maps.merged, kUncounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_descend, maps.descend, kUncounted)) return rc;
+    if (int rc = device_array(ix, &ix.d_merged_off, maps.moff, kUncounted, n)) return rc;
+    if (maps.compact)
+        if (int rc = device_array(ix, &ix.d_nodes, maps.nodes, kCounted)) return rc;
+    // a regular two-level tree: the child-stationary descent; any other tree: sessions work in layout order
+    if (const auto regular = plan_regular(tree, desc, ix.ibf, maps.compact, ix.shard_word0, ix.shard_words)) return upload_regular(ix, *regular);
+    if (const auto layout = plan_layout_order(tree, desc, ix.ibf, ix.mask_words, ix.shard_word0, ix.shard_words, maps.compact ? &maps.nodes : nullptr))
+        return upload_layout_order(ix, *layout);
     return TXQ_OK;
 }
 
@@ -1387,8 +1063,7 @@ static bool hibf_probe_fused(Index& ix, const Knobs& kn, const uint64_t* d_kmers
     const size_t wave_bytes = wave_words * 8;
     const size_t lds_budget = 64u << 10;
     if (!w_out || wave_bytes > lds_budget || !ix.d_nodes || kn.hibf_levels) return false;
-    uint32_t h_max = 1;
-    for (const IbfDev& f : ix.ibf) if (f.hash_funs > h_max) h_max = f.hash_funs;
+    uint32_t h_max = ix.tree_hash_max;
     const HibfView t{ix.d_ibf, ix.d_next, ix.d_tb_user, ix.d_map_off, ix.d_merged, ix.d_descend, ix.d_merged_off, (const HibfNode*)ix.d_nodes, (uint32_t)ix.hibf_total_tbs};
     *rc = TXQ_OK;
     // regular two-level trees: the children stay put in L2, the k-mers stream past (TXQ_HIBF_STATIONARY=0: A/B against the kernels below)
@@ -1412,11 +1087,6 @@ static bool hibf_probe_fused(Index& ix, const Knobs& kn, const uint64_t* d_kmers
                 const IbfDev& root = ix.ibf[0];
                 const uint32_t cm_words = root.stride;
                 if (int e = ensure((void**)&ix.scratch_cm, &ix.cap_cm, n * (size_t)cm_words * 8)) { *rc = e; return true; }
-                HibfNode rn{};
-                rn.words = (uint64_t)(uintptr_t)root.words;
-                rn.bin_size = (uint32_t)root.bin_size;
-                rn.packed = root.stride | (root.hash_shift << 20) | (root.hash_funs << 26);
-                rn.bins = root.bins;
                 size_t rb = (n + 255) / 256;
                 if (rb > 256 * 32) rb = 256 * 32;
                 const bool uniform = ix.children_uniform && !kn.hibf_lane_hash;  // (A/B: per-lane hashing on a uniform tree)
@@ -1427,7 +1097,7 @@ static bool hibf_probe_fused(Index& ix, const Knobs& kn, const uint64_t* d_kmers
                     d_child_rows = ix.scratch_crows;
                     h_max = c0.hash_funs;
                 }
-                hibf_root_kernel<<<(unsigned)rb, 256, 0, s>>>(rn, d_kmers, n, ix.scratch_cm, cm_words, d_child_rows, (uint32_t)c0.bin_size, c0.hash_shift, c0.hash_funs);
+                hibf_root_kernel<<<(unsigned)rb, 256, 0, s>>>(ix.root_node, d_kmers, n, ix.scratch_cm, cm_words, d_child_rows, (uint32_t)c0.bin_size, c0.hash_shift, c0.hash_funs);
                 if (d_alive) {
                     hipError_t e = hipMemsetAsync(d_alive, 0, ((n + 63) / 64) * 8, s);
                     if (e != hipSuccess) { *rc = fail_hip(e, "hipMemsetAsync(alive)"); return true; }

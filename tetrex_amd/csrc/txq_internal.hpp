@@ -1,6 +1,7 @@
 // Internal (non-ABI) declarations shared by the translation units of libtxq.so.
 #pragma once
 #include "txq_kernels.hpp"
+#include "txq_records.hpp"
 #include "../../include/txq.h"
 #include <cstdlib>
 #include <map>
@@ -76,78 +77,7 @@ struct Knobs {
 Knobs knobs();      // a copy of the snapshot taken at the last entry point (published under a lock: entry points run on several threads)
 void read_knobs();  // take it (txq_api.hip)
 
-// Everything about one IBF of an HIBF tree in one 32-byte record (txq_hibf.hip: nodes[e] = the child behind merged
-// technical bin e; the dense steps on a regular tree take the root as a kernel argument).
-struct HibfNode {  // 32 bytes = two 16-byte loads per lane
-    uint64_t words;       // device pointer to the IBF's rows
-    uint32_t bin_size;    // rows (< 2^32: the fused kernel is not used for larger IBFs)
-    uint32_t packed;      // stride (bits 0-19) | hash_shift (20-25) | hash_funs (26-28) | has merged bins (29)
-    uint32_t off;         // first entry of the IBF's technical bins in the flattened maps
-    uint32_t moff;        // first word of the IBF in `merged` / `descend`
-    uint32_t ident_word;  // see IbfDev::ident_word
-    uint32_t bins;        // technical bins
-    __host__ __device__ uint32_t stride() const { return packed & 0xFFFFFu; }
-    __host__ __device__ uint32_t hash_shift() const { return (packed >> 20) & 63u; }
-    __host__ __device__ uint32_t hash_funs() const { return (packed >> 26) & 7u; }
-    __host__ __device__ bool has_merged() const { return (packed >> 29) & 1u; }
-    __host__ __device__ uint32_t words_per_row() const { return (bins + 63u) >> 6; }
-};
-static_assert(sizeof(HibfNode) == 32, "two 16-byte pieces per node");
-
-// Regular two-level trees: one record per child in mask-column order (child-stationary descent in txq_hibf.hip, dense
-// steps on the tree in txq_exec.hip).
-struct ChildRec {   // 16 bytes, one per child in mask-column order
-    uint64_t words;     // device pointer to the child's rows (stride = row words, a power of two >= 2)
-    uint32_t bin_size;  // rows
-    uint32_t packed;    // hash_shift (bits 0-7) | hash_funs (8-11) | root technical bin (12-31)
-};
-static_assert(sizeof(ChildRec) == 16, "one 16-byte load per lane");
-
-// General HIBFs in LAYOUT ORDER (sessions on trees that are not regular: three and more levels, user bins next to merged
-// bins, split bins, user bins in any order — what seqan::hibf's layout produces, reference include/index_hibf.h:114-129).
-// A session on such a tree does not work on masks in user-bin order but on rows in the order of the tree's own
-// technical bins: the row of every IBF, one after the other (levels ascending, every IBF padded to an even number of
-// words), W_v words in all.  In that order every IBF owns an aligned segment of the row, so a k-mer's mask is written
-// segment by segment with coalesced stores and no atomics (child-stationary, level by level), and a dense step gathers a
-// lane's 16 bytes from ONE IBF.  Every operation of the collector is bin-wise, so the order of the bins does not matter
-// until the final masks are handed out: those are converted to user-bin order (split bins ORed) once per query.
-// Merged bins keep their bits in the rows (the next level reads them as its gates); they never reach a result because
-// the ONES slot of a layout-order session only has the bits of technical bins that ARE user bins.
-struct VChunk {          // one chunk of the layout-order row: two row words (16 bytes) of one IBF, or one (Index::v_chunk_words)
-    uint64_t words;      // the IBF's rows
-    uint32_t bin_size;   // rows (< 2^32)
-    uint32_t packed;     // stride (bits 0-19) | hash_shift (20-25) | hash_funs (26-28) | single-word rows (29) | holds representatives of split user bins (30)
-    uint32_t col;        // word column of the chunk within the IBF's row
-    uint32_t gate_word;  // layout-order word that holds the parent's merged bin leading here (kNoGate: the root)
-    uint32_t gate_bit;
-    uint32_t ibf;        // IBF id (its VPath)
-};
-static_assert(sizeof(VChunk) == 32, "two 16-byte loads per lane");
-static constexpr uint32_t kNoGate = 0xFFFFFFFFu;
-static constexpr uint32_t kMaxVDepth = 3;  // ancestors a fused dense step follows (trees of up to 4 levels)
-struct VPath {           // the ancestors of an IBF, root first: whose merged bin (row word, bit) leads towards it
-    uint32_t depth, pad;
-    struct { uint64_t words; uint32_t bin_size, packed, word, bit; } anc[kMaxVDepth];
-};
-// Split user bins in layout order.  A user bin that the layout spreads over several technical bins of one IBF holds a k-mer when
-// ANY of its parts does, and masks are combined per USER bin (reference include/index_hibf.h:132-147 ORs the parts before the
-// collector ANDs anything) — so in a layout-order row a split bin is ONE bit, its first part's (the representative), which
-// stands for the OR of the parts; the other parts' bits are always zero.  Rows of plain k-mers are put into that form as they
-// are written (hibf_fused_kernel<G, LAYOUT>) or right after (unify_split_rows_kernel behind the level kernels).  A fused step
-// (PathRows) works on one 16-byte chunk of an IBF's row and does not see the other parts: for them every IBF with split bins has
-// a SIDE matrix — the columns of its non-representative parts once more, packed so that the parts belonging to one chunk's
-// representatives are consecutive bits of one 64-bit word per row.  ANDing the k-mer's h side rows gives those parts' hits
-// exactly (they are the IBF's own columns), and a hit sets its representative: VSplit entry e of the chunk (sorted by
-// representative) is side bit `bit0 + e`.
-struct VSplit { uint32_t part_word; uint16_t rep_bit, part_bit; };  // word column and bit of the part in the IBF's row; its representative's bit in the chunk
-struct VSplitRange {
-    uint32_t first, count;   // the chunk's entries in Index::d_vsplits (any number: every part of a split bin whose representative is in the chunk)
-    uint32_t reps[4];        // the chunk's bits that are representatives (bit b of the 128: reps[b >> 5] >> (b & 31))
-    uint64_t side;           // device pointer: row 0 of the chunk's (first) word in the IBF's side matrix — entry e is bit bit0 + e from there
-    uint32_t side_stride;    // words per side row
-    uint32_t bit0;           // the chunk's first bit in that word
-};
-struct VLevel { uint32_t first_chunk, n_chunks; std::vector<uint32_t> group_first; };  // groups: chunk ranges whose IBFs share an L2's worth of rows
+// (the records an index keeps in HBM — HibfNode, ChildRec, VChunk, VPath, VSplit, VSplitRange — and VLevel: txq_records.hpp)
 
 // One HIBF work item: k-mer `kmer` (index into the batch) must be looked up in IBF `ibf`.
 struct WorkItem { uint32_t kmer; uint32_t ibf; };
@@ -157,6 +87,9 @@ struct Index {
     bool is_hibf = false;
     uint64_t user_bins = 0, mask_words = 0, shard_word0 = 0, shard_words = 0, device_bytes = 0;
     std::vector<IbfDev> ibf;  // host copies of the device descriptors ([0] = flat IBF / HIBF root)
+    // Every array below that an HIBF upload sends to the device (txq_hibf.hip device_array) is owned through this list: a new one
+    // needs its field here and its call there, release() frees the list.
+    std::vector<void*> uploaded;
 
     // HIBF tree in HBM
     IbfDev* d_ibf = nullptr;         // [n_ibf]
@@ -164,14 +97,14 @@ struct Index {
     uint64_t* d_tb_user = nullptr;   // flattened tb_to_user_bin (TXQ_MERGED_BIN for merged)
     uint64_t* d_map_off = nullptr;   // [n_ibf] offset of IBF i's maps in the flattened arrays
     uint64_t* d_merged = nullptr;    // merged-bin bitmask words of every IBF, flattened
-    void* d_nodes = nullptr;         // HibfNode[total technical bins + 1] for the fused descent (txq_hibf.hip)
+    HibfNode* d_nodes = nullptr;     // [total technical bins + 1] for the fused descent (txq_hibf.hip)
     uint64_t* d_descend = nullptr;   // same layout: merged bins worth descending into for this shard
     uint64_t* d_merged_off = nullptr;
     // Regular two-level trees (root of merged bins over leaf IBFs that each map an aligned run of user bins, all of
     // one row width): the child-stationary descent of txq_hibf.hip (rows of >= 2 words) and the fused dense steps of
     // txq_exec.hip.  d_children = ChildRec[n_children] in mask-column
     // order for THIS shard's columns; empty when the tree does not have that shape.
-    void* d_children = nullptr;
+    ChildRec* d_children = nullptr;
     uint32_t n_children = 0;         // children whose columns this shard owns
     uint32_t child_row_words = 0;    // mask words per child (a power of two)
     // Small regular trees with uniform children (root of <= 64 merged bins, mask of <= 32 words): the children's matrices
@@ -184,7 +117,7 @@ struct Index {
                root_node.bins <= 64 && kn.hibf_interleave_probe;
     }
     HibfNode root_node{};            // host copy of the root's record
-    uint32_t tree_hash_max = 0;      // most hash functions of any IBF of the regular tree
+    uint32_t tree_hash_max = 0;      // most hash functions of any IBF of the tree (every HIBF: set at upload)
     bool children_uniform = false;   // same rows / hash shift / hash count in every child: scalar hashing
     uint64_t children_bytes = 0;     // their matrices
     uint32_t* scratch_crows = nullptr; size_t cap_crows = 0;  // uniform children: per k-mer its row indexes in a child
@@ -200,7 +133,7 @@ struct Index {
     VSplitRange* d_vsplit_range = nullptr;  // [n_vchunks]
     VSplit* d_vsplits = nullptr;
     uint64_t* d_vside = nullptr;     // the side matrices of all IBFs with split bins
-    void* d_vnodes = nullptr;        // HibfNode records (as d_nodes) whose ident_word is the IBF's first word in the layout-order row
+    HibfNode* d_vnodes = nullptr;    // records as d_nodes whose ident_word is the IBF's first word in the layout-order row
     uint32_t v_inner_words = 0;  // of a row: the words of IBFs with merged bins (what the next level reads as gates)
     uint32_t v_words = 0, n_vchunks = 0, v_depth = 0, v_chunk_words = 2;  // (chunks of 16 bytes, or of 8 for trees of narrow IBFs)
     std::vector<VLevel> vlevels;
@@ -410,9 +343,6 @@ hipError_t launch_probe_interleaved(const IbfDev& interleaved, const HibfNode& r
 hipError_t launch_emplace(const IbfDev& f, const uint64_t* values, const uint32_t* bins_of, size_t n, hipStream_t s);
 
 // txq_hibf.hip
-// A technical bin of a sub-tree shard's root whose column was cleared because another shard owns it (txq_index_upload_subtrees):
-// internal only, accepted by hibf_upload with `cleared_ok`; it is no user bin and no merged bin, and it never fires.
-static constexpr uint64_t kClearedBin = 0xFFFFFFFFFFFFFFFEull;
 int hibf_upload(Index& ix, const txq_index_desc& desc, bool cleared_ok = false);
 int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, uint64_t* d_masks, uint64_t* d_alive, hipStream_t s);
 // layout-order rows of n k-mers: d_rows[n][v_words]

@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "txq_records.hpp"
 
 namespace txq {
 
@@ -19,21 +20,7 @@ __device__ __constant__ const uint64_t kSeeds[5] = {
     16499269484942379435ULL, 4893150838803335377ULL};
 static constexpr uint64_t kGolden = 11400714819323198485ULL;
 
-struct IbfDev {
-    uint64_t* words;      // device pointer, [bin_size][stride]
-    uint64_t bin_size;    // rows
-    uint32_t hash_shift;  // countl_zero(bin_size)
-    uint32_t hash_funs;   // 1..5
-    uint32_t stride;      // words per row in HBM
-    uint32_t shard_words; // mask words this shard owns (<= stride)
-    uint32_t word0;       // first full-mask word owned by this shard
-    uint32_t bins;        // technical bins in use (unsharded)
-    // HIBF leaves whose technical bin b is user bin 64*ident_word + b (no merged bins): a hit word
-    // of the row IS a word of the result mask.  ident_word == kNoIdent otherwise.
-    uint32_t ident_word;
-    uint32_t reserved;
-};
-static constexpr uint32_t kNoIdent = 0xFFFFFFFFu;
+// (IbfDev, the descriptor of one IBF in HBM: txq_records.hpp)
 
 // floor(x * n / 2^64) for n < 2^32 (every IBF with fewer than 4 G rows): two 32-bit multiplies
 __device__ __forceinline__ uint64_t fastrange32(uint64_t x, uint32_t n) {
