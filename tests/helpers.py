@@ -352,13 +352,16 @@ class SessionSimulator:
     BLOCK_SHIFT = 22
     INDEX_MASK = 0x3FFFFF
 
-    def __init__(self, oracle_index, n_programs, dgram_index=None):
+    def __init__(self, oracle_index, n_programs, dgram_index=None, window=None):
+        """window = (word0, words): a column shard.  ONES and every probed mask are cut to these words — every op is
+        column-wise, so all slots are exactly the shard's columns of the whole masks — and the alive answers count the
+        shard's bits, as a device session on that shard does."""
         from tetrex_amd import host
         self.host = host
         self.ox = oracle_index
         self.dg = dgram_index  # oracle flat IBF over d-gram codes (the session's auxiliary index)
-        self.W = oracle_index.words_per_mask
-        self.ones = ones_mask(oracle_index.bins)
+        self.word0, self.W = (0, oracle_index.words_per_mask) if window is None else (int(window[0]), int(window[1]))
+        self.ones = self._pad(ones_mask(oracle_index.bins, self.word0, self.W))
         self.slots = [dict() for _ in range(n_programs)]
         # per program: block id -> dict(arr [cap, W], valid [cap] (which entries hold defined values: a shaped DENSE_ZERO of an
         # untracked block leaves the rest undefined, and nothing may touch them), geom = per position the sorted codes)
@@ -368,7 +371,20 @@ class SessionSimulator:
         self.dense_kinds = [0, 0, 0, 0]  # ZERO, STEP, REDUCE, FILL ops seen
         self.tracked = [False] * n_programs  # TXQ_PROGRAM_TRACKED_BIT: the program's blocks carry live lists
         self.tracked_ops = 0
+        self.noprobe_steps = 0
         self.block_entries = []  # capacities of the tracked blocks created
+
+    def _pad(self, m):
+        """words of the window behind the last word of the masks (a shard padded past the bins) are zero"""
+        if m.shape[-1] == self.W:
+            return np.ascontiguousarray(m)
+        out = np.zeros(m.shape[:-1] + (self.W,), dtype=np.uint64)
+        out[..., :m.shape[-1]] = m
+        return out
+
+    def _probe(self, index, values):
+        """bulk_contains of the values, the simulator's columns of it"""
+        return self._pad(index.probe(values)[..., self.word0:self.word0 + self.W])
 
     def _entry(self, p, s):
         blk = self.blocks[p][(s & ~self.DENSE_BIT) >> self.BLOCK_SHIFT]
@@ -440,7 +456,7 @@ class SessionSimulator:
         assert int(row[15]) < 4
         self.tracked_ops += int(row[15]) & 1
         noprobe = bool(int(row[15]) & 2)
-        self.noprobe_steps = getattr(self, "noprobe_steps", 0) + int(noprobe)
+        self.noprobe_steps += int(noprobe)
         shape = [self._codes(int(row[4 + j])) for j in range(pos)]
         assert all(c < A for cs in shape for c in cs)
 
@@ -525,7 +541,7 @@ class SessionSimulator:
                 val = self._canonical(fwd, k) if par["canonical"] else fwd
                 si = int(srk[0][ai]) * s_stride0 + smid
                 assert sblk["valid"][si].all(), "DENSE_STEP reads outside the zeroed shape of its source block"
-                acc |= sblk["arr"][si] if noprobe else sblk["arr"][si] & self.ox.probe(val)
+                acc |= sblk["arr"][si] if noprobe else sblk["arr"][si] & self._probe(self.ox, val)
             di = dmid * dn[pos - 1] + int(drk[pos - 1][r])
             assert dblk["valid"][di].all(), "DENSE_STEP accumulates outside the zeroed shape of its destination block"
             dblk["arr"][di] |= acc
@@ -604,10 +620,10 @@ class SessionSimulator:
                                                      geom=[list(range(A))] * pos)
         n_aux = self.host.blob_aux_kmers(blob)
         n_main = kmers.size - n_aux
-        M = self.ox.probe(kmers[:n_main]) if n_main else np.zeros((0, self.W), dtype=np.uint64)
+        M = self._probe(self.ox, kmers[:n_main]) if n_main else np.zeros((0, self.W), dtype=np.uint64)
         if n_aux:
             assert self.dg is not None, "blob has d-gram k-mers but no auxiliary index is attached"
-            M = np.concatenate([M, self.dg.probe(kmers[n_main:])])
+            M = np.concatenate([M, self._probe(self.dg, kmers[n_main:])])
         for p, (n_slots, ops) in enumerate(progs):
             for k, d, a, b in ops:
                 if k == self.DENSE_OP:

@@ -451,14 +451,16 @@ class Session:
         self._aux = aux  # keep it alive
         check(lib().txq_session_set_aux_index(self._h, aux._h if aux is not None else None))
 
-    def stage(self, blob, query_program=(), query_slot=()):
+    def stage(self, blob, query_program=(), query_slot=(), raw=False):
+        """Runs a stage and answers its feedback queries: is the slot alive?  raw: the library's bytes themselves (0, or
+        1 + floor(log2(bits set)), include/txq.h) instead of their truth value."""
         al, size = _aligned(blob)
         qp = np.ascontiguousarray(query_program, dtype=np.uint32)
         qs = np.ascontiguousarray(query_slot, dtype=np.uint32)
         alive = np.zeros(max(qp.size, 1), dtype=np.uint8)
         check(lib().txq_session_stage(self._h, al.ctypes.data, size, qp.ctypes.data_as(u32p), qs.ctypes.data_as(u32p),
                                       qp.size, alive.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return alive[:qp.size].astype(bool)
+        return alive[:qp.size].copy() if raw else alive[:qp.size].astype(bool)
 
     def end(self):
         out = np.zeros((self.n, self.index.shard_words), dtype=np.uint64)

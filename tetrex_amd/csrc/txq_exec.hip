@@ -2482,6 +2482,8 @@ static int stage_decide(Stage& g, bool* empty) {
     BlobView& bv = g.bv;
     g.t0 = now_s();
     if (int rc = validate_blob(g.blob, g.bytes, s.n_programs, s.kn, &bv)) return rc;
+    // (refused here, like everything else that is wrong with a stage: before a region is grown or a kernel launched)
+    if (bv.n_aux_kmers && !s.aux) return fail(TXQ_ERR_STATE, "the blob has auxiliary (d-gram) k-mers but the session has no auxiliary index");
     s.t_validate += now_s() - g.t0;
     g.t0 = g.t_begin = now_s();
     ++s.n_stages;
@@ -2707,7 +2709,6 @@ static int stage_prologue(Stage& g) {
     }
     const uint64_t* d_kmers = (const uint64_t*)(g.d_blob + g.bv.kmers_offset);
     const size_t n_aux = (size_t)g.bv.n_aux_kmers, n_main = g.bv.n_kmers - n_aux;
-    if (n_aux && !s.aux) return fail(TXQ_ERR_STATE, "the blob has auxiliary (d-gram) k-mers but the session has no auxiliary index");
     if (n_main) {
         if (s.vspace) {
             if (int rc = hibf_probe_layout_order(ix, d_kmers, n_main, g.d_masks, st)) return rc;
