@@ -504,7 +504,8 @@ def random_session(rng, spec, meta=None):
     """A well-formed session of N_STAGES stages: [(blob, query_program, query_slot)].
     spec: dict(W = mask words (sizes the big programs), n_kmers = main k-mers per stage, kmer_pool = values to draw them from,
     n_aux_kmers, aux_pool, dense = None or dict(k, bits, alphabet, canonical), dense_mode = "both" | "untracked" | "tracked",
-    twins = T, scale = how many of the small kinds).  Program ids: logical program i, copy t is program sum(T) ... in order;
+    twins = T, scale = how many of the small kinds; fan_in = accumulations per fan-in program, big = (ops above the unit
+    threshold, levels) per big program: smaller sessions for fixtures).  Program ids: logical program i, copy t is program sum(T) ... in order;
     the T copies of a logical program are consecutive programs.  meta: a list that receives, per program, (kind of its logical
     program, number of the logical program, the slot its last level copies into RESULT or None) — for messages."""
     c = _Ctx(rng, spec)
@@ -516,13 +517,13 @@ def random_session(rng, spec, meta=None):
     else:
         for _ in range(5 * scale):
             logical.append(_small(c))
-        logical.append(_fan_in(c, 500))
-        logical.append(_fan_in(c, 137))
+        for n_acc in spec.get("fan_in", (500, 137)):
+            logical.append(_fan_in(c, n_acc))
         logical.append(_chain(c, 30))
         logical.append(_Prog())  # no op at all: result zero
         need = -(-32768 // W)
-        logical.append(_big(c, need + 8, 32))
-        logical.append(_big(c, need + 300, 5))
+        for extra, depth in spec.get("big", ((8, 32), (300, 5))):
+            logical.append(_big(c, need + extra, depth))
         logical.append(_small(c, first=2))  # its first op comes in stage 2
         if spec.get("dense"):
             mode = spec.get("dense_mode", "both")

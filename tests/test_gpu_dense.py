@@ -302,7 +302,7 @@ def test_large_blocks_k5_base_alphabet_and_k6_murphy(capi, oracle, monkeypatch):
 def test_dense_regions_are_recycled_when_block_memory_is_short(capi, oracle, monkeypatch):
     """TETREX_DENSE_POOL_MB=200 (about 170 blocks of a 1024-bin index) for 80 wildcard motifs: queries are admitted in waves,
     finished ones hand their blocks back and the device gives their dense regions to the next wave (txq_exec.hip
-    grow_slot_regions).  Same masks as with the default pool, and as the oracle's."""
+    SlotBook::grow).  Same masks as with the default pool, and as the oracle's."""
     ox = _oracle_index(oracle, bins=1024, m=4099, h=3, k=4, dna=False, per_bin=1500, seed=31)
     qs = [q for q in random_prosite_motifs(400, 41, wildcard=0.15, ranges=0.08) if "." in q][:80]
     sh = ox.shape()

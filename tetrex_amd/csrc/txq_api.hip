@@ -443,8 +443,8 @@ int txq_index_memory(const txq_index* ix, uint64_t* free_bytes, uint64_t* kept_b
     size_t free_b = 0, total_b = 0;
     TXQ_HIP(hipMemGetInfo(&free_b, &total_b));
     uint64_t kept = 0;
-    for (const Index::ArenaChunk& c : ix->session_cache.chunks) kept += (uint64_t)c.cap * 8;
-    for (const Index::ArenaChunk& c : ix->session_cache.block_chunks) kept += (uint64_t)c.cap * 8;
+    for (const ArenaChunk& c : ix->session_cache.chunks) kept += (uint64_t)c.cap * 8;
+    for (const ArenaChunk& c : ix->session_cache.block_chunks) kept += (uint64_t)c.cap * 8;
     *free_bytes = free_b;
     *kept_bytes = kept;
     return TXQ_OK;

@@ -16,7 +16,9 @@
 //                  it expands them further — answered as 0 or 1 + floor(log2(bits set)): how full the
 //                  surviving masks are tells the host whether dense blocks pay on this index.
 // Most queries finish in one stage; txq_run_programs is exactly that case.
-// Format of a stage's op list: include/txq_program.h.
+// Format of a stage's op list: include/txq_program.h.  What a stage plans on the host before anything is uploaded — the blob's
+// validation, the books on slot regions and dense blocks, units, tiles and chunks — is txq_exec_plan.hpp (no HIP: a CPU test
+// runs it); this file keeps the kernels, the row sources, the phases with their launches and the session's HIP resources.
 //
 // Stages are not waited for one by one: a session owns two staging sets (blob, tables, unit and tile-group lists,
 // the probe's output) and uploads on its own stream, so stage n+1 is submitted while the kernels of stage n run —
@@ -35,8 +37,6 @@
 // TreeRowsByLane) or the interleaved children of a small uniform one (InterleavedRows).
 #include "txq_internal.hpp"
 #include <algorithm>
-#include <thread>
-#include <atomic>
 #include "../../include/txq_program.h"
 #include <chrono>
 #include <cstdio>
@@ -56,10 +56,9 @@ __device__ __forceinline__ void slot_store(uint64_t* p, uint64_t v) {
 }
 
 // A dense block in HBM: [cap][W] mask words, then its live list (include/txq_program.h, tracked programs): a 64-byte
-// header — number of listed entries, capacity, the block's geometry —, a bitmap of cap bits ("entry is listed"), the list.
+// header — number of listed entries, capacity, the block's geometry —, a bitmap of cap bits ("entry is listed"), the list
+// (kBlockHeaderWords, block_meta_words: txq_exec_plan.hpp).
 struct BlockMeta { uint32_t* count; uint32_t* geom; uint64_t* bitmap; uint32_t* list; };
-static constexpr uint32_t kBlockHeaderWords = 8;
-__host__ __device__ __forceinline__ size_t block_meta_words(uint32_t cap) { return kBlockHeaderWords + ((size_t)cap + 63) / 64 + ((size_t)cap + 1) / 2; }
 __device__ __forceinline__ BlockMeta block_meta(uint64_t* block, uint32_t cap, uint32_t W) {
     uint64_t* m = block + (size_t)cap * W;
     uint32_t* h = reinterpret_cast<uint32_t*>(m);
@@ -154,10 +153,7 @@ __global__ __launch_bounds__(1024) void exec_kernel(const DevProgram* __restrict
 // Big programs: one launch per dependency level, the level's ops of ALL big programs cut into
 // units of <= unit_ops(W) ops; one workgroup per unit, G lanes per op (up to the whole workgroup for wide masks).  The kernel boundary is the
 // barrier between levels, so slot words are plain loads/stores; concurrent accumulations use
-// agent-scope atomics (units of one program may run on different XCDs).
-struct ExecUnit { uint32_t program, begin, end; };
-static constexpr uint32_t kUnitWords = 2048;  // mask words one unit moves per operand: 128 ops of a 1024-bin index, 2 ops at 65536 bins
-static inline uint32_t unit_ops(uint32_t W) { return W >= kUnitWords ? 1u : kUnitWords / W; }
+// agent-scope atomics (units of one program may run on different XCDs).  (ExecUnit, unit_ops: txq_exec_plan.hpp)
 
 // g_log2: log2 of the lanes per op (a power of two <= 256)
 __device__ __forceinline__ void run_unit(const ExecUnit u, const txq_op* __restrict__ ops, uint64_t* const* __restrict__ slot_base,
@@ -201,24 +197,8 @@ __global__ __launch_bounds__(256) void exec_units_kernel(const ExecUnit* __restr
 struct LevelUnits { const ExecUnit* units; const txq_op* ops; const uint64_t* M; uint32_t n_units, g_log2; };
 
 // ---- dense DP steps ---------------------------------------------------------------------------
-// One workgroup per tile: `count` work entries of one dense op, starting at `first`.
-//   ZERO    entries = slots of the block
-//   REDUCE  entries = suffixes inside shape[0] x .. x shape[k-2]
-//   STEP    entries = destination suffixes (x1 .. x_{k-2}, r) inside shape[1] x .. x shape[k-2] x R; each is
-//           handled by G lanes (a lane owns 16 bytes of the mask: WIDE, or one word) which loop over the
-//           predecessors a in shape[0], two at a time: 2 * (H row gathers + 1 source mask) loads in flight
-struct DenseTile { uint32_t program, op, first, count; };
-// The host does not spell the tiles of a stage out (the bench batch: 210 000 of them for 6 800 dense ops): it sends one
-// group per dense op — its tiles are [first_tile, first_tile + ceil(entries / per_tile)) of the stage's tile array, the
-// groups of one level back to back — and make_tiles_kernel writes them (one workgroup per group).
-struct TileGroup { uint32_t program, op, entries, per_tile; uint64_t first_tile; };
+// (DenseTile, TileGroup, DenseParams, DenseOpPtr — what a tile is and where its blocks live: txq_exec_plan.hpp)
 static constexpr uint32_t kRootWordsLds = 4096;  // 32 KB of root verdicts per workgroup (TreeRowsByLane)
-struct DenseParams { uint32_t k, bits, A, canonical, pos; uint32_t pow_a[TXQ_DENSE_MAX_POSITIONS + 1]; uint32_t nt; };  // nt: A/B bits (TXQ_DENSE_NT): 1 destination stores, 2 destination loads
-// Where the blocks (and slots) of a stage's dense op live, resolved by the host side when it plans the stage:
-// dst = the block written (ZERO, STEP, FILL) or the slot accumulated into (REDUCE); src = the block read (STEP, REDUCE) or
-// the slot spread (FILL).  A tile reads this next to the op itself: no pointer chase through the program's tables.
-struct DenseOpPtr { uint64_t* dst; const uint64_t* src; uint32_t dst_cap, src_cap; };  // (capacities of the blocks: where their live lists sit)
-
 __global__ __launch_bounds__(256) void make_tiles_kernel(const TileGroup* __restrict__ groups, DenseTile* __restrict__ tiles) {
     const TileGroup g = groups[blockIdx.x];
     const uint32_t n = (g.entries + g.per_tile - 1) / g.per_tile;
@@ -857,9 +837,6 @@ __device__ __forceinline__ void dense_codes(const txq_dense_op* __restrict__ d, 
 // groups (one group per op), turns them into chunks of kSparseChunk entries and leaves counts and the running chunk
 // total in the stage's tables; sparse_kernel's workgroups share the chunks out evenly.  A ZERO's count is reset by
 // the plan kernel (the chunks work from the snapshot): nothing else of the level touches that block.
-struct SparseGroup { uint32_t op; uint32_t fixed; };  // fixed != kNotFixed: the host knows the entries (FILL: its shape)
-static constexpr uint32_t kNotFixed = 0xFFFFFFFFu;
-static constexpr uint32_t kSparseChunk = 64;
 static constexpr uint32_t kUnitChunk = 256;      // most entries per chunk of sparse_units_kernel: one decoding thread each
 static constexpr uint32_t kUnitFresh = 2048;     // fresh destination entries it collects per chunk (more: appended one by one)
 // sparse_units_kernel cuts a group's list into chunks of about 512 UNITS (entry x residue), not of a fixed number of entries: a
@@ -873,7 +850,6 @@ __host__ __device__ __forceinline__ uint32_t unit_chunk_entries(uint32_t n_r, ui
     return c & ~7u;
 }
 static constexpr uint32_t kUnitStepWords = 32;  // masks up to this wide (2048 bins) step by units (sparse_kernel, narrow masks)
-static constexpr uint32_t kMaxSparseGroups = 1024;  // per launch (the chunk totals sit in LDS)
 
 __global__ __launch_bounds__(1024) void sparse_plan_kernel(const SparseGroup* __restrict__ groups, uint32_t n_groups, const txq_dense_op* __restrict__ dops,
                                                            const DenseOpPtr* __restrict__ optr, uint32_t W, uint32_t pos, uint32_t chunk, uint32_t* __restrict__ counts,
@@ -1484,7 +1460,6 @@ __global__ __launch_bounds__(256) void dense_hibf_combine_kernel(const DenseTile
 
 // grown slot regions keep their contents: all moves of a stage in ONE launch (a hipMemcpyAsync per program cost 20 ms
 // of host time when a thousand programs' dense regions doubled in the same stage); blockIdx.y cuts a move into 16 slices
-struct RegionMove { uint64_t* dst; const uint64_t* src; size_t words; };
 __global__ __launch_bounds__(256) void move_regions_kernel(const RegionMove* __restrict__ moves) {
     const RegionMove m = moves[blockIdx.x];
     const size_t per = (m.words + gridDim.y - 1) / gridDim.y;
@@ -1544,189 +1519,6 @@ __global__ __launch_bounds__(256) void gather_result_kernel(uint64_t* const* __r
     }
 }
 
-// Host-side validation: nothing malformed may reach the GPU (a stray slot or k-mer index would
-// be an out-of-bounds access there).  Accepts version 1 (op order), 2 (levels) and 3 (levels + dense
-// ops) blobs and normalises the program table.
-struct BlobView {
-    uint32_t n_kmers = 0, n_ops = 0, n_levels = 0, n_dense = 0;
-    uint64_t kmers_offset = 0, ops_offset = 0, levels_offset = 0, n_aux_kmers = 0, dense_offset = 0;
-    DenseParams dense{};
-    uint32_t block_slots = 0;  // A^(k-1) when the blob is version 3
-    std::vector<DevProgram> programs;
-    std::vector<uint32_t> n_slots, n_blocks;  // per program: ordinary slots; dense blocks (ids 0 .. n-1)
-    std::vector<uint8_t> has_dense;  // the program has dense ops in this stage
-    std::vector<uint8_t> tracked;    // TXQ_PROGRAM_TRACKED_BIT
-};
-
-static int validate_blob(const unsigned char* blob, size_t bytes, size_t n_programs, const Knobs& kn, BlobView* out) {
-    if (bytes < sizeof(txq_blob_header)) return fail(TXQ_ERR_PROGRAM, "blob shorter than its header");
-    if ((uintptr_t)blob % 8) return fail(TXQ_ERR_PROGRAM, "blob must be 8-byte aligned");
-    const txq_blob_header* h1 = (const txq_blob_header*)blob;
-    if (h1->magic != TXQ_PROGRAM_MAGIC) return fail(TXQ_ERR_PROGRAM, "bad blob magic");
-    const bool v3 = h1->version == TXQ_PROGRAM_VERSION_DENSE;  // (levels + dense ops)
-    const bool v2 = v3 || h1->version == TXQ_PROGRAM_VERSION_LEVELS;
-    if (!v2 && h1->version != TXQ_PROGRAM_VERSION) return fail(TXQ_ERR_PROGRAM, "unsupported blob version %u", h1->version);
-    if (bytes < (v3 ? sizeof(txq_blob_header_v3) : v2 ? sizeof(txq_blob_header_v2) : sizeof(txq_blob_header)))
-        return fail(TXQ_ERR_PROGRAM, "blob shorter than its header");
-    const txq_blob_header_v2* h2 = (const txq_blob_header_v2*)blob;
-    const txq_blob_header_v3* h3 = (const txq_blob_header_v3*)blob;
-    BlobView v;
-    uint64_t programs_offset;
-    if (v2) {
-        v.n_kmers = h2->n_kmers; v.n_ops = h2->n_ops; v.n_levels = h2->n_levels;
-        v.kmers_offset = h2->kmers_offset; v.ops_offset = h2->ops_offset; v.levels_offset = h2->levels_offset;
-        v.n_aux_kmers = h2->n_aux_kmers;
-        if (v.n_aux_kmers > v.n_kmers) return fail(TXQ_ERR_PROGRAM, "more auxiliary k-mers than k-mers");
-        programs_offset = h2->programs_offset;
-        if (h2->n_programs != n_programs) return fail(TXQ_ERR_PROGRAM, "blob holds %u programs, caller says %zu", h2->n_programs, n_programs);
-    } else {
-        v.n_kmers = h1->n_kmers; v.n_ops = h1->n_ops;
-        v.kmers_offset = h1->kmers_offset; v.ops_offset = h1->ops_offset;
-        programs_offset = h1->programs_offset;
-        if (h1->n_programs != n_programs) return fail(TXQ_ERR_PROGRAM, "blob holds %u programs, caller says %zu", h1->n_programs, n_programs);
-    }
-    auto in_range = [&](uint64_t off, uint64_t count, uint64_t elem) {
-        return off % 4 == 0 && off <= bytes && count <= (bytes - off) / elem;
-    };
-    if (v.kmers_offset % 8 || !in_range(v.kmers_offset, v.n_kmers, 8) || !in_range(v.ops_offset, v.n_ops, sizeof(txq_op)) ||
-        !in_range(programs_offset, n_programs, v2 ? sizeof(txq_program_v2) : sizeof(txq_program)) ||
-        (v2 && !in_range(v.levels_offset, v.n_levels, 4)))
-        return fail(TXQ_ERR_PROGRAM, "blob table outside the blob");
-    if (v3) {
-        v.n_dense = h3->n_dense;
-        v.dense_offset = h3->dense_offset;
-        if (v.dense_offset % 8 || !in_range(v.dense_offset, v.n_dense, sizeof(txq_dense_op))) return fail(TXQ_ERR_PROGRAM, "dense table outside the blob");
-        DenseParams& P = v.dense;
-        P.k = h3->k; P.bits = h3->bits; P.A = h3->alphabet; P.canonical = h3->canonical ? 1u : 0u;
-        if (P.k < 2 || P.k - 1 > TXQ_DENSE_MAX_POSITIONS || P.bits < 1 || P.bits > 8 || (uint64_t)P.bits * P.k > 64 || P.A < 1 || P.A > 32 ||
-            P.A > (1u << P.bits) || (P.canonical && P.bits != 2))
-            return fail(TXQ_ERR_PROGRAM, "dense parameters out of range (k %u, %u bits, alphabet %u)", P.k, P.bits, P.A);
-        P.pos = P.k - 1;
-        P.nt = (uint32_t)kn.dense_nt;
-        uint64_t n = 1;
-        P.pow_a[0] = 1;
-        for (uint32_t j = 1; j <= P.pos; ++j) {
-            n *= P.A;
-            if (n > (1u << 22)) return fail(TXQ_ERR_PROGRAM, "dense block of %u^%u slots is too large", P.A, P.pos);
-            P.pow_a[j] = (uint32_t)n;
-        }
-        v.block_slots = (uint32_t)n;
-    }
-    v.programs.resize(n_programs);
-    v.n_slots.resize(n_programs);
-    v.n_blocks.assign(n_programs, 0);
-    v.has_dense.assign(n_programs, 0);
-    v.tracked.assign(n_programs, 0);
-    const txq_op* ops = (const txq_op*)(blob + v.ops_offset);
-    const txq_dense_op* dops = v3 ? (const txq_dense_op*)(blob + v.dense_offset) : nullptr;
-    const uint32_t* levels = v2 ? (const uint32_t*)(blob + v.levels_offset) : nullptr;
-    for (uint32_t p = 0; p < n_programs; ++p) {
-        DevProgram d{};
-        if (v2) {
-            const txq_program_v2& s = ((const txq_program_v2*)(blob + programs_offset))[p];
-            d = DevProgram{s.first_op, s.n_ops, s.first_level, s.n_levels};
-            v.n_slots[p] = s.n_slots;
-            if (v3) {
-                v.tracked[p] = (s.reserved & TXQ_PROGRAM_TRACKED_BIT) != 0;
-                v.n_blocks[p] = s.reserved & ~TXQ_PROGRAM_TRACKED_BIT;
-                if (v.n_blocks[p] > TXQ_DENSE_MAX_BLOCKS) return fail(TXQ_ERR_PROGRAM, "program %u: more than %u dense blocks", p, TXQ_DENSE_MAX_BLOCKS);
-            }
-        } else {
-            const txq_program& s = ((const txq_program*)(blob + programs_offset))[p];
-            d = DevProgram{s.first_op, s.n_ops, 0, 0};
-            v.n_slots[p] = s.n_slots;
-        }
-        const uint32_t n_slots = v.n_slots[p];
-        if (n_slots < TXQ_SLOT_FIRST_FREE || n_slots >= TXQ_DENSE_SLOT_BIT) return fail(TXQ_ERR_PROGRAM, "program %u: n_slots out of range", p);
-        if (d.first_op > v.n_ops || d.n_ops > v.n_ops - d.first_op) return fail(TXQ_ERR_PROGRAM, "program %u: ops out of range", p);
-        if (d.n_levels) {
-            if (d.first_level > v.n_levels || d.n_levels > v.n_levels - d.first_level) return fail(TXQ_ERR_PROGRAM, "program %u: levels out of range", p);
-            uint32_t prev = 0;
-            for (uint32_t l = 0; l < d.n_levels; ++l) {
-                const uint32_t e = levels[d.first_level + l];
-                if (e < prev || e > d.n_ops) return fail(TXQ_ERR_PROGRAM, "program %u: level table not ascending", p);
-                prev = e;
-            }
-            if (prev != d.n_ops) return fail(TXQ_ERR_PROGRAM, "program %u: levels do not cover the ops", p);
-        }
-        v.programs[p] = d;
-    }
-    // every op of every program: operands inside the program's slot regions, k-mer inside the table, dense ops on
-    // whole blocks.  Large stages (hundreds of MB of ops) are checked by several threads, each taking whole programs.
-    struct Bad { uint32_t program = 0xFFFFFFFFu, op = 0; int kind = 0; };
-    auto check_program = [&](uint32_t p, Bad& bad) {
-        const DevProgram& d = v.programs[p];
-        const uint32_t n_slots = v.n_slots[p], n_blocks = v.n_blocks[p];
-        const bool tracked = v.tracked[p] != 0;
-        const txq_op* o = ops + d.first_op;
-        // a dense slot: an existing block id; its index inside A^(k-1) for untracked blocks (a tracked block's capacity is only
-        // known to the session: plan_units checks those)
-        auto slot_ok = [&](uint32_t s) {
-            if (s & 0x80000000u) return false;
-            if (!(s & TXQ_DENSE_SLOT_BIT)) return s < n_slots;
-            return ((s & ~TXQ_DENSE_SLOT_BIT) >> TXQ_DENSE_BLOCK_SHIFT) < n_blocks && (tracked || (s & TXQ_DENSE_INDEX_MASK) < v.block_slots);
-        };
-        auto block_ok = [&](uint32_t s) {
-            return !(s & 0x80000000u) && (s & TXQ_DENSE_SLOT_BIT) && (s & TXQ_DENSE_INDEX_MASK) == 0 && ((s & ~TXQ_DENSE_SLOT_BIT) >> TXQ_DENSE_BLOCK_SHIFT) < n_blocks;
-        };
-        for (uint32_t i = 0; i < d.n_ops; ++i) {
-            int kind = 0;
-            if (o[i].kmer == TXQ_DENSE_OP) {
-                if (!v3 || o[i].dst >= v.n_dense || d.n_levels == 0) kind = 4;
-                else {
-                    const txq_dense_op& x = dops[o[i].dst];
-                    const uint32_t code_mask = v.dense.A >= 32 ? 0xFFFFFFFFu : ((1u << v.dense.A) - 1u);
-                    bool ok = x.kind <= TXQ_DENSE_FILL;
-                    if (ok) ok = ((x.reserved & TXQ_DENSE_TRACKED) != 0) == (v.tracked[p] != 0) && (x.reserved & ~(TXQ_DENSE_TRACKED | TXQ_DENSE_NOPROBE)) == 0;
-                    if (ok && (x.reserved & TXQ_DENSE_NOPROBE)) ok = x.kind == TXQ_DENSE_STEP && v.tracked[p] != 0;  // (only the pushed steps of tracked programs)
-                    if (ok && x.kind != TXQ_DENSE_REDUCE) ok = block_ok(x.dst);
-                    if (ok && (x.kind == TXQ_DENSE_STEP || x.kind == TXQ_DENSE_REDUCE)) ok = block_ok(x.src);
-                    if (ok && x.kind == TXQ_DENSE_FILL) ok = !(x.src & TXQ_DENSE_SLOT_BIT) && x.src < n_slots;
-                    if (ok && (x.kind != TXQ_DENSE_ZERO || x.r_mask))
-                        for (uint32_t j = 0; ok && j < v.dense.pos; ++j) ok = (x.shape[j] & ~code_mask) == 0;
-                    if (ok && x.kind == TXQ_DENSE_STEP) ok = x.src != x.dst && (x.r_mask & ~code_mask) == 0;
-                    if (ok && x.kind == TXQ_DENSE_REDUCE) ok = slot_ok(x.dst) && x.dst != TXQ_SLOT_ZERO && x.dst != TXQ_SLOT_ONES && !(tracked && (x.dst & TXQ_DENSE_SLOT_BIT));
-                    if (ok && x.kind == TXQ_DENSE_ZERO && tracked) {  // (re)creates the block: geometry in shape[], capacity in src
-                        uint64_t entries = 1;
-                        for (uint32_t j = 0; j < v.dense.pos; ++j) entries *= (uint64_t)__builtin_popcount(x.shape[j]);
-                        ok = entries >= 1 && entries <= x.src && x.src <= (1u << TXQ_DENSE_BLOCK_SHIFT);
-                    }
-                    if (!ok) kind = 4;
-                    v.has_dense[p] = 1;
-                }
-            } else if (!slot_ok(o[i].dst) || !slot_ok(o[i].a) || !slot_ok(o[i].b)) kind = 1;
-            else if (o[i].dst == TXQ_SLOT_ZERO || o[i].dst == TXQ_SLOT_ONES) kind = 2;
-            else if (o[i].kmer != TXQ_NO_KMER && o[i].kmer >= v.n_kmers) kind = 3;
-            else if ((o[i].dst | o[i].a | o[i].b) & TXQ_DENSE_SLOT_BIT) {  // an ordinary op on block entries: the program runs level by level, like one with dense ops
-                if (d.n_levels == 0) kind = 4;
-                v.has_dense[p] = 1;
-            }
-            if (kind) { if (p < bad.program) bad = Bad{p, i, kind}; return; }
-        }
-    };
-    Bad bad;
-    unsigned n_threads = v.n_ops >= (1u << 20) ? std::min(8u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
-    if (n_threads <= 1) {
-        for (uint32_t p = 0; p < n_programs && bad.program == 0xFFFFFFFFu; ++p) check_program(p, bad);
-    } else {
-        std::vector<Bad> found(n_threads);
-        std::atomic<uint32_t> next{0};
-        std::vector<std::thread> workers;
-        for (unsigned t = 0; t < n_threads; ++t)
-            workers.emplace_back([&, t]() {
-                for (uint32_t p; (p = next.fetch_add(1)) < n_programs;) check_program(p, found[t]);
-            });
-        for (auto& w : workers) w.join();
-        for (const Bad& b : found) if (b.program < bad.program) bad = b;
-    }
-    if (bad.program != 0xFFFFFFFFu) {
-        static const char* const what[] = {"", "slot out of range", "writes a constant slot", "k-mer index out of range", "malformed dense op"};
-        return fail(TXQ_ERR_PROGRAM, "program %u op %u: %s", bad.program, bad.op, what[bad.kind]);
-    }
-    *out = std::move(v);
-    return TXQ_OK;
-}
-
 static double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -1736,15 +1528,15 @@ Session::~Session() {
         fprintf(stderr, "[txq] session: %zu programs, %zu stages, %.1f MB uploaded, %.1f MB of slots; validate %.3f s, upload %.3f s, device+sync %.3f s; "
                         "(regions %.3f, plan %.3f, wait for the staging set %.3f, buffers %.3f) "
                         "%zu levels, %zu unit launches (%zu units), %zu dense launches (%zu tiles), step rows: %s\n",
-                n_programs, n_stages, bytes_uploaded / 1e6, arena_words * 8 / 1e6, t_validate, t_upload, t_device, t_grow, t_plan, t_wait, t_alloc, n_levels, n_unit_launches, n_units,
+                n_programs, n_stages, bytes_uploaded / 1e6, book.slots.words * 8 / 1e6, t_validate, t_upload, t_device, t_grow, t_plan, t_wait, t_alloc, n_levels, n_unit_launches, n_units,
                 n_dense_launches, n_dense_tiles, row_source);
     if (kn.trace && n_step_pairs)
         fprintf(stderr, "[txq]   dense work: %llu predecessor visits for %llu destination suffixes, %llu slots zeroed, %llu entries reduced; mask %u words\n",
                 (unsigned long long)n_step_pairs, (unsigned long long)n_step_suffixes, (unsigned long long)n_zero_slots, (unsigned long long)n_reduce_entries, W);
     if (kn.trace && n_beside) fprintf(stderr, "[txq]   %zu stage(s) ran beside the previous one (second stream)\n", n_beside);
-    if (kn.trace && n_blocks_made + n_block_memsets + n_blocks_relisted)
+    if (kn.trace && book.n_blocks_made + n_block_memsets + book.n_blocks_relisted)
         fprintf(stderr, "[txq]   dense blocks: %zu made (%.1f MB in all; %zu chunks of block memory, %.2f ms in hipMalloc), %zu cleared for tracked programs, %zu taken over as a tracked program left them; %zu sparse launches (%zu groups)\n",
-                n_blocks_made, block_bytes_made / 1e6, block_chunks.size(), block_alloc_seconds * 1e3, n_block_memsets, n_blocks_relisted, n_sparse_launches, n_sparse_groups);
+                book.n_blocks_made, book.block_bytes_made / 1e6, book.block_mem.chunks.size(), block_alloc_seconds * 1e3, n_block_memsets, book.n_blocks_relisted, n_sparse_launches, n_sparse_groups);
     if (aux) --aux->open_sessions;
     if (ix) --ix->open_sessions;
     for (Index::StagingSet& t : set)  // nothing of the session may still be running when its buffers change hands
@@ -1772,31 +1564,9 @@ Session::~Session() {
         ~Lap() { if (on) fprintf(stderr, "[txq]   release: %zu outgrown staging buffers freed, then %.2f ms for buffers and blocks going back to the index\n", retired, (now_s() - t0) * 1e3); }
     } lap{kn.trace, now_s(), retired.size()};
     if (kn.trace && !retired.empty()) fprintf(stderr, "[txq]   release: hipFree of outgrown staging buffers %.2f ms\n", (lap.t0 - t_retire) * 1e3);
-    if (owns_cache && ix) {  // hand the buffers back for the next session (the chunks up to a total of kArenaKeepBytes)
+    if (owns_cache && ix) {  // hand the buffers back for the next session (SlotBook::hand_back says which chunks and blocks)
         Index::SessionCache& c = ix->session_cache;
-        size_t kept = 0;
-        for (const Index::ArenaChunk& k : chunks) {
-            if (kept + k.cap * 8 <= Index::kArenaKeepBytes) { c.chunks.push_back(k); kept += k.cap * 8; }
-            else (void)hipFree(k.p);
-        }
-        // the blocks: every one this session holds goes into the index's pool (a tracked program's are all zero outside their
-        // lists), unless a stage failed (their state is unknown) or slots and blocks together outgrow what an index keeps
-        size_t block_bytes = 0;
-        for (const Index::ArenaChunk& k : block_chunks) block_bytes += k.cap * 8;
-        if (!failed && kept + block_bytes <= Index::kArenaKeepBytes) {
-            c.block_chunks.swap(block_chunks);
-            c.block_cur = bcur;
-            c.block_used = bused;
-            c.blocks_W = W;
-            c.blocks.swap(pool);
-            for (size_t p = 0; p < blocks.size(); ++p)
-                for (const DenseBlock& b : blocks[p])
-                    if (b.p) c.blocks.put(DenseBlock{b.p, b.cap, (uint8_t)(tracked[p] ? kListed : kGarbage)});
-            c.blocks.absorb(free_blocks);
-            for (const std::vector<DenseBlock>& v : given_back)
-                for (const DenseBlock& b : v) c.blocks.put(b);
-        } else
-            for (const Index::ArenaChunk& k : block_chunks) (void)hipFree(k.p);
+        for (const ArenaChunk& k : book.hand_back(c, W, failed, Index::kArenaKeepBytes)) (void)hipFree(k.p);
         c.set[0] = set[0];
         c.set[1] = set[1];
         c.upload = upload;
@@ -1804,34 +1574,14 @@ Session::~Session() {
         c.in_use = false;
         return;
     }
-    for (const Index::ArenaChunk& k : chunks) (void)hipFree(k.p);
-    for (const Index::ArenaChunk& k : block_chunks) (void)hipFree(k.p);
+    for (const ArenaChunk& k : book.slots.chunks) (void)hipFree(k.p);
+    for (const ArenaChunk& k : book.block_mem.chunks) (void)hipFree(k.p);
     for (Index::StagingSet& t : set) {
         if (t.done) (void)hipEventDestroy(t.done);
         for (void* p : {(void*)t.d_blob, (void*)t.d_aux, (void*)t.d_masks}) if (p) (void)hipFree(p);
     }
     if (upload) (void)hipStreamDestroy(upload);
     if (side) (void)hipStreamDestroy(side);
-}
-
-
-// bump allocation of `words` 64-bit words of slot storage (an even number wherever W is even: 16-byte lanes)
-static int arena_alloc(Session& s, size_t words, uint64_t** out) {
-    while (s.cur < s.chunks.size() && s.chunk_used + words > s.chunks[s.cur].cap) { ++s.cur; s.chunk_used = 0; }  // adopted chunks
-    if (s.cur >= s.chunks.size()) {
-        // 8 MiB first, then as much again as the session already holds (at least 64 MiB): few, large chunks
-        size_t cap = s.chunks.empty() ? (size_t)1 << 20 : std::max((size_t)8 << 20, s.arena_words);
-        if (words > cap) cap = words;
-        uint64_t* c = nullptr;
-        TXQ_HIP(hipMalloc((void**)&c, cap * 8));
-        s.chunks.push_back(Index::ArenaChunk{c, cap});
-        s.arena_words += cap;
-        s.cur = s.chunks.size() - 1;
-        s.chunk_used = 0;
-    }
-    *out = s.chunks[s.cur].p + s.chunk_used;
-    s.chunk_used += words;
-    return TXQ_OK;
 }
 
 int session_begin(Index& ix, size_t n_programs, Session** out) {
@@ -1844,23 +1594,12 @@ int session_begin(Index& ix, size_t n_programs, Session** out) {
     s->n_programs = n_programs;
     s->vspace = ix.layout_order(s->kn);  // a general HIBF: the session's masks are rows in layout order (txq_records.hpp VChunk)
     s->W = s->vspace ? ix.v_words : (uint32_t)ix.shard_words;
-    s->base.assign(2 * n_programs, nullptr);
-    s->cap.assign(n_programs, 0);
-    s->blocks.assign(n_programs, {});
-    s->tracked.assign(n_programs, 0);
+    s->book.begin(n_programs);
     Index::SessionCache& c = ix.session_cache;
     if (!c.in_use) {  // adopt the previous session's buffers
         c.in_use = true;
         s->owns_cache = true;
-        s->chunks.swap(c.chunks);
-        for (const Index::ArenaChunk& k : s->chunks) s->arena_words += k.cap;
-        s->block_chunks.swap(c.block_chunks);
-        for (const Index::ArenaChunk& k : s->block_chunks) s->block_arena_words += k.cap;
-        if (c.blocks_W == s->W) {  // the pooled blocks fit this session's masks: take them over, go on allocating behind them
-            s->pool.swap(c.blocks);
-            s->bcur = c.block_cur;
-            s->bused = c.block_used;
-        }  // (else: another mask width — the chunks are reused from their beginning)
+        s->book.adopt(c, s->W);  // (the chunks, and the pooled blocks where they fit this session's masks)
         s->set[0] = c.set[0];
         s->set[1] = c.set[1];
         s->upload = c.upload;
@@ -1868,7 +1607,6 @@ int session_begin(Index& ix, size_t n_programs, Session** out) {
         c = Index::SessionCache{};
         c.in_use = true;
     }
-    s->last_stage.assign(n_programs, 0);
     if (s->kn.trace && hipMalloc((void**)&s->d_step_ctr, 4 * sizeof(unsigned long long)) == hipSuccess)
         (void)hipMemset(s->d_step_ctr, 0, 4 * sizeof(unsigned long long));
     else { (void)hipGetLastError(); s->d_step_ctr = nullptr; }
@@ -1887,309 +1625,6 @@ int session_begin(Index& ix, size_t n_programs, Session** out) {
     if (s->kn.trace) fprintf(stderr, "[txq] session begin: streams %.3f ms, events %.3f ms\n", (t_events - t_streams) * 1e3, (now_s() - t_events) * 1e3);
     *out = s;
     return TXQ_OK;
-}
-
-// (re)size the programs' slot regions to what the stage needs; a grown region keeps its contents
-// (host side only: the caller uploads `moves` and the base table with the stage and launches move_regions_kernel).
-// Dense blocks: an untracked program gets the blocks it counts (A^(k-1) entries each); a tracked program gets a block
-// when a ZERO of this stage creates it, with the capacity the op names (a block id keeps its capacity).  Blocks come
-// from those that finished programs gave back, or from the arena; `to_clear` = blocks that go to a tracked program and
-// must be all zero first (the caller memsets them on the stage's stream).
-static size_t block_alloc_words(uint32_t cap, uint32_t W) { return ((size_t)cap * W + block_meta_words(cap) + 1) & ~(size_t)1; }
-
-// the blocks' own arena (kept with the index between sessions together with the pool of blocks inside it)
-static int block_arena_alloc(Session& s, size_t words, uint64_t** out) {
-    while (s.bcur < s.block_chunks.size() && s.bused + words > s.block_chunks[s.bcur].cap) { ++s.bcur; s.bused = 0; }
-    if (s.bcur >= s.block_chunks.size()) {
-        size_t cap = std::max((size_t)8 << 20, s.block_arena_words);  // 64 MiB first, then as much again as there is
-        if (words > cap) cap = words;
-        uint64_t* c = nullptr;
-        const double t0 = now_s();
-        TXQ_HIP(hipMalloc((void**)&c, cap * 8));
-        s.block_alloc_seconds += now_s() - t0;
-        s.block_chunks.push_back(Index::ArenaChunk{c, cap});
-        s.block_arena_words += cap;
-        s.bcur = s.block_chunks.size() - 1;
-        s.bused = 0;
-    }
-    *out = s.block_chunks[s.bcur].p + s.bused;
-    s.bused += words;
-    return TXQ_OK;
-}
-
-static int take_block(Session& s, uint32_t cap, Session::DenseBlock* out) {
-    for (auto* from : {&s.free_blocks, &s.pool})  // given back in this session; left by earlier sessions on this index
-        if (from->take(cap, out)) return TXQ_OK;
-    Session::DenseBlock b{nullptr, cap, Session::kGarbage};
-    if (int rc = block_arena_alloc(s, block_alloc_words(cap, s.W), &b.p)) return rc;
-    ++s.n_blocks_made;
-    s.block_bytes_made += block_alloc_words(cap, s.W) * 8;
-    *out = b;
-    return TXQ_OK;
-}
-
-static int grow_slot_regions(Session& s, const BlobView& bv, const unsigned char* blob, std::vector<uint32_t>* fresh, std::vector<RegionMove>* moves_out,
-                             std::vector<std::pair<uint64_t*, size_t>>* to_clear) {
-    std::vector<RegionMove>& moves = *moves_out;
-    if (bv.block_slots) {
-        if (!s.block_slots) s.block_slots = bv.block_slots;
-        else if (s.block_slots != bv.block_slots)
-            return fail(TXQ_ERR_PROGRAM, "the block size changed within a session (%u -> %u slots)", s.block_slots, bv.block_slots);
-    }
-    // Blocks given back two stages ago serve other programs now: whatever used them has finished (a stage waits for the
-    // stage before the previous one, whose staging set it takes over), so a recycled block ties its new owner to nobody.
-    for (const Session::DenseBlock& b : s.given_back[1]) s.free_blocks.put(b);
-    s.given_back[1].swap(s.given_back[0]);
-    s.given_back[0].clear();
-    // a program that reports no dense blocks any more is finished with them
-    if (bv.block_slots)
-        for (size_t p = 0; p < s.n_programs; ++p)
-            if (bv.n_blocks[p] == 0 && !s.blocks[p].empty()) {
-                for (const Session::DenseBlock& b : s.blocks[p])
-                    if (b.p) {
-                        s.given_back[0].push_back(Session::DenseBlock{b.p, b.cap, (uint8_t)(s.tracked[p] ? Session::kListed : Session::kGarbage)});
-                        --s.n_blocks_live;
-                    }
-                s.blocks[p].clear();
-                s.base[s.n_programs + p] = nullptr;
-            }
-    const txq_op* ops = (const txq_op*)(blob + bv.ops_offset);
-    const txq_dense_op* dops = bv.n_dense ? (const txq_dense_op*)(blob + bv.dense_offset) : nullptr;
-    for (size_t p = 0; p < s.n_programs; ++p) {
-        // a program gets its region with its first ops (a query of a later wave would otherwise get eight slots now and
-        // outgrow them — a move, tied to this stage's init kernel — the moment it begins)
-        const uint32_t need = s.cap[p] || bv.programs[p].n_ops ? bv.n_slots[p] : 0;
-        if (need > s.cap[p]) {
-            uint32_t cap = s.cap[p] ? s.cap[p] * 2 : 8;
-            if (cap < need) cap = need;
-            uint64_t* region = nullptr;
-            if (int rc = arena_alloc(s, (size_t)cap * s.W, &region)) return rc;
-            if (s.cap[p]) moves.push_back(RegionMove{region, s.base[p], (size_t)s.cap[p] * s.W});
-            else fresh->push_back((uint32_t)p);
-            s.base[p] = region;
-            s.cap[p] = cap;
-        }
-        const size_t bneed = bv.block_slots ? bv.n_blocks[p] : 0;
-        if (!bneed) continue;
-        if (s.blocks[p].empty()) s.tracked[p] = bv.tracked[p];
-        else if (s.tracked[p] != bv.tracked[p]) return fail(TXQ_ERR_PROGRAM, "program %zu: tracked and untracked blocks in one program", p);
-        if (s.blocks[p].size() < bneed) s.blocks[p].resize(bneed, Session::DenseBlock{nullptr, 0, Session::kGarbage});
-        if (!s.tracked[p]) {
-            for (Session::DenseBlock& b : s.blocks[p])
-                if (!b.p) {
-                    if (int rc = take_block(s, bv.block_slots, &b)) return rc;
-                    ++s.n_blocks_live;
-                }
-            continue;
-        }
-        if (!bv.has_dense[p]) continue;
-        const DevProgram& d = bv.programs[p];
-        for (uint32_t i = 0; i < d.n_ops; ++i) {
-            const txq_op& o = ops[d.first_op + i];
-            if (o.kmer != TXQ_DENSE_OP || dops[o.dst].kind != TXQ_DENSE_ZERO) continue;
-            const txq_dense_op& z = dops[o.dst];
-            Session::DenseBlock& b = s.blocks[p][(z.dst & ~TXQ_DENSE_SLOT_BIT) >> TXQ_DENSE_BLOCK_SHIFT];
-            if (b.p) {
-                if (b.cap != z.src) return fail(TXQ_ERR_PROGRAM, "program %zu: a tracked block changed its capacity (%u -> %u entries)", p, b.cap, z.src);
-                continue;
-            }
-            if (int rc = take_block(s, z.src, &b)) return rc;
-            ++s.n_blocks_live;
-            // a block a tracked program left behind is all zero outside its list, and the ZERO that creates the block here
-            // clears what is listed (sparse_plan_kernel resets the count, the chunks clear entries and bitmap bits): as it is
-            if (b.state == Session::kListed) ++s.n_blocks_relisted;
-            else to_clear->emplace_back(b.p, block_alloc_words(b.cap, s.W) * 8);
-            b.state = Session::kGarbage;  // (what it is while its program runs; tracked[p] decides what it is given back as)
-        }
-    }
-    return TXQ_OK;
-}
-
-// Big level-scheduled programs, and every program with dense ops, leave the one-workgroup-per-program kernel:
-// their ops are cut into units per dependency level (units of level l, all programs, are contiguous in `units`),
-// their dense ops into tiles, and every level becomes one launch of each kind over the whole GPU.
-struct LevelPlan {
-    size_t units = 0, tiles = 0, hsteps = 0, sparse = 0, sparse_chunks = 0;
-    // the level's sparse groups are ordered [others | STEPs]: the first sparse_misc go to the sparse_kernel without step code,
-    // the STEPs to the one with it (sparse_chunks counts the others' chunks)
-    size_t sparse_misc = 0, step_chunks = 0;
-};
-// What plan_units makes of a stage's programs: the lists a stage uploads and the launches of its levels.
-struct StagePlan {
-    std::vector<ExecUnit> units;          // ordinary ops, level by level
-    std::vector<TileGroup> tile_groups;   // untracked dense ops; make_tiles_kernel cuts them into n_tiles tiles
-    size_t n_tiles = 0;
-    std::vector<DenseTile> hsteps;        // HIBF descent: the STEP tiles ...
-    std::vector<uint32_t> hstep_na;       // ... and their predecessors per suffix
-    std::vector<SparseGroup> sparse_groups;
-    std::vector<DenseOpPtr> optr;         // every dense op's blocks, indexed like the stage's dense table
-    std::vector<LevelPlan> levels;
-    size_t n_small = 0;                   // programs left to exec_kernel
-    uint64_t work[4] = {0, 0, 0, 0};      // step pairs, step suffixes, slots zeroed or filled, entries reduced (TXQ_TRACE)
-    // chunk_hibf_steps: chunk c = hsteps [chunk_first[c], chunk_first[c + 1]), pair_base[tile] = first pair of the tile within its chunk
-    std::vector<uint32_t> pair_base, chunk_pairs;
-    std::vector<size_t> chunk_first;
-    size_t most_pairs = 0;
-};
-// hibf: STEP tiles go to their own list (`hsteps`, with the number of predecessors per suffix in `hstep_na`): on an
-// HIBF a step is three launches (dense_hibf_*), not a tile of dense_kernel.
-// The dense ops of tracked programs become sparse groups (one per op; sparse_kernel), and every dense op's blocks are
-// resolved to pointers here (`optr`, indexed like the stage's dense table).
-static int plan_units(const Session& s, BlobView& bv, const unsigned char* blob, uint32_t W, uint32_t G_dense, bool hibf, StagePlan* out) {
-    const uint32_t per_unit = unit_ops(W);
-    const uint32_t* levels_host = bv.n_levels ? (const uint32_t*)(blob + bv.levels_offset) : nullptr;
-    const txq_op* ops = (const txq_op*)(blob + bv.ops_offset);
-    const txq_dense_op* dops = bv.n_dense ? (const txq_dense_op*)(blob + bv.dense_offset) : nullptr;
-    out->optr.assign(bv.n_dense, DenseOpPtr{nullptr, nullptr, 0, 0});
-    std::vector<std::vector<ExecUnit>> per_level;
-    std::vector<std::vector<TileGroup>> groups_level;
-    std::vector<std::vector<DenseTile>> hsteps_level;
-    std::vector<std::vector<SparseGroup>> sparse_level, step_level;  // (step_level: the STEP groups)
-    std::vector<size_t> sparse_chunks, step_chunks;
-    // entries per tile: every lane-group set of the workgroup gets two destination suffixes of a step (TXQ_DENSE_TILE_ROUNDS)
-    const uint32_t step_tile = (uint32_t)s.kn.dense_tile_rounds * (256 / (G_dense ? G_dense : 1));
-    size_t n_small = 0;
-    int bad_program = -1;
-    for (size_t p = 0; p < bv.programs.size(); ++p) {
-        DevProgram& d = bv.programs[p];
-        const bool dense = bv.has_dense[p] != 0;
-        // small = less work than a unit launch is worth: 2048 ops of a 1024-bin index, 32 ops at 65536 bins
-        if (!dense && (d.n_levels == 0 || (uint64_t)d.n_ops * W < 2048u * 16u)) { n_small += d.n_ops != 0; continue; }
-        if (per_level.size() < d.n_levels) {
-            per_level.resize(d.n_levels); groups_level.resize(d.n_levels); hsteps_level.resize(d.n_levels);
-            sparse_level.resize(d.n_levels); sparse_chunks.resize(d.n_levels, 0);
-            step_level.resize(d.n_levels); step_chunks.resize(d.n_levels, 0);
-        }
-        // (validate_blob has checked that block operands name existing block ids; grow_slot_regions has given the program its
-        // blocks — a tracked block exists once a ZERO has created it: an op on one that was never created is refused here)
-        auto block_of = [&](uint32_t slot) -> const Session::DenseBlock& {
-            const Session::DenseBlock& b = s.blocks[p][(slot & ~TXQ_DENSE_SLOT_BIT) >> TXQ_DENSE_BLOCK_SHIFT];
-            if (!b.p) bad_program = (int)p;
-            return b;
-        };
-        auto slot_of = [&](uint32_t slot) -> uint64_t* {
-            if (!(slot & TXQ_DENSE_SLOT_BIT)) return s.base[p] + (size_t)slot * W;
-            const Session::DenseBlock& b = block_of(slot);
-            if ((slot & TXQ_DENSE_INDEX_MASK) >= b.cap) bad_program = (int)p;
-            return b.p + (size_t)(slot & TXQ_DENSE_INDEX_MASK) * W;
-        };
-        const bool check_slots = dense && bv.tracked[p];  // ordinary ops on dense slots of tracked blocks: inside the block's capacity?
-        uint32_t begin = 0;
-        for (uint32_t l = 0; l < d.n_levels; ++l) {
-            const uint32_t end = levels_host[d.first_level + l];
-            auto cut = [&](uint32_t from, uint32_t to) {  // a run of ordinary ops -> units
-                for (uint32_t at = from; at < to; at += per_unit)
-                    per_level[l].push_back(ExecUnit{(uint32_t)p, d.first_op + at, d.first_op + (to - at < per_unit ? to : at + per_unit)});
-            };
-            if (!dense) cut(begin, end);
-            else {
-                uint32_t run = begin;
-                for (uint32_t i = begin; i < end; ++i) {
-                    const txq_op& o = ops[d.first_op + i];
-                    if (o.kmer != TXQ_DENSE_OP) {
-                        if (check_slots)
-                            for (uint32_t operand : {o.dst, o.a, o.b})
-                                if (operand & TXQ_DENSE_SLOT_BIT) (void)slot_of(operand);
-                        continue;
-                    }
-                    cut(run, i);
-                    run = i + 1;
-                    const txq_dense_op& x = dops[o.dst];
-                    DenseOpPtr& q = out->optr[o.dst];
-                    if (x.kind == TXQ_DENSE_REDUCE) q.dst = slot_of(x.dst);
-                    else { const Session::DenseBlock& b = block_of(x.dst); q.dst = b.p; q.dst_cap = b.cap; }
-                    if (x.kind == TXQ_DENSE_STEP || x.kind == TXQ_DENSE_REDUCE) { const Session::DenseBlock& b = block_of(x.src); q.src = b.p; q.src_cap = b.cap; }
-                    else if (x.kind == TXQ_DENSE_FILL) q.src = slot_of(x.src);
-                    uint64_t shape_entries = 1;
-                    for (uint32_t j = 0; j < bv.dense.pos; ++j) shape_entries *= (uint64_t)__builtin_popcount(x.shape[j]);
-                    if (x.reserved & TXQ_DENSE_TRACKED) {  // work follows the block's live list (FILL: its shape)
-                        const bool fixed = x.kind == TXQ_DENSE_FILL;
-                        if (fixed && !shape_entries) continue;
-                        const bool to_steps = x.kind == TXQ_DENSE_STEP;
-                        (to_steps ? step_level : sparse_level)[l].push_back(SparseGroup{o.dst, fixed ? (uint32_t)shape_entries : kNotFixed});
-                        // most chunks this group can turn out to have: a list never outgrows its block
-                        const uint64_t most = fixed ? shape_entries : x.kind == TXQ_DENSE_ZERO ? q.dst_cap : q.src_cap;
-                        (to_steps ? step_chunks : sparse_chunks)[l] += (size_t)((most + kSparseChunk - 1) / kSparseChunk);
-                        continue;
-                    }
-                    uint64_t entries = 1, per_tile = step_tile;
-                    if (x.kind == TXQ_DENSE_ZERO || x.kind == TXQ_DENSE_FILL) {
-                        per_tile = std::max<uint64_t>(1, 8192 / W);
-                        entries = x.kind == TXQ_DENSE_ZERO && !x.r_mask ? bv.block_slots : shape_entries;
-                    } else {
-                        for (uint32_t j = x.kind == TXQ_DENSE_STEP ? 1 : 0; j < bv.dense.pos; ++j) entries *= (uint64_t)__builtin_popcount(x.shape[j]);
-                        if (x.kind == TXQ_DENSE_STEP) entries *= (uint64_t)__builtin_popcount(x.r_mask) * (__builtin_popcount(x.shape[0]) ? 1 : 0);
-                        else per_tile = 1024;
-                    }
-                    if (x.kind == TXQ_DENSE_STEP) { out->work[0] += entries * (uint64_t)__builtin_popcount(x.shape[0]); out->work[1] += entries; }
-                    else if (x.kind == TXQ_DENSE_REDUCE) out->work[3] += entries;
-                    else out->work[2] += entries;
-                    const bool hstep = hibf && x.kind == TXQ_DENSE_STEP;
-                    if (hstep) per_tile = 256;  // 256 suffixes x up to 32 predecessors: at most 8192 k-mers per tile
-                    if (!hstep) {
-                        if (entries) groups_level[l].push_back(TileGroup{(uint32_t)p, o.dst, (uint32_t)entries, (uint32_t)per_tile, 0});
-                        continue;
-                    }
-                    for (uint64_t at = 0; at < entries; at += per_tile)
-                        hsteps_level[l].push_back(DenseTile{(uint32_t)p, o.dst, (uint32_t)at, (uint32_t)std::min<uint64_t>(per_tile, entries - at)});
-                }
-                cut(run, end);
-            }
-            begin = end;
-        }
-        d.n_ops = 0;  // the per-program kernel skips it
-    }
-    if (bad_program >= 0)
-        return fail(TXQ_ERR_PROGRAM, "program %d: an op on a dense block that no ZERO has created, or beyond its capacity", bad_program);
-    out->levels.resize(per_level.size());
-    for (size_t l = 0; l < per_level.size(); ++l) {
-        out->levels[l].units = per_level[l].size();
-        size_t level_tiles = 0;
-        for (TileGroup& g : groups_level[l]) {
-            g.first_tile = out->n_tiles + level_tiles;
-            level_tiles += (g.entries + g.per_tile - 1) / g.per_tile;
-        }
-        out->levels[l].tiles = level_tiles;
-        out->n_tiles += level_tiles;
-        out->tile_groups.insert(out->tile_groups.end(), groups_level[l].begin(), groups_level[l].end());
-        out->levels[l].hsteps = hsteps_level[l].size();
-        out->levels[l].sparse = sparse_level[l].size() + step_level[l].size();
-        out->levels[l].sparse_misc = sparse_level[l].size();
-        out->levels[l].sparse_chunks = sparse_chunks[l];
-        out->levels[l].step_chunks = step_chunks[l];
-        out->sparse_groups.insert(out->sparse_groups.end(), sparse_level[l].begin(), sparse_level[l].end());
-        out->sparse_groups.insert(out->sparse_groups.end(), step_level[l].begin(), step_level[l].end());
-        out->units.insert(out->units.end(), per_level[l].begin(), per_level[l].end());
-        for (const DenseTile& t : hsteps_level[l]) {
-            out->hsteps.push_back(t);
-            out->hstep_na.push_back((uint32_t)__builtin_popcount(dops[t.op].shape[0]));
-        }
-    }
-    out->n_small = n_small;
-    return TXQ_OK;
-}
-
-// HIBF steps run in chunks of tiles whose masks fit the scratch (2 GiB), never across a level.
-static void chunk_hibf_steps(StagePlan& plan, uint32_t W) {
-    plan.pair_base.assign(plan.hsteps.size(), 0);
-    const uint64_t budget = std::max<uint64_t>(((uint64_t)2 << 30) / ((uint64_t)W * 8), 8192);
-    size_t at = 0;
-    for (const LevelPlan& lp : plan.levels) {
-        uint64_t pairs = 0;
-        for (size_t i = 0; i < lp.hsteps; ++i, ++at) {
-            const uint64_t mine = (uint64_t)plan.hsteps[at].count * plan.hstep_na[at];
-            if (i == 0 || pairs + mine > budget) {
-                plan.chunk_first.push_back(at);
-                plan.chunk_pairs.push_back(0);
-                pairs = 0;
-            }
-            plan.pair_base[at] = (uint32_t)pairs;
-            pairs += mine;
-            plan.chunk_pairs.back() = (uint32_t)pairs;
-        }
-    }
-    for (uint32_t c : plan.chunk_pairs) plan.most_pairs = std::max<size_t>(plan.most_pairs, c);
-    plan.chunk_first.push_back(plan.hsteps.size());
 }
 
 __global__ __launch_bounds__(256) void iota_kernel(uint64_t* __restrict__ v, uint64_t n) {
@@ -2387,8 +1822,8 @@ struct Stage {
     // stage_plan
     StagePlan plan;
     size_t n_sparse_launches = 0;
-    std::vector<uint64_t*> block_table;  // per program with blocks a row [flags | block 0 | its capacity | block 1 | ..] (DenseRow)
-    std::vector<size_t> row_of;
+    std::vector<uint64_t*> block_table;  // per program with blocks a row [flags | block 0 | its capacity | block 1 | ..] (DenseRow) ...
+    std::vector<size_t> row_of;          // ... beginning at row_of[p]
     // stage_upload
     Index::StagingSet* set = nullptr;
     StageTables tables;
@@ -2481,7 +1916,8 @@ static int stage_decide(Stage& g, bool* empty) {
     Index& ix = g.ix;
     BlobView& bv = g.bv;
     g.t0 = now_s();
-    if (int rc = validate_blob(g.blob, g.bytes, s.n_programs, s.kn, &bv)) return rc;
+    if (PlanError e = validate_blob(g.blob, g.bytes, s.n_programs, &bv)) return fail(e.code, "%s", e.text.c_str());
+    bv.dense.nt = (uint32_t)s.kn.dense_nt;
     // (refused here, like everything else that is wrong with a stage: before a region is grown or a kernel launched)
     if (bv.n_aux_kmers && !s.aux) return fail(TXQ_ERR_STATE, "the blob has auxiliary (d-gram) k-mers but the session has no auxiliary index");
     s.t_validate += now_s() - g.t0;
@@ -2502,10 +1938,7 @@ static int stage_decide(Stage& g, bool* empty) {
         }
     }
     g.W = s.W;
-    for (size_t i = 0; i < g.n_q; ++i) {
-        if (g.q_prog[i] >= s.n_programs) return fail(TXQ_ERR_ARG, "feedback query %zu: program out of range", i);
-        if (g.q_slot[i] >= bv.n_slots[g.q_prog[i]]) return fail(TXQ_ERR_ARG, "feedback query %zu: slot out of range", i);
-    }
+    if (PlanError e = check_questions(bv, s.n_programs, g.q_prog, g.q_slot, g.n_q)) return fail(e.code, "%s", e.text.c_str());
     if (g.W == 0 || s.n_programs == 0) {
         for (size_t i = 0; i < g.n_q; ++i) g.alive[i] = 0;
         *empty = true;
@@ -2516,12 +1949,7 @@ static int stage_decide(Stage& g, bool* empty) {
     // Does this stage continue anything the previous stage — possibly still running — works on?  Programs with ops in both,
     // feedback questions, grown regions (moves), an HIBF that is descended or a d-gram index (scratch of the index) tie it
     // to the previous stage's stream; a stage of other programs only (the next wave of queries) runs beside it.
-    g.continues = g.n_q != 0 || (ix.is_hibf && !ix.probes_interleaved(s.kn) && !s.vspace) || s.aux != nullptr;
-    for (size_t p = 0; p < s.n_programs; ++p)
-        if (bv.programs[p].n_ops) {
-            g.continues = g.continues || s.last_stage[p] + 1 == s.n_stages;
-            s.last_stage[p] = (uint32_t)s.n_stages;
-        }
+    g.continues = s.book.continues_previous(bv, s.n_stages) || g.n_q != 0 || (ix.is_hibf && !ix.probes_interleaved(s.kn) && !s.vspace) || s.aux != nullptr;
     g.rows = decide_rows(ix, s, g.table);
     bool any_tracked = false;
     for (size_t p = 0; p < s.n_programs; ++p) any_tracked |= bv.tracked[p] != 0 && bv.has_dense[p] != 0;
@@ -2533,13 +1961,18 @@ static int stage_decide(Stage& g, bool* empty) {
 // Phase 2: every program has its slot region and its dense blocks.
 static int stage_regions(Stage& g) {
     Session& s = g.s;
-    std::vector<std::pair<uint64_t*, size_t>> to_clear;
-    if (int rc = grow_slot_regions(s, g.bv, g.blob, &g.fresh, &g.moves, &to_clear)) return rc;
-    for (const auto& b : to_clear) g.clears.push_back(RegionMove{b.first, nullptr, b.second / 8});
+    // a new chunk of slot or block memory (the session's destructor, or the index it hands them to, frees the chunks)
+    const ChunkAlloc chunk = [&s](bool blocks, size_t words, uint64_t** out) {
+        const double t0 = now_s();
+        const hipError_t e = hipMalloc((void**)out, words * 8);
+        if (e != hipSuccess) return plan_refusal(e == hipErrorOutOfMemory ? TXQ_ERR_NOMEM : TXQ_ERR_HIP, "%s: %s", "hipMalloc((void**)&c, cap * 8)", hipGetErrorString(e));
+        if (blocks) s.block_alloc_seconds += now_s() - t0;
+        return PlanError{};
+    };
+    if (PlanError e = s.book.grow(g.bv, g.blob, g.W, chunk, &g.fresh, &g.moves, &g.clears)) return fail(e.code, "%s", e.text.c_str());
     s.t_grow += now_s() - g.t0;
     g.t_mark[0] = now_s();
-    for (size_t i = 0; i < g.n_q; ++i)
-        if (!s.base[g.q_prog[i]]) return fail(TXQ_ERR_ARG, "feedback query %zu: program %u has not run an op yet", i, g.q_prog[i]);
+    if (PlanError e = s.book.check_questions_ran(g.q_prog, g.n_q)) return fail(e.code, "%s", e.text.c_str());
     if (g.any_dense) s.row_source = g.rows.name;
     return TXQ_OK;
 }
@@ -2548,19 +1981,11 @@ static int stage_regions(Stage& g) {
 static int stage_plan(Stage& g) {
     Session& s = g.s;
     const double t1 = now_s();
-    if (int rc = plan_units(s, g.bv, g.blob, g.W, g.rows.g * g.rows.slices, !g.rows.fused(), &g.plan)) return rc;
+    if (PlanError e = plan_units(s.book, g.bv, g.blob, g.W, g.rows.g * g.rows.slices, s.kn.dense_tile_rounds, !g.rows.fused(), &g.plan))
+        return fail(e.code, "%s", e.text.c_str());
     for (const LevelPlan& lp : g.plan.levels)
         g.n_sparse_launches += (lp.sparse_misc + kMaxSparseGroups - 1) / kMaxSparseGroups + (lp.sparse - lp.sparse_misc + kMaxSparseGroups - 1) / kMaxSparseGroups;
-    g.row_of.assign(s.n_programs, 0);
-    for (size_t p = 0; p < s.n_programs; ++p)
-        if (!s.blocks[p].empty()) {
-            g.row_of[p] = g.block_table.size();
-            g.block_table.push_back(reinterpret_cast<uint64_t*>((uintptr_t)(s.tracked[p] ? 1 : 0)));
-            for (const Session::DenseBlock& b : s.blocks[p]) {
-                g.block_table.push_back(b.p);
-                g.block_table.push_back(reinterpret_cast<uint64_t*>((uintptr_t)b.cap));
-            }
-        }
+    s.book.block_table(&g.block_table, &g.row_of);
     const uint64_t* work = g.plan.work;
     s.n_step_pairs += work[0]; s.n_step_suffixes += work[1]; s.n_zero_slots += work[2]; s.n_reduce_entries += work[3];
     chunk_hibf_steps(g.plan, g.W);
@@ -2583,7 +2008,7 @@ static void stage_tables(Stage& g) {
     T.add(kHsteps, P.hsteps.data(), P.hsteps.size() * sizeof(DenseTile));
     T.add(kPairBase, P.pair_base.data(), P.hsteps.size() * 4);
     T.add(kMoves, g.moves.data(), g.moves.size() * sizeof(RegionMove));
-    T.add(kBase, s.base.data(), 2 * s.n_programs * sizeof(uint64_t*));  // (its second half is filled in once `aux` has its address)
+    T.add(kBase, s.book.base.data(), 2 * s.n_programs * sizeof(uint64_t*));  // (its second half is filled in once `aux` has its address)
     T.add(kOptr, P.optr.data(), P.optr.size() * sizeof(DenseOpPtr));
     T.add(kBlockTable, g.block_table.data(), g.block_table.size() * sizeof(uint64_t*));
     T.add(kSparseGroups, P.sparse_groups.data(), P.sparse_groups.size() * sizeof(SparseGroup));
@@ -2649,7 +2074,7 @@ static int stage_upload(Stage& g) {
     if (int rc = ensure_idle((void**)&S.d_aux, &S.cap_aux, T.bytes + 16)) return rc;
     g.d_blob = T.packed ? g.dev<const unsigned char>(kBlob) : S.d_blob;
     for (size_t p = 0; p < s.n_programs; ++p)  // (the aux buffer has its final address now)
-        s.base[s.n_programs + p] = s.blocks[p].empty() ? nullptr : reinterpret_cast<uint64_t*>(g.dev<uint64_t*>(kBlockTable) + g.row_of[p]);
+        s.book.base[s.n_programs + p] = s.book.blocks[p].empty() ? nullptr : reinterpret_cast<uint64_t*>(g.dev<uint64_t*>(kBlockTable) + g.row_of[p]);
     const size_t nk = g.bv.n_kmers;
     if (int rc = ensure_idle((void**)&S.d_masks, &S.cap_masks, std::max((nk ? nk : 1) * (size_t)g.W * 8, (size_t)16 << 20))) return rc;
     g.d_masks = S.d_masks;

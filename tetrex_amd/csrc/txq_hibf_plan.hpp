@@ -21,14 +21,7 @@
 
 namespace txq {
 
-// why a plan was refused: handed to fail(code, "%s", text)
-struct PlanError {
-    int code = TXQ_OK;
-    std::string text;
-    enum Kind { kNone, kOther, kBadChild, kTwoParents } kind = kNone;  // (the sub-tree entry point words two of them its own way)
-    uint64_t ibf = 0;                                                  // kBadChild / kTwoParents: the child
-    explicit operator bool() const { return code != TXQ_OK; }
-};
+// (PlanError: txq_records.hpp) a refused tree: TXQ_ERR_ARG, which fault, and the IBF it is about
 inline PlanError plan_error(PlanError::Kind kind, uint64_t ibf, const char* fmt, ...) {
     char buf[512];
     va_list ap;

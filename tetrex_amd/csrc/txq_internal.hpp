@@ -2,6 +2,7 @@
 #pragma once
 #include "txq_kernels.hpp"
 #include "txq_records.hpp"
+#include "txq_exec_plan.hpp"
 #include "../../include/txq.h"
 #include <cstdlib>
 #include <map>
@@ -173,7 +174,7 @@ struct Index {
 
     // Device buffers of the last session, kept for the next one: a single query must not pay
     // hipMalloc/hipFree (they cost more than its kernels).  One session at a time may hold them.
-    struct ArenaChunk { uint64_t* p; size_t cap; };  // cap in 64-bit words
+    // (the chunks and dense blocks an index keeps for the next session — ArenaChunk, DenseBlock, BlockBins, BookCache: txq_exec_plan.hpp)
     // What one stage of a session uploads: the blob, and `aux` = program table, lists, units, tiles, region moves and the
     // table of region bases.  A session alternates between two sets, so stage n+1 is uploaded (on its own stream) while
     // the kernels of stage n still read theirs; `done` is recorded behind a stage's last kernel.
@@ -184,50 +185,7 @@ struct Index {
         hipEvent_t done = nullptr;
         bool pending = false;
     };
-    // A dense block as it is handed on: [cap][W] mask words, then its live list.  state: kGarbage (fresh memory, or left by an
-    // untracked program), kListed (left by a tracked program: all zero except the entries in its list, which is intact — the
-    // ZERO that re-creates it for a tracked program clears exactly those, so such a block needs no clearing at all).
-    struct DenseBlock { uint64_t* p; uint32_t cap; uint8_t state; };
-    // blocks by capacity: a handful of capacities (powers of two for tracked blocks, A^(k-1) for untracked ones) with thousands
-    // of blocks each — a vector per capacity (a multimap's node per block made releasing a 10 000-query session 2.5 ms)
-    struct BlockBins {
-        std::vector<std::pair<uint32_t, std::vector<DenseBlock>>> bins;
-        std::vector<DenseBlock>& of(uint32_t cap) {
-            for (auto& b : bins) if (b.first == cap) return b.second;
-            bins.emplace_back(cap, std::vector<DenseBlock>());
-            return bins.back().second;
-        }
-        void put(const DenseBlock& b) { of(b.cap).push_back(b); }
-        bool take(uint32_t cap, DenseBlock* out) {
-            for (auto& b : bins)
-                if (b.first == cap) {
-                    if (b.second.empty()) return false;
-                    *out = b.second.back();
-                    b.second.pop_back();
-                    return true;
-                }
-            return false;
-        }
-        void absorb(BlockBins& other) {  // everything of `other` moves in
-            for (auto& b : other.bins) {
-                std::vector<DenseBlock>& mine = of(b.first);
-                if (mine.empty()) mine.swap(b.second);
-                else { mine.insert(mine.end(), b.second.begin(), b.second.end()); b.second.clear(); }
-            }
-        }
-        void swap(BlockBins& o) { bins.swap(o.bins); }
-        size_t size() const { size_t n = 0; for (const auto& b : bins) n += b.second.size(); return n; }
-        void clear() { bins.clear(); }
-    };
-    struct SessionCache {
-        std::vector<ArenaChunk> chunks;  // slot-arena chunks, at most kArenaKeepBytes in all
-        // dense blocks live in chunks of their own, and ALL blocks of a session go back into a pool by capacity when it ends:
-        // the next batch on this index takes its blocks from there — no allocation, and for tracked programs no clearing
-        // (5.3 GB of memset per 200-motif batch at k = 6 before)
-        std::vector<ArenaChunk> block_chunks;
-        size_t block_cur = 0, block_used = 0;
-        BlockBins blocks;
-        uint32_t blocks_W = 0;  // the mask width the pooled blocks were laid out for
+    struct SessionCache : BookCache {
         StagingSet set[2];
         hipStream_t upload = nullptr, side = nullptr;
         bool in_use = false;
@@ -261,9 +219,6 @@ inline bool index_fuses_tree_steps(const Index& ix, const Knobs& kn) {
            (uint64_t)ix.n_children * ix.child_row_words == ix.shard_words;
 }
 
-// Normalised program descriptor the executor kernel reads (both blob versions map onto it).
-struct DevProgram { uint32_t first_op, n_ops, first_level, n_levels; };
-
 // A batch of programs whose slot masks persist in HBM across stages (txq_exec.hip).
 struct Session {
     Index* ix = nullptr;
@@ -273,31 +228,9 @@ struct Session {
     uint32_t W = 0;        // words of a slot mask: the shard's mask words, or (vspace) the words of a layout-order row
     bool failed = false;   // a stage failed after it may have launched kernels: the device was drained, further stages are refused
     bool vspace = false;   // the index is a general HIBF: masks are rows in layout order, final masks are converted (Index::layout_order)
-    std::vector<Index::ArenaChunk> chunks;  // arena chunks; bump allocation in chunks[cur]
-    size_t cur = 0, chunk_used = 0, arena_words = 0;
-    std::vector<uint64_t*> base;    // [2 * n_programs]: per program its slot region [cap][W], then (device address of) its row of the stage's block table
-    std::vector<uint32_t> cap;      // per program: slots allocated
-    // Dense blocks (include/txq_program.h, version 3): block b of program p is blocks[p][b], an allocation of its own —
-    // [N][W] mask words, then the block's live list (tracked programs): count | bitmap of N bits | list of N entries.
-    // A program that needs more blocks just gets more (nothing ever moves); kernels find a block through the stage's
-    // block table (ordinary ops on dense slots) or through the per-op pointers the host side resolves (DenseOpPtr).
-    // What a block holds when it is handed on: kGarbage (fresh arena memory, or left by an untracked program),
-    // kListed (left by a tracked program: all zero except the entries in its list, which is intact).
-    using DenseBlock = Index::DenseBlock;  // cap: entries ([cap][W] mask words, then the live list)
-    enum : uint8_t { kGarbage = 0, kListed = 1 };
-    std::vector<Index::ArenaChunk> block_chunks;  // the blocks' own arena (bump allocation in block_chunks[bcur]); kept with the index
-    size_t bcur = 0, bused = 0, block_arena_words = 0;
-    Index::BlockBins pool;     // blocks earlier sessions on this index left behind, by capacity
-    std::vector<std::vector<DenseBlock>> blocks;  // per program, by block id (p == nullptr: a tracked block no ZERO has created yet)
-    std::vector<uint8_t> tracked;                 // per program: TXQ_PROGRAM_TRACKED_BIT (fixed with its first block)
-    Index::BlockBins free_blocks;  // blocks of finished programs by capacity, reusable ...
-    // ... two stages after they were given back: the stage before the current one may still be running, on another stream
-    std::vector<DenseBlock> given_back[2];
-    uint32_t block_slots = 0;       // N = A^(k-1) of this session's blobs (0: no dense blob seen yet): the capacity of untracked blocks
-    size_t block_bytes_made = 0;
+    SlotBook book;         // the programs' slot regions and dense blocks (txq_exec_plan.hpp)
     double block_alloc_seconds = 0;  // spent in hipMalloc for block chunks (TXQ_TRACE)
-    size_t n_blocks_live = 0, n_blocks_made = 0, n_block_memsets = 0, n_blocks_relisted = 0, n_sparse_launches = 0, n_sparse_groups = 0;
-    std::vector<uint32_t> last_stage;  // per program: the last stage (1-based) that had ops for it
+    size_t n_block_memsets = 0, n_sparse_launches = 0, n_sparse_groups = 0;
     hipStream_t side = nullptr;        // a stage that continues nothing of the stage in flight runs beside it, on the other stream
     int stream_of_last = 0;            // 0: the caller's stream, 1: `side`
     uint64_t** d_base = nullptr;  // device copy of `base` as of the last stage (lives in that stage's staging set)

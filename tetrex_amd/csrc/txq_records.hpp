@@ -1,7 +1,10 @@
 // The records libtxq.so keeps in HBM for an index, as plain C++: no HIP here, so that the host code which fills them
-// (txq_hibf_plan.hpp) compiles and is tested without a GPU.  The kernels read them through txq_kernels.hpp.
+// (txq_hibf_plan.hpp; a stage's records: txq_exec_plan.hpp) compiles and is tested without a GPU.  The kernels read them through txq_kernels.hpp.
 #pragma once
 #include <stdint.h>
+#include <cstdarg>
+#include <cstdio>
+#include <string>
 #include <vector>
 
 // accessors that kernels call too
@@ -12,6 +15,24 @@
 #endif
 
 namespace txq {
+
+// why the host-side planning of an upload or a stage was refused (txq_hibf_plan.hpp, txq_exec_plan.hpp): handed to
+// fail(code, "%s", text)
+struct PlanError {
+    int code = 0;  // TXQ_OK
+    std::string text;
+    enum Kind { kNone, kOther, kBadChild, kTwoParents } kind = kNone;  // (the sub-tree entry point words two of them its own way)
+    uint64_t ibf = 0;                                                  // kBadChild / kTwoParents: the child
+    explicit operator bool() const { return code != 0; }
+};
+inline PlanError plan_refusal(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return PlanError{code, buf, PlanError::kOther, 0};
+}
 
 struct IbfDev {
     uint64_t* words;      // device pointer, [bin_size][stride]
