@@ -137,6 +137,18 @@ int64_t txh_translate_frame(const char* seq, size_t len, unsigned frame, char* o
 /* the 256-byte residue code table of the peptide encoder of a reduction (what txq_translate takes as `codes`) */
 int txh_peptide_codes(unsigned reduction, uint8_t out[256]);
 
+/* Approximate matching by edit distance on the host (host/edit_distance.hpp): the semantics of txq_edit_search
+ * (include/txq.h, where they are spelled out: class table, Sellers' recurrence, the (distance, record, end) of a pair or
+ * three times 0xFFFFFFFF above the cap) with NO limit on the pattern length.  The CPU twin of the kernel: `tetrex search
+ * --verify` answers patterns longer than TXQ_EDIT_MAX_PATTERN with it, and the kernel is measured against it.  Pattern p is
+ * patterns[pat_offsets[p] .. pat_offsets[p+1]), record r is text[rec_offsets[r] .. rec_offsets[r+1]), group g is records
+ * group_offsets[g] .. group_offsets[g+1] - 1; pairs: 3 u32 each (pattern, group, cap); out: 3 u32 each; the pairs are
+ * dealt over `threads` threads (0: one).  Returns 0, or a negative number (offsets not ascending, a pair out of range, an
+ * empty pattern, null pointers). */
+int txh_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                    size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
+                    const uint8_t* codes, unsigned threads, uint32_t* out);
+
 /* ---- .ibf index files (include/index_base.h:160-202 layout; see host/index_file.hpp) ---- */
 typedef struct txh_index txh_index;
 int txh_index_parse(const void* bytes, size_t n, txh_index** out);

@@ -18,6 +18,7 @@
  *   txq_emplace_device      <- interleaved_bloom_filter::emplace     include/index_ibf.h:94-98 (index build, "next")
  *   txq_count / _device     <- seqan::hibf membership_for(values, threshold) / counting_agent::bulk_count, the general form of
  *                              the one-value, threshold-1 call at include/index_hibf.h:142-147 (`tetrex search`)
+ *   txq_edit_search / _device  (no counterpart: `tetrex search --verify` confirms candidate bins by edit distance)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every function returns 0 on success or a
  * negative txq_status; txq_last_error() gives the message for the calling thread.  Host buffers are
@@ -43,7 +44,7 @@ extern "C" {
 
 /* Environment variables.  Every one selects between code paths that give the SAME results (A/B measurements, tests that
  * run one input through every path); none is needed in production.  They are read at txq_init, txq_index_upload,
- * txq_session_begin, txq_run_programs* and txq_probe* — never while a stage runs — and a session keeps the values it began with.
+ * txq_session_begin, txq_run_programs*, txq_probe* and txq_edit_search* — never while a stage runs — and a session keeps the values it began with.
  *   TXQ_TRACE, TXQ_TRACE_STAGES, TXQ_TRACE_SYNC      timers and per-stage notes on stderr
  *   TXQ_DENSE_TREE=0|1|2                              dense steps on a regular HIBF: generic descent | TreeRows | TreeRowsByLane
  *   TXQ_DENSE_UNROLL, TXQ_DENSE_SLICES, TXQ_DENSE_TILE_ROUNDS, TXQ_DENSE_NT   shape of a dense step's tiles, cache policy of its destination accesses
@@ -58,6 +59,7 @@ extern "C" {
  *   TXQ_HIBF_LAYOUT_ORDER=0, TXQ_HIBF_LAYOUT_FUSED=0, TXQ_HIBF_LANE_HASH, TXQ_HIBF_STEPS_PER_GROUP, TXQ_HIBF_TILE, TXQ_HIBF_UNROLL, TXQ_HIBF_STORE_KIND, TXQ_HIBF_WAVES, TXQ_HIBF_STACK_LDS, TXQ_HIBF_LAYOUT_DIRECT=0
  *                                                     which HIBF descent kernel runs, and its tiling
  *   TXQ_PROBE_BLOCKS_PER_CU, TXQ_PROBE_UNROLL, TXQ_PROBE_NT   grid and variant of the flat probe kernel
+ *   TXQ_EDIT_CHUNK=<bytes>                            bytes of text per lane of the edit-distance kernel (txq_edit_search, below)
  *   TXQ_PROBE_TABLE=0|1                               a flat probe's table of its batch's k-mer domain: never | whenever it fits
  *                                                     (unset: where the batch repeats its values often enough to pay for it)
  * (tests/test_gpu_knobs.py runs a workload under each of them against the oracle.) */
@@ -212,6 +214,42 @@ int txq_translate_device(const uint8_t* d_seq, const uint64_t* d_rec_offsets, si
                          uint64_t* d_values, uint64_t* d_offsets, void* stream);
 int txq_translate(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_records, unsigned k, const uint8_t* codes,
                   uint64_t* values, uint64_t* offsets);
+
+/* Approximate matching of (pattern, bin) pairs by edit distance (`tetrex search --verify`; not in the reference).
+ * Classes: d_codes[256] maps a byte to a class 0..30; any other value (255 by convention) is "matches nothing, not even
+ * itself".  Two bytes match when their classes are equal and below 31.
+ * Distance of a pattern P of m >= 1 bytes to a text record R of n >= 0 bytes, by Sellers' recurrence:
+ *     D[i][0] = i, D[0][j] = 0, D[i][j] = min(D[i-1][j-1] + [P[i-1] and R[j-1] do not match], D[i-1][j] + 1, D[i][j-1] + 1),
+ *     d(P, R) = min over j = 0..n of D[m][j]     (the fewest edits that turn P into a substring of R; never across two records).
+ * Pattern p is d_patterns[d_pat_offsets[p] .. d_pat_offsets[p+1]), record r is d_text[d_rec_offsets[r] .. d_rec_offsets[r+1])
+ * (records back to back: n + 1 ascending offsets each), group g — one bin — is records d_group_offsets[g] ..
+ * d_group_offsets[g+1] - 1.  Pair i is d_pairs[3 i .. 3 i + 2] = (pattern, group, cap e).  With d* the least d(P, R) over the
+ * group's records, d_out[3 i .. 3 i + 2] = (d*, r, j) where d* <= e: r the lowest record index (into d_rec_offsets) that reaches
+ * d*, j the lowest end position in r that reaches it — the number of bytes of r before the match's end, 0 for an empty
+ * match; otherwise (a distance above the cap, a group of no records) all three are 0xFFFFFFFF.  Distances above the cap are
+ * never reported.
+ * Patterns of 1 .. TXQ_EDIT_MAX_PATTERN bytes run on the device (longer ones: txh_edit_search of include/txh.h, the same
+ * semantics on the host).  txq_edit_search checks its host buffers first: m = 0, m > TXQ_EDIT_MAX_PATTERN, a pair that names a
+ * pattern or group out of range, offsets that do not ascend or leave their array, null pointers: TXQ_ERR_ARG, nothing
+ * launched.  txq_edit_search_device cannot read its device buffers without waiting for them, so it returns TXQ_ERR_ARG only
+ * for what it can see (null pointers, the size limits below) and the kernels check the rest: such a pair gets
+ * (0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFE) — a caller that cannot vouch for its buffers looks for 0xFFFFFFFE in the second field —, and with pattern_bytes / text_bytes (the sizes of d_patterns /
+ * d_text) no load leaves a buffer whatever the offsets say.  At most 2^31 pairs, text_bytes + n_records < 2^48.
+ * d_workspace: TXQ_EDIT_WORKSPACE(n_pairs) bytes of device memory, 8-byte aligned, the caller's like every other buffer of
+ * a _device call (it holds a 64-bit key and a unit count per pair while the call runs; its contents mean nothing afterwards).
+ * The call allocates nothing and does not synchronise with the host.
+ *   TXQ_EDIT_CHUNK=<bytes>   the bytes of text one lane owns (default 512, a multiple of 16 in 16 .. 2^20; read at every call).
+ *                            A lane re-reads m + min(e, m) bytes in front of its chunk, 64 chunks are one wave's unit of
+ *                            work; the results do not depend on it (tests use 64 to cut small texts into many units). */
+#define TXQ_EDIT_MAX_PATTERN 512
+#define TXQ_EDIT_WORKSPACE(n_pairs) (16 * (size_t)(n_pairs) + 8)
+int txq_edit_search_device(const uint8_t* d_patterns, const uint64_t* d_pat_offsets, size_t n_patterns, size_t pattern_bytes,
+                           const uint8_t* d_text, const uint64_t* d_rec_offsets, size_t n_records, size_t text_bytes,
+                           const uint64_t* d_group_offsets, size_t n_groups, const uint32_t* d_pairs, size_t n_pairs,
+                           const uint8_t* d_codes, uint32_t* d_out, void* d_workspace, void* stream);
+int txq_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                    size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
+                    const uint8_t* codes, uint32_t* out);  /* host buffers, synchronous */
 
 /* The set bits of a hit matrix (n_queries x words words, as txq_count_device writes it) as a list of (query, bin, count)
  * u32 triples in (query, bin) order: bin = 64 * word + bit — on a column shard the column within the shard —, count =

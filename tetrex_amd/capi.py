@@ -22,7 +22,7 @@ SYMBOLS = [
     "txq_init", "txq_shutdown", "txq_last_error", "txq_device_count",
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
-    "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_hit_list_device",
+    "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
     "txq_malloc", "txq_free", "txq_memcpy_h2d", "txq_memcpy_d2h", "txq_synchronize", "txq_host_alloc", "txq_host_free",
@@ -83,6 +83,10 @@ def lib():
         L.txq_translate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.txq_translate.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_uint, C.c_void_p, u64p, u64p]
         L.txq_hit_list_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.txq_edit_search_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.txq_edit_search.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_void_p]
         L.txq_run_programs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, u64p]
         L.txq_run_programs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         L.txq_session_begin.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
@@ -511,6 +515,42 @@ def translate(records, k, codes):
     check(lib().txq_translate(seq.ctypes.data, rec.ctypes.data_as(u64p), n, k, codes.ctypes.data, values.ctypes.data_as(u64p),
                               offsets.ctypes.data_as(u64p)))
     return values[:int(offsets[-1])], offsets
+
+
+EDIT_MAX_PATTERN = 512
+EDIT_NONE = 0xFFFFFFFF
+
+
+def edit_workspace_bytes(n_pairs):
+    """TXQ_EDIT_WORKSPACE: the device workspace txq_edit_search_device needs for n_pairs pairs"""
+    return 16 * int(n_pairs) + 8
+
+
+def edit_arrays(patterns, records, groups, pairs, codes):
+    """the arguments of edit_search as contiguous arrays: (pattern bytes, offsets, text bytes, offsets, group offsets,
+    pairs (n, 3) uint32, codes)"""
+    pat, po = patterns if isinstance(patterns, tuple) else _records(patterns)
+    txt, ro = records if isinstance(records, tuple) else _records(records)
+    pat, txt = np.ascontiguousarray(pat, dtype=np.uint8), np.ascontiguousarray(txt, dtype=np.uint8)
+    po, ro = np.ascontiguousarray(po, dtype=np.uint64), np.ascontiguousarray(ro, dtype=np.uint64)
+    go = np.ascontiguousarray(groups, dtype=np.uint64)
+    pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 3)
+    cd = np.ascontiguousarray(codes, dtype=np.uint8)
+    if cd.size != 256 or po.size < 1 or ro.size < 1 or go.size < 1 or int(po[-1]) > pat.size or int(ro[-1]) > txt.size:
+        raise TxqError(-1, "edit_search: offsets, bytes and class table disagree")
+    return pat, po, txt, ro, go, pr, cd
+
+
+def edit_search(patterns, records, groups, pairs, codes):
+    """Approximate matching by edit distance on the GPU (txq_edit_search, include/txq.h).  patterns, records: lists of
+    bytes/str, or (uint8 array, uint64 offsets); groups: uint64 offsets into the records (a group is one bin); pairs: rows of
+    (pattern, group, cap); codes: the 256-byte class table.  Returns an (n, 3) uint32 array of (distance, record, end),
+    EDIT_NONE three times where the least distance is above the cap."""
+    pat, po, txt, ro, go, pr, cd = edit_arrays(patterns, records, groups, pairs, codes)
+    out = np.zeros((pr.shape[0], 3), dtype=np.uint32)
+    check(lib().txq_edit_search(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
+                                go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], cd.ctypes.data, out.ctypes.data))
+    return out
 
 
 def hit_list(hits, counts=None, capacity=None, guard=0):

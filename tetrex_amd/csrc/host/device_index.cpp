@@ -1,4 +1,5 @@
 #include "device_index.hpp"
+#include "edit_distance.hpp"
 #include "fasta.hpp"
 #include "kgraph.hpp"
 #include "regex_front.hpp"
@@ -10,6 +11,7 @@
 #include <cstdlib>
 #include <future>
 #include <memory>
+#include <numeric>
 #include <stdexcept>
 
 namespace tetrex {
@@ -729,6 +731,198 @@ void DeviceIndex::search_translated(std::string_view seq, const std::vector<uint
         if (total) txq_check(txq_memcpy_d2h(list.data(), d_list.p, total * 12), "d2h");
         const uint32_t q0 = (uint32_t)(6 * (r1 - nr)), bin0 = (uint32_t)(info_.shard_word0 * 64);
         for (uint64_t i = 0; i < total; ++i) hits.push_back(TranslatedHit{q0 + list[3 * i], bin0 + list[3 * i + 1], list[3 * i + 2]});
+    }
+}
+
+// ---- tetrex search --verify --------------------------------------------------------------------------------------------
+
+BinVerifier::BinVerifier(const std::vector<std::string>& bin_paths, bool dna, uint32_t errors)
+    : paths_(bin_paths), bins_(bin_paths.size()), dna_(dna), errors_(errors) {
+    std::fill(codes_, codes_ + 256, (uint8_t)255);
+    if (dna) {
+        const char* acgt = "ACGT";
+        for (uint8_t c = 0; c < 4; ++c) codes_[(uint8_t)acgt[c]] = codes_[(uint8_t)(acgt[c] | 0x20)] = c;
+        codes_[(uint8_t)'U'] = codes_[(uint8_t)'u'] = 3;
+    } else {
+        for (uint8_t c = 0; c < 26; ++c) codes_[(uint8_t)('A' + c)] = codes_[(uint8_t)('a' + c)] = c;
+    }
+    const char* mb = std::getenv("TETREX_VERIFY_TEXT_MB");
+    const double mib = mb && *mb ? std::atof(mb) : 4096.0;  // (a fraction is allowed: tests bound the cache to one bin)
+    limit_bytes_ = (uint64_t)std::max(1.0, std::min(mib, 1e9) * 1048576.0);
+    txq_check(txq_malloc(&d_codes_, 256), "txq_malloc");
+    txq_check(txq_memcpy_h2d(d_codes_, codes_, 256), "h2d");
+}
+
+BinVerifier::~BinVerifier() {
+    for (Bin& b : bins_) drop(b);
+    if (d_codes_) txq_free(d_codes_);
+}
+
+void BinVerifier::drop(Bin& b) {
+    if (b.d_text) txq_free(b.d_text);  // (waits for the kernels that read it)
+    if (b.d_rec) txq_free(b.d_rec);
+    b.d_text = b.d_rec = nullptr;
+    held_bytes_ -= b.device_bytes;
+    b.device_bytes = 0;
+}
+
+void BinVerifier::read_bin(uint32_t bin, std::string& text, std::vector<uint64_t>& rec, std::vector<std::string>& names) const {
+    text.clear();
+    rec.assign(1, 0);
+    names.clear();
+    try {
+        for_each_record(paths_[bin], [&](const FastaRecord& r) {
+            names.push_back(r.name);
+            text.append(r.seq);
+            rec.push_back(text.size());
+        });
+    } catch (const std::exception& e) {
+        throw std::runtime_error("tetrex search --verify: cannot read bin file " + paths_[bin] + ": " + e.what());
+    }
+}
+
+BinVerifier::Bin& BinVerifier::resident(uint32_t bin) {
+    Bin& b = bins_[bin];
+    b.last_use = ++clock_;
+    if (b.d_rec) return b;
+    std::string text;
+    std::vector<uint64_t> rec;
+    read_bin(bin, text, rec, b.names);
+    const uint64_t n = rec.size() - 1;
+    rec.push_back(0);  // behind the record offsets: the one group's offsets {0, n}
+    rec.push_back(n);
+    const uint64_t bytes = text.size() + 16 + rec.size() * 8;
+    while (held_bytes_ && held_bytes_ + bytes > limit_bytes_) {  // the bin used longest ago leaves
+        Bin* oldest = nullptr;
+        for (Bin& o : bins_)
+            if (o.d_rec && &o != &b && (!oldest || o.last_use < oldest->last_use)) oldest = &o;
+        if (!oldest) break;
+        drop(*oldest);
+    }
+    txq_check(txq_malloc(&b.d_text, text.size() + 16), "txq_malloc");
+    txq_check(txq_malloc(&b.d_rec, rec.size() * 8), "txq_malloc");
+    b.device_bytes = bytes;
+    held_bytes_ += bytes;
+    if (!text.empty()) txq_check(txq_memcpy_h2d(b.d_text, text.data(), text.size()), "h2d");
+    txq_check(txq_memcpy_h2d(b.d_rec, rec.data(), rec.size() * 8), "h2d");
+    b.n_records = n;
+    b.text_bytes = text.size();
+    return b;
+}
+
+void BinVerifier::verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits) {
+    hits.assign(candidates.size(), Hit{});
+    n_candidates_ += candidates.size();
+    if (candidates.empty()) return;
+    const size_t strands = dna_ ? 2 : 1;
+    // the patterns: every record that is a candidate somewhere, and on a nucleotide index its reverse complement behind it
+    constexpr uint32_t kNoPattern = 0xFFFFFFFFu;
+    std::vector<uint32_t> pattern_of(queries.size(), kNoPattern);
+    std::vector<uint64_t> pat_off{0};
+    std::string pat;
+    const auto reverse_complement = [](const std::string& s) {
+        std::string out(s.rbegin(), s.rend());
+        for (char& c : out) switch (c & 0xDF) {
+            case 'A': c = 'T'; break;
+            case 'C': c = 'G'; break;
+            case 'G': c = 'C'; break;
+            case 'T': case 'U': c = 'A'; break;
+            default: c = 'N'; break;  // (no class: matches nothing, as the byte it stands for)
+        }
+        return out;
+    };
+    std::vector<size_t> order(candidates.size()), on_host;
+    std::iota(order.begin(), order.end(), (size_t)0);
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return candidates[x].bin < candidates[y].bin; });
+    std::vector<size_t> on_device;  // candidate of every `strands` pairs, by bin
+    for (size_t i : order) {
+        const uint32_t q = candidates[i].query;
+        const std::string& s = queries.at(q);
+        if (s.empty() || s.size() > TXQ_EDIT_MAX_PATTERN) { on_host.push_back(i); continue; }
+        if (pattern_of[q] == kNoPattern) {
+            pattern_of[q] = (uint32_t)(pat_off.size() - 1);
+            pat.append(s);
+            pat_off.push_back(pat.size());
+            if (dna_) {
+                pat.append(reverse_complement(s));
+                pat_off.push_back(pat.size());
+            }
+        }
+        on_device.push_back(i);
+    }
+    // take the better strand of `strands` results (distance, record, end); + wins on equal distance
+    const auto settle = [&](size_t i, const uint32_t* res, const std::vector<std::string>& names) {
+        Hit& h = hits[i];
+        for (size_t s = 0; s < strands; ++s)
+            if (res[3 * s] != kEditNone && (h.distance == kEditNone || res[3 * s] < h.distance)) {
+                h.distance = res[3 * s];
+                h.target = &names.at(res[3 * s + 1]);
+                h.end = res[3 * s + 2];
+                h.strand = s ? '-' : '+';
+            }
+        if (h.distance != kEditNone) ++n_confirmed_;
+    };
+    if (!on_device.empty()) {
+        std::vector<uint32_t> pairs;
+        pairs.reserve(on_device.size() * strands * 3);
+        for (size_t i : on_device)
+            for (size_t s = 0; s < strands; ++s) {
+                pairs.push_back(pattern_of[candidates[i].query] + (uint32_t)s);
+                pairs.push_back(0);
+                pairs.push_back(errors_);
+            }
+        const size_t n_patterns = pat_off.size() - 1;
+        DevBuf d_pat(pat.size() + 16), d_po(pat_off.size() * 8), d_pairs(pairs.size() * 4), d_out(pairs.size() * 4);
+        DevBuf d_work(TXQ_EDIT_WORKSPACE(pairs.size() / 3) + 8 * on_device.size());  // (every call its own part: they are all in flight at once)
+        size_t n_calls = 0;
+        txq_check(txq_memcpy_h2d(d_pat.p, pat.data(), pat.size()), "h2d");
+        txq_check(txq_memcpy_h2d(d_po.p, pat_off.data(), pat_off.size() * 8), "h2d");
+        txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
+        for (size_t a = 0; a < on_device.size();) {  // one call per bin: its records are one group
+            size_t b = a;
+            const uint32_t bin = candidates[on_device[a]].bin;
+            while (b < on_device.size() && candidates[on_device[b]].bin == bin) ++b;
+            Bin& e = resident(bin);
+            const uint64_t* d_rec = (const uint64_t*)e.d_rec;
+            txq_check(txq_edit_search_device((const uint8_t*)d_pat.p, (const uint64_t*)d_po.p, n_patterns, pat.size(), (const uint8_t*)e.d_text, d_rec,
+                                             e.n_records, e.text_bytes, d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * strands * a,
+                                             (b - a) * strands, (const uint8_t*)d_codes_, (uint32_t*)d_out.p + 3 * strands * a,
+                                             (unsigned char*)d_work.p + 16 * strands * a + 8 * n_calls++, nullptr),
+                      "txq_edit_search_device");
+            a = b;
+        }
+        std::vector<uint32_t> out(pairs.size());
+        txq_check(txq_memcpy_d2h(out.data(), d_out.p, out.size() * 4), "d2h");  // (waits for the kernels)
+        for (size_t k = 0; k < on_device.size(); ++k)
+            settle(on_device[k], out.data() + 3 * strands * k, bins_[candidates[on_device[k]].bin].names);
+    }
+    // records too long for the device: the bin is read once more, the pairs of a bin run side by side
+    for (size_t a = 0; a < on_host.size();) {
+        size_t b = a;
+        const uint32_t bin = candidates[on_host[a]].bin;
+        while (b < on_host.size() && candidates[on_host[b]].bin == bin) ++b;
+        std::string text;
+        std::vector<uint64_t> rec;
+        std::vector<std::string> names;
+        read_bin(bin, text, rec, names);
+        if (bins_[bin].names.empty()) bins_[bin].names = std::move(names);  // (else they are the same, and hits point into them)
+        std::vector<uint32_t> out(3 * strands * (b - a), kEditNone);
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic)
+#endif
+        for (size_t k = a; k < b; ++k) {
+            const std::string& s = queries[candidates[on_host[k]].query];
+            if (s.empty()) continue;
+            for (size_t st = 0; st < strands; ++st) {
+                const std::string p = st ? reverse_complement(s) : s;
+                EditPattern ep((const uint8_t*)p.data(), p.size(), codes_);
+                const EditResult r = edit_search_group(ep, (const uint8_t*)text.data(), rec.data(), 0, rec.size() - 1, errors_);
+                uint32_t* o = out.data() + 3 * (strands * (k - a) + st);
+                o[0] = r.distance, o[1] = r.record, o[2] = r.end;
+            }
+        }
+        for (size_t k = a; k < b; ++k) settle(on_host[k], out.data() + 3 * strands * (k - a), bins_[bin].names);
+        a = b;
     }
 }
 

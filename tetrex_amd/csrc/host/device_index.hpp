@@ -122,6 +122,53 @@ class DeviceIndex {
     KmerEncoder enc_;
 };
 
+// `tetrex search --verify`: candidate (record, bin) pairs confirmed by edit distance on the bins' raw letters
+// (txq_edit_search_device, include/txq.h, where the semantics are).  Comparison is case-insensitive whatever reduction the
+// index uses: on a peptide index every letter is a class of its own, on a nucleotide index A, C, G and T = U are, every
+// other byte matches nothing; a nucleotide record is tried on both strands (its reverse complement is a second pattern, in
+// which an ambiguous byte stays one).  A bin's FASTA (plain or gzip) is read when it is first a candidate; its records go to
+// the device once and stay there for the run, at most TETREX_VERIFY_TEXT_MB MiB of them (default 4096; the bin used longest
+// ago leaves first).  Records longer than TXQ_EDIT_MAX_PATTERN are answered on the host (host/edit_distance.hpp), with
+// OpenMP over the pairs.  Needs txq_init (DeviceIndex::upload).
+class BinVerifier {
+  public:
+    BinVerifier(const std::vector<std::string>& bin_paths, bool dna, uint32_t errors);
+    BinVerifier(const BinVerifier&) = delete;
+    BinVerifier& operator=(const BinVerifier&) = delete;
+    ~BinVerifier();
+    struct Candidate { uint32_t query, bin; };
+    struct Hit {
+        uint32_t distance = 0xFFFFFFFFu;  // 0xFFFFFFFF: not within `errors` of any record of the bin
+        uint32_t end = 0;                 // 1-based position of the match's last letter in the target, 0 for an empty match
+        char strand = '+';                // '-': the reverse complement matched better (on equal distance + wins)
+        const std::string* target = nullptr;  // the target record's name (valid as long as the verifier)
+    };
+    // hits[i] answers candidates[i]; queries[c.query] are the batch's records.  Throws std::runtime_error naming the bin file
+    // that cannot be read.
+    void verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits);
+    size_t n_candidates() const { return n_candidates_; }
+    size_t n_confirmed() const { return n_confirmed_; }
+
+  private:
+    struct Bin {
+        std::vector<std::string> names;  // kept once read
+        void* d_text = nullptr;          // device: the records back to back, their n + 1 offsets, and {0, n}
+        void* d_rec = nullptr;
+        uint64_t n_records = 0, text_bytes = 0, device_bytes = 0, last_use = 0;
+    };
+    Bin& resident(uint32_t bin);  // reads and uploads the bin unless it is on the device
+    void read_bin(uint32_t bin, std::string& text, std::vector<uint64_t>& rec, std::vector<std::string>& names) const;
+    void drop(Bin& b);
+    const std::vector<std::string>& paths_;
+    std::vector<Bin> bins_;
+    bool dna_;
+    uint32_t errors_;
+    uint8_t codes_[256];
+    void* d_codes_ = nullptr;
+    uint64_t limit_bytes_, held_bytes_ = 0, clock_ = 0;
+    size_t n_candidates_ = 0, n_confirmed_ = 0;
+};
+
 // ascending ids of the set bits (compute_set_bins, reference src/query.cpp:40-75)
 std::vector<uint64_t> set_bins(const uint64_t* mask, uint64_t bins);
 

@@ -1,6 +1,7 @@
 // C entry points of the host front-end (include/txh.h).
 #include "../../../include/txh.h"
 #include "compiler.hpp"
+#include "edit_distance.hpp"
 #include "encoder.hpp"
 #include "index_file.hpp"
 #include "kgraph.hpp"
@@ -12,7 +13,9 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <atomic>
 #include <string>
+#include <thread>
 
 using namespace tetrex;
 
@@ -388,6 +391,46 @@ const void* txh_index_serialise(txh_index* ix, size_t* bytes) {
 }
 
 void txh_index_free(txh_index* ix) { delete ix; }
+
+int txh_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                    size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
+                    const uint8_t* codes, unsigned threads, uint32_t* out) {
+    if (!pat_offsets || !rec_offsets || !group_offsets || !codes || (n_pairs && (!pairs || !out))) return fail("null argument");
+    for (size_t p = 0; p < n_patterns; ++p)
+        if (pat_offsets[p + 1] < pat_offsets[p]) return fail("pattern offsets are not ascending");
+    for (size_t r = 0; r < n_records; ++r)
+        if (rec_offsets[r + 1] < rec_offsets[r]) return fail("record offsets are not ascending");
+    for (size_t g = 0; g < n_groups; ++g)
+        if (group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > n_records) return fail("group offsets are not ascending within the records");
+    if ((n_patterns && pat_offsets[n_patterns] > pat_offsets[0] && !patterns) || (n_records && rec_offsets[n_records] > rec_offsets[0] && !text))
+        return fail("null argument");
+    for (size_t i = 0; i < n_pairs; ++i) {
+        const uint32_t p = pairs[3 * i], g = pairs[3 * i + 1];
+        if (p >= n_patterns || g >= n_groups) return fail("pair " + std::to_string(i) + " names a pattern or group out of range");
+        if (pat_offsets[p + 1] == pat_offsets[p]) return fail("pattern " + std::to_string(p) + " is empty");
+    }
+    std::atomic<size_t> next{0};
+    const auto work = [&]() {
+        constexpr size_t kGrain = 16;
+        for (size_t i0; (i0 = next.fetch_add(kGrain)) < n_pairs;)
+            for (size_t i = i0; i < std::min(i0 + kGrain, n_pairs); ++i) {
+                const uint32_t p = pairs[3 * i], g = pairs[3 * i + 1];
+                EditPattern pat(patterns + pat_offsets[p], (size_t)(pat_offsets[p + 1] - pat_offsets[p]), codes);
+                const EditResult r = edit_search_group(pat, text, rec_offsets, group_offsets[g], group_offsets[g + 1], pairs[3 * i + 2]);
+                out[3 * i] = r.distance;
+                out[3 * i + 1] = r.record;
+                out[3 * i + 2] = r.end;
+            }
+    };
+    try {
+        const size_t n_threads = std::max<size_t>(1, std::min<size_t>(threads ? threads : 1, (n_pairs + 15) / 16));
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < n_threads; ++t) pool.emplace_back(work);
+        work();
+        for (std::thread& t : pool) t.join();
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
 
 int txh_hibf_layout(const double* counts, uint64_t user_bins, const double* unions, uint64_t window, const txh_layout_params* params,
                     txh_layout** out) {

@@ -3,9 +3,10 @@
 //     (include/arg_parse.h:57-71, src/main.cpp:36-59, src/query.cpp:477-498)
 //   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] [--layout uniform|sized [--tmax N] [--rearrange [--rearrange-ratio R]]] <name> <libs...>
 //     (include/arg_parse.h:10-38, src/index_base.cpp:73-117)
-//   tetrex search [-e E | --threshold F] [--counts] [--translate] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//   tetrex search [-e E [--verify] | --threshold F] [--counts] [--translate] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (not in the reference: every FASTA record a query, answered by seqan::hibf membership_for(values, threshold);
-//      --translate: nucleotide records on a peptide index, every record's six frames a query of their own)
+//      --translate: nucleotide records on a peptide index, every record's six frames a query of their own;
+//      --verify: only the bins that hold the record within E edits, confirmed on the bins' own letters)
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
 #include "device_index.hpp"
@@ -458,15 +459,20 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
 // bin is reported when at least t of them are in it (txq_count).  -e E: t = max(n - k E, 0) — a record within E edits of a
 // substring of a bin shares at least n - k E k-mer positions with it (q-gram lemma), and a Bloom filter drops none of them,
 // so that bin is always reported.  --threshold F (0 < F <= 1): t = ceil(F n).  Rows: name \t bin path [\t count/n].
+// -e E --verify: the reported bins are candidates; each is confirmed by the edit distance of the record to the
+// bin's records (BinVerifier) and only the bins within E edits are written, with distance \t target \t end [\t strand] appended.
 int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
-                                       {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}};
+                                       {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false}};
     Args a;
     unsigned long long errors = 0;
     double fraction = 0;
     try {
         a = parse(argc, argv, 2, spec);
         if (a.pos.size() != 2) throw std::runtime_error("expected <index> <queries.fa>");
+        if (a.has("verify") && a.has("threshold")) throw std::runtime_error("--verify confirms the bins of -e E: it cannot be combined with --threshold");
+        if (a.has("verify") && a.has("translate")) throw std::runtime_error("--verify cannot be combined with --translate");
+        if (a.has("verify") && !a.has("errors")) throw std::runtime_error("--verify needs -e E: the number of edits a confirmed bin may be away");
         if (a.has("errors") && a.has("threshold")) throw std::runtime_error("-e and --threshold exclude each other");
         if (a.has("errors")) {
             const std::string e = a.get("errors", "");
@@ -520,14 +526,38 @@ int cmd_search(int argc, char** argv) {
     std::vector<uint32_t> thresholds, counts;
     std::vector<uint64_t> hits;
     std::string row;
+    const bool verify = a.has("verify"), dna = enc.molecule() == Molecule::DNA;
+    std::unique_ptr<BinVerifier> verifier;
+    if (verify) verifier = std::make_unique<BinVerifier>(image.bin_paths, dna, (uint32_t)std::min<unsigned long long>(errors, 0xFFFFFFFEull));
+    std::vector<std::string> seqs;  // --verify: the batch's records themselves
+    std::vector<BinVerifier::Candidate> candidates;
+    std::vector<BinVerifier::Hit> confirmed;
     auto flush = [&]() {
         if (names.empty()) return;
         dev.count(values, offsets, thresholds, hits, with_counts ? &counts : nullptr);
-        for (size_t q = 0; q < names.size(); ++q) {
-            for (uint64_t u : set_bins(hits.data() + q * W, bins)) {
+        if (verify) {
+            candidates.clear();
+            for (size_t q = 0; q < names.size(); ++q)
+                for (uint64_t u : set_bins(hits.data() + q * W, bins)) candidates.push_back({(uint32_t)q, (uint32_t)u});
+            verifier->verify(seqs, candidates, confirmed);
+            for (size_t c = 0; c < candidates.size(); ++c) {
+                const BinVerifier::Hit& h = confirmed[c];
+                if (h.distance == 0xFFFFFFFFu) continue;
+                const size_t q = candidates[c].query, u = candidates[c].bin;
                 row.assign(names[q]).append("\t").append(image.bin_paths[u]);
                 if (with_counts) row.append("\t").append(std::to_string(counts[q * W * 64 + u])).append("/").append(std::to_string(n_of[q]));
+                row.append("\t").append(std::to_string(h.distance)).append("\t").append(*h.target).append("\t").append(std::to_string(h.end));
+                if (dna) row.append("\t").append(1, h.strand);
                 out << row << '\n';
+            }
+            seqs.clear();
+        } else {
+            for (size_t q = 0; q < names.size(); ++q) {
+                for (uint64_t u : set_bins(hits.data() + q * W, bins)) {
+                    row.assign(names[q]).append("\t").append(image.bin_paths[u]);
+                    if (with_counts) row.append("\t").append(std::to_string(counts[q * W * 64 + u])).append("/").append(std::to_string(n_of[q]));
+                    out << row << '\n';
+                }
             }
         }
         names.clear();
@@ -551,6 +581,7 @@ int cmd_search(int argc, char** argv) {
         if (t == 0) std::cerr << "[tetrex search] " << r.name << ": threshold 0, every bin is reported" << std::endl;
         if (values.size() + n > max_values || names.size() >= max_queries) flush();
         names.push_back(r.name);
+        if (verify) seqs.push_back(r.seq);
         values.insert(values.end(), v.begin(), v.end());
         offsets.push_back(values.size());
         n_of.push_back(n);
@@ -558,6 +589,7 @@ int cmd_search(int argc, char** argv) {
     });
     flush();
     out.flush();
+    if (verbose && verify) std::cerr << "Verified: " << verifier->n_confirmed() << " of " << verifier->n_candidates() << " candidate pairs" << std::endl;
     if (verbose) std::cerr << "Search time: " << (now() - t_start) << " s" << std::endl;
     return 0;
 }

@@ -283,6 +283,37 @@ def peptide_codes(reduction=0):
     return out
 
 
+def edit_search(patterns, records, groups, pairs, codes, threads=1):
+    """txh_edit_search: approximate matching by edit distance on the host (include/txh.h).  patterns, records: lists of
+    bytes/str, or (uint8 array, uint64 offsets); groups: uint64 offsets into the records; pairs: (n, 3) of (pattern, group,
+    cap); codes: the 256-byte class table.  Returns an (n, 3) uint32 array of (distance, record, end)."""
+    L = lib()
+    L.txh_edit_search.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                  C.c_void_p, C.c_uint, C.c_void_p]
+    pat, po = patterns if isinstance(patterns, tuple) else _byte_records(patterns)
+    txt, ro = records if isinstance(records, tuple) else _byte_records(records)
+    pat, txt = np.ascontiguousarray(pat, dtype=np.uint8), np.ascontiguousarray(txt, dtype=np.uint8)
+    po, ro = np.ascontiguousarray(po, dtype=np.uint64), np.ascontiguousarray(ro, dtype=np.uint64)
+    go = np.ascontiguousarray(groups, dtype=np.uint64)
+    pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 3)
+    cd = np.ascontiguousarray(codes, dtype=np.uint8)
+    if cd.size != 256 or po.size < 1 or ro.size < 1 or go.size < 1 or int(po[-1]) > pat.size or int(ro[-1]) > txt.size:
+        raise HostError("edit_search: offsets, bytes and class table disagree")
+    out = np.zeros((pr.shape[0], 3), dtype=np.uint32)
+    rc = L.txh_edit_search(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
+                           go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], cd.ctypes.data, threads, out.ctypes.data)
+    if rc < 0:
+        raise _err()
+    return out
+
+
+def _byte_records(records):
+    recs = [r.encode() if isinstance(r, str) else bytes(r) for r in records]
+    offsets = np.zeros(len(recs) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(r) for r in recs])
+    return np.frombuffer(b"".join(recs), dtype=np.uint8), offsets
+
+
 def parse_blob(blob):
     """Decode a txq_program.h blob (version 1, 2 or 4): (kmers uint64[], [(n_slots, ops array [n,4] =
     kmer,dst,a,b)]).  Version-2/4 ops are in level order, which is also a valid sequential order.
