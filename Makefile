@@ -9,15 +9,15 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-functi
 ifdef EXPERIMENTS
 HIPFLAGS += -DTXQ_EXPERIMENTS $(EXPERIMENT_FLAGS)
 endif
-HIP_SRCS := $(CSRC)/txq_api.hip $(CSRC)/txq_probe.hip $(CSRC)/txq_hibf.hip $(CSRC)/txq_exec.hip $(CSRC)/txq_build.hip $(CSRC)/txq_count.hip $(CSRC)/txq_translate.hip $(CSRC)/txq_edit.hip
+HIP_SRCS := $(CSRC)/txq_api.hip $(CSRC)/txq_probe.hip $(CSRC)/txq_hibf.hip $(CSRC)/txq_exec.hip $(CSRC)/txq_build.hip $(CSRC)/txq_count.hip $(CSRC)/txq_translate.hip $(CSRC)/txq_edit.hip $(CSRC)/txq_regex.hip
 HIP_OBJS := $(HIP_SRCS:.hip=.o)
-HIP_HDRS := $(wildcard $(CSRC)/*.hpp) include/txq.h include/txq_program.h
+HIP_HDRS := $(wildcard $(CSRC)/*.hpp) include/txq.h include/txq_program.h include/txq_regex.h
 
 HOST_DIR  := $(CSRC)/host
 HOST_SRCS := $(HOST_DIR)/encoder.cpp $(HOST_DIR)/regex_front.cpp $(HOST_DIR)/kgraph.cpp $(HOST_DIR)/compiler.cpp $(HOST_DIR)/staged.cpp $(HOST_DIR)/index_file.cpp $(HOST_DIR)/layout.cpp $(HOST_DIR)/matcher.cpp $(HOST_DIR)/host_capi.cpp
 CLI_SRCS  := $(HOST_DIR)/main.cpp $(HOST_DIR)/device_index.cpp $(HOST_DIR)/verify.cpp $(HOST_DIR)/fasta.cpp
 # (the verification matcher, matcher.cpp, is part of the host library so that tests can reach it through txh_regex_find_all)
-HOST_HDRS := $(wildcard $(HOST_DIR)/*.hpp) include/txh.h include/txq_program.h
+HOST_HDRS := $(wildcard $(HOST_DIR)/*.hpp) include/txh.h include/txq_program.h include/txq_regex.h
 HOSTFLAGS := -O2 -g -std=c++20 -fPIC -Wall -Wextra -pthread
 
 all: tetrex_amd/libtxq.so tetrex_amd/libtetrex_host.so tetrex_amd/libtetrex_query.so bin/tetrex oracle/liboracle.so

@@ -122,6 +122,28 @@ int64_t txh_regex_find_all(const char* pattern, int posix, const char* text, siz
  * automata; may be empty).  Writes at most `cap` bytes, returns the literal's length, < 0 on a syntax error. */
 int64_t txh_regex_required_literal(const char* pattern, int posix, char* out, size_t cap);
 
+/* The pattern as a flat automaton (include/txq_regex.h, where the layout and the semantics are; Matcher::export_dfa): what the
+ * record filter of `tetrex query --gpu-verify` runs.  strand 0: the automaton accepts a record exactly when
+ * txh_regex_find_all reports a match in it.  strand 1: built from the reversed pattern — it accepts T exactly when the
+ * pattern matches reverse(T); with the nucleotide complement as byte_map that is a match on T's reverse complement, found by
+ * scanning T forward.  byte_map (256 bytes, or NULL for the identity) is applied to a text byte before the pattern sees it
+ * and is folded into the automaton's class table.  Returns the blob's bytes (nothing is written where they exceed cap),
+ * 0 where the automaton has more than 65 535 states ("too large": determinisation stops there), < 0 on a syntax error. */
+int64_t txh_regex_automaton(const char* pattern, int posix, int strand, const uint8_t* byte_map, uint8_t* out, size_t cap);
+/* the byte -> letter table of a peptide reduction (0 none, 1 murphy, 2 li): what verification applies to a bin's text on a
+ * reduced index before matching, and what txh_regex_automaton takes as byte_map there */
+int txh_reduce_table(unsigned reduction, uint8_t out[256]);
+/* The host twin of txq_regex_filter_device (include/txq.h, where the arguments are described), on the inline interpreter
+ * of include/txq_regex.h: bit r - group start of the bitmap at out[out_offsets[i]] is set iff the automaton of pair i matches
+ * record r; out[0 .. out_words) is zeroed first; status[i] = 0, or 0xFFFFFFFE for a pair that names an automaton or a group
+ * out of range, offsets that leave their arrays or a malformed blob (such a pair sets no bit).  max_serial: 0, or
+ * TXQ_REGEX_MAX_SERIAL — a record longer than that is flagged without being scanned where the automaton is unbounded, as
+ * the device does it.  Returns 0, or a negative number for null pointers. */
+int txh_regex_filter(const uint8_t* automata, const uint64_t* auto_offsets, size_t n_automata, size_t automata_bytes, const uint8_t* text,
+                     const uint64_t* rec_offsets, size_t n_records, size_t text_bytes, const uint64_t* group_offsets, size_t n_groups,
+                     const uint32_t* pairs, size_t n_pairs, const uint64_t* out_offsets, uint32_t* out, size_t out_words, uint64_t max_serial,
+                     uint32_t* status);
+
 /* values inserted for one record; returns the count (may exceed cap; nothing written past cap) */
 int64_t txh_record_values(int dna, unsigned k, unsigned reduction, const char* seq, size_t len, int wraparound,
                           uint64_t* out, size_t cap);

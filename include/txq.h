@@ -251,6 +251,42 @@ int txq_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t
                     size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
                     const uint8_t* codes, uint32_t* out);  /* host buffers, synchronous */
 
+/* Which records of a bin does a regular expression match?  (`tetrex query --gpu-verify`; not in the reference.)
+ * An automaton is a blob of include/txq_regex.h, where its layout and the meaning of "matches" are stated (as code: the
+ * kernel, the host twin txh_regex_filter of include/txh.h and the tests run the same inline interpreter).  Automaton p is
+ * d_automata[d_auto_offsets[p] .. d_auto_offsets[p+1]) — n + 1 ascending offsets, each a multiple of 16, d_automata itself
+ * 16-byte aligned —, record r is d_text[d_rec_offsets[r] .. d_rec_offsets[r+1]) (records back to back), group g — one bin — is
+ * records d_group_offsets[g] .. d_group_offsets[g+1] - 1.  Pair i is d_pairs[2 i .. 2 i + 1] = (automaton, group).  Its answer
+ * is a bitmap of ceil(records of the group / 32) u32 words at d_out[d_out_offsets[i]]: bit j of word w is set iff the
+ * automaton matches record d_group_offsets[g] + 32 w + j.  The call zeroes d_out[0 .. out_words) itself (bitmaps may not
+ * overlap), and d_status[i] = 0 where pair i was answered, TXQ_REGEX_REFUSED where it was not: an automaton or a group out
+ * of range, offsets that leave their arrays (automata_bytes / text_bytes / n_records / out_words are the sizes), an automaton
+ * that is not 16-byte aligned or whose header is malformed.  A refused pair sets no bit; whatever the buffers hold, no load
+ * leaves them (a class or a transition outside an automaton's tables reads as the dead state).
+ * An automaton whose lmax is TXQ_REGEX_UNBOUNDED is run over a record by ONE lane, so a record of more than
+ * TXQ_REGEX_MAX_SERIAL bytes is flagged without being looked at: a set bit then means "matches, or too long to tell", which
+ * is what a caller that confirms flagged records on the host needs.  Bounded automata are exact at any record length.
+ * txq_regex_filter checks its host buffers first (offsets that do not ascend, pairs out of range, malformed automata, every
+ * table entry, bitmaps outside the output, null pointers: TXQ_ERR_ARG, nothing launched).  txq_regex_filter_device returns
+ * TXQ_ERR_ARG only for what it can see (null pointers, alignment, more than 2^31 pairs or 2^32 - 2 records) and the kernels check
+ * the rest.  d_workspace: TXQ_REGEX_WORKSPACE(n_pairs) bytes of device memory, 8-byte aligned, the caller's (a unit count per
+ * pair while the call runs).  The call allocates nothing and does not synchronise with the host.
+ *   TXQ_REGEX_CHUNK=<bytes>       the bytes of text one lane owns (default 256, a multiple of 16 in 16 .. 2^20; read at every
+ *                                 call).  256 chunks are one workgroup's unit of work, for which it loads the automaton into
+ *                                 LDS once; a lane re-reads lmax - 1 bytes in front of its chunk.  The results do not depend
+ *                                 on it (tests use 16).
+ *   TXQ_REGEX_MAX_SERIAL=<bytes>  the longest record an unbounded automaton is run over (default 65536; read at every call). */
+#define TXQ_REGEX_REFUSED 0xFFFFFFFEu
+#define TXQ_REGEX_WORKSPACE(n_pairs) (8 * (size_t)(n_pairs) + 8)
+int txq_regex_filter_device(const uint8_t* d_automata, const uint64_t* d_auto_offsets, size_t n_automata, size_t automata_bytes,
+                            const uint8_t* d_text, const uint64_t* d_rec_offsets, size_t n_records, size_t text_bytes,
+                            const uint64_t* d_group_offsets, size_t n_groups, const uint32_t* d_pairs, size_t n_pairs,
+                            const uint64_t* d_out_offsets, uint32_t* d_out, size_t out_words, uint32_t* d_status, void* d_workspace,
+                            void* stream);
+int txq_regex_filter(const uint8_t* automata, const uint64_t* auto_offsets, size_t n_automata, const uint8_t* text, const uint64_t* rec_offsets,
+                     size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
+                     const uint64_t* out_offsets, uint32_t* out, size_t out_words, uint32_t* status);  /* host buffers, synchronous */
+
 /* The set bits of a hit matrix (n_queries x words words, as txq_count_device writes it) as a list of (query, bin, count)
  * u32 triples in (query, bin) order: bin = 64 * word + bit — on a column shard the column within the shard —, count =
  * d_counts[query * 64 * words + bin], or 0 where d_counts is NULL.  *d_total receives the number of set bits whatever

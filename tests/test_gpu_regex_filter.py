@@ -1,0 +1,149 @@
+"""GPU parity of the record filter (include/txq.h txq_regex_filter): capi.regex_filter against the host twin
+host.regex_filter — the same automaton blobs through the same inline interpreter — bit for bit, with TXQ_REGEX_CHUNK=16 and
+with the default chunk."""
+import numpy as np
+import pytest
+
+from tetrex_amd import host
+
+pytestmark = pytest.mark.gpu
+
+MOTIFS = ["(LMAEGLYN)", "(^M.K)", "(GT$)", "(A(C+|G+)T)", "(A.{12}C)", "(C.{2,4}C.{3}[LIVMFYWC])", "(A|)", "(^MAEG$)"]
+INSTANCE = ["LMAEGLYN", "MWK", "GT", "ACCCT", "AWWWWWWWWWWWWC", "CWWCWWWL", "", "MAEG"]
+LDS, L2 = 0, 4  # a small automaton and the one above 64 KiB
+BOUNDARY = 256  # a multiple of both chunks the tests run
+
+
+@pytest.fixture(scope="module")
+def capi():
+    from tetrex_amd import capi as c
+    c.init(0)
+    return c
+
+
+@pytest.fixture(scope="module")
+def automata():
+    blobs = [host.regex_automaton(rx, True) for rx in MOTIFS]
+    assert len(blobs[L2]) > 65536 and all(len(b) <= 8192 for i, b in enumerate(blobs) if i != L2)
+    return blobs
+
+
+@pytest.fixture(scope="module")
+def case(automata):
+    """records, groups, pairs and the host twin's answer, computed once.  Filler letters occur in no motif, so a record matches
+    only what was planted in it."""
+    rng = np.random.default_rng(5)
+    filler = lambda n: "".join(rng.choice(list("WYQ"), size=n)) if n else ""
+    recs, expect = [], {}  # expect[(automaton, record)] = the answer the construction intends
+    size = lambda: sum(len(r) for r in recs)
+
+    def planted(a, tail_at):
+        """a record with INSTANCE[a] in it, the instance's last byte at text offset = tail_at modulo BOUNDARY"""
+        inst = INSTANCE[a]
+        lead = (tail_at - (size() + len(inst) - 1)) % BOUNDARY
+        recs.append(filler(lead) + inst + filler(7))
+        expect[(a, len(recs) - 1)] = True
+
+    # group 0: matches that straddle a chunk boundary, end exactly on one, begin exactly on one
+    for a in (0, 3, 4, 5):
+        planted(a, len(INSTANCE[a]) // 2 - 1)          # the boundary in the middle of the match
+        planted(a, BOUNDARY - 1)                       # the match's last byte is a chunk's last byte
+        planted(a, len(INSTANCE[a]) - 1)               # its first byte is a chunk's first byte
+        planted(a, 17 + len(INSTANCE[a]) // 2 - 1)     # the same at a 16-byte boundary that is no 256-byte boundary
+        planted(a, 15)
+    # `^` at a record start that is no chunk start, `$` at a record end in mid-chunk; and the same letters where they must not match
+    recs.append(filler((5 - size()) % 16))  # the next record starts 5 bytes behind a 16-byte boundary and ends 2 in front of one
+    recs.append("MWK" + filler(20) + "GT"); expect[(1, len(recs) - 1)] = True; expect[(2, len(recs) - 1)] = True
+    recs.append("W" + "MWK" + filler(9) + "GT" + "W"); expect[(1, len(recs) - 1)] = False; expect[(2, len(recs) - 1)] = False
+    recs.append("MAEG"); expect[(7, len(recs) - 1)] = True
+    recs.append("MAEGW"); expect[(7, len(recs) - 1)] = False
+    # records of 0, 1, 15, 16, 17 and about 5 000 bytes
+    for n in (0, 1, 15, 16, 17):
+        recs.append(filler(n)); expect[(6, len(recs) - 1)] = True; expect[(0, len(recs) - 1)] = False
+    long = filler(5003)
+    recs.append(long[:3000] + "LMAEGLYN" + long[3000:]); expect[(0, len(recs) - 1)] = True; expect[(4, len(recs) - 1)] = False
+    recs.append(long[:4990] + "AWWWWWWWWWWWWC"); expect[(4, len(recs) - 1)] = True; expect[(0, len(recs) - 1)] = False
+    recs.append(long); expect[(0, len(recs) - 1)] = False
+    n0 = len(recs)
+    # group 1: no records.  group 2: 70 records, a bitmap of three words
+    for i in range(70):
+        body = filler(int(rng.integers(0, 60)))
+        if i % 3 == 0:
+            a = int(rng.integers(len(MOTIFS)))
+            body = (INSTANCE[a] + body) if a in (1, 7) and i % 2 else body[:len(body) // 2] + INSTANCE[a] + body[len(body) // 2:]
+        recs.append(body)
+    recs.append(filler(11))  # group 3: one record; the text's size is no multiple of 16
+    groups = [0, n0, n0, n0 + 70, n0 + 71]
+    recs = [r.encode() for r in recs]
+    assert sum(len(r) for r in recs) % 16 != 0 and sum(len(r) for r in recs) < 1_000_000
+    # every automaton on groups 0 and 2 (several pairs on one group, one automaton on several groups), some on the others
+    pairs = [(a, g) for g in (0, 2) for a in range(len(MOTIFS))] + [(LDS, 1), (L2, 1), (LDS, 3), (L2, 3), (3, 3)]
+    want = host.regex_filter(automata, recs, groups, pairs)
+    for (a, r), answer in expect.items():
+        assert want[pairs.index((a, 0))][r] == answer, (MOTIFS[a], r, recs[r][:40])
+    assert len(want[pairs.index((LDS, 2))]) == 70 and want[pairs.index((LDS, 1))].size == 0
+    return recs, groups, pairs, want
+
+
+def _same(got, want):
+    assert len(got) == len(want)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g.tolist() == w.tolist(), (i, np.flatnonzero(g != w)[:8].tolist() if g.size == w.size else (g.size, w.size))
+
+
+@pytest.mark.parametrize("chunk", [None, "16"])
+def test_parity_with_host_twin(capi, automata, case, monkeypatch, chunk):
+    """bounded matches across, at and behind chunk boundaries; ^ and $ off the boundaries; records of 0, 1, 15, 16, 17 and 5 000
+    bytes; groups of 0, 1 and 70 records; a text whose size is no multiple of 16; both table tiers in one call"""
+    if chunk:
+        monkeypatch.setenv("TXQ_REGEX_CHUNK", chunk)
+    recs, groups, pairs, want = case
+    got, status = capi.regex_filter(automata, recs, groups, pairs, return_status=True)
+    assert status.tolist() == [0] * len(pairs)
+    _same(got, want)
+
+
+@pytest.mark.parametrize("chunk", [None, "16"])
+def test_unbounded_automaton_and_serial_cap(capi, automata, monkeypatch, chunk):
+    """A(C+|G+)T with TXQ_REGEX_MAX_SERIAL=256: a record of 300 bytes is flagged whether or not it holds a match, records of
+    255 and 256 bytes are answered exactly; the bounded automaton beside it does not know the cap"""
+    monkeypatch.setenv("TXQ_REGEX_MAX_SERIAL", "256")
+    if chunk:
+        monkeypatch.setenv("TXQ_REGEX_CHUNK", chunk)
+    recs = []
+    for n in (255, 256, 300):
+        recs += [b"W" * n, b"W" * (n - 9) + b"AGGGGGGGT", b"ACT" + b"W" * (n - 3), b"W" * (n - 120) + b"A" + b"C" * 118 + b"T"]
+    recs.append(b"W" * 290 + b"LMAEGLYN" + b"WW")
+    pairs = [(3, 0), (LDS, 0)]
+    want = host.regex_filter(automata, recs, [0, len(recs)], pairs, max_serial=256)
+    assert want[0].tolist() == [False, True, True, True] * 2 + [True] * 5 and want[1].tolist() == [False] * 12 + [True]
+    _same(capi.regex_filter(automata, recs, [0, len(recs)], pairs), want)
+
+
+def test_refused_pairs_leave_their_neighbours_alone(capi, automata, case):
+    """a pair that names an automaton or a group out of range, and an automaton with a broken header: status
+    TXQ_REGEX_REFUSED, no bit set, the pairs around them answered.  (The kernels check every offset against the sizes passed
+    before they use it.)"""
+    recs, groups, _, _ = case
+    broken = bytearray(automata[1])
+    broken[8] = 0  # no classes
+    blobs = [automata[LDS], bytes(broken), automata[L2]]
+    pairs = [(0, 0), (3, 0), (2, 2), (0, 9), (1, 0), (0, 2), (0xFFFFFFFF, 0xFFFFFFFF), (2, 3)]
+    want, want_status = host.regex_filter(blobs, recs, groups, pairs, return_status=True)
+    R = capi.REGEX_REFUSED
+    assert want_status.tolist() == [0, R, 0, R, R, 0, R, 0]
+    got, status = capi.regex_filter(blobs, recs, groups, pairs, validate=False, return_status=True)
+    assert status.tolist() == want_status.tolist()
+    _same(got, want)
+    with pytest.raises(capi.TxqError):  # the host-buffer call checks first and launches nothing
+        capi.regex_filter(blobs, recs, groups, pairs)
+    with pytest.raises(capi.TxqError):
+        capi.regex_filter([automata[LDS]], recs, groups, [(0, 9)])
+
+
+def test_no_pairs_and_no_records(capi, automata):
+    assert capi.regex_filter(automata, [b"ACGT"], [0, 1], []) == []
+    got = capi.regex_filter(automata, [], [0, 0], [(6, 0)])
+    assert got[0].size == 0
+    got = capi.regex_filter(automata, [b"", b"", b"MWK"], [0, 2, 3], [(6, 0), (0, 0), (1, 1)])  # a group of empty records only
+    assert [g.tolist() for g in got] == [[True, True], [False, False], [True]]

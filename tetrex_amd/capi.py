@@ -23,6 +23,7 @@ SYMBOLS = [
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
     "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
+    "txq_regex_filter", "txq_regex_filter_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
     "txq_malloc", "txq_free", "txq_memcpy_h2d", "txq_memcpy_d2h", "txq_synchronize", "txq_host_alloc", "txq_host_free",
@@ -87,6 +88,11 @@ def lib():
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.txq_edit_search.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.c_void_p, C.c_void_p]
+        L.txq_regex_filter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
+        L.txq_regex_filter.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                       u64p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.txq_run_programs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, u64p]
         L.txq_run_programs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         L.txq_session_begin.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
@@ -551,6 +557,48 @@ def edit_search(patterns, records, groups, pairs, codes):
     check(lib().txq_edit_search(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
                                 go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], cd.ctypes.data, out.ctypes.data))
     return out
+
+
+REGEX_REFUSED = 0xFFFFFFFE
+
+
+def regex_workspace_bytes(n_pairs):
+    """TXQ_REGEX_WORKSPACE: the device workspace txq_regex_filter_device needs for n_pairs pairs"""
+    return 8 * int(n_pairs) + 8
+
+
+def regex_filter(automata, records, groups, pairs, validate=True, return_status=False):
+    """Which records of a group does an automaton match, on the GPU (txq_regex_filter, include/txq.h)?  automata: blobs of
+    host.regex_automaton (include/txq_regex.h), or (uint8 arena, uint64 offsets); records: list of bytes/str, or (uint8 array,
+    uint64 offsets); groups: uint64 offsets into the records (a group is one bin); pairs: rows of (automaton, group).
+    Returns one boolean array per pair over its group's records (empty for a refused pair), and the status array if asked
+    for.  validate=False: the buffers go to the device unchecked and txq_regex_filter_device answers — a pair it cannot
+    answer gets REGEX_REFUSED — where txq_regex_filter would refuse the whole call."""
+    from . import host as H
+    arena, ao, txt, ro, go, pr, oo, n_words = H.regex_filter_arrays(automata, records, groups, pairs)
+    n = pr.shape[0]
+    out = np.zeros(max(1, n_words), dtype=np.uint32)
+    status = np.zeros(max(1, n), dtype=np.uint32)
+    if validate:
+        check(lib().txq_regex_filter(arena.ctypes.data, ao.ctypes.data_as(u64p), ao.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
+                                     go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, n, oo.ctypes.data_as(u64p), out.ctypes.data, n_words,
+                                     status.ctypes.data))
+    else:
+        pad = lambda a: a if a.size else np.zeros(1, dtype=a.dtype)
+        bufs = [DeviceBuffer.from_numpy(pad(x)) for x in (arena, ao, txt, ro, go, pr, oo)]
+        d_out, d_status, d_work = DeviceBuffer(out.nbytes), DeviceBuffer(status.nbytes), DeviceBuffer(regex_workspace_bytes(n))
+        try:
+            check(lib().txq_regex_filter_device(bufs[0].ptr, bufs[1].ptr, ao.size - 1, arena.size, bufs[2].ptr, bufs[3].ptr, ro.size - 1, txt.size,
+                                                bufs[4].ptr, go.size - 1, bufs[5].ptr, n, bufs[6].ptr, d_out.ptr, n_words, d_status.ptr, d_work.ptr,
+                                                None))
+            out = d_out.to_numpy(np.uint32, out.shape)  # (waits for the kernels)
+            status = d_status.to_numpy(np.uint32, status.shape)
+        finally:
+            for b in bufs + [d_out, d_status, d_work]:
+                b.free()
+    status = status[:n]
+    res = H.regex_filter_unpack(go, pr, oo, out, status)
+    return (res, status) if return_status else res
 
 
 def hit_list(hits, counts=None, capacity=None, guard=0):

@@ -7,6 +7,7 @@
 #include "encoder.hpp"
 #include "index_file.hpp"
 #include "layout.hpp"
+#include "verify.hpp"
 #include "../../../include/txq.h"
 
 #include <functional>
@@ -122,13 +123,47 @@ class DeviceIndex {
     KmerEncoder enc_;
 };
 
+// The records of bins' FASTA files, resident on the device: what `tetrex search --verify` and `tetrex query --gpu-verify` run
+// their kernels over.  A bin's file (plain or gzip) is read when it is first asked for; its records go to the device once —
+// the bytes back to back, their n + 1 offsets, and behind those the offsets {0, n} of the one group they form — and stay
+// there, at most TETREX_VERIFY_TEXT_MB MiB of them (default 4096; the bin used longest ago leaves first; a fraction is
+// allowed).  Needs txq_init (DeviceIndex::upload).
+class ResidentBins {
+  public:
+    // `who` begins the message of the std::runtime_error that names a bin file which cannot be read
+    ResidentBins(const std::vector<std::string>& bin_paths, std::string who);
+    ResidentBins(const ResidentBins&) = delete;
+    ResidentBins& operator=(const ResidentBins&) = delete;
+    ~ResidentBins();
+    struct Bin {
+        std::vector<std::string> names;  // kept once read
+        void* d_text = nullptr;          // device: the records back to back, their n + 1 offsets, and {0, n}
+        void* d_rec = nullptr;
+        uint64_t n_records = 0, text_bytes = 0, device_bytes = 0, last_use = 0;
+    };
+    // the bin's records as the device gets them (rec: n + 1 offsets)
+    void read(uint32_t bin, std::string& text, std::vector<uint64_t>& rec, std::vector<std::string>& names) const;
+    Bin& resident(uint32_t bin);  // reads and uploads the bin unless it is on the device
+    // the same with the file already read (text, rec, names as read() gives them; names are moved from)
+    Bin& resident(uint32_t bin, const std::string& text, std::vector<uint64_t>& rec, std::vector<std::string>& names);
+    bool is_resident(uint32_t bin) const { return bins_[bin].d_rec != nullptr; }
+    Bin& at(uint32_t bin) { return bins_[bin]; }
+    size_t size() const { return bins_.size(); }
+
+  private:
+    void drop(Bin& b);
+    const std::vector<std::string>& paths_;
+    std::string who_;
+    std::vector<Bin> bins_;
+    uint64_t limit_bytes_, held_bytes_ = 0, clock_ = 0;
+};
+
 // `tetrex search --verify`: candidate (record, bin) pairs confirmed by edit distance on the bins' raw letters
 // (txq_edit_search_device, include/txq.h, where the semantics are).  Comparison is case-insensitive whatever reduction the
 // index uses: on a peptide index every letter is a class of its own, on a nucleotide index A, C, G and T = U are, every
 // other byte matches nothing; a nucleotide record is tried on both strands (its reverse complement is a second pattern, in
-// which an ambiguous byte stays one).  A bin's FASTA (plain or gzip) is read when it is first a candidate; its records go to
-// the device once and stay there for the run, at most TETREX_VERIFY_TEXT_MB MiB of them (default 4096; the bin used longest
-// ago leaves first).  Records longer than TXQ_EDIT_MAX_PATTERN are answered on the host (host/edit_distance.hpp), with
+// which an ambiguous byte stays one).  A bin's FASTA is read when it is first a candidate and its records stay on the device
+// (ResidentBins).  Records longer than TXQ_EDIT_MAX_PATTERN are answered on the host (host/edit_distance.hpp), with
 // OpenMP over the pairs.  Needs txq_init (DeviceIndex::upload).
 class BinVerifier {
   public:
@@ -150,23 +185,39 @@ class BinVerifier {
     size_t n_confirmed() const { return n_confirmed_; }
 
   private:
-    struct Bin {
-        std::vector<std::string> names;  // kept once read
-        void* d_text = nullptr;          // device: the records back to back, their n + 1 offsets, and {0, n}
-        void* d_rec = nullptr;
-        uint64_t n_records = 0, text_bytes = 0, device_bytes = 0, last_use = 0;
-    };
-    Bin& resident(uint32_t bin);  // reads and uploads the bin unless it is on the device
-    void read_bin(uint32_t bin, std::string& text, std::vector<uint64_t>& rec, std::vector<std::string>& names) const;
-    void drop(Bin& b);
-    const std::vector<std::string>& paths_;
-    std::vector<Bin> bins_;
+    ResidentBins bins_;
     bool dna_;
     uint32_t errors_;
     uint8_t codes_[256];
     void* d_codes_ = nullptr;
-    uint64_t limit_bytes_, held_bytes_ = 0, clock_ = 0;
     size_t n_candidates_ = 0, n_confirmed_ = 0;
+};
+
+// `tetrex query --gpu-verify`: which records of its candidate bins does a motif match at all?  Answered on the
+// device (txq_regex_filter_device, include/txq.h) for a batch of motifs and their candidate masks, so that verification runs
+// the matcher's find_all on those records only.  Each motif is exported once as an automaton (Matcher::export_dfa: the pattern
+// as verification hands it to the matcher, the index's reduction folded into the class table; on a nucleotide index a second
+// automaton for the reverse strand, the complement folded in), candidate bins become resident (ResidentBins), one filter call
+// per bin is queued and the bitmaps come back once per block of bins.  A motif whose automaton is too large, and a pair the
+// device refused, are not in the selection: verification takes them the way it does without the flag.  Needs txq_init.
+class RecordFilter {
+  public:
+    RecordFilter(const std::vector<std::string>& bin_paths, const KmerEncoder& enc, int threads);
+    struct Stats {
+        uint64_t pairs_device = 0, pairs_host = 0;         // (motif, bin) pairs answered by the device / left to the host
+        uint64_t records_flagged = 0, records_total = 0;   // over the device's pairs and strands
+        uint64_t automata_lds = 0, automata_l2 = 0, automata_host = 0;  // automata by table tier; motifs too large to export
+        double export_seconds = 0, upload_seconds = 0, filter_seconds = 0, copy_seconds = 0;
+    };
+    // masks[q]: the candidate-bin mask of motif q (nullptr: skipped); the selection receives every pair the device answered
+    void run(const std::vector<const uint64_t*>& masks, uint64_t bins, const std::vector<std::string>& regexes, RecordSelection& out);
+    const Stats& stats() const { return stats_; }
+
+  private:
+    ResidentBins bins_;
+    KmerEncoder enc_;
+    int threads_;
+    Stats stats_;
 };
 
 // ascending ids of the set bits (compute_set_bins, reference src/query.cpp:40-75)

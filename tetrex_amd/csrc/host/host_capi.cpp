@@ -1,5 +1,6 @@
 // C entry points of the host front-end (include/txh.h).
 #include "../../../include/txh.h"
+#include "../../../include/txq_regex.h"
 #include "compiler.hpp"
 #include "edit_distance.hpp"
 #include "encoder.hpp"
@@ -241,6 +242,58 @@ int64_t txh_regex_required_literal(const char* pattern, int posix, char* out, si
         for (size_t i = 0; i < lit.size() && i < cap; ++i) out[i] = lit[i];
         return (int64_t)lit.size();
     } catch (const std::exception& e) { return fail(e.what()); }
+}
+
+int64_t txh_regex_automaton(const char* pattern, int posix, int strand, const uint8_t* byte_map, uint8_t* out, size_t cap) {
+    try {
+        const Matcher m(pattern, posix ? Matcher::Semantics::LeftmostLongest : Matcher::Semantics::LeftmostFirst);
+        std::vector<uint8_t> blob;
+        if (!m.export_dfa(strand != 0, byte_map, blob)) return 0;
+        if (blob.size() <= cap && out) std::memcpy(out, blob.data(), blob.size());
+        return (int64_t)blob.size();
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+
+int txh_reduce_table(unsigned reduction, uint8_t out[256]) {
+    try {
+        const KmerEncoder enc = encoder(0, 6, reduction);
+        for (unsigned b = 0; b < 256; ++b) out[b] = (uint8_t)enc.reduce((unsigned char)b);
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+
+int txh_regex_filter(const uint8_t* automata, const uint64_t* auto_offsets, size_t n_automata, size_t automata_bytes, const uint8_t* text,
+                     const uint64_t* rec_offsets, size_t n_records, size_t text_bytes, const uint64_t* group_offsets, size_t n_groups,
+                     const uint32_t* pairs, size_t n_pairs, const uint64_t* out_offsets, uint32_t* out, size_t out_words, uint64_t max_serial,
+                     uint32_t* status) {
+    if (!auto_offsets || !rec_offsets || !group_offsets || (n_pairs && (!pairs || !out_offsets || !status)) || (out_words && !out) ||
+        (automata_bytes && !automata) || (text_bytes && !text))
+        return fail("null argument");
+    std::fill(out, out + out_words, 0u);
+    for (size_t i = 0; i < n_pairs; ++i) {
+        status[i] = 0xFFFFFFFEu;  // TXQ_REGEX_REFUSED of include/txq.h
+        const uint32_t a = pairs[2 * i], g = pairs[2 * i + 1];
+        if (a >= n_automata || g >= n_groups) continue;
+        const uint64_t a0 = auto_offsets[a], a1 = auto_offsets[a + 1];
+        if (a0 > a1 || a1 > automata_bytes || (a0 & 15)) continue;
+        txq_regex_view v;
+        if (!txq_regex_open(automata + a0, (size_t)(a1 - a0), &v)) continue;
+        const uint64_t r0 = group_offsets[g], r1 = group_offsets[g + 1];
+        if (r0 > r1 || r1 > n_records) continue;
+        if (rec_offsets[r0] > rec_offsets[r1] || rec_offsets[r1] > text_bytes) continue;
+        const uint64_t o = out_offsets[i], words = (r1 - r0 + 31) / 32;
+        if (o > out_words || words > out_words - o) continue;
+        bool ascending = true;
+        for (uint64_t r = r0; r < r1; ++r) ascending = ascending && rec_offsets[r] <= rec_offsets[r + 1];
+        if (!ascending) continue;
+        for (uint64_t r = r0; r < r1; ++r) {
+            const uint64_t n = rec_offsets[r + 1] - rec_offsets[r];
+            const bool hit = (v.lmax == TXQ_REGEX_UNBOUNDED && max_serial && n > max_serial) || txq_regex_view_matches(v, text + rec_offsets[r], (size_t)n);
+            if (hit) out[o + (r - r0) / 32] |= 1u << ((r - r0) & 31);
+        }
+        status[i] = 0;
+    }
+    return 0;
 }
 
 int64_t txh_record_values(int dna, unsigned k, unsigned reduction, const char* seq, size_t len, int wraparound,

@@ -1,6 +1,7 @@
 // `tetrex` command line — product code.  Keeps the reference's surface for the query path:
-//   tetrex query [-d] [-v] [-f] [-c] [-a] [-t N] [-o dest] [-g dibf] <index.ibf> <regex|->
-//     (include/arg_parse.h:57-71, src/main.cpp:36-59, src/query.cpp:477-498)
+//   tetrex query [-d] [-v] [-f] [-c] [-a] [-t N] [-o dest] [-g dibf] [--gpu-verify] <index.ibf> <regex|->
+//     (include/arg_parse.h:57-71, src/main.cpp:36-59, src/query.cpp:477-498; --gpu-verify is not in the reference: the records of
+//      the candidate bins that hold a match at all are found on the device, the matcher runs on those only — same rows)
 //   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] [--layout uniform|sized [--tmax N] [--rearrange [--rearrange-ratio R]]] <name> <libs...>
 //     (include/arg_parse.h:10-38, src/index_base.cpp:73-117)
 //   tetrex search [-e E [--verify] | --threshold F] [--counts] [--translate] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
@@ -105,11 +106,13 @@ size_t popcount_mask(const uint64_t* m, uint64_t words) {
 int cmd_query(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'d', "draw", false}, {'v', "verbose", false}, {'f', "file", false}, {'c', "conj", false},
                                        {'a', "augment", false}, {'t', "threads", true}, {'o', "output", true}, {'g', "gibf", true},
-                                       {'D', "device", true}, {'S', "stats", false}, {'G', "gpus", true}, {'R', "shards", true}, {'M', "max-ops", true}};
+                                       {'D', "device", true}, {'S', "stats", false}, {'G', "gpus", true}, {'R', "shards", true}, {'M', "max-ops", true},
+                                       {'\0', "gpu-verify", false}};
     Args a;
     try {
         a = parse(argc, argv, 2, spec);
         if (a.pos.size() != 2) throw std::runtime_error("expected <index> <regex>");
+        if (a.has("gpu-verify") && a.has("conj")) throw std::runtime_error("--gpu-verify does not work with -c");
     } catch (const std::exception& e) {
         std::cerr << "[Error TetRex Query module " << e.what() << "\n";
         return 0;  // the reference returns normally after a parser error (src/main.cpp:42-46)
@@ -160,6 +163,30 @@ int cmd_query(int argc, char** argv) {
     const KmerEncoder enc = dev.encoder();
     const uint64_t bins = dev.bins(), W = dev.result_words();
     const VerifyOptions vopt{threads};
+    // --gpu-verify: the record filter in front of verification.  On a sharded index it runs on the first device.
+    const bool gpu_verify = a.has("gpu-verify");
+    // fills `sel` for the masks; false (and an empty selection: verification as without the flag) where a bin cannot be read
+    auto filter_records = [&](const std::vector<const uint64_t*>& mptr, const std::vector<std::string>& rxs, RecordSelection& sel, RecordFilter::Stats& fs) {
+        try {
+            RecordFilter rf(image.bin_paths, enc, threads);
+            rf.run(mptr, bins, rxs, sel);
+            fs = rf.stats();
+            return true;
+        } catch (const std::exception& e) {
+            std::cerr << e.what() << '\n';
+            sel.pairs.clear();
+            return false;
+        }
+    };
+    auto print_filter_stats = [&](const RecordFilter::Stats& fs, double find_all_seconds) {
+        if (trace)
+            std::cerr << "[tetrex] gpu-verify: export " << fs.export_seconds << " s, read + upload " << fs.upload_seconds << " s, filter " << fs.filter_seconds
+                      << " s, copy back " << fs.copy_seconds << " s, find_all + rows " << find_all_seconds << " s" << std::endl;
+        if (!a.has("stats")) return;
+        std::cerr << "{\"gpu_verify\": {\"pairs_device\": " << fs.pairs_device << ", \"pairs_host\": " << fs.pairs_host << ", \"records_flagged\": "
+                  << fs.records_flagged << ", \"records_total\": " << fs.records_total << ", \"automata_lds\": " << fs.automata_lds
+                  << ", \"automata_l2\": " << fs.automata_l2 << ", \"automata_host\": " << fs.automata_host << "}}" << std::endl;
+    };
     // -S/--stats (not in the reference): one JSON line on stderr about the candidate-mask stage
     auto print_stats = [&](const StagedStats& st, size_t queries, double seconds) {
         if (!a.has("stats")) return;
@@ -176,12 +203,18 @@ int cmd_query(int argc, char** argv) {
         if (narrowed) {
             try {
                 const std::vector<uint64_t> hit = set_bins(mask, bins);
-                if (destination == "-") verify_bins(hit, image.bin_paths, rx, enc, std::cout, std::cout, vopt);
+                RecordSelection sel;
+                RecordFilter::Stats fs;
+                const bool filtered = gpu_verify && !log_file_mode && filter_records({mask}, {rx}, sel, fs);
+                const RecordSelection* selection = filtered ? &sel : nullptr;
+                const double t_find = now();
+                if (destination == "-") verify_bins(hit, image.bin_paths, rx, enc, std::cout, std::cout, vopt, selection);
                 else {
                     std::ofstream f(destination);
                     if (!f) throw std::runtime_error("Failed to open output file: " + destination);
-                    verify_bins(hit, image.bin_paths, rx, enc, f, std::cout, vopt);
+                    verify_bins(hit, image.bin_paths, rx, enc, f, std::cout, vopt, selection);
                 }
+                if (filtered) print_filter_stats(fs, now() - t_find);
             } catch (const std::exception& e) {
                 std::cerr << e.what() << '\n';
             }
@@ -220,8 +253,13 @@ int cmd_query(int argc, char** argv) {
             std::vector<const uint64_t*> mptr(motifs.size(), nullptr);
             for (size_t i = 0; i < motifs.size(); ++i)
                 if (!status[i]) mptr[i] = masks.data() + i * W;
+            RecordSelection sel;
+            RecordFilter::Stats fs;
+            const bool filtered = gpu_verify && filter_records(mptr, motifs, sel, fs);
             try {
-                verify_batch(mptr, bins, image.bin_paths, motifs, enc, &fwd, &rev, vopt);
+                const double t_find = now();
+                verify_batch(mptr, bins, image.bin_paths, motifs, enc, &fwd, &rev, vopt, filtered ? &sel : nullptr);
+                if (filtered) print_filter_stats(fs, now() - t_find);
             } catch (const std::exception& e) {  // (a bin that cannot be read: motif by motif, so that the others still get their results)
                 std::cerr << e.what() << '\n';
                 bin_major = false;

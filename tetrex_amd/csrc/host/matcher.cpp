@@ -1,4 +1,5 @@
 #include "matcher.hpp"
+#include "../../../include/txq_regex.h"
 
 #include <algorithm>
 #include <cstring>
@@ -192,6 +193,23 @@ Matcher::Matcher(const std::string& pattern, Semantics semantics) : semantics_(s
     build(false, fwd_);
     build(true, rev_);
     for (const Inst& in : fwd_.inst) has_begin_ = has_begin_ || in.op == kBegin;
+    // the longest match: sums and maxima over the parse; a `*`, `+` or `{m,}` anywhere makes it unbounded
+    {
+        constexpr uint64_t kInf = 0xFFFFFFFFull;
+        std::function<uint64_t(int)> longest = [&](int id) -> uint64_t {
+            const Node n = ps.nodes[id];
+            switch (n.type) {
+                case nSet: return 1;
+                case nCat: { const uint64_t a = longest(n.a), b = longest(n.b); return a >= kInf || b >= kInf ? kInf : std::min(kInf, a + b); }
+                case nAlt: return std::max(longest(n.a), longest(n.b));
+                case nQuest: return longest(n.a);
+                case nStar: case nPlus: (void)longest(n.a); return kInf;
+                case nRepeat: { const uint64_t a = longest(n.a); return n.hi < 0 || a >= kInf ? kInf : std::min(kInf, a * (uint64_t)n.hi); }
+                default: return 0;  // nEmpty, anchors
+            }
+        };
+        max_len_ = (uint32_t)longest(root);
+    }
     // The longest run of single-byte factors on the pattern's spine — the factors every match goes through in order: the
     // concatenation at the top, and what sits inside `+` / {m,..} with m >= 1 (at least one round) — is a string every
     // match contains.  Alternations, optional parts and byte sets end a run and contribute nothing.
@@ -428,6 +446,56 @@ size_t Matcher::pike_end(std::string_view text, size_t start, Cache& c, bool at_
     }
     if (matched) *matched = any;
     return last;
+}
+
+bool Matcher::export_dfa(bool reverse, const uint8_t* byte_map, std::vector<uint8_t>& out) const {
+    out.clear();
+    try {
+        const Prog& p = reverse ? rev_ : fwd_;
+        Cache c;
+        Cache::Dfa d;
+        dfa_init(p, true, d, c);
+        // breadth first; an accepting state is not expanded (it becomes the absorbing accept state)
+        size_t plain = 0, positions = 0, counted = 0;
+        auto count_new = [&]() {
+            for (; counted < d.sets.size(); ++counted)
+                if (!(d.flags[counted] & 1)) { ++plain; positions += d.sets[counted].size(); }
+            return plain + 2 <= TXQ_REGEX_MAX_STATES && positions <= kExportBudget;
+        };
+        if (!count_new()) return false;
+        for (uint32_t s = 0; s < d.sets.size(); ++s) {
+            if (d.flags[s] & 1) continue;
+            for (uint32_t k = 0; k < n_classes_; ++k) dfa_step(p, d, s, k, c);
+            if (!count_new()) return false;
+        }
+        std::vector<uint32_t> id(d.sets.size());
+        uint32_t n_states = 2;
+        for (size_t s = 0; s < d.sets.size(); ++s) id[s] = (d.flags[s] & 1) ? TXQ_REGEX_ACCEPT : n_states++;
+        auto renamed = [&](uint32_t s) { return s == kDead || s == kUnknown ? (uint32_t)TXQ_REGEX_DEAD : id[s]; };
+        out.assign(TXQ_REGEX_BYTES(n_states, n_classes_), 0);
+        const uint32_t header[8] = {TXQ_REGEX_MAGIC, n_states, n_classes_, renamed(d.start_begin), renamed(d.start_mid), max_len_,
+                                    (uint32_t)out.size(), 0};
+        for (int i = 0; i < 8; ++i)
+            for (int b = 0; b < 4; ++b) out[4 * i + b] = (uint8_t)(header[i] >> (8 * b));
+        for (unsigned b = 0; b < 256; ++b) out[TXQ_REGEX_HEADER + b] = class_of_[byte_map ? byte_map[b] : b];
+        uint8_t* next = out.data() + TXQ_REGEX_TABLES;
+        uint8_t* flags = next + (size_t)n_states * n_classes_ * 2;
+        auto put = [&](uint32_t s, uint32_t k, uint32_t to) {
+            next[2 * ((size_t)s * n_classes_ + k)] = (uint8_t)to;
+            next[2 * ((size_t)s * n_classes_ + k) + 1] = (uint8_t)(to >> 8);
+        };
+        for (uint32_t k = 0; k < n_classes_; ++k) put(TXQ_REGEX_ACCEPT, k, TXQ_REGEX_ACCEPT);  // (the dead state's row is zero)
+        flags[TXQ_REGEX_ACCEPT] = 1;
+        for (size_t s = 0; s < d.sets.size(); ++s) {
+            if (d.flags[s] & 1) continue;
+            for (uint32_t k = 0; k < n_classes_; ++k) put(id[s], k, renamed(d.next[s * n_classes_ + k]));
+            flags[id[s]] = d.flags[s] & 2;
+        }
+        return true;
+    } catch (const std::exception&) {
+        out.clear();
+        return false;
+    }
 }
 
 bool Matcher::contains(std::string_view text, Cache& c) const {

@@ -92,6 +92,18 @@ class Matcher {
     // (A literal is a run of one-byte sets.)  Empty: nothing usable.
     const std::vector<std::array<uint64_t, 4>>& required_run() const { return run_; }
 
+    // The pattern as a flat automaton for the device's record filter (include/txq_regex.h, `tetrex query --gpu-verify`,
+    // DESIGN.md §13): the unanchored "contains" automaton, determinised eagerly, every accepting state folded into the one
+    // absorbing accept state.  reverse = false: from the forward program, what contains() runs lazily.  reverse = true: from
+    // the reversed program — it accepts T exactly when the pattern matches reverse(T), so with the complement in byte_map
+    // it answers "does the pattern match the reverse complement of T" on T itself, scanned forward.  byte_map[256] is
+    // applied to every text byte before its class is looked up (the identity, a reduction of the alphabet, the complement):
+    // it is folded into the blob's class table, so the scan sees raw record bytes.  false: more than 65 535 states (or more
+    // NFA positions in them than kExportBudget) — determinisation stops there; nothing is thrown.
+    bool export_dfa(bool reverse, const uint8_t* byte_map, std::vector<uint8_t>& out) const;
+    // the longest match in bytes; 0xFFFFFFFF: unbounded (the pattern has `*`, `+` or `{m,}`)
+    uint32_t max_match_length() const { return max_len_; }
+
   private:
     struct Inst { uint8_t op; uint32_t x, y; };  // Char: x = set index, y unused; Split: x preferred over y; Jmp: x
     enum : uint8_t { kChar, kSplit, kJmp, kBegin, kEnd, kMatch };
@@ -103,6 +115,8 @@ class Matcher {
     };
     Semantics semantics_;
     bool has_begin_ = false;                     // the pattern has a `^`
+    uint32_t max_len_ = 0;                       // max_match_length()
+    static constexpr size_t kExportBudget = size_t(1) << 24;  // NFA positions held by the states of one export at most
     std::string literal_;                        // a string every match contains (may be empty)
     std::vector<std::array<uint64_t, 4>> run_;   // the byte sets of the most selective run of single-byte factors (may be empty)
     std::vector<std::array<uint64_t, 4>> sets_;  // byte sets of the pattern

@@ -15,21 +15,12 @@
 namespace tetrex {
 
 namespace {
-
-char complement(char c) {
-    switch (c) {  // comp_tab of src/query.cpp:7-16 restricted to the IUPAC letters
-        case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; case 'U': return 'A';
-        case 'a': return 't'; case 'c': return 'g'; case 'g': return 'c'; case 't': return 'a'; case 'u': return 'a';
-        case 'M': return 'K'; case 'K': return 'M'; case 'R': return 'Y'; case 'Y': return 'R';
-        case 'V': return 'B'; case 'B': return 'V'; case 'H': return 'D'; case 'D': return 'H';
-        default: return c;
-    }
-}
-
+char complement(char c) { return complement_base(c); }
 }  // namespace
 
 size_t verify_bins(const std::vector<uint64_t>& bins, const std::vector<std::string>& bin_paths, const std::string& regex,
-                   const KmerEncoder& enc, std::ostream& out, std::ostream& reverse_out, const VerifyOptions& opt) {
+                   const KmerEncoder& enc, std::ostream& out, std::ostream& reverse_out, const VerifyOptions& opt,
+                   const RecordSelection* selection) {
     const bool dna = enc.molecule() == Molecule::DNA;
     const bool reduced = !dna && enc.alphabet() != Alphabet::Base;
     std::string pattern = regex;
@@ -46,14 +37,28 @@ size_t verify_bins(const std::vector<uint64_t>& bins, const std::vector<std::str
             const std::string& path = bin_paths.at(bins[i]);
             std::ostringstream f, r;
             Matcher::Cache cache;  // lazily built automaton states: per thread
+            // the records to look at, where the bin has a selection: two cursors over its ascending lists
+            const RecordSelection::Lists* lists = selection ? selection->find(0, bins[i]) : nullptr;
+            if (lists && lists->strand[0].empty() && lists->strand[1].empty()) continue;  // (nothing in this bin: not even read)
+            size_t at[2] = {0, 0};
+            uint32_t index = 0;
+            auto listed = [&](int strand) {
+                if (!lists) return true;
+                const std::vector<uint32_t>& l = lists->strand[strand];
+                while (at[strand] < l.size() && l[at[strand]] < index) ++at[strand];
+                return at[strand] < l.size() && l[at[strand]] == index;
+            };
             for_each_record(path, [&](const FastaRecord& rec) {
+                const bool look_fwd = listed(0), look_rev = dna && listed(1);
+                ++index;
+                if (!look_fwd && !look_rev) return;
                 std::string seq = rec.seq;
                 if (reduced) for (char& c : seq) c = enc.reduce((unsigned char)c);
-                rx.find_all(seq, cache, [&](size_t s, size_t n) {
+                if (look_fwd) rx.find_all(seq, cache, [&](size_t s, size_t n) {
                     f << path << "\t>" << rec.name << "\t" << seq.substr(s, n) << "\t" << s << "," << s + n << "\n";
                     ++found[i];
                 });
-                if (dna) {
+                if (look_rev) {
                     std::string rc(seq.rbegin(), seq.rend());
                     for (char& c : rc) c = complement(c);
                     rx.find_all(rc, cache, [&](size_t s, size_t n) {
@@ -81,7 +86,7 @@ size_t verify_bins(const std::vector<uint64_t>& bins, const std::vector<std::str
 
 size_t verify_batch(const std::vector<const uint64_t*>& masks, uint64_t bins, const std::vector<std::string>& bin_paths,
                     const std::vector<std::string>& regexes, const KmerEncoder& enc, std::vector<std::string>* forward,
-                    std::vector<std::string>* reverse, const VerifyOptions& opt) {
+                    std::vector<std::string>* reverse, const VerifyOptions& opt, const RecordSelection* selection) {
     const bool dna = enc.molecule() == Molecule::DNA;
     const bool reduced = !dna && enc.alphabet() != Alphabet::Base;
     const size_t nq = regexes.size();
@@ -132,6 +137,14 @@ size_t verify_batch(const std::vector<const uint64_t*>& masks, uint64_t bins, co
                 std::vector<Rows>& mine = rows[i];
                 mine.resize(qs.size());
                 const double t0 = trace ? now() : 0;
+                if (selection) {  // a bin in which no motif has a record to look at is not even read
+                    bool needed = false;
+                    for (uint32_t q : qs) {
+                        const RecordSelection::Lists* l = selection->find(q, todo[i]);
+                        needed = needed || !l || !l->strand[0].empty() || !l->strand[1].empty();
+                    }
+                    if (!needed) continue;
+                }
                 load_records(path, recs);  // ONE read of the bin for all its motifs
                 if (reduced)
                     for (char& c : recs.text) if (c != '\n') c = enc.reduce((unsigned char)c);
@@ -160,16 +173,19 @@ size_t verify_batch(const std::vector<const uint64_t*>& masks, uint64_t bins, co
                     const uint32_t q = qs[j];
                     const Matcher& m = *rx[q];
                     if (!caches[q]) caches[q] = std::make_unique<Matcher::Cache>();
+                    const RecordSelection::Lists* lists = selection ? selection->find(q, todo[i]) : nullptr;
                     auto scan = [&](const std::string& text, bool reverse_strand) {
                         const double ta = trace ? now() : 0;
-                        const bool listed = candidates(m, text);
+                        const std::vector<uint32_t>* chosen = lists ? &lists->strand[reverse_strand] : nullptr;  // the records to look at
+                        const bool listed = !chosen && candidates(m, text);
                         const double tb = trace ? now() : 0;
                         my_literal += tb - ta;
-                        const size_t n_scan = listed ? hits.size() : recs.size();
+                        const size_t n_scan = chosen ? chosen->size() : listed ? hits.size() : recs.size();
                         my_listed += listed;
                         my_scanned += n_scan;
                         for (size_t at = 0; at < n_scan; ++at) {
-                            const size_t r = listed ? hits[at] : at;
+                            const size_t r = chosen ? (*chosen)[at] : listed ? hits[at] : at;
+                            if (r >= recs.size()) continue;  // (a list made from another file than the one read now)
                             const std::string_view seq(text.data() + recs.start[r], recs.start[r + 1] - recs.start[r] - 1);
                             m.find_all(seq, *caches[q], [&](size_t s, size_t n) {
                                 std::string& o = reverse_strand ? mine[j].rev : mine[j].fwd;

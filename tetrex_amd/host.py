@@ -222,6 +222,104 @@ def regex_required_literal(pattern, posix=True):
     return buf.raw[:n].decode()
 
 
+REGEX_REFUSED = 0xFFFFFFFE
+REGEX_UNBOUNDED = 0xFFFFFFFF
+
+
+def regex_automaton(pattern, posix, strand=0, byte_map=None):
+    """txh_regex_automaton: the pattern as the flat automaton of include/txq_regex.h (bytes), or None where it has more than
+    65 535 states.  strand 1: the reversed pattern; byte_map: 256 bytes applied to the text first (None: the identity)."""
+    L = lib()
+    L.txh_regex_automaton.restype = C.c_int64
+    L.txh_regex_automaton.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+    bm = None if byte_map is None else np.ascontiguousarray(byte_map, dtype=np.uint8)
+    if bm is not None and bm.size != 256:
+        raise HostError("regex_automaton: byte_map must have 256 entries")
+    cap = 1 << 16
+    for _ in range(2):
+        out = np.zeros(cap, dtype=np.uint8)
+        n = L.txh_regex_automaton(pattern.encode(), int(posix), int(strand), None if bm is None else bm.ctypes.data, out.ctypes.data, cap)
+        if n < 0:
+            raise _err()
+        if n == 0:
+            return None
+        if n <= cap:
+            return out[:n].tobytes()
+        cap = int(n)
+    raise HostError("regex_automaton: the blob changed its size")
+
+
+def reduce_table(reduction):
+    """txh_reduce_table: byte -> letter of a peptide reduction (1 murphy, 2 li), as 256 uint8"""
+    L = lib()
+    L.txh_reduce_table.argtypes = [C.c_uint, C.c_void_p]
+    out = np.zeros(256, dtype=np.uint8)
+    if L.txh_reduce_table(reduction, out.ctypes.data) < 0:
+        raise _err()
+    return out
+
+
+def regex_automaton_header(blob):
+    """the header fields of an automaton blob (include/txq_regex.h) as a dict"""
+    f = struct.unpack_from("<8I", blob, 0)
+    return dict(magic=f[0], n_states=f[1], n_classes=f[2], start_begin=f[3], start_mid=f[4], lmax=f[5], total_bytes=f[6])
+
+
+def regex_filter_arrays(automata, records, groups, pairs):
+    """the arguments of regex_filter as contiguous arrays: (arena, automaton offsets, text, record offsets, group offsets,
+    pairs (n, 2) uint32, bitmap word offsets, bitmap words).  An automaton starts at a multiple of 16 bytes of the arena;
+    a pair that names a group out of range gets no words."""
+    if isinstance(automata, tuple):
+        arena, ao = automata
+    else:
+        blobs = [bytes(a) + b"\0" * (-len(a) % 16) for a in automata]
+        arena, ao = _byte_records(blobs)
+    txt, ro = records if isinstance(records, tuple) else _byte_records(records)
+    arena, txt = np.ascontiguousarray(arena, dtype=np.uint8), np.ascontiguousarray(txt, dtype=np.uint8)
+    ao, ro = np.ascontiguousarray(ao, dtype=np.uint64), np.ascontiguousarray(ro, dtype=np.uint64)
+    go = np.ascontiguousarray(groups, dtype=np.uint64)
+    pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    if ao.size < 1 or ro.size < 1 or go.size < 1 or int(ao[-1]) > arena.size or int(ro[-1]) > txt.size:
+        raise HostError("regex_filter: offsets and bytes disagree")
+    words = [(int(go[g + 1]) - int(go[g]) + 31) // 32 if g + 1 < go.size and go[g + 1] >= go[g] else 0 for g in pr[:, 1].tolist()]
+    oo = np.zeros(pr.shape[0] + 1, dtype=np.uint64)
+    oo[1:] = np.cumsum(words, dtype=np.uint64)
+    return arena, ao, txt, ro, go, pr, oo, int(oo[-1])
+
+
+def regex_filter_unpack(go, pr, oo, out, status):
+    """per pair a boolean array over its group's records (empty for a refused pair)"""
+    res = []
+    for i, (_, g) in enumerate(pr.tolist()):
+        if status[i] != 0:
+            res.append(np.zeros(0, dtype=bool))
+            continue
+        n = int(go[g + 1]) - int(go[g])
+        w = out[int(oo[i]):int(oo[i + 1])]
+        res.append(np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool))
+    return res
+
+
+def regex_filter(automata, records, groups, pairs, max_serial=0, return_status=False):
+    """txh_regex_filter: which records of a group does an automaton match (include/txh.h)?  automata: blobs of
+    regex_automaton; records: list of bytes/str, or (uint8 array, uint64 offsets); groups: uint64 offsets into the records;
+    pairs: rows of (automaton, group).  Returns one boolean array per pair (and the status array if asked for)."""
+    L = lib()
+    L.txh_regex_filter.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_size_t, C.c_void_p, u64p, C.c_size_t, C.c_size_t, u64p, C.c_size_t,
+                                   C.c_void_p, C.c_size_t, u64p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]
+    arena, ao, txt, ro, go, pr, oo, n_words = regex_filter_arrays(automata, records, groups, pairs)
+    out = np.zeros(max(1, n_words), dtype=np.uint32)
+    status = np.zeros(max(1, pr.shape[0]), dtype=np.uint32)
+    rc = L.txh_regex_filter(arena.ctypes.data, ao.ctypes.data_as(u64p), ao.size - 1, arena.size, txt.ctypes.data, ro.ctypes.data_as(u64p),
+                            ro.size - 1, txt.size, go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], oo.ctypes.data_as(u64p),
+                            out.ctypes.data, n_words, max_serial, status.ctypes.data)
+    if rc < 0:
+        raise _err()
+    status = status[:pr.shape[0]]
+    res = regex_filter_unpack(go, pr, oo, out, status)
+    return (res, status) if return_status else res
+
+
 def record_values(seq, k, dna=True, reduction=0, wraparound=False):
     s = seq.encode() if isinstance(seq, str) else seq
     cap = len(s) + 2
