@@ -62,6 +62,8 @@ extern "C" {
  *   TXQ_EDIT_CHUNK=<bytes>                            bytes of text per lane of the edit-distance kernel (txq_edit_search, below)
  *   TXQ_PROBE_TABLE=0|1                               a flat probe's table of its batch's k-mer domain: never | whenever it fits
  *                                                     (unset: where the batch repeats its values often enough to pay for it)
+ *   TXQ_PROBE_TABLE_KEEP=0                            that table is built from its first row on every call, not kept with the
+ *                                                     index and extended (the rows never outlive txq_emplace_device either way)
  * (tests/test_gpu_knobs.py runs a workload under each of them against the oracle.) */
 
 typedef enum {

@@ -83,6 +83,7 @@ void read_knobs() {
     k.probe_unroll = (int)num("TXQ_PROBE_UNROLL", 2);
     k.probe_nt = flag("TXQ_PROBE_NT");
     k.probe_table = is("TXQ_PROBE_TABLE", '0') ? 0 : is("TXQ_PROBE_TABLE", '1') ? 1 : -1;
+    k.probe_table_keep = !is("TXQ_PROBE_TABLE_KEEP", '0');
     std::lock_guard<std::mutex> lock(g_knobs_mutex);
     g_knobs = k;
 }
@@ -169,10 +170,11 @@ void Index::release() {
     }
     host_pipe = HostPipe{};
     if (probe_table.rows) (void)hipFree(probe_table.rows);
-    if (probe_table.dom) (void)hipFree(probe_table.dom);
+    if (probe_table.state) (void)hipFree(probe_table.state);
     if (probe_table.done) (void)hipEventDestroy(probe_table.done);
-    probe_table.rows = nullptr; probe_table.dom = nullptr; probe_table.done = nullptr;
+    probe_table.rows = nullptr; probe_table.state = nullptr; probe_table.done = nullptr;
     probe_table.cap_rows = 0; probe_table.recorded = probe_table.refused = false;
+    probe_table.keep = ProbeKeep{};
     for (const ArenaChunk& c : session_cache.chunks) (void)hipFree(c.p);
     for (const ArenaChunk& c : session_cache.block_chunks) (void)hipFree(c.p);
     for (StagingSet& t : session_cache.set)
@@ -633,6 +635,13 @@ int txq_emplace_device(txq_index* ix, const uint64_t* d_values, const uint32_t* 
         }
         ix->kmer_table_refused = false;
     }
+    // ... and the flat probe's domain table: the next probe call finds another generation and starts its rows over.  A probe
+    // enqueued earlier, on whatever stream, has left rows of the old bits behind; the kernel below waits for it, so that none of
+    // them is written after the bits changed (no device-wide wait: the event of the last table call is enough).
+    Index::ProbeTable& pt = ix->probe_table;
+    std::lock_guard<std::mutex> lock(pt.mutex);
+    ++ix->generation;
+    if (pt.recorded) TXQ_HIP(hipStreamWaitEvent((hipStream_t)stream, pt.done, 0));
     hipError_t e = launch_emplace(ix->ibf[0], d_values, d_bins_of, n, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "emplace kernel launch");
     return TXQ_OK;

@@ -3,6 +3,7 @@
 #include "txq_kernels.hpp"
 #include "txq_records.hpp"
 #include "txq_exec_plan.hpp"
+#include "txq_probe_plan.hpp"
 #include "../../include/txq.h"
 #include <cstdlib>
 #include <map>
@@ -74,6 +75,7 @@ struct Knobs {
     int probe_blocks_per_cu = 256, probe_unroll = 2;  // TXQ_PROBE_BLOCKS_PER_CU, TXQ_PROBE_UNROLL
     bool probe_nt = false;                            // TXQ_PROBE_NT
     int probe_table = -1;  // TXQ_PROBE_TABLE: 0 never the domain table of a flat probe, 1 whenever it fits (tests), unset: where it pays
+    bool probe_table_keep = true;  // TXQ_PROBE_TABLE_KEEP=0: the domain table is built from row 0 on every call (A/B and tests)
 };
 Knobs knobs();      // a copy of the snapshot taken at the last entry point (published under a lock: entry points run on several threads)
 void read_knobs();  // take it (txq_api.hip)
@@ -162,11 +164,20 @@ struct Index {
     uint64_t* kmer_table = nullptr; uint32_t kmer_table_bits = 0;  // bits = bits per residue * k of the table that is built
     bool kmer_table_refused = false;                               // (the allocation failed once: not tried again)
     std::mutex table_mutex;                                        // building / dropping the table (sessions of one index may run on several threads)
-    // The flat probe's scratch table of a call's k-mer domain (txq_probe.hip probe_flat): rebuilt on every call, so nothing in
-    // it outlives the call; `done` is recorded behind the call's last kernel and the next call, on whatever stream, waits for it.
+    // Calls that changed a flat index's bits after it was made: txq_emplace_device, the only writer of ibf[0].words besides upload
+    // and create (which make a new Index).  What is derived from the bits and kept remembers the generation it was derived from.
+    uint64_t generation = 0;  // (read and written under probe_table.mutex)
+    // The flat probe's table of its batches' k-mer domain (txq_probe.hip probe_flat): T[v] = the mask of value v, for v below
+    // a device word `built`.  The rows depend on the index's bits alone, so they are kept from call to call and extended when
+    // a batch's domain is larger; they are started over (txq_probe_plan.hpp plan_probe_call) when `generation` — the calls
+    // that changed the bits, txq_emplace_device — is not the one they were built for, when the table was just (re)allocated,
+    // and on every call under TXQ_PROBE_TABLE_KEEP=0.  `done` is recorded behind a call's last kernel and the next call, on
+    // whatever stream, waits for it; so does txq_emplace_device before it changes the bits.  Everything here is read and
+    // written under `mutex`.
     struct ProbeTable {
         uint64_t* rows = nullptr; size_t cap_rows = 0;  // [cap_rows][stride]
-        uint32_t* dom = nullptr;                        // the domain pass's answer: D, k-mers below the capacity
+        uint32_t* state = nullptr;                      // [kStateWords]: two sample accumulators {top, count}, `built`
+        ProbeKeep keep;                                 // the generation the rows belong to, the calls so far
         hipEvent_t done = nullptr;
         bool recorded = false, refused = false;         // (refused: the allocation failed once, not tried again)
         std::mutex mutex;

@@ -16,15 +16,23 @@
 // Algorithmic HBM bytes per probe: h*W*8 (rows) + W*8 (mask) + 8 (k-mer); W = shard_words.
 //
 // Domain table (probe_flat, the path of txq_probe_device on a flat IBF): a batch whose values lie in a domain [0, D)
-// several times smaller than the batch holds each value n/D times, and every repeat gathers the same h rows again.  Per call:
-//   1. probe_domain_kernel: a 1/16 sample of the k-mers -> D = 1 + the largest value below the table's capacity, and how
-//      many values lie below it (device word; the host gets no answer back, the call stays stream-ordered),
-//   2. probe_kernel<..., kBuild>: every value of [0, D) probed into a scratch table T[v] (row pitch = stride),
-//   3. probe_kernel<..., kAnswer>: the same lane layout; a k-mer v < D reads ONE row T[v], any other k-mer (and every
-//      k-mer when the domain does not pay, count < ratio * D) gathers its h rows as above.
-// The table is rebuilt on every call (no answer survives a call; emplace needs no invalidation).  Per probe of the
-// answer: 8 (k-mer) + W*8 (table row) + W*8 (mask); per call D * (h*W*8 + W*8) to build and n/2 bytes of sample.
+// several times smaller than the batch holds each value n/D times, and every repeat gathers the same h rows again.  The row
+// T[v] = bulk_contains(v) depends on the index's bits and on nothing in the batch, so the table is kept with the index from
+// call to call and only EXTENDED: a device word `built` says that rows [0, built) hold the masks of the current bits.  Per call:
+//   1. probe_domain_kernel: a 1/16 sample of the k-mers -> D = 1 + the largest value below the call's capacity, and how
+//      many values lie below it (device words; the host gets no answer back, the call stays stream-ordered),
+//   2. probe_kernel<..., kBuild>: the values [built, D) probed into the table T[v] (row pitch = stride) - in the steady
+//      state nothing, every wave leaves at once,
+//   3. probe_kernel<..., kAnswer>: the same lane layout; a k-mer v < rows = max(built, D) reads ONE row T[v], any other k-mer
+//      gathers its h rows as above (when the domain does not pay, count < ratio * D, rows = built).  One thread stores
+//      built = rows and zeroes the sample words of the next call (two sets, used alternately: no memset launch).
+// Whether the rows are still valid is the host's decision, by API call order (txq_probe_plan.hpp plan_probe_call): the index
+// counts the calls that change its bits (txq_emplace_device), and a call that finds another count than the table was built for,
+// a table just (re)allocated, or TXQ_PROBE_TABLE_KEEP=0 is `fresh`: it builds from row 0 and does not read `built`.
+// Per probe of the answer: 8 (k-mer) + W*8 (table row) + W*8 (mask); per call n/2 bytes of sample, and (D - built) *
+// (h*W*8 + W*8) to extend the table.
 #include "txq_internal.hpp"
+#include "txq_probe_plan.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -55,24 +63,25 @@ struct TreeRoot {
     uint32_t wpr_log2;         // log2(mask words per child)
 };
 
-// The domain table of one call (see the header): dom[0] = D = 1 + the largest k-mer value below `cap` in a sample of the
-// batch (0: none), dom[1] = how many k-mers of the sample lie below `cap`.  The table is used when the batch holds about
-// ratio * D k-mers below D, dom[1] * sample >= ratio * D (ratio 0: always).
+// The domain table of one call (see the header).  state: the words the kernels keep beside the table (txq_probe_plan.hpp
+// kState...): this call's sample {top, count} at kStateAcc + 2 * parity, `built` at kStateBuilt.
 struct TableArgs {
-    uint64_t* table;        // T[v] at table + v * stride, v < D
-    const uint32_t* dom;
-    uint32_t ratio, sample;
+    uint64_t* table;  // T[v] at table + v * stride, v < rows
+    uint32_t* state;
+    uint32_t ratio, cap_rows;
+    uint32_t parity, fresh;
 };
-__device__ __forceinline__ uint32_t table_rows(const TableArgs& T) {
-    const uint32_t d = T.dom[0], c = T.dom[1];
-    return d && (uint64_t)c * T.sample >= (uint64_t)T.ratio * d ? d : 0u;
+__device__ __forceinline__ ProbeRows table_rows(const TableArgs& T) {
+    const uint32_t* acc = T.state + kStateAcc + 2u * T.parity;
+    return table_rows(T.fresh != 0, T.state[kStateBuilt], acc[0], acc[1], T.ratio, kDomainSample, T.cap_rows);
 }
 enum ProbeMode { kPlain = 0, kBuild = 1, kAnswer = 2 };
 
 // LPK lanes per k-mer, H hash functions, U steps in flight.  Requires bin_size < 2^32 and an even
 // stride.  U*H independent 16-byte gathers per lane are issued before the first AND.
-// MODE kBuild: the k-mers are 0 .. D-1 (no input), written to T.table at row pitch stride (whole 16-byte chunks, plain
-// stores: the answer reads them back); MODE kAnswer: k-mers below D read their row of T.table instead of gathering.
+// MODE kBuild: the k-mers are the values [lo, rows) of table_rows (no input; from the tile that holds lo), written to T.table
+// at row pitch stride (whole 16-byte chunks, plain stores: the answer reads them back); MODE kAnswer: k-mers below `rows`
+// read their row of T.table instead of gathering, and one thread leaves `built` and the next call's sample words behind.
 template <int LPK, int H, int U, bool NT, class ROOT = NoRoot, int MODE = kPlain>
 __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __restrict__ kmers, size_t n,
                                                     uint64_t* __restrict__ masks, uint64_t* __restrict__ alive, ROOT R = ROOT{},
@@ -82,11 +91,25 @@ __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __
     const int lane = threadIdx.x & 63;
     const int sub = lane % LPK, grp = lane / LPK;
     const uint32_t chunks = f.stride >> 1;
-    const uint32_t tab_rows = MODE == kPlain ? 0u : table_rows(T);
-    if constexpr (MODE == kBuild) n = tab_rows;
+    uint32_t tab_rows = 0;
+    size_t tile0 = 0;
+    if constexpr (MODE != kPlain) {
+        const ProbeRows tr = table_rows(T);
+        tab_rows = tr.rows;
+        if constexpr (MODE == kBuild) {
+            n = tr.rows;
+            tile0 = tr.lo >> 6;
+        } else if (blockIdx.x == 0 && threadIdx.x == 0) {
+            // (every wave computes the same rows whether it reads the old `built` or this one: txq_probe_plan.hpp)
+            T.state[kStateBuilt] = tr.rows;
+            uint32_t* next = T.state + kStateAcc + 2u * (T.parity ^ 1u);
+            next[0] = 0;
+            next[1] = 0;
+        }
+    }
     const size_t n_tiles = (n + 63) >> 6;
     const size_t n_waves = (size_t)gridDim.x * (blockDim.x >> 6);
-    for (size_t tile = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); tile < n_tiles; tile += n_waves) {
+    for (size_t tile = tile0 + (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); tile < n_tiles; tile += n_waves) {
         const size_t base = tile << 6;
         const size_t mine = base + lane;
         const uint64_t v = MODE == kBuild ? (uint64_t)mine : mine < n ? __builtin_nontemporal_load(kmers + mine) : 0;
@@ -247,21 +270,29 @@ __global__ __launch_bounds__(256) void emplace_kernel(IbfDev f, const uint64_t* 
     }
 }
 
-// The domain pass of the table path: dom[0] = max(v + 1), dom[1] = count over the k-mers v < cap of a SAMPLE (dom zeroed
-// before): block b reads the head of the b-th of gridDim.x equal segments of the batch, 1 / kDomainSample of it in all.
+// The domain pass of the table path: acc[0] = max(v + 1), acc[1] = count over the k-mers v < cap of a SAMPLE (acc zeroed
+// by the call before): the head of each of `segs` equal segments of the batch, 1 / kDomainSample of it in all.  A head is
+// shared by `parts` blocks (blockIdx.x = segment * parts + part), so that a thread has at most kDomainLoads k-mers and
+// issues their loads together; one block per segment had eight dependent loads per thread on the bench batch, 17 us for 8 MB.
 // The gate does not decide correctness (a k-mer the sample missed, v >= D, gathers its rows), so a sample is enough, and
 // a batch whose domain does not pay costs a few microseconds rather than a pass over all its k-mers.
-static constexpr uint32_t kDomainSample = 16;
-__global__ __launch_bounds__(256) void probe_domain_kernel(const uint64_t* __restrict__ kmers, size_t n, uint32_t cap, uint32_t* __restrict__ dom) {
+static constexpr int kDomainLoads = 4;
+__global__ __launch_bounds__(256) void probe_domain_kernel(const uint64_t* __restrict__ kmers, size_t n, uint32_t cap, uint32_t segs, uint32_t parts,
+                                                           uint32_t* __restrict__ acc) {
     uint32_t top = 0, count = 0;
-    const size_t lo = n * blockIdx.x / gridDim.x, hi = n * (blockIdx.x + 1) / gridDim.x;
+    const uint32_t seg = blockIdx.x / parts, part = blockIdx.x % parts;
+    const size_t lo = n * seg / segs, hi = n * (seg + 1) / segs;
     const size_t end = lo + (hi - lo + kDomainSample - 1) / kDomainSample;
-    for (size_t i = lo + threadIdx.x; i < end; i += blockDim.x) {
-        const uint64_t v = kmers[i];
-        if (v < cap) {
-            top = max(top, (uint32_t)v + 1u);
-            ++count;
-        }
+    for (size_t i0 = lo + (size_t)part * (256 * kDomainLoads) + threadIdx.x; i0 < end; i0 += (size_t)parts * (256 * kDomainLoads)) {
+        uint64_t v[kDomainLoads];
+#pragma unroll
+        for (int u = 0; u < kDomainLoads; ++u) v[u] = i0 + u * 256 < end ? kmers[i0 + u * 256] : ~0ULL;
+#pragma unroll
+        for (int u = 0; u < kDomainLoads; ++u)
+            if (v[u] < cap) {
+                top = max(top, (uint32_t)v[u] + 1u);
+                ++count;
+            }
     }
     for (int o = 32; o > 0; o >>= 1) {
         top = max(top, (uint32_t)__shfl_xor((int)top, o));
@@ -280,8 +311,8 @@ __global__ __launch_bounds__(256) void probe_domain_kernel(const uint64_t* __res
             top = max(top, s_top[w]);
             count += s_count[w];
         }
-        if (top) atomicMax(dom, top);
-        if (count) atomicAdd(dom + 1, count);
+        if (top) atomicMax(acc, top);
+        if (count) atomicAdd(acc + 1, count);
     }
 }
 
@@ -357,24 +388,24 @@ hipError_t launch_probe(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* 
     return launch_lpk<64>(f, k, n, m, a, s);
 }
 
-// The domain-table path (header comment).  ratio: the table is used when at least ratio * D k-mers of the batch lie below D
-// (0: whenever D fits the table).  The table must hold `cap` rows; the caller keeps other calls off it until the answer ran.
+// The domain-table path (header comment).  T.ratio: the table is used when at least ratio * D k-mers of the batch lie below D
+// (0: whenever D fits the table).  The table holds T.cap_rows >= cap rows; the caller keeps other calls off it until the answer ran.
 template <int LPK>
-static hipError_t launch_table_lpk(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* m, uint64_t* a, uint64_t* table, uint32_t* dom,
-                                   uint32_t cap, uint32_t ratio, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(dom, 0, 2 * sizeof(uint32_t), s);
-    if (e != hipSuccess) return e;
-    const unsigned dgrid = (unsigned)std::min<size_t>(std::max<size_t>(n / 1024, 1), 512);  // segments of the sample
-    probe_domain_kernel<<<dgrid, 256, 0, s>>>(k, n, cap, dom);
-    const TableArgs T{table, dom, ratio, kDomainSample};
-    // the build's grid covers the capacity (D is not known on the host); waves past D leave at once
+static hipError_t launch_table_lpk(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* m, uint64_t* a, const TableArgs& T, uint32_t cap,
+                                   hipStream_t s) {
+    // the sample: the heads of `segs` segments, each shared by as many blocks as give a thread at most kDomainLoads k-mers
+    const uint32_t segs = (uint32_t)std::min<size_t>(std::max<size_t>(n / 1024, 1), 512);
+    const size_t head = ((n + segs - 1) / segs + kDomainSample - 1) / kDomainSample;
+    const uint32_t parts = (uint32_t)std::max<size_t>((head + 256 * kDomainLoads - 1) / (256 * kDomainLoads), 1);
+    probe_domain_kernel<<<segs * parts, 256, 0, s>>>(k, n, cap, segs, parts, T.state + kStateAcc + 2u * T.parity);
+    // the build's grid covers the call's capacity (neither `built` nor D is known on the host); waves with nothing to do leave at once
     const unsigned bgrid = (unsigned)std::min<size_t>(((size_t)cap + 255) / 256, 2048);
     const unsigned grid = grid_for((n + 63) / 64, 4);
     // (one hash function: a table row would be the IBF's own row — table_capacity never sends such an index here)
     if (f.hash_funs < 2 || !with_hash_funs(f.hash_funs, [&](auto h) {
             constexpr int H = decltype(h)::value;
             if constexpr (H >= 2) {
-                probe_kernel<LPK, H, 2, false, NoRoot, kBuild><<<bgrid, 256, 0, s>>>(f, nullptr, 0, table, nullptr, NoRoot{}, T);
+                probe_kernel<LPK, H, 2, false, NoRoot, kBuild><<<bgrid, 256, 0, s>>>(f, nullptr, 0, T.table, nullptr, NoRoot{}, T);
                 probe_kernel<LPK, H, 2, false, NoRoot, kAnswer><<<grid, 256, 0, s>>>(f, k, n, m, a, NoRoot{}, T);
             }
         }))
@@ -382,27 +413,17 @@ static hipError_t launch_table_lpk(const IbfDev& f, const uint64_t* k, size_t n,
     return hipGetLastError();
 }
 
-// Rows a call of n k-mers may give the table, 0: the plain path (the host's half of the gate; the device decides from D).
-static constexpr uint32_t kTableRatio = 4;  // n / D at which the table pays: (h + 1) / (h - 1) = 2 at h = 3, with margin
-static size_t table_capacity(const IbfDev& f, const Knobs& kn, size_t n) {
-    if (kn.probe_table == 0 || kn.kmer_table_mb <= 0 || (f.bin_size >> 32) || f.stride < 2 || (f.stride & 1) || f.hash_funs < 2)
-        return 0;
-    const size_t budget = ((size_t)kn.kmer_table_mb << 20) / ((size_t)f.stride * 8);
-    size_t cap = kn.probe_table == 1 ? std::max<size_t>(n, 1 << 16) : n / kTableRatio;
-    cap = std::min(cap, budget) & ~(size_t)63;
-    if (kn.probe_table != 1 && cap < (1 << 14)) return 0;  // a batch this small does not pay for three launches
-    return cap;
-}
-
 hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* k, size_t n, uint64_t* m, uint64_t* a, hipStream_t s) {
     const IbfDev& f = ix.ibf[0];
-    const size_t cap = n && f.shard_words ? table_capacity(f, kn, n) : 0;
+    const size_t cap = n && f.shard_words ? table_capacity(kn.probe_table, kn.kmer_table_mb, f.bin_size, f.stride, f.hash_funs, n) : 0;
     if (!cap) return launch_probe(f, k, n, m, a, s);
     Index::ProbeTable& pt = ix.probe_table;
     // one table per index: a call on another stream (txq_probe's second stream, another host thread) waits for the
-    // answer of the call before it; the lock keeps (wait, launches, record) of two host threads apart
+    // answer of the call before it — which may have extended the table this call reads, and zeroed its sample words; the
+    // lock keeps (wait, launches, record) of two host threads apart, and txq_emplace_device's change of the bits from both
     std::lock_guard<std::mutex> lock(pt.mutex);
     if (pt.refused) return launch_probe(f, k, n, m, a, s);
+    bool reallocated = false;
     if (pt.cap_rows < cap) {
         if (pt.rows) {  // growing: the kernels of an earlier call may still read the old table
             if (pt.recorded) (void)hipEventSynchronize(pt.done);
@@ -410,34 +431,42 @@ hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* k, size_t n, u
             pt.rows = nullptr;
             pt.cap_rows = 0;
         }
-        if (!pt.dom && hipMalloc((void**)&pt.dom, 2 * sizeof(uint32_t)) != hipSuccess) pt.dom = nullptr;
+        if (!pt.state && hipMalloc((void**)&pt.state, kStateWords * sizeof(uint32_t)) != hipSuccess) pt.state = nullptr;
         if (!pt.done && hipEventCreateWithFlags(&pt.done, hipEventDisableTiming) != hipSuccess) pt.done = nullptr;
-        if (!pt.dom || !pt.done || hipMalloc((void**)&pt.rows, cap * f.stride * 8) != hipSuccess) {
+        if (!pt.state || !pt.done || hipMalloc((void**)&pt.rows, cap * f.stride * 8) != hipSuccess) {
             (void)hipGetLastError();  // (out of memory is not an error of this call: the rows are gathered as before)
             pt.rows = nullptr;
             pt.refused = true;
             return launch_probe(f, k, n, m, a, s);
         }
         pt.cap_rows = cap;
+        reallocated = true;
     }
     if (pt.recorded) {
         hipError_t e = hipStreamWaitEvent(s, pt.done, 0);
         if (e != hipSuccess) return e;
     }
-    const uint32_t ratio = kn.probe_table == 1 ? 0u : kTableRatio;
+    const ProbeCall call = plan_probe_call(pt.keep, ix.generation, reallocated, kn.probe_table_keep);
+    pt.keep.valid = false;  // until this call's launches are through: a call after a failed one zeroes the state words again
+    if (call.zero_state) {  // on this call's stream, like everything else: later calls are ordered behind it by `done`
+        hipError_t e = hipMemsetAsync(pt.state, 0, kStateWords * sizeof(uint32_t), s);
+        if (e != hipSuccess) return e;
+    }
+    const TableArgs T{pt.rows, pt.state, kn.probe_table == 1 ? 0u : kTableRatio, (uint32_t)pt.cap_rows, call.parity, call.fresh ? 1u : 0u};
     const uint32_t chunks = f.stride >> 1;
     hipError_t e;
-    if (chunks <= 1) e = launch_table_lpk<1>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
-    else if (chunks <= 2) e = launch_table_lpk<2>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
-    else if (chunks <= 4) e = launch_table_lpk<4>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
-    else if (chunks <= 8) e = launch_table_lpk<8>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
-    else if (chunks <= 16) e = launch_table_lpk<16>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
-    else if (chunks <= 32) e = launch_table_lpk<32>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
-    else e = launch_table_lpk<64>(f, k, n, m, a, pt.rows, pt.dom, (uint32_t)cap, ratio, s);
+    if (chunks <= 1) e = launch_table_lpk<1>(f, k, n, m, a, T, (uint32_t)cap, s);
+    else if (chunks <= 2) e = launch_table_lpk<2>(f, k, n, m, a, T, (uint32_t)cap, s);
+    else if (chunks <= 4) e = launch_table_lpk<4>(f, k, n, m, a, T, (uint32_t)cap, s);
+    else if (chunks <= 8) e = launch_table_lpk<8>(f, k, n, m, a, T, (uint32_t)cap, s);
+    else if (chunks <= 16) e = launch_table_lpk<16>(f, k, n, m, a, T, (uint32_t)cap, s);
+    else if (chunks <= 32) e = launch_table_lpk<32>(f, k, n, m, a, T, (uint32_t)cap, s);
+    else e = launch_table_lpk<64>(f, k, n, m, a, T, (uint32_t)cap, s);
     if (e != hipSuccess) return e;
     e = hipEventRecord(pt.done, s);
     if (e != hipSuccess) return e;
     pt.recorded = true;
+    pt.keep.valid = true;
     return hipSuccess;
 }
 
