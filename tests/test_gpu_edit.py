@@ -155,6 +155,45 @@ def test_device_entry_point_on_a_stream(capi):
     del rng
 
 
+def test_text_that_is_not_16_byte_aligned(capi, monkeypatch):
+    """txq_edit_search_device on a text that begins 1, 7 and 15 bytes behind a 16-byte boundary: records of 40, 0 and 150 bytes,
+    patterns of 8 and 70 bytes (one and two words), chunks of 16 bytes.  The 16-byte blocks at either end of the text are
+    assembled from byte loads; the bytes around the text are letters, so a block that took them in would change the answer."""
+    import torch
+    from tetrex_amd import host
+    monkeypatch.setenv("TXQ_EDIT_CHUNK", "16")
+    rng = np.random.default_rng(17)
+    codes = E.letter_codes("ACGT")
+    text = edit_cases.random_text(rng, "ACGT", 190, junk=0)
+    records = [text[:40].tobytes(), b"", text[40:].tobytes()]
+    swap = bytes.maketrans(b"ACGTacgt", b"CATGcatg")
+    cut8, cut70 = text[20:28].tobytes(), text[100:170].tobytes()  # from the first record and from the last, one and two substitutions
+    patterns = [cut8[:3] + cut8[3:4].translate(swap) + cut8[4:], cut70[:9] + cut70[9:10].translate(swap) + cut70[10:40] + cut70[40:41].translate(swap) + cut70[41:]]
+    groups, pairs = [0, 3], [(0, 0, 2), (1, 0, 2)]
+    want = E.search(patterns, records, groups, pairs, codes)
+    assert want.tolist() == [[1, 0, 28], [2, 2, 130]]
+    pat, po, txt, ro, go, pr, cd = capi.edit_arrays(patterns, records, groups, pairs, codes)
+    assert np.array_equal(host.edit_search((pat, po), (txt, ro), go, pr, cd), want)
+    dev = torch.device("cuda:0")
+    t = [torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).to(dev) for x in (pat, po, txt, ro, go, pr, cd)]
+    work = torch.empty(capi.edit_workspace_bytes(pr.shape[0]) // 8, dtype=torch.int64, device=dev)
+    results = {}
+    for at in (0, 1, 7, 15):
+        around = torch.full((at + txt.size + 33,), ord("A"), dtype=torch.uint8, device=dev)
+        shifted = around[at:at + txt.size]
+        shifted.copy_(t[2])
+        assert shifted.data_ptr() % 16 == at
+        out = torch.zeros(pr.shape[0] * 12, dtype=torch.uint8, device=dev)
+        capi.check(capi.lib().txq_edit_search_device(t[0].data_ptr(), t[1].data_ptr(), po.size - 1, pat.size, shifted.data_ptr(), t[3].data_ptr(),
+                                                      ro.size - 1, txt.size, t[4].data_ptr(), go.size - 1, t[5].data_ptr(), pr.shape[0],
+                                                      t[6].data_ptr(), out.data_ptr(), work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        torch.cuda.synchronize(dev)
+        results[at] = out.cpu().numpy().view(np.uint32).reshape(-1, 3)
+    for at in (1, 7, 15):
+        assert results[at].tolist() == results[0].tolist(), at
+    assert _differing(results[0], want, pairs) == ([], 0)
+
+
 def test_refusals_leave_the_library_usable(capi):
     codes = E.letter_codes("ACGT")
     records, groups = ["ACGTACGT", "TTTT"], [0, 1, 2]

@@ -120,6 +120,45 @@ def test_unbounded_automaton_and_serial_cap(capi, automata, monkeypatch, chunk):
     _same(capi.regex_filter(automata, recs, [0, len(recs)], pairs), want)
 
 
+def test_text_that_is_not_16_byte_aligned(capi, automata, monkeypatch):
+    """txq_regex_filter_device on a text that begins 1, 7 and 15 bytes behind a 16-byte boundary: records of 40, 0 and 150 bytes,
+    a bounded and an unbounded automaton, chunks of 16 bytes.  The 16-byte blocks at either end of the text are assembled from
+    byte loads; the byte in front of the text would complete ACCT and the byte behind it LMAEGLYN, were they taken in."""
+    import torch
+    monkeypatch.setenv("TXQ_REGEX_CHUNK", "16")
+    rng = np.random.default_rng(6)
+    filler = lambda n: "".join(rng.choice(list("WYQ"), size=n))
+    recs = ["CCT" + filler(9) + "LMAEGLYN" + filler(20), "", filler(60) + "AGGGT" + filler(78) + "LMAEGLY"]
+    assert [len(r) for r in recs] == [40, 0, 150]
+    recs, groups, pairs = [r.encode() for r in recs], [0, 3], [(0, 0), (1, 0)]
+    blobs = [automata[LDS], automata[3]]  # (LMAEGLYN), bounded; (A(C+|G+)T), unbounded
+    want, want_status = host.regex_filter(blobs, recs, groups, pairs, return_status=True)
+    assert [w.tolist() for w in want] == [[True, False, False], [False, False, True]] and want_status.tolist() == [0, 0]
+    arena, ao, txt, ro, go, pr, oo, n_words = host.regex_filter_arrays(blobs, recs, groups, pairs)
+    dev = torch.device("cuda:0")
+    t = [torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).to(dev) for x in (arena, ao, txt, ro, go, pr, oo)]
+    work = torch.empty(capi.regex_workspace_bytes(len(pairs)) // 8, dtype=torch.int64, device=dev)
+    results = {}
+    for at in (0, 1, 7, 15):
+        around = torch.full((at + txt.size + 33,), ord("N"), dtype=torch.uint8, device=dev)
+        around[:at] = ord("A")
+        shifted = around[at:at + txt.size]
+        shifted.copy_(t[2])
+        assert shifted.data_ptr() % 16 == at
+        out = torch.full((n_words,), -1, dtype=torch.int32, device=dev)
+        status = torch.full((len(pairs),), -1, dtype=torch.int32, device=dev)
+        capi.check(capi.lib().txq_regex_filter_device(t[0].data_ptr(), t[1].data_ptr(), ao.size - 1, arena.size, shifted.data_ptr(), t[3].data_ptr(),
+                                                       ro.size - 1, txt.size, t[4].data_ptr(), go.size - 1, t[5].data_ptr(), len(pairs), t[6].data_ptr(),
+                                                       out.data_ptr(), n_words, status.data_ptr(), work.data_ptr(),
+                                                       torch.cuda.current_stream(dev).cuda_stream))
+        torch.cuda.synchronize(dev)
+        results[at] = (out.cpu().numpy().view(np.uint32), status.cpu().numpy().view(np.uint32))
+    for at in (1, 7, 15):
+        assert results[at][0].tolist() == results[0][0].tolist() and results[at][1].tolist() == results[0][1].tolist(), at
+    assert results[0][1].tolist() == want_status.tolist()
+    _same(host.regex_filter_unpack(go, pr, oo, results[0][0], results[0][1]), want)
+
+
 def test_refused_pairs_leave_their_neighbours_alone(capi, automata, case):
     """a pair that names an automaton or a group out of range, and an automaton with a broken header: status
     TXQ_REGEX_REFUSED, no bit set, the pairs around them answered.  (The kernels check every offset against the sizes passed

@@ -134,6 +134,40 @@ def test_translate_device_entry_point(capi):
         b.free()
 
 
+def test_translate_device_sequence_that_is_not_16_byte_aligned(capi):
+    """txq_translate_device on a sequence that begins 1, 7 and 15 bytes behind a 16-byte boundary: records of 50 and 7 bytes,
+    k = 3.  The 16-byte blocks at either end of the sequence are staged from byte loads."""
+    from tetrex_amd import host
+    rng = np.random.default_rng(8)
+    records = [random_nt(rng, 50, 0.02), random_nt(rng, 7)]
+    seq, rec = capi._records(records)
+    k = 3
+    bound = capi.translate_bound(rec, k)
+    want_v, want_o = T.translate_records(records, k)
+    assert want_v.size > 50
+    d_rec, d_codes = capi.DeviceBuffer.from_numpy(rec), capi.DeviceBuffer.from_numpy(host.peptide_codes(0))
+    results = {}
+    for at in (0, 1, 7, 15):
+        around = np.full(at + seq.size + 33, ord("A"), dtype=np.uint8)
+        around[at:at + seq.size] = seq
+        d_seq = capi.DeviceBuffer.from_numpy(around)
+        assert d_seq.ptr % 16 == 0
+        d_val = capi.DeviceBuffer.from_numpy(np.full(bound + 8, 0xABABABABABABABAB, dtype=np.uint64))
+        d_off = capi.DeviceBuffer(8 * (6 * len(records) + 1))
+        capi.check(capi.lib().txq_translate_device(d_seq.ptr + at, d_rec.ptr, len(records), k, d_codes.ptr, d_val.ptr, d_off.ptr, None))
+        capi.synchronize()
+        results[at] = (d_val.to_numpy(np.uint64, (bound + 8,)), d_off.to_numpy(np.uint64, (6 * len(records) + 1,)))
+        for b in (d_seq, d_val, d_off):
+            b.free()
+    for at in (1, 7, 15):
+        assert np.array_equal(results[at][0], results[0][0]) and np.array_equal(results[at][1], results[0][1]), at
+    assert np.array_equal(results[0][1], want_o)
+    assert np.array_equal(results[0][0][:want_v.size], want_v)
+    assert (results[0][0][bound:] == np.uint64(0xABABABABABABABAB)).all()
+    d_rec.free()
+    d_codes.free()
+
+
 # ---- hit list -----------------------------------------------------------------------------------------------------------
 
 def numpy_list(hits, counts):

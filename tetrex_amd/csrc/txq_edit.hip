@@ -18,7 +18,7 @@
 //     max(record start, a - (m + min(e, m))) and only records scores at bytes of its own chunk.  Exact for every D[m][j] <= e:
 //     an alignment of cost <= e that ends at j begins no earlier than j - m - e + 1, and a later start only raises the
 //     value.  At a record's end the state is reset;
-//   * the text comes in 16-byte loads (byte loads only where the 16 bytes would leave the buffer);
+//   * the text comes in 16-byte loads (byte loads only where the 16 bytes would leave the buffer: txq_text.hpp load_block);
 //   * a result is one 64-bit key: distance << 48 | position, the position of end j of record r being (bytes of the group
 //     before r) + (records of the group before r) + j, so records and ends are ordered as the contract orders them and j = 0
 //     of a record differs from the end of the record before.  Lane minimum, wave minimum (shuffles), one atomicMin per unit;
@@ -27,9 +27,7 @@
 #include "../../include/txq.h"
 #include "txq_internal.hpp"
 #include "txq_scan.hpp"
-
-#include <cstdlib>
-#include <vector>
+#include "txq_text.hpp"
 
 namespace txq {
 namespace {
@@ -41,17 +39,11 @@ constexpr uint64_t kNoKey = ~0ULL;
 constexpr uint64_t kBadPair = ~0ULL - 1;    // a pair the plan kernel refused
 constexpr uint32_t kPosBits = 48;
 
-typedef uint32_t ed4 __attribute__((ext_vector_type(4)));
-
 struct EdArgs {
     const uint8_t* pat;
     const uint64_t* pat_off;
     uint64_t n_pat, pat_bytes;
-    const uint8_t* text;
-    const uint64_t* rec;
-    uint64_t n_rec, text_bytes;
-    const uint64_t* grp;
-    uint64_t n_grp;
+    TextGroups t;
     const uint32_t* pairs;
     uint64_t n_pairs;
     const uint8_t* codes;
@@ -72,16 +64,13 @@ __device__ __forceinline__ PairView view_pair(const EdArgs& a, uint64_t i) {
     PairView v{};
     const uint32_t p = a.pairs[3 * i], g = a.pairs[3 * i + 1];
     v.e = a.pairs[3 * i + 2];
-    if (p >= a.n_pat || g >= a.n_grp) return v;
+    if (p >= a.n_pat) return v;
     const uint64_t p0 = a.pat_off[p], p1 = a.pat_off[p + 1];
     if (p1 > a.pat_bytes || p0 >= p1 || p1 - p0 > kMaxPattern) return v;
-    const uint64_t r0 = a.grp[g], r1 = a.grp[g + 1];
-    if (r0 > r1 || r1 > a.n_rec) return v;
-    const uint64_t gs = a.rec[r0], ge = a.rec[r1];
-    if (gs > ge || ge > a.text_bytes) return v;
-    v.ok = true;
+    const GroupView gv = view_group(a.t, g);
+    v.ok = gv.ok;
     v.m = (uint32_t)(p1 - p0);
-    v.p0 = p0, v.r0 = r0, v.r1 = r1, v.gs = gs, v.ge = ge;
+    v.p0 = p0, v.r0 = gv.r0, v.r1 = gv.r1, v.gs = gv.gs, v.ge = gv.ge;
     return v;
 }
 
@@ -94,35 +83,12 @@ __global__ __launch_bounds__(256) void edit_plan_kernel(EdArgs a) {
     const PairView v = view_pair(a, i);
     uint64_t units = 0, key = kBadPair;
     if (v.ok) {
-        const uint64_t per_unit = 64ull * a.chunk;
-        units = (v.ge - v.gs + per_unit - 1) / per_unit;
+        units = units_of(v.ge - v.gs, 64, a.chunk);
         // end 0 of the group's first record: distance m, the lowest position there is
         key = v.r1 > v.r0 && v.m <= v.e ? (uint64_t)v.m << kPosBits : kNoKey;
     }
     a.pref[i + 1] = units;
     a.keys[i] = key;
-}
-
-// the pair that owns unit u: the first i with pref[i + 1] > u (u < pref[n])
-__device__ __forceinline__ uint64_t pair_of_unit(const uint64_t* pref, uint64_t n, uint64_t u) {
-    uint64_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (pref[mid + 1] > u) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// the record of [r0, r1) that holds byte x (rec[r0] <= x < rec[r1]): the last r with rec[r] <= x
-__device__ __forceinline__ uint64_t record_of(const uint64_t* rec, uint64_t r0, uint64_t r1, uint64_t x) {
-    uint64_t lo = r0 + 1, hi = r1;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (rec[mid] > x) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo - 1;
 }
 
 template <int W>
@@ -136,7 +102,7 @@ __global__ __launch_bounds__(64) void edit_kernel(EdArgs a) {
         const uint8_t c = a.codes[i];
         codes[i] = c < 31 ? c : (uint8_t)31;
     }
-    const uintptr_t text_lo = (uintptr_t)a.text, text_hi = text_lo + a.text_bytes;
+    const uintptr_t text_lo = (uintptr_t)a.t.text, text_hi = text_lo + a.t.text_bytes;
     for (uint64_t u = blockIdx.x; u < total; u += gridDim.x) {
         const uint64_t pair = pair_of_unit(a.pref, a.n_pairs, u);
         const PairView v = view_pair(a, pair);
@@ -154,12 +120,11 @@ __global__ __launch_bounds__(64) void edit_kernel(EdArgs a) {
         const uint32_t m = v.m, e = v.e;
         const uint32_t hw = (m - 1) >> 6, hs = (m - 1) & 63;
         const uint64_t lead = (uint64_t)m + (e < m ? e : m);
-        const uint64_t ca = v.gs + (slice * 64 + lane) * (uint64_t)a.chunk;
-        const uint64_t cb = ca + a.chunk < v.ge ? ca + a.chunk : v.ge;
+        const auto [ca, cb] = chunk_bounds(v.gs, v.ge, slice, 64, lane, a.chunk);
         uint64_t best = kNoKey;
         if (ca < v.ge) {
-            uint64_t r = record_of(a.rec, v.r0, v.r1, ca);
-            uint64_t rs = a.rec[r], re = a.rec[r + 1];
+            uint64_t r = record_of(a.t.rec, v.r0, v.r1, ca);
+            uint64_t rs = a.t.rec[r], re = a.t.rec[r + 1];
             // (offsets that do not ascend cannot take a load outside [gs, ge): every byte index below stays in [start, cb))
             if (rs < v.gs || rs > ca) rs = ca;
             const uint64_t start = ca - rs > lead ? ca - lead : rs;
@@ -169,30 +134,18 @@ __global__ __launch_bounds__(64) void edit_kernel(EdArgs a) {
             uint32_t score = m;
             const uintptr_t first = (text_lo + start) & ~(uintptr_t)15, last = text_lo + cb;
             for (uintptr_t blk = first; blk < last; blk += 16) {
-                ed4 raw;
-                if (blk >= text_lo && blk + 16 <= text_hi) raw = *reinterpret_cast<const ed4*>(blk);
-                else {
-                    uint32_t q[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                    for (int b = 0; b < 16; ++b)
-                        if (blk + b >= text_lo && blk + b < text_hi) q[b >> 2] |= (uint32_t)*reinterpret_cast<const uint8_t*>(blk + b) << (8 * (b & 3));
-                    raw = ed4{q[0], q[1], q[2], q[3]};
-                }
+                const TextBlock raw = load_block(blk, text_lo, text_hi, 0);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const uint32_t word = q == 0 ? raw.x : q == 1 ? raw.y : q == 2 ? raw.z : raw.w;
+                    const uint32_t word = raw.w[q];
 #pragma nounroll
                     for (uint32_t b = 0; b < 4; ++b) {
-                        // The byte's index in the text.  Where the block begins below text_lo (the buffer is not 16-byte
-                        // aligned), blk - text_lo is -k in unsigned arithmetic, k = 1..15: the bytes below text_lo get an index
-                        // of 2^64 - k + offset >= cb and are skipped, the bytes at and above it wrap back to their true index
-                        // offset - k.  The record-boundary handling below relies on t being exact there.
-                        const uint64_t t = (uint64_t)(blk - text_lo) + 4u * q + b;
+                        const uint64_t t = raw.t0 + 4u * q + b;  // (bytes below text_lo: an index >= cb, see load_block)
                         if (t < start || t >= cb) continue;
                         if (t >= re) {  // the record ended: a fresh state in the next one that has bytes
                             do {
                                 ++r;
-                                re = r + 1 <= v.r1 ? a.rec[r + 1] : v.ge;
+                                re = r + 1 <= v.r1 ? a.t.rec[r + 1] : v.ge;
                             } while (t >= re && r + 1 < v.r1);
                             if (re > v.ge || t >= re) re = v.ge;
 #pragma unroll
@@ -252,25 +205,17 @@ __global__ __launch_bounds__(256) void edit_finish_kernel(EdArgs a) {
         uint64_t lo = v.r0 + 1, hi = v.r1;
         while (lo < hi) {
             const uint64_t mid = (lo + hi) >> 1;
-            if (a.rec[mid] - v.gs + (mid - v.r0) > pos) hi = mid;
+            if (a.t.rec[mid] - v.gs + (mid - v.r0) > pos) hi = mid;
             else lo = mid + 1;
         }
         const uint64_t rr = lo - 1;
         d = (uint32_t)(key >> kPosBits);
         r = (uint32_t)rr;
-        j = (uint32_t)(pos - (a.rec[rr] - v.gs + (rr - v.r0)));
+        j = (uint32_t)(pos - (a.t.rec[rr] - v.gs + (rr - v.r0)));
     }
     a.out[3 * i] = d;
     a.out[3 * i + 1] = r;
     a.out[3 * i + 2] = j;
-}
-
-uint32_t chunk_knob() {
-    const char* e = std::getenv("TXQ_EDIT_CHUNK");
-    long long c = e && *e ? std::atoll(e) : (long long)kDefaultChunk;
-    if (c < (long long)kMinChunk) c = kMinChunk;
-    if (c > (long long)kMaxChunk) c = kMaxChunk;
-    return (uint32_t)((c + 15) / 16 * 16);
 }
 
 int edit_args(const void* pat_off, const void* rec, const void* grp, const void* pairs, size_t n_pairs, size_t n_records, size_t text_bytes,
@@ -299,8 +244,9 @@ int txq_edit_search_device(const uint8_t* d_patterns, const uint64_t* d_pat_offs
     if (n_pairs == 0) return TXQ_OK;
     hipStream_t st = (hipStream_t)stream;
     void* scratch = d_workspace;  // keys and prefix: TXQ_EDIT_WORKSPACE(n_pairs) bytes of the caller's
-    const EdArgs a{d_patterns, d_pat_offsets, n_patterns, pattern_bytes, d_text, d_rec_offsets, n_records, text_bytes, d_group_offsets, n_groups,
-                   d_pairs, n_pairs, d_codes, d_out, (uint64_t*)scratch, (uint64_t*)scratch + n_pairs, chunk_knob()};
+    const uint32_t chunk = (env_u32("TXQ_EDIT_CHUNK", kDefaultChunk, kMinChunk, kMaxChunk) + 15) / 16 * 16;
+    const EdArgs a{d_patterns, d_pat_offsets, n_patterns, pattern_bytes, {d_text, d_rec_offsets, n_records, text_bytes, d_group_offsets, n_groups},
+                   d_pairs, n_pairs, d_codes, d_out, (uint64_t*)scratch, (uint64_t*)scratch + n_pairs, chunk};
     const unsigned per_pair = (unsigned)((n_pairs + 255) / 256);
     edit_plan_kernel<<<per_pair, 256, 0, st>>>(a);
     scan_kernel<<<1, 1024, 0, st>>>(a.pref + 1, n_pairs);
@@ -318,13 +264,9 @@ int txq_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t
                     size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
                     const uint8_t* codes, uint32_t* out) {
     if (!pat_offsets || !rec_offsets || !group_offsets) return fail(TXQ_ERR_ARG, "null argument");
-    for (size_t p = 0; p < n_patterns; ++p)
-        if (pat_offsets[p + 1] < pat_offsets[p]) return fail(TXQ_ERR_ARG, "pattern offsets are not ascending at pattern %zu", p);
-    for (size_t r = 0; r < n_records; ++r)
-        if (rec_offsets[r + 1] < rec_offsets[r]) return fail(TXQ_ERR_ARG, "record offsets are not ascending at record %zu", r);
-    for (size_t g = 0; g < n_groups; ++g)
-        if (group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > n_records)
-            return fail(TXQ_ERR_ARG, "group offsets are not ascending within the records at group %zu", g);
+    if (int rc = check_ascending(pat_offsets, n_patterns, "pattern")) return rc;
+    if (int rc = check_ascending(rec_offsets, n_records, "record")) return rc;
+    if (int rc = check_ascending(group_offsets, n_groups, "group", "records", n_records)) return rc;
     const uint64_t pat0 = pat_offsets[0], pat_bytes = pat_offsets[n_patterns] - pat0;
     const uint64_t text0 = rec_offsets[0], text_bytes = rec_offsets[n_records] - text0;
     if (int rc = edit_args(pat_offsets, rec_offsets, group_offsets, pairs, n_pairs, n_records, text_bytes, codes, out)) return rc;
@@ -337,40 +279,26 @@ int txq_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t
     }
     if (int rc = require_init()) return rc;
     if (n_pairs == 0) return TXQ_OK;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_pat = up(pat_bytes + 16), b_po = up((n_patterns + 1) * 8), b_text = up(text_bytes + 16), b_rec = up((n_records + 1) * 8),
-                 b_grp = up((n_groups + 1) * 8), b_pairs = up(n_pairs * 12), b_codes = 256, b_out = up(n_pairs * 12), b_work = up(TXQ_EDIT_WORKSPACE(n_pairs));
-    unsigned char* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, b_pat + b_po + b_text + b_rec + b_grp + b_pairs + b_codes + b_out + b_work);
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc");
-    unsigned char* at = d;
-    auto take = [&](size_t b) { unsigned char* p = at; at += b; return p; };
-    uint8_t* d_pat = take(b_pat);
-    uint64_t* d_po = (uint64_t*)take(b_po);
-    uint8_t* d_text = take(b_text);
-    uint64_t* d_rec = (uint64_t*)take(b_rec);
-    uint64_t* d_grp = (uint64_t*)take(b_grp);
-    uint32_t* d_pairs = (uint32_t*)take(b_pairs);
-    uint8_t* d_codes = take(b_codes);
-    uint32_t* d_out = (uint32_t*)take(b_out);
-    void* d_work = take(b_work);
-    std::vector<uint64_t> po(pat_offsets, pat_offsets + n_patterns + 1), ro(rec_offsets, rec_offsets + n_records + 1);
-    for (uint64_t& o : po) o -= pat0;
-    for (uint64_t& o : ro) o -= text0;
+    DeviceStage d;  // (+16: the kernels' 16-byte loads of patterns and text end inside the slice)
+    const size_t s_pat = d.add(pat_bytes + 16), s_po = d.add((n_patterns + 1) * 8), s_text = d.add(text_bytes + 16), s_rec = d.add((n_records + 1) * 8),
+                 s_grp = d.add((n_groups + 1) * 8), s_pairs = d.add(n_pairs * 12), s_codes = d.add(256), s_out = d.add(n_pairs * 12),
+                 s_work = d.add(TXQ_EDIT_WORKSPACE(n_pairs));
+    if (const hipError_t e = d.alloc(); e != hipSuccess) return fail_hip(e, "hipMalloc");
+    const std::vector<uint64_t> po = rebased(pat_offsets, n_patterns), ro = rebased(rec_offsets, n_records);
+    d.upload(s_pat, patterns + pat0, pat_bytes);
+    d.upload(s_po, po.data(), po.size() * 8);
+    d.upload(s_text, text + text0, text_bytes);
+    d.upload(s_rec, ro.data(), ro.size() * 8);
+    d.upload(s_grp, group_offsets, (n_groups + 1) * 8);
+    d.upload(s_pairs, pairs, n_pairs * 12);
+    d.upload(s_codes, codes, 256);
     int rc = TXQ_OK;
-    if (pat_bytes) e = hipMemcpy(d_pat, patterns + pat0, pat_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_po, po.data(), po.size() * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && text_bytes) e = hipMemcpy(d_text, text + text0, text_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_rec, ro.data(), ro.size() * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_grp, group_offsets, (n_groups + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pairs, pairs, n_pairs * 12, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_codes, codes, 256, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        rc = txq_edit_search_device(d_pat, d_po, n_patterns, pat_bytes, d_text, d_rec, n_records, text_bytes, d_grp, n_groups, d_pairs, n_pairs,
-                                    d_codes, d_out, d_work, nullptr);
-    if (e == hipSuccess && rc == TXQ_OK) e = hipMemcpy(out, d_out, n_pairs * 12, hipMemcpyDeviceToHost);  // (waits for the kernels)
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail_hip(e, "txq_edit_search copies");
+    if (d.error() == hipSuccess)
+        rc = txq_edit_search_device(d.at<uint8_t>(s_pat), d.at<uint64_t>(s_po), n_patterns, pat_bytes, d.at<uint8_t>(s_text), d.at<uint64_t>(s_rec), n_records,
+                                    text_bytes, d.at<uint64_t>(s_grp), n_groups, d.at<uint32_t>(s_pairs), n_pairs, d.at<uint8_t>(s_codes),
+                                    d.at<uint32_t>(s_out), d.at<void>(s_work), nullptr);
+    if (rc == TXQ_OK) d.download(out, s_out, n_pairs * 12);  // (waits for the kernels)
+    if (d.error() != hipSuccess) return fail_hip(d.error(), "txq_edit_search copies");
     return rc;
 }
 

@@ -278,6 +278,60 @@ int fail_hip(hipError_t e, const char* what);
 int ensure(void** p, size_t* cap, size_t bytes);
 int alloc_ibf(const txq_ibf_desc& d, uint64_t w0, uint64_t w1, IbfDev* out, uint64_t* bytes);
 
+// An environment variable as a number in [lo, hi]; `def` where it is unset or empty.  For the knobs that are read per call
+// (TXQ_EDIT_CHUNK, TXQ_REGEX_CHUNK, TXQ_REGEX_MAX_SERIAL: tests change them between calls), not at the entry points above.
+inline uint32_t env_u32(const char* name, uint32_t def, uint32_t lo, uint32_t hi) {
+    const char* e = std::getenv(name);
+    const long long c = e && *e ? std::atoll(e) : (long long)def;
+    return (uint32_t)(c < (long long)lo ? lo : c > (long long)hi ? hi : c);
+}
+
+// off[0 .. n] ascend — and stay at or below `upper`, the size of the array `within` that they point into, where one is given
+inline int check_ascending(const uint64_t* off, size_t n, const char* what, const char* within = nullptr, uint64_t upper = UINT64_MAX) {
+    for (size_t i = 0; i < n; ++i)
+        if (off[i + 1] < off[i] || off[i + 1] > upper)
+            return within ? fail(TXQ_ERR_ARG, "%s offsets are not ascending within the %s at %s %zu", what, within, what, i)
+                          : fail(TXQ_ERR_ARG, "%s offsets are not ascending at %s %zu", what, what, i);
+    return TXQ_OK;
+}
+// off[0 .. n] as the device form takes them: counted from off[0]
+inline std::vector<uint64_t> rebased(const uint64_t* off, size_t n) {
+    std::vector<uint64_t> v(off, off + n + 1);
+    for (uint64_t& o : v) o -= off[0];
+    return v;
+}
+
+// The device side of a host-buffer call (txq_translate, txq_edit_search, txq_regex_filter): add() the buffers' sizes, alloc()
+// makes ONE allocation and every buffer a 256-byte aligned slice of it, upload / download are synchronous copies that do
+// nothing once a call has failed — error() is the first failure —, and the destructor frees.
+class DeviceStage {
+public:
+    size_t add(size_t bytes) {
+        const size_t at = total_;
+        total_ += (bytes + 255) & ~(size_t)255;
+        return at;
+    }
+    hipError_t alloc() { return err_ = hipMalloc((void**)&base_, total_); }
+    template <class T>
+    T* at(size_t slice) const { return reinterpret_cast<T*>(base_ + slice); }
+    void upload(size_t slice, const void* src, size_t bytes) {
+        if (err_ == hipSuccess && bytes) err_ = hipMemcpy(base_ + slice, src, bytes, hipMemcpyHostToDevice);
+    }
+    void download(void* dst, size_t slice, size_t bytes) {
+        if (err_ == hipSuccess && bytes) err_ = hipMemcpy(dst, base_ + slice, bytes, hipMemcpyDeviceToHost);
+    }
+    hipError_t error() const { return err_; }
+    ~DeviceStage() { (void)hipFree(base_); }
+    DeviceStage() = default;
+    DeviceStage(const DeviceStage&) = delete;
+    DeviceStage& operator=(const DeviceStage&) = delete;
+
+private:
+    unsigned char* base_ = nullptr;
+    size_t total_ = 0;
+    hipError_t err_ = hipSuccess;
+};
+
 // txq_probe.hip
 hipError_t launch_probe(const IbfDev& f, const uint64_t* kmers, size_t n, uint64_t* masks, uint64_t* alive, hipStream_t s);
 // txq_probe_device on a flat index: launch_probe, or the domain-table path where the batch's k-mer domain is small

@@ -3,7 +3,7 @@
 // include/txq.h, the automaton and what "matches" means in include/txq_regex.h: the kernel steps through txq_regex_step, the
 // same function the host twin (txh_regex_filter) and the CPU tests run.
 //
-// Mapping to the machine (the pattern of txq_edit.hip):
+// Mapping to the machine (units, prefix and clipped loads: see txq_text.hpp):
 //   * a pair's text is the bytes of its group's records, back to back.  regex_plan_kernel checks the pair, writes its status and
 //     cuts the text into units of 256 lane chunks of `chunk` bytes (TXQ_REGEX_CHUNK); scan_kernel (txq_scan.hpp) turns the unit
 //     counts into a prefix; the grid of regex_kernel is persistent: a workgroup of four waves takes units u = block, block +
@@ -28,9 +28,7 @@
 #include "../../include/txq_regex.h"
 #include "txq_internal.hpp"
 #include "txq_scan.hpp"
-
-#include <cstdlib>
-#include <vector>
+#include "txq_text.hpp"
 
 namespace txq {
 namespace {
@@ -47,11 +45,7 @@ struct RxArgs {
     const uint8_t* arena;
     const uint64_t* aoff;
     uint64_t n_auto, arena_bytes;
-    const uint8_t* text;
-    const uint64_t* rec;
-    uint64_t n_rec, text_bytes;
-    const uint64_t* grp;
-    uint64_t n_grp;
+    TextGroups t;
     const uint32_t* pairs;
     uint64_t n_pairs;
     const uint64_t* out_off;
@@ -72,20 +66,17 @@ struct PairView {
 __device__ __forceinline__ PairView view_pair(const RxArgs& a, uint64_t i) {
     PairView v{};
     const uint32_t p = a.pairs[2 * i], g = a.pairs[2 * i + 1];
-    if (p >= a.n_auto || g >= a.n_grp) return v;
+    if (p >= a.n_auto) return v;
     const uint64_t a0 = a.aoff[p], a1 = a.aoff[p + 1];
     if (a0 > a1 || a1 > a.arena_bytes || (a0 & 15) || a1 - a0 < TXQ_REGEX_TABLES) return v;
     const uint32_t* hw = reinterpret_cast<const uint32_t*>(a.arena + a0);
     const uint32_t h[8] = {hw[0], hw[1], hw[2], hw[3], hw[4], hw[5], hw[6], hw[7]};
     if (!txq_regex_header(h, (size_t)(a1 - a0), &v.rx)) return v;
-    const uint64_t r0 = a.grp[g], r1 = a.grp[g + 1];
-    if (r0 > r1 || r1 > a.n_rec) return v;
-    const uint64_t gs = a.rec[r0], ge = a.rec[r1];
-    if (gs > ge || ge > a.text_bytes) return v;
-    const uint64_t o = a.out_off[i], words = (r1 - r0 + 31) / 32;
-    if (o > a.out_words || words > a.out_words - o) return v;
-    v.ok = true;
-    v.a0 = a0, v.r0 = r0, v.r1 = r1, v.gs = gs, v.ge = ge, v.o = o;
+    const GroupView gv = view_group(a.t, g);
+    if (!gv.ok) return v;
+    const uint64_t o = a.out_off[i], words = (gv.r1 - gv.r0 + 31) / 32;
+    v.ok = o <= a.out_words && words <= a.out_words - o;
+    v.a0 = a0, v.r0 = gv.r0, v.r1 = gv.r1, v.gs = gv.gs, v.ge = gv.ge, v.o = o;
     return v;
 }
 
@@ -98,67 +89,30 @@ __global__ __launch_bounds__(256) void regex_plan_kernel(RxArgs a) {
     const PairView v = view_pair(a, i);
     uint64_t units = 0;
     if (v.ok && v.r1 > v.r0) {
-        const uint64_t per_unit = (uint64_t)kBlock * a.chunk;
-        units = (v.ge - v.gs + per_unit - 1) / per_unit;
+        units = units_of(v.ge - v.gs, kBlock, a.chunk);
         if (units == 0) units = 1;  // records of no bytes still want their answer
     }
     a.pref[i + 1] = units;
     a.status[i] = v.ok ? 0u : TXQ_REGEX_REFUSED;
 }
 
-// the pair that owns unit u: the first i with pref[i + 1] > u (u < pref[n])
-__device__ __forceinline__ uint64_t pair_of_unit(const uint64_t* pref, uint64_t n, uint64_t u) {
-    uint64_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (pref[mid + 1] > u) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// the record of [r0, r1) that holds byte x (rec[r0] <= x < rec[r1]): the last r with rec[r] <= x
-__device__ __forceinline__ uint64_t record_of(const uint64_t* rec, uint64_t r0, uint64_t r1, uint64_t x) {
-    uint64_t lo = r0 + 1, hi = r1;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (rec[mid] > x) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo - 1;
-}
-
 // The automaton over text[p0, p1) from state s (p1 <= text_bytes): 16-byte loads, the state looked at once per load.
 __device__ __forceinline__ uint32_t scan_bytes(const txq_regex_view& v, uintptr_t text_lo, uintptr_t text_hi, uint64_t p0, uint64_t p1, uint32_t s) {
     const uintptr_t first = (text_lo + p0) & ~(uintptr_t)15, last = text_lo + p1;
     for (uintptr_t blk = first; blk < last && s > TXQ_REGEX_ACCEPT; blk += 16) {
-        const bool inside = blk >= text_lo && blk + 16 <= text_hi;
-        rx4 raw;
-        if (inside) raw = *reinterpret_cast<const rx4*>(blk);
-        else {
-            uint32_t q[4] = {0u, 0u, 0u, 0u};
+        const TextBlock raw = load_block(blk, text_lo, text_hi, 0);
+        if (raw.whole && raw.t0 >= p0 && raw.t0 + 16 <= p1) {
 #pragma unroll
-            for (int b = 0; b < 16; ++b)
-                if (blk + b >= text_lo && blk + b < text_hi) q[b >> 2] |= (uint32_t)*reinterpret_cast<const uint8_t*>(blk + b) << (8 * (b & 3));
-            raw = rx4{q[0], q[1], q[2], q[3]};
-        }
-        // The first byte's index in the text.  Where the block begins below text_lo (the buffer is not 16-byte aligned) this is
-        // -k in unsigned arithmetic: the bytes below text_lo get an index >= p1 and are skipped, the others wrap to their own.
-        const uint64_t t0 = (uint64_t)(blk - text_lo);
-        if (inside && t0 >= p0 && t0 + 16 <= p1) {
+            for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t word = q == 0 ? raw.x : q == 1 ? raw.y : q == 2 ? raw.z : raw.w;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) s = txq_regex_step(v, s, (uint8_t)(word >> (8 * b)));
-            }
+                for (int b = 0; b < 4; ++b) s = txq_regex_step(v, s, (uint8_t)(raw.w[q] >> (8 * b)));
         } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const uint32_t word = q == 0 ? raw.x : q == 1 ? raw.y : q == 2 ? raw.z : raw.w;
+                const uint32_t word = raw.w[q];
 #pragma nounroll
                 for (uint32_t b = 0; b < 4; ++b) {
-                    const uint64_t t = t0 + 4u * q + b;
+                    const uint64_t t = raw.t0 + 4u * q + b;  // (bytes below text_lo: an index >= p1, see load_block)
                     if (t >= p0 && t < p1) s = txq_regex_step(v, s, (uint8_t)(word >> (8 * b)));
                 }
             }
@@ -173,7 +127,7 @@ __global__ __launch_bounds__(256) void regex_kernel(RxArgs a) {
     constexpr uint32_t kTier = kLds == kSmallLds ? 0u : kLds == kLargeLds ? 1u : 2u;
     const uint32_t tid = threadIdx.x;
     const uint64_t total = a.pref[a.n_pairs];
-    const uintptr_t text_lo = (uintptr_t)a.text, text_hi = text_lo + a.text_bytes;
+    const uintptr_t text_lo = (uintptr_t)a.t.text, text_hi = text_lo + a.t.text_bytes;
     for (uint64_t u = blockIdx.x; u < total; u += gridDim.x) {
         const uint64_t pair = pair_of_unit(a.pref, a.n_pairs, u);
         const PairView v = view_pair(a, pair);
@@ -193,17 +147,16 @@ __global__ __launch_bounds__(256) void regex_kernel(RxArgs a) {
         const auto flag = [&](uint64_t r) { atomicOr(bits + ((r - v.r0) >> 5), 1u << ((r - v.r0) & 31)); };
         // a record offset as the kernel uses it: inside the group's bytes whatever the array holds
         const auto at = [&](uint64_t r) {
-            const uint64_t x = a.rec[r];
+            const uint64_t x = a.t.rec[r];
             return x < v.gs ? v.gs : x > v.ge ? v.ge : x;
         };
         if (slice == 0 && txq_regex_accepts_at_end(rx, rx.start_begin))  // the records of no bytes
             for (uint64_t r = v.r0 + tid; r < v.r1; r += kBlock)
                 if (at(r + 1) <= at(r)) flag(r);
 
-        const uint64_t ca = v.gs + (slice * kBlock + tid) * (uint64_t)a.chunk;
-        const uint64_t cb = ca + a.chunk < v.ge ? ca + a.chunk : v.ge;
+        const auto [ca, cb] = chunk_bounds(v.gs, v.ge, slice, kBlock, tid, a.chunk);
         if (ca >= v.ge) continue;
-        uint64_t r = record_of(a.rec, v.r0, v.r1, ca);
+        uint64_t r = record_of(a.t.rec, v.r0, v.r1, ca);
         if (rx.lmax != TXQ_REGEX_UNBOUNDED) {
             const uint64_t lead = rx.lmax ? rx.lmax - 1 : 0;
             uint64_t pos = ca;
@@ -232,22 +185,6 @@ __global__ __launch_bounds__(256) void regex_kernel(RxArgs a) {
             }
         }
     }
-}
-
-uint32_t chunk_knob() {
-    const char* e = std::getenv("TXQ_REGEX_CHUNK");
-    long long c = e && *e ? std::atoll(e) : (long long)kDefaultChunk;
-    if (c < (long long)kMinChunk) c = kMinChunk;
-    if (c > (long long)kMaxChunk) c = kMaxChunk;
-    return (uint32_t)((c + 15) / 16 * 16);
-}
-
-uint32_t serial_knob() {
-    const char* e = std::getenv("TXQ_REGEX_MAX_SERIAL");
-    long long c = e && *e ? std::atoll(e) : (long long)kDefaultSerial;
-    if (c < 1) c = 1;
-    if (c > 0x7FFFFFFFll) c = 0x7FFFFFFFll;
-    return (uint32_t)c;
 }
 
 int regex_args(const void* aoff, const void* rec, const void* grp, const void* pairs, size_t n_pairs, size_t n_records, const void* out_off,
@@ -281,8 +218,10 @@ int txq_regex_filter_device(const uint8_t* d_automata, const uint64_t* d_auto_of
         if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
     }
     if (n_pairs == 0) return TXQ_OK;
-    const RxArgs a{d_automata, d_auto_offsets, n_automata, automata_bytes, d_text, d_rec_offsets, n_records, text_bytes, d_group_offsets, n_groups,
-                   d_pairs, n_pairs, d_out_offsets, d_out, out_words, d_status, (uint64_t*)d_workspace, chunk_knob(), serial_knob()};
+    const uint32_t chunk = (env_u32("TXQ_REGEX_CHUNK", kDefaultChunk, kMinChunk, kMaxChunk) + 15) / 16 * 16;
+    const RxArgs a{d_automata, d_auto_offsets, n_automata, automata_bytes, {d_text, d_rec_offsets, n_records, text_bytes, d_group_offsets, n_groups},
+                   d_pairs, n_pairs, d_out_offsets, d_out, out_words, d_status, (uint64_t*)d_workspace, chunk,
+                   env_u32("TXQ_REGEX_MAX_SERIAL", kDefaultSerial, 1, 0x7FFFFFFFu)};
     regex_plan_kernel<<<(unsigned)((n_pairs + 255) / 256), 256, 0, st>>>(a);
     scan_kernel<<<1, 1024, 0, st>>>(a.pref + 1, n_pairs);
     regex_kernel<kSmallLds><<<kCus * 8, kBlock, 0, st>>>(a);
@@ -297,13 +236,9 @@ int txq_regex_filter(const uint8_t* automata, const uint64_t* auto_offsets, size
                      size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
                      const uint64_t* out_offsets, uint32_t* out, size_t out_words, uint32_t* status) {
     if (!auto_offsets || !rec_offsets || !group_offsets) return fail(TXQ_ERR_ARG, "null argument");
-    for (size_t p = 0; p < n_automata; ++p)
-        if (auto_offsets[p + 1] < auto_offsets[p]) return fail(TXQ_ERR_ARG, "automaton offsets are not ascending at automaton %zu", p);
-    for (size_t r = 0; r < n_records; ++r)
-        if (rec_offsets[r + 1] < rec_offsets[r]) return fail(TXQ_ERR_ARG, "record offsets are not ascending at record %zu", r);
-    for (size_t g = 0; g < n_groups; ++g)
-        if (group_offsets[g + 1] < group_offsets[g] || group_offsets[g + 1] > n_records)
-            return fail(TXQ_ERR_ARG, "group offsets are not ascending within the records at group %zu", g);
+    if (int rc = check_ascending(auto_offsets, n_automata, "automaton")) return rc;
+    if (int rc = check_ascending(rec_offsets, n_records, "record")) return rc;
+    if (int rc = check_ascending(group_offsets, n_groups, "group", "records", n_records)) return rc;
     const uint64_t arena0 = auto_offsets[0], arena_bytes = auto_offsets[n_automata] - arena0;
     const uint64_t text0 = rec_offsets[0], text_bytes = rec_offsets[n_records] - text0;
     if (int rc = regex_args(auto_offsets, rec_offsets, group_offsets, pairs, n_pairs, n_records, out_offsets, out, out_words, status)) return rc;
@@ -325,43 +260,27 @@ int txq_regex_filter(const uint8_t* automata, const uint64_t* auto_offsets, size
         if (out_offsets[i] > out_words || words > out_words - out_offsets[i]) return fail(TXQ_ERR_ARG, "pair %zu: its bitmap leaves the output", i);
     }
     if (int rc = require_init()) return rc;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_arena = up(arena_bytes + 16), b_ao = up((n_automata + 1) * 8), b_text = up(text_bytes + 16), b_rec = up((n_records + 1) * 8),
-                 b_grp = up((n_groups + 1) * 8), b_pairs = up(n_pairs * 8 + 8), b_oo = up(n_pairs * 8 + 8), b_out = up(out_words * 4 + 4),
-                 b_status = up(n_pairs * 4 + 4), b_work = up(TXQ_REGEX_WORKSPACE(n_pairs));
-    unsigned char* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, b_arena + b_ao + b_text + b_rec + b_grp + b_pairs + b_oo + b_out + b_status + b_work);
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc");
-    unsigned char* at = d;
-    auto take = [&](size_t b) { unsigned char* p = at; at += b; return p; };
-    uint8_t* d_arena = take(b_arena);
-    uint64_t* d_ao = (uint64_t*)take(b_ao);
-    uint8_t* d_text = take(b_text);
-    uint64_t* d_rec = (uint64_t*)take(b_rec);
-    uint64_t* d_grp = (uint64_t*)take(b_grp);
-    uint32_t* d_pairs = (uint32_t*)take(b_pairs);
-    uint64_t* d_oo = (uint64_t*)take(b_oo);
-    uint32_t* d_out = (uint32_t*)take(b_out);
-    uint32_t* d_status = (uint32_t*)take(b_status);
-    void* d_work = take(b_work);
-    std::vector<uint64_t> ao(auto_offsets, auto_offsets + n_automata + 1), ro(rec_offsets, rec_offsets + n_records + 1);
-    for (uint64_t& o : ao) o -= arena0;
-    for (uint64_t& o : ro) o -= text0;
+    DeviceStage d;  // (+16: the kernels' 16-byte loads of blobs and text end inside the slice; +8, +4: no slice of no bytes where n_pairs = 0)
+    const size_t s_arena = d.add(arena_bytes + 16), s_ao = d.add((n_automata + 1) * 8), s_text = d.add(text_bytes + 16), s_rec = d.add((n_records + 1) * 8),
+                 s_grp = d.add((n_groups + 1) * 8), s_pairs = d.add(n_pairs * 8 + 8), s_oo = d.add(n_pairs * 8 + 8), s_out = d.add(out_words * 4 + 4),
+                 s_status = d.add(n_pairs * 4 + 4), s_work = d.add(TXQ_REGEX_WORKSPACE(n_pairs));
+    if (const hipError_t e = d.alloc(); e != hipSuccess) return fail_hip(e, "hipMalloc");
+    const std::vector<uint64_t> ao = rebased(auto_offsets, n_automata), ro = rebased(rec_offsets, n_records);
+    d.upload(s_arena, automata + arena0, arena_bytes);
+    d.upload(s_ao, ao.data(), ao.size() * 8);
+    d.upload(s_text, text + text0, text_bytes);
+    d.upload(s_rec, ro.data(), ro.size() * 8);
+    d.upload(s_grp, group_offsets, (n_groups + 1) * 8);
+    d.upload(s_pairs, pairs, n_pairs * 8);
+    d.upload(s_oo, out_offsets, n_pairs * 8);
     int rc = TXQ_OK;
-    if (arena_bytes) e = hipMemcpy(d_arena, automata + arena0, arena_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_ao, ao.data(), ao.size() * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && text_bytes) e = hipMemcpy(d_text, text + text0, text_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_rec, ro.data(), ro.size() * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_grp, group_offsets, (n_groups + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_pairs) e = hipMemcpy(d_pairs, pairs, n_pairs * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_pairs) e = hipMemcpy(d_oo, out_offsets, n_pairs * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        rc = txq_regex_filter_device(d_arena, d_ao, n_automata, arena_bytes, d_text, d_rec, n_records, text_bytes, d_grp, n_groups, d_pairs, n_pairs,
-                                     d_oo, d_out, out_words, d_status, d_work, nullptr);
-    if (e == hipSuccess && rc == TXQ_OK && out_words) e = hipMemcpy(out, d_out, out_words * 4, hipMemcpyDeviceToHost);  // (waits for the kernels)
-    if (e == hipSuccess && rc == TXQ_OK && n_pairs) e = hipMemcpy(status, d_status, n_pairs * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail_hip(e, "txq_regex_filter copies");
+    if (d.error() == hipSuccess)
+        rc = txq_regex_filter_device(d.at<uint8_t>(s_arena), d.at<uint64_t>(s_ao), n_automata, arena_bytes, d.at<uint8_t>(s_text), d.at<uint64_t>(s_rec),
+                                     n_records, text_bytes, d.at<uint64_t>(s_grp), n_groups, d.at<uint32_t>(s_pairs), n_pairs, d.at<uint64_t>(s_oo),
+                                     d.at<uint32_t>(s_out), out_words, d.at<uint32_t>(s_status), d.at<void>(s_work), nullptr);
+    if (rc == TXQ_OK) d.download(out, s_out, out_words * 4);  // (waits for the kernels)
+    if (rc == TXQ_OK) d.download(status, s_status, n_pairs * 4);
+    if (d.error() != hipSuccess) return fail_hip(d.error(), "txq_regex_filter copies");
     return rc;
 }
 

@@ -1,5 +1,5 @@
 // One-workgroup inclusive scan, shared by the translation units that turn per-item counts into offsets on the device
-// (txq_translate.hip: frame and hit-list offsets; txq_edit.hip: the pairs' work units).
+// (txq_translate.hip: frame and hit-list offsets; txq_edit.hip and txq_regex.hip: the pairs' work units).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

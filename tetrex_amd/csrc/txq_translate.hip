@@ -26,8 +26,7 @@
 #include "../../include/txq.h"
 #include "txq_internal.hpp"
 #include "txq_scan.hpp"
-
-#include <vector>
+#include "txq_text.hpp"
 
 namespace txq {
 namespace {
@@ -42,8 +41,6 @@ constexpr uint8_t kStop = 0xFF;
 
 // NCBI translation table 1, codon index 16 a + 4 b + c with T = 0, C = 1, A = 2, G = 3
 __constant__ char kTable1[65] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
-
-typedef uint32_t tx4 __attribute__((ext_vector_type(4)));
 
 struct TrArgs {
     const uint8_t* seq;
@@ -60,17 +57,6 @@ __device__ __forceinline__ uint64_t chunk_len(uint64_t total) {
     const uint64_t c = (total + kUnits - 1) / kUnits;
     const uint64_t tiles = (c + kTile - 1) / kTile;
     return tiles * kTile < kMinChunk ? kMinChunk : tiles * kTile;
-}
-
-// the record that holds byte x (rec[0] <= x < rec[n]): the last r with rec[r] <= x
-__device__ __forceinline__ uint64_t record_of(const uint64_t* rec, uint64_t n, uint64_t x) {
-    uint64_t lo = 1, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (rec[mid] > x) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo - 1;
 }
 
 // T/U = 0, C = 1, A = 2, G = 3 in either case; anything else is ambiguous (4).  The complement is code ^ 2.
@@ -108,7 +94,7 @@ __global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
 
     uint32_t cnt[6] = {0u, 0u, 0u, 0u, 0u, 0u};  // (count) windows of the current record in this unit: forward j, reverse j
     bool runs_on = false;                        // the current record runs past the unit's end
-    for (uint64_t r = record_of(a.rec, a.n, ua); r < a.n; ++r) {
+    for (uint64_t r = record_of(a.rec, 0, a.n, ua); r < a.n; ++r) {
         const uint64_t rs = a.rec[r];
         if (rs >= ub) break;
         const uint64_t re = a.rec[r + 1], L = re - rs;
@@ -147,20 +133,13 @@ __global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
             }
         }
         for (uint64_t t0 = lo / 3 * 3; t0 < hi; t0 += kTile) {
-            // stage the step's bytes: 16-byte loads where the whole chunk lies inside the sequence buffer
+            // stage the step's bytes: 16-byte blocks, 'N' for what lies outside the sequence buffer (txq_text.hpp load_block)
             const uintptr_t first = (uintptr_t)(a.seq + rs + t0);
             const uint32_t shift = (uint32_t)(first & 15u);
             const uint64_t left = L - t0;
             const uint32_t nbytes = left < kTile + span - 1 ? (uint32_t)left : kTile + span - 1;
-            if (lane < (shift + nbytes + 15u) / 16u) {
-                const uintptr_t p = first - shift + 16u * lane;
-                if (p >= seq_lo && p + 16 <= seq_hi) {
-                    *reinterpret_cast<tx4*>(raw + 16u * lane) = *reinterpret_cast<const tx4*>(p);
-                } else {
-                    for (uint32_t b = 0; b < 16; ++b)
-                        raw[16u * lane + b] = p + b >= seq_lo && p + b < seq_hi ? *reinterpret_cast<const uint8_t*>(p + b) : (uint8_t)'N';
-                }
-            }
+            if (lane < (shift + nbytes + 15u) / 16u)
+                *reinterpret_cast<text4*>(raw + 16u * lane) = load_block(first - shift + 16u * lane, seq_lo, seq_hi, 'N').w;
             __syncthreads();
             for (uint32_t i = lane; i < kTile + span - 3; i += 64) {
                 uint8_t f = kStop, g = kStop;  // (a codon that does not fit is never part of a window that fits)
@@ -314,12 +293,9 @@ uint64_t txq_translate_bound(const uint64_t* rec_offsets, size_t n_records, unsi
         (void)fail(TXQ_ERR_ARG, "txq_translate_bound: null offsets or k outside 1..12");
         return UINT64_MAX;
     }
+    if (check_ascending(rec_offsets, n_records, "record")) return UINT64_MAX;
     uint64_t bound = 0;
     for (size_t r = 0; r < n_records; ++r) {
-        if (rec_offsets[r + 1] < rec_offsets[r]) {
-            (void)fail(TXQ_ERR_ARG, "record offsets are not ascending at record %zu", r);
-            return UINT64_MAX;
-        }
         const uint64_t L = rec_offsets[r + 1] - rec_offsets[r];
         for (uint64_t o = 0; o < 3; ++o) {
             const uint64_t codons = L >= o ? (L - o) / 3 : 0;
@@ -360,30 +336,22 @@ int txq_translate(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_reco
     if ((bytes && !seq) || (bound && !values)) return fail(TXQ_ERR_ARG, "null argument");
     if (int rc = require_init()) return rc;
     const size_t m = 6 * n_records;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_seq = up(bytes + 16), b_rec = up((n_records + 1) * 8), b_codes = 256, b_off = up((m + 1) * 8), b_val = up(bound * 8 + 8);
-    unsigned char* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, b_seq + b_rec + b_codes + b_off + b_val);
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc");
-    uint8_t* d_seq = d;
-    uint64_t* d_rec = (uint64_t*)(d + b_seq);
-    uint8_t* d_codes = d + b_seq + b_rec;
-    uint64_t* d_off = (uint64_t*)(d + b_seq + b_rec + b_codes);
-    uint64_t* d_val = (uint64_t*)(d + b_seq + b_rec + b_codes + b_off);
-    std::vector<uint64_t> rebased(rec_offsets, rec_offsets + n_records + 1);
-    for (uint64_t& o : rebased) o -= first;
+    DeviceStage d;  // (+16: the kernels' 16-byte loads of the sequence end inside the slice; +8: no slice of no bytes)
+    const size_t s_seq = d.add(bytes + 16), s_rec = d.add((n_records + 1) * 8), s_codes = d.add(256), s_off = d.add((m + 1) * 8), s_val = d.add(bound * 8 + 8);
+    if (const hipError_t e = d.alloc(); e != hipSuccess) return fail_hip(e, "hipMalloc");
+    const std::vector<uint64_t> ro = rebased(rec_offsets, n_records);
+    d.upload(s_seq, seq + first, bytes);
+    d.upload(s_rec, ro.data(), ro.size() * 8);
+    d.upload(s_codes, codes, n_records ? 256 : 0);
     int rc = TXQ_OK;
-    if (bytes) e = hipMemcpy(d_seq, seq + first, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_rec, rebased.data(), rebased.size() * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_records) e = hipMemcpy(d_codes, codes, 256, hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = txq_translate_device(d_seq, d_rec, n_records, k, d_codes, d_val, d_off, nullptr);
-    if (e == hipSuccess && rc == TXQ_OK) e = hipMemcpy(offsets, d_off, (m + 1) * 8, hipMemcpyDeviceToHost);  // (waits for the kernels)
-    if (e == hipSuccess && rc == TXQ_OK && offsets[m]) {
+    if (d.error() == hipSuccess)
+        rc = txq_translate_device(d.at<uint8_t>(s_seq), d.at<uint64_t>(s_rec), n_records, k, d.at<uint8_t>(s_codes), d.at<uint64_t>(s_val), d.at<uint64_t>(s_off), nullptr);
+    if (rc == TXQ_OK) d.download(offsets, s_off, (m + 1) * 8);  // (waits for the kernels)
+    if (rc == TXQ_OK && d.error() == hipSuccess && offsets[m]) {
         if (offsets[m] > bound) rc = fail(TXQ_ERR_OVERFLOW, "translation produced more values than its bound");
-        else e = hipMemcpy(values, d_val, offsets[m] * 8, hipMemcpyDeviceToHost);
+        else d.download(values, s_val, offsets[m] * 8);
     }
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail_hip(e, "txq_translate copies");
+    if (d.error() != hipSuccess) return fail_hip(d.error(), "txq_translate copies");
     return rc;
 }
 
