@@ -64,6 +64,8 @@ extern "C" {
  *                                                     (unset: where the batch repeats its values often enough to pay for it)
  *   TXQ_PROBE_TABLE_KEEP=0                            that table is built from its first row on every call, not kept with the
  *                                                     index and extended (the rows never outlive txq_emplace_device either way)
+ *   TXQ_PROBE_TABLE_FUSED=0                           a call on kept rows runs three launches (sample, build, answer) like a first
+ *                                                     call, not the one launch that answers, counts and extends the table
  * (tests/test_gpu_knobs.py runs a workload under each of them against the oracle.) */
 
 typedef enum {

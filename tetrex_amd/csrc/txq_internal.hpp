@@ -76,6 +76,8 @@ struct Knobs {
     bool probe_nt = false;                            // TXQ_PROBE_NT
     int probe_table = -1;  // TXQ_PROBE_TABLE: 0 never the domain table of a flat probe, 1 whenever it fits (tests), unset: where it pays
     bool probe_table_keep = true;  // TXQ_PROBE_TABLE_KEEP=0: the domain table is built from row 0 on every call (A/B and tests)
+    bool probe_table_fused = true;  // TXQ_PROBE_TABLE_FUSED=0: a call on kept rows runs sample, build and answer, not the one launch that does all three (A/B and tests)
+    int probe_experiment = 0;       // TXQ_PROBE_EXPERIMENT, TXQ_EXPERIMENTS builds only: bit 0 the answer loads no rows, bit 1 it stores no masks (timing, wrong masks)
 };
 Knobs knobs();      // a copy of the snapshot taken at the last entry point (published under a lock: entry points run on several threads)
 void read_knobs();  // take it (txq_api.hip)
@@ -176,7 +178,7 @@ struct Index {
     // written under `mutex`.
     struct ProbeTable {
         uint64_t* rows = nullptr; size_t cap_rows = 0;  // [cap_rows][stride]
-        uint32_t* state = nullptr;                      // [kStateWords]: two sample accumulators {top, count}, `built`
+        uint32_t* state = nullptr;                      // [kStateWords]: sample accumulators, the valid-rows word twice, statistics (txq_probe_plan.hpp)
         ProbeKeep keep;                                 // the generation the rows belong to, the calls so far
         hipEvent_t done = nullptr;
         bool recorded = false, refused = false;         // (refused: the allocation failed once, not tried again)

@@ -18,19 +18,30 @@
 // Domain table (probe_flat, the path of txq_probe_device on a flat IBF): a batch whose values lie in a domain [0, D)
 // several times smaller than the batch holds each value n/D times, and every repeat gathers the same h rows again.  The row
 // T[v] = bulk_contains(v) depends on the index's bits and on nothing in the batch, so the table is kept with the index from
-// call to call and only EXTENDED: a device word `built` says that rows [0, built) hold the masks of the current bits.  Per call:
-//   1. probe_domain_kernel: a 1/16 sample of the k-mers -> D = 1 + the largest value below the call's capacity, and how
-//      many values lie below it (device words; the host gets no answer back, the call stays stream-ordered),
-//   2. probe_kernel<..., kBuild>: the values [built, D) probed into the table T[v] (row pitch = stride) - in the steady
-//      state nothing, every wave leaves at once,
-//   3. probe_kernel<..., kAnswer>: the same lane layout; a k-mer v < rows = max(built, D) reads ONE row T[v], any other k-mer
-//      gathers its h rows as above (when the domain does not pay, count < ratio * D, rows = built).  One thread stores
-//      built = rows and zeroes the sample words of the next call (two sets, used alternately: no memset launch).
-// Whether the rows are still valid is the host's decision, by API call order (txq_probe_plan.hpp plan_probe_call): the index
-// counts the calls that change its bits (txq_emplace_device), and a call that finds another count than the table was built for,
-// a table just (re)allocated, or TXQ_PROBE_TABLE_KEEP=0 is `fresh`: it builds from row 0 and does not read `built`.
-// Per probe of the answer: 8 (k-mer) + W*8 (table row) + W*8 (mask); per call n/2 bytes of sample, and (D - built) *
-// (h*W*8 + W*8) to extend the table.
+// call to call and only EXTENDED: a device word `valid` says that rows [0, valid) hold the masks of the current bits.
+// A call has one of three shapes (the host decides which, by API call order: txq_probe_plan.hpp plan_probe_call):
+//   fresh (first call, table (re)allocated, the index's bits changed - txq_emplace_device counts its calls -, a call before
+//   failed, TXQ_PROBE_TABLE_KEEP=0): three launches.
+//     1. probe_domain_kernel: a 1/16 sample of the k-mers -> D = 1 + the largest value below the call's capacity, and how
+//        many values lie below it (device words; the host gets no answer back, the call stays stream-ordered),
+//     2. probe_kernel<..., kBuild>: the values [0, D) probed into the table T[v] (row pitch = stride) - if the domain pays,
+//        count * 16 >= ratio * D,
+//     3. probe_kernel<..., kAnswer>: the plain kernel's lane layout; a k-mer v < rows reads ONE row T[v], any other k-mer
+//        gathers its h rows as above.
+//   kept: ONE launch of probe_kernel<..., kAnswer>, which also does what the other two did.  Every answer counts, exactly and
+//     for nothing in the steady state, the k-mers it had to gather although they lie below the call's capacity: a wave that
+//     met any adds {1 + the largest, how many} to the call's statistics.  The NEXT kept call reads them: with V = `valid` and
+//     E = top if the extension pays (count >= ratio * (top - V)), else V, its k-mers below V read their row, all others
+//     gather, and the values [V, E) are probed into the table by the same waves after the batch's tiles (the build's tiles).
+//     So an extension takes two calls: call c gathers the new values and counts them, call c + 1 gathers them again and
+//     builds their rows, call c + 2 reads them.
+//   kept, TXQ_PROBE_TABLE_FUSED=0: the three launches of a fresh call, on the rows the table holds (build [valid, D)).
+// One thread of every answer leaves `valid` = the rows valid after the call behind, and zeroes the words the next call adds
+// into.  `valid` has two copies, used alternately: a one-launch call writes the rows [V, E) in the launch that publishes E,
+// and a wave that read E there would read rows not yet written.  The statistics have three slots (add, read, zero).  No
+// state word is read by the waves of a launch and written in the same launch (txq_probe_plan.hpp probe_slots).
+// Per probe of the answer: 8 (k-mer) + W*8 (table row) + W*8 (mask); a fresh call n/2 bytes of sample, and per new row
+// h*W*8 + W*8 to extend the table.
 #include "txq_internal.hpp"
 #include "txq_probe_plan.hpp"
 #include <algorithm>
@@ -64,56 +75,65 @@ struct TreeRoot {
 };
 
 // The domain table of one call (see the header).  state: the words the kernels keep beside the table (txq_probe_plan.hpp
-// kState...): this call's sample {top, count} at kStateAcc + 2 * parity, `built` at kStateBuilt.
+// kState..., probe_slots): `slot` says which of them this call reads, adds into, stores and zeroes.
 struct TableArgs {
     uint64_t* table;  // T[v] at table + v * stride, v < rows
     uint32_t* state;
     uint32_t ratio, cap_rows;
-    uint32_t parity, fresh;
+    uint32_t cap;             // this call's capacity: the answer counts the k-mers in [rows, cap) it had to gather
+    uint32_t fresh, sampled;  // sampled: a domain pass and a build ran in front of the answer (fresh calls, TXQ_PROBE_TABLE_FUSED=0)
+    ProbeSlots slot;
+    uint32_t experiment;      // TXQ_EXPERIMENTS builds only (TXQ_PROBE_EXPERIMENT: timing experiments, wrong masks)
 };
+// the rows of a sampled call: the build writes [lo, rows), its answer reads [0, rows)
 __device__ __forceinline__ ProbeRows table_rows(const TableArgs& T) {
-    const uint32_t* acc = T.state + kStateAcc + 2u * T.parity;
-    return table_rows(T.fresh != 0, T.state[kStateBuilt], acc[0], acc[1], T.ratio, kDomainSample, T.cap_rows);
+    const uint32_t* acc = T.state + T.slot.acc;
+    return table_rows(T.fresh != 0, T.state[T.slot.valid_read], acc[0], acc[1], T.ratio, kDomainSample, T.cap_rows);
+}
+// the rows of an answer: k-mers below `valid` read their row, the launch itself builds [valid, rows) (a sampled call: nothing)
+__device__ __forceinline__ ProbeExtend answer_rows(const TableArgs& T) {
+    if (T.sampled) {
+        const uint32_t rows = table_rows(T).rows;
+        return ProbeExtend{rows, rows};
+    }
+    const uint32_t* stat = T.state + T.slot.stat_read;
+    return extend_rows(T.state[T.slot.valid_read], stat[0], stat[1], T.ratio, T.cap_rows);
 }
 enum ProbeMode { kPlain = 0, kBuild = 1, kAnswer = 2 };
 
-// LPK lanes per k-mer, H hash functions, U steps in flight.  Requires bin_size < 2^32 and an even
-// stride.  U*H independent 16-byte gathers per lane are issued before the first AND.
-// MODE kBuild: the k-mers are the values [lo, rows) of table_rows (no input; from the tile that holds lo), written to T.table
-// at row pitch stride (whole 16-byte chunks, plain stores: the answer reads them back); MODE kAnswer: k-mers below `rows`
-// read their row of T.table instead of gathering, and one thread leaves `built` and the next call's sample words behind.
-template <int LPK, int H, int U, bool NT, class ROOT = NoRoot, int MODE = kPlain>
-__global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __restrict__ kmers, size_t n,
-                                                    uint64_t* __restrict__ masks, uint64_t* __restrict__ alive, ROOT R = ROOT{},
-                                                    TableArgs T = TableArgs{}) {
+// What an answering wave learns about its k-mers in [rows, cap): 1 + the largest, and how many (wave-uniform).
+struct WaveStats { uint32_t top = 0, count = 0; };
+
+// One tile of probe_kernel: 64 consecutive k-mers, one wave.  LPK lanes per k-mer, H hash functions, U steps in flight.
+// U*H independent 16-byte gathers per lane are issued before the first AND.
+// MODE kBuild: the k-mers are the values of the tile themselves (no input), of which [lo, n) are written to `masks` = the table
+// at row pitch stride (whole 16-byte chunks, plain stores: an answer reads them back); MODE kAnswer: k-mers below `tab_rows`
+// read their row of `table` instead of gathering, and those in [cnt_lo, cnt_hi) are counted into `st`.
+template <int LPK, int H, int U, bool NT, class ROOT, int MODE>
+__device__ __forceinline__ void probe_tile(const IbfDev& f, const uint64_t* __restrict__ kmers, size_t n, uint64_t* __restrict__ masks,
+                                           uint64_t* __restrict__ alive, const ROOT& R, const uint64_t* __restrict__ table, uint32_t tab_rows,
+                                           uint32_t lo, uint32_t cnt_lo, uint32_t cnt_hi, WaveStats& st, uint32_t experiment, size_t tile) {
     constexpr int KPS = 64 / LPK;          // k-mers per step
     constexpr int UU = U < LPK ? U : LPK;  // a tile has LPK steps
     const int lane = threadIdx.x & 63;
     const int sub = lane % LPK, grp = lane / LPK;
     const uint32_t chunks = f.stride >> 1;
-    uint32_t tab_rows = 0;
-    size_t tile0 = 0;
-    if constexpr (MODE != kPlain) {
-        const ProbeRows tr = table_rows(T);
-        tab_rows = tr.rows;
-        if constexpr (MODE == kBuild) {
-            n = tr.rows;
-            tile0 = tr.lo >> 6;
-        } else if (blockIdx.x == 0 && threadIdx.x == 0) {
-            // (every wave computes the same rows whether it reads the old `built` or this one: txq_probe_plan.hpp)
-            T.state[kStateBuilt] = tr.rows;
-            uint32_t* next = T.state + kStateAcc + 2u * (T.parity ^ 1u);
-            next[0] = 0;
-            next[1] = 0;
-        }
-    }
-    const size_t n_tiles = (n + 63) >> 6;
-    const size_t n_waves = (size_t)gridDim.x * (blockDim.x >> 6);
-    for (size_t tile = tile0 + (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); tile < n_tiles; tile += n_waves) {
+    (void)experiment;
+    {
         const size_t base = tile << 6;
         const size_t mine = base + lane;
         const uint64_t v = MODE == kBuild ? (uint64_t)mine : mine < n ? __builtin_nontemporal_load(kmers + mine) : 0;
         const bool tab = MODE == kAnswer && mine < n && v < tab_rows;  // my k-mer's mask is row v of the table
+        if constexpr (MODE == kAnswer) {
+            const bool beyond = mine < n && v >= cnt_lo && v < cnt_hi;
+            const uint64_t b = __ballot(beyond);
+            if (b) {  // (in the steady state never)
+                uint32_t t = beyond ? (uint32_t)v + 1u : 0u;
+                for (int o = 32; o > 0; o >>= 1) t = max(t, (uint32_t)__shfl_xor((int)t, o));
+                st.top = max(st.top, (uint32_t)__builtin_amdgcn_readfirstlane((int)t));
+                st.count += (uint32_t)__popcll(b);
+            }
+        }
         uint32_t row[H];
         if (tab) {
             row[0] = (uint32_t)v;
@@ -133,6 +153,9 @@ __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __
             root_lo = (uint32_t)x;
             root_hi = (uint32_t)(x >> 32);
         }
+#ifdef TXQ_EXPERIMENTS
+        uint32_t sink = 0;  // (experiment bit 1: what the loads gave, one word per wave instead of the masks)
+#endif
         bool my_alive = false;
         for (int s = 0; s < LPK; s += UU) {
             uint32_t r[UU][H];
@@ -165,7 +188,13 @@ __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __
                             x[u][i] = u32x4{~0u, ~0u, ~0u, ~0u};
                             continue;
                         }
-                        const uint64_t* p = (MODE == kAnswer && t ? T.table : f.words) + (size_t)r[u][i] * f.stride + 2u * c;
+#ifdef TXQ_EXPERIMENTS
+                        if (MODE == kAnswer && (experiment & 1u)) {  // no table or row loads: the mask is a constant
+                            x[u][i] = u32x4{0x55555555u, 0x33333333u, 0x0f0f0f0fu, 0x00ff00ffu};
+                            continue;
+                        }
+#endif
+                        const uint64_t* p = (MODE == kAnswer && t ? table : f.words) + (size_t)r[u][i] * f.stride + 2u * c;
                         x[u][i] = NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)) : ld16(p);
                     }
                 }
@@ -179,8 +208,15 @@ __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __
                         acc.x &= m0; acc.y &= m0; acc.z &= m1; acc.w &= m1;
                     }
                     const size_t kidx = base + (s + u) * KPS + grp;
+#ifdef TXQ_EXPERIMENTS
+                    if (MODE == kAnswer && (experiment & 2u)) {  // no mask stores
+                        sink ^= acc.x ^ acc.y ^ acc.z ^ acc.w;
+                        nz[u] |= nonzero(acc);
+                        continue;
+                    }
+#endif
                     if (MODE == kBuild) {
-                        if (kidx < n) *reinterpret_cast<u32x4*>(masks + kidx * f.stride + 2u * c) = acc;
+                        if (kidx >= lo && kidx < n) *reinterpret_cast<u32x4*>(masks + kidx * f.stride + 2u * c) = acc;
                     } else if (kidx < n) store_chunk(f, masks, kidx, c, acc);
                     nz[u] |= nonzero(acc);
                 }
@@ -199,6 +235,57 @@ __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __
             const uint64_t bits = __ballot(my_alive && mine < n);
             if (lane == 0) alive[tile] = bits;
         }
+#ifdef TXQ_EXPERIMENTS
+        if (MODE == kAnswer && (experiment & 2u)) {
+            const uint64_t bits = __ballot(sink & 1u);
+            if (lane == 0) masks[base * f.shard_words] = bits;
+        }
+#endif
+    }
+}
+
+// A wave owns the tiles wave, wave + n_waves, ... of the batch.  Requires bin_size < 2^32 and an even stride.
+// MODE kBuild: the tiles are those of the values [lo, rows) of table_rows, written to T.table.
+// MODE kAnswer: the batch's tiles read the table below `valid`; then the tiles of the values [valid, rows) of answer_rows are
+// built into T.table as a second loop of the same waves (its registers are the larger of the two bodies, not their sum) -
+// nothing in a sampled call, whose build ran before.  Each wave that met k-mers in [rows, cap) adds them to this call's
+// statistics, and one thread leaves behind what the next call reads: `valid` = rows in the copy this launch does not read,
+// and the next call's statistics and sample words zeroed.
+template <int LPK, int H, int U, bool NT, class ROOT = NoRoot, int MODE = kPlain>
+__global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __restrict__ kmers, size_t n,
+                                                    uint64_t* __restrict__ masks, uint64_t* __restrict__ alive, ROOT R = ROOT{},
+                                                    TableArgs T = TableArgs{}) {
+    const size_t wave = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const size_t n_waves = (size_t)gridDim.x * (blockDim.x >> 6);
+    WaveStats st;
+    if constexpr (MODE == kPlain) {
+        const size_t n_tiles = (n + 63) >> 6;
+        for (size_t tile = wave; tile < n_tiles; tile += n_waves)
+            probe_tile<LPK, H, U, NT, ROOT, kPlain>(f, kmers, n, masks, alive, R, nullptr, 0, 0, 0, 0, st, 0, tile);
+    } else if constexpr (MODE == kBuild) {
+        const ProbeRows tr = table_rows(T);
+        const size_t n_tiles = ((size_t)tr.rows + 63) >> 6;
+        for (size_t tile = (tr.lo >> 6) + wave; tile < n_tiles; tile += n_waves)
+            probe_tile<LPK, H, U, NT, ROOT, kBuild>(f, nullptr, tr.rows, T.table, nullptr, R, nullptr, 0, tr.lo, 0, 0, st, 0, tile);
+    } else {
+        const ProbeExtend ex = answer_rows(T);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            T.state[T.slot.valid_write] = ex.rows;
+            T.state[T.slot.stat_zero] = 0;
+            T.state[T.slot.stat_zero + 1] = 0;
+            T.state[T.slot.acc_zero] = 0;
+            T.state[T.slot.acc_zero + 1] = 0;
+        }
+        const size_t n_tiles = (n + 63) >> 6;
+        for (size_t tile = wave; tile < n_tiles; tile += n_waves)
+            probe_tile<LPK, H, U, NT, ROOT, kAnswer>(f, kmers, n, masks, alive, R, T.table, ex.valid, 0, ex.rows, T.cap, st, T.experiment, tile);
+        if (st.count && (threadIdx.x & 63) == 0) {
+            atomicMax(T.state + T.slot.stat_add, st.top);
+            atomicAdd(T.state + T.slot.stat_add + 1, st.count);
+        }
+        const size_t x_tiles = ((size_t)ex.rows + 63) >> 6;
+        for (size_t tile = (ex.valid >> 6) + wave; tile < x_tiles; tile += n_waves)
+            probe_tile<LPK, H, U, NT, ROOT, kBuild>(f, nullptr, ex.rows, T.table, nullptr, R, nullptr, 0, ex.valid, 0, 0, st, 0, tile);
     }
 }
 
@@ -391,22 +478,24 @@ hipError_t launch_probe(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* 
 // The domain-table path (header comment).  T.ratio: the table is used when at least ratio * D k-mers of the batch lie below D
 // (0: whenever D fits the table).  The table holds T.cap_rows >= cap rows; the caller keeps other calls off it until the answer ran.
 template <int LPK>
-static hipError_t launch_table_lpk(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* m, uint64_t* a, const TableArgs& T, uint32_t cap,
-                                   hipStream_t s) {
-    // the sample: the heads of `segs` segments, each shared by as many blocks as give a thread at most kDomainLoads k-mers
-    const uint32_t segs = (uint32_t)std::min<size_t>(std::max<size_t>(n / 1024, 1), 512);
-    const size_t head = ((n + segs - 1) / segs + kDomainSample - 1) / kDomainSample;
-    const uint32_t parts = (uint32_t)std::max<size_t>((head + 256 * kDomainLoads - 1) / (256 * kDomainLoads), 1);
-    probe_domain_kernel<<<segs * parts, 256, 0, s>>>(k, n, cap, segs, parts, T.state + kStateAcc + 2u * T.parity);
-    // the build's grid covers the call's capacity (neither `built` nor D is known on the host); waves with nothing to do leave at once
-    const unsigned bgrid = (unsigned)std::min<size_t>(((size_t)cap + 255) / 256, 2048);
+static hipError_t launch_table_lpk(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* m, uint64_t* a, const TableArgs& T, hipStream_t s) {
+    // a build's grid covers the call's capacity (neither `valid` nor D is known on the host); waves with nothing to do leave at once
+    const unsigned bgrid = (unsigned)std::min<size_t>(((size_t)T.cap + 255) / 256, kBuildBlocks);
     const unsigned grid = grid_for((n + 63) / 64, 4);
-    // (one hash function: a table row would be the IBF's own row — table_capacity never sends such an index here)
+    if (T.sampled) {
+        // the sample: the heads of `segs` segments, each shared by as many blocks as give a thread at most kDomainLoads k-mers
+        const uint32_t segs = (uint32_t)std::min<size_t>(std::max<size_t>(n / 1024, 1), 512);
+        const size_t head = ((n + segs - 1) / segs + kDomainSample - 1) / kDomainSample;
+        const uint32_t parts = (uint32_t)std::max<size_t>((head + 256 * kDomainLoads - 1) / (256 * kDomainLoads), 1);
+        probe_domain_kernel<<<segs * parts, 256, 0, s>>>(k, n, T.cap, segs, parts, T.state + T.slot.acc);
+    }
+    // (one hash function: a table row would be the IBF's own row - table_capacity never sends such an index here)
     if (f.hash_funs < 2 || !with_hash_funs(f.hash_funs, [&](auto h) {
             constexpr int H = decltype(h)::value;
             if constexpr (H >= 2) {
-                probe_kernel<LPK, H, 2, false, NoRoot, kBuild><<<bgrid, 256, 0, s>>>(f, nullptr, 0, T.table, nullptr, NoRoot{}, T);
-                probe_kernel<LPK, H, 2, false, NoRoot, kAnswer><<<grid, 256, 0, s>>>(f, k, n, m, a, NoRoot{}, T);
+                if (T.sampled) probe_kernel<LPK, H, 2, false, NoRoot, kBuild><<<bgrid, 256, 0, s>>>(f, nullptr, 0, T.table, nullptr, NoRoot{}, T);
+                // a one-launch call builds too: a small batch that has to build many rows does not do it with a handful of blocks
+                probe_kernel<LPK, H, 2, false, NoRoot, kAnswer><<<T.sampled ? grid : std::max(grid, bgrid), 256, 0, s>>>(f, k, n, m, a, NoRoot{}, T);
             }
         }))
         return hipErrorInvalidValue;
@@ -452,16 +541,20 @@ hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* k, size_t n, u
         hipError_t e = hipMemsetAsync(pt.state, 0, kStateWords * sizeof(uint32_t), s);
         if (e != hipSuccess) return e;
     }
-    const TableArgs T{pt.rows, pt.state, kn.probe_table == 1 ? 0u : kTableRatio, (uint32_t)pt.cap_rows, call.parity, call.fresh ? 1u : 0u};
+    // a kept call is one launch: the answer counts what it had to gather and builds what the call before counted
+    // (TXQ_PROBE_TABLE_FUSED=0: sample, build and answer as in a fresh call, on the rows the table holds)
+    const bool sampled = call.fresh || !kn.probe_table_fused;
+    const TableArgs T{pt.rows, pt.state, kn.probe_table == 1 ? 0u : kTableRatio, (uint32_t)pt.cap_rows, (uint32_t)cap, call.fresh ? 1u : 0u,
+                      sampled ? 1u : 0u, probe_slots(pt.keep.calls - 1), (uint32_t)kn.probe_experiment};
     const uint32_t chunks = f.stride >> 1;
     hipError_t e;
-    if (chunks <= 1) e = launch_table_lpk<1>(f, k, n, m, a, T, (uint32_t)cap, s);
-    else if (chunks <= 2) e = launch_table_lpk<2>(f, k, n, m, a, T, (uint32_t)cap, s);
-    else if (chunks <= 4) e = launch_table_lpk<4>(f, k, n, m, a, T, (uint32_t)cap, s);
-    else if (chunks <= 8) e = launch_table_lpk<8>(f, k, n, m, a, T, (uint32_t)cap, s);
-    else if (chunks <= 16) e = launch_table_lpk<16>(f, k, n, m, a, T, (uint32_t)cap, s);
-    else if (chunks <= 32) e = launch_table_lpk<32>(f, k, n, m, a, T, (uint32_t)cap, s);
-    else e = launch_table_lpk<64>(f, k, n, m, a, T, (uint32_t)cap, s);
+    if (chunks <= 1) e = launch_table_lpk<1>(f, k, n, m, a, T, s);
+    else if (chunks <= 2) e = launch_table_lpk<2>(f, k, n, m, a, T, s);
+    else if (chunks <= 4) e = launch_table_lpk<4>(f, k, n, m, a, T, s);
+    else if (chunks <= 8) e = launch_table_lpk<8>(f, k, n, m, a, T, s);
+    else if (chunks <= 16) e = launch_table_lpk<16>(f, k, n, m, a, T, s);
+    else if (chunks <= 32) e = launch_table_lpk<32>(f, k, n, m, a, T, s);
+    else e = launch_table_lpk<64>(f, k, n, m, a, T, s);
     if (e != hipSuccess) return e;
     e = hipEventRecord(pt.done, s);
     if (e != hipSuccess) return e;
