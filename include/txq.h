@@ -19,6 +19,7 @@
  *   txq_count / _device     <- seqan::hibf membership_for(values, threshold) / counting_agent::bulk_count, the general form of
  *                              the one-value, threshold-1 call at include/index_hibf.h:142-147 (`tetrex search`)
  *   txq_edit_search / _device  (no counterpart: `tetrex search --verify` confirms candidate bins by edit distance)
+ *   txq_edit_search_long / _device  (the same for patterns of up to 4096 bytes, the pattern spread over the lanes of a wave)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every function returns 0 on success or a
  * negative txq_status; txq_last_error() gives the message for the calling thread.  Host buffers are
@@ -60,6 +61,7 @@ extern "C" {
  *                                                     which HIBF descent kernel runs, and its tiling
  *   TXQ_PROBE_BLOCKS_PER_CU, TXQ_PROBE_UNROLL, TXQ_PROBE_NT   grid and variant of the flat probe kernel
  *   TXQ_EDIT_CHUNK=<bytes>                            bytes of text per lane of the edit-distance kernel (txq_edit_search, below)
+ *   TXQ_EDIT_LONG_SPAN=<bytes>                        bytes of text per lane group of the long-pattern edit-distance kernel (txq_edit_search_long, below)
  *   TXQ_PROBE_TABLE=0|1                               a flat probe's table of its batch's k-mer domain: never | whenever it fits
  *                                                     (unset: where the batch repeats its values often enough to pay for it)
  *   TXQ_PROBE_TABLE_KEEP=0                            that table is built from its first row on every call, not kept with the
@@ -232,8 +234,8 @@ int txq_translate(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_reco
  * d*, j the lowest end position in r that reaches it — the number of bytes of r before the match's end, 0 for an empty
  * match; otherwise (a distance above the cap, a group of no records) all three are 0xFFFFFFFF.  Distances above the cap are
  * never reported.
- * Patterns of 1 .. TXQ_EDIT_MAX_PATTERN bytes run on the device (longer ones: txh_edit_search of include/txh.h, the same
- * semantics on the host).  txq_edit_search checks its host buffers first: m = 0, m > TXQ_EDIT_MAX_PATTERN, a pair that names a
+ * Patterns of 1 .. TXQ_EDIT_MAX_PATTERN bytes run here (up to TXQ_EDIT_LONG_MAX_PATTERN: txq_edit_search_long below; longer
+ * ones: txh_edit_search of include/txh.h, the same semantics on the host).  txq_edit_search checks its host buffers first: m = 0, m > TXQ_EDIT_MAX_PATTERN, a pair that names a
  * pattern or group out of range, offsets that do not ascend or leave their array, null pointers: TXQ_ERR_ARG, nothing
  * launched.  txq_edit_search_device cannot read its device buffers without waiting for them, so it returns TXQ_ERR_ARG only
  * for what it can see (null pointers, the size limits below) and the kernels check the rest: such a pair gets
@@ -254,6 +256,30 @@ int txq_edit_search_device(const uint8_t* d_patterns, const uint64_t* d_pat_offs
 int txq_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
                     size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
                     const uint8_t* codes, uint32_t* out);  /* host buffers, synchronous */
+
+/* The same for patterns of 1 .. TXQ_EDIT_LONG_MAX_PATTERN bytes (`tetrex search --verify` sends records of 513 .. 4096 letters
+ * here; DESIGN.md §12 "Long patterns").  Arguments, semantics, results, the refusal marker (0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFE),
+ * the size limits and the promises of the _device call — nothing allocated, nothing read back, nothing waited for, no load
+ * outside a buffer — are those of txq_edit_search / txq_edit_search_device above, word for word; only the limit on m differs:
+ * txq_edit_search_long returns TXQ_ERR_ARG for m = 0, m > TXQ_EDIT_LONG_MAX_PATTERN or a pair that names a missing pattern or
+ * group, the _device call marks such a pair in its result and answers the others.  Short patterns are accepted too (slower than
+ * above: a pattern of any length up to 1024 bytes occupies 16 lanes), so the two kernels can be checked against each other.
+ * The pattern's 64-bit words lie over the lanes of a wave, one word per lane, which is where the limit of 64 x 64 bytes comes
+ * from; longer patterns: txh_edit_search of include/txh.h.
+ * d_workspace: TXQ_EDIT_LONG_WORKSPACE(n_pairs) bytes of device memory, 8-byte aligned.
+ *   TXQ_EDIT_LONG_SPAN=<bytes>   the bytes of text one lane group walks (default 4096, a multiple of 16 in 16 .. 2^20; read at
+ *                                every call).  A group re-reads m + min(e, m) bytes in front of its span, 64 / G spans are one
+ *                                wave's unit of work (G = 16, 32 or 64 lanes by the pattern's length); the results do not
+ *                                depend on it (tests use 64 and 16 to cut small texts into many units). */
+#define TXQ_EDIT_LONG_MAX_PATTERN 4096
+#define TXQ_EDIT_LONG_WORKSPACE(n_pairs) (16 * (size_t)(n_pairs) + 8)
+int txq_edit_search_long_device(const uint8_t* d_patterns, const uint64_t* d_pat_offsets, size_t n_patterns, size_t pattern_bytes,
+                                const uint8_t* d_text, const uint64_t* d_rec_offsets, size_t n_records, size_t text_bytes,
+                                const uint64_t* d_group_offsets, size_t n_groups, const uint32_t* d_pairs, size_t n_pairs,
+                                const uint8_t* d_codes, uint32_t* d_out, void* d_workspace, void* stream);
+int txq_edit_search_long(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                         size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
+                         const uint8_t* codes, uint32_t* out);  /* host buffers, synchronous */
 
 /* Which records of a bin does a regular expression match?  (`tetrex query --gpu-verify`; not in the reference.)
  * An automaton is a blob of include/txq_regex.h, where its layout and the meaning of "matches" are stated (as code: the

@@ -23,6 +23,7 @@ SYMBOLS = [
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
     "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
+    "txq_edit_search_long", "txq_edit_search_long_device",
     "txq_regex_filter", "txq_regex_filter_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
@@ -88,6 +89,8 @@ def lib():
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.txq_edit_search.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.c_void_p, C.c_void_p]
+        L.txq_edit_search_long_device.argtypes = L.txq_edit_search_device.argtypes
+        L.txq_edit_search_long.argtypes = L.txq_edit_search.argtypes
         L.txq_regex_filter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
@@ -556,6 +559,24 @@ def edit_search(patterns, records, groups, pairs, codes):
     out = np.zeros((pr.shape[0], 3), dtype=np.uint32)
     check(lib().txq_edit_search(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
                                 go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], cd.ctypes.data, out.ctypes.data))
+    return out
+
+
+EDIT_LONG_MAX_PATTERN = 4096
+
+
+def edit_long_workspace(n_pairs):
+    """TXQ_EDIT_LONG_WORKSPACE: the device workspace txq_edit_search_long_device needs for n_pairs pairs"""
+    return 16 * int(n_pairs) + 8
+
+
+def edit_search_long(patterns, records, groups, pairs, codes):
+    """edit_search for patterns of up to EDIT_LONG_MAX_PATTERN bytes (txq_edit_search_long, include/txq.h): the same arguments,
+    the same results"""
+    pat, po, txt, ro, go, pr, cd = edit_arrays(patterns, records, groups, pairs, codes)
+    out = np.zeros((pr.shape[0], 3), dtype=np.uint32)
+    check(lib().txq_edit_search_long(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
+                                     go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], cd.ctypes.data, out.ctypes.data))
     return out
 
 

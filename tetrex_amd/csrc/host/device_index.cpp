@@ -851,11 +851,15 @@ void BinVerifier::verify(const std::vector<std::string>& queries, const std::vec
     std::vector<size_t> order(candidates.size()), on_host;
     std::iota(order.begin(), order.end(), (size_t)0);
     std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return candidates[x].bin < candidates[y].bin; });
-    std::vector<size_t> on_device;  // candidate of every `strands` pairs, by bin
+    // candidate of every `strands` pairs, by bin: records of up to TXQ_EDIT_MAX_PATTERN letters first, behind them those of up
+    // to TXQ_EDIT_LONG_MAX_PATTERN, which the long-pattern kernel answers (TETREX_VERIFY_LONG=0: the host, for A/B runs)
+    const char* long_env = std::getenv("TETREX_VERIFY_LONG");
+    const size_t device_max = long_env && long_env[0] == '0' && !long_env[1] ? TXQ_EDIT_MAX_PATTERN : TXQ_EDIT_LONG_MAX_PATTERN;
+    std::vector<size_t> on_device, on_long;
     for (size_t i : order) {
         const uint32_t q = candidates[i].query;
         const std::string& s = queries.at(q);
-        if (s.empty() || s.size() > TXQ_EDIT_MAX_PATTERN) { on_host.push_back(i); continue; }
+        if (s.empty() || s.size() > device_max) { on_host.push_back(i); continue; }
         if (pattern_of[q] == kNoPattern) {
             pattern_of[q] = (uint32_t)(pat_off.size() - 1);
             pat.append(s);
@@ -865,8 +869,11 @@ void BinVerifier::verify(const std::vector<std::string>& queries, const std::vec
                 pat_off.push_back(pat.size());
             }
         }
-        on_device.push_back(i);
+        (s.size() > TXQ_EDIT_MAX_PATTERN ? on_long : on_device).push_back(i);
     }
+    const size_t n_short = on_device.size();
+    on_device.insert(on_device.end(), on_long.begin(), on_long.end());
+    n_device_ += n_short, n_device_long_ += on_long.size(), n_host_ += on_host.size();
     // take the better strand of `strands` results (distance, record, end); + wins on equal distance
     const auto settle = [&](size_t i, const uint32_t* res, const std::vector<std::string>& names) {
         Hit& h = hits[i];
@@ -890,22 +897,24 @@ void BinVerifier::verify(const std::vector<std::string>& queries, const std::vec
             }
         const size_t n_patterns = pat_off.size() - 1;
         DevBuf d_pat(pat.size() + 16), d_po(pat_off.size() * 8), d_pairs(pairs.size() * 4), d_out(pairs.size() * 4);
+        static_assert(TXQ_EDIT_LONG_WORKSPACE(7) == TXQ_EDIT_WORKSPACE(7), "one workspace, cut the same way for either call");
         DevBuf d_work(TXQ_EDIT_WORKSPACE(pairs.size() / 3) + 8 * on_device.size());  // (every call its own part: they are all in flight at once)
         size_t n_calls = 0;
         txq_check(txq_memcpy_h2d(d_pat.p, pat.data(), pat.size()), "h2d");
         txq_check(txq_memcpy_h2d(d_po.p, pat_off.data(), pat_off.size() * 8), "h2d");
         txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
-        for (size_t a = 0; a < on_device.size();) {  // one call per bin: its records are one group
+        for (size_t a = 0; a < on_device.size();) {  // one call per bin and kernel: the bin's records are one group
             size_t b = a;
             const uint32_t bin = candidates[on_device[a]].bin;
-            while (b < on_device.size() && candidates[on_device[b]].bin == bin) ++b;
+            const bool is_long = a >= n_short;
+            while (b < (is_long ? on_device.size() : n_short) && candidates[on_device[b]].bin == bin) ++b;
             ResidentBins::Bin& e = bins_.resident(bin);
             const uint64_t* d_rec = (const uint64_t*)e.d_rec;
-            txq_check(txq_edit_search_device((const uint8_t*)d_pat.p, (const uint64_t*)d_po.p, n_patterns, pat.size(), (const uint8_t*)e.d_text, d_rec,
+            txq_check((is_long ? txq_edit_search_long_device : txq_edit_search_device)((const uint8_t*)d_pat.p, (const uint64_t*)d_po.p, n_patterns, pat.size(), (const uint8_t*)e.d_text, d_rec,
                                              e.n_records, e.text_bytes, d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * strands * a,
                                              (b - a) * strands, (const uint8_t*)d_codes_, (uint32_t*)d_out.p + 3 * strands * a,
                                              (unsigned char*)d_work.p + 16 * strands * a + 8 * n_calls++, nullptr),
-                      "txq_edit_search_device");
+                      is_long ? "txq_edit_search_long_device" : "txq_edit_search_device");
             a = b;
         }
         std::vector<uint32_t> out(pairs.size());

@@ -163,8 +163,11 @@ class ResidentBins {
 // index uses: on a peptide index every letter is a class of its own, on a nucleotide index A, C, G and T = U are, every
 // other byte matches nothing; a nucleotide record is tried on both strands (its reverse complement is a second pattern, in
 // which an ambiguous byte stays one).  A bin's FASTA is read when it is first a candidate and its records stay on the device
-// (ResidentBins).  Records longer than TXQ_EDIT_MAX_PATTERN are answered on the host (host/edit_distance.hpp), with
-// OpenMP over the pairs.  Needs txq_init (DeviceIndex::upload).
+// (ResidentBins).  Records of up to TXQ_EDIT_MAX_PATTERN letters go to txq_edit_search_device, those of up to
+// TXQ_EDIT_LONG_MAX_PATTERN to txq_edit_search_long_device (TETREX_VERIFY_LONG=0: to the host, as before that kernel
+// existed), one call per candidate bin each, all queued before the one copy back.  Longer records and empty ones are
+// answered on the host (host/edit_distance.hpp), with OpenMP over the pairs.  n_routed() counts the candidate pairs each of
+// the three routes answered.  Needs txq_init (DeviceIndex::upload).
 class BinVerifier {
   public:
     BinVerifier(const std::vector<std::string>& bin_paths, bool dna, uint32_t errors);
@@ -183,6 +186,8 @@ class BinVerifier {
     void verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits);
     size_t n_candidates() const { return n_candidates_; }
     size_t n_confirmed() const { return n_confirmed_; }
+    struct Routed { size_t device, device_long, host; };
+    Routed n_routed() const { return {n_device_, n_device_long_, n_host_}; }
 
   private:
     ResidentBins bins_;
@@ -190,7 +195,7 @@ class BinVerifier {
     uint32_t errors_;
     uint8_t codes_[256];
     void* d_codes_ = nullptr;
-    size_t n_candidates_ = 0, n_confirmed_ = 0;
+    size_t n_candidates_ = 0, n_confirmed_ = 0, n_device_ = 0, n_device_long_ = 0, n_host_ = 0;
 };
 
 // `tetrex query --gpu-verify`: which records of its candidate bins does a motif match at all?  Answered on the

@@ -628,6 +628,10 @@ int cmd_search(int argc, char** argv) {
     flush();
     out.flush();
     if (verbose && verify) std::cerr << "Verified: " << verifier->n_confirmed() << " of " << verifier->n_candidates() << " candidate pairs" << std::endl;
+    if (verify && std::getenv("TETREX_TRACE")) {
+        const BinVerifier::Routed n = verifier->n_routed();
+        std::cerr << "[tetrex search] verify routes: device " << n.device << ", device-long " << n.device_long << ", host " << n.host << std::endl;
+    }
     if (verbose) std::cerr << "Search time: " << (now() - t_start) << " s" << std::endl;
     return 0;
 }

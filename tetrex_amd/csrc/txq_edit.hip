@@ -24,10 +24,8 @@
 //     of a record differs from the end of the record before.  Lane minimum, wave minimum (shuffles), one atomicMin per unit;
 //     j = 0 (distance m) is put in by the plan kernel where m <= e.  edit_finish_kernel turns keys into (d, r, j).
 // Four instances (W = 1, 2, 4, 8), one launch each: a unit whose pattern has another word count is skipped.
-#include "../../include/txq.h"
-#include "txq_internal.hpp"
+#include "txq_edit_common.hpp"
 #include "txq_scan.hpp"
-#include "txq_text.hpp"
 
 namespace txq {
 namespace {
@@ -35,44 +33,6 @@ namespace {
 constexpr uint32_t kMaxPattern = TXQ_EDIT_MAX_PATTERN;
 constexpr uint32_t kDefaultChunk = 512, kMinChunk = 16, kMaxChunk = 1u << 20;
 constexpr uint32_t kGridBlocks = 256 * 16;  // waves of the persistent grid: 16 per CU
-constexpr uint64_t kNoKey = ~0ULL;
-constexpr uint64_t kBadPair = ~0ULL - 1;    // a pair the plan kernel refused
-constexpr uint32_t kPosBits = 48;
-
-struct EdArgs {
-    const uint8_t* pat;
-    const uint64_t* pat_off;
-    uint64_t n_pat, pat_bytes;
-    TextGroups t;
-    const uint32_t* pairs;
-    uint64_t n_pairs;
-    const uint8_t* codes;
-    uint32_t* out;
-    uint64_t* keys;  // n_pairs
-    uint64_t* pref;  // n_pairs + 1: pref[0] = 0, pref[i + 1] = units of pairs 0 .. i
-    uint32_t chunk;
-};
-
-// What a pair works on; ok = false: an index or an offset outside its array, m = 0 or m > kMaxPattern.
-struct PairView {
-    bool ok;
-    uint32_t m, e;
-    uint64_t p0, r0, r1, gs, ge;
-};
-
-__device__ __forceinline__ PairView view_pair(const EdArgs& a, uint64_t i) {
-    PairView v{};
-    const uint32_t p = a.pairs[3 * i], g = a.pairs[3 * i + 1];
-    v.e = a.pairs[3 * i + 2];
-    if (p >= a.n_pat) return v;
-    const uint64_t p0 = a.pat_off[p], p1 = a.pat_off[p + 1];
-    if (p1 > a.pat_bytes || p0 >= p1 || p1 - p0 > kMaxPattern) return v;
-    const GroupView gv = view_group(a.t, g);
-    v.ok = gv.ok;
-    v.m = (uint32_t)(p1 - p0);
-    v.p0 = p0, v.r0 = gv.r0, v.r1 = gv.r1, v.gs = gv.gs, v.ge = gv.ge;
-    return v;
-}
 
 __device__ __forceinline__ uint32_t words_of(uint32_t m) { return m <= 64 ? 1u : m <= 128 ? 2u : m <= 256 ? 4u : 8u; }
 
@@ -80,7 +40,7 @@ __global__ __launch_bounds__(256) void edit_plan_kernel(EdArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i == 0) a.pref[0] = 0;
     if (i >= a.n_pairs) return;
-    const PairView v = view_pair(a, i);
+    const PairView v = view_pair<kMaxPattern>(a, i);
     uint64_t units = 0, key = kBadPair;
     if (v.ok) {
         units = units_of(v.ge - v.gs, 64, a.chunk);
@@ -105,7 +65,7 @@ __global__ __launch_bounds__(64) void edit_kernel(EdArgs a) {
     const uintptr_t text_lo = (uintptr_t)a.t.text, text_hi = text_lo + a.t.text_bytes;
     for (uint64_t u = blockIdx.x; u < total; u += gridDim.x) {
         const uint64_t pair = pair_of_unit(a.pref, a.n_pairs, u);
-        const PairView v = view_pair(a, pair);
+        const PairView v = view_pair<kMaxPattern>(a, pair);
         if (!v.ok || words_of(v.m) != (uint32_t)W) continue;  // (uniform over the wave)
         const uint64_t slice = u - a.pref[pair];
         __syncthreads();  // the unit before is done with peq
@@ -192,40 +152,6 @@ __global__ __launch_bounds__(64) void edit_kernel(EdArgs a) {
     }
 }
 
-__global__ __launch_bounds__(256) void edit_finish_kernel(EdArgs a) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.n_pairs) return;
-    const uint64_t key = a.keys[i];
-    uint32_t d = 0xFFFFFFFFu, r = 0xFFFFFFFFu, j = 0xFFFFFFFFu;
-    if (key == kBadPair) r = j = 0xFFFFFFFEu;
-    else if (key != kNoKey) {
-        const PairView v = view_pair(a, i);
-        const uint64_t pos = key & ((1ULL << kPosBits) - 1);
-        // the last record of the group whose end 0 is at or before pos: position of (r, 0) = rec[r] - gs + (r - r0)
-        uint64_t lo = v.r0 + 1, hi = v.r1;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (a.t.rec[mid] - v.gs + (mid - v.r0) > pos) hi = mid;
-            else lo = mid + 1;
-        }
-        const uint64_t rr = lo - 1;
-        d = (uint32_t)(key >> kPosBits);
-        r = (uint32_t)rr;
-        j = (uint32_t)(pos - (a.t.rec[rr] - v.gs + (rr - v.r0)));
-    }
-    a.out[3 * i] = d;
-    a.out[3 * i + 1] = r;
-    a.out[3 * i + 2] = j;
-}
-
-int edit_args(const void* pat_off, const void* rec, const void* grp, const void* pairs, size_t n_pairs, size_t n_records, size_t text_bytes,
-              const void* codes, const void* out) {
-    if (!pat_off || !rec || !grp || !codes || (n_pairs && (!pairs || !out))) return fail(TXQ_ERR_ARG, "null argument");
-    if (n_pairs > 0x7FFFFFFFull || n_records >= 0xFFFFFFFEull) return fail(TXQ_ERR_ARG, "at most 2^31 pairs and 2^32 - 2 records per call");
-    if ((uint64_t)text_bytes + n_records >= 1ULL << kPosBits) return fail(TXQ_ERR_ARG, "text too large for one call");
-    return TXQ_OK;
-}
-
 }  // namespace
 }  // namespace txq
 
@@ -237,10 +163,9 @@ int txq_edit_search_device(const uint8_t* d_patterns, const uint64_t* d_pat_offs
                            const uint8_t* d_text, const uint64_t* d_rec_offsets, size_t n_records, size_t text_bytes,
                            const uint64_t* d_group_offsets, size_t n_groups, const uint32_t* d_pairs, size_t n_pairs,
                            const uint8_t* d_codes, uint32_t* d_out, void* d_workspace, void* stream) {
-    if (int rc = edit_args(d_pat_offsets, d_rec_offsets, d_group_offsets, d_pairs, n_pairs, n_records, text_bytes, d_codes, d_out)) return rc;
-    if (n_pairs && (!d_workspace || ((uintptr_t)d_workspace & 7))) return fail(TXQ_ERR_ARG, "the workspace must be an 8-byte aligned device pointer");
-    if ((pattern_bytes && !d_patterns) || (text_bytes && !d_text)) return fail(TXQ_ERR_ARG, "null argument");
-    if (int rc = require_init()) return rc;
+    if (int rc = edit_device_args(d_patterns, d_pat_offsets, pattern_bytes, d_text, d_rec_offsets, n_records, text_bytes, d_group_offsets, d_pairs, n_pairs,
+                                  d_codes, d_out, d_workspace))
+        return rc;
     if (n_pairs == 0) return TXQ_OK;
     hipStream_t st = (hipStream_t)stream;
     void* scratch = d_workspace;  // keys and prefix: TXQ_EDIT_WORKSPACE(n_pairs) bytes of the caller's
@@ -254,7 +179,7 @@ int txq_edit_search_device(const uint8_t* d_patterns, const uint64_t* d_pat_offs
     edit_kernel<2><<<kGridBlocks, 64, 0, st>>>(a);
     edit_kernel<4><<<kGridBlocks, 64, 0, st>>>(a);
     edit_kernel<8><<<kGridBlocks, 64, 0, st>>>(a);
-    edit_finish_kernel<<<per_pair, 256, 0, st>>>(a);
+    edit_finish_kernel<kMaxPattern><<<per_pair, 256, 0, st>>>(a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "edit kernel launch");
     return TXQ_OK;
@@ -263,43 +188,8 @@ int txq_edit_search_device(const uint8_t* d_patterns, const uint64_t* d_pat_offs
 int txq_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
                     size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
                     const uint8_t* codes, uint32_t* out) {
-    if (!pat_offsets || !rec_offsets || !group_offsets) return fail(TXQ_ERR_ARG, "null argument");
-    if (int rc = check_ascending(pat_offsets, n_patterns, "pattern")) return rc;
-    if (int rc = check_ascending(rec_offsets, n_records, "record")) return rc;
-    if (int rc = check_ascending(group_offsets, n_groups, "group", "records", n_records)) return rc;
-    const uint64_t pat0 = pat_offsets[0], pat_bytes = pat_offsets[n_patterns] - pat0;
-    const uint64_t text0 = rec_offsets[0], text_bytes = rec_offsets[n_records] - text0;
-    if (int rc = edit_args(pat_offsets, rec_offsets, group_offsets, pairs, n_pairs, n_records, text_bytes, codes, out)) return rc;
-    if ((pat_bytes && !patterns) || (text_bytes && !text)) return fail(TXQ_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n_pairs; ++i) {
-        const uint32_t p = pairs[3 * i], g = pairs[3 * i + 1];
-        if (p >= n_patterns || g >= n_groups) return fail(TXQ_ERR_ARG, "pair %zu names pattern %u of %zu, group %u of %zu", i, p, n_patterns, g, n_groups);
-        const uint64_t m = pat_offsets[p + 1] - pat_offsets[p];
-        if (m < 1 || m > kMaxPattern) return fail(TXQ_ERR_ARG, "pair %zu: a pattern of %llu bytes (1..%u run on the device)", i, (unsigned long long)m, kMaxPattern);
-    }
-    if (int rc = require_init()) return rc;
-    if (n_pairs == 0) return TXQ_OK;
-    DeviceStage d;  // (+16: the kernels' 16-byte loads of patterns and text end inside the slice)
-    const size_t s_pat = d.add(pat_bytes + 16), s_po = d.add((n_patterns + 1) * 8), s_text = d.add(text_bytes + 16), s_rec = d.add((n_records + 1) * 8),
-                 s_grp = d.add((n_groups + 1) * 8), s_pairs = d.add(n_pairs * 12), s_codes = d.add(256), s_out = d.add(n_pairs * 12),
-                 s_work = d.add(TXQ_EDIT_WORKSPACE(n_pairs));
-    if (const hipError_t e = d.alloc(); e != hipSuccess) return fail_hip(e, "hipMalloc");
-    const std::vector<uint64_t> po = rebased(pat_offsets, n_patterns), ro = rebased(rec_offsets, n_records);
-    d.upload(s_pat, patterns + pat0, pat_bytes);
-    d.upload(s_po, po.data(), po.size() * 8);
-    d.upload(s_text, text + text0, text_bytes);
-    d.upload(s_rec, ro.data(), ro.size() * 8);
-    d.upload(s_grp, group_offsets, (n_groups + 1) * 8);
-    d.upload(s_pairs, pairs, n_pairs * 12);
-    d.upload(s_codes, codes, 256);
-    int rc = TXQ_OK;
-    if (d.error() == hipSuccess)
-        rc = txq_edit_search_device(d.at<uint8_t>(s_pat), d.at<uint64_t>(s_po), n_patterns, pat_bytes, d.at<uint8_t>(s_text), d.at<uint64_t>(s_rec), n_records,
-                                    text_bytes, d.at<uint64_t>(s_grp), n_groups, d.at<uint32_t>(s_pairs), n_pairs, d.at<uint8_t>(s_codes),
-                                    d.at<uint32_t>(s_out), d.at<void>(s_work), nullptr);
-    if (rc == TXQ_OK) d.download(out, s_out, n_pairs * 12);  // (waits for the kernels)
-    if (d.error() != hipSuccess) return fail_hip(d.error(), "txq_edit_search copies");
-    return rc;
+    return edit_search_staged(patterns, pat_offsets, n_patterns, text, rec_offsets, n_records, group_offsets, n_groups, pairs, n_pairs, codes, out,
+                              kMaxPattern, TXQ_EDIT_WORKSPACE(n_pairs), txq_edit_search_device, "txq_edit_search copies");
 }
 
 }  // extern "C"
