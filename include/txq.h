@@ -68,6 +68,8 @@ extern "C" {
  *                                                     index and extended (the rows never outlive txq_emplace_device either way)
  *   TXQ_PROBE_TABLE_FUSED=0                           a call on kept rows runs three launches (sample, build, answer) like a first
  *                                                     call, not the one launch that answers, counts and extends the table
+ *   TXQ_PROBE_TABLE_TILE=0                            no table-only tile body: a full tile whose 64 k-mers all have a table row
+ *                                                     takes the general body like every other tile (A/B and cross-checks)
  * (tests/test_gpu_knobs.py runs a workload under each of them against the oracle.) */
 
 typedef enum {

@@ -85,6 +85,7 @@ void read_knobs() {
     k.probe_table = is("TXQ_PROBE_TABLE", '0') ? 0 : is("TXQ_PROBE_TABLE", '1') ? 1 : -1;
     k.probe_table_keep = !is("TXQ_PROBE_TABLE_KEEP", '0');
     k.probe_table_fused = !is("TXQ_PROBE_TABLE_FUSED", '0');
+    k.probe_table_tile = !is("TXQ_PROBE_TABLE_TILE", '0');
 #ifdef TXQ_EXPERIMENTS
     // timing experiment of tools/ab_probe_ceiling.sh: the domain table's answer without its row loads (1) or its mask stores (2) - WRONG masks
     k.probe_experiment = (int)num("TXQ_PROBE_EXPERIMENT", 0) & 3;

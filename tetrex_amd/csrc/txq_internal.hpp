@@ -77,6 +77,7 @@ struct Knobs {
     int probe_table = -1;  // TXQ_PROBE_TABLE: 0 never the domain table of a flat probe, 1 whenever it fits (tests), unset: where it pays
     bool probe_table_keep = true;  // TXQ_PROBE_TABLE_KEEP=0: the domain table is built from row 0 on every call (A/B and tests)
     bool probe_table_fused = true;  // TXQ_PROBE_TABLE_FUSED=0: a call on kept rows runs sample, build and answer, not the one launch that does all three (A/B and tests)
+    bool probe_table_tile = true;   // TXQ_PROBE_TABLE_TILE=0: no table-only tile body, every tile of an answer takes probe_tile (A/B and tests)
     int probe_experiment = 0;       // TXQ_PROBE_EXPERIMENT, TXQ_EXPERIMENTS builds only: bit 0 the answer loads no rows, bit 1 it stores no masks (timing, wrong masks)
 };
 Knobs knobs();      // a copy of the snapshot taken at the last entry point (published under a lock: entry points run on several threads)

@@ -27,7 +27,8 @@
 //     2. probe_kernel<..., kBuild>: the values [0, D) probed into the table T[v] (row pitch = stride) - if the domain pays,
 //        count * 16 >= ratio * D,
 //     3. probe_kernel<..., kAnswer>: the plain kernel's lane layout; a k-mer v < rows reads ONE row T[v], any other k-mer
-//        gathers its h rows as above.
+//        gathers its h rows as above.  A full tile whose 64 k-mers all have a row takes a body of its own (table_tile: no
+//        hashing, its row loads back to back in front of its stores; TXQ_PROBE_TABLE_TILE=0: never).
 //   kept: ONE launch of probe_kernel<..., kAnswer>, which also does what the other two did.  Every answer counts, exactly and
 //     for nothing in the steady state, the k-mers it had to gather although they lie below the call's capacity: a wave that
 //     met any adds {1 + the largest, how many} to the call's statistics.  The NEXT kept call reads them: with V = `valid` and
@@ -84,6 +85,7 @@ struct TableArgs {
     uint32_t fresh, sampled;  // sampled: a domain pass and a build ran in front of the answer (fresh calls, TXQ_PROBE_TABLE_FUSED=0)
     ProbeSlots slot;
     uint32_t experiment;      // TXQ_EXPERIMENTS builds only (TXQ_PROBE_EXPERIMENT: timing experiments, wrong masks)
+    uint32_t table_tile;      // a full tile whose 64 k-mers all have a row takes table_tile (TXQ_PROBE_TABLE_TILE=0: never)
 };
 // the rows of a sampled call: the build writes [lo, rows), its answer reads [0, rows)
 __device__ __forceinline__ ProbeRows table_rows(const TableArgs& T) {
@@ -108,11 +110,12 @@ struct WaveStats { uint32_t top = 0, count = 0; };
 // U*H independent 16-byte gathers per lane are issued before the first AND.
 // MODE kBuild: the k-mers are the values of the tile themselves (no input), of which [lo, n) are written to `masks` = the table
 // at row pitch stride (whole 16-byte chunks, plain stores: an answer reads them back); MODE kAnswer: k-mers below `tab_rows`
-// read their row of `table` instead of gathering, and those in [cnt_lo, cnt_hi) are counted into `st`.
+// read their row of `table` instead of gathering, and those in [cnt_lo, cnt_hi) are counted into `st`; the caller has
+// loaded the tile's k-mers (v_in: lane l holds k-mer l, 0 past n).
 template <int LPK, int H, int U, bool NT, class ROOT, int MODE>
 __device__ __forceinline__ void probe_tile(const IbfDev& f, const uint64_t* __restrict__ kmers, size_t n, uint64_t* __restrict__ masks,
                                            uint64_t* __restrict__ alive, const ROOT& R, const uint64_t* __restrict__ table, uint32_t tab_rows,
-                                           uint32_t lo, uint32_t cnt_lo, uint32_t cnt_hi, WaveStats& st, uint32_t experiment, size_t tile) {
+                                           uint32_t lo, uint32_t cnt_lo, uint32_t cnt_hi, WaveStats& st, uint32_t experiment, size_t tile, uint64_t v_in = 0) {
     constexpr int KPS = 64 / LPK;          // k-mers per step
     constexpr int UU = U < LPK ? U : LPK;  // a tile has LPK steps
     const int lane = threadIdx.x & 63;
@@ -122,7 +125,7 @@ __device__ __forceinline__ void probe_tile(const IbfDev& f, const uint64_t* __re
     {
         const size_t base = tile << 6;
         const size_t mine = base + lane;
-        const uint64_t v = MODE == kBuild ? (uint64_t)mine : mine < n ? __builtin_nontemporal_load(kmers + mine) : 0;
+        const uint64_t v = MODE == kBuild ? (uint64_t)mine : MODE == kAnswer ? v_in : mine < n ? __builtin_nontemporal_load(kmers + mine) : 0;
         const bool tab = MODE == kAnswer && mine < n && v < tab_rows;  // my k-mer's mask is row v of the table
         if constexpr (MODE == kAnswer) {
             const bool beyond = mine < n && v >= cnt_lo && v < cnt_hi;
@@ -244,10 +247,103 @@ __device__ __forceinline__ void probe_tile(const IbfDev& f, const uint64_t* __re
     }
 }
 
+// One full tile of an answer whose 64 k-mers all have a row in the table (lane l: row `row`): no hashing, no statistics, no
+// choice per lane.  The steps are taken in groups of G = min(LPK, 8): G shuffles of the row index, G 16-byte loads of T[v]
+// back to back, then the G stores, then the `alive` ballots.
+// Loads and stores share the one in-order vmcnt counter: a wait on loads issued AFTER a store also waits for that store's
+// acknowledgement.  Here every load a store depends on is older than every store in flight, so the waits in front of the
+// stores can be counted ones that leave the wave's own stores outstanding; with more than one group (LPK > 8) the loads of
+// group g + 1 are issued before the stores of group g.
+// WHOLE: every lane has a chunk and the row has no odd tail word (chunks == LPK, shard_words even): the body is straight-line
+// code, and the compiler's waits are exactly those.  Otherwise the lanes past the row's chunks are masked once around a group's
+// loads and once around its stores, and the tail lane stores 8 bytes: behind such a branch the compiler's counted waits assume
+// the path WITHOUT the stores, and would wait for earlier stores of the group.  With one group the loads are therefore waited
+// for as a whole in front of the stores, which then need no wait at all; with several (LPK > 8 and an odd or masked row) the
+// compiler's waits stand.  Requires chunks <= LPK (the caller takes it at LPK <= 16 only).
+template <int LPK, bool WHOLE>
+__device__ __forceinline__ void table_tile(const IbfDev& f, uint64_t* __restrict__ masks, uint64_t* __restrict__ alive,
+                                           const uint64_t* __restrict__ table, uint32_t row, uint32_t experiment, size_t tile) {
+    constexpr int KPS = 64 / LPK;
+    constexpr int G = LPK < 8 ? LPK : 8;
+    constexpr int GROUPS = LPK / G;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane % LPK, grp = lane / LPK;
+    const bool on = WHOLE || (uint32_t)sub < (f.stride >> 1);
+    const size_t base = tile << 6;
+    const uint64_t gm = LPK == 64 ? ~0ULL : ((1ULL << LPK) - 1ULL);
+    const int my_step = lane / KPS, my_grp = lane % KPS;
+    (void)experiment;
+#ifdef TXQ_EXPERIMENTS
+    uint32_t sink = 0;
+#endif
+    bool my_alive = false;
+    u32x4 x[2][G];
+    auto load_group = [&](int g, u32x4* dst) {
+        uint32_t r[G];
+#pragma unroll
+        for (int u = 0; u < G; ++u) r[u] = (uint32_t)__shfl((int)row, (g * G + u) * KPS + grp);
+        if constexpr (!WHOLE) {
+#pragma unroll
+            for (int u = 0; u < G; ++u) dst[u] = u32x4{0u, 0u, 0u, 0u};
+        }
+#ifdef TXQ_EXPERIMENTS
+        if (experiment & 1u) {  // no row loads: the mask is a constant
+#pragma unroll
+            for (int u = 0; u < G; ++u) dst[u] = u32x4{0x55555555u, 0x33333333u, 0x0f0f0f0fu, 0x00ff00ffu};
+            return;
+        }
+#endif
+        if (on) {
+#pragma unroll
+            for (int u = 0; u < G; ++u) dst[u] = ld16(table + (size_t)r[u] * f.stride + 2u * sub);
+        }
+    };
+    load_group(0, x[0]);
+#pragma unroll
+    for (int g = 0; g < GROUPS; ++g) {
+        if (g + 1 < GROUPS) load_group(g + 1, x[(g + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);  // (left alone, the scheduler sinks loads of the group between the stores before it)
+        const u32x4* cur = x[g & 1];
+        if constexpr (!WHOLE && GROUPS == 1) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the group's loads, nothing else is in flight
+#ifdef TXQ_EXPERIMENTS
+        if (experiment & 2u) {  // no mask stores
+#pragma unroll
+            for (int u = 0; u < G; ++u) sink ^= cur[u].x ^ cur[u].y ^ cur[u].z ^ cur[u].w;
+        } else
+#endif
+        if constexpr (WHOLE) {
+#pragma unroll
+            for (int u = 0; u < G; ++u) st16_stream(masks + (base + (g * G + u) * KPS + grp) * f.shard_words + 2u * sub, cur[u]);
+        } else if (on) {
+#pragma unroll
+            for (int u = 0; u < G; ++u) store_chunk(f, masks, base + (g * G + u) * KPS + grp, sub, cur[u]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (alive) {
+#pragma unroll
+            for (int u = 0; u < G; ++u) {
+                const uint64_t b = __ballot(on && nonzero(cur[u]));
+                if (my_step == g * G + u) my_alive = ((b >> (my_grp * LPK)) & gm) != 0;
+            }
+        }
+    }
+    if (alive) {
+        const uint64_t bits = __ballot(my_alive);
+        if (lane == 0) alive[tile] = bits;
+    }
+#ifdef TXQ_EXPERIMENTS
+    if (experiment & 2u) {
+        const uint64_t bits = __ballot(sink & 1u);
+        if (lane == 0) masks[base * f.shard_words] = bits;
+    }
+#endif
+}
+
 // A wave owns the tiles wave, wave + n_waves, ... of the batch.  Requires bin_size < 2^32 and an even stride.
 // MODE kBuild: the tiles are those of the values [lo, rows) of table_rows, written to T.table.
-// MODE kAnswer: the batch's tiles read the table below `valid`; then the tiles of the values [valid, rows) of answer_rows are
-// built into T.table as a second loop of the same waves (its registers are the larger of the two bodies, not their sum) -
+// MODE kAnswer: the batch's tiles read the table below `valid` - a full tile that lies below it as a whole through table_tile,
+// any other (the ragged last tile, a k-mer at or above `valid`, a tree root) through probe_tile; then the tiles of the values
+// [valid, rows) of answer_rows are built into T.table as a second loop of the same waves (its registers are the larger of the two bodies, not their sum) -
 // nothing in a sampled call, whose build ran before.  Each wave that met k-mers in [rows, cap) adds them to this call's
 // statistics, and one thread leaves behind what the next call reads: `valid` = rows in the copy this launch does not read,
 // and the next call's statistics and sample words zeroed.
@@ -277,8 +373,23 @@ __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __
             T.state[T.slot.acc_zero + 1] = 0;
         }
         const size_t n_tiles = (n + 63) >> 6;
-        for (size_t tile = wave; tile < n_tiles; tile += n_waves)
-            probe_tile<LPK, H, U, NT, ROOT, kAnswer>(f, kmers, n, masks, alive, R, T.table, ex.valid, 0, ex.rows, T.cap, st, T.experiment, tile);
+        // (rows of up to 32 words only: at LPK 32 and 64 the body's two row buffers cost the kernel 1 to 4 waves/SIMD and
+        // measured no gain, profiles/probe_table_tile_ab.txt)
+        constexpr bool kTableTile = !ROOT::kActive && LPK <= 16;
+        const bool tile_ok = kTableTile && T.table_tile && ex.valid;
+        const bool whole = (f.stride >> 1) == (uint32_t)LPK && !(f.shard_words & 1u);
+        for (size_t tile = wave; tile < n_tiles; tile += n_waves) {
+            const size_t mine = (tile << 6) + (threadIdx.x & 63);
+            const uint64_t v = mine < n ? __builtin_nontemporal_load(kmers + mine) : 0;
+            if constexpr (kTableTile) {
+                if (tile_ok && (tile << 6) + 64 <= n && __ballot(v < ex.valid) == ~0ULL) {
+                    if (whole) table_tile<LPK, true>(f, masks, alive, T.table, (uint32_t)v, T.experiment, tile);
+                    else table_tile<LPK, false>(f, masks, alive, T.table, (uint32_t)v, T.experiment, tile);
+                    continue;
+                }
+            }
+            probe_tile<LPK, H, U, NT, ROOT, kAnswer>(f, kmers, n, masks, alive, R, T.table, ex.valid, 0, ex.rows, T.cap, st, T.experiment, tile, v);
+        }
         if (st.count && (threadIdx.x & 63) == 0) {
             atomicMax(T.state + T.slot.stat_add, st.top);
             atomicAdd(T.state + T.slot.stat_add + 1, st.count);
@@ -545,7 +656,7 @@ hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* k, size_t n, u
     // (TXQ_PROBE_TABLE_FUSED=0: sample, build and answer as in a fresh call, on the rows the table holds)
     const bool sampled = call.fresh || !kn.probe_table_fused;
     const TableArgs T{pt.rows, pt.state, kn.probe_table == 1 ? 0u : kTableRatio, (uint32_t)pt.cap_rows, (uint32_t)cap, call.fresh ? 1u : 0u,
-                      sampled ? 1u : 0u, probe_slots(pt.keep.calls - 1), (uint32_t)kn.probe_experiment};
+                      sampled ? 1u : 0u, probe_slots(pt.keep.calls - 1), (uint32_t)kn.probe_experiment, kn.probe_table_tile ? 1u : 0u};
     const uint32_t chunks = f.stride >> 1;
     hipError_t e;
     if (chunks <= 1) e = launch_table_lpk<1>(f, k, n, m, a, T, s);
