@@ -223,6 +223,23 @@ int txq_translate_device(const uint8_t* d_seq, const uint64_t* d_rec_offsets, si
 int txq_translate(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_records, unsigned k, const uint8_t* codes,
                   uint64_t* values, uint64_t* offsets);
 
+/* The six frames of nucleotide records as residue letters (`tetrex search --translate --verify-frames`; not in
+ * the reference).  Records, letters, frames and the genetic code are those of txq_translate above; a frame with offset o over
+ * L bytes has floor((L - o) / 3) residues (none where L < o), upper-case letters of NCBI table 1, '*' for a stop, 'X' for a
+ * codon with an ambiguous byte.  Frame 6 r + f is d_frames[d_frame_offsets[6 r + f] .. d_frame_offsets[6 r + f + 1]): 6 n_records
+ * + 1 offsets, the first 0, the frames back to back — the form txq_edit_search*_device take as d_patterns / d_pat_offsets.
+ * txq_translate_frames_bound is the exact size in bytes: the sum over records and o = 0, 1, 2 of 2 floor((L_r - o) / 3)
+ * (UINT64_MAX: bad arguments).  d_frames may have any alignment; no byte at or behind frames_bytes is written (the offsets are
+ * complete all the same), no byte outside the frames is written, and nothing of d_frames is read.  The call is deterministic,
+ * allocates nothing, reads nothing back and does not synchronise with the host.  txq_translate_frames is the synchronous twin
+ * on host buffers (it checks the record offsets; a buffer below the bound: TXQ_ERR_ARG).  Null pointers: TXQ_ERR_ARG (d_seq
+ * may be null where the records have no bytes, d_frames where frames_bytes is 0). */
+uint64_t txq_translate_frames_bound(const uint64_t* rec_offsets, size_t n_records);
+int txq_translate_frames_device(const uint8_t* d_seq, const uint64_t* d_rec_offsets, size_t n_records, uint8_t* d_frames, size_t frames_bytes,
+                                uint64_t* d_frame_offsets, void* stream);
+int txq_translate_frames(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_records, uint8_t* frames, size_t frames_bytes,
+                         uint64_t* frame_offsets);  /* host buffers, synchronous */
+
 /* Approximate matching of (pattern, bin) pairs by edit distance (`tetrex search --verify`; not in the reference).
  * Classes: d_codes[256] maps a byte to a class 0..30; any other value (255 by convention) is "matches nothing, not even
  * itself".  Two bytes match when their classes are equal and below 31.

@@ -22,7 +22,8 @@ SYMBOLS = [
     "txq_init", "txq_shutdown", "txq_last_error", "txq_device_count",
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
-    "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
+    "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_translate_frames_bound", "txq_translate_frames_device", "txq_translate_frames",
+    "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
     "txq_edit_search_long", "txq_edit_search_long_device",
     "txq_regex_filter", "txq_regex_filter_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
@@ -84,6 +85,10 @@ def lib():
         L.txq_translate_bound.argtypes = [u64p, C.c_size_t, C.c_uint]
         L.txq_translate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.txq_translate.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_uint, C.c_void_p, u64p, u64p]
+        L.txq_translate_frames_bound.restype = C.c_uint64
+        L.txq_translate_frames_bound.argtypes = [u64p, C.c_size_t]
+        L.txq_translate_frames_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.txq_translate_frames.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, C.c_size_t, u64p]
         L.txq_hit_list_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.txq_edit_search_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -524,6 +529,60 @@ def translate(records, k, codes):
     check(lib().txq_translate(seq.ctypes.data, rec.ctypes.data_as(u64p), n, k, codes.ctypes.data, values.ctypes.data_as(u64p),
                               offsets.ctypes.data_as(u64p)))
     return values[:int(offsets[-1])], offsets
+
+
+def translate_frames_bound(rec_offsets):
+    """txq_translate_frames_bound: the bytes the six frames of these records take as residue letters (no GPU needed)."""
+    o = np.ascontiguousarray(rec_offsets, dtype=np.uint64)
+    b = lib().txq_translate_frames_bound(o.ctypes.data_as(u64p), max(o.size - 1, 0))
+    if b == 0xFFFFFFFFFFFFFFFF:
+        raise TxqError(-1, lib().txq_last_error().decode(errors="replace"))
+    return int(b)
+
+
+def translate_frames(records):
+    """The six frames of nucleotide records as residue letters on the GPU (txq_translate_frames).  records: list of bytes/str,
+    or (uint8 array, uint64 offsets).  Returns (frames uint8[], offsets uint64[6 n + 1]): frame 6 r + f is
+    frames[offsets[6 r + f]:offsets[6 r + f + 1]]."""
+    seq, rec = records if isinstance(records, tuple) else _records(records)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    rec = np.ascontiguousarray(rec, dtype=np.uint64)
+    n = rec.size - 1
+    if n < 0 or (n and int(rec[-1]) > seq.size):
+        raise TxqError(-1, "translate_frames: offsets and bytes disagree")
+    bound = translate_frames_bound(rec)
+    frames = np.zeros(bound, dtype=np.uint8)
+    offsets = np.zeros(6 * n + 1, dtype=np.uint64)
+    check(lib().txq_translate_frames(seq.ctypes.data, rec.ctypes.data_as(u64p), n, frames.ctypes.data, bound, offsets.ctypes.data_as(u64p)))
+    return frames, offsets
+
+
+def translate_frames_device(records, capacity=None, seq_at=0, frames_at=0, guard=64, fill=0xA5):
+    """txq_translate_frames_device on buffers the caller places: the sequence begins seq_at bytes behind a 16-byte boundary,
+    the frames buffer frames_at bytes behind one, with `guard` bytes of `fill` on either side; capacity (default: the bound)
+    is the frames_bytes the call is given.  Returns (buffer uint8[guard + bound + guard], offsets uint64[6 n + 1], bound): the
+    frames begin at buffer[guard]; whatever the call did not write still holds `fill`."""
+    seq, rec = records if isinstance(records, tuple) else _records(records)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    rec = np.ascontiguousarray(rec, dtype=np.uint64)
+    n = rec.size - 1
+    bound = translate_frames_bound(rec)
+    capacity = bound if capacity is None else int(capacity)
+    around = np.full(seq_at + seq.size + 33, ord("A"), dtype=np.uint8)
+    around[seq_at:seq_at + seq.size] = seq
+    total = 16 + guard + bound + guard
+    d_seq, d_rec = DeviceBuffer.from_numpy(around), DeviceBuffer.from_numpy(rec)
+    d_frames, d_off = DeviceBuffer.from_numpy(np.full(16 + total, fill, dtype=np.uint8)), DeviceBuffer(8 * (6 * n + 1))
+    try:
+        first = (-(d_frames.ptr + guard) % 16 + frames_at) % 16  # the frames begin frames_at bytes behind a 16-byte boundary
+        assert d_seq.ptr % 16 == 0 and (d_frames.ptr + first + guard) % 16 == frames_at % 16
+        check(lib().txq_translate_frames_device(d_seq.ptr + seq_at, d_rec.ptr, n, d_frames.ptr + first + guard, capacity, d_off.ptr, None))
+        synchronize()
+        buf = d_frames.to_numpy(np.uint8, (16 + total,))[first:first + guard + bound + guard]
+        return buf, d_off.to_numpy(np.uint64, (6 * n + 1,)), bound
+    finally:
+        for b in (d_seq, d_rec, d_frames, d_off):
+            b.free()
 
 
 EDIT_MAX_PATTERN = 512

@@ -662,8 +662,11 @@ struct GrowBuf {
 
 void DeviceIndex::search_translated(std::string_view seq, const std::vector<uint64_t>& rec_offsets,
                                     const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& n_of,
-                                    std::vector<uint64_t>& thresholds, std::vector<TranslatedHit>& hits) {
+                                    std::vector<uint64_t>& thresholds, std::vector<TranslatedHit>& hits, BinVerifier* verifier,
+                                    std::vector<VerifiedHit>* confirmed) {
     if (!ix_) throw std::runtime_error("index not uploaded");
+    if (verifier && !confirmed) throw std::runtime_error("search_translated: a verifier needs somewhere to put its answers");
+    if (confirmed) confirmed->clear();
     if (shards_.size() > 1) throw std::runtime_error("search_translated: one shard only");
     if (enc_.molecule() != Molecule::Peptide) throw std::runtime_error("search_translated: a peptide index is needed");
     if (rec_offsets.empty() || rec_offsets.back() > seq.size()) throw std::runtime_error("search_translated: record offsets run past the bytes");
@@ -682,6 +685,14 @@ void DeviceIndex::search_translated(std::string_view seq, const std::vector<uint
     size_t list_cap = (size_t)1 << 20;
     std::vector<uint64_t> rebased, off;
     std::vector<uint32_t> thr, list;
+    // --verify-frames
+    const char* frames_env = std::getenv("TETREX_VERIFY_FRAMES");
+    const bool frames_on_host = frames_env && std::string(frames_env) == "host";
+    GrowBuf d_frames, d_foff;
+    std::vector<BinVerifier::Candidate> candidates;
+    std::vector<uint64_t> lengths;
+    std::vector<std::string> frame_strings;
+    std::vector<VerifiedHit> batch_confirmed;
     for (size_t r0 = 0; r0 < R;) {
         size_t r1 = r0;
         uint64_t bound = 0;
@@ -733,6 +744,35 @@ void DeviceIndex::search_translated(std::string_view seq, const std::vector<uint
         if (total) txq_check(txq_memcpy_d2h(list.data(), d_list.p, total * 12), "d2h");
         const uint32_t q0 = (uint32_t)(6 * (r1 - nr)), bin0 = (uint32_t)(info_.shard_word0 * 64);
         for (uint64_t i = 0; i < total; ++i) hits.push_back(TranslatedHit{q0 + list[3 * i], bin0 + list[3 * i + 1], list[3 * i + 2]});
+        if (!verifier || total == 0) continue;
+        // --verify-frames: the batch's hits are candidates, pattern index = query index within the batch
+        candidates.resize(total);
+        for (uint64_t i = 0; i < total; ++i) candidates[i] = BinVerifier::Candidate{list[3 * i], bin0 + list[3 * i + 1]};
+        const auto frame_letters = [&](uint32_t q) {
+            return translate_frame(seq.substr(first + rebased[q / 6], rebased[q / 6 + 1] - rebased[q / 6]), q % 6);
+        };
+        if (frames_on_host) {
+            frame_strings.assign(nq, std::string());
+            for (const BinVerifier::Candidate& c : candidates)
+                if (frame_strings[c.query].empty()) frame_strings[c.query] = frame_letters(c.query);
+            verifier->verify(frame_strings, candidates, batch_confirmed);
+        } else {
+            const uint64_t frames_bytes = txq_translate_frames_bound(rebased.data(), nr);
+            if (frames_bytes == UINT64_MAX) txq_check(TXQ_ERR_ARG, "txq_translate_frames_bound");
+            d_frames.reserve(frames_bytes + 16);  // (the slack BinVerifier gives its own pattern buffer)
+            d_foff.reserve((nq + 1) * 8);
+            txq_check(txq_translate_frames_device((const uint8_t*)d_seq.p, (const uint64_t*)d_rec.p, nr, (uint8_t*)d_frames.p, frames_bytes,
+                                                  (uint64_t*)d_foff.p, nullptr), "txq_translate_frames_device");
+            lengths.resize(total);
+            for (uint64_t i = 0; i < total; ++i) {
+                const uint32_t q = candidates[i].query;
+                const uint64_t L = rebased[q / 6 + 1] - rebased[q / 6], o = q % 3;
+                lengths[i] = L >= o ? (L - o) / 3 : 0;
+            }
+            verifier->verify(BinVerifier::DevicePatterns{(const uint8_t*)d_frames.p, (const uint64_t*)d_foff.p, nq, frames_bytes}, candidates, lengths,
+                             frame_letters, batch_confirmed);
+        }
+        confirmed->insert(confirmed->end(), batch_confirmed.begin(), batch_confirmed.end());
     }
 }
 
@@ -827,15 +867,19 @@ BinVerifier::~BinVerifier() {
     if (d_codes_) txq_free(d_codes_);
 }
 
+size_t BinVerifier::device_max() {
+    const char* long_env = std::getenv("TETREX_VERIFY_LONG");
+    return long_env && long_env[0] == '0' && !long_env[1] ? TXQ_EDIT_MAX_PATTERN : TXQ_EDIT_LONG_MAX_PATTERN;
+}
+
 void BinVerifier::verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits) {
     hits.assign(candidates.size(), Hit{});
-    n_candidates_ += candidates.size();
     if (candidates.empty()) return;
     const size_t strands = dna_ ? 2 : 1;
     // the patterns: every record that is a candidate somewhere, and on a nucleotide index its reverse complement behind it
     constexpr uint32_t kNoPattern = 0xFFFFFFFFu;
-    std::vector<uint32_t> pattern_of(queries.size(), kNoPattern);
-    std::vector<uint64_t> pat_off{0};
+    std::vector<uint32_t> pattern_of(queries.size(), kNoPattern), of_candidate(candidates.size(), kNoPattern);
+    std::vector<uint64_t> pat_off{0}, lengths(candidates.size());
     std::string pat;
     const auto reverse_complement = [](const std::string& s) {
         std::string out(s.rbegin(), s.rend());
@@ -848,18 +892,12 @@ void BinVerifier::verify(const std::vector<std::string>& queries, const std::vec
         }
         return out;
     };
-    std::vector<size_t> order(candidates.size()), on_host;
-    std::iota(order.begin(), order.end(), (size_t)0);
-    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return candidates[x].bin < candidates[y].bin; });
-    // candidate of every `strands` pairs, by bin: records of up to TXQ_EDIT_MAX_PATTERN letters first, behind them those of up
-    // to TXQ_EDIT_LONG_MAX_PATTERN, which the long-pattern kernel answers (TETREX_VERIFY_LONG=0: the host, for A/B runs)
-    const char* long_env = std::getenv("TETREX_VERIFY_LONG");
-    const size_t device_max = long_env && long_env[0] == '0' && !long_env[1] ? TXQ_EDIT_MAX_PATTERN : TXQ_EDIT_LONG_MAX_PATTERN;
-    std::vector<size_t> on_device, on_long;
-    for (size_t i : order) {
+    const size_t longest = device_max();
+    for (size_t i = 0; i < candidates.size(); ++i) {
         const uint32_t q = candidates[i].query;
         const std::string& s = queries.at(q);
-        if (s.empty() || s.size() > device_max) { on_host.push_back(i); continue; }
+        lengths[i] = s.size();
+        if (s.empty() || s.size() > longest) continue;  // (the host route: letters() below)
         if (pattern_of[q] == kNoPattern) {
             pattern_of[q] = (uint32_t)(pat_off.size() - 1);
             pat.append(s);
@@ -869,7 +907,39 @@ void BinVerifier::verify(const std::vector<std::string>& queries, const std::vec
                 pat_off.push_back(pat.size());
             }
         }
-        (s.size() > TXQ_EDIT_MAX_PATTERN ? on_long : on_device).push_back(i);
+        of_candidate[i] = pattern_of[q];
+    }
+    DevBuf d_pat(pat.size() + 16), d_po(pat_off.size() * 8);
+    if (!pat.empty()) {
+        txq_check(txq_memcpy_h2d(d_pat.p, pat.data(), pat.size()), "h2d");
+        txq_check(txq_memcpy_h2d(d_po.p, pat_off.data(), pat_off.size() * 8), "h2d");
+    }
+    run(DevicePatterns{(const uint8_t*)d_pat.p, (const uint64_t*)d_po.p, pat_off.size() - 1, pat.size()}, strands, candidates, of_candidate, lengths,
+        [&](size_t i, size_t strand) { return strand ? reverse_complement(queries[candidates[i].query]) : queries[candidates[i].query]; }, hits);
+}
+
+void BinVerifier::verify(const DevicePatterns& patterns, const std::vector<Candidate>& candidates, const std::vector<uint64_t>& lengths,
+                         const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits) {
+    hits.assign(candidates.size(), Hit{});
+    if (candidates.empty()) return;
+    std::vector<uint32_t> of_candidate(candidates.size());
+    for (size_t i = 0; i < candidates.size(); ++i) of_candidate[i] = candidates[i].query;
+    run(patterns, 1, candidates, of_candidate, lengths, [&](size_t i, size_t) { return letters(candidates[i].query); }, hits);
+}
+
+void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
+                      const std::vector<uint64_t>& lengths, const std::function<std::string(size_t, size_t)>& letters, std::vector<Hit>& hits) {
+    n_candidates_ += candidates.size();
+    std::vector<size_t> order(candidates.size()), on_host;
+    std::iota(order.begin(), order.end(), (size_t)0);
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return candidates[x].bin < candidates[y].bin; });
+    // candidate of every `strands` pairs, by bin: patterns of up to TXQ_EDIT_MAX_PATTERN letters first, behind them those of up
+    // to TXQ_EDIT_LONG_MAX_PATTERN, which the long-pattern kernel answers (TETREX_VERIFY_LONG=0: the host, for A/B runs)
+    const size_t longest = device_max();
+    std::vector<size_t> on_device, on_long;
+    for (size_t i : order) {
+        if (lengths[i] == 0 || lengths[i] > longest) on_host.push_back(i);
+        else (lengths[i] > TXQ_EDIT_MAX_PATTERN ? on_long : on_device).push_back(i);
     }
     const size_t n_short = on_device.size();
     on_device.insert(on_device.end(), on_long.begin(), on_long.end());
@@ -891,17 +961,14 @@ void BinVerifier::verify(const std::vector<std::string>& queries, const std::vec
         pairs.reserve(on_device.size() * strands * 3);
         for (size_t i : on_device)
             for (size_t s = 0; s < strands; ++s) {
-                pairs.push_back(pattern_of[candidates[i].query] + (uint32_t)s);
+                pairs.push_back(pattern_of[i] + (uint32_t)s);
                 pairs.push_back(0);
                 pairs.push_back(errors_);
             }
-        const size_t n_patterns = pat_off.size() - 1;
-        DevBuf d_pat(pat.size() + 16), d_po(pat_off.size() * 8), d_pairs(pairs.size() * 4), d_out(pairs.size() * 4);
+        DevBuf d_pairs(pairs.size() * 4), d_out(pairs.size() * 4);
         static_assert(TXQ_EDIT_LONG_WORKSPACE(7) == TXQ_EDIT_WORKSPACE(7), "one workspace, cut the same way for either call");
         DevBuf d_work(TXQ_EDIT_WORKSPACE(pairs.size() / 3) + 8 * on_device.size());  // (every call its own part: they are all in flight at once)
         size_t n_calls = 0;
-        txq_check(txq_memcpy_h2d(d_pat.p, pat.data(), pat.size()), "h2d");
-        txq_check(txq_memcpy_h2d(d_po.p, pat_off.data(), pat_off.size() * 8), "h2d");
         txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
         for (size_t a = 0; a < on_device.size();) {  // one call per bin and kernel: the bin's records are one group
             size_t b = a;
@@ -910,7 +977,7 @@ void BinVerifier::verify(const std::vector<std::string>& queries, const std::vec
             while (b < (is_long ? on_device.size() : n_short) && candidates[on_device[b]].bin == bin) ++b;
             ResidentBins::Bin& e = bins_.resident(bin);
             const uint64_t* d_rec = (const uint64_t*)e.d_rec;
-            txq_check((is_long ? txq_edit_search_long_device : txq_edit_search_device)((const uint8_t*)d_pat.p, (const uint64_t*)d_po.p, n_patterns, pat.size(), (const uint8_t*)e.d_text, d_rec,
+            txq_check((is_long ? txq_edit_search_long_device : txq_edit_search_device)(patterns.d_letters, patterns.d_offsets, patterns.n_patterns, patterns.bytes, (const uint8_t*)e.d_text, d_rec,
                                              e.n_records, e.text_bytes, d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * strands * a,
                                              (b - a) * strands, (const uint8_t*)d_codes_, (uint32_t*)d_out.p + 3 * strands * a,
                                              (unsigned char*)d_work.p + 16 * strands * a + 8 * n_calls++, nullptr),
@@ -937,10 +1004,9 @@ void BinVerifier::verify(const std::vector<std::string>& queries, const std::vec
 #pragma omp parallel for schedule(dynamic)
 #endif
         for (size_t k = a; k < b; ++k) {
-            const std::string& s = queries[candidates[on_host[k]].query];
-            if (s.empty()) continue;
+            if (lengths[on_host[k]] == 0) continue;
             for (size_t st = 0; st < strands; ++st) {
-                const std::string p = st ? reverse_complement(s) : s;
+                const std::string p = letters(on_host[k], st);
                 EditPattern ep((const uint8_t*)p.data(), p.size(), codes_);
                 const EditResult r = edit_search_group(ep, (const uint8_t*)text.data(), rec.data(), 0, rec.size() - 1, errors_);
                 uint32_t* o = out.data() + 3 * (strands * (k - a) + st);

@@ -62,6 +62,15 @@ std::vector<uint64_t> run_queries_sharded(const std::vector<txq_index*>& shards,
                                           std::vector<int>* status, std::vector<std::string>* messages, StagedStats* stats,
                                           const StagedOptions* options, const std::vector<txq_index*>& aux = {});
 
+// what BinVerifier (below) says about one candidate pair
+struct VerifiedHit {
+    uint32_t distance = 0xFFFFFFFFu;  // 0xFFFFFFFF: not within `errors` of any record of the bin
+    uint32_t end = 0;                 // 1-based position of the match's last letter in the target, 0 for an empty match
+    char strand = '+';                // '-': the reverse complement matched better (on equal distance + wins)
+    const std::string* target = nullptr;  // the target record's name (valid as long as the verifier)
+};
+class BinVerifier;
+
 class DeviceIndex {
   public:
     DeviceIndex() = default;
@@ -101,10 +110,15 @@ class DeviceIndex {
     // where n_of[q] = 0), a query with threshold 0 is not searched, the others are counted (txq_count_device on the device's
     // values) and only the list of their hits comes back (txq_hit_list_device), in (query, bin) order.  Records are batched
     // by txq_translate_bound to at most 2^24 values a batch (one larger record: a batch of its own).  One shard only.
+    // With a verifier (`--verify-frames`) every hit is a candidate: for a batch with at least one hit the
+    // frames of its records become letters on the device (txq_translate_frames_device on the batch's bytes, which are still
+    // there), the verifier compares frame `query` with bin `bin` by edit distance and confirmed[i] answers hits[i].
+    // TETREX_VERIFY_FRAMES=host: the candidate frames are translated on the host (translate_frame) and verified as strings.
     struct TranslatedHit { uint32_t query, bin, count; };  // count: 0 unless with_counts
     void search_translated(std::string_view seq, const std::vector<uint64_t>& rec_offsets,
                            const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& n_of,
-                           std::vector<uint64_t>& thresholds, std::vector<TranslatedHit>& hits);
+                           std::vector<uint64_t>& thresholds, std::vector<TranslatedHit>& hits, BinVerifier* verifier = nullptr,
+                           std::vector<VerifiedHit>* confirmed = nullptr);
     // `tetrex query -g`: upload the d-gram index next to the main index (same device, same shard)
     void attach_dgram(const DgramImage& dgram);
     bool has_dgram() const { return aux_ != nullptr; }
@@ -175,21 +189,33 @@ class BinVerifier {
     BinVerifier& operator=(const BinVerifier&) = delete;
     ~BinVerifier();
     struct Candidate { uint32_t query, bin; };
-    struct Hit {
-        uint32_t distance = 0xFFFFFFFFu;  // 0xFFFFFFFF: not within `errors` of any record of the bin
-        uint32_t end = 0;                 // 1-based position of the match's last letter in the target, 0 for an empty match
-        char strand = '+';                // '-': the reverse complement matched better (on equal distance + wins)
-        const std::string* target = nullptr;  // the target record's name (valid as long as the verifier)
-    };
+    using Hit = VerifiedHit;
     // hits[i] answers candidates[i]; queries[c.query] are the batch's records.  Throws std::runtime_error naming the bin file
     // that cannot be read.
     void verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits);
+    // The same for patterns that are on the device already (`tetrex search --translate --verify-frames`, DESIGN.md §14: the
+    // frames of txq_translate_frames_device).  Pattern p is d_letters[d_offsets[p] .. d_offsets[p+1]), n_patterns + 1 offsets,
+    // `bytes` letters in all in a buffer with 16 bytes of slack behind them; candidates[i].query names a pattern,
+    // lengths[i] is its length, and letters(p) gives the pattern to the host route (longer than TXQ_EDIT_LONG_MAX_PATTERN).
+    // One strand: a pattern is compared as it stands, whatever the index's molecule.
+    struct DevicePatterns {
+        const uint8_t* d_letters;
+        const uint64_t* d_offsets;
+        size_t n_patterns, bytes;
+    };
+    void verify(const DevicePatterns& patterns, const std::vector<Candidate>& candidates, const std::vector<uint64_t>& lengths,
+                const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits);
     size_t n_candidates() const { return n_candidates_; }
     size_t n_confirmed() const { return n_confirmed_; }
     struct Routed { size_t device, device_long, host; };
     Routed n_routed() const { return {n_device_, n_device_long_, n_host_}; }
 
   private:
+    // what both entries share: candidate i compares `strands` consecutive patterns from pattern_of[i] (lengths[i] letters each)
+    // with its bin — routing by length, the pairs, one call per bin and kernel, the one copy back, the host route, settle
+    void run(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
+             const std::vector<uint64_t>& lengths, const std::function<std::string(size_t, size_t)>& letters, std::vector<Hit>& hits);
+    static size_t device_max();  // the longest pattern the device answers (TETREX_VERIFY_LONG)
     ResidentBins bins_;
     bool dna_;
     uint32_t errors_;

@@ -4,10 +4,11 @@
 //      the candidate bins that hold a match at all are found on the device, the matcher runs on those only — same rows)
 //   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] [--layout uniform|sized [--tmax N] [--rearrange [--rearrange-ratio R]]] <name> <libs...>
 //     (include/arg_parse.h:10-38, src/index_base.cpp:73-117)
-//   tetrex search [-e E [--verify] | --threshold F] [--counts] [--translate] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//   tetrex search [-e E [--verify] | --threshold F] [--counts] [--translate [--verify-frames]] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (not in the reference: every FASTA record a query, answered by seqan::hibf membership_for(values, threshold);
 //      --translate: nucleotide records on a peptide index, every record's six frames a query of their own;
-//      --verify: only the bins that hold the record within E edits, confirmed on the bins' own letters)
+//      --verify: only the bins that hold the record within E edits, confirmed on the bins' own letters;
+//      --verify-frames, with --translate -e E: only the bins that hold the frame's residues within E edits, confirmed likewise)
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
 #include "device_index.hpp"
@@ -436,7 +437,9 @@ int cmd_track(int argc, char** argv) {
 // and the plain rules with n = n_f: -e E gives t = max(n_f - k E, 0), --threshold F gives t = ceil(F n_f).  A frame with
 // n_f = 0 or t = 0 reports nothing (a wrong frame is short and full of stops: "every bin" for it would be noise); a record
 // none of whose frames is searched gets a note.  Rows: name \t bin path \t frame [\t count/n_f], by record, frame
-// (+1 +2 +3 -1 -2 -3) and bin.
+// (+1 +2 +3 -1 -2 -3) and bin.  -e E --verify-frames: the rows are candidates; each is confirmed by the edit
+// distance of the frame's residue letters to the bin's records (BinVerifier, the frames translated on the device) and only
+// those within E edits are written, with distance \t target \t end appended.
 int search_translated(const Args& a, const IndexImage& image, unsigned long long errors, double fraction) {
     const bool verbose = a.has("verbose"), with_counts = a.has("counts"), by_fraction = a.has("threshold");
     const std::string dest = a.get("output", "-");
@@ -461,9 +464,14 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
     std::string seq, row;
     std::vector<uint64_t> rec_offsets{0}, n_of, thresholds;
     std::vector<DeviceIndex::TranslatedHit> hits;
+    // --verify-frames: every row is a candidate (frame, bin); only those within E residue edits are written
+    const bool verify = a.has("verify-frames");
+    std::unique_ptr<BinVerifier> verifier;
+    if (verify) verifier = std::make_unique<BinVerifier>(image.bin_paths, false, (uint32_t)std::min<unsigned long long>(errors, 0xFFFFFFFEull));
+    std::vector<BinVerifier::Hit> confirmed;
     auto flush = [&]() {
         if (names.empty()) return;
-        dev.search_translated(seq, rec_offsets, threshold_of, with_counts, n_of, thresholds, hits);
+        dev.search_translated(seq, rec_offsets, threshold_of, with_counts, n_of, thresholds, hits, verifier.get(), verify ? &confirmed : nullptr);
         size_t h = 0;
         for (size_t r = 0; r < names.size(); ++r) {
             bool searched = false;
@@ -472,8 +480,12 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
                 std::cerr << "[tetrex search] " << names[r] << ": no frame with " << k << "-mers enough for a threshold above 0, skipped" << std::endl;
             for (; h < hits.size() && hits[h].query < 6 * (r + 1); ++h) {
                 const DeviceIndex::TranslatedHit& x = hits[h];
+                if (verify && confirmed[h].distance == 0xFFFFFFFFu) continue;
                 row.assign(names[r]).append("\t").append(image.bin_paths[x.bin]).append("\t").append(kFrames[x.query % 6]);
                 if (with_counts) row.append("\t").append(std::to_string(x.count)).append("/").append(std::to_string(n_of[x.query]));
+                if (verify)
+                    row.append("\t").append(std::to_string(confirmed[h].distance)).append("\t").append(*confirmed[h].target).append("\t")
+                        .append(std::to_string(confirmed[h].end));
                 out << row << '\n';
             }
         }
@@ -489,6 +501,11 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
     });
     flush();
     out.flush();
+    if (verbose && verify) std::cerr << "Verified: " << verifier->n_confirmed() << " of " << verifier->n_candidates() << " candidate pairs" << std::endl;
+    if (verify && std::getenv("TETREX_TRACE")) {
+        const BinVerifier::Routed n = verifier->n_routed();
+        std::cerr << "[tetrex search] verify routes: device " << n.device << ", device-long " << n.device_long << ", host " << n.host << std::endl;
+    }
     if (verbose) std::cerr << "Search time: " << (now() - t_start) << " s" << std::endl;
     return 0;
 }
@@ -501,15 +518,22 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
 // bin's records (BinVerifier) and only the bins within E edits are written, with distance \t target \t end [\t strand] appended.
 int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
-                                       {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false}};
+                                       {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false},
+                                       {'\0', "verify-frames", false}};
     Args a;
     unsigned long long errors = 0;
     double fraction = 0;
     try {
         a = parse(argc, argv, 2, spec);
         if (a.pos.size() != 2) throw std::runtime_error("expected <index> <queries.fa>");
+        if (a.has("verify-frames")) {
+            if (a.has("verify")) throw std::runtime_error("--verify-frames cannot be combined with --verify: one confirms translated frames, the other plain records");
+            if (!a.has("translate")) throw std::runtime_error("--verify-frames confirms the rows of --translate: it needs --translate");
+            if (a.has("threshold")) throw std::runtime_error("--verify-frames confirms the bins of -e E: it cannot be combined with --threshold");
+            if (!a.has("errors")) throw std::runtime_error("--verify-frames needs -e E: the number of residue edits a confirmed frame may be away");
+        }
         if (a.has("verify") && a.has("threshold")) throw std::runtime_error("--verify confirms the bins of -e E: it cannot be combined with --threshold");
-        if (a.has("verify") && a.has("translate")) throw std::runtime_error("--verify cannot be combined with --translate");
+        if (a.has("verify") && a.has("translate")) throw std::runtime_error("--verify cannot be combined with --translate (translated rows are confirmed with --verify-frames)");
         if (a.has("verify") && !a.has("errors")) throw std::runtime_error("--verify needs -e E: the number of edits a confirmed bin may be away");
         if (a.has("errors") && a.has("threshold")) throw std::runtime_error("-e and --threshold exclude each other");
         if (a.has("errors")) {

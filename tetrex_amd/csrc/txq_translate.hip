@@ -23,17 +23,16 @@
 //     past the unit's end; scan_kernel turns the counts into offsets; fill_kernel recomputes the windows and, for a record
 //     that began in an earlier unit, first sums those units' counts.
 // Scratch (6 u32 per unit; the hit list's tile sums) is allocated and freed in stream order by the library.
+// The same pass with the frames as residue letters instead of values (txq_translate_frames*) is frames_kernel below.
 #include "../../include/txq.h"
 #include "txq_internal.hpp"
+#include "txq_frames_plan.hpp"
 #include "txq_scan.hpp"
-#include "txq_text.hpp"
 
 namespace txq {
 namespace {
 
-constexpr uint32_t kUnits = 8192;            // waves of a translation call
-constexpr uint32_t kTile = 192;              // start positions per step: 64 lanes x 3 frames
-constexpr uint64_t kMinChunk = 4 * kTile;    // start positions per unit, at least
+using namespace tr;                         // kUnits, kTile, chunk_len, nucleotide and the frames' addresses: txq_frames_plan.hpp
 constexpr uint32_t kMaxK = 12;               // 5 bits per residue in 64 (and the staging buffers below)
 constexpr uint32_t kRawBytes = 256;          // 15 (alignment) + kTile + 3 kMaxK - 1 = 242 bytes at most
 constexpr uint32_t kResidues = 256;          // kTile + 3 (kMaxK - 1) = 225 residues at most
@@ -52,23 +51,6 @@ struct TrArgs {
     uint64_t* offsets;  // 6 n + 1
     uint32_t* tails;    // kUnits x 6: per unit, the counts (forward j, reverse j) of the record that runs past the unit's end
 };
-
-__device__ __forceinline__ uint64_t chunk_len(uint64_t total) {
-    const uint64_t c = (total + kUnits - 1) / kUnits;
-    const uint64_t tiles = (c + kTile - 1) / kTile;
-    return tiles * kTile < kMinChunk ? kMinChunk : tiles * kTile;
-}
-
-// T/U = 0, C = 1, A = 2, G = 3 in either case; anything else is ambiguous (4).  The complement is code ^ 2.
-__device__ __forceinline__ uint32_t nucleotide(uint8_t c) {
-    switch (c & 0xDFu) {
-        case 'T': case 'U': return 0u;
-        case 'C': return 1u;
-        case 'A': return 2u;
-        case 'G': return 3u;
-        default: return 4u;
-    }
-}
 
 template <bool FILL>
 __global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
@@ -198,6 +180,99 @@ __global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
         for (int c = 0; c < 6; ++c)
             if (lane == (uint32_t)c) mine = cnt[c];
         a.tails[(uint64_t)blockIdx.x * 6 + lane] = runs_on ? mine : 0u;
+    }
+}
+
+// ---- frames as letters ----------------------------------------------------------------------------------------------------
+// txq_translate_frames_device: the six frames of every record as residue letters, back to back, in the form
+// the edit-distance kernels take their patterns.  The pass is translate_kernel's — the same units, the same steps of kTile
+// start positions, the same staging of the bytes — but nothing is compacted: a frame's length is closed-form in L, so the
+// offsets are a per-record fill and a scan, and the codon at start position p has its place in both directions
+// (txq_frames_plan.hpp).  A step yields six runs of up to 64 letters, which are staged in LDS at their address modulo 16 and
+// stored as the 16-byte blocks, 4-byte words and single bytes that lie inside the run (store_block): the units next to this
+// one write the bytes next to the run, so no store covers a byte that is not the run's and nothing is read back.
+
+struct FrArgs {
+    const uint8_t* seq;
+    const uint64_t* rec;  // n + 1
+    uint64_t n;
+    uint8_t* frames;
+    uint64_t cap;             // bytes of `frames`: nothing at or behind it is written
+    const uint64_t* offsets;  // 6 n + 1, complete
+};
+
+__global__ __launch_bounds__(256) void frame_lengths_kernel(const uint64_t* __restrict__ rec, uint64_t n, uint64_t* __restrict__ offsets) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r == 0) offsets[0] = 0;
+    if (r >= n) return;
+    const uint64_t L = rec[r + 1] - rec[r];
+#pragma unroll
+    for (uint32_t f = 0; f < 6; ++f) offsets[1 + 6 * r + f] = frame_len(L, f % 3);
+}
+
+struct GlobalSink {
+    __device__ __forceinline__ void store16(uintptr_t at, const uint8_t* src) { *reinterpret_cast<text4*>(at) = *reinterpret_cast<const text4*>(src); }
+    __device__ __forceinline__ void store4(uintptr_t at, const uint8_t* src) { *reinterpret_cast<uint32_t*>(at) = *reinterpret_cast<const uint32_t*>(src); }
+    __device__ __forceinline__ void store1(uintptr_t at, uint8_t byte) { *reinterpret_cast<uint8_t*>(at) = byte; }
+};
+
+__global__ __launch_bounds__(64) void frames_kernel(FrArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t raw[kRawBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kRuns][kStageRow];  // run c, the byte for address x at x - block_floor(run_a0[c])
+    __shared__ uint64_t run_org[kRuns], run_a0[kRuns], run_a1[kRuns];         // the run's frame begins at org; the run is the addresses [a0, a1)
+    const uint32_t lane = threadIdx.x;
+    const uint64_t base = a.rec[0], end = a.rec[a.n];
+    if (end <= base) return;
+    const uint64_t chunk = chunk_len(end - base);
+    const uint64_t ua = base + (uint64_t)blockIdx.x * chunk;
+    if (ua >= end) return;
+    const uint64_t ub = ua + chunk < end ? ua + chunk : end;
+    const uintptr_t seq_lo = (uintptr_t)(a.seq + base), seq_hi = (uintptr_t)(a.seq + end);
+    const uintptr_t out_lo = (uintptr_t)a.frames, out_hi = out_lo + a.cap;
+    GlobalSink sink;
+    for (uint64_t r = record_of(a.rec, 0, a.n, ua); r < a.n; ++r) {
+        const uint64_t rs = a.rec[r];
+        if (rs >= ub) break;
+        const uint64_t re = a.rec[r + 1], L = re - rs;
+        if (L < 3) continue;
+        const Owned own = owned_starts(rs, re, ua, ub);
+        if (own.lo >= own.hi) continue;
+        uint64_t org = 0;
+        if (lane < kRuns) run_org[lane] = org = out_lo + a.offsets[6 * r + run_frame(L, lane)];
+        for (uint64_t t0 = own.lo / 3 * 3; t0 < own.hi; t0 += kTile) {
+            // stage the step's bytes: 16-byte blocks, 'N' for what lies outside the sequence buffer (txq_text.hpp load_block)
+            const uintptr_t first = (uintptr_t)(a.seq + rs + t0);
+            const uint32_t shift = (uint32_t)(first & 15u);
+            const uint64_t left = L - t0;
+            const uint32_t nbytes = left < kTile + 2 ? (uint32_t)left : kTile + 2;
+            if (lane < (shift + nbytes + 15u) / 16u)
+                *reinterpret_cast<text4*>(raw + 16u * lane) = load_block(first - shift + 16u * lane, seq_lo, seq_hi, 'N').w;
+            if (lane < kRuns) {
+                const Run q = step_run(L, t0, own, lane);
+                run_a0[lane] = org + q.first;
+                run_a1[lane] = org + q.first + q.count;
+            }
+            __syncthreads();
+#pragma unroll
+            for (uint32_t i = lane; i < kTile; i += 64) {
+                const uint64_t p = t0 + i;
+                if (p < own.lo || p >= own.hi) continue;  // (hi <= L - 2: the codon fits)
+                const uint32_t j = i % 3;                 // = p mod 3
+                uint8_t f, g;
+                codon_letters(kTable1, nucleotide(raw[shift + i]), nucleotide(raw[shift + i + 1]), nucleotide(raw[shift + i + 2]), &f, &g);
+                stage[j][run_org[j] + fwd_index(p) - block_floor(run_a0[j])] = f;
+                stage[3 + j][run_org[3 + j] + rev_index(L, p) - block_floor(run_a0[3 + j])] = g;
+            }
+            __syncthreads();
+            if (lane < kRuns * kRunBlocks) {
+                const uint32_t c = lane / kRunBlocks, b = lane % kRunBlocks;
+                const uintptr_t a0 = run_a0[c], a1 = run_a1[c] < out_hi ? run_a1[c] : out_hi;
+                const uintptr_t blk = block_floor(a0) + 16u * b;
+                const uint32_t mask = block_mask(a0, a1, blk);
+                if (mask) store_block(mask, blk, &stage[c][16u * b], sink);
+            }
+            __syncthreads();
+        }
     }
 }
 
@@ -352,6 +427,62 @@ int txq_translate(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_reco
         else d.download(values, s_val, offsets[m] * 8);
     }
     if (d.error() != hipSuccess) return fail_hip(d.error(), "txq_translate copies");
+    return rc;
+}
+
+uint64_t txq_translate_frames_bound(const uint64_t* rec_offsets, size_t n_records) {
+    if (n_records && !rec_offsets) {
+        (void)fail(TXQ_ERR_ARG, "txq_translate_frames_bound: null offsets");
+        return UINT64_MAX;
+    }
+    if (check_ascending(rec_offsets, n_records, "record")) return UINT64_MAX;
+    uint64_t bound = 0;
+    for (size_t r = 0; r < n_records; ++r)
+        for (uint32_t o = 0; o < 3; ++o) bound += 2 * frame_len(rec_offsets[r + 1] - rec_offsets[r], o);
+    return bound;
+}
+
+int txq_translate_frames_device(const uint8_t* d_seq, const uint64_t* d_rec_offsets, size_t n_records, uint8_t* d_frames, size_t frames_bytes,
+                                uint64_t* d_frame_offsets, void* stream) {
+    if (!d_frame_offsets || (n_records && !d_rec_offsets) || (frames_bytes && !d_frames)) return fail(TXQ_ERR_ARG, "null argument");
+    (void)d_seq;  // (may be null where there are no bytes: only the caller knows)
+    if (n_records > 0x7FFFFFFFull / 6) return fail(TXQ_ERR_ARG, "at most 2^31 / 6 records per call");
+    if (int rc = require_init()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_records == 0) {
+        const hipError_t e = hipMemsetAsync(d_frame_offsets, 0, 8, st);
+        return e == hipSuccess ? TXQ_OK : fail_hip(e, "hipMemsetAsync");
+    }
+    frame_lengths_kernel<<<(unsigned)((n_records + 255) / 256), 256, 0, st>>>(d_rec_offsets, (uint64_t)n_records, d_frame_offsets);
+    scan_kernel<<<1, 1024, 0, st>>>(d_frame_offsets + 1, (uint64_t)(6 * n_records));
+    frames_kernel<<<kUnits, 64, 0, st>>>(FrArgs{d_seq, d_rec_offsets, (uint64_t)n_records, d_frames, (uint64_t)frames_bytes, d_frame_offsets});
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "translate frames kernel launch");
+    return TXQ_OK;
+}
+
+int txq_translate_frames(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_records, uint8_t* frames, size_t frames_bytes,
+                         uint64_t* frame_offsets) {
+    if (!frame_offsets || (n_records && !rec_offsets)) return fail(TXQ_ERR_ARG, "null argument");
+    const uint64_t bound = txq_translate_frames_bound(rec_offsets, n_records);
+    if (bound == UINT64_MAX) return TXQ_ERR_ARG;
+    if (frames_bytes < bound) return fail(TXQ_ERR_ARG, "the frames need %llu bytes, the buffer has %zu", (unsigned long long)bound, frames_bytes);
+    const uint64_t first = n_records ? rec_offsets[0] : 0, bytes = n_records ? rec_offsets[n_records] - first : 0;
+    if ((bytes && !seq) || (bound && !frames)) return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = require_init()) return rc;
+    const size_t m = 6 * n_records;
+    DeviceStage d;  // (+16: the kernel's 16-byte loads of the sequence end inside the slice; +8: no slice of no bytes)
+    const size_t s_seq = d.add(bytes + 16), s_rec = d.add((n_records + 1) * 8), s_off = d.add((m + 1) * 8), s_frm = d.add(bound + 8);
+    if (const hipError_t e = d.alloc(); e != hipSuccess) return fail_hip(e, "hipMalloc");
+    const std::vector<uint64_t> ro = n_records ? rebased(rec_offsets, n_records) : std::vector<uint64_t>{0};
+    if (bytes) d.upload(s_seq, seq + first, bytes);
+    d.upload(s_rec, ro.data(), ro.size() * 8);
+    int rc = TXQ_OK;
+    if (d.error() == hipSuccess)
+        rc = txq_translate_frames_device(d.at<uint8_t>(s_seq), d.at<uint64_t>(s_rec), n_records, d.at<uint8_t>(s_frm), bound, d.at<uint64_t>(s_off), nullptr);
+    if (rc == TXQ_OK) d.download(frame_offsets, s_off, (m + 1) * 8);  // (waits for the kernels)
+    if (rc == TXQ_OK && d.error() == hipSuccess && bound) d.download(frames, s_frm, bound);
+    if (d.error() != hipSuccess) return fail_hip(d.error(), "txq_translate_frames copies");
     return rc;
 }
 
