@@ -1,6 +1,7 @@
 """numpy restatements for the size-aware HIBF layout (include/txq.h txq_sketch_device / txq_union_estimates_device /
 txq_tree_insert_device, tetrex_amd/csrc/host/layout.hpp): the hash, the HyperLogLog registers and estimator, the part rule
-of split bins, and checks of a layout's structure."""
+of split bins, checks of a layout's structure, and what tests/test_gpu_build_kernels.py makes its inputs with: the inverse
+of the hash, values crafted for a register and a rank, the sketch's slices and the chunk rule of the build."""
 import math
 
 import numpy as np
@@ -21,6 +22,45 @@ def fmix(x):
         x *= _U(0x94d049bb133111eb)
         x ^= x >> _U(31)
     return x
+
+
+_INV_C1 = pow(0xbf58476d1ce4e5b9, -1, 1 << 64)
+_INV_C2 = pow(0x94d049bb133111eb, -1, 1 << 64)
+
+
+def inv_fmix(x):
+    """The inverse of fmix: each xorshift undone (y ^ y >> s ^ y >> 2s ...), each multiply by the constant's inverse mod 2^64."""
+    x = np.array(x, dtype=np.uint64, copy=True)
+    with np.errstate(over="ignore"):
+        x ^= (x >> _U(31)) ^ (x >> _U(62))
+        x *= _U(_INV_C2)
+        x ^= (x >> _U(27)) ^ (x >> _U(54))
+        x *= _U(_INV_C1)
+        x ^= (x >> _U(30)) ^ (x >> _U(60))
+    return x
+
+
+def craft(reg, rank):
+    """The hashed value x that sets register `reg` to exactly `rank` (1 .. 53): the top 12 bits are reg, the low 52 bits
+    1 << (52 - rank), or 0 for rank 53 (x << 12 == 0).  inv_fmix(craft(reg, rank)) is the value to put in a bin."""
+    reg, rank = np.asarray(reg, dtype=np.uint64), np.asarray(rank, dtype=np.uint64)
+    assert np.all(reg < M) and np.all((rank >= 1) & (rank <= 53))
+    low = np.where(rank < 53, _U(1) << (_U(52) - np.minimum(rank, _U(52))), _U(0))
+    return (reg << _U(52)) | low
+
+
+def sketch_slices(n):
+    """(first, last) index of every slice of a bin of n values, as sketch_kernel cuts it: 16 workgroups at most, each with
+    max(16384, ceil(n / 16)) values, a slice that would begin at or behind n not run."""
+    chunk = max(16384, (n + 15) // 16)
+    return [(s * chunk, min(n, (s + 1) * chunk) - 1) for s in range(16) if s * chunk < n]
+
+
+def chunk_csr(flat, offsets, g0, g1):
+    """Values [g0, g1) of a CSR array as a chunk of its own over all bins (device_index.cpp upload_chunk):
+    offsets[b] = clamp(offsets[b], g0, g1) - g0.  Returns (values, offsets, n_values)."""
+    offs = np.asarray(offsets, dtype=np.uint64)
+    return flat[g0:g1], np.clip(offs, _U(g0), _U(g1)) - _U(g0), g1 - g0
 
 
 def _clz64(w):

@@ -8,9 +8,12 @@ from tetrex_amd import host
 
 pytestmark = pytest.mark.gpu
 
-MOTIFS = ["(LMAEGLYN)", "(^M.K)", "(GT$)", "(A(C+|G+)T)", "(A.{12}C)", "(C.{2,4}C.{3}[LIVMFYWC])", "(A|)", "(^MAEG$)"]
-INSTANCE = ["LMAEGLYN", "MWK", "GT", "ACCCT", "AWWWWWWWWWWWWC", "CWWCWWWL", "", "MAEG"]
+MOTIFS = ["(LMAEGLYN)", "(^M.K)", "(GT$)", "(A(C+|G+)T)", "(A.{12}C)", "(C.{2,4}C.{3}[LIVMFYWC])", "(A|)", "(^MAEG$)",
+          "(A.{9}C)", "(A.{11}C)", "(A.{9}C+T)"]
+INSTANCE = ["LMAEGLYN", "MWK", "GT", "ACCCT", "AWWWWWWWWWWWWC", "CWWCWWWL", "", "MAEG",
+            "AWWWWWWWWWC", "AWWWWWWWWWWWC", "AWWWWWWWWWCCT"]
 LDS, L2 = 0, 4  # a small automaton and the one above 64 KiB
+MIDDLE = (8, 9, 10)  # tables of 9 536, 37 184 and 14 400 bytes: the tier between (64 KiB of LDS); the last one is unbounded
 BOUNDARY = 256  # a multiple of both chunks the tests run
 
 
@@ -24,7 +27,8 @@ def capi():
 @pytest.fixture(scope="module")
 def automata():
     blobs = [host.regex_automaton(rx, True) for rx in MOTIFS]
-    assert len(blobs[L2]) > 65536 and all(len(b) <= 8192 for i, b in enumerate(blobs) if i != L2)
+    assert len(blobs[L2]) > 65536 and all(len(b) <= 8192 for i, b in enumerate(blobs) if i != L2 and i not in MIDDLE)
+    assert all(8192 < len(blobs[i]) <= 65536 for i in MIDDLE)  # each of the three table tiers is there
     return blobs
 
 
@@ -45,7 +49,7 @@ def case(automata):
         expect[(a, len(recs) - 1)] = True
 
     # group 0: matches that straddle a chunk boundary, end exactly on one, begin exactly on one
-    for a in (0, 3, 4, 5):
+    for a in (0, 3, 4, 5) + MIDDLE:
         planted(a, len(INSTANCE[a]) // 2 - 1)          # the boundary in the middle of the match
         planted(a, BOUNDARY - 1)                       # the match's last byte is a chunk's last byte
         planted(a, len(INSTANCE[a]) - 1)               # its first byte is a chunk's first byte
@@ -77,7 +81,7 @@ def case(automata):
     recs = [r.encode() for r in recs]
     assert sum(len(r) for r in recs) % 16 != 0 and sum(len(r) for r in recs) < 1_000_000
     # every automaton on groups 0 and 2 (several pairs on one group, one automaton on several groups), some on the others
-    pairs = [(a, g) for g in (0, 2) for a in range(len(MOTIFS))] + [(LDS, 1), (L2, 1), (LDS, 3), (L2, 3), (3, 3)]
+    pairs = [(a, g) for g in (0, 2) for a in range(len(MOTIFS))] + [(LDS, 1), (L2, 1), (LDS, 3), (L2, 3), (3, 3), (MIDDLE[1], 1), (MIDDLE[1], 3), (MIDDLE[2], 3)]
     want = host.regex_filter(automata, recs, groups, pairs)
     for (a, r), answer in expect.items():
         assert want[pairs.index((a, 0))][r] == answer, (MOTIFS[a], r, recs[r][:40])
@@ -94,7 +98,8 @@ def _same(got, want):
 @pytest.mark.parametrize("chunk", [None, "16"])
 def test_parity_with_host_twin(capi, automata, case, monkeypatch, chunk):
     """bounded matches across, at and behind chunk boundaries; ^ and $ off the boundaries; records of 0, 1, 15, 16, 17 and 5 000
-    bytes; groups of 0, 1 and 70 records; a text whose size is no multiple of 16; both table tiers in one call"""
+    bytes; groups of 0, 1 and 70 records; a text whose size is no multiple of 16; all three table tiers in one call (tables
+    of at most 8 KiB, of at most 64 KiB — regex_kernel<kLargeLds>, MIDDLE — and above, read from L2)"""
     if chunk:
         monkeypatch.setenv("TXQ_REGEX_CHUNK", chunk)
     recs, groups, pairs, want = case
@@ -106,7 +111,8 @@ def test_parity_with_host_twin(capi, automata, case, monkeypatch, chunk):
 @pytest.mark.parametrize("chunk", [None, "16"])
 def test_unbounded_automaton_and_serial_cap(capi, automata, monkeypatch, chunk):
     """A(C+|G+)T with TXQ_REGEX_MAX_SERIAL=256: a record of 300 bytes is flagged whether or not it holds a match, records of
-    255 and 256 bytes are answered exactly; the bounded automaton beside it does not know the cap"""
+    255 and 256 bytes are answered exactly; the bounded automaton beside it does not know the cap.  A.{9}C+T, unbounded with a
+    table of the middle tier, is capped and answered in the same way."""
     monkeypatch.setenv("TXQ_REGEX_MAX_SERIAL", "256")
     if chunk:
         monkeypatch.setenv("TXQ_REGEX_CHUNK", chunk)
@@ -114,9 +120,10 @@ def test_unbounded_automaton_and_serial_cap(capi, automata, monkeypatch, chunk):
     for n in (255, 256, 300):
         recs += [b"W" * n, b"W" * (n - 9) + b"AGGGGGGGT", b"ACT" + b"W" * (n - 3), b"W" * (n - 120) + b"A" + b"C" * 118 + b"T"]
     recs.append(b"W" * 290 + b"LMAEGLYN" + b"WW")
-    pairs = [(3, 0), (LDS, 0)]
+    pairs = [(3, 0), (LDS, 0), (MIDDLE[2], 0)]
     want = host.regex_filter(automata, recs, [0, len(recs)], pairs, max_serial=256)
     assert want[0].tolist() == [False, True, True, True] * 2 + [True] * 5 and want[1].tolist() == [False] * 12 + [True]
+    assert want[2].tolist() == [False, False, False, True] * 2 + [True] * 5  # only A C{118} T holds A.{9}C+T
     _same(capi.regex_filter(automata, recs, [0, len(recs)], pairs), want)
 
 

@@ -713,21 +713,81 @@ def _csr(values_per_bin):
     return flat, offsets
 
 
+def _padded_values(flat, n_values):
+    """The values on the device, zero-filled up to n_values where the call names more than there are"""
+    flat = np.ascontiguousarray(flat, dtype=np.uint64)
+    if flat.size < max(1, int(n_values)):
+        flat = np.concatenate([flat, np.zeros(max(1, int(n_values)) - flat.size, dtype=np.uint64)])
+    return DeviceBuffer.from_numpy(flat)
+
+
 def sketch(values_per_bin):
     """HyperLogLog registers of every bin (txq_sketch_device): uint8 array (B, 4096)."""
+    flat, offsets = _csr(values_per_bin)
+    return sketch_csr(flat, offsets, flat.size)
+
+
+def sketch_csr(flat, offsets, n_values, registers=None):
+    """txq_sketch_device on a CSR array as the caller cut it: bin b holds flat[offsets[b] .. offsets[b+1]), of which only
+    indices below n_values count.  registers: what earlier chunks left, (B, 4096) uint8 (None: zeroes); returns the registers
+    after this call."""
     L = lib()
     L.txq_sketch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    flat, offsets = _csr(values_per_bin)
-    B = len(values_per_bin)
-    dv, do = DeviceBuffer.from_numpy(flat if flat.size else np.zeros(1, np.uint64)), DeviceBuffer.from_numpy(offsets)
-    dr = DeviceBuffer.from_numpy(np.zeros(B * HLL_REGISTERS, dtype=np.uint8))
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    B = offsets.size - 1
+    regs = np.zeros((B, HLL_REGISTERS), dtype=np.uint8) if registers is None else np.ascontiguousarray(registers, dtype=np.uint8)
+    if regs.shape != (B, HLL_REGISTERS):
+        raise ValueError("registers must be (%d, %d)" % (B, HLL_REGISTERS))
+    dv, do = _padded_values(flat, n_values), DeviceBuffer.from_numpy(offsets)
+    dr = DeviceBuffer.from_numpy(regs if regs.size else np.zeros(1, dtype=np.uint8))
     try:
-        check(L.txq_sketch_device(dv.ptr, flat.size, do.ptr, B, dr.ptr, None))
+        check(L.txq_sketch_device(dv.ptr, int(n_values), do.ptr, B, dr.ptr, None))
         check(L.txq_synchronize())
         return dr.to_numpy(np.uint8, (B, HLL_REGISTERS))
     finally:
         for b in (dv, do, dr):
             b.free()
+
+
+def tree_insert(flat, offsets, n_values, path_offsets, path, ibfs, words=None):
+    """txq_tree_insert_device: the values of a CSR array (bin b: flat[offsets[b] .. offsets[b+1]), indices below n_values)
+    into every IBF on their bin's path.  path: rows of (ibf, first technical bin, parts), path_offsets: each bin's rows.
+    ibfs: dicts {bins, bin_size, hash_funs}; one with bin_size 0 gets no matrix (a null pointer).  words: what earlier calls
+    left, one array per IBF (None: zeroes).  Returns each IBF's [bin_size * bin_words] words after this call."""
+    L = lib()
+    L.txq_tree_insert_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_uint64, C.c_void_p]
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    path_offsets = np.ascontiguousarray(path_offsets, dtype=np.uint64)
+    path = np.ascontiguousarray(path, dtype=np.uint64).reshape(-1, 3)
+    B = offsets.size - 1
+    if path_offsets.size != B + 1 or (B and int(path_offsets.max()) > path.shape[0]):
+        raise ValueError("path_offsets must hold n_bins + 1 offsets into the path rows")
+    n = len(ibfs)
+    descs = (IbfDesc * max(1, n))()
+    sizes, d_words = [], []
+    bufs = [_padded_values(flat, n_values), DeviceBuffer.from_numpy(offsets), DeviceBuffer.from_numpy(path_offsets),
+            DeviceBuffer.from_numpy(path if path.size else np.zeros(3, dtype=np.uint64))]
+    try:
+        for i, f in enumerate(ibfs):
+            descs[i] = _ibf_desc(f["bins"], f["bin_size"], f["hash_funs"], None)
+            sizes.append(int(f["bin_size"]) * int(descs[i].bin_words))
+            w = np.zeros(sizes[i], dtype=np.uint64) if words is None else np.ascontiguousarray(words[i], dtype=np.uint64)
+            if w.size != sizes[i]:
+                raise ValueError("IBF %d has %d words" % (i, sizes[i]))
+            d_words.append(DeviceBuffer.from_numpy(w) if sizes[i] else None)
+            if sizes[i]:
+                descs[i].words = C.cast(C.c_void_p(d_words[i].ptr), u64p)
+        d_descs = DeviceBuffer(C.sizeof(descs))
+        bufs.append(d_descs)
+        check(L.txq_memcpy_h2d(d_descs.ptr, C.addressof(descs), C.sizeof(descs)))
+        check(L.txq_tree_insert_device(bufs[0].ptr, int(n_values), bufs[1].ptr, B, bufs[2].ptr, bufs[3].ptr, d_descs.ptr, n, None))
+        check(L.txq_synchronize())
+        return [d.to_numpy(np.uint64, (s,)) if d is not None else np.zeros(0, dtype=np.uint64) for d, s in zip(d_words, sizes)]
+    finally:
+        for b in bufs + d_words:
+            if b is not None:
+                b.free()
 
 
 def union_estimates(registers, order, window):
@@ -737,7 +797,7 @@ def union_estimates(registers, order, window):
     regs = np.ascontiguousarray(registers, dtype=np.uint8)
     B = regs.shape[0]
     dr, do = DeviceBuffer.from_numpy(regs), DeviceBuffer.from_numpy(np.asarray(order, dtype=np.uint32))
-    de = DeviceBuffer(B * window * 8)
+    de = DeviceBuffer.from_numpy(np.full(B * window, np.nan))  # an entry the kernel leaves out stays NaN
     try:
         check(L.txq_union_estimates_device(dr.ptr, do.ptr, B, window, de.ptr, None))
         check(L.txq_synchronize())
@@ -761,7 +821,8 @@ def pair_unions(registers, ids):
         check(L.txq_pair_unions_device(None, None, 0, None, None))
         return np.zeros((0, 0), dtype=np.float64)
     dr, di = DeviceBuffer.from_numpy(regs), DeviceBuffer.from_numpy(ids)
-    de = DeviceBuffer(min(n, 4096) ** 2 * 8)  # n > 4096 is refused by the library
+    # n > 4096 is refused by the library; an entry the kernel leaves out stays NaN
+    de = DeviceBuffer.from_numpy(np.full(n * n, np.nan)) if n <= 4096 else DeviceBuffer(4096 ** 2 * 8)
     try:
         check(L.txq_pair_unions_device(dr.ptr, di.ptr, n, de.ptr, None))
         check(L.txq_synchronize())

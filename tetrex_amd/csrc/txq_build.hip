@@ -1,7 +1,7 @@
 // Index construction kernels for gfx950 (`tetrex index --layout sized`, host/layout.hpp): HyperLogLog sketches of the
 // user bins, the table of union estimates the layout DP reads, and the insertion of every k-mer into each IBF on its user
 // bin's path.  The hash, the registers and the estimator are defined exactly (include/txq.h) so that a numpy restatement
-// matches them bit for bit (tests/test_gpu_sized_hibf.py).
+// matches them bit for bit (tests/test_gpu_sized_hibf.py; each kernel alone at its edges: tests/test_gpu_build_kernels.py).
 #include "txq_internal.hpp"
 
 #include <cmath>
