@@ -170,6 +170,16 @@ int txh_peptide_codes(unsigned reduction, uint8_t out[256]);
 int txh_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
                     size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
                     const uint8_t* codes, unsigned threads, uint32_t* out);
+/* Start and alignment of confirmed pairs on the host (host/edit_distance.hpp): the semantics and the layout of
+ * txq_edit_align_device (include/txq.h: the walk back by three rules, 2 max_errors + 3 u32 words a pair — start, n_runs, runs as
+ * (length << 2) | op —, "none" and the refusal marker passed on) with NO limit on the pattern length or the distance.  The CPU
+ * twin of that kernel: it answers the pairs the device declines and the kernel is compared with it.  results: the 3 u32 a
+ * search call wrote per pair.  A pair with d > max_errors, or whose triple is not a cell of its matrix (a record outside the
+ * group, an end beyond the record, d > m, D[m][j] != d), gets start = 0xFFFFFFFE and nothing else written.  Buffers, threads and
+ * the return value as txh_edit_search; max_errors is at most 2^24. */
+int txh_edit_align(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                   size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs, const uint32_t* results,
+                   const uint8_t* codes, uint32_t max_errors, unsigned threads, uint32_t* align);
 
 /* ---- .ibf index files (include/index_base.h:160-202 layout; see host/index_file.hpp) ---- */
 typedef struct txh_index txh_index;

@@ -20,6 +20,7 @@
  *                              the one-value, threshold-1 call at include/index_hibf.h:142-147 (`tetrex search`)
  *   txq_edit_search / _device  (no counterpart: `tetrex search --verify` confirms candidate bins by edit distance)
  *   txq_edit_search_long / _device  (the same for patterns of up to 4096 bytes, the pattern spread over the lanes of a wave)
+ *   txq_edit_align / _device  (no counterpart: start and CIGAR of the pairs a search call confirmed, `--verify --align`)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every function returns 0 on success or a
  * negative txq_status; txq_last_error() gives the message for the calling thread.  Host buffers are
@@ -299,6 +300,47 @@ int txq_edit_search_long_device(const uint8_t* d_patterns, const uint64_t* d_pat
 int txq_edit_search_long(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
                          size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
                          const uint8_t* codes, uint32_t* out);  /* host buffers, synchronous */
+
+/* Where a confirmed match begins, and its alignment (`tetrex search --verify --align`; not in the reference).
+ * Take a pair (pattern P of m bytes, group, cap) of txq_edit_search* above, its result (d, r, j) with d != 0xFFFFFFFF, R = record
+ * r, the class table and Sellers' D as defined there (D[0][.] = 0, D[.][0] = i).  The alignment of the pair is the path found
+ * by walking back from (i, j') = (m, j) until i = 0, at each cell taking the FIRST rule that holds:
+ *   1. diagonal: j' > 0 and D[i-1][j'-1] + c = D[i][j'], c = 0 if P[i-1] and R[j'-1] match, else 1: operation '=' where c = 0,
+ *      'X' where c = 1; then i--, j'--;
+ *   2. up: D[i-1][j'] + 1 = D[i][j']: operation 'I', a pattern letter with no target letter; then i--;
+ *   3. left: operation 'D', a target letter skipped; then j'--.
+ * `start` is the j' at which i reaches 0 — the bytes of R in front of the match, which is R[start .. j) — and the operations,
+ * read from the pattern's first letter to its last, are run-length encoded.  There are at most 2 d + 1 runs; the '=', 'X' and
+ * 'D' lengths sum to j - start, the '=', 'X' and 'I' lengths to m, the 'X', 'I' and 'D' lengths to d.  A byte of no class
+ * matches nothing, itself included, so it gives 'X'.
+ * Arguments: the pattern, text and group buffers and the d_pairs of the search call, the d_out it wrote (read on the device:
+ * queue this call behind the search call on the same stream; no host round trip is needed in between), the class table, and
+ * max_errors, which sizes the answers: pair i owns d_align[i * TXQ_EDIT_ALIGN_STRIDE(max_errors) ..), u32 words
+ *     start, n_runs, then n_runs runs as (length << 2) | op with op 0 '=', 1 'X', 2 'I', 3 'D'; the other run words are zero.
+ * A pair whose result is "none" gets start = 0xFFFFFFFF, n_runs = 0 and zero run words; a pair that carries the search calls'
+ * refusal marker, or that this call's own checks refuse (a pattern or group out of range, an empty pattern, offsets that leave
+ * their array), gets start = 0xFFFFFFFF, n_runs = 0xFFFFFFFE and zero run words.  A pair the device does not align gets start =
+ * 0xFFFFFFFE and NOTHING else of its words is written: d > TXQ_EDIT_ALIGN_MAX_DISTANCE (the 2 d + 1 diagonals of the walk are
+ * the lanes of one wave), d > max_errors, m > TXQ_EDIT_LONG_MAX_PATTERN — the caller takes these to txh_edit_align of
+ * include/txh.h, the same semantics on the host with no limit on m or d —, and a triple that is not a cell of the pair's matrix
+ * (the triples are device data: a record outside the group, an end beyond the record, d > m, D[m][j] != d).  Whatever the
+ * offsets and the triples say, no load or store leaves a buffer.  The result is deterministic; the call allocates nothing,
+ * reads nothing back and does not synchronise with the host.  max_errors is at most TXQ_EDIT_ALIGN_MAX_ERRORS (TXQ_ERR_ARG).
+ * d_workspace: TXQ_EDIT_ALIGN_WORKSPACE(n_pairs) bytes — none: a wave keeps the direction bits of its pair in LDS (16 bytes a
+ * pattern letter), so the argument may be null and nothing of it is touched; it is there for the shape the sibling calls have.
+ * txq_edit_align is the synchronous twin on host buffers; it checks them first as txq_edit_search does (any m >= 1 passes: a
+ * long pattern is declined, not refused).  A declined pair's words behind the marker keep what `align` held. */
+#define TXQ_EDIT_ALIGN_MAX_DISTANCE 31
+#define TXQ_EDIT_ALIGN_MAX_ERRORS (1u << 24)
+#define TXQ_EDIT_ALIGN_STRIDE(max_errors) (2 * (size_t)(max_errors) + 3)
+#define TXQ_EDIT_ALIGN_WORKSPACE(n_pairs) ((size_t)0)
+int txq_edit_align_device(const uint8_t* d_patterns, const uint64_t* d_pat_offsets, size_t n_patterns, size_t pattern_bytes,
+                          const uint8_t* d_text, const uint64_t* d_rec_offsets, size_t n_records, size_t text_bytes,
+                          const uint64_t* d_group_offsets, size_t n_groups, const uint32_t* d_pairs, size_t n_pairs, const uint32_t* d_out,
+                          const uint8_t* d_codes, uint32_t max_errors, uint32_t* d_align, void* d_workspace, void* stream);
+int txq_edit_align(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                   size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs, const uint32_t* results,
+                   const uint8_t* codes, uint32_t max_errors, uint32_t* align);  /* host buffers, synchronous */
 
 /* Which records of a bin does a regular expression match?  (`tetrex query --gpu-verify`; not in the reference.)
  * An automaton is a blob of include/txq_regex.h, where its layout and the meaning of "matches" are stated (as code: the

@@ -24,7 +24,7 @@ SYMBOLS = [
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
     "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_translate_frames_bound", "txq_translate_frames_device", "txq_translate_frames",
     "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
-    "txq_edit_search_long", "txq_edit_search_long_device",
+    "txq_edit_search_long", "txq_edit_search_long_device", "txq_edit_align", "txq_edit_align_device",
     "txq_regex_filter", "txq_regex_filter_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
@@ -96,6 +96,11 @@ def lib():
                                       C.c_void_p, C.c_void_p]
         L.txq_edit_search_long_device.argtypes = L.txq_edit_search_device.argtypes
         L.txq_edit_search_long.argtypes = L.txq_edit_search.argtypes
+        L.txq_edit_align_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]
+        L.txq_edit_align.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.txq_regex_filter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
@@ -637,6 +642,77 @@ def edit_search_long(patterns, records, groups, pairs, codes):
     check(lib().txq_edit_search_long(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
                                      go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], cd.ctypes.data, out.ctypes.data))
     return out
+
+
+EDIT_ALIGN_MAX_DISTANCE = 31
+EDIT_ALIGN_DECLINED = 0xFFFFFFFE  # start of a pair the device does not align: txh_edit_align (tetrex_amd.host.edit_align) answers it
+EDIT_ALIGN_OPS = "=XID"
+
+
+def edit_align_stride(max_errors):
+    """TXQ_EDIT_ALIGN_STRIDE: the uint32 words of one pair's answer"""
+    return 2 * int(max_errors) + 3
+
+
+def decode_alignments(words, max_errors):
+    """The answers of txq_edit_align in the layout of include/txq.h as (start uint32[n], list of [(op, length), ...]) with op
+    one of "=XID"; a pair whose start is EDIT_NONE or EDIT_ALIGN_DECLINED has no runs."""
+    words = np.asarray(words, dtype=np.uint32).reshape(-1, edit_align_stride(max_errors))
+    runs = []
+    for row in words:
+        n = int(row[1]) if int(row[0]) < EDIT_ALIGN_DECLINED else 0
+        runs.append([(EDIT_ALIGN_OPS[int(w) & 3], int(w) >> 2) for w in row[2:2 + n]])
+    return words[:, 0].copy(), runs
+
+
+def edit_align(patterns, records, groups, pairs, results, codes, max_errors, raw=False):
+    """Start and alignment of the pairs a search confirmed, on the GPU (txq_edit_align, include/txq.h).  The arguments of
+    edit_search, then results, the (n, 3) array edit_search or edit_search_long returned for these pairs, and max_errors,
+    which sizes the answers.  Returns (start uint32[n], list of [(op, length), ...]); raw=True: the (n, 2 max_errors + 3)
+    uint32 words instead (a declined pair keeps the 0xA5A5A5A5 fill behind its marker)."""
+    pat, po, txt, ro, go, pr, cd = edit_arrays(patterns, records, groups, pairs, codes)
+    res = np.ascontiguousarray(results, dtype=np.uint32).reshape(-1, 3)
+    if res.shape != pr.shape or not 0 <= int(max_errors) <= 1 << 24:
+        raise TxqError(-1, "edit_align: one result triple per pair, max_errors at most 2^24")
+    out = np.full((pr.shape[0], edit_align_stride(max_errors)), 0xA5A5A5A5, dtype=np.uint32)
+    check(lib().txq_edit_align(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
+                               go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], res.ctypes.data, cd.ctypes.data, int(max_errors),
+                               out.ctypes.data))
+    return out if raw else decode_alignments(out, max_errors)
+
+
+def edit_align_device(patterns, records, groups, pairs, codes, max_errors, results=None, long=False, pat_at=0, text_at=0, guard=64, fill=0xA5,
+                      stream=None):
+    """txq_edit_align_device on buffers the caller places: the patterns begin pat_at bytes behind a 16-byte boundary, the text
+    text_at bytes behind one — with text_at = 0 at the very start of its allocation — and the answers lie between `guard` bytes
+    of `fill` on either side.  results None: txq_edit_search_device (long: txq_edit_search_long_device) runs first and the
+    align call is queued directly behind it on `stream` (a hipStream_t as an integer; None: the default stream), nothing being
+    read back in between; otherwise the (n, 3) triples given are uploaded as they are.  Returns (results uint32 (n, 3), buffer
+    uint8[guard + 4 n stride + guard]): the answers begin at buffer[guard], and what no call wrote still holds `fill`."""
+    pat, po, txt, ro, go, pr, cd = edit_arrays(patterns, records, groups, pairs, codes)
+    n, body = pr.shape[0], 4 * pr.shape[0] * edit_align_stride(max_errors)
+    pat_around = np.full(pat_at + pat.size + 33, ord("A"), dtype=np.uint8)
+    pat_around[pat_at:pat_at + pat.size] = pat
+    txt_around = np.full(text_at + txt.size + 33, ord("A"), dtype=np.uint8)
+    txt_around[text_at:text_at + txt.size] = txt
+    given = None if results is None else np.ascontiguousarray(results, dtype=np.uint32).reshape(n, 3)
+    bufs = [DeviceBuffer.from_numpy(x) for x in (pat_around, po, txt_around, ro, go, pr, cd)]
+    d_res = DeviceBuffer(max(12 * n, 4)) if given is None else DeviceBuffer.from_numpy(given)
+    d_work = DeviceBuffer(max(edit_workspace_bytes(n), edit_long_workspace(n)))
+    d_align = DeviceBuffer.from_numpy(np.full(guard + body + guard, fill, dtype=np.uint8))
+    try:
+        assert bufs[0].ptr % 16 == 0 and bufs[2].ptr % 16 == 0 and guard % 4 == 0
+        L = lib()
+        head = (bufs[0].ptr + pat_at, bufs[1].ptr, po.size - 1, pat.size, bufs[2].ptr + text_at, bufs[3].ptr, ro.size - 1, txt.size, bufs[4].ptr,
+                go.size - 1, bufs[5].ptr, n)
+        if given is None:
+            check((L.txq_edit_search_long_device if long else L.txq_edit_search_device)(*head, bufs[6].ptr, d_res.ptr, d_work.ptr, stream))
+        check(L.txq_edit_align_device(*head, d_res.ptr, bufs[6].ptr, int(max_errors), d_align.ptr + guard, None, stream))
+        synchronize()
+        return d_res.to_numpy(np.uint32, (n, 3)), d_align.to_numpy(np.uint8, (guard + body + guard,))
+    finally:
+        for b in bufs + [d_res, d_work, d_align]:
+            b.free()
 
 
 REGEX_REFUSED = 0xFFFFFFFE

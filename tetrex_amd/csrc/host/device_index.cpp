@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <exception>
 #include <future>
 #include <memory>
 #include <numeric>
@@ -944,17 +945,38 @@ void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std:
     const size_t n_short = on_device.size();
     on_device.insert(on_device.end(), on_long.begin(), on_long.end());
     n_device_ += n_short, n_device_long_ += on_long.size(), n_host_ += on_host.size();
-    // take the better strand of `strands` results (distance, record, end); + wins on equal distance
+    // take the better strand of `strands` results (distance, record, end); + wins on equal distance.  Returns that strand, or
+    // `strands` where neither is within the cap.
     const auto settle = [&](size_t i, const uint32_t* res, const std::vector<std::string>& names) {
         Hit& h = hits[i];
+        size_t kept = strands;
         for (size_t s = 0; s < strands; ++s)
             if (res[3 * s] != kEditNone && (h.distance == kEditNone || res[3 * s] < h.distance)) {
                 h.distance = res[3 * s];
                 h.target = &names.at(res[3 * s + 1]);
                 h.end = res[3 * s + 2];
                 h.strand = s ? '-' : '+';
+                kept = s;
             }
         if (h.distance != kEditNone) ++n_confirmed_;
+        return kept;
+    };
+    // --align: the alignment of the strand that settle kept.  On the device unless TETREX_VERIFY_ALIGN=host says otherwise; what
+    // the device declines, and the pairs of the host route, wait in `pending` for the host twin.
+    const char* align_env = std::getenv("TETREX_VERIFY_ALIGN");
+    const bool align_on_device = align_ && !(align_env && std::string(align_env) == "host");
+    const uint32_t device_errors = std::min<uint32_t>(errors_, TXQ_EDIT_ALIGN_MAX_DISTANCE);  // (the device declines more anyway)
+    const size_t stride = TXQ_EDIT_ALIGN_STRIDE(device_errors);
+    struct Pending { size_t candidate, strand; uint32_t d, r, j; };
+    std::vector<Pending> pending;
+    const auto align_on_host = [&](const Pending& p, const std::string& text, const std::vector<uint64_t>& rec) {
+        const std::string pattern = letters(p.candidate, p.strand);
+        EditAlignment a;
+        if (p.r + 1 >= rec.size() ||
+            !edit_align((const uint8_t*)pattern.data(), pattern.size(), (const uint8_t*)text.data() + rec[p.r], (size_t)(rec[p.r + 1] - rec[p.r]), p.d, p.j, codes_, a))
+            throw std::runtime_error("tetrex search --align: a confirmed pair has no alignment (bin " + std::to_string(candidates[p.candidate].bin) + ")");
+        hits[p.candidate].start = a.start;
+        hits[p.candidate].runs = std::move(a.runs);
     };
     if (!on_device.empty()) {
         std::vector<uint32_t> pairs;
@@ -965,7 +987,10 @@ void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std:
                 pairs.push_back(0);
                 pairs.push_back(errors_);
             }
-        DevBuf d_pairs(pairs.size() * 4), d_out(pairs.size() * 4);
+        // (the alignments lie behind the triples: one buffer, one copy back)
+        const size_t n_pairs = pairs.size() / 3, align_words = align_on_device ? n_pairs * stride : 0;
+        DevBuf d_pairs(pairs.size() * 4), d_out((pairs.size() + align_words) * 4);
+        uint32_t* const d_align = (uint32_t*)d_out.p + pairs.size();
         static_assert(TXQ_EDIT_LONG_WORKSPACE(7) == TXQ_EDIT_WORKSPACE(7), "one workspace, cut the same way for either call");
         DevBuf d_work(TXQ_EDIT_WORKSPACE(pairs.size() / 3) + 8 * on_device.size());  // (every call its own part: they are all in flight at once)
         size_t n_calls = 0;
@@ -982,12 +1007,27 @@ void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std:
                                              (b - a) * strands, (const uint8_t*)d_codes_, (uint32_t*)d_out.p + 3 * strands * a,
                                              (unsigned char*)d_work.p + 16 * strands * a + 8 * n_calls++, nullptr),
                       is_long ? "txq_edit_search_long_device" : "txq_edit_search_device");
+            if (align_on_device)  // behind the search call on its stream: the triples are read where it left them
+                txq_check(txq_edit_align_device(patterns.d_letters, patterns.d_offsets, patterns.n_patterns, patterns.bytes, (const uint8_t*)e.d_text, d_rec,
+                                                e.n_records, e.text_bytes, d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * strands * a,
+                                                (b - a) * strands, (const uint32_t*)d_out.p + 3 * strands * a, (const uint8_t*)d_codes_, device_errors,
+                                                d_align + stride * strands * a, nullptr, nullptr),
+                          "txq_edit_align_device");
             a = b;
         }
-        std::vector<uint32_t> out(pairs.size());
+        std::vector<uint32_t> out(pairs.size() + align_words);
         txq_check(txq_memcpy_d2h(out.data(), d_out.p, out.size() * 4), "d2h");  // (waits for the kernels)
-        for (size_t k = 0; k < on_device.size(); ++k)
-            settle(on_device[k], out.data() + 3 * strands * k, bins_.at(candidates[on_device[k]].bin).names);
+        for (size_t k = 0; k < on_device.size(); ++k) {
+            const uint32_t* res = out.data() + 3 * strands * k;
+            const size_t i = on_device[k], kept = settle(i, res, bins_.at(candidates[i].bin).names);
+            if (!align_ || kept == strands) continue;
+            const uint32_t* words = out.data() + pairs.size() + stride * (strands * k + kept);
+            if (align_on_device && words[0] < kEditNotAligned) {
+                hits[i].start = words[0];
+                hits[i].runs.assign(words + 2, words + 2 + words[1]);
+                ++n_align_device_;
+            } else pending.push_back({i, kept, res[3 * kept], res[3 * kept + 1], res[3 * kept + 2]});
+        }
     }
     // records too long for the device: the bin is read once more, the pairs of a bin run side by side
     for (size_t a = 0; a < on_host.size();) {
@@ -1013,7 +1053,41 @@ void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std:
                 o[0] = r.distance, o[1] = r.record, o[2] = r.end;
             }
         }
-        for (size_t k = a; k < b; ++k) settle(on_host[k], out.data() + 3 * strands * (k - a), bins_.at(bin).names);
+        for (size_t k = a; k < b; ++k) {
+            const uint32_t* res = out.data() + 3 * strands * (k - a);
+            const size_t kept = settle(on_host[k], res, bins_.at(bin).names);
+            if (!align_ || kept == strands) continue;
+            align_on_host({on_host[k], kept, res[3 * kept], res[3 * kept + 1], res[3 * kept + 2]}, text, rec);
+            ++n_align_host_;
+        }
+        a = b;
+    }
+    // alignments the device did not make: a bin's letters are read once more, its pairs run side by side
+    std::stable_sort(pending.begin(), pending.end(), [&](const Pending& x, const Pending& y) { return candidates[x.candidate].bin < candidates[y.candidate].bin; });
+    for (size_t a = 0; a < pending.size();) {
+        size_t b = a;
+        const uint32_t bin = candidates[pending[a].candidate].bin;
+        while (b < pending.size() && candidates[pending[b].candidate].bin == bin) ++b;
+        std::string text;
+        std::vector<uint64_t> rec;
+        std::vector<std::string> names;
+        bins_.read(bin, text, rec, names);
+        std::exception_ptr failed;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic)
+#endif
+        for (size_t k = a; k < b; ++k) {
+            try {
+                align_on_host(pending[k], text, rec);
+            } catch (...) {
+#ifdef _OPENMP
+#pragma omp critical(tetrex_align_failed)
+#endif
+                failed = std::current_exception();
+            }
+        }
+        if (failed) std::rethrow_exception(failed);
+        n_align_host_ += b - a;
         a = b;
     }
 }

@@ -68,6 +68,10 @@ struct VerifiedHit {
     uint32_t end = 0;                 // 1-based position of the match's last letter in the target, 0 for an empty match
     char strand = '+';                // '-': the reverse complement matched better (on equal distance + wins)
     const std::string* target = nullptr;  // the target record's name (valid as long as the verifier)
+    // with BinVerifier::set_align (include/txq.h at txq_edit_align_device): the letters of the target in front of the match, and
+    // the alignment's runs as (length << 2) | op, op 0 '=', 1 'X', 2 'I', 3 'D', from the pattern's first letter to its last
+    uint32_t start = 0;
+    std::vector<uint32_t> runs;
 };
 class BinVerifier;
 
@@ -181,7 +185,12 @@ class ResidentBins {
 // TXQ_EDIT_LONG_MAX_PATTERN to txq_edit_search_long_device (TETREX_VERIFY_LONG=0: to the host, as before that kernel
 // existed), one call per candidate bin each, all queued before the one copy back.  Longer records and empty ones are
 // answered on the host (host/edit_distance.hpp), with OpenMP over the pairs.  n_routed() counts the candidate pairs each of
-// the three routes answered.  Needs txq_init (DeviceIndex::upload).
+// the three routes answered.
+// set_align (`--align`): every confirmed pair also gets the start and the runs of its alignment.  Behind each
+// search call txq_edit_align_device is queued on the same stream, reading the triples where the search call left them, and its
+// answers come back in the verifier's one copy; a pair the device declines (more than TXQ_EDIT_ALIGN_MAX_DISTANCE edits), a pair
+// of the host route, and with TETREX_VERIFY_ALIGN=host every pair, is aligned by edit_align of host/edit_distance.hpp on the
+// bin's letters read once more.  n_aligned() counts the pairs each of the two routes aligned.  Needs txq_init (DeviceIndex::upload).
 class BinVerifier {
   public:
     BinVerifier(const std::vector<std::string>& bin_paths, bool dna, uint32_t errors);
@@ -209,6 +218,9 @@ class BinVerifier {
     size_t n_confirmed() const { return n_confirmed_; }
     struct Routed { size_t device, device_long, host; };
     Routed n_routed() const { return {n_device_, n_device_long_, n_host_}; }
+    void set_align(bool on) { align_ = on; }
+    struct Aligned { size_t device, host; };
+    Aligned n_aligned() const { return {n_align_device_, n_align_host_}; }
 
   private:
     // what both entries share: candidate i compares `strands` consecutive patterns from pattern_of[i] (lengths[i] letters each)
@@ -222,6 +234,8 @@ class BinVerifier {
     uint8_t codes_[256];
     void* d_codes_ = nullptr;
     size_t n_candidates_ = 0, n_confirmed_ = 0, n_device_ = 0, n_device_long_ = 0, n_host_ = 0;
+    bool align_ = false;
+    size_t n_align_device_ = 0, n_align_host_ = 0;
 };
 
 // `tetrex query --gpu-verify`: which records of its candidate bins does a motif match at all?  Answered on the

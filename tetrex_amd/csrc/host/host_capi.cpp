@@ -445,9 +445,10 @@ const void* txh_index_serialise(txh_index* ix, size_t* bytes) {
 
 void txh_index_free(txh_index* ix) { delete ix; }
 
-int txh_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
-                    size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
-                    const uint8_t* codes, unsigned threads, uint32_t* out) {
+// what txh_edit_search and txh_edit_align check of their buffers before they compute (`out`: the array the call writes)
+static int check_edit_buffers(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                              size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
+                              const uint8_t* codes, const uint32_t* out) {
     if (!pat_offsets || !rec_offsets || !group_offsets || !codes || (n_pairs && (!pairs || !out))) return fail("null argument");
     for (size_t p = 0; p < n_patterns; ++p)
         if (pat_offsets[p + 1] < pat_offsets[p]) return fail("pattern offsets are not ascending");
@@ -462,6 +463,13 @@ int txh_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t
         if (p >= n_patterns || g >= n_groups) return fail("pair " + std::to_string(i) + " names a pattern or group out of range");
         if (pat_offsets[p + 1] == pat_offsets[p]) return fail("pattern " + std::to_string(p) + " is empty");
     }
+    return 0;
+}
+
+int txh_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                    size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
+                    const uint8_t* codes, unsigned threads, uint32_t* out) {
+    if (int rc = check_edit_buffers(patterns, pat_offsets, n_patterns, text, rec_offsets, n_records, group_offsets, n_groups, pairs, n_pairs, codes, out)) return rc;
     std::atomic<size_t> next{0};
     const auto work = [&]() {
         constexpr size_t kGrain = 16;
@@ -473,6 +481,33 @@ int txh_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t
                 out[3 * i] = r.distance;
                 out[3 * i + 1] = r.record;
                 out[3 * i + 2] = r.end;
+            }
+    };
+    try {
+        const size_t n_threads = std::max<size_t>(1, std::min<size_t>(threads ? threads : 1, (n_pairs + 15) / 16));
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < n_threads; ++t) pool.emplace_back(work);
+        work();
+        for (std::thread& t : pool) t.join();
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+
+int txh_edit_align(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                   size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs, const uint32_t* results,
+                   const uint8_t* codes, uint32_t max_errors, unsigned threads, uint32_t* align) {
+    if (!results && n_pairs) return fail("null argument");
+    if (max_errors > (1u << 24)) return fail("max_errors is at most 2^24");
+    if (int rc = check_edit_buffers(patterns, pat_offsets, n_patterns, text, rec_offsets, n_records, group_offsets, n_groups, pairs, n_pairs, codes, align)) return rc;
+    const size_t stride = 2 * (size_t)max_errors + 3;
+    std::atomic<size_t> next{0};
+    const auto work = [&]() {
+        constexpr size_t kGrain = 16;
+        for (size_t i0; (i0 = next.fetch_add(kGrain)) < n_pairs;)
+            for (size_t i = i0; i < std::min(i0 + kGrain, n_pairs); ++i) {
+                const uint32_t p = pairs[3 * i], g = pairs[3 * i + 1];
+                edit_align_pair(patterns + pat_offsets[p], (size_t)(pat_offsets[p + 1] - pat_offsets[p]), text, rec_offsets, group_offsets[g],
+                                group_offsets[g + 1], results + 3 * i, codes, max_errors, align + i * stride);
             }
     };
     try {

@@ -4,11 +4,12 @@
 //      the candidate bins that hold a match at all are found on the device, the matcher runs on those only — same rows)
 //   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] [--layout uniform|sized [--tmax N] [--rearrange [--rearrange-ratio R]]] <name> <libs...>
 //     (include/arg_parse.h:10-38, src/index_base.cpp:73-117)
-//   tetrex search [-e E [--verify] | --threshold F] [--counts] [--translate [--verify-frames]] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//   tetrex search [-e E [--verify [--align]] | --threshold F] [--counts] [--translate [--verify-frames [--align]]] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (not in the reference: every FASTA record a query, answered by seqan::hibf membership_for(values, threshold);
 //      --translate: nucleotide records on a peptide index, every record's six frames a query of their own;
 //      --verify: only the bins that hold the record within E edits, confirmed on the bins' own letters;
-//      --verify-frames, with --translate -e E: only the bins that hold the frame's residues within E edits, confirmed likewise)
+//      --verify-frames, with --translate -e E: only the bins that hold the frame's residues within E edits, confirmed likewise;
+//      --align, with either: where each confirmed match begins in its target, and its alignment as a CIGAR string)
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
 #include "device_index.hpp"
@@ -432,6 +433,17 @@ int cmd_track(int argc, char** argv) {
     return 0;
 }
 
+// --align: the two columns behind a confirmed row, \t start \t cigar — start 1-based (end + 1 for a match that takes
+// no target letter), the cigar like 12=1X30=2I7= ('I': a query letter with no target letter, 'D': a target letter skipped)
+void append_alignment(std::string& row, const VerifiedHit& h) {
+    row.append("\t").append(std::to_string((uint64_t)h.start + 1)).append("\t");
+    for (const uint32_t run : h.runs) row.append(std::to_string(run >> 2)).append(1, "=XID"[run & 3]);
+}
+void trace_align_routes(const BinVerifier& verifier) {
+    const BinVerifier::Aligned n = verifier.n_aligned();
+    std::cerr << "[tetrex search] align routes: device " << n.device << ", host " << n.host << std::endl;
+}
+
 // tetrex search --translate: nucleotide records on a peptide index.  Every record is translated in its six
 // frames on the device; frame f of a record is a query of its own with n_f values (the k-mers of the frame without a stop)
 // and the plain rules with n = n_f: -e E gives t = max(n_f - k E, 0), --threshold F gives t = ceil(F n_f).  A frame with
@@ -439,7 +451,7 @@ int cmd_track(int argc, char** argv) {
 // none of whose frames is searched gets a note.  Rows: name \t bin path \t frame [\t count/n_f], by record, frame
 // (+1 +2 +3 -1 -2 -3) and bin.  -e E --verify-frames: the rows are candidates; each is confirmed by the edit
 // distance of the frame's residue letters to the bin's records (BinVerifier, the frames translated on the device) and only
-// those within E edits are written, with distance \t target \t end appended.
+// those within E edits are written, with distance \t target \t end appended; --align appends \t start \t cigar (append_alignment).
 int search_translated(const Args& a, const IndexImage& image, unsigned long long errors, double fraction) {
     const bool verbose = a.has("verbose"), with_counts = a.has("counts"), by_fraction = a.has("threshold");
     const std::string dest = a.get("output", "-");
@@ -468,6 +480,8 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
     const bool verify = a.has("verify-frames");
     std::unique_ptr<BinVerifier> verifier;
     if (verify) verifier = std::make_unique<BinVerifier>(image.bin_paths, false, (uint32_t)std::min<unsigned long long>(errors, 0xFFFFFFFEull));
+    const bool align = verify && a.has("align");
+    if (align) verifier->set_align(true);
     std::vector<BinVerifier::Hit> confirmed;
     auto flush = [&]() {
         if (names.empty()) return;
@@ -486,6 +500,7 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
                 if (verify)
                     row.append("\t").append(std::to_string(confirmed[h].distance)).append("\t").append(*confirmed[h].target).append("\t")
                         .append(std::to_string(confirmed[h].end));
+                if (align) append_alignment(row, confirmed[h]);
                 out << row << '\n';
             }
         }
@@ -505,6 +520,7 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
     if (verify && std::getenv("TETREX_TRACE")) {
         const BinVerifier::Routed n = verifier->n_routed();
         std::cerr << "[tetrex search] verify routes: device " << n.device << ", device-long " << n.device_long << ", host " << n.host << std::endl;
+        if (align) trace_align_routes(*verifier);
     }
     if (verbose) std::cerr << "Search time: " << (now() - t_start) << " s" << std::endl;
     return 0;
@@ -516,10 +532,12 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
 // so that bin is always reported.  --threshold F (0 < F <= 1): t = ceil(F n).  Rows: name \t bin path [\t count/n].
 // -e E --verify: the reported bins are candidates; each is confirmed by the edit distance of the record to the
 // bin's records (BinVerifier) and only the bins within E edits are written, with distance \t target \t end [\t strand] appended.
+// --align (with --verify or --verify-frames) appends \t start \t cigar to each of those rows; on strand - the cigar is
+// that of the reverse-complemented record against the target, in the target's coordinates.
 int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
                                        {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false},
-                                       {'\0', "verify-frames", false}};
+                                       {'\0', "verify-frames", false}, {'\0', "align", false}};
     Args a;
     unsigned long long errors = 0;
     double fraction = 0;
@@ -532,6 +550,8 @@ int cmd_search(int argc, char** argv) {
             if (a.has("threshold")) throw std::runtime_error("--verify-frames confirms the bins of -e E: it cannot be combined with --threshold");
             if (!a.has("errors")) throw std::runtime_error("--verify-frames needs -e E: the number of residue edits a confirmed frame may be away");
         }
+        if (a.has("align") && !a.has("verify") && !a.has("verify-frames"))
+            throw std::runtime_error("--align gives the alignment of confirmed rows: it needs --verify, or --translate --verify-frames");
         if (a.has("verify") && a.has("threshold")) throw std::runtime_error("--verify confirms the bins of -e E: it cannot be combined with --threshold");
         if (a.has("verify") && a.has("translate")) throw std::runtime_error("--verify cannot be combined with --translate (translated rows are confirmed with --verify-frames)");
         if (a.has("verify") && !a.has("errors")) throw std::runtime_error("--verify needs -e E: the number of edits a confirmed bin may be away");
@@ -591,6 +611,8 @@ int cmd_search(int argc, char** argv) {
     const bool verify = a.has("verify"), dna = enc.molecule() == Molecule::DNA;
     std::unique_ptr<BinVerifier> verifier;
     if (verify) verifier = std::make_unique<BinVerifier>(image.bin_paths, dna, (uint32_t)std::min<unsigned long long>(errors, 0xFFFFFFFEull));
+    const bool align = verify && a.has("align");
+    if (align) verifier->set_align(true);
     std::vector<std::string> seqs;  // --verify: the batch's records themselves
     std::vector<BinVerifier::Candidate> candidates;
     std::vector<BinVerifier::Hit> confirmed;
@@ -610,6 +632,7 @@ int cmd_search(int argc, char** argv) {
                 if (with_counts) row.append("\t").append(std::to_string(counts[q * W * 64 + u])).append("/").append(std::to_string(n_of[q]));
                 row.append("\t").append(std::to_string(h.distance)).append("\t").append(*h.target).append("\t").append(std::to_string(h.end));
                 if (dna) row.append("\t").append(1, h.strand);
+                if (align) append_alignment(row, h);
                 out << row << '\n';
             }
             seqs.clear();
@@ -655,6 +678,7 @@ int cmd_search(int argc, char** argv) {
     if (verify && std::getenv("TETREX_TRACE")) {
         const BinVerifier::Routed n = verifier->n_routed();
         std::cerr << "[tetrex search] verify routes: device " << n.device << ", device-long " << n.device_long << ", host " << n.host << std::endl;
+        if (align) trace_align_routes(*verifier);
     }
     if (verbose) std::cerr << "Search time: " << (now() - t_start) << " s" << std::endl;
     return 0;

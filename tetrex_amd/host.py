@@ -405,6 +405,48 @@ def edit_search(patterns, records, groups, pairs, codes, threads=1):
     return out
 
 
+EDIT_ALIGN_OPS = "=XID"
+
+
+def decode_alignments(words, max_errors):
+    """The answers of edit_align in the layout of include/txq.h (2 max_errors + 3 uint32 a pair) as (start uint32[n], list of
+    [(op, length), ...]) with op one of "=XID"; a pair whose start is 0xFFFFFFFF or 0xFFFFFFFE has no runs."""
+    words = np.asarray(words, dtype=np.uint32).reshape(-1, 2 * int(max_errors) + 3)
+    runs = []
+    for row in words:
+        n = int(row[1]) if int(row[0]) < 0xFFFFFFFE else 0
+        runs.append([(EDIT_ALIGN_OPS[int(w) & 3], int(w) >> 2) for w in row[2:2 + n]])
+    return words[:, 0].copy(), runs
+
+
+def edit_align(patterns, records, groups, pairs, results, codes, max_errors, threads=1, raw=False):
+    """txh_edit_align: start and alignment of the pairs a search confirmed, on the host (include/txh.h; the semantics are in
+    include/txq.h at txq_edit_align_device).  The arguments of edit_search, then results, the (n, 3) array a search returned, and
+    max_errors, which sizes the answers.  Returns (start uint32[n], list of [(op, length), ...]); raw=True: the (n, 2 max_errors
+    + 3) uint32 words instead (a pair that is not aligned keeps the 0xA5A5A5A5 fill behind its marker)."""
+    L = lib()
+    L.txh_edit_align.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                 C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p]
+    pat, po = patterns if isinstance(patterns, tuple) else _byte_records(patterns)
+    txt, ro = records if isinstance(records, tuple) else _byte_records(records)
+    pat, txt = np.ascontiguousarray(pat, dtype=np.uint8), np.ascontiguousarray(txt, dtype=np.uint8)
+    po, ro = np.ascontiguousarray(po, dtype=np.uint64), np.ascontiguousarray(ro, dtype=np.uint64)
+    go = np.ascontiguousarray(groups, dtype=np.uint64)
+    pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 3)
+    res = np.ascontiguousarray(results, dtype=np.uint32).reshape(-1, 3)
+    cd = np.ascontiguousarray(codes, dtype=np.uint8)
+    if (cd.size != 256 or po.size < 1 or ro.size < 1 or go.size < 1 or int(po[-1]) > pat.size or int(ro[-1]) > txt.size
+            or res.shape != pr.shape or not 0 <= int(max_errors) <= 1 << 24):
+        raise HostError("edit_align: offsets, bytes, results and class table disagree")
+    out = np.full((pr.shape[0], 2 * int(max_errors) + 3), 0xA5A5A5A5, dtype=np.uint32)
+    rc = L.txh_edit_align(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
+                          go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], res.ctypes.data, cd.ctypes.data, int(max_errors),
+                          threads, out.ctypes.data)
+    if rc < 0:
+        raise _err()
+    return out if raw else decode_alignments(out, max_errors)
+
+
 def _byte_records(records):
     recs = [r.encode() if isinstance(r, str) else bytes(r) for r in records]
     offsets = np.zeros(len(recs) + 1, dtype=np.uint64)
