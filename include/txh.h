@@ -170,6 +170,16 @@ int txh_peptide_codes(unsigned reduction, uint8_t out[256]);
 int txh_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
                     size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
                     const uint8_t* codes, unsigned threads, uint32_t* out);
+/* Every record of a group that a pattern matches within its cap, on the host (host/edit_distance.hpp): the semantics of
+ * txq_edit_targets_device (include/txq.h: a hit is (pair, d, r, j) for every record r of the pair's group with d <= e, empty
+ * records included, listed by pair, then by record) with NO limit on the pattern length.  The CPU twin of those kernels:
+ * `tetrex search --verify --all-targets` answers patterns longer than TXQ_EDIT_LONG_MAX_PATTERN with it and the kernels are
+ * compared with it.  hits: room for `capacity` quadruples of u32; *total receives the number of hits whatever the capacity
+ * and the first `capacity` of them are written.  Buffers, threads, checks and the return value as txh_edit_search: a pair
+ * out of range or an empty pattern is an error, so there are no status words. */
+int txh_edit_targets(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                     size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
+                     const uint8_t* codes, unsigned threads, uint32_t* hits, size_t capacity, uint64_t* total);
 /* Start and alignment of confirmed pairs on the host (host/edit_distance.hpp): the semantics and the layout of
  * txq_edit_align_device (include/txq.h: the walk back by three rules, 2 max_errors + 3 u32 words a pair — start, n_runs, runs as
  * (length << 2) | op —, "none" and the refusal marker passed on) with NO limit on the pattern length or the distance.  The CPU

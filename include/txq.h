@@ -301,6 +301,53 @@ int txq_edit_search_long(const uint8_t* patterns, const uint64_t* pat_offsets, s
                          size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
                          const uint8_t* codes, uint32_t* out);  /* host buffers, synchronous */
 
+/* Every record of a group that a pattern matches within its cap (`tetrex search --verify --all-targets`; not in
+ * the reference).  Classes, Sellers' D, patterns, records, groups, pairs (pattern, group, cap e) and the refusal rules are
+ * those of txq_edit_search above, word for word.  A HIT of pair i is a record r of its group, empty ones included, with
+ * d(P, r) = min_j D[m][j] <= e: the quadruple (i, d, r, j), j the lowest end position in r that reaches d, 0 for an empty
+ * match — so m <= e makes every record of the group a hit of distance at most m, and an empty record the hit (m, r, 0).
+ * The hits are listed by pair, then by record index; no atomic append, the order does not depend on scheduling (the rule of
+ * txq_hit_list_device below).  The least (d, r, j) of a pair's hits, d first, then r, is exactly what txq_edit_search* answers
+ * for the pair, and a pair of no hit is the pair that gets "none" there.
+ * In place of d_out the calls take
+ *   d_hits, capacity   room for `capacity` quadruples of u32 (pair, d, r, j);
+ *   d_total            one u64: the number of hits whatever the capacity.  At most `capacity` are written, the first ones in
+ *                      order; the caller retries with a larger list;
+ *   d_status           one u32 per pair: 0 where the pair was answered, 0xFFFFFFFE where it was refused — an index or an
+ *                      offset outside its array, m = 0 or above the limit, or slots that do not fit (next).  A refused pair
+ *                      contributes no hit;
+ *   n_slots            a slot is one 64-bit key per (pair, record of its group) and lives in the workspace.  The pairs'
+ *                      slots lie one behind the other in pair order; a pair whose slots would end beyond n_slots is refused
+ *                      — and so is every pair behind it, one whose group has no records included: its (empty) slots
+ *                      lie beyond n_slots as well.  The caller knows the sum over its pairs of the
+ *                      records of their groups from the group offsets it already has;
+ *   d_workspace        TXQ_EDIT_TARGETS_WORKSPACE(n_pairs, n_slots) bytes of device memory, 8-byte aligned.
+ * txq_edit_targets_device takes patterns of 1 .. TXQ_EDIT_MAX_PATTERN bytes, txq_edit_targets_long_device of 1 ..
+ * TXQ_EDIT_LONG_MAX_PATTERN (longer ones: txh_edit_targets of include/txh.h, the same semantics on the host).  The promises of
+ * the sibling _device calls hold: nothing allocated, nothing read back, nothing waited for, and no load or store outside a
+ * buffer whatever offsets and pairs say; TXQ_ERR_ARG only for what the call can see (null pointers, the size limits: those of
+ * txq_edit_search_device, and at most 2^38 slots and rows).  txq_edit_targets and txq_edit_targets_long are the synchronous
+ * twins on host buffers; they check them first as txq_edit_search does (TXQ_ERR_ARG, nothing launched) and copy back the
+ * total, the status words and the rows written.  TXQ_EDIT_CHUNK and TXQ_EDIT_LONG_SPAN cut the text as they do for the search
+ * calls; the results do not depend on them. */
+#define TXQ_EDIT_TARGETS_WORKSPACE(n_pairs, n_slots) (8 * (2 * (size_t)(n_pairs) + (size_t)(n_slots) + (size_t)(n_slots) / 256 + 4))
+int txq_edit_targets_device(const uint8_t* d_patterns, const uint64_t* d_pat_offsets, size_t n_patterns, size_t pattern_bytes,
+                            const uint8_t* d_text, const uint64_t* d_rec_offsets, size_t n_records, size_t text_bytes,
+                            const uint64_t* d_group_offsets, size_t n_groups, const uint32_t* d_pairs, size_t n_pairs,
+                            const uint8_t* d_codes, uint32_t* d_hits, size_t capacity, uint64_t* d_total, uint32_t* d_status, size_t n_slots,
+                            void* d_workspace, void* stream);
+int txq_edit_targets_long_device(const uint8_t* d_patterns, const uint64_t* d_pat_offsets, size_t n_patterns, size_t pattern_bytes,
+                                 const uint8_t* d_text, const uint64_t* d_rec_offsets, size_t n_records, size_t text_bytes,
+                                 const uint64_t* d_group_offsets, size_t n_groups, const uint32_t* d_pairs, size_t n_pairs,
+                                 const uint8_t* d_codes, uint32_t* d_hits, size_t capacity, uint64_t* d_total, uint32_t* d_status, size_t n_slots,
+                                 void* d_workspace, void* stream);
+int txq_edit_targets(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                     size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs, const uint8_t* codes,
+                     uint32_t* hits, size_t capacity, uint64_t* total, uint32_t* status, size_t n_slots);  /* host buffers, synchronous */
+int txq_edit_targets_long(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                          size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs, const uint8_t* codes,
+                          uint32_t* hits, size_t capacity, uint64_t* total, uint32_t* status, size_t n_slots);  /* host buffers, synchronous */
+
 /* Where a confirmed match begins, and its alignment (`tetrex search --verify --align`; not in the reference).
  * Take a pair (pattern P of m bytes, group, cap) of txq_edit_search* above, its result (d, r, j) with d != 0xFFFFFFFF, R = record
  * r, the class table and Sellers' D as defined there (D[0][.] = 0, D[.][0] = i).  The alignment of the pair is the path found

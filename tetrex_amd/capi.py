@@ -25,6 +25,7 @@ SYMBOLS = [
     "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_translate_frames_bound", "txq_translate_frames_device", "txq_translate_frames",
     "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
     "txq_edit_search_long", "txq_edit_search_long_device", "txq_edit_align", "txq_edit_align_device",
+    "txq_edit_targets", "txq_edit_targets_device", "txq_edit_targets_long", "txq_edit_targets_long_device",
     "txq_regex_filter", "txq_regex_filter_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
@@ -101,6 +102,13 @@ def lib():
                                             C.c_void_p]
         L.txq_edit_align.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.txq_edit_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_void_p, C.c_void_p]
+        L.txq_edit_targets.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, u64p, C.c_void_p, C.c_size_t]
+        L.txq_edit_targets_long_device.argtypes = L.txq_edit_targets_device.argtypes
+        L.txq_edit_targets_long.argtypes = L.txq_edit_targets.argtypes
         L.txq_regex_filter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
@@ -642,6 +650,79 @@ def edit_search_long(patterns, records, groups, pairs, codes):
     check(lib().txq_edit_search_long(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
                                      go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], cd.ctypes.data, out.ctypes.data))
     return out
+
+
+EDIT_TARGETS_REFUSED = 0xFFFFFFFE  # status of a pair txq_edit_targets* did not answer
+
+
+def edit_targets_workspace(n_pairs, n_slots):
+    """TXQ_EDIT_TARGETS_WORKSPACE: the device workspace txq_edit_targets*_device needs for n_pairs pairs and n_slots slots"""
+    return 8 * (2 * int(n_pairs) + int(n_slots) + int(n_slots) // 256 + 4)
+
+
+def edit_targets_slots(groups, pairs):
+    """the slots a call needs: the sum over the pairs of the records of their groups (pairs that name no group count nothing)"""
+    go = np.asarray(groups, dtype=np.uint64).astype(np.int64)
+    g = np.asarray(pairs, dtype=np.int64).reshape(-1, 3)[:, 1]
+    g = g[(g >= 0) & (g < go.size - 1)]
+    return int((go[g + 1] - go[g]).sum())
+
+
+def _edit_targets(fn, patterns, records, groups, pairs, codes, capacity, n_slots):
+    pat, po, txt, ro, go, pr, cd = edit_arrays(patterns, records, groups, pairs, codes)
+    n_slots = edit_targets_slots(go, pr) if n_slots is None else int(n_slots)
+    room = 1024 if capacity is None else int(capacity)
+    while True:
+        hits, total, status = np.zeros((room, 4), dtype=np.uint32), np.zeros(1, dtype=np.uint64), np.zeros(pr.shape[0], dtype=np.uint32)
+        check(fn(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
+                 go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], cd.ctypes.data, hits.ctypes.data, room,
+                 total.ctypes.data_as(u64p), status.ctypes.data, n_slots))
+        if capacity is not None or int(total[0]) <= room:
+            return hits[:min(int(total[0]), room)].copy(), int(total[0]), status
+        room = int(total[0])
+
+
+def edit_targets(patterns, records, groups, pairs, codes, capacity=None, n_slots=None):
+    """Every record of a pair's group within the cap, on the GPU (txq_edit_targets, include/txq.h).  The arguments of
+    edit_search.  Returns (hits, total, status): hits an (n, 4) uint32 array of (pair, distance, record, end) by pair, then by
+    record; total the number of hits; status one uint32 per pair, 0 or EDIT_TARGETS_REFUSED.  Without a capacity the call is
+    repeated until every hit fits; with one, only the first `capacity` rows are returned.  n_slots: the slots the call is given
+    (default: what the pairs need)."""
+    return _edit_targets(lib().txq_edit_targets, patterns, records, groups, pairs, codes, capacity, n_slots)
+
+
+def edit_targets_long(patterns, records, groups, pairs, codes, capacity=None, n_slots=None):
+    """edit_targets for patterns of up to EDIT_LONG_MAX_PATTERN bytes (txq_edit_targets_long, include/txq.h): the same
+    arguments, the same results"""
+    return _edit_targets(lib().txq_edit_targets_long, patterns, records, groups, pairs, codes, capacity, n_slots)
+
+
+def edit_targets_device(patterns, records, groups, pairs, codes, capacity, n_slots=None, long=False, guard=64, fill=0xA5, stream=None):
+    """txq_edit_targets_device (long: txq_edit_targets_long_device) on device buffers that hold the arrays as they are (16
+    bytes of zeros behind each) — the call cannot read them before it launches, so pairs that name what is not there are the
+    kernels' to refuse —, the rows between
+    `guard` bytes of `fill` on either side and the workspace filled with `fill`.  Returns (buffer uint8[guard + 16 capacity +
+    guard], total, status uint32[n]): the rows begin at buffer[guard], and what the call did not write still holds `fill`."""
+    pat, po, txt, ro, go, pr, cd = edit_arrays(patterns, records, groups, pairs, codes)
+    n, capacity = pr.shape[0], int(capacity)
+    n_slots = edit_targets_slots(go, pr) if n_slots is None else int(n_slots)
+    pad = lambda a: np.concatenate([a.view(np.uint8).ravel(), np.zeros(16, dtype=np.uint8)])  # (no buffer of no bytes)
+    bufs = [DeviceBuffer.from_numpy(pad(x)) for x in (pat, po, txt, ro, go, pr, cd)]
+    d_hits = DeviceBuffer.from_numpy(np.full(guard + 16 * capacity + guard, fill, dtype=np.uint8))
+    d_total, d_status = DeviceBuffer.from_numpy(np.full(8, fill, dtype=np.uint8)), DeviceBuffer.from_numpy(np.full(4 * n + 4, fill, dtype=np.uint8))
+    d_work = DeviceBuffer.from_numpy(np.full(edit_targets_workspace(n, n_slots), fill, dtype=np.uint8))
+    try:
+        assert guard % 4 == 0
+        L = lib()
+        check((L.txq_edit_targets_long_device if long else L.txq_edit_targets_device)(
+            bufs[0].ptr, bufs[1].ptr, po.size - 1, pat.size, bufs[2].ptr, bufs[3].ptr, ro.size - 1, txt.size, bufs[4].ptr, go.size - 1, bufs[5].ptr, n,
+            bufs[6].ptr, d_hits.ptr + guard, capacity, d_total.ptr, d_status.ptr, n_slots, d_work.ptr, stream))
+        synchronize()
+        return (d_hits.to_numpy(np.uint8, (guard + 16 * capacity + guard,)), int(d_total.to_numpy(np.uint64, (1,))[0]),
+                d_status.to_numpy(np.uint32, (n,)))
+    finally:
+        for b in bufs + [d_hits, d_total, d_status, d_work]:
+            b.free()
 
 
 EDIT_ALIGN_MAX_DISTANCE = 31

@@ -15,6 +15,7 @@
 #include <future>
 #include <memory>
 #include <numeric>
+#include <tuple>
 #include <stdexcept>
 
 namespace tetrex {
@@ -664,10 +665,12 @@ struct GrowBuf {
 void DeviceIndex::search_translated(std::string_view seq, const std::vector<uint64_t>& rec_offsets,
                                     const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& n_of,
                                     std::vector<uint64_t>& thresholds, std::vector<TranslatedHit>& hits, BinVerifier* verifier,
-                                    std::vector<VerifiedHit>* confirmed) {
+                                    std::vector<VerifiedHit>* confirmed, std::vector<std::vector<VerifiedHit>>* all_targets) {
     if (!ix_) throw std::runtime_error("index not uploaded");
     if (verifier && !confirmed) throw std::runtime_error("search_translated: a verifier needs somewhere to put its answers");
     if (confirmed) confirmed->clear();
+    if (all_targets) all_targets->clear();
+    std::vector<std::vector<VerifiedHit>> batch_targets;
     if (shards_.size() > 1) throw std::runtime_error("search_translated: one shard only");
     if (enc_.molecule() != Molecule::Peptide) throw std::runtime_error("search_translated: a peptide index is needed");
     if (rec_offsets.empty() || rec_offsets.back() > seq.size()) throw std::runtime_error("search_translated: record offsets run past the bytes");
@@ -756,7 +759,7 @@ void DeviceIndex::search_translated(std::string_view seq, const std::vector<uint
             frame_strings.assign(nq, std::string());
             for (const BinVerifier::Candidate& c : candidates)
                 if (frame_strings[c.query].empty()) frame_strings[c.query] = frame_letters(c.query);
-            verifier->verify(frame_strings, candidates, batch_confirmed);
+            verifier->verify(frame_strings, candidates, batch_confirmed, all_targets ? &batch_targets : nullptr);
         } else {
             const uint64_t frames_bytes = txq_translate_frames_bound(rebased.data(), nr);
             if (frames_bytes == UINT64_MAX) txq_check(TXQ_ERR_ARG, "txq_translate_frames_bound");
@@ -771,9 +774,10 @@ void DeviceIndex::search_translated(std::string_view seq, const std::vector<uint
                 lengths[i] = L >= o ? (L - o) / 3 : 0;
             }
             verifier->verify(BinVerifier::DevicePatterns{(const uint8_t*)d_frames.p, (const uint64_t*)d_foff.p, nq, frames_bytes}, candidates, lengths,
-                             frame_letters, batch_confirmed);
+                             frame_letters, batch_confirmed, all_targets ? &batch_targets : nullptr);
         }
         confirmed->insert(confirmed->end(), batch_confirmed.begin(), batch_confirmed.end());
+        if (all_targets) all_targets->insert(all_targets->end(), std::make_move_iterator(batch_targets.begin()), std::make_move_iterator(batch_targets.end()));
     }
 }
 
@@ -827,7 +831,8 @@ ResidentBins::Bin& ResidentBins::resident(uint32_t bin, const std::string& text,
     Bin& b = bins_[bin];
     b.last_use = ++clock_;
     if (b.d_rec) return b;
-    b.names = std::move(names);
+    // (a bin that left the device and comes back keeps the names it has: they are the same, and confirmed rows point into them)
+    if (b.names.empty()) b.names = std::move(names);
     const uint64_t n = rec.size() - 1;
     rec.push_back(0);  // behind the record offsets: the one group's offsets {0, n}
     rec.push_back(n);
@@ -873,8 +878,10 @@ size_t BinVerifier::device_max() {
     return long_env && long_env[0] == '0' && !long_env[1] ? TXQ_EDIT_MAX_PATTERN : TXQ_EDIT_LONG_MAX_PATTERN;
 }
 
-void BinVerifier::verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits) {
+void BinVerifier::verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits,
+                         std::vector<std::vector<Hit>>* rows) {
     hits.assign(candidates.size(), Hit{});
+    if (rows) rows->assign(candidates.size(), {});
     if (candidates.empty()) return;
     const size_t strands = dna_ ? 2 : 1;
     // the patterns: every record that is a candidate somewhere, and on a nucleotide index its reverse complement behind it
@@ -916,20 +923,23 @@ void BinVerifier::verify(const std::vector<std::string>& queries, const std::vec
         txq_check(txq_memcpy_h2d(d_po.p, pat_off.data(), pat_off.size() * 8), "h2d");
     }
     run(DevicePatterns{(const uint8_t*)d_pat.p, (const uint64_t*)d_po.p, pat_off.size() - 1, pat.size()}, strands, candidates, of_candidate, lengths,
-        [&](size_t i, size_t strand) { return strand ? reverse_complement(queries[candidates[i].query]) : queries[candidates[i].query]; }, hits);
+        [&](size_t i, size_t strand) { return strand ? reverse_complement(queries[candidates[i].query]) : queries[candidates[i].query]; }, hits, rows);
 }
 
 void BinVerifier::verify(const DevicePatterns& patterns, const std::vector<Candidate>& candidates, const std::vector<uint64_t>& lengths,
-                         const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits) {
+                         const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows) {
     hits.assign(candidates.size(), Hit{});
+    if (rows) rows->assign(candidates.size(), {});
     if (candidates.empty()) return;
     std::vector<uint32_t> of_candidate(candidates.size());
     for (size_t i = 0; i < candidates.size(); ++i) of_candidate[i] = candidates[i].query;
-    run(patterns, 1, candidates, of_candidate, lengths, [&](size_t i, size_t) { return letters(candidates[i].query); }, hits);
+    run(patterns, 1, candidates, of_candidate, lengths, [&](size_t i, size_t) { return letters(candidates[i].query); }, hits, rows);
 }
 
 void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
-                      const std::vector<uint64_t>& lengths, const std::function<std::string(size_t, size_t)>& letters, std::vector<Hit>& hits) {
+                      const std::vector<uint64_t>& lengths, const std::function<std::string(size_t, size_t)>& letters, std::vector<Hit>& hits,
+                      std::vector<std::vector<Hit>>* rows) {
+    if (rows) return run_targets(patterns, strands, candidates, pattern_of, lengths, letters, *rows);
     n_candidates_ += candidates.size();
     std::vector<size_t> order(candidates.size()), on_host;
     std::iota(order.begin(), order.end(), (size_t)0);
@@ -1087,6 +1097,268 @@ void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std:
             }
         }
         if (failed) std::rethrow_exception(failed);
+        n_align_host_ += b - a;
+        a = b;
+    }
+}
+
+// ---- tetrex search --verify --all-targets ------------------------------------------------------------------------------
+
+namespace {
+// slots of one txq_edit_targets*_device call (TETREX_VERIFY_TARGET_SLOTS, default 2^20: 8 MiB of keys and 16 MiB of rows)
+uint64_t target_slot_budget() {
+    const char* e = std::getenv("TETREX_VERIFY_TARGET_SLOTS");
+    const long long v = e && *e ? std::atoll(e) : 1ll << 20;
+    return (uint64_t)std::max<long long>(1, std::min<long long>(v, 1ll << 32));
+}
+}  // namespace
+
+void BinVerifier::run_targets(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
+                              const std::vector<uint64_t>& lengths, const std::function<std::string(size_t, size_t)>& letters,
+                              std::vector<std::vector<Hit>>& rows) {
+    rows.assign(candidates.size(), {});
+    n_candidates_ += candidates.size();
+    std::vector<size_t> order(candidates.size()), on_host, on_device, on_long;
+    std::iota(order.begin(), order.end(), (size_t)0);
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return candidates[x].bin < candidates[y].bin; });
+    const char* route_env = std::getenv("TETREX_VERIFY_TARGETS");
+    const bool all_on_host = route_env && std::string(route_env) == "host";
+    const size_t longest = device_max();
+    const uint64_t budget = target_slot_budget();
+    for (size_t i : order) {
+        if (all_on_host || lengths[i] == 0 || lengths[i] > longest) on_host.push_back(i);
+        else (lengths[i] > TXQ_EDIT_MAX_PATTERN ? on_long : on_device).push_back(i);
+    }
+    // what the routes find: (record, strand, distance, end) of every hit of a candidate; settled below
+    struct Found { uint32_t r, strand, d, j; };
+    std::vector<std::vector<Found>> found(candidates.size());
+
+    // the device: one call per bin, kernel and at most `budget` slots, queued in rounds with one copy back each
+    struct Call { uint32_t bin; bool is_long; size_t first, n_pairs; uint64_t n_records; size_t row0, work0; };
+    const auto run_round = [&](const std::vector<Call>& calls, const std::vector<uint32_t>& pairs, const std::vector<size_t>& owner, size_t n_rows, size_t work_bytes) {
+        const size_t n_pairs = pairs.size() / 3;
+        DevBuf d_pairs(pairs.size() * 4 + 4), d_hits(n_rows * 16 + 16), d_total(calls.size() * 8), d_status(n_pairs * 4 + 4), d_work(work_bytes + 8);
+        txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
+        for (size_t c = 0; c < calls.size(); ++c) {
+            const Call& k = calls[c];
+            ResidentBins::Bin& e = bins_.resident(k.bin);
+            const uint64_t* d_rec = (const uint64_t*)e.d_rec;
+            const size_t n_slots = k.n_pairs * k.n_records;
+            txq_check((k.is_long ? txq_edit_targets_long_device : txq_edit_targets_device)(
+                          patterns.d_letters, patterns.d_offsets, patterns.n_patterns, patterns.bytes, (const uint8_t*)e.d_text, d_rec, e.n_records, e.text_bytes,
+                          d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * k.first, k.n_pairs, (const uint8_t*)d_codes_,
+                          (uint32_t*)d_hits.p + 4 * k.row0, n_slots, (uint64_t*)d_total.p + c, (uint32_t*)d_status.p + k.first, n_slots,
+                          (unsigned char*)d_work.p + k.work0, nullptr),
+                      k.is_long ? "txq_edit_targets_long_device" : "txq_edit_targets_device");
+        }
+        std::vector<uint32_t> hits, status(n_pairs + 1);
+        std::vector<uint64_t> totals(calls.size());
+        txq_check(txq_memcpy_d2h(totals.data(), d_total.p, totals.size() * 8), "d2h");  // (waits for the kernels)
+        txq_check(txq_memcpy_d2h(status.data(), d_status.p, n_pairs * 4), "d2h");
+        for (size_t p = 0; p < n_pairs; ++p)
+            if (status[p] != 0) throw std::runtime_error("tetrex search --all-targets: the device refused a pair of bin " + std::to_string(candidates[owner[p / strands]].bin));
+        // The rows: a call's area is as large as its slots, what was written is usually far less.  One copy of the round's whole
+        // area where that is at most kOneCopyBytes; above it, only the rows that were written, call by call.
+        constexpr size_t kOneCopyBytes = (size_t)4 << 20;
+        const bool one_copy = n_rows * 16 <= kOneCopyBytes;
+        if (one_copy && n_rows) {
+            hits.resize(4 * n_rows);
+            txq_check(txq_memcpy_d2h(hits.data(), d_hits.p, n_rows * 16), "d2h");
+        }
+        for (size_t c = 0; c < calls.size(); ++c) {
+            const Call& k = calls[c];
+            if (totals[c] > k.n_pairs * k.n_records) throw std::runtime_error("tetrex search --all-targets: more hits than slots");
+            if (totals[c] == 0) continue;
+            if (!one_copy) {
+                hits.resize(4 * totals[c]);
+                txq_check(txq_memcpy_d2h(hits.data(), (const uint32_t*)d_hits.p + 4 * k.row0, totals[c] * 16), "d2h");
+            }
+            for (uint64_t h = 0; h < totals[c]; ++h) {
+                const uint32_t* row = hits.data() + 4 * ((one_copy ? k.row0 : 0) + h);
+                const size_t pair = k.first + row[0];
+                found[owner[pair / strands]].push_back({row[2], (uint32_t)(pair % strands), row[1], row[3]});
+            }
+        }
+    };
+    {
+        const size_t n_short = on_device.size();
+        on_device.insert(on_device.end(), on_long.begin(), on_long.end());
+        std::vector<Call> calls;
+        std::vector<uint32_t> pairs;
+        std::vector<size_t> owner;  // the candidate of every `strands` pairs of the round
+        size_t n_rows = 0, work_bytes = 0;
+        const auto flush_round = [&]() {
+            if (!calls.empty()) run_round(calls, pairs, owner, n_rows, work_bytes);
+            calls.clear(), pairs.clear(), owner.clear();
+            n_rows = work_bytes = 0;
+        };
+        for (size_t a = 0; a < on_device.size();) {
+            size_t b = a;
+            const uint32_t bin = candidates[on_device[a]].bin;
+            const bool is_long = a >= n_short;
+            while (b < (is_long ? on_device.size() : n_short) && candidates[on_device[b]].bin == bin) ++b;
+            // the bin's record count decides its route, so a bin that is not on the device is read first and uploaded only if it stays
+            uint64_t n_records;
+            if (bins_.is_resident(bin)) n_records = bins_.at(bin).n_records;
+            else {
+                std::string text;
+                std::vector<uint64_t> rec;
+                std::vector<std::string> names;
+                bins_.read(bin, text, rec, names);
+                n_records = rec.size() - 1;
+                if (n_records <= budget) bins_.resident(bin, text, rec, names);
+            }
+            if (n_records > budget) {  // a single pair above the bound: the host
+                on_host.insert(on_host.end(), on_device.begin() + (long)a, on_device.begin() + (long)b);
+                a = b;
+                continue;
+            }
+            (is_long ? n_device_long_ : n_device_) += b - a;
+            const size_t first = pairs.size() / 3;
+            for (size_t k = a; k < b; ++k) {
+                owner.push_back(on_device[k]);
+                for (size_t s = 0; s < strands; ++s) {
+                    pairs.push_back(pattern_of[on_device[k]] + (uint32_t)s);
+                    pairs.push_back(0);
+                    pairs.push_back(errors_);
+                }
+            }
+            const size_t n_pairs = (b - a) * strands, per_call = (size_t)std::max<uint64_t>(1, n_records ? budget / n_records : n_pairs);
+            for (size_t p = 0; p < n_pairs; p += per_call) {
+                const size_t np = std::min(per_call, n_pairs - p), n_slots = np * n_records;
+                calls.push_back({bin, is_long, first + p, np, n_records, n_rows, work_bytes});
+                n_rows += n_slots;
+                work_bytes += TXQ_EDIT_TARGETS_WORKSPACE(np, n_slots);
+            }
+            a = b;
+            // (pairs of one candidate stay in one round: a round ends between bins)
+            if (n_rows >= 8 * budget) flush_round();
+        }
+        flush_round();
+    }
+    // the host: what is too long or empty, bins of more records than a call's slots, and with TETREX_VERIFY_TARGETS=host everything
+    std::stable_sort(on_host.begin(), on_host.end(), [&](size_t x, size_t y) { return candidates[x].bin < candidates[y].bin; });
+    n_host_ += on_host.size();
+    for (size_t a = 0; a < on_host.size();) {
+        size_t b = a;
+        const uint32_t bin = candidates[on_host[a]].bin;
+        while (b < on_host.size() && candidates[on_host[b]].bin == bin) ++b;
+        std::string text;
+        std::vector<uint64_t> rec;
+        std::vector<std::string> names;
+        bins_.read(bin, text, rec, names);
+        if (bins_.at(bin).names.empty()) bins_.at(bin).names = std::move(names);  // (else they are the same, and hits point into them)
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic)
+#endif
+        for (size_t k = a; k < b; ++k) {
+            if (lengths[on_host[k]] == 0) continue;
+            std::vector<uint32_t> quads;
+            for (size_t st = 0; st < strands; ++st) {
+                const std::string p = letters(on_host[k], st);
+                EditPattern ep((const uint8_t*)p.data(), p.size(), codes_);
+                quads.clear();
+                edit_targets_group(ep, (const uint8_t*)text.data(), rec.data(), 0, rec.size() - 1, errors_, 0, quads);
+                for (size_t h = 0; h < quads.size(); h += 4) found[on_host[k]].push_back({quads[h + 2], (uint32_t)st, quads[h + 1], quads[h + 3]});
+            }
+        }
+        a = b;
+    }
+    // settle: a target's row is its better strand, + on equal distance; rows in the order of the bin's file
+    struct ToAlign { size_t candidate, row; uint32_t strand, d, r, j; };
+    std::vector<ToAlign> to_align;
+    for (size_t i : order) {
+        std::vector<Found>& f = found[i];
+        std::sort(f.begin(), f.end(), [](const Found& x, const Found& y) { return std::tie(x.r, x.d, x.strand) < std::tie(y.r, y.d, y.strand); });
+        const std::vector<std::string>& names = bins_.at(candidates[i].bin).names;
+        for (size_t k = 0; k < f.size(); ++k) {
+            if (k && f[k].r == f[k - 1].r) continue;
+            Hit h;
+            h.distance = f[k].d, h.end = f[k].j, h.strand = f[k].strand ? '-' : '+', h.target = &names.at(f[k].r);
+            if (align_) to_align.push_back({i, rows[i].size(), f[k].strand, f[k].d, f[k].r, f[k].j});
+            rows[i].push_back(std::move(h));
+        }
+        if (!rows[i].empty()) ++n_confirmed_;
+        n_targets_ += rows[i].size();
+    }
+    if (to_align.empty()) return;
+    // --align: the rows that were kept, bin by bin (to_align is in bin order).  One txq_edit_align_device call per bin on pair and
+    // triple arrays built here, after the copy back; what the device declines or cannot reach, on the host.
+    const char* align_env = std::getenv("TETREX_VERIFY_ALIGN");
+    const bool align_on_device = !(align_env && std::string(align_env) == "host");
+    const uint32_t device_errors = std::min<uint32_t>(errors_, TXQ_EDIT_ALIGN_MAX_DISTANCE);
+    const size_t stride = TXQ_EDIT_ALIGN_STRIDE(device_errors);
+    std::vector<size_t> pending, sent;
+    for (size_t t = 0; t < to_align.size(); ++t) {
+        const size_t i = to_align[t].candidate;
+        const bool reachable = align_on_device && pattern_of[i] != 0xFFFFFFFFu && lengths[i] >= 1 && lengths[i] <= TXQ_EDIT_LONG_MAX_PATTERN &&
+                               to_align[t].d <= device_errors;
+        (reachable ? sent : pending).push_back(t);
+    }
+    if (!sent.empty()) {
+        std::vector<uint32_t> pairs, triples;
+        for (size_t t : sent) {
+            const ToAlign& x = to_align[t];
+            pairs.insert(pairs.end(), {pattern_of[x.candidate] + x.strand, 0u, errors_});
+            triples.insert(triples.end(), {x.d, x.r, x.j});
+        }
+        DevBuf d_pairs(pairs.size() * 4), d_triples(triples.size() * 4), d_align(sent.size() * stride * 4);
+        txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
+        txq_check(txq_memcpy_h2d(d_triples.p, triples.data(), triples.size() * 4), "h2d");
+        for (size_t a = 0; a < sent.size();) {
+            size_t b = a;
+            const uint32_t bin = candidates[to_align[sent[a]].candidate].bin;
+            while (b < sent.size() && candidates[to_align[sent[b]].candidate].bin == bin) ++b;
+            ResidentBins::Bin& e = bins_.resident(bin);
+            const uint64_t* d_rec = (const uint64_t*)e.d_rec;
+            txq_check(txq_edit_align_device(patterns.d_letters, patterns.d_offsets, patterns.n_patterns, patterns.bytes, (const uint8_t*)e.d_text, d_rec,
+                                            e.n_records, e.text_bytes, d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * a, b - a,
+                                            (const uint32_t*)d_triples.p + 3 * a, (const uint8_t*)d_codes_, device_errors, (uint32_t*)d_align.p + stride * a,
+                                            nullptr, nullptr),
+                      "txq_edit_align_device");
+            a = b;
+        }
+        std::vector<uint32_t> words(sent.size() * stride);
+        txq_check(txq_memcpy_d2h(words.data(), d_align.p, words.size() * 4), "d2h");  // (waits for the kernels)
+        for (size_t k = 0; k < sent.size(); ++k) {
+            const uint32_t* w = words.data() + stride * k;
+            const ToAlign& x = to_align[sent[k]];
+            if (w[0] < kEditNotAligned) {
+                rows[x.candidate][x.row].start = w[0];
+                rows[x.candidate][x.row].runs.assign(w + 2, w + 2 + w[1]);
+                ++n_align_device_;
+            } else pending.push_back(sent[k]);
+        }
+    }
+    std::stable_sort(pending.begin(), pending.end(), [&](size_t x, size_t y) { return candidates[to_align[x].candidate].bin < candidates[to_align[y].candidate].bin; });
+    for (size_t a = 0; a < pending.size();) {
+        size_t b = a;
+        const uint32_t bin = candidates[to_align[pending[a]].candidate].bin;
+        while (b < pending.size() && candidates[to_align[pending[b]].candidate].bin == bin) ++b;
+        std::string text;
+        std::vector<uint64_t> rec;
+        std::vector<std::string> names;
+        bins_.read(bin, text, rec, names);
+        bool failed = false;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic)
+#endif
+        for (size_t k = a; k < b; ++k) {
+            const ToAlign& x = to_align[pending[k]];
+            const std::string pattern = letters(x.candidate, x.strand);
+            EditAlignment al;
+            if (x.r + 1 >= rec.size() || !edit_align((const uint8_t*)pattern.data(), pattern.size(), (const uint8_t*)text.data() + rec[x.r],
+                                                     (size_t)(rec[x.r + 1] - rec[x.r]), x.d, x.j, codes_, al)) {
+#ifdef _OPENMP
+#pragma omp atomic write
+#endif
+                failed = true;
+                continue;
+            }
+            rows[x.candidate][x.row].start = al.start;
+            rows[x.candidate][x.row].runs = std::move(al.runs);
+        }
+        if (failed) throw std::runtime_error("tetrex search --align: a confirmed pair has no alignment (bin " + std::to_string(bin) + ")");
         n_align_host_ += b - a;
         a = b;
     }

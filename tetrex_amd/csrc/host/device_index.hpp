@@ -118,11 +118,12 @@ class DeviceIndex {
     // frames of its records become letters on the device (txq_translate_frames_device on the batch's bytes, which are still
     // there), the verifier compares frame `query` with bin `bin` by edit distance and confirmed[i] answers hits[i].
     // TETREX_VERIFY_FRAMES=host: the candidate frames are translated on the host (translate_frame) and verified as strings.
+    // all_targets (`--all-targets`): all_targets->at(i) receives every target of hits[i]; confirmed[i] then says nothing.
     struct TranslatedHit { uint32_t query, bin, count; };  // count: 0 unless with_counts
     void search_translated(std::string_view seq, const std::vector<uint64_t>& rec_offsets,
                            const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& n_of,
                            std::vector<uint64_t>& thresholds, std::vector<TranslatedHit>& hits, BinVerifier* verifier = nullptr,
-                           std::vector<VerifiedHit>* confirmed = nullptr);
+                           std::vector<VerifiedHit>* confirmed = nullptr, std::vector<std::vector<VerifiedHit>>* all_targets = nullptr);
     // `tetrex query -g`: upload the d-gram index next to the main index (same device, same shard)
     void attach_dgram(const DgramImage& dgram);
     bool has_dgram() const { return aux_ != nullptr; }
@@ -191,6 +192,15 @@ class ResidentBins {
 // answers come back in the verifier's one copy; a pair the device declines (more than TXQ_EDIT_ALIGN_MAX_DISTANCE edits), a pair
 // of the host route, and with TETREX_VERIFY_ALIGN=host every pair, is aligned by edit_align of host/edit_distance.hpp on the
 // bin's letters read once more.  n_aligned() counts the pairs each of the two routes aligned.  Needs txq_init (DeviceIndex::upload).
+// `--all-targets` (verify with `rows`): every record of the bin within E edits is a row of its pair, in the
+// order of the bin's file — on a nucleotide index a target's better strand, + on equal distance.  The routes are the same,
+// with txq_edit_targets_device / txq_edit_targets_long_device in place of the search calls and edit_targets_group on the host.
+// A call's slots — its pairs times the bin's records — are bounded by TETREX_VERIFY_TARGET_SLOTS (default 2^20): a bin
+// whose pairs need more is answered in several calls, a bin with more records than that on the host, and the calls are
+// queued in rounds of at most eight times that many slots; a round waits once, for its totals, and copies its rows back — the
+// whole row area in one copy where that is at most 4 MiB, else only the rows written, call by call.  TETREX_VERIFY_TARGETS=host sends every pair
+// to the host.  With set_align the rows that were kept are aligned by one txq_edit_align_device call per bin on pair and triple
+// arrays built after the copy back (one more round trip a batch), the rest on the host as above.
 class BinVerifier {
   public:
     BinVerifier(const std::vector<std::string>& bin_paths, bool dna, uint32_t errors);
@@ -201,7 +211,9 @@ class BinVerifier {
     using Hit = VerifiedHit;
     // hits[i] answers candidates[i]; queries[c.query] are the batch's records.  Throws std::runtime_error naming the bin file
     // that cannot be read.
-    void verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits);
+    // rows (`--all-targets`, below): rows->at(i) receives every target of candidates[i] instead, and hits stays as assign() left it.
+    void verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits,
+                std::vector<std::vector<Hit>>* rows = nullptr);
     // The same for patterns that are on the device already (`tetrex search --translate --verify-frames`, DESIGN.md §14: the
     // frames of txq_translate_frames_device).  Pattern p is d_letters[d_offsets[p] .. d_offsets[p+1]), n_patterns + 1 offsets,
     // `bytes` letters in all in a buffer with 16 bytes of slack behind them; candidates[i].query names a pattern,
@@ -213,9 +225,10 @@ class BinVerifier {
         size_t n_patterns, bytes;
     };
     void verify(const DevicePatterns& patterns, const std::vector<Candidate>& candidates, const std::vector<uint64_t>& lengths,
-                const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits);
+                const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows = nullptr);
     size_t n_candidates() const { return n_candidates_; }
     size_t n_confirmed() const { return n_confirmed_; }
+    size_t n_targets() const { return n_targets_; }  // `--all-targets`: the rows of all confirmed pairs
     struct Routed { size_t device, device_long, host; };
     Routed n_routed() const { return {n_device_, n_device_long_, n_host_}; }
     void set_align(bool on) { align_ = on; }
@@ -226,7 +239,12 @@ class BinVerifier {
     // what both entries share: candidate i compares `strands` consecutive patterns from pattern_of[i] (lengths[i] letters each)
     // with its bin — routing by length, the pairs, one call per bin and kernel, the one copy back, the host route, settle
     void run(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
-             const std::vector<uint64_t>& lengths, const std::function<std::string(size_t, size_t)>& letters, std::vector<Hit>& hits);
+             const std::vector<uint64_t>& lengths, const std::function<std::string(size_t, size_t)>& letters, std::vector<Hit>& hits,
+             std::vector<std::vector<Hit>>* rows);
+    // `--all-targets`: the same routing with txq_edit_targets*_device and edit_targets_group in place of the search calls
+    void run_targets(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
+                     const std::vector<uint64_t>& lengths, const std::function<std::string(size_t, size_t)>& letters,
+                     std::vector<std::vector<Hit>>& rows);
     static size_t device_max();  // the longest pattern the device answers (TETREX_VERIFY_LONG)
     ResidentBins bins_;
     bool dna_;
@@ -236,6 +254,7 @@ class BinVerifier {
     size_t n_candidates_ = 0, n_confirmed_ = 0, n_device_ = 0, n_device_long_ = 0, n_host_ = 0;
     bool align_ = false;
     size_t n_align_device_ = 0, n_align_host_ = 0;
+    size_t n_targets_ = 0;
 };
 
 // `tetrex query --gpu-verify`: which records of its candidate bins does a motif match at all?  Answered on the

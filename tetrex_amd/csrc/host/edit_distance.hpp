@@ -114,6 +114,19 @@ inline EditResult edit_search_group(EditPattern& p, const uint8_t* text, const u
     return out;
 }
 
+// One pair, every target (include/txq.h at txq_edit_targets_device): each record of [r0, r1) whose least
+// distance is within the cap, in record order, appended to `hits` as (pair, d, r, j), j the lowest end that reaches d.  The
+// least (d, r, j) of what is appended is what edit_search_group answers for the pair.
+inline void edit_targets_group(EditPattern& p, const uint8_t* text, const uint64_t* rec, uint64_t r0, uint64_t r1, uint32_t cap, uint32_t pair,
+                               std::vector<uint32_t>& hits) {
+    for (uint64_t r = r0; r < r1; ++r) {
+        uint32_t d;
+        size_t j;
+        p.scan(text + rec[r], (size_t)(rec[r + 1] - rec[r]), d, j);
+        if (d <= cap) hits.insert(hits.end(), {pair, d, (uint32_t)r, (uint32_t)j});
+    }
+}
+
 // ---- where a match begins, and its alignment (include/txq.h at txq_edit_align_device) -------------------
 // The host twin of the kernel in txq_edit_align.hip, with no limit on m or d: it answers the pairs the device declines and is
 // what the kernel is compared with.  Sellers' matrix on the 2 d + 1 diagonals around the one through (m, j) — row by row,

@@ -493,6 +493,40 @@ int txh_edit_search(const uint8_t* patterns, const uint64_t* pat_offsets, size_t
     } catch (const std::exception& e) { return fail(e.what()); }
 }
 
+int txh_edit_targets(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
+                     size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
+                     const uint8_t* codes, unsigned threads, uint32_t* hits, size_t capacity, uint64_t* total) {
+    if (!total || (capacity && !hits)) return fail("null argument");
+    // (`total` stands in for the array the call writes: it is written whatever the capacity)
+    if (int rc = check_edit_buffers(patterns, pat_offsets, n_patterns, text, rec_offsets, n_records, group_offsets, n_groups, pairs, n_pairs, codes,
+                                    (const uint32_t*)total))
+        return rc;
+    try {
+        std::vector<std::vector<uint32_t>> found(n_pairs);  // the hits of each pair; put together in pair order below
+        std::atomic<size_t> next{0};
+        const auto work = [&]() {
+            constexpr size_t kGrain = 16;
+            for (size_t i0; (i0 = next.fetch_add(kGrain)) < n_pairs;)
+                for (size_t i = i0; i < std::min(i0 + kGrain, n_pairs); ++i) {
+                    const uint32_t p = pairs[3 * i], g = pairs[3 * i + 1];
+                    EditPattern pat(patterns + pat_offsets[p], (size_t)(pat_offsets[p + 1] - pat_offsets[p]), codes);
+                    edit_targets_group(pat, text, rec_offsets, group_offsets[g], group_offsets[g + 1], pairs[3 * i + 2], (uint32_t)i, found[i]);
+                }
+        };
+        const size_t n_threads = std::max<size_t>(1, std::min<size_t>(threads ? threads : 1, (n_pairs + 15) / 16));
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < n_threads; ++t) pool.emplace_back(work);
+        work();
+        for (std::thread& t : pool) t.join();
+        uint64_t rows = 0;
+        for (const std::vector<uint32_t>& f : found)
+            for (size_t k = 0; k < f.size(); k += 4, ++rows)
+                if (rows < capacity) std::copy(f.begin() + (long)k, f.begin() + (long)k + 4, hits + 4 * rows);
+        *total = rows;
+        return 0;
+    } catch (const std::exception& e) { return fail(e.what()); }
+}
+
 int txh_edit_align(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
                    size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs, const uint32_t* results,
                    const uint8_t* codes, uint32_t max_errors, unsigned threads, uint32_t* align) {

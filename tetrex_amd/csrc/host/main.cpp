@@ -4,12 +4,13 @@
 //      the candidate bins that hold a match at all are found on the device, the matcher runs on those only — same rows)
 //   tetrex index [-k K] [-p fpr] [-c hashes] [-t N] [-n] [-i] [-r murphy|li] [--layout uniform|sized [--tmax N] [--rearrange [--rearrange-ratio R]]] <name> <libs...>
 //     (include/arg_parse.h:10-38, src/index_base.cpp:73-117)
-//   tetrex search [-e E [--verify [--align]] | --threshold F] [--counts] [--translate [--verify-frames [--align]]] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//   tetrex search [-e E [--verify [--align] [--all-targets]] | --threshold F] [--counts] [--translate [--verify-frames [--align] [--all-targets]]] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (not in the reference: every FASTA record a query, answered by seqan::hibf membership_for(values, threshold);
 //      --translate: nucleotide records on a peptide index, every record's six frames a query of their own;
 //      --verify: only the bins that hold the record within E edits, confirmed on the bins' own letters;
 //      --verify-frames, with --translate -e E: only the bins that hold the frame's residues within E edits, confirmed likewise;
-//      --align, with either: where each confirmed match begins in its target, and its alignment as a CIGAR string)
+//      --align, with either: where each confirmed match begins in its target, and its alignment as a CIGAR string;
+//      --all-targets, with either: one row per record of the bin within E edits, not only the bin's best one)
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
 #include "device_index.hpp"
@@ -482,10 +483,13 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
     if (verify) verifier = std::make_unique<BinVerifier>(image.bin_paths, false, (uint32_t)std::min<unsigned long long>(errors, 0xFFFFFFFEull));
     const bool align = verify && a.has("align");
     if (align) verifier->set_align(true);
+    const bool all_targets = verify && a.has("all-targets");  // a row per target, not per bin
     std::vector<BinVerifier::Hit> confirmed;
+    std::vector<std::vector<BinVerifier::Hit>> targets;
     auto flush = [&]() {
         if (names.empty()) return;
-        dev.search_translated(seq, rec_offsets, threshold_of, with_counts, n_of, thresholds, hits, verifier.get(), verify ? &confirmed : nullptr);
+        dev.search_translated(seq, rec_offsets, threshold_of, with_counts, n_of, thresholds, hits, verifier.get(), verify ? &confirmed : nullptr,
+                              all_targets ? &targets : nullptr);
         size_t h = 0;
         for (size_t r = 0; r < names.size(); ++r) {
             bool searched = false;
@@ -494,14 +498,19 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
                 std::cerr << "[tetrex search] " << names[r] << ": no frame with " << k << "-mers enough for a threshold above 0, skipped" << std::endl;
             for (; h < hits.size() && hits[h].query < 6 * (r + 1); ++h) {
                 const DeviceIndex::TranslatedHit& x = hits[h];
+                const auto write = [&](const BinVerifier::Hit* v) {
+                    row.assign(names[r]).append("\t").append(image.bin_paths[x.bin]).append("\t").append(kFrames[x.query % 6]);
+                    if (with_counts) row.append("\t").append(std::to_string(x.count)).append("/").append(std::to_string(n_of[x.query]));
+                    if (v) row.append("\t").append(std::to_string(v->distance)).append("\t").append(*v->target).append("\t").append(std::to_string(v->end));
+                    if (align) append_alignment(row, *v);
+                    out << row << '\n';
+                };
+                if (all_targets) {
+                    for (const BinVerifier::Hit& v : targets[h]) write(&v);
+                    continue;
+                }
                 if (verify && confirmed[h].distance == 0xFFFFFFFFu) continue;
-                row.assign(names[r]).append("\t").append(image.bin_paths[x.bin]).append("\t").append(kFrames[x.query % 6]);
-                if (with_counts) row.append("\t").append(std::to_string(x.count)).append("/").append(std::to_string(n_of[x.query]));
-                if (verify)
-                    row.append("\t").append(std::to_string(confirmed[h].distance)).append("\t").append(*confirmed[h].target).append("\t")
-                        .append(std::to_string(confirmed[h].end));
-                if (align) append_alignment(row, confirmed[h]);
-                out << row << '\n';
+                write(verify ? &confirmed[h] : nullptr);
             }
         }
         names.clear();
@@ -517,6 +526,7 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
     flush();
     out.flush();
     if (verbose && verify) std::cerr << "Verified: " << verifier->n_confirmed() << " of " << verifier->n_candidates() << " candidate pairs" << std::endl;
+    if (verbose && all_targets) std::cerr << "Targets: " << verifier->n_targets() << std::endl;
     if (verify && std::getenv("TETREX_TRACE")) {
         const BinVerifier::Routed n = verifier->n_routed();
         std::cerr << "[tetrex search] verify routes: device " << n.device << ", device-long " << n.device_long << ", host " << n.host << std::endl;
@@ -537,7 +547,7 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
 int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
                                        {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false},
-                                       {'\0', "verify-frames", false}, {'\0', "align", false}};
+                                       {'\0', "verify-frames", false}, {'\0', "align", false}, {'\0', "all-targets", false}};
     Args a;
     unsigned long long errors = 0;
     double fraction = 0;
@@ -552,6 +562,8 @@ int cmd_search(int argc, char** argv) {
         }
         if (a.has("align") && !a.has("verify") && !a.has("verify-frames"))
             throw std::runtime_error("--align gives the alignment of confirmed rows: it needs --verify, or --translate --verify-frames");
+        if (a.has("all-targets") && !a.has("verify") && !a.has("verify-frames"))
+            throw std::runtime_error("--all-targets lists every target of confirmed rows: it needs -e E --verify, or --translate -e E --verify-frames");
         if (a.has("verify") && a.has("threshold")) throw std::runtime_error("--verify confirms the bins of -e E: it cannot be combined with --threshold");
         if (a.has("verify") && a.has("translate")) throw std::runtime_error("--verify cannot be combined with --translate (translated rows are confirmed with --verify-frames)");
         if (a.has("verify") && !a.has("errors")) throw std::runtime_error("--verify needs -e E: the number of edits a confirmed bin may be away");
@@ -613,9 +625,11 @@ int cmd_search(int argc, char** argv) {
     if (verify) verifier = std::make_unique<BinVerifier>(image.bin_paths, dna, (uint32_t)std::min<unsigned long long>(errors, 0xFFFFFFFEull));
     const bool align = verify && a.has("align");
     if (align) verifier->set_align(true);
+    const bool all_targets = verify && a.has("all-targets");  // a row per target, not per bin
     std::vector<std::string> seqs;  // --verify: the batch's records themselves
     std::vector<BinVerifier::Candidate> candidates;
     std::vector<BinVerifier::Hit> confirmed;
+    std::vector<std::vector<BinVerifier::Hit>> targets;
     auto flush = [&]() {
         if (names.empty()) return;
         dev.count(values, offsets, thresholds, hits, with_counts ? &counts : nullptr);
@@ -623,17 +637,24 @@ int cmd_search(int argc, char** argv) {
             candidates.clear();
             for (size_t q = 0; q < names.size(); ++q)
                 for (uint64_t u : set_bins(hits.data() + q * W, bins)) candidates.push_back({(uint32_t)q, (uint32_t)u});
-            verifier->verify(seqs, candidates, confirmed);
+            verifier->verify(seqs, candidates, confirmed, all_targets ? &targets : nullptr);
             for (size_t c = 0; c < candidates.size(); ++c) {
+                const size_t q = candidates[c].query, u = candidates[c].bin;
+                const auto write = [&](const BinVerifier::Hit& h) {
+                    row.assign(names[q]).append("\t").append(image.bin_paths[u]);
+                    if (with_counts) row.append("\t").append(std::to_string(counts[q * W * 64 + u])).append("/").append(std::to_string(n_of[q]));
+                    row.append("\t").append(std::to_string(h.distance)).append("\t").append(*h.target).append("\t").append(std::to_string(h.end));
+                    if (dna) row.append("\t").append(1, h.strand);
+                    if (align) append_alignment(row, h);
+                    out << row << '\n';
+                };
+                if (all_targets) {
+                    for (const BinVerifier::Hit& h : targets[c]) write(h);
+                    continue;
+                }
                 const BinVerifier::Hit& h = confirmed[c];
                 if (h.distance == 0xFFFFFFFFu) continue;
-                const size_t q = candidates[c].query, u = candidates[c].bin;
-                row.assign(names[q]).append("\t").append(image.bin_paths[u]);
-                if (with_counts) row.append("\t").append(std::to_string(counts[q * W * 64 + u])).append("/").append(std::to_string(n_of[q]));
-                row.append("\t").append(std::to_string(h.distance)).append("\t").append(*h.target).append("\t").append(std::to_string(h.end));
-                if (dna) row.append("\t").append(1, h.strand);
-                if (align) append_alignment(row, h);
-                out << row << '\n';
+                write(h);
             }
             seqs.clear();
         } else {
@@ -675,6 +696,7 @@ int cmd_search(int argc, char** argv) {
     flush();
     out.flush();
     if (verbose && verify) std::cerr << "Verified: " << verifier->n_confirmed() << " of " << verifier->n_candidates() << " candidate pairs" << std::endl;
+    if (verbose && all_targets) std::cerr << "Targets: " << verifier->n_targets() << std::endl;
     if (verify && std::getenv("TETREX_TRACE")) {
         const BinVerifier::Routed n = verifier->n_routed();
         std::cerr << "[tetrex search] verify routes: device " << n.device << ", device-long " << n.device_long << ", host " << n.host << std::endl;

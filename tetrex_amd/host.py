@@ -405,6 +405,36 @@ def edit_search(patterns, records, groups, pairs, codes, threads=1):
     return out
 
 
+def edit_targets(patterns, records, groups, pairs, codes, threads=1, capacity=None):
+    """txh_edit_targets: every record of a pair's group within the cap, on the host (include/txh.h; the semantics are in
+    include/txq.h at txq_edit_targets_device).  The arguments of edit_search.  Returns (hits, total): hits an (n, 4) uint32 array
+    of (pair, distance, record, end) by pair, then by record, and total the number of hits; with a capacity only the first
+    `capacity` rows are returned, total still counting all."""
+    L = lib()
+    L.txh_edit_targets.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                   C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+    pat, po = patterns if isinstance(patterns, tuple) else _byte_records(patterns)
+    txt, ro = records if isinstance(records, tuple) else _byte_records(records)
+    pat, txt = np.ascontiguousarray(pat, dtype=np.uint8), np.ascontiguousarray(txt, dtype=np.uint8)
+    po, ro = np.ascontiguousarray(po, dtype=np.uint64), np.ascontiguousarray(ro, dtype=np.uint64)
+    go = np.ascontiguousarray(groups, dtype=np.uint64)
+    pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 3)
+    cd = np.ascontiguousarray(codes, dtype=np.uint8)
+    if cd.size != 256 or po.size < 1 or ro.size < 1 or go.size < 1 or int(po[-1]) > pat.size or int(ro[-1]) > txt.size:
+        raise HostError("edit_targets: offsets, bytes and class table disagree")
+    room = 1024 if capacity is None else int(capacity)
+    while True:
+        hits, total = np.zeros((room, 4), dtype=np.uint32), C.c_uint64(0)
+        rc = L.txh_edit_targets(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
+                                go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], cd.ctypes.data, threads, hits.ctypes.data, room,
+                                C.byref(total))
+        if rc < 0:
+            raise _err()
+        if capacity is not None or total.value <= room:
+            return hits[:min(total.value, room)].copy(), int(total.value)
+        room = int(total.value)
+
+
 EDIT_ALIGN_OPS = "=XID"
 
 
