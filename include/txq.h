@@ -63,6 +63,7 @@ extern "C" {
  *   TXQ_PROBE_BLOCKS_PER_CU, TXQ_PROBE_UNROLL, TXQ_PROBE_NT   grid and variant of the flat probe kernel
  *   TXQ_EDIT_CHUNK=<bytes>                            bytes of text per lane of the edit-distance kernel (txq_edit_search, below)
  *   TXQ_EDIT_LONG_SPAN=<bytes>                        bytes of text per lane group of the long-pattern edit-distance kernel (txq_edit_search_long, below)
+ *   TXQ_COUNT_WINDOWS_UNIT=<n>, TXQ_COUNT_WINDOWS_WAVES=1|4   windows per workgroup of the sliding count and its waves (txq_count_windows, below)
  *   TXQ_PROBE_TABLE=0|1                               a flat probe's table of its batch's k-mer domain: never | whenever it fits
  *                                                     (unset: where the batch repeats its values often enough to pay for it)
  *   TXQ_PROBE_TABLE_KEEP=0                            that table is built from its first row on every call, not kept with the
@@ -204,6 +205,28 @@ int txq_count_device(txq_index* ix, const uint64_t* d_values, const uint64_t* d_
                      const uint32_t* d_thresholds, uint64_t* d_hits, uint32_t* d_counts, void* stream);
 int txq_count(txq_index* ix, const uint64_t* values, const uint64_t* offsets, size_t n_queries,
               const uint32_t* thresholds, uint64_t* hits, uint32_t* counts);  /* host buffers, synchronous */
+
+/* The same of sliding windows over one value array (`tetrex search --window`; not in the reference).  Window j owns
+ * d_values[d_win_begin[j] .. d_win_begin[j] + d_win_len[j]).  The windows form a sliding sequence: d_win_begin does not
+ * decrease and d_win_begin + d_win_len does not decrease; they may overlap, touch, leave gaps, repeat, or be empty.  The result
+ * is DEFINED as what txq_count_device gives when window j is query j — hits, counts, threshold 0 selecting every user bin of the
+ * shard, a column shard answering for its own columns, d_counts == NULL — and sub-tree shards are refused (TXQ_ERR_ARG).
+ * Flat IBF: a workgroup takes TXQ_COUNT_WINDOWS_UNIT consecutive windows, counts the first in full and every next one from
+ * its predecessor: the values that enter are added to the counters, those that leave are subtracted (their rows were read a
+ * window ago and come from L2), so a window costs the rows of two steps, not of its whole length.  A window is counted by ONE
+ * workgroup: a window of 10^5 values is exact, but slow (txq_count_device spreads such a query over many workgroups).
+ * HIBF: the windows run as independent queries, each (window, IBF) pair counted in full by one wave — exact, no sliding; every
+ * IBF may have at most 8192 technical bins, as for txq_count.
+ * txq_count_windows checks before anything is launched that the windows slide, that each ends within n_values and that no
+ * pointer it needs is NULL (TXQ_ERR_ARG); txq_count_windows_device trusts the device arrays it is given.  It allocates nothing
+ * outside the index's scratch and does not synchronise with the host.
+ *   TXQ_COUNT_WINDOWS_UNIT=<n>    windows per workgroup on a flat IBF (default 16, 1 .. 2^20; read at every call)
+ *   TXQ_COUNT_WINDOWS_WAVES=1|4   waves of that workgroup (default 1; read at every call)
+ * The results are the same for every value of either. */
+int txq_count_windows_device(txq_index* ix, const uint64_t* d_values, const uint64_t* d_win_begin, const uint32_t* d_win_len,
+                             size_t n_windows, const uint32_t* d_thresholds, uint64_t* d_hits, uint32_t* d_counts, void* stream);
+int txq_count_windows(txq_index* ix, const uint64_t* values, size_t n_values, const uint64_t* win_begin, const uint32_t* win_len,
+                      size_t n_windows, const uint32_t* thresholds, uint64_t* hits, uint32_t* counts);  /* host buffers, synchronous */
 
 /* Six-frame translation of nucleotide records into the k-mer values of a peptide index (`tetrex search --translate`; not in
  * the reference).  Record r is the bytes d_seq[d_rec_offsets[r] .. d_rec_offsets[r+1]) (n_records + 1 ascending offsets).

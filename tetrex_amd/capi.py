@@ -22,6 +22,7 @@ SYMBOLS = [
     "txq_init", "txq_shutdown", "txq_last_error", "txq_device_count",
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
+    "txq_count_windows", "txq_count_windows_device",
     "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_translate_frames_bound", "txq_translate_frames_device", "txq_translate_frames",
     "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
     "txq_edit_search_long", "txq_edit_search_long_device", "txq_edit_align", "txq_edit_align_device",
@@ -82,6 +83,8 @@ def lib():
         L.txq_emplace_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.txq_count.argtypes = [C.c_void_p, u64p, u64p, C.c_size_t, u32p, u64p, u32p]
         L.txq_count_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.txq_count_windows.argtypes = [C.c_void_p, u64p, C.c_size_t, u64p, u32p, C.c_size_t, u32p, u64p, u32p]
+        L.txq_count_windows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.txq_translate_bound.restype = C.c_uint64
         L.txq_translate_bound.argtypes = [u64p, C.c_size_t, C.c_uint]
         L.txq_translate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -364,6 +367,28 @@ class Index:
 
     def count_device(self, d_values, d_offsets, n_queries, d_thresholds, d_hits, d_counts=None, stream=None):
         check(lib().txq_count_device(self._h, d_values, d_offsets, n_queries, d_thresholds, d_hits, d_counts, stream))
+
+    def count_windows(self, values, begins, lens, thresholds, counts=False):
+        """Threshold membership of sliding windows (txq_count_windows): window j owns values[begins[j]:begins[j] + lens[j]] and
+        thresholds[j]; begins and begins + lens do not decrease.  Returns hits (n_windows, shard_words) uint64, and with
+        counts=True also counts (n_windows, 64 * shard_words) uint32: what count() gives with window j as query j."""
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        b = np.ascontiguousarray(begins, dtype=np.uint64)
+        n = np.ascontiguousarray(lens, dtype=np.uint32)
+        t = np.ascontiguousarray(thresholds, dtype=np.uint32)
+        nw = b.size
+        if n.size != nw or t.size != nw:
+            raise TxqError(-1, "count_windows: %d begins, %d lens and %d thresholds" % (b.size, n.size, t.size))
+        if nw and int((b + n.astype(np.uint64)).max()) > v.size:
+            raise TxqError(-1, "count_windows: windows run past the %d values" % v.size)
+        hits = np.zeros((nw, self.shard_words), dtype=np.uint64)
+        cnt = np.zeros((nw, 64 * self.shard_words), dtype=np.uint32) if counts else None
+        check(lib().txq_count_windows(self._h, v.ctypes.data_as(u64p), v.size, b.ctypes.data_as(u64p), n.ctypes.data_as(u32p), nw,
+                                      t.ctypes.data_as(u32p), hits.ctypes.data_as(u64p), cnt.ctypes.data_as(u32p) if counts else None))
+        return (hits, cnt) if counts else hits
+
+    def count_windows_device(self, d_values, d_begins, d_lens, n_windows, d_thresholds, d_hits, d_counts=None, stream=None):
+        check(lib().txq_count_windows_device(self._h, d_values, d_begins, d_lens, n_windows, d_thresholds, d_hits, d_counts, stream))
 
     def emplace_device(self, d_values, d_bins_of, n, stream=None):
         check(lib().txq_emplace_device(self._h, d_values, d_bins_of, n, stream))

@@ -781,6 +781,83 @@ void DeviceIndex::search_translated(std::string_view seq, const std::vector<uint
     }
 }
 
+void DeviceIndex::search_windows(const std::vector<uint64_t>& values, const std::vector<uint64_t>& begins, const std::vector<uint32_t>& lens,
+                                 const std::vector<uint32_t>& thresholds, bool with_counts, std::vector<TranslatedHit>& hits) {
+    if (!ix_) throw std::runtime_error("index not uploaded");
+    if (shards_.size() > 1) throw std::runtime_error("search_windows: one shard only");
+    const size_t N = begins.size(), W = info_.shard_words;
+    if (lens.size() != N || thresholds.size() != N) throw std::runtime_error("search_windows: begins, lens and thresholds disagree");
+    hits.clear();
+    for (size_t j = 0; j < N; ++j) {
+        if (begins[j] > values.size() || lens[j] > values.size() - begins[j]) throw std::runtime_error("search_windows: a window runs past the values");
+        if (j && (begins[j] < begins[j - 1] || begins[j] + lens[j] < begins[j - 1] + lens[j - 1])) throw std::runtime_error("search_windows: the windows do not slide");
+    }
+    if (N == 0 || W == 0) return;
+    const uint64_t max_values = (uint64_t)1 << 24;
+    size_t max_windows = std::max<size_t>(1, ((size_t)256 << 20) / (W * (with_counts ? 64 * 4 : 8)));
+    if (const char* e = std::getenv("TETREX_SEARCH_BATCH_WINDOWS"); e && *e) max_windows = std::min<size_t>(max_windows, std::max<long long>(1, std::atoll(e)));
+    const bool trace = std::getenv("TETREX_TRACE") != nullptr;
+    GrowBuf d_val, d_beg, d_len, d_thr, d_hit, d_cnt, d_list, d_total;
+    d_total.reserve(8);
+    size_t list_cap = (size_t)1 << 20;
+    std::vector<uint64_t> beg;
+    std::vector<uint32_t> thr, list;
+    // the batches: windows [cut[i], cut[i + 1]), values [begin of the first, end of the last) (a window longer than the bound
+    // on values: a batch of its own).  The buffers are sized for the largest batch before the first one runs, so that no
+    // device memory is freed or allocated between the launches of a call.
+    std::vector<size_t> cut{0};
+    size_t most_windows = 0;
+    uint64_t most_values = 0;
+    for (size_t j0 = 0; j0 < N;) {
+        size_t j1 = j0;
+        while (j1 < N && j1 - j0 < max_windows && (j1 == j0 || begins[j1] + lens[j1] - begins[j0] <= max_values)) ++j1;
+        most_windows = std::max(most_windows, j1 - j0);
+        most_values = std::max(most_values, begins[j1 - 1] + lens[j1 - 1] - begins[j0]);
+        cut.push_back(j0 = j1);
+    }
+    d_val.reserve(most_values * 8 + 8);
+    d_beg.reserve(most_windows * 8);
+    d_len.reserve(most_windows * 4);
+    d_thr.reserve(most_windows * 4);
+    d_hit.reserve(most_windows * W * 8);
+    if (with_counts) d_cnt.reserve(most_windows * W * 64 * 4);
+    d_list.reserve(list_cap * 12);
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        const size_t first = cut[c], j1 = cut[c + 1], n = j1 - first;
+        const uint64_t v0 = begins[first], v1 = begins[j1 - 1] + lens[j1 - 1];
+        bool any = false;
+        for (size_t j = first; j < j1; ++j) any = any || thresholds[j] > 0;
+        if (!any) continue;
+        beg.assign(begins.begin() + first, begins.begin() + j1);
+        for (uint64_t& b : beg) b -= v0;
+        thr.assign(thresholds.begin() + first, thresholds.begin() + j1);
+        for (uint32_t& t : thr)
+            if (t == 0) t = 0xFFFFFFFFu;  // (no count reaches it: a window that is not searched has no hits)
+        if (v1 > v0) txq_check(txq_memcpy_h2d(d_val.p, values.data() + v0, (v1 - v0) * 8), "h2d");
+        txq_check(txq_memcpy_h2d(d_beg.p, beg.data(), n * 8), "h2d");
+        txq_check(txq_memcpy_h2d(d_len.p, lens.data() + first, n * 4), "h2d");
+        txq_check(txq_memcpy_h2d(d_thr.p, thr.data(), n * 4), "h2d");
+        txq_check(txq_count_windows_device(ix_, (const uint64_t*)d_val.p, (const uint64_t*)d_beg.p, (const uint32_t*)d_len.p, n, (const uint32_t*)d_thr.p,
+                                           (uint64_t*)d_hit.p, with_counts ? (uint32_t*)d_cnt.p : nullptr, nullptr), "txq_count_windows_device");
+        uint64_t total = 0;
+        for (;;) {
+            d_list.reserve(list_cap * 12);
+            txq_check(txq_hit_list_device((const uint64_t*)d_hit.p, with_counts ? (const uint32_t*)d_cnt.p : nullptr, n, W, (uint32_t*)d_list.p,
+                                          list_cap, (uint64_t*)d_total.p, nullptr), "txq_hit_list_device");
+            txq_check(txq_memcpy_d2h(&total, d_total.p, 8), "d2h");
+            if (total <= list_cap) break;
+            list_cap = total;  // (the list did not fit: once more with room for all of it)
+        }
+        list.resize(3 * total);
+        if (total) txq_check(txq_memcpy_d2h(list.data(), d_list.p, total * 12), "d2h");
+        if (trace)
+            std::fprintf(stderr, "[tetrex search] window batch: windows %zu..%zu, values %llu..%llu, %llu hits\n", first, j1, (unsigned long long)v0,
+                         (unsigned long long)v1, (unsigned long long)total);
+        const uint32_t bin0 = (uint32_t)(info_.shard_word0 * 64);
+        for (uint64_t i = 0; i < total; ++i) hits.push_back(TranslatedHit{(uint32_t)first + list[3 * i], bin0 + list[3 * i + 1], list[3 * i + 2]});
+    }
+}
+
 // ---- tetrex search --verify --------------------------------------------------------------------------------------------
 
 ResidentBins::ResidentBins(const std::vector<std::string>& bin_paths, std::string who)

@@ -124,6 +124,15 @@ class DeviceIndex {
                            const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& n_of,
                            std::vector<uint64_t>& thresholds, std::vector<TranslatedHit>& hits, BinVerifier* verifier = nullptr,
                            std::vector<VerifiedHit>* confirmed = nullptr, std::vector<std::vector<VerifiedHit>>* all_targets = nullptr);
+    // `tetrex search --window`: sliding windows over one value array.  Window j owns
+    // values[begins[j] .. begins[j] + lens[j]) and thresholds[j]; begins and begins + lens do not decrease.  A window with
+    // threshold 0 is not searched and has no hits.  Windows go to the device in batches that end at a window boundary: at most
+    // 2^24 values (the values a batch's last windows share with the next batch's first are sent again), at most 256 MiB of hit
+    // words / counts, and at most TETREX_SEARCH_BATCH_WINDOWS windows where that is set (for tests: the hits are the same for
+    // every value).  The hit and count matrices stay on the device (txq_count_windows_device); only the list of
+    // (window, bin, count) comes back (txq_hit_list_device), in (window, bin) order.  One shard only.
+    void search_windows(const std::vector<uint64_t>& values, const std::vector<uint64_t>& begins, const std::vector<uint32_t>& lens,
+                        const std::vector<uint32_t>& thresholds, bool with_counts, std::vector<TranslatedHit>& hits);
     // `tetrex query -g`: upload the d-gram index next to the main index (same device, same shard)
     void attach_dgram(const DgramImage& dgram);
     bool has_dgram() const { return aux_ != nullptr; }

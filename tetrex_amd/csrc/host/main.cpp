@@ -11,6 +11,9 @@
 //      --verify-frames, with --translate -e E: only the bins that hold the frame's residues within E edits, confirmed likewise;
 //      --align, with either: where each confirmed match begins in its target, and its alignment as a CIGAR string;
 //      --all-targets, with either: one row per record of the bin within E edits, not only the bin's best one)
+//   tetrex search --window W [--step S] (-e E | --threshold F) [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//     (a local search: every record cut into overlapping windows of W letters, S apart, each answered like a record of its own,
+//      slid on the device; the rows say where on the record each bin is hit)
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
 #include "device_index.hpp"
@@ -536,6 +539,115 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
     return 0;
 }
 
+// tetrex search --window W [--step S]: a local search for records longer than what they match.  A record of
+// L letters is cut into windows of W letters at letter offsets 0, S, 2 S, ... while offset + W <= L, and one more at L - W where
+// the last of these ends before L (every letter is covered); a record of at most W letters is one window.  A window of l
+// letters has w = l - k + 1 values and the plain rules with n = w: -e E gives t = max(w - k E, 0), --threshold F gives
+// t = ceil(F w).  A window with t = 0 is not searched and reports nothing; a record that had such a window gets one note.
+// All windows of a batch of records are counted on the device by sliding (txq_count_windows_device) and only the hit list
+// comes back.  Rows: for each (record, bin) every maximal run of consecutive hit windows is one row,
+// name \t bin path \t begin \t end [\t count/w], begin and end the 1-based inclusive letter positions of the run's union,
+// count/w those of the run's best window (the highest count, the earliest on a tie); by record, bin, begin.
+int search_windowed(const Args& a, const IndexImage& image, unsigned long long errors, double fraction, uint64_t window, uint64_t step) {
+    const bool verbose = a.has("verbose"), with_counts = a.has("counts"), by_fraction = a.has("threshold");
+    const std::string dest = a.get("output", "-");
+    const double t_start = now();
+    DeviceIndex dev;
+    dev.upload(image, std::atoi(a.get("device", "0").c_str()));
+    const KmerEncoder enc = dev.encoder();
+    const uint64_t k = enc.k();
+    std::ofstream file;
+    if (dest != "-") {
+        file.open(dest);
+        if (!file) throw std::runtime_error("Failed to open output file: " + dest);
+    }
+    std::ostream& out = dest == "-" ? std::cout : file;
+    // records are collected up to 2^24 values (one longer record: alone); search_windows cuts their windows into device batches
+    const size_t max_values = (size_t)1 << 24, max_windows = (size_t)1 << 22;
+    struct Rec { std::string name; size_t w0, w1; };  // its windows [w0, w1)
+    std::vector<Rec> recs;
+    std::vector<uint64_t> values, begins, letter_at;  // letter_at[j]: the 0-based letter offset of window j in its record
+    std::vector<uint32_t> lens, thresholds;
+    std::vector<DeviceIndex::TranslatedHit> hits;
+    std::string row;
+    uint64_t n_searched = 0, n_hit = 0, n_rows = 0;
+    auto flush = [&]() {
+        if (recs.empty()) return;
+        dev.search_windows(values, begins, lens, thresholds, with_counts, hits);
+        size_t h = 0;
+        std::vector<DeviceIndex::TranslatedHit> mine;
+        for (const Rec& r : recs) {
+            mine.clear();
+            for (; h < hits.size() && hits[h].query < r.w1; ++h) mine.push_back(hits[h]);
+            if (verbose) {
+                for (size_t i = 0; i < mine.size(); ++i) n_hit += i == 0 || mine[i].query != mine[i - 1].query;
+            }
+            std::stable_sort(mine.begin(), mine.end(), [](const DeviceIndex::TranslatedHit& x, const DeviceIndex::TranslatedHit& y) { return x.bin < y.bin; });
+            for (size_t i = 0; i < mine.size();) {  // a run: the same bin, windows j, j + 1, ...
+                size_t e = i + 1, best = i;
+                while (e < mine.size() && mine[e].bin == mine[i].bin && mine[e].query == mine[e - 1].query + 1) {
+                    if (mine[e].count > mine[best].count) best = e;
+                    ++e;
+                }
+                const uint32_t jf = mine[i].query, jl = mine[e - 1].query;
+                row.assign(r.name).append("\t").append(image.bin_paths[mine[i].bin]).append("\t").append(std::to_string(letter_at[jf] + 1));
+                row.append("\t").append(std::to_string(letter_at[jl] + lens[jl] + k - 1));
+                if (with_counts) row.append("\t").append(std::to_string(mine[best].count)).append("/").append(std::to_string(lens[mine[best].query]));
+                out << row << '\n';
+                ++n_rows;
+                i = e;
+            }
+        }
+        recs.clear();
+        values.clear();
+        begins.clear();
+        letter_at.clear();
+        lens.clear();
+        thresholds.clear();
+    };
+    std::vector<uint64_t> v;
+    for_each_record(a.pos[1], [&](const FastaRecord& r) {
+        v.clear();
+        enc.record_values(r.seq, false, v);
+        const uint64_t L = r.seq.size();
+        if (v.empty()) {
+            std::cerr << "[tetrex search] " << r.name << ": no k-mer of length " << k << ", skipped" << std::endl;
+            return;
+        }
+        if (!recs.empty() && (values.size() + v.size() > max_values || begins.size() >= max_windows)) flush();
+        const uint64_t base = values.size();
+        values.insert(values.end(), v.begin(), v.end());
+        Rec rec{r.name, begins.size(), 0};
+        bool unsearched = false;
+        const auto add = [&](uint64_t at, uint64_t letters) {
+            const uint64_t w = letters - k + 1;
+            uint64_t t;
+            if (by_fraction) t = (uint64_t)std::ceil(fraction * (double)w);
+            else t = w > k * errors ? w - k * errors : 0;
+            unsearched = unsearched || t == 0;
+            n_searched += t != 0;
+            begins.push_back(base + at);
+            letter_at.push_back(at);
+            lens.push_back((uint32_t)w);
+            thresholds.push_back((uint32_t)std::min<uint64_t>(t, 0xFFFFFFFEull));
+        };
+        if (L <= window) add(0, L);
+        else {
+            uint64_t at = 0;
+            for (; at + window <= L; at += step) add(at, window);
+            if (at - step + window < L) add(L - window, window);
+        }
+        rec.w1 = begins.size();
+        recs.push_back(std::move(rec));
+        if (unsearched) std::cerr << "[tetrex search] " << r.name << ": a window with threshold 0 is not searched" << std::endl;
+    });
+    flush();
+    out.flush();
+    if (verbose) std::cerr << "Windows: " << n_searched << " searched, " << n_hit << " hit, " << n_rows << " rows" << std::endl;
+    if (verbose) std::cerr << "Search time: " << (now() - t_start) << " s" << std::endl;
+    return 0;
+}
+
 // tetrex search: each record of the query file is a query; its values are the index's k-mers of the record (n of them) and a
 // bin is reported when at least t of them are in it (txq_count).  -e E: t = max(n - k E, 0) — a record within E edits of a
 // substring of a bin shares at least n - k E k-mer positions with it (q-gram lemma), and a Bloom filter drops none of them,
@@ -547,13 +659,33 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
 int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
                                        {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false},
-                                       {'\0', "verify-frames", false}, {'\0', "align", false}, {'\0', "all-targets", false}};
+                                       {'\0', "verify-frames", false}, {'\0', "align", false}, {'\0', "all-targets", false},
+                                       {'\0', "window", true}, {'\0', "step", true}};
     Args a;
-    unsigned long long errors = 0;
+    unsigned long long errors = 0, window = 0, step = 0;
     double fraction = 0;
     try {
         a = parse(argc, argv, 2, spec);
         if (a.pos.size() != 2) throw std::runtime_error("expected <index> <queries.fa>");
+        if (a.has("step") && !a.has("window")) throw std::runtime_error("--step is the distance between the windows of --window W: it needs --window");
+        if (a.has("window")) {
+            if (a.has("translate")) throw std::runtime_error("--window cannot be combined with --translate: translated frames lose their positions where stops are taken out");
+            if (a.has("verify-frames")) throw std::runtime_error("--window cannot be combined with --verify-frames: it confirms translated frames, which --window does not search");
+            if (a.has("all-targets")) throw std::runtime_error("--window cannot be combined with --all-targets: windows are not verified in this version");
+            if (a.has("align")) throw std::runtime_error("--window cannot be combined with --align: windows are not verified in this version");
+            if (a.has("verify")) throw std::runtime_error("--window cannot be combined with --verify: windows are not verified in this version");
+            if (!a.has("errors") && !a.has("threshold")) throw std::runtime_error("--window needs -e E or --threshold F");
+            const std::string w = a.get("window", "");
+            char* end = nullptr;
+            window = std::strtoull(w.c_str(), &end, 10);
+            if (w.empty() || *end || w[0] == '-' || window == 0 || window > 0x7FFFFFFFull) throw std::runtime_error("--window must be a number of letters >= k");
+            step = std::max<unsigned long long>(1, window / 2);
+            if (a.has("step")) {
+                const std::string s = a.get("step", "");
+                step = std::strtoull(s.c_str(), &end, 10);
+                if (s.empty() || *end || s[0] == '-' || step < 1 || step > window) throw std::runtime_error("--step must be a number of letters in 1 .. --window");
+            }
+        }
         if (a.has("verify-frames")) {
             if (a.has("verify")) throw std::runtime_error("--verify-frames cannot be combined with --verify: one confirms translated frames, the other plain records");
             if (!a.has("translate")) throw std::runtime_error("--verify-frames confirms the rows of --translate: it needs --translate");
@@ -602,6 +734,20 @@ int cmd_search(int argc, char** argv) {
             return 1;
         }
         return search_translated(a, image, errors, fraction);
+    }
+    if (a.has("window")) {
+        const unsigned long long k = image.k;
+        if (window < k) {
+            std::cerr << "[Search Parser Error] --window must be a number of letters >= k: the index has k = " << k << "\n";
+            return 1;
+        }
+        // -e E: a full window has w = W - k + 1 values and t = max(w - k E, 0); with t = 0 no full window would be searched
+        if (a.has("errors") && (errors > 0xFFFFFFFFull || window - k + 1 <= k * errors)) {
+            std::cerr << "[Search Parser Error] --window " << window << " with -e " << errors << " leaves every window a threshold of 0 (k = " << k
+                      << "): the smallest workable --window is " << (k * errors + k) << "\n";
+            return 1;
+        }
+        return search_windowed(a, image, errors, fraction, window, step);
     }
     DeviceIndex dev;
     dev.upload(image, std::atoi(a.get("device", "0").c_str()));

@@ -610,6 +610,66 @@ int txq_count(txq_index* ix, const uint64_t* values, const uint64_t* offsets, si
     return TXQ_OK;
 }
 
+int txq_count_windows_device(txq_index* ix, const uint64_t* d_values, const uint64_t* d_win_begin, const uint32_t* d_win_len, size_t n_windows,
+                             const uint32_t* d_thresholds, uint64_t* d_hits, uint32_t* d_counts, void* stream) {
+    if (!ix) return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = bind_index(ix)) return rc;
+    if (n_windows && (!d_values || !d_win_begin || !d_win_len || !d_thresholds || !d_hits)) return fail(TXQ_ERR_ARG, "null argument");
+    if (ix->join_or) return fail(TXQ_ERR_ARG, "txq_count_windows does not support sub-tree shards (txq_index_upload_subtrees)");
+    if (n_windows >= 0xFFFFFFFFull) return fail(TXQ_ERR_ARG, "at most 2^32-2 windows per call");
+    return count_windows_device(*ix, d_values, d_win_begin, d_win_len, n_windows, d_thresholds, d_hits, d_counts, (hipStream_t)stream);
+}
+
+// Host buffers: the windows are checked here, then the values they span, the windows (rebased to the first one's begin),
+// thresholds and results go through the device buffer of txq_count, on the index's first host-pipe stream.
+int txq_count_windows(txq_index* ix, const uint64_t* values, size_t n_values, const uint64_t* win_begin, const uint32_t* win_len, size_t n_windows,
+                      const uint32_t* thresholds, uint64_t* hits, uint32_t* counts) {
+    if (!ix) return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = bind_index(ix)) return rc;
+    if (n_windows && (!win_begin || !win_len || !thresholds || !hits)) return fail(TXQ_ERR_ARG, "null argument");
+    if (ix->join_or) return fail(TXQ_ERR_ARG, "txq_count_windows does not support sub-tree shards (txq_index_upload_subtrees)");
+    if (n_windows >= 0xFFFFFFFFull) return fail(TXQ_ERR_ARG, "at most 2^32-2 windows per call");
+    for (size_t j = 0; j < n_windows; ++j) {
+        if (win_begin[j] > n_values || win_len[j] > n_values - win_begin[j])
+            return fail(TXQ_ERR_ARG, "window %zu runs past the %zu values", j, n_values);
+        if (j && win_begin[j] < win_begin[j - 1]) return fail(TXQ_ERR_ARG, "window begins are not ascending at window %zu", j);
+        if (j && win_begin[j] + win_len[j] < win_begin[j - 1] + win_len[j - 1]) return fail(TXQ_ERR_ARG, "window ends are not ascending at window %zu", j);
+    }
+    const size_t W = ix->shard_words;
+    if (n_windows == 0 || W == 0) return TXQ_OK;
+    const uint64_t v0 = win_begin[0], span = win_begin[n_windows - 1] + win_len[n_windows - 1] - v0;
+    if (span >> 32) return fail(TXQ_ERR_ARG, "%llu values: at most 2^32-1 per call", (unsigned long long)span);
+    if (span && !values) return fail(TXQ_ERR_ARG, "null argument");
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_val = up(span * 8), b_beg = up(n_windows * 8), b_len = up(n_windows * 4), b_thr = up(n_windows * 4), b_hit = up(n_windows * W * 8);
+    const size_t b_cnt = counts ? up(n_windows * W * 64 * 4) : 0;
+    if (int rc = ensure((void**)&ix->scratch_count_io, &ix->cap_count_io, b_val + b_beg + b_len + b_thr + b_hit + b_cnt)) return rc;
+    unsigned char* base = ix->scratch_count_io;
+    uint64_t* d_val = (uint64_t*)base;
+    uint64_t* d_beg = (uint64_t*)(base + b_val);
+    uint32_t* d_len = (uint32_t*)(base + b_val + b_beg);
+    uint32_t* d_thr = (uint32_t*)(base + b_val + b_beg + b_len);
+    uint64_t* d_hit = (uint64_t*)(base + b_val + b_beg + b_len + b_thr);
+    uint32_t* d_cnt = counts ? (uint32_t*)(base + b_val + b_beg + b_len + b_thr + b_hit) : nullptr;
+    std::vector<uint64_t> begins(win_begin, win_begin + n_windows);
+    for (uint64_t& b : begins) b -= v0;
+    Index::HostPipe& hp = ix->host_pipe;
+    if (!hp.stream[0]) TXQ_HIP(hipStreamCreateWithFlags(&hp.stream[0], hipStreamNonBlocking));
+    hipStream_t st = hp.stream[0];
+    if (span) TXQ_HIP(hipMemcpyAsync(d_val, values + v0, span * 8, hipMemcpyHostToDevice, st));
+    TXQ_HIP(hipMemcpyAsync(d_beg, begins.data(), n_windows * 8, hipMemcpyHostToDevice, st));
+    TXQ_HIP(hipMemcpyAsync(d_len, win_len, n_windows * 4, hipMemcpyHostToDevice, st));
+    TXQ_HIP(hipMemcpyAsync(d_thr, thresholds, n_windows * 4, hipMemcpyHostToDevice, st));
+    if (int rc = count_windows_device(*ix, d_val, d_beg, d_len, n_windows, d_thr, d_hit, d_cnt, st)) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    TXQ_HIP(hipMemcpyAsync(hits, d_hit, n_windows * W * 8, hipMemcpyDeviceToHost, st));
+    if (counts) TXQ_HIP(hipMemcpyAsync(counts, d_cnt, n_windows * W * 64 * 4, hipMemcpyDeviceToHost, st));
+    TXQ_HIP(hipStreamSynchronize(st));
+    return TXQ_OK;
+}
+
 int txq_host_alloc(void** ptr, size_t bytes) {
     if (int rc = require_init()) return rc;
     if (!ptr) return fail(TXQ_ERR_ARG, "null argument");

@@ -26,6 +26,7 @@
 // columns and appends (query, child) for merged bins that pass.  Each level reads its item count from HBM: no host
 // synchronisation inside a call.
 #include "txq_internal.hpp"
+#include "txq_count_windows_plan.hpp"
 #include <algorithm>
 
 namespace txq {
@@ -37,6 +38,7 @@ static constexpr uint32_t kTileChunks = 64;     // 16-byte chunks per column til
 static constexpr uint64_t kSegMin = 512;        // values per unit of the flat kernel, at least ...
 static constexpr uint64_t kTargetUnits = 8192;  // ... and about this many units per call
 static constexpr int kFlatWaves = 4;            // waves of a flat workgroup: they share one unit and its LDS counters
+static constexpr uint32_t kWindowsWaves = 1;    // waves of a sliding-window workgroup: 1 or 4 (TXQ_COUNT_WINDOWS_WAVES; DESIGN.md §17: one wave won)
 
 __device__ __forceinline__ uint64_t seg_len(uint64_t n) { return max(kSegMin, (n + kTargetUnits - 1) / kTargetUnits); }
 
@@ -63,6 +65,7 @@ __device__ __forceinline__ uint64_t unit_start(const uint64_t* off, uint32_t nq,
 struct CountOut {
     const uint64_t* values;
     const uint64_t* offsets;  // nq + 1
+    const uint32_t* lens;     // null, or nq lengths: query q owns [offsets[q], offsets[q] + lens[q]) (txq_count_windows on an HIBF)
     const uint32_t* thr;      // nq
     uint64_t* hits;           // [nq][W]
     uint32_t* counts;         // [nq][64 W] or null
@@ -73,8 +76,9 @@ struct CountOut {
 
 // Count values [lo, hi) on the column tile of chunks [c0, c0 + 2^lpk_log2) of IBF f into the workgroup's LDS counters: wave
 // `wave` of `n_waves` takes every n_waves-th pair of steps.  H: hash functions loaded per value (an IBF with fewer repeats its
-// last row).  lo, hi are workgroup-uniform.
-template <int H>
+// last row).  lo, hi are workgroup-uniform.  SUB: the values LEAVE the counters (txq_count_windows): one atomic subtraction per
+// set bit, on the same counters.
+template <int H, bool SUB = false>
 __device__ __forceinline__ void count_values(const IbfDev& f, uint32_t lpk_log2, uint32_t c0, uint32_t chunks, const uint64_t* __restrict__ values,
                                              uint64_t lo, uint64_t hi, uint32_t* lds, uint32_t wave = 0, uint32_t n_waves = 1) {
     const uint32_t lane = threadIdx.x & 63;
@@ -112,7 +116,8 @@ __device__ __forceinline__ void count_values(const IbfDev& f, uint32_t lpk_log2,
             for (int d = 0; d < 4; ++d) {
                 uint32_t m = a[d];
                 while (m) {
-                    atomicAdd(cnt + d * 32 + (uint32_t)__builtin_ctz(m), 1u);
+                    if (SUB) atomicSub(cnt + d * 32 + (uint32_t)__builtin_ctz(m), 1u);
+                    else atomicAdd(cnt + d * 32 + (uint32_t)__builtin_ctz(m), 1u);
                     m &= m - 1u;
                 }
             }
@@ -209,6 +214,69 @@ __global__ __launch_bounds__(64) void count_finish_kernel(CountOut o) {
     }
 }
 
+// ---- flat IBF, sliding windows (txq_count_windows) --------------------------------------------------------------------------
+//
+// Window j owns values [begin[j], begin[j] + len[j]); the windows slide (begin and begin + len do not decrease).  A workgroup
+// of NW waves takes a unit of U consecutive windows and one column tile, and keeps the CURRENT window's counters in LDS:
+// cw_step (txq_count_windows_plan.hpp) says which values enter (added) and which leave (subtracted), or that the counters
+// start from zero.  u32 arithmetic is modular, so the waves add and subtract concurrently; the counters are read behind a
+// barrier, thresholded and written once per (window, word) as count_flat_kernel writes a whole query, and NOT cleared.  A
+// leaving row was read at most one window length ago by the same workgroup: it comes from L2.  The leaving pass starts at
+// wave NW / 2, so that a step of a few values keeps two waves busy, not one twice.  A window is counted by ONE workgroup.
+
+struct WindowsOut {
+    const uint64_t* values;
+    const uint64_t* begin;  // n
+    const uint32_t* len;    // n
+    const uint32_t* thr;    // n
+    uint64_t* hits;         // [n][W]
+    uint32_t* counts;       // [n][64 W] or null
+    uint64_t user_bins;
+    uint64_t n;
+    uint32_t W, word0, U;
+};
+
+template <int H, int NW>
+__global__ __launch_bounds__(64 * NW) void count_windows_kernel(IbfDev f, WindowsOut o, uint32_t lpk_log2, uint32_t n_tiles) {
+    extern __shared__ uint32_t lds[];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t chunks = f.stride == 1 ? 1u : f.stride >> 1;
+    const uint32_t tile = 1u << lpk_log2;
+    const uint32_t lds_words = (chunks < tile ? chunks : tile) * kLdsPitch;
+    const uint64_t n_units = cw_units(o.n, o.U);
+    const size_t W = o.W;
+    for (uint64_t work = blockIdx.x; work < n_units * n_tiles; work += gridDim.x) {
+        const uint64_t u = work / n_tiles;
+        const uint32_t c0 = (uint32_t)(work % n_tiles) << lpk_log2;
+        const uint32_t tcn = chunks - c0 < tile ? chunks - c0 : tile;  // chunks of this tile
+        const uint64_t j0 = cw_unit_first(u, o.U), j1 = cw_unit_last(u, o.U, o.n);
+        uint64_t pb = 0, pe = 0;
+        for (uint64_t j = j0; j < j1; ++j) {
+            const uint64_t b = o.begin[j], e = b + o.len[j];
+            const CwStep st = cw_step(j == j0, pb, pe, b, e);
+            if (st.reset) {  // (the reads of the window before are behind the barrier that ended it)
+                for (uint32_t i = threadIdx.x; i < lds_words; i += 64 * NW) lds[i] = 0;
+                __syncthreads();
+            }
+            count_values<H, false>(f, lpk_log2, c0, chunks, o.values, st.add_lo, st.add_hi, lds, wave, NW);
+            if (st.sub_lo < st.sub_hi) count_values<H, true>(f, lpk_log2, c0, chunks, o.values, st.sub_lo, st.sub_hi, lds, (wave + NW / 2) % NW, NW);
+            __syncthreads();
+            const uint32_t t = o.thr[j];
+            for (uint32_t wl = wave; wl < 2u * tcn; wl += NW) {
+                const uint32_t w = 2u * c0 + wl;
+                if (w >= o.W) break;
+                const uint32_t n = lds[(wl >> 1) * kLdsPitch + (wl & 1u) * 64u + lane];
+                const bool valid = ((uint64_t)(o.word0 + w) << 6) + lane < o.user_bins;
+                const uint64_t hit = __ballot(valid && n >= t);
+                if (lane == 0) o.hits[(size_t)j * W + w] = hit;
+                if (o.counts) o.counts[((size_t)j * W + w) * 64 + lane] = n;
+            }
+            __syncthreads();
+            pb = b, pe = e;
+        }
+    }
+}
+
 // ---- HIBF ---------------------------------------------------------------------------------------------------------------
 
 struct HibfCountView {
@@ -241,7 +309,8 @@ __global__ __launch_bounds__(64) void count_hibf_level_kernel(HibfCountView t, C
         const uint32_t chunks = f.stride == 1 ? 1u : f.stride >> 1;
         uint32_t lpk_log2 = 0;
         while ((1u << lpk_log2) < chunks) ++lpk_log2;
-        count_values<H>(f, lpk_log2, 0, chunks, o.values, o.offsets[q], o.offsets[q + 1], lds);
+        const uint64_t q_lo = o.offsets[q], q_hi = o.lens ? q_lo + o.lens[q] : o.offsets[q + 1];
+        count_values<H>(f, lpk_log2, 0, chunks, o.values, q_lo, q_hi, lds);
         __syncthreads();
         const uint32_t thr = o.thr[q];
         for (uint32_t b0 = 0; b0 < f.bins; b0 += 64) {
@@ -339,6 +408,7 @@ static int count_hibf(Index& ix, CountOut o, hipStream_t s) {
         CountOut c = o;
         c.nq = (uint32_t)std::min(chunk, (size_t)o.nq - q0);
         c.offsets = o.offsets + q0;
+        c.lens = o.lens ? o.lens + q0 : nullptr;
         c.thr = o.thr + q0;
         c.hits = o.hits + q0 * o.W;
         c.counts = o.counts ? o.counts + q0 * row : nullptr;
@@ -376,6 +446,58 @@ int count_device(Index& ix, const uint64_t* d_values, const uint64_t* d_offsets,
     o.W = (uint32_t)ix.shard_words;
     o.word0 = (uint32_t)ix.shard_word0;
     return ix.is_hibf ? count_hibf(ix, o, s) : count_flat(ix, o, s);
+}
+
+static int count_windows_flat(Index& ix, WindowsOut o, hipStream_t s) {
+    const IbfDev& f = ix.ibf[0];
+    const uint32_t chunks = f.stride == 1 ? 1u : f.stride >> 1;
+    uint32_t lpk_log2 = 0;
+    while ((1u << lpk_log2) < std::min(chunks, kTileChunks)) ++lpk_log2;
+    const uint32_t n_tiles = (chunks + kTileChunks - 1) / kTileChunks;
+    const size_t lds = (size_t)std::min(chunks, 1u << lpk_log2) * kLdsPitch * 4;
+    o.U = env_u32("TXQ_COUNT_WINDOWS_UNIT", kCountWindowsUnitDefault, 1, kCountWindowsUnitMax);
+    const uint32_t waves = env_u32("TXQ_COUNT_WINDOWS_WAVES", kWindowsWaves, 1, 4) >= 4 ? 4 : 1;
+    const unsigned grid = (unsigned)std::min<uint64_t>(cw_units(o.n, o.U) * n_tiles, (uint64_t)kCountGrid * 4);
+    const bool ok = with_hash_funs(f.hash_funs, [&](auto h) {
+        if (waves == 4) count_windows_kernel<decltype(h)::value, 4><<<grid, 256, lds, s>>>(f, o, lpk_log2, n_tiles);
+        else count_windows_kernel<decltype(h)::value, 1><<<grid, 64, lds, s>>>(f, o, lpk_log2, n_tiles);
+    });
+    if (!ok) return fail(TXQ_ERR_ARG, "hash_funs outside 1..5");
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "count windows kernel launch");
+    return TXQ_OK;
+}
+
+int count_windows_device(Index& ix, const uint64_t* d_values, const uint64_t* d_begin, const uint32_t* d_len, size_t n_windows,
+                         const uint32_t* d_thr, uint64_t* d_hits, uint32_t* d_counts, hipStream_t s) {
+    if (n_windows == 0 || ix.shard_words == 0) return TXQ_OK;
+    if (ix.is_hibf) {  // the windows as independent queries: each (window, IBF) pair counted in full by one wave, no sliding
+        CountOut o{};
+        o.values = d_values;
+        o.offsets = d_begin;
+        o.lens = d_len;
+        o.thr = d_thr;
+        o.hits = d_hits;
+        o.counts = d_counts;
+        o.acc = d_counts;
+        o.user_bins = ix.user_bins;
+        o.nq = (uint32_t)n_windows;
+        o.W = (uint32_t)ix.shard_words;
+        o.word0 = (uint32_t)ix.shard_word0;
+        return count_hibf(ix, o, s);
+    }
+    WindowsOut o{};
+    o.values = d_values;
+    o.begin = d_begin;
+    o.len = d_len;
+    o.thr = d_thr;
+    o.hits = d_hits;
+    o.counts = d_counts;
+    o.user_bins = ix.user_bins;
+    o.n = n_windows;
+    o.W = (uint32_t)ix.shard_words;
+    o.word0 = (uint32_t)ix.shard_word0;
+    return count_windows_flat(ix, o, s);
 }
 
 }  // namespace txq

@@ -354,6 +354,9 @@ int hibf_layout_to_user(const Index& ix, const uint64_t* d_rows, size_t n, uint6
 // txq_count.hip: threshold membership of n_queries value sets (include/txq.h txq_count_device; arguments checked by the caller)
 int count_device(Index& ix, const uint64_t* d_values, const uint64_t* d_offsets, size_t n_queries, const uint32_t* d_thr,
                  uint64_t* d_hits, uint32_t* d_counts, hipStream_t s);
+// the same of n_windows sliding windows [d_begin[j], d_begin[j] + d_len[j]) (txq_count_windows_device)
+int count_windows_device(Index& ix, const uint64_t* d_values, const uint64_t* d_begin, const uint32_t* d_len, size_t n_windows,
+                         const uint32_t* d_thr, uint64_t* d_hits, uint32_t* d_counts, hipStream_t s);
 
 // txq_exec.hip
 int run_programs(Index& ix, const void* blob, size_t blob_bytes, size_t n_programs, uint64_t* d_final, hipStream_t s);
