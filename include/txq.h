@@ -247,6 +247,32 @@ int txq_translate_device(const uint8_t* d_seq, const uint64_t* d_rec_offsets, si
 int txq_translate(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_records, unsigned k, const uint8_t* codes,
                   uint64_t* values, uint64_t* offsets);
 
+/* The same translation, and the frames cut into windows (`tetrex search --translate --frame-window`; not in the
+ * reference).  Records, frames, genetic code and values are those of txq_translate above: d_values and d_offsets come out
+ * exactly as txq_translate_device writes them.  A frame of R = floor((L - o) / 3) residues is cut like a record of R letters
+ * under `tetrex search --window`: no window where R < k; one, [0, R), where R <= window; otherwise [a, a + window) at a = 0,
+ * step, 2 step, ... while a + window <= R, and one more at R - window where the last of these ends before R.  window and step
+ * count residues.  The windows of frame q = 6 r + f are d_win_offsets[q] .. d_win_offsets[q + 1] (6 n_records + 1 entries, the
+ * first 0).  Window [a, a + l) owns the frame's stop-free k-mers at residue positions a .. a + l - k, which are consecutive
+ * values: d_win_begin[j] is the index of the first of them in d_values (where there is none: the index of the frame's first
+ * value behind position a, d_offsets[q + 1] at the latest) and d_win_len[j] their number, which may be 0.
+ * Sliding order: over the whole array d_win_begin does not decrease and d_win_begin + d_win_len does not decrease — within a
+ * frame because the windows ascend, from frame to frame because the frames' values follow each other — so d_values,
+ * d_win_begin and d_win_len are what txq_count_windows_device takes, unchanged, for any range of windows.
+ * txq_translate_windows_bound is the exact number of windows (no GPU needed; UINT64_MAX: bad arguments): d_win_begin and
+ * d_win_len must hold that many entries.  k outside 1..12, window < k, step outside 1..window and null pointers: TXQ_ERR_ARG,
+ * and nothing is written.  A call may produce at most 2^32 - 2 windows: txq_translate_windows refuses more (TXQ_ERR_ARG);
+ * txq_translate_windows_device cannot see the record lengths, so its caller asks txq_translate_windows_bound.  The device
+ * call is deterministic, allocates nothing outside the library's stream-ordered scratch, reads nothing back and does not
+ * synchronise with the host.  Thresholds are the caller's: they follow from d_win_len.  txq_translate_windows is the
+ * synchronous twin on host buffers (it checks the record offsets). */
+uint64_t txq_translate_windows_bound(const uint64_t* rec_offsets, size_t n_records, unsigned k, uint32_t window, uint32_t step);
+int txq_translate_windows_device(const uint8_t* d_seq, const uint64_t* d_rec_offsets, size_t n_records, unsigned k, const uint8_t* d_codes,
+                                 uint32_t window, uint32_t step, uint64_t* d_values, uint64_t* d_offsets, uint64_t* d_win_offsets,
+                                 uint64_t* d_win_begin, uint32_t* d_win_len, void* stream);
+int txq_translate_windows(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_records, unsigned k, const uint8_t* codes, uint32_t window,
+                          uint32_t step, uint64_t* values, uint64_t* offsets, uint64_t* win_offsets, uint64_t* win_begin, uint32_t* win_len);
+
 /* The six frames of nucleotide records as residue letters (`tetrex search --translate --verify-frames`; not in
  * the reference).  Records, letters, frames and the genetic code are those of txq_translate above; a frame with offset o over
  * L bytes has floor((L - o) / 3) residues (none where L < o), upper-case letters of NCBI table 1, '*' for a stop, 'X' for a

@@ -23,7 +23,8 @@ SYMBOLS = [
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
     "txq_count_windows", "txq_count_windows_device",
-    "txq_translate_bound", "txq_translate_device", "txq_translate", "txq_translate_frames_bound", "txq_translate_frames_device", "txq_translate_frames",
+    "txq_translate_bound", "txq_translate_device", "txq_translate",
+    "txq_translate_windows_bound", "txq_translate_windows_device", "txq_translate_windows", "txq_translate_frames_bound", "txq_translate_frames_device", "txq_translate_frames",
     "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
     "txq_edit_search_long", "txq_edit_search_long_device", "txq_edit_align", "txq_edit_align_device",
     "txq_edit_targets", "txq_edit_targets_device", "txq_edit_targets_long", "txq_edit_targets_long_device",
@@ -89,6 +90,11 @@ def lib():
         L.txq_translate_bound.argtypes = [u64p, C.c_size_t, C.c_uint]
         L.txq_translate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.txq_translate.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_uint, C.c_void_p, u64p, u64p]
+        L.txq_translate_windows_bound.restype = C.c_uint64
+        L.txq_translate_windows_bound.argtypes = [u64p, C.c_size_t, C.c_uint, C.c_uint32, C.c_uint32]
+        L.txq_translate_windows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.txq_translate_windows.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_uint, C.c_void_p, C.c_uint32, C.c_uint32, u64p, u64p, u64p, u64p, u32p]
         L.txq_translate_frames_bound.restype = C.c_uint64
         L.txq_translate_frames_bound.argtypes = [u64p, C.c_size_t]
         L.txq_translate_frames_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
@@ -567,6 +573,46 @@ def translate(records, k, codes):
     check(lib().txq_translate(seq.ctypes.data, rec.ctypes.data_as(u64p), n, k, codes.ctypes.data, values.ctypes.data_as(u64p),
                               offsets.ctypes.data_as(u64p)))
     return values[:int(offsets[-1])], offsets
+
+
+def translate_windows_bound(rec_offsets, k, window, step):
+    """txq_translate_windows_bound: how many windows txq_translate_windows* cut the six frames of these records into (no GPU
+    needed).  window and step count residues; window < k or step outside 1..window raise."""
+    o = np.ascontiguousarray(rec_offsets, dtype=np.uint64)
+    if not (0 <= int(window) <= 0xFFFFFFFF and 0 <= int(step) <= 0xFFFFFFFF):
+        raise TxqError(-1, "translate_windows_bound: window and step must fit 32 bits")
+    b = lib().txq_translate_windows_bound(o.ctypes.data_as(u64p), max(o.size - 1, 0), k, int(window), int(step))
+    if b == 0xFFFFFFFFFFFFFFFF:
+        raise TxqError(-1, lib().txq_last_error().decode(errors="replace"))
+    return int(b)
+
+
+def translate_windows(records, k, codes, window, step):
+    """Six-frame translation and the frames cut into windows of `window` residues, `step` apart, on the GPU
+    (txq_translate_windows).  records and codes as for translate().  Returns (values, offsets, win_offsets, begins, lens):
+    values and offsets are translate()'s; the windows of query 6 r + f are win_offsets[6 r + f] .. win_offsets[6 r + f + 1],
+    window j owns values[begins[j]:begins[j] + lens[j]] — the form Index.count_windows takes."""
+    seq, rec = records if isinstance(records, tuple) else _records(records)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    rec = np.ascontiguousarray(rec, dtype=np.uint64)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    n = rec.size - 1
+    if n < 0 or codes.size != 256 or (n and int(rec[-1]) > seq.size):
+        raise TxqError(-1, "translate_windows: offsets, bytes and code table disagree")
+    if not (0 <= int(window) <= 0xFFFFFFFF and 0 <= int(step) <= 0xFFFFFFFF):
+        raise TxqError(-1, "translate_windows: window and step must fit 32 bits")
+    bound = lib().txq_translate_bound(rec.ctypes.data_as(u64p), n, k)
+    n_win = lib().txq_translate_windows_bound(rec.ctypes.data_as(u64p), n, k, int(window), int(step))
+    bad = 0xFFFFFFFFFFFFFFFF
+    values = np.zeros(0 if bound == bad else bound, dtype=np.uint64)
+    offsets = np.zeros(6 * n + 1, dtype=np.uint64)
+    win_offsets = np.zeros(6 * n + 1, dtype=np.uint64)
+    begins = np.zeros(0 if n_win == bad else n_win, dtype=np.uint64)
+    lens = np.zeros(begins.size, dtype=np.uint32)
+    check(lib().txq_translate_windows(seq.ctypes.data, rec.ctypes.data_as(u64p), n, k, codes.ctypes.data, int(window), int(step),
+                                      values.ctypes.data_as(u64p), offsets.ctypes.data_as(u64p), win_offsets.ctypes.data_as(u64p),
+                                      begins.ctypes.data_as(u64p), lens.ctypes.data_as(u32p)))
+    return values[:int(offsets[-1])], offsets, win_offsets, begins, lens
 
 
 def translate_frames_bound(rec_offsets):

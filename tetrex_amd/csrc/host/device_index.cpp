@@ -5,6 +5,7 @@
 #include "matcher.hpp"
 #include "regex_front.hpp"
 #include "../../../include/txq_regex.h"
+#include "../txq_frame_windows_plan.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -855,6 +856,125 @@ void DeviceIndex::search_windows(const std::vector<uint64_t>& values, const std:
                          (unsigned long long)v1, (unsigned long long)total);
         const uint32_t bin0 = (uint32_t)(info_.shard_word0 * 64);
         for (uint64_t i = 0; i < total; ++i) hits.push_back(TranslatedHit{(uint32_t)first + list[3 * i], bin0 + list[3 * i + 1], list[3 * i + 2]});
+    }
+}
+
+void DeviceIndex::search_translated_windows(std::string_view seq, const std::vector<uint64_t>& rec_offsets, uint32_t window, uint32_t step,
+                                            const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts,
+                                            std::vector<uint64_t>& win_offsets, std::vector<uint32_t>& lens, std::vector<uint32_t>& thresholds,
+                                            std::vector<TranslatedHit>& hits) {
+    if (!ix_) throw std::runtime_error("index not uploaded");
+    if (shards_.size() > 1) throw std::runtime_error("search_translated_windows: one shard only");
+    if (enc_.molecule() != Molecule::Peptide) throw std::runtime_error("search_translated_windows: a peptide index is needed");
+    if (rec_offsets.empty() || rec_offsets.back() > seq.size()) throw std::runtime_error("search_translated_windows: record offsets run past the bytes");
+    const unsigned k = enc_.k();
+    if (window < k || step < 1 || step > window) throw std::runtime_error("search_translated_windows: the window must hold a k-mer and the step lie in 1 .. window");
+    const size_t R = rec_offsets.size() - 1, W = info_.shard_words;
+    // the window layout is closed-form in the record lengths (txq_frame_windows_plan.hpp): the device writes the same offsets
+    win_offsets.assign(6 * R + 1, 0);
+    for (size_t r = 0; r < R; ++r) {
+        if (rec_offsets[r + 1] < rec_offsets[r]) throw std::runtime_error("search_translated_windows: record offsets descend");
+        for (uint32_t f = 0; f < 6; ++f)
+            win_offsets[6 * r + f + 1] = win_offsets[6 * r + f] + txq::fw::window_count(txq::tr::frame_len(rec_offsets[r + 1] - rec_offsets[r], f % 3), k, window, step);
+    }
+    const uint64_t N = win_offsets.back();
+    if (N > 0xFFFFFFFEull) throw std::runtime_error("search_translated_windows: more than 2^32 - 2 windows in one call");
+    lens.assign(N, 0);
+    thresholds.assign(N, 0);
+    hits.clear();
+    if (R == 0 || W == 0 || N == 0) return;
+    const uint64_t max_values = (uint64_t)1 << 24;
+    size_t max_windows = std::max<size_t>(1, ((size_t)256 << 20) / (W * (with_counts ? 64 * 4 : 8)));
+    if (const char* e = std::getenv("TETREX_SEARCH_BATCH_WINDOWS"); e && *e) max_windows = std::min<size_t>(max_windows, std::max<long long>(1, std::atoll(e)));
+    const bool trace = std::getenv("TETREX_TRACE") != nullptr;
+    // the record batches [cut[i], cut[i + 1]): at most 2^24 values by their bound, a larger record alone.  The buffers are sized
+    // for the largest batch before the first one runs, so that no device memory of the call is freed or allocated between
+    // its launches ("Host").
+    std::vector<size_t> cut{0};
+    uint64_t most_values = 0, most_bytes = 0, most_windows = 0;
+    size_t most_records = 0;
+    for (size_t r0 = 0; r0 < R;) {
+        size_t r1 = r0;
+        uint64_t bound = 0;
+        while (r1 < R) {
+            const uint64_t b = txq_translate_bound(rec_offsets.data() + r1, 1, k);
+            if (b == UINT64_MAX) txq_check(TXQ_ERR_ARG, "txq_translate_bound");
+            if (r1 > r0 && bound + b > max_values) break;
+            bound += b;
+            ++r1;
+        }
+        most_values = std::max(most_values, bound);
+        most_bytes = std::max(most_bytes, rec_offsets[r1] - rec_offsets[r0]);
+        most_windows = std::max(most_windows, win_offsets[6 * r1] - win_offsets[6 * r0]);
+        most_records = std::max(most_records, r1 - r0);
+        cut.push_back(r0 = r1);
+    }
+    const size_t sub_windows = (size_t)std::min<uint64_t>(most_windows, max_windows);
+    GrowBuf d_codes, d_seq, d_rec, d_val, d_off, d_woff, d_beg, d_len, d_thr, d_hit, d_cnt, d_list, d_total;
+    txq_check(txq_memcpy_h2d(d_codes.reserve(256), enc_.aa_table().data(), 256), "h2d");
+    d_total.reserve(8);
+    size_t list_cap = (size_t)1 << 20;
+    d_seq.reserve(most_bytes + 16);
+    d_rec.reserve((most_records + 1) * 8);
+    d_val.reserve(most_values * 8 + 8);
+    d_off.reserve((6 * most_records + 1) * 8);
+    d_woff.reserve((6 * most_records + 1) * 8);
+    d_beg.reserve(most_windows * 8 + 8);
+    d_len.reserve(most_windows * 4 + 8);
+    d_thr.reserve(most_windows * 4 + 8);
+    d_hit.reserve(sub_windows * W * 8);
+    if (with_counts) d_cnt.reserve(sub_windows * W * 64 * 4);
+    d_list.reserve(list_cap * 12);
+    std::vector<uint64_t> rebased;
+    std::vector<uint32_t> thr, list;
+    const uint32_t bin0 = (uint32_t)(info_.shard_word0 * 64);
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        const size_t r0 = cut[c], r1 = cut[c + 1], nr = r1 - r0;
+        const uint64_t w0 = win_offsets[6 * r0], nw = win_offsets[6 * r1] - w0;
+        if (nw == 0) continue;
+        const uint64_t first = rec_offsets[r0], bytes = rec_offsets[r1] - first;
+        rebased.assign(rec_offsets.begin() + r0, rec_offsets.begin() + r1 + 1);
+        for (uint64_t& o : rebased) o -= first;
+        txq_check(txq_memcpy_h2d(d_seq.p, seq.data() + first, bytes), "h2d");
+        txq_check(txq_memcpy_h2d(d_rec.p, rebased.data(), rebased.size() * 8), "h2d");
+        txq_check(txq_translate_windows_device((const uint8_t*)d_seq.p, (const uint64_t*)d_rec.p, nr, k, (const uint8_t*)d_codes.p, window, step,
+                                               (uint64_t*)d_val.p, (uint64_t*)d_off.p, (uint64_t*)d_woff.p, (uint64_t*)d_beg.p, (uint32_t*)d_len.p, nullptr),
+                  "txq_translate_windows_device");
+        txq_check(txq_memcpy_d2h(lens.data() + w0, d_len.p, nw * 4), "d2h");
+        thr.assign(nw, 0xFFFFFFFFu);  // (no count reaches it: a window that is not searched has no hits)
+        bool any = false;
+        for (uint64_t j = 0; j < nw; ++j) {
+            const uint64_t w = lens[w0 + j], t = w ? threshold_of(w) : 0;
+            if (t) thresholds[w0 + j] = thr[j] = (uint32_t)std::min<uint64_t>(t, 0xFFFFFFFEull), any = true;
+        }
+        if (!any) continue;
+        txq_check(txq_memcpy_h2d(d_thr.p, thr.data(), nw * 4), "h2d");
+        // sub-ranges of the batch's windows: the begins are absolute in the batch's values, so nothing is sent again
+        for (uint64_t j0 = 0; j0 < nw; j0 += sub_windows) {
+            const size_t n = (size_t)std::min<uint64_t>(sub_windows, nw - j0);
+            bool some = false;
+            for (size_t j = 0; j < n && !some; ++j) some = thr[j0 + j] != 0xFFFFFFFFu;
+            if (!some) continue;
+            txq_check(txq_count_windows_device(ix_, (const uint64_t*)d_val.p, (const uint64_t*)d_beg.p + j0, (const uint32_t*)d_len.p + j0, n,
+                                               (const uint32_t*)d_thr.p + j0, (uint64_t*)d_hit.p, with_counts ? (uint32_t*)d_cnt.p : nullptr, nullptr),
+                      "txq_count_windows_device");
+            uint64_t total = 0;
+            for (;;) {
+                d_list.reserve(list_cap * 12);
+                txq_check(txq_hit_list_device((const uint64_t*)d_hit.p, with_counts ? (const uint32_t*)d_cnt.p : nullptr, n, W, (uint32_t*)d_list.p,
+                                              list_cap, (uint64_t*)d_total.p, nullptr), "txq_hit_list_device");
+                txq_check(txq_memcpy_d2h(&total, d_total.p, 8), "d2h");
+                if (total <= list_cap) break;
+                list_cap = total;  // (the list did not fit: once more with room for all of it)
+            }
+            list.resize(3 * total);
+            if (total) txq_check(txq_memcpy_d2h(list.data(), d_list.p, total * 12), "d2h");
+            if (trace)
+                std::fprintf(stderr, "[tetrex search] frame window batch: records %zu..%zu, windows %llu..%llu, %llu hits\n", r0, r1,
+                             (unsigned long long)(w0 + j0), (unsigned long long)(w0 + j0 + n), (unsigned long long)total);
+            for (uint64_t i = 0; i < total; ++i)
+                hits.push_back(TranslatedHit{(uint32_t)(w0 + j0) + list[3 * i], bin0 + list[3 * i + 1], list[3 * i + 2]});
+        }
     }
 }
 

@@ -133,6 +133,19 @@ class DeviceIndex {
     // (window, bin, count) comes back (txq_hit_list_device), in (window, bin) order.  One shard only.
     void search_windows(const std::vector<uint64_t>& values, const std::vector<uint64_t>& begins, const std::vector<uint32_t>& lens,
                         const std::vector<uint32_t>& thresholds, bool with_counts, std::vector<TranslatedHit>& hits);
+    // `tetrex search --translate --frame-window`: the six frames of nucleotide records cut into windows of
+    // `window` residues, `step` apart, all on the device.  Record r is seq[rec_offsets[r] .. rec_offsets[r+1]); the windows of
+    // its frame f are win_offsets[6 r + f] .. win_offsets[6 r + f + 1] (csrc/txq_frame_windows_plan.hpp gives window j's
+    // residues).  Records are batched as search_translated batches them; a batch is uploaded and one
+    // txq_translate_windows_device call leaves its values and window arrays on the device.  lens[j] — the window's stop-free
+    // k-mers — comes back, thresholds[j] = threshold_of(lens[j]) (0 where lens[j] = 0), a window with threshold 0 is not
+    // searched, and the others are counted by sliding (txq_count_windows_device) over sub-ranges of the batch's windows: at
+    // most 256 MiB of hit words / counts, and TETREX_SEARCH_BATCH_WINDOWS windows where set (for tests: the hits are the same
+    // for every value).  No value is sent twice.  Only the list of (window, bin, count) comes back, in (window, bin) order.
+    // One shard only; flat and hierarchical indexes alike.
+    void search_translated_windows(std::string_view seq, const std::vector<uint64_t>& rec_offsets, uint32_t window, uint32_t step,
+                                   const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& win_offsets,
+                                   std::vector<uint32_t>& lens, std::vector<uint32_t>& thresholds, std::vector<TranslatedHit>& hits);
     // `tetrex query -g`: upload the d-gram index next to the main index (same device, same shard)
     void attach_dgram(const DgramImage& dgram);
     bool has_dgram() const { return aux_ != nullptr; }

@@ -14,9 +14,13 @@
 //   tetrex search --window W [--step S] (-e E | --threshold F) [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (a local search: every record cut into overlapping windows of W letters, S apart, each answered like a record of its own,
 //      slid on the device; the rows say where on the record each bin is hit)
+//   tetrex search --translate --frame-window W [--frame-step S] (-e E | --threshold F) [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//     (the local search in the six frames of nucleotide records: every frame cut into overlapping windows of W residues, S apart,
+//      translated, cut and slid on the device; the rows say in which frame and where on the record, in nucleotides, each bin is hit)
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
 #include "device_index.hpp"
+#include "../txq_frame_windows_plan.hpp"
 #include "fasta.hpp"
 #include "index_file.hpp"
 #include "kgraph.hpp"
@@ -648,6 +652,101 @@ int search_windowed(const Args& a, const IndexImage& image, unsigned long long e
     return 0;
 }
 
+// tetrex search --translate --frame-window W [--frame-step S]: the local search of --window in the six frames
+// of nucleotide records.  A frame of R residues is cut like a record of R letters under --window (W and S count residues); a
+// window is a query of its own with w = its stop-free k-mers — what n_f is to --translate — and t = max(w - k E, 0) or
+// ceil(F w).  A window with t = 0 is not searched and reports nothing; a record none of whose windows is searched gets one
+// note (wrong frames are full of stops: a note per window would be noise), a record with no k-mer in any window the note of
+// --translate.  Translation, the windows' value ranges and the sliding count all stay on the device
+// (DeviceIndex::search_translated_windows); the windows' w and the hit list come back.  Rows: for each (record, frame, bin)
+// every maximal run of consecutive hit windows is one row, name \t bin path \t frame \t begin \t end [\t count/w]: begin and end
+// the 1-based inclusive nucleotide positions of the run's residues on the record as given (begin <= end; the frame carries
+// the strand), count/w those of the run's best window (the highest count, the earliest on a tie); by record, frame
+// (+1 +2 +3 -1 -2 -3), bin, begin.
+int search_translated_windowed(const Args& a, const IndexImage& image, unsigned long long errors, double fraction, uint32_t window, uint32_t step) {
+    const bool verbose = a.has("verbose"), with_counts = a.has("counts"), by_fraction = a.has("threshold");
+    const std::string dest = a.get("output", "-");
+    const double t_start = now();
+    DeviceIndex dev;
+    dev.upload(image, std::atoi(a.get("device", "0").c_str()));
+    const uint64_t k = dev.encoder().k();
+    std::ofstream file;
+    if (dest != "-") {
+        file.open(dest);
+        if (!file) throw std::runtime_error("Failed to open output file: " + dest);
+    }
+    std::ostream& out = dest == "-" ? std::cout : file;
+    static const char* const kFrames[6] = {"+1", "+2", "+3", "-1", "-2", "-3"};
+    const auto threshold_of = [&](uint64_t n) -> uint64_t {
+        if (by_fraction) return (uint64_t)std::ceil(fraction * (double)n);
+        return n > k * errors ? n - k * errors : 0;
+    };
+    // records go to the device in chunks of their bytes (search_translated_windows cuts a chunk into batches of values)
+    const size_t max_bytes = (size_t)64 << 20, max_records = (size_t)1 << 20;
+    std::vector<std::string> names;
+    std::string seq, row;
+    std::vector<uint64_t> rec_offsets{0}, win_offsets;
+    std::vector<uint32_t> lens, thresholds;
+    std::vector<DeviceIndex::TranslatedHit> hits, mine;
+    uint64_t n_searched = 0, n_hit = 0, n_rows = 0;
+    auto flush = [&]() {
+        if (names.empty()) return;
+        dev.search_translated_windows(seq, rec_offsets, window, step, threshold_of, with_counts, win_offsets, lens, thresholds, hits);
+        size_t h = 0;
+        for (size_t r = 0; r < names.size(); ++r) {
+            const uint64_t L = rec_offsets[r + 1] - rec_offsets[r];
+            bool searched = false, any_kmer = false;
+            for (uint64_t j = win_offsets[6 * r]; j < win_offsets[6 * r + 6]; ++j) {
+                searched = searched || thresholds[j] > 0;
+                any_kmer = any_kmer || lens[j] > 0;
+                n_searched += thresholds[j] > 0;
+            }
+            if (!any_kmer)
+                std::cerr << "[tetrex search] " << names[r] << ": no frame with " << k << "-mers enough for a threshold above 0, skipped" << std::endl;
+            else if (!searched)
+                std::cerr << "[tetrex search] " << names[r] << ": no window with a threshold above 0, not searched" << std::endl;
+            for (uint32_t f = 0; f < 6; ++f) {
+                const uint64_t w0 = win_offsets[6 * r + f], w1 = win_offsets[6 * r + f + 1];
+                mine.clear();
+                for (; h < hits.size() && hits[h].query < w1; ++h) mine.push_back(hits[h]);
+                if (mine.empty()) continue;
+                const txq::fw::Frame plan = txq::fw::frame_plan(txq::tr::frame_len(L, f % 3), (uint32_t)k, window, step);
+                for (size_t i = 0; i < mine.size(); ++i) n_hit += i == 0 || mine[i].query != mine[i - 1].query;
+                std::stable_sort(mine.begin(), mine.end(), [](const DeviceIndex::TranslatedHit& x, const DeviceIndex::TranslatedHit& y) { return x.bin < y.bin; });
+                for (size_t i = 0; i < mine.size();) {  // a run: the same bin, windows j, j + 1, ...
+                    size_t e = i + 1, best = i;
+                    while (e < mine.size() && mine[e].bin == mine[i].bin && mine[e].query == mine[e - 1].query + 1) {
+                        if (mine[e].count > mine[best].count) best = e;
+                        ++e;
+                    }
+                    const txq::fw::Window wf = txq::fw::window_at(plan, mine[i].query - w0), wl = txq::fw::window_at(plan, mine[e - 1].query - w0);
+                    const txq::fw::Span at = txq::fw::residues_on_record(L, f, wf.a, wl.a + wl.len);
+                    row.assign(names[r]).append("\t").append(image.bin_paths[mine[i].bin]).append("\t").append(kFrames[f]);
+                    row.append("\t").append(std::to_string(at.begin)).append("\t").append(std::to_string(at.end));
+                    if (with_counts) row.append("\t").append(std::to_string(mine[best].count)).append("/").append(std::to_string(lens[mine[best].query]));
+                    out << row << '\n';
+                    ++n_rows;
+                    i = e;
+                }
+            }
+        }
+        names.clear();
+        seq.clear();
+        rec_offsets.assign(1, 0);
+    };
+    for_each_record(a.pos[1], [&](const FastaRecord& r) {
+        if (!names.empty() && (seq.size() + r.seq.size() > max_bytes || names.size() >= max_records)) flush();
+        names.push_back(r.name);
+        seq.append(r.seq);
+        rec_offsets.push_back(seq.size());
+    });
+    flush();
+    out.flush();
+    if (verbose) std::cerr << "Windows: " << n_searched << " searched, " << n_hit << " hit, " << n_rows << " rows" << std::endl;
+    if (verbose) std::cerr << "Search time: " << (now() - t_start) << " s" << std::endl;
+    return 0;
+}
+
 // tetrex search: each record of the query file is a query; its values are the index's k-mers of the record (n of them) and a
 // bin is reported when at least t of them are in it (txq_count).  -e E: t = max(n - k E, 0) — a record within E edits of a
 // substring of a bin shares at least n - k E k-mer positions with it (q-gram lemma), and a Bloom filter drops none of them,
@@ -660,16 +759,40 @@ int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
                                        {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false},
                                        {'\0', "verify-frames", false}, {'\0', "align", false}, {'\0', "all-targets", false},
-                                       {'\0', "window", true}, {'\0', "step", true}};
+                                       {'\0', "window", true}, {'\0', "step", true}, {'\0', "frame-window", true}, {'\0', "frame-step", true}};
     Args a;
-    unsigned long long errors = 0, window = 0, step = 0;
+    unsigned long long errors = 0, window = 0, step = 0, frame_window = 0, frame_step = 0;
     double fraction = 0;
     try {
         a = parse(argc, argv, 2, spec);
         if (a.pos.size() != 2) throw std::runtime_error("expected <index> <queries.fa>");
         if (a.has("step") && !a.has("window")) throw std::runtime_error("--step is the distance between the windows of --window W: it needs --window");
+        if (a.has("frame-step") && !a.has("frame-window"))
+            throw std::runtime_error("--frame-step is the distance between the windows of --frame-window W: it needs --frame-window");
+        if (a.has("frame-window")) {
+            if (!a.has("translate")) throw std::runtime_error("--frame-window cuts the translated frames of --translate into windows: it needs --translate");
+            if (a.has("window")) throw std::runtime_error("--frame-window cannot be combined with --window: one counts residues of a translated frame, the other letters of the record");
+            if (a.has("step")) throw std::runtime_error("--frame-window cannot be combined with --step: the distance between frame windows is --frame-step");
+            if (a.has("verify-frames")) throw std::runtime_error("--frame-window cannot be combined with --verify-frames: frame windows are not verified in this version");
+            if (a.has("all-targets")) throw std::runtime_error("--frame-window cannot be combined with --all-targets: frame windows are not verified in this version");
+            if (a.has("align")) throw std::runtime_error("--frame-window cannot be combined with --align: frame windows are not verified in this version");
+            if (a.has("verify")) throw std::runtime_error("--frame-window cannot be combined with --verify: frame windows are not verified in this version");
+            if (!a.has("errors") && !a.has("threshold")) throw std::runtime_error("--frame-window needs -e E or --threshold F");
+            const std::string w = a.get("frame-window", "");
+            char* end = nullptr;
+            frame_window = std::strtoull(w.c_str(), &end, 10);
+            if (w.empty() || *end || w[0] == '-' || frame_window == 0 || frame_window > 0x7FFFFFFFull)
+                throw std::runtime_error("--frame-window must be a number of residues >= k");
+            frame_step = std::max<unsigned long long>(1, frame_window / 2);
+            if (a.has("frame-step")) {
+                const std::string s = a.get("frame-step", "");
+                frame_step = std::strtoull(s.c_str(), &end, 10);
+                if (s.empty() || *end || s[0] == '-' || frame_step < 1 || frame_step > frame_window)
+                    throw std::runtime_error("--frame-step must be a number of residues in 1 .. --frame-window");
+            }
+        }
         if (a.has("window")) {
-            if (a.has("translate")) throw std::runtime_error("--window cannot be combined with --translate: translated frames lose their positions where stops are taken out");
+            if (a.has("translate")) throw std::runtime_error("--window cannot be combined with --translate: translated frames lose their positions where stops are taken out (translated records: --frame-window)");
             if (a.has("verify-frames")) throw std::runtime_error("--window cannot be combined with --verify-frames: it confirms translated frames, which --window does not search");
             if (a.has("all-targets")) throw std::runtime_error("--window cannot be combined with --all-targets: windows are not verified in this version");
             if (a.has("align")) throw std::runtime_error("--window cannot be combined with --align: windows are not verified in this version");
@@ -732,6 +855,20 @@ int cmd_search(int argc, char** argv) {
             std::cerr << "[tetrex search] --translate needs a peptide index with k in 1..12: " << a.pos[0] << " is a "
                       << (image.molecule == "na" ? "nucleotide index" : "peptide index with k = " + std::to_string(image.k)) << std::endl;
             return 1;
+        }
+        if (a.has("frame-window")) {
+            const unsigned long long k = image.k;
+            if (frame_window < k) {
+                std::cerr << "[Search Parser Error] --frame-window must be a number of residues >= k: the index has k = " << k << "\n";
+                return 1;
+            }
+            // -e E: a stop-free window has w = W - k + 1 values and t = max(w - k E, 0); with t = 0 no window at all would be searched
+            if (a.has("errors") && (errors > 0xFFFFFFFFull || frame_window - k + 1 <= k * errors)) {
+                std::cerr << "[Search Parser Error] --frame-window " << frame_window << " with -e " << errors << " leaves every window a threshold of 0 (k = "
+                          << k << "): the smallest workable --frame-window is " << (k * errors + k) << "\n";
+                return 1;
+            }
+            return search_translated_windowed(a, image, errors, fraction, (uint32_t)frame_window, (uint32_t)frame_step);
         }
         return search_translated(a, image, errors, fraction);
     }

@@ -24,9 +24,12 @@
 //     that began in an earlier unit, first sums those units' counts.
 // Scratch (6 u32 per unit; the hit list's tile sums) is allocated and freed in stream order by the library.
 // The same pass with the frames as residue letters instead of values (txq_translate_frames*) is frames_kernel below.
+// The fill pass that also cuts every frame into windows and writes each window's range of values (txq_translate_windows*,
+// DESIGN.md §18) is translate_windows_kernel: the same body, instantiated with a compile-time flag.
 #include "../../include/txq.h"
 #include "txq_internal.hpp"
 #include "txq_frames_plan.hpp"
+#include "txq_frame_windows_plan.hpp"
 #include "txq_scan.hpp"
 
 namespace txq {
@@ -52,8 +55,16 @@ struct TrArgs {
     uint32_t* tails;    // kUnits x 6: per unit, the counts (forward j, reverse j) of the record that runs past the unit's end
 };
 
-template <bool FILL>
-__global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
+// what the fill pass writes besides the values when it also cuts the frames into windows (translate_windows_kernel below)
+struct WinArgs {
+    uint32_t window, step;        // residues
+    const uint64_t* win_offsets;  // 6 n + 1, complete
+    uint64_t* begin;              // per window: V(begin boundary), relative to the frame's first value
+    uint32_t* end;                // per window: the low 32 bits of V(end boundary), likewise
+};
+
+template <bool FILL, bool WIN>
+__device__ __forceinline__ void translate_pass(const TrArgs& a, const WinArgs& w) {
     __shared__ __attribute__((aligned(16))) uint8_t raw[kRawBytes];
     __shared__ uint8_t res[2][kResidues];  // residue codes of the codon at t0 + i: forward, reverse-complemented
     __shared__ uint8_t lut[64];            // codon -> residue code of this index, kStop for a stop
@@ -91,6 +102,8 @@ __global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
         // frame of the reverse windows at p = j (mod 3), and where the frames' values go
         uint32_t rframe[3];
         uint64_t fbase[3], rlast[3], run[6];
+        fw::Frame wplan[6];            // (WIN) the windows of forward frame j, of the reverse frame of p = j (mod 3)
+        uint64_t wbase[6], rcount[3];  // (WIN) their first window slots; the value count of that reverse frame
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             rframe[j] = 3u + (uint32_t)((L - span + 3u - (uint32_t)j) % 3u);  // (L - 3k - p) mod 3 for every p = j (mod 3) that fits
@@ -98,6 +111,13 @@ __global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
             if (FILL) {
                 fbase[j] = a.offsets[6 * r + j];
                 rlast[j] = a.offsets[6 * r + rframe[j] + 1] - 1;  // the frame's first codon is its last start position
+            }
+            if (WIN) {
+                wplan[j] = fw::frame_plan(frame_len(L, (uint32_t)j), k, w.window, w.step);
+                wplan[3 + j] = fw::frame_plan(frame_len(L, rframe[j] - 3u), k, w.window, w.step);
+                wbase[j] = w.win_offsets[6 * r + j];
+                wbase[3 + j] = w.win_offsets[6 * r + rframe[j]];
+                rcount[j] = a.offsets[6 * r + rframe[j] + 1] - a.offsets[6 * r + rframe[j]];
             }
         }
         if (FILL && lo > 0) {  // the record began in an earlier unit: the windows those units found
@@ -154,6 +174,18 @@ __global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
                     }
                 }
                 const uint64_t bf = __ballot(okf), br = __ballot(okr);
+                if (WIN && mine) {
+                    // V at this lane's k-mer position in either frame: the rank its value is (or would be) written at, and
+                    // the same counted from the frame's far end.  Each window slot has one owner (txq_frame_windows_plan.hpp).
+                    const uint64_t vfw = run[j] + (uint64_t)__builtin_popcountll(bf & below);
+                    const fw::Slots sf = fw::codon_slots(wplan[j], p / 3);
+                    if (sf.begin != fw::kNone) w.begin[wbase[j] + sf.begin] = vfw;
+                    if (sf.end != fw::kNone) w.end[wbase[j] + sf.end] = (uint32_t)vfw;
+                    const uint64_t vrv = rcount[j] - (run[3 + j] + (uint64_t)__builtin_popcountll(br & below) + (okr ? 1u : 0u));
+                    const fw::Slots sr = fw::codon_slots(wplan[3 + j], fw::rev_kmer_index(L, p, k));
+                    if (sr.begin != fw::kNone) w.begin[wbase[3 + j] + sr.begin] = vrv;
+                    if (sr.end != fw::kNone) w.end[wbase[3 + j] + sr.end] = (uint32_t)vrv;
+                }
                 if (FILL) {
                     if (okf) a.values[fbase[j] + run[j] + (uint64_t)__builtin_popcountll(bf & below)] = vf;
                     if (okr) a.values[rlast[j] - run[3 + j] - (uint64_t)__builtin_popcountll(br & below)] = vr;
@@ -180,6 +212,50 @@ __global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
         for (int c = 0; c < 6; ++c)
             if (lane == (uint32_t)c) mine = cnt[c];
         a.tails[(uint64_t)blockIdx.x * 6 + lane] = runs_on ? mine : 0u;
+    }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(64) void translate_kernel(TrArgs a) {
+    translate_pass<FILL, false>(a, WinArgs{});
+}
+
+// ---- windows of the frames ------------------------------------------------------------------------------------------------
+// txq_translate_windows_device: the fill pass once more, and while a lane holds the rank of its k-mer position
+// it stores that rank into the window slots the position bounds.  The number of windows of a frame is closed-form in L
+// (window_counts_kernel, then scan_kernel); a window's begin and end may be written by different waves, so the pass writes
+// them relative to the frame and window_finish_kernel turns them into (first value, value count) afterwards.
+__global__ __launch_bounds__(64) void translate_windows_kernel(TrArgs a, WinArgs w) {
+    translate_pass<true, true>(a, w);
+}
+
+__global__ __launch_bounds__(256) void window_counts_kernel(const uint64_t* __restrict__ rec, uint64_t n, uint32_t k, uint32_t window, uint32_t step,
+                                                            uint64_t* __restrict__ win_offsets) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r == 0) win_offsets[0] = 0;
+    if (r >= n) return;
+    const uint64_t L = rec[r + 1] - rec[r];
+#pragma unroll
+    for (uint32_t f = 0; f < 6; ++f) win_offsets[1 + 6 * r + f] = fw::window_count(frame_len(L, f % 3), k, window, step);
+}
+
+constexpr uint32_t kFinishBlocks = 1024;
+// window j of frame q: begin[j] = offsets[q] + V(begin boundary), len[j] = V(end boundary) - V(begin boundary); the end
+// boundary of the frame's last window is the frame's end, which no start position owns: V there is the frame's value count
+__global__ __launch_bounds__(256) void window_finish_kernel(const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ win_offsets, uint64_t m,
+                                                            uint64_t* __restrict__ begin, uint32_t* __restrict__ len) {
+    const uint64_t total = win_offsets[m];
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < total; j += (uint64_t)kFinishBlocks * 256) {
+        uint64_t lo = 0, hi = m;  // the frame q with win_offsets[q] <= j < win_offsets[q + 1]
+        while (hi - lo > 1) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (win_offsets[mid] <= j) lo = mid;
+            else hi = mid;
+        }
+        const uint64_t b = begin[j];
+        const uint32_t e = j + 1 == win_offsets[lo + 1] ? (uint32_t)(offsets[lo + 1] - offsets[lo]) : len[j];
+        begin[j] = offsets[lo] + b;
+        len[j] = e - (uint32_t)b;
     }
 }
 
@@ -427,6 +503,91 @@ int txq_translate(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_reco
         else d.download(values, s_val, offsets[m] * 8);
     }
     if (d.error() != hipSuccess) return fail_hip(d.error(), "txq_translate copies");
+    return rc;
+}
+
+uint64_t txq_translate_windows_bound(const uint64_t* rec_offsets, size_t n_records, unsigned k, uint32_t window, uint32_t step) {
+    if (k < 1 || k > kMaxK || (n_records && !rec_offsets) || window < k || step < 1 || step > window) {
+        (void)fail(TXQ_ERR_ARG, "txq_translate_windows_bound: null offsets, k outside 1..12, window below k or step outside 1..window");
+        return UINT64_MAX;
+    }
+    if (check_ascending(rec_offsets, n_records, "record")) return UINT64_MAX;
+    uint64_t bound = 0;
+    for (size_t r = 0; r < n_records; ++r)
+        for (uint32_t o = 0; o < 3; ++o) bound += 2 * fw::window_count(frame_len(rec_offsets[r + 1] - rec_offsets[r], o), k, window, step);
+    return bound;
+}
+
+int txq_translate_windows_device(const uint8_t* d_seq, const uint64_t* d_rec_offsets, size_t n_records, unsigned k, const uint8_t* d_codes,
+                                 uint32_t window, uint32_t step, uint64_t* d_values, uint64_t* d_offsets, uint64_t* d_win_offsets,
+                                 uint64_t* d_win_begin, uint32_t* d_win_len, void* stream) {
+    if (int rc = translate_args(d_seq, d_rec_offsets, n_records, k, d_codes, d_values, d_offsets)) return rc;
+    if (window < k || step < 1 || step > window) return fail(TXQ_ERR_ARG, "window = %u, step = %u: windows need window >= k and step in 1..window", window, step);
+    if (!d_win_offsets || (n_records && (!d_win_begin || !d_win_len))) return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = require_init()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t m = 6 * n_records;
+    hipError_t e = hipMemsetAsync(d_offsets, 0, (m + 1) * 8, st);
+    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
+    if (n_records == 0) {
+        e = hipMemsetAsync(d_win_offsets, 0, 8, st);
+        return e == hipSuccess ? TXQ_OK : fail_hip(e, "hipMemsetAsync");
+    }
+    void* tails = nullptr;
+    if (e = hipMallocAsync(&tails, (size_t)kUnits * 6 * 4, st); e != hipSuccess) return fail_hip(e, "hipMallocAsync");
+    const TrArgs a{d_seq, d_rec_offsets, (uint64_t)n_records, k, d_codes, d_values, d_offsets, (uint32_t*)tails};
+    const WinArgs w{window, step, d_win_offsets, d_win_begin, d_win_len};
+    translate_kernel<false><<<kUnits, 64, 0, st>>>(a);
+    scan_kernel<<<1, 1024, 0, st>>>(d_offsets + 1, m);
+    window_counts_kernel<<<(unsigned)((n_records + 255) / 256), 256, 0, st>>>(d_rec_offsets, (uint64_t)n_records, k, window, step, d_win_offsets);
+    scan_kernel<<<1, 1024, 0, st>>>(d_win_offsets + 1, m);
+    translate_windows_kernel<<<kUnits, 64, 0, st>>>(a, w);
+    window_finish_kernel<<<kFinishBlocks, 256, 0, st>>>(d_offsets, d_win_offsets, (uint64_t)m, d_win_begin, d_win_len);
+    e = hipGetLastError();
+    const hipError_t ef = hipFreeAsync(tails, st);
+    if (e != hipSuccess) return fail_hip(e, "translate windows kernel launch");
+    if (ef != hipSuccess) return fail_hip(ef, "hipFreeAsync");
+    return TXQ_OK;
+}
+
+int txq_translate_windows(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_records, unsigned k, const uint8_t* codes, uint32_t window,
+                          uint32_t step, uint64_t* values, uint64_t* offsets, uint64_t* win_offsets, uint64_t* win_begin, uint32_t* win_len) {
+    if (int rc = translate_args(seq, rec_offsets, n_records, k, codes, values, offsets)) return rc;
+    if (!win_offsets) return fail(TXQ_ERR_ARG, "null argument");
+    const uint64_t bound = txq_translate_bound(rec_offsets, n_records, k);
+    if (bound == UINT64_MAX) return TXQ_ERR_ARG;
+    const uint64_t n_win = txq_translate_windows_bound(rec_offsets, n_records, k, window, step);
+    if (n_win == UINT64_MAX) return TXQ_ERR_ARG;
+    if (n_win > 0xFFFFFFFEull) return fail(TXQ_ERR_ARG, "%llu windows: at most 2^32 - 2 per call", (unsigned long long)n_win);
+    const uint64_t first = n_records ? rec_offsets[0] : 0, bytes = n_records ? rec_offsets[n_records] - first : 0;
+    if ((bytes && !seq) || (bound && !values) || (n_win && (!win_begin || !win_len))) return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = require_init()) return rc;
+    const size_t m = 6 * n_records;
+    DeviceStage d;  // (+16: the kernels' 16-byte loads of the sequence end inside the slice; +8: no slice of no bytes)
+    const size_t s_seq = d.add(bytes + 16), s_rec = d.add((n_records + 1) * 8), s_codes = d.add(256), s_off = d.add((m + 1) * 8), s_val = d.add(bound * 8 + 8);
+    const size_t s_woff = d.add((m + 1) * 8), s_wbeg = d.add(n_win * 8 + 8), s_wlen = d.add(n_win * 4 + 8);
+    if (const hipError_t e = d.alloc(); e != hipSuccess) return fail_hip(e, "hipMalloc");
+    const std::vector<uint64_t> ro = rebased(rec_offsets, n_records);
+    d.upload(s_seq, seq + first, bytes);
+    d.upload(s_rec, ro.data(), ro.size() * 8);
+    d.upload(s_codes, codes, n_records ? 256 : 0);
+    int rc = TXQ_OK;
+    if (d.error() == hipSuccess)
+        rc = txq_translate_windows_device(d.at<uint8_t>(s_seq), d.at<uint64_t>(s_rec), n_records, k, d.at<uint8_t>(s_codes), window, step, d.at<uint64_t>(s_val),
+                                          d.at<uint64_t>(s_off), d.at<uint64_t>(s_woff), d.at<uint64_t>(s_wbeg), d.at<uint32_t>(s_wlen), nullptr);
+    if (rc == TXQ_OK) d.download(offsets, s_off, (m + 1) * 8);  // (waits for the kernels)
+    if (rc == TXQ_OK && d.error() == hipSuccess) d.download(win_offsets, s_woff, (m + 1) * 8);
+    if (rc == TXQ_OK && d.error() == hipSuccess) {
+        if (offsets[m] > bound || win_offsets[m] != n_win) rc = fail(TXQ_ERR_OVERFLOW, "translation produced more values or other windows than its bounds");
+        else {
+            if (offsets[m]) d.download(values, s_val, offsets[m] * 8);
+            if (n_win) {
+                d.download(win_begin, s_wbeg, n_win * 8);
+                d.download(win_len, s_wlen, n_win * 4);
+            }
+        }
+    }
+    if (d.error() != hipSuccess) return fail_hip(d.error(), "txq_translate_windows copies");
     return rc;
 }
 
