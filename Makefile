@@ -15,7 +15,8 @@ HIP_HDRS := $(wildcard $(CSRC)/*.hpp) include/txq.h include/txq_program.h includ
 
 HOST_DIR  := $(CSRC)/host
 HOST_SRCS := $(HOST_DIR)/encoder.cpp $(HOST_DIR)/regex_front.cpp $(HOST_DIR)/kgraph.cpp $(HOST_DIR)/compiler.cpp $(HOST_DIR)/staged.cpp $(HOST_DIR)/index_file.cpp $(HOST_DIR)/layout.cpp $(HOST_DIR)/matcher.cpp $(HOST_DIR)/host_capi.cpp
-CLI_SRCS  := $(HOST_DIR)/main.cpp $(HOST_DIR)/device_index.cpp $(HOST_DIR)/verify.cpp $(HOST_DIR)/fasta.cpp
+CLI_SRCS  := $(HOST_DIR)/main.cpp $(HOST_DIR)/search_cmd.cpp $(HOST_DIR)/device_index.cpp $(HOST_DIR)/index_build.cpp $(HOST_DIR)/search_device.cpp \
+             $(HOST_DIR)/bin_verifier.cpp $(HOST_DIR)/record_filter.cpp $(HOST_DIR)/verify.cpp $(HOST_DIR)/fasta.cpp
 # (the verification matcher, matcher.cpp, is part of the host library so that tests can reach it through txh_regex_find_all)
 HOST_HDRS := $(wildcard $(HOST_DIR)/*.hpp) include/txh.h include/txq_program.h include/txq_regex.h \
              $(CSRC)/txq_frame_windows_plan.hpp $(CSRC)/txq_frames_plan.hpp $(CSRC)/txq_text.hpp $(CSRC)/txq_records.hpp
@@ -23,8 +24,8 @@ HOSTFLAGS := -O2 -g -std=c++20 -fPIC -Wall -Wextra -Wno-unknown-pragmas -pthread
 
 all: tetrex_amd/libtxq.so tetrex_amd/libtetrex_host.so tetrex_amd/libtetrex_query.so bin/tetrex oracle/liboracle.so
 
-# whole-query execution on a GPU-resident index (host front-end + libtxq session), for bindings
-QUERY_SRCS := $(HOST_DIR)/query_capi.cpp $(HOST_DIR)/device_index.cpp $(HOST_DIR)/fasta.cpp
+# whole-query execution on a GPU-resident index (host front-end + libtxq session), for bindings: what query_capi.cpp reaches
+QUERY_SRCS := $(HOST_DIR)/query_capi.cpp $(HOST_DIR)/device_index.cpp $(HOST_DIR)/index_build.cpp $(HOST_DIR)/fasta.cpp
 tetrex_amd/libtetrex_query.so: $(QUERY_SRCS) $(HOST_SRCS) $(HOST_HDRS) tetrex_amd/libtxq.so tetrex_amd/libtetrex_host.so
 	$(CXX) $(HOSTFLAGS) -shared -o $@ $(QUERY_SRCS) -Ltetrex_amd -ltetrex_host -ltxq -lz \
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib -Wl,--enable-new-dtags

@@ -1,4 +1,4 @@
-"""Python restatement of `tetrex search --translate --frame-window W [--frame-step S]` (csrc/host/main.cpp
+"""Python restatement of `tetrex search --translate --frame-window W [--frame-step S]` (csrc/host/search_cmd.cpp
 search_translated_windowed, include/txq.h txq_translate_windows), on top of tests/translate_ref.py (frames,
 genetic code, values) and tests/search_window_ref.py (how R letters are cut into windows, thresholds).
 

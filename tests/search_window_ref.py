@@ -1,4 +1,4 @@
-"""Python restatement of the host side of `tetrex search --window W [--step S]` (csrc/host/main.cpp search_windowed; DESIGN.md
+"""Python restatement of the host side of `tetrex search --window W [--step S]` (csrc/host/search_cmd.cpp search_windowed, whose window layout and run merge are csrc/host/search_plan.hpp's; DESIGN.md
 §17): how a record is cut into windows, what a window's threshold is, and how the hit windows of a (record, bin) become rows.
 Positions are letters; a window of l letters has w = l - k + 1 values, value i being the k-mer that starts at letter i."""
 import math

@@ -57,7 +57,7 @@ def sketch_slices(n):
 
 
 def chunk_csr(flat, offsets, g0, g1):
-    """Values [g0, g1) of a CSR array as a chunk of its own over all bins (device_index.cpp upload_chunk):
+    """Values [g0, g1) of a CSR array as a chunk of its own over all bins (index_build.cpp upload_chunk):
     offsets[b] = clamp(offsets[b], g0, g1) - g0.  Returns (values, offsets, n_values)."""
     offs = np.asarray(offsets, dtype=np.uint64)
     return flat[g0:g1], np.clip(offs, _U(g0), _U(g1)) - _U(g0), g1 - g0
@@ -156,7 +156,7 @@ def total_bits(ibfs):
 
 
 def uniform_bits(counts, fpr=0.05):
-    """Bits of the uniform two-level tree `tetrex index` writes by default (device_index.cpp build_index) for bins of
+    """Bits of the uniform two-level tree `tetrex index` writes by default (index_build.cpp build_index) for bins of
     these sizes: a child of 64 * ceil(ceil(B / t_max) / 64) user bins each, every child with the rows of the largest
     bin, the root sized by its largest merged bin."""
     def bitcount(n):

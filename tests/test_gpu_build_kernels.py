@@ -106,7 +106,7 @@ def test_sketch_counts_only_values_below_n_values(capi, cut):
 
 def test_sketch_does_not_depend_on_the_chunking(capi):
     """One CSR of 12 bins (empty first, middle and last; 1 value; 40 000 values) sketched in one call and as three chunks cut
-    as device_index.cpp upload_chunk cuts them (chunk_csr), the registers zeroed before the first only: narrow_kernel's max
+    as index_build.cpp upload_chunk cuts them (chunk_csr), the registers zeroed before the first only: narrow_kernel's max
     with what earlier chunks left, a bin cut in the middle (twice), bins empty in a chunk.  Repeating the last chunk changes
     nothing."""
     rng = np.random.default_rng(23)
@@ -336,7 +336,7 @@ def test_tree_insert_ignores_values_outside_every_bin(capi, tree):
 
 
 def test_tree_insert_does_not_depend_on_the_chunking(capi, tree):
-    """The library as three chunks cut as device_index.cpp upload_chunk cuts them (two bins cut in the middle, bins empty in a
+    """The library as three chunks cut as index_build.cpp upload_chunk cuts them (two bins cut in the middle, bins empty in a
     chunk), each call ORing into the words the one before left; then the last chunk once more."""
     bins, want = tree
     flat, offsets = _csr(bins)

@@ -165,7 +165,7 @@ def test_megabyte_records_with_quantifier_motifs(tmp_path):
 
 
 def test_hibf_written_by_tetrex_index_takes_the_fused_tree_steps(tmp_path):
-    """`tetrex index` deals the user bins over word-aligned children of equal rows (host/device_index.cpp), so the device
+    """`tetrex index` deals the user bins over word-aligned children of equal rows (host/index_build.cpp), so the device
     recognises the tree as regular with uniform children and runs wildcard motifs as fused dense steps on the
     interleaved children.  The verified matches equal those found through a flat IBF of the same bins."""
     import json

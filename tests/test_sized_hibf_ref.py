@@ -1,6 +1,6 @@
 """The helpers of tests/sized_hibf_ref.py that tests/test_gpu_build_kernels.py builds its inputs with, checked on the CPU:
 the inverse of the hash, values crafted for a register and a rank, the slices sketch_kernel cuts a bin into and the chunk
-rule of device_index.cpp.  With these right, what the GPU tests expect of a crafted bin is known without a GPU."""
+rule of index_build.cpp.  With these right, what the GPU tests expect of a crafted bin is known without a GPU."""
 import numpy as np
 import pytest
 

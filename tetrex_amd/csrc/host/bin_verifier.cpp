@@ -1,0 +1,553 @@
+#include "bin_verifier.hpp"
+#include "device_buffer.hpp"
+#include "edit_distance.hpp"
+#include "fasta.hpp"
+
+#include <algorithm>
+#include <cstdlib>
+#include <numeric>
+#include <stdexcept>
+#include <tuple>
+
+namespace tetrex {
+
+ResidentBins::ResidentBins(const std::vector<std::string>& bin_paths, std::string who)
+    : paths_(bin_paths), who_(std::move(who)), bins_(bin_paths.size()) {
+    const char* mb = std::getenv("TETREX_VERIFY_TEXT_MB");
+    const double mib = mb && *mb ? std::atof(mb) : 4096.0;  // (a fraction is allowed: tests bound the cache to one bin)
+    limit_bytes_ = (uint64_t)std::max(1.0, std::min(mib, 1e9) * 1048576.0);
+}
+
+ResidentBins::~ResidentBins() {
+    for (Bin& b : bins_) drop(b);
+}
+
+void ResidentBins::drop(Bin& b) {
+    if (b.d_text) txq_free(b.d_text);  // (waits for the kernels that read it)
+    if (b.d_rec) txq_free(b.d_rec);
+    b.d_text = b.d_rec = nullptr;
+    held_bytes_ -= b.device_bytes;
+    b.device_bytes = 0;
+}
+
+void ResidentBins::read(uint32_t bin, std::string& text, std::vector<uint64_t>& rec, std::vector<std::string>& names) const {
+    text.clear();
+    rec.assign(1, 0);
+    names.clear();
+    try {
+        for_each_record(paths_[bin], [&](const FastaRecord& r) {
+            names.push_back(r.name);
+            text.append(r.seq);
+            rec.push_back(text.size());
+        });
+    } catch (const std::exception& e) {
+        throw std::runtime_error(who_ + ": cannot read bin file " + paths_[bin] + ": " + e.what());
+    }
+}
+
+void ResidentBins::read_keeping_names(uint32_t bin, std::string& text, std::vector<uint64_t>& rec) {
+    std::vector<std::string> names;
+    read(bin, text, rec, names);
+    if (bins_[bin].names.empty()) bins_[bin].names = std::move(names);
+}
+
+ResidentBins::Bin& ResidentBins::resident(uint32_t bin) {
+    Bin& b = bins_[bin];
+    if (b.d_rec) { b.last_use = ++clock_; return b; }
+    std::string text;
+    std::vector<uint64_t> rec;
+    std::vector<std::string> names;
+    read(bin, text, rec, names);
+    return resident(bin, text, rec, names);
+}
+
+ResidentBins::Bin& ResidentBins::resident(uint32_t bin, const std::string& text, std::vector<uint64_t>& rec, std::vector<std::string>& names) {
+    Bin& b = bins_[bin];
+    b.last_use = ++clock_;
+    if (b.d_rec) return b;
+    // (a bin that left the device and comes back keeps the names it has: they are the same, and confirmed rows point into them)
+    if (b.names.empty()) b.names = std::move(names);
+    const uint64_t n = rec.size() - 1;
+    rec.push_back(0);  // behind the record offsets: the one group's offsets {0, n}
+    rec.push_back(n);
+    const uint64_t bytes = text.size() + 16 + rec.size() * 8;
+    while (held_bytes_ && held_bytes_ + bytes > limit_bytes_) {  // the bin used longest ago leaves
+        Bin* oldest = nullptr;
+        for (Bin& o : bins_)
+            if (o.d_rec && &o != &b && (!oldest || o.last_use < oldest->last_use)) oldest = &o;
+        if (!oldest) break;
+        drop(*oldest);
+    }
+    txq_check(txq_malloc(&b.d_text, text.size() + 16), "txq_malloc");
+    txq_check(txq_malloc(&b.d_rec, rec.size() * 8), "txq_malloc");
+    b.device_bytes = bytes;
+    held_bytes_ += bytes;
+    if (!text.empty()) txq_check(txq_memcpy_h2d(b.d_text, text.data(), text.size()), "h2d");
+    txq_check(txq_memcpy_h2d(b.d_rec, rec.data(), rec.size() * 8), "h2d");
+    b.n_records = n;
+    b.text_bytes = text.size();
+    return b;
+}
+
+// ---- tetrex search --verify --------------------------------------------------------------------------------------------
+
+BinVerifier::BinVerifier(const std::vector<std::string>& bin_paths, bool dna, uint32_t errors)
+    : bins_(bin_paths, "tetrex search --verify"), dna_(dna), errors_(errors) {
+    std::fill(codes_, codes_ + 256, (uint8_t)255);
+    if (dna) {
+        const char* acgt = "ACGT";
+        for (uint8_t c = 0; c < 4; ++c) codes_[(uint8_t)acgt[c]] = codes_[(uint8_t)(acgt[c] | 0x20)] = c;
+        codes_[(uint8_t)'U'] = codes_[(uint8_t)'u'] = 3;
+    } else {
+        for (uint8_t c = 0; c < 26; ++c) codes_[(uint8_t)('A' + c)] = codes_[(uint8_t)('a' + c)] = c;
+    }
+    txq_check(txq_malloc(&d_codes_, 256), "txq_malloc");
+    txq_check(txq_memcpy_h2d(d_codes_, codes_, 256), "h2d");
+}
+
+BinVerifier::~BinVerifier() {
+    if (d_codes_) txq_free(d_codes_);
+}
+
+size_t BinVerifier::device_max() {
+    const char* long_env = std::getenv("TETREX_VERIFY_LONG");
+    return long_env && long_env[0] == '0' && !long_env[1] ? TXQ_EDIT_MAX_PATTERN : TXQ_EDIT_LONG_MAX_PATTERN;
+}
+
+void BinVerifier::verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits,
+                         std::vector<std::vector<Hit>>* rows) {
+    hits.assign(candidates.size(), Hit{});
+    if (rows) rows->assign(candidates.size(), {});
+    if (candidates.empty()) return;
+    const size_t strands = dna_ ? 2 : 1;
+    // the patterns: every record that is a candidate somewhere, and on a nucleotide index its reverse complement behind it
+    constexpr uint32_t kNoPattern = 0xFFFFFFFFu;
+    std::vector<uint32_t> pattern_of(queries.size(), kNoPattern), of_candidate(candidates.size(), kNoPattern);
+    std::vector<uint64_t> pat_off{0}, lengths(candidates.size());
+    std::string pat;
+    const auto reverse_complement = [](const std::string& s) {
+        std::string out(s.rbegin(), s.rend());
+        for (char& c : out) switch (c & 0xDF) {
+            case 'A': c = 'T'; break;
+            case 'C': c = 'G'; break;
+            case 'G': c = 'C'; break;
+            case 'T': case 'U': c = 'A'; break;
+            default: c = 'N'; break;  // (no class: matches nothing, as the byte it stands for)
+        }
+        return out;
+    };
+    const size_t longest = device_max();
+    for (size_t i = 0; i < candidates.size(); ++i) {
+        const uint32_t q = candidates[i].query;
+        const std::string& s = queries.at(q);
+        lengths[i] = s.size();
+        if (s.empty() || s.size() > longest) continue;  // (the host route: letters() below)
+        if (pattern_of[q] == kNoPattern) {
+            pattern_of[q] = (uint32_t)(pat_off.size() - 1);
+            pat.append(s);
+            pat_off.push_back(pat.size());
+            if (dna_) {
+                pat.append(reverse_complement(s));
+                pat_off.push_back(pat.size());
+            }
+        }
+        of_candidate[i] = pattern_of[q];
+    }
+    DeviceBuffer d_pat(pat.size() + 16), d_po(pat_off.size() * 8);
+    if (!pat.empty()) {
+        txq_check(txq_memcpy_h2d(d_pat.p, pat.data(), pat.size()), "h2d");
+        txq_check(txq_memcpy_h2d(d_po.p, pat_off.data(), pat_off.size() * 8), "h2d");
+    }
+    run(DevicePatterns{(const uint8_t*)d_pat.p, (const uint64_t*)d_po.p, pat_off.size() - 1, pat.size()}, strands, candidates, of_candidate, lengths,
+        [&](size_t i, size_t strand) { return strand ? reverse_complement(queries[candidates[i].query]) : queries[candidates[i].query]; }, hits, rows);
+}
+
+void BinVerifier::verify(const DevicePatterns& patterns, const std::vector<Candidate>& candidates, const std::vector<uint64_t>& lengths,
+                         const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows) {
+    hits.assign(candidates.size(), Hit{});
+    if (rows) rows->assign(candidates.size(), {});
+    if (candidates.empty()) return;
+    std::vector<uint32_t> of_candidate(candidates.size());
+    for (size_t i = 0; i < candidates.size(); ++i) of_candidate[i] = candidates[i].query;
+    run(patterns, 1, candidates, of_candidate, lengths, [&](size_t i, size_t) { return letters(candidates[i].query); }, hits, rows);
+}
+
+namespace {
+// each(bin, a, b) for every maximal run [a, b) of positions in [begin, end) with the same bin_at(position)
+template <class BinAt, class Each>
+void for_each_bin_run(size_t begin, size_t end, BinAt&& bin_at, Each&& each) {
+    for (size_t a = begin; a < end;) {
+        size_t b = a;
+        const uint32_t bin = bin_at(a);
+        while (b < end && bin_at(b) == bin) ++b;
+        each(bin, a, b);
+        a = b;
+    }
+}
+}  // namespace
+
+BinVerifier::Routes BinVerifier::split_routes(const std::vector<Candidate>& candidates, const std::vector<uint64_t>& lengths, bool all_on_host) const {
+    Routes r;
+    r.order.resize(candidates.size());
+    std::iota(r.order.begin(), r.order.end(), (size_t)0);
+    std::stable_sort(r.order.begin(), r.order.end(), [&](size_t x, size_t y) { return candidates[x].bin < candidates[y].bin; });
+    // (TETREX_VERIFY_LONG=0: what the long-pattern kernels would answer goes to the host, for A/B runs)
+    const size_t longest = device_max();
+    std::vector<size_t> on_long;
+    for (size_t i : r.order) {
+        if (all_on_host || lengths[i] == 0 || lengths[i] > longest) r.on_host.push_back(i);
+        else (lengths[i] > TXQ_EDIT_MAX_PATTERN ? on_long : r.on_device).push_back(i);
+    }
+    r.n_short = r.on_device.size();
+    r.on_device.insert(r.on_device.end(), on_long.begin(), on_long.end());
+    return r;
+}
+
+BinVerifier::AlignRoute BinVerifier::align_route() const {
+    const char* align_env = std::getenv("TETREX_VERIFY_ALIGN");
+    const uint32_t device_errors = std::min<uint32_t>(errors_, TXQ_EDIT_ALIGN_MAX_DISTANCE);
+    return {align_ && !(align_env && std::string(align_env) == "host"), device_errors, TXQ_EDIT_ALIGN_STRIDE(device_errors)};
+}
+
+void BinVerifier::align_on_host(uint32_t bin, const PendingAlign* pairs, size_t n, const std::string& text, const std::vector<uint64_t>& rec,
+                                const Letters& letters) {
+    bool failed = false;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic)
+#endif
+    for (size_t k = 0; k < n; ++k) {
+        const PendingAlign& p = pairs[k];
+        const std::string pattern = letters(p.candidate, p.strand);
+        EditAlignment a;
+        if (p.r + 1 >= rec.size() ||
+            !edit_align((const uint8_t*)pattern.data(), pattern.size(), (const uint8_t*)text.data() + rec[p.r], (size_t)(rec[p.r + 1] - rec[p.r]), p.d, p.j, codes_, a)) {
+#ifdef _OPENMP
+#pragma omp atomic write
+#endif
+            failed = true;
+            continue;
+        }
+        p.into->start = a.start;
+        p.into->runs = std::move(a.runs);
+    }
+    if (failed) throw std::runtime_error("tetrex search --align: a confirmed pair has no alignment (bin " + std::to_string(bin) + ")");
+    n_align_host_ += n;
+}
+
+void BinVerifier::align_rest(std::vector<PendingAlign>& pending, const std::vector<Candidate>& candidates, const Letters& letters) {
+    std::stable_sort(pending.begin(), pending.end(), [&](const PendingAlign& x, const PendingAlign& y) { return candidates[x.candidate].bin < candidates[y.candidate].bin; });
+    for_each_bin_run(0, pending.size(), [&](size_t k) { return candidates[pending[k].candidate].bin; }, [&](uint32_t bin, size_t a, size_t b) {
+        std::string text;
+        std::vector<uint64_t> rec;
+        bins_.read_keeping_names(bin, text, rec);
+        align_on_host(bin, pending.data() + a, b - a, text, rec, letters);
+    });
+}
+
+void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
+                      const std::vector<uint64_t>& lengths, const Letters& letters, std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows) {
+    if (rows) return run_targets(patterns, strands, candidates, pattern_of, lengths, letters, *rows);
+    n_candidates_ += candidates.size();
+    const Routes routes = split_routes(candidates, lengths, false);
+    const std::vector<size_t>&on_device = routes.on_device, &on_host = routes.on_host;
+    const size_t n_short = routes.n_short;
+    n_device_ += n_short, n_device_long_ += on_device.size() - n_short, n_host_ += on_host.size();
+    // take the better strand of `strands` results (distance, record, end); + wins on equal distance.  Returns that strand, or
+    // `strands` where neither is within the cap.
+    const auto settle = [&](size_t i, const uint32_t* res, const std::vector<std::string>& names) {
+        Hit& h = hits[i];
+        size_t kept = strands;
+        for (size_t s = 0; s < strands; ++s)
+            if (res[3 * s] != kEditNone && (h.distance == kEditNone || res[3 * s] < h.distance)) {
+                h.distance = res[3 * s];
+                h.target = &names.at(res[3 * s + 1]);
+                h.end = res[3 * s + 2];
+                h.strand = s ? '-' : '+';
+                kept = s;
+            }
+        if (h.distance != kEditNone) ++n_confirmed_;
+        return kept;
+    };
+    // --align: the alignment of the strand that settle kept.  What the device declines waits in `pending` for the host twin.
+    const AlignRoute align = align_route();
+    const size_t stride = align.stride;
+    std::vector<PendingAlign> pending;
+    if (!on_device.empty()) {
+        std::vector<uint32_t> pairs;
+        pairs.reserve(on_device.size() * strands * 3);
+        for (size_t i : on_device)
+            for (size_t s = 0; s < strands; ++s) pairs.insert(pairs.end(), {pattern_of[i] + (uint32_t)s, 0u, errors_});
+        // (the alignments lie behind the triples: one buffer, one copy back)
+        const size_t n_pairs = pairs.size() / 3, align_words = align.on_device ? n_pairs * stride : 0;
+        DeviceBuffer d_pairs(pairs.size() * 4), d_out((pairs.size() + align_words) * 4);
+        uint32_t* const d_align = (uint32_t*)d_out.p + pairs.size();
+        static_assert(TXQ_EDIT_LONG_WORKSPACE(7) == TXQ_EDIT_WORKSPACE(7), "one workspace, cut the same way for either call");
+        DeviceBuffer d_work(TXQ_EDIT_WORKSPACE(pairs.size() / 3) + 8 * on_device.size());  // (every call its own part: they are all in flight at once)
+        size_t n_calls = 0;
+        txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
+        for (int is_long = 0; is_long < 2; ++is_long)  // one call per bin and kernel: the bin's records are one group
+            for_each_bin_run(is_long ? n_short : 0, is_long ? on_device.size() : n_short, [&](size_t k) { return candidates[on_device[k]].bin; }, [&](uint32_t bin, size_t a, size_t b) {
+                ResidentBins::Bin& e = bins_.resident(bin);
+                const uint64_t* d_rec = (const uint64_t*)e.d_rec;
+                txq_check((is_long ? txq_edit_search_long_device : txq_edit_search_device)(patterns.d_letters, patterns.d_offsets, patterns.n_patterns, patterns.bytes, (const uint8_t*)e.d_text, d_rec,
+                                                 e.n_records, e.text_bytes, d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * strands * a,
+                                                 (b - a) * strands, (const uint8_t*)d_codes_, (uint32_t*)d_out.p + 3 * strands * a,
+                                                 (unsigned char*)d_work.p + 16 * strands * a + 8 * n_calls++, nullptr),
+                          is_long ? "txq_edit_search_long_device" : "txq_edit_search_device");
+                if (align.on_device)  // behind the search call on its stream: the triples are read where it left them
+                    txq_check(txq_edit_align_device(patterns.d_letters, patterns.d_offsets, patterns.n_patterns, patterns.bytes, (const uint8_t*)e.d_text, d_rec,
+                                                    e.n_records, e.text_bytes, d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * strands * a,
+                                                    (b - a) * strands, (const uint32_t*)d_out.p + 3 * strands * a, (const uint8_t*)d_codes_, align.device_errors,
+                                                    d_align + stride * strands * a, nullptr, nullptr),
+                              "txq_edit_align_device");
+            });
+        std::vector<uint32_t> out(pairs.size() + align_words);
+        txq_check(txq_memcpy_d2h(out.data(), d_out.p, out.size() * 4), "d2h");  // (waits for the kernels)
+        for (size_t k = 0; k < on_device.size(); ++k) {
+            const uint32_t* res = out.data() + 3 * strands * k;
+            const size_t i = on_device[k], kept = settle(i, res, bins_.at(candidates[i].bin).names);
+            if (!align_ || kept == strands) continue;
+            const uint32_t* words = out.data() + pairs.size() + stride * (strands * k + kept);
+            if (align.on_device && words[0] < kEditNotAligned) {
+                hits[i].start = words[0];
+                hits[i].runs.assign(words + 2, words + 2 + words[1]);
+                ++n_align_device_;
+            } else pending.push_back({i, kept, res[3 * kept], res[3 * kept + 1], res[3 * kept + 2], &hits[i]});
+        }
+    }
+    // records too long for the device: the bin is read once more, the pairs of a bin run side by side
+    for_each_bin_run(0, on_host.size(), [&](size_t k) { return candidates[on_host[k]].bin; }, [&](uint32_t bin, size_t a, size_t b) {
+        std::string text;
+        std::vector<uint64_t> rec;
+        bins_.read_keeping_names(bin, text, rec);
+        std::vector<uint32_t> out(3 * strands * (b - a), kEditNone);
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic)
+#endif
+        for (size_t k = a; k < b; ++k) {
+            if (lengths[on_host[k]] == 0) continue;
+            for (size_t st = 0; st < strands; ++st) {
+                const std::string p = letters(on_host[k], st);
+                EditPattern ep((const uint8_t*)p.data(), p.size(), codes_);
+                const EditResult r = edit_search_group(ep, (const uint8_t*)text.data(), rec.data(), 0, rec.size() - 1, errors_);
+                uint32_t* o = out.data() + 3 * (strands * (k - a) + st);
+                o[0] = r.distance, o[1] = r.record, o[2] = r.end;
+            }
+        }
+        std::vector<PendingAlign> confirmed;
+        for (size_t k = a; k < b; ++k) {
+            const uint32_t* res = out.data() + 3 * strands * (k - a);
+            const size_t kept = settle(on_host[k], res, bins_.at(bin).names);
+            if (!align_ || kept == strands) continue;
+            confirmed.push_back({on_host[k], kept, res[3 * kept], res[3 * kept + 1], res[3 * kept + 2], &hits[on_host[k]]});
+        }
+        align_on_host(bin, confirmed.data(), confirmed.size(), text, rec, letters);
+    });
+    align_rest(pending, candidates, letters);
+}
+
+// ---- tetrex search --verify --all-targets ------------------------------------------------------------------------------
+
+namespace {
+// slots of one txq_edit_targets*_device call (TETREX_VERIFY_TARGET_SLOTS, default 2^20: 8 MiB of keys and 16 MiB of rows)
+uint64_t target_slot_budget() {
+    const char* e = std::getenv("TETREX_VERIFY_TARGET_SLOTS");
+    const long long v = e && *e ? std::atoll(e) : 1ll << 20;
+    return (uint64_t)std::max<long long>(1, std::min<long long>(v, 1ll << 32));
+}
+}  // namespace
+
+void BinVerifier::run_targets(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
+                              const std::vector<uint64_t>& lengths, const Letters& letters, std::vector<std::vector<Hit>>& rows) {
+    rows.assign(candidates.size(), {});
+    n_candidates_ += candidates.size();
+    const char* route_env = std::getenv("TETREX_VERIFY_TARGETS");
+    Routes routes = split_routes(candidates, lengths, route_env && std::string(route_env) == "host");
+    const std::vector<size_t>& on_device = routes.on_device;
+    std::vector<size_t>& on_host = routes.on_host;
+    const uint64_t budget = target_slot_budget();
+    // what the routes find: (record, strand, distance, end) of every hit of a candidate; settled below
+    struct Found { uint32_t r, strand, d, j; };
+    std::vector<std::vector<Found>> found(candidates.size());
+
+    // the device: one call per bin, kernel and at most `budget` slots, queued in rounds with one copy back each
+    struct Call { uint32_t bin; bool is_long; size_t first, n_pairs; uint64_t n_records; size_t row0, work0; };
+    const auto run_round = [&](const std::vector<Call>& calls, const std::vector<uint32_t>& pairs, const std::vector<size_t>& owner, size_t n_rows, size_t work_bytes) {
+        const size_t n_pairs = pairs.size() / 3;
+        DeviceBuffer d_pairs(pairs.size() * 4 + 4), d_hits(n_rows * 16 + 16), d_total(calls.size() * 8), d_status(n_pairs * 4 + 4), d_work(work_bytes + 8);
+        txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
+        for (size_t c = 0; c < calls.size(); ++c) {
+            const Call& k = calls[c];
+            ResidentBins::Bin& e = bins_.resident(k.bin);
+            const uint64_t* d_rec = (const uint64_t*)e.d_rec;
+            const size_t n_slots = k.n_pairs * k.n_records;
+            txq_check((k.is_long ? txq_edit_targets_long_device : txq_edit_targets_device)(
+                          patterns.d_letters, patterns.d_offsets, patterns.n_patterns, patterns.bytes, (const uint8_t*)e.d_text, d_rec, e.n_records, e.text_bytes,
+                          d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * k.first, k.n_pairs, (const uint8_t*)d_codes_,
+                          (uint32_t*)d_hits.p + 4 * k.row0, n_slots, (uint64_t*)d_total.p + c, (uint32_t*)d_status.p + k.first, n_slots,
+                          (unsigned char*)d_work.p + k.work0, nullptr),
+                      k.is_long ? "txq_edit_targets_long_device" : "txq_edit_targets_device");
+        }
+        std::vector<uint32_t> hits, status(n_pairs + 1);
+        std::vector<uint64_t> totals(calls.size());
+        txq_check(txq_memcpy_d2h(totals.data(), d_total.p, totals.size() * 8), "d2h");  // (waits for the kernels)
+        txq_check(txq_memcpy_d2h(status.data(), d_status.p, n_pairs * 4), "d2h");
+        for (size_t p = 0; p < n_pairs; ++p)
+            if (status[p] != 0) throw std::runtime_error("tetrex search --all-targets: the device refused a pair of bin " + std::to_string(candidates[owner[p / strands]].bin));
+        // The rows: a call's area is as large as its slots, what was written is usually far less.  One copy of the round's whole
+        // area where that is at most kOneCopyBytes; above it, only the rows that were written, call by call.
+        constexpr size_t kOneCopyBytes = (size_t)4 << 20;
+        const bool one_copy = n_rows * 16 <= kOneCopyBytes;
+        if (one_copy && n_rows) {
+            hits.resize(4 * n_rows);
+            txq_check(txq_memcpy_d2h(hits.data(), d_hits.p, n_rows * 16), "d2h");
+        }
+        for (size_t c = 0; c < calls.size(); ++c) {
+            const Call& k = calls[c];
+            if (totals[c] > k.n_pairs * k.n_records) throw std::runtime_error("tetrex search --all-targets: more hits than slots");
+            if (totals[c] == 0) continue;
+            if (!one_copy) {
+                hits.resize(4 * totals[c]);
+                txq_check(txq_memcpy_d2h(hits.data(), (const uint32_t*)d_hits.p + 4 * k.row0, totals[c] * 16), "d2h");
+            }
+            for (uint64_t h = 0; h < totals[c]; ++h) {
+                const uint32_t* row = hits.data() + 4 * ((one_copy ? k.row0 : 0) + h);
+                const size_t pair = k.first + row[0];
+                found[owner[pair / strands]].push_back({row[2], (uint32_t)(pair % strands), row[1], row[3]});
+            }
+        }
+    };
+    {
+        std::vector<Call> calls;
+        std::vector<uint32_t> pairs;
+        std::vector<size_t> owner;  // the candidate of every `strands` pairs of the round
+        size_t n_rows = 0, work_bytes = 0;
+        const auto flush_round = [&]() {
+            if (!calls.empty()) run_round(calls, pairs, owner, n_rows, work_bytes);
+            calls.clear(), pairs.clear(), owner.clear();
+            n_rows = work_bytes = 0;
+        };
+        for (int is_long = 0; is_long < 2; ++is_long)
+            for_each_bin_run(is_long ? routes.n_short : 0, is_long ? on_device.size() : routes.n_short, [&](size_t k) { return candidates[on_device[k]].bin; }, [&](uint32_t bin, size_t a, size_t b) {
+                // the bin's record count decides its route, so a bin that is not on the device is read first and uploaded only if it stays
+                uint64_t n_records;
+                if (bins_.is_resident(bin)) n_records = bins_.at(bin).n_records;
+                else {
+                    std::string text;
+                    std::vector<uint64_t> rec;
+                    std::vector<std::string> names;
+                    bins_.read(bin, text, rec, names);
+                    n_records = rec.size() - 1;
+                    if (n_records <= budget) bins_.resident(bin, text, rec, names);
+                }
+                if (n_records > budget) {  // a single pair above the bound: the host
+                    on_host.insert(on_host.end(), on_device.begin() + (long)a, on_device.begin() + (long)b);
+                    return;
+                }
+                (is_long ? n_device_long_ : n_device_) += b - a;
+                const size_t first = pairs.size() / 3;
+                for (size_t k = a; k < b; ++k) {
+                    owner.push_back(on_device[k]);
+                    for (size_t s = 0; s < strands; ++s) pairs.insert(pairs.end(), {pattern_of[on_device[k]] + (uint32_t)s, 0u, errors_});
+                }
+                const size_t n_pairs = (b - a) * strands, per_call = (size_t)std::max<uint64_t>(1, n_records ? budget / n_records : n_pairs);
+                for (size_t p = 0; p < n_pairs; p += per_call) {
+                    const size_t np = std::min(per_call, n_pairs - p), n_slots = np * n_records;
+                    calls.push_back({bin, is_long != 0, first + p, np, n_records, n_rows, work_bytes});
+                    n_rows += n_slots;
+                    work_bytes += TXQ_EDIT_TARGETS_WORKSPACE(np, n_slots);
+                }
+                // (pairs of one candidate stay in one round: a round ends between bins)
+                if (n_rows >= 8 * budget) flush_round();
+            });
+        flush_round();
+    }
+    // the host: what is too long or empty, bins of more records than a call's slots, and with TETREX_VERIFY_TARGETS=host everything
+    std::stable_sort(on_host.begin(), on_host.end(), [&](size_t x, size_t y) { return candidates[x].bin < candidates[y].bin; });
+    n_host_ += on_host.size();
+    for_each_bin_run(0, on_host.size(), [&](size_t k) { return candidates[on_host[k]].bin; }, [&](uint32_t bin, size_t a, size_t b) {
+        std::string text;
+        std::vector<uint64_t> rec;
+        bins_.read_keeping_names(bin, text, rec);
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic)
+#endif
+        for (size_t k = a; k < b; ++k) {
+            if (lengths[on_host[k]] == 0) continue;
+            std::vector<uint32_t> quads;
+            for (size_t st = 0; st < strands; ++st) {
+                const std::string p = letters(on_host[k], st);
+                EditPattern ep((const uint8_t*)p.data(), p.size(), codes_);
+                quads.clear();
+                edit_targets_group(ep, (const uint8_t*)text.data(), rec.data(), 0, rec.size() - 1, errors_, 0, quads);
+                for (size_t h = 0; h < quads.size(); h += 4) found[on_host[k]].push_back({quads[h + 2], (uint32_t)st, quads[h + 1], quads[h + 3]});
+            }
+        }
+    });
+    // settle: a target's row is its better strand, + on equal distance; rows in the order of the bin's file
+    struct ToAlign { size_t candidate, row; uint32_t strand, d, r, j; };
+    std::vector<ToAlign> to_align;
+    for (size_t i : routes.order) {
+        std::vector<Found>& f = found[i];
+        std::sort(f.begin(), f.end(), [](const Found& x, const Found& y) { return std::tie(x.r, x.d, x.strand) < std::tie(y.r, y.d, y.strand); });
+        const std::vector<std::string>& names = bins_.at(candidates[i].bin).names;
+        for (size_t k = 0; k < f.size(); ++k) {
+            if (k && f[k].r == f[k - 1].r) continue;
+            Hit h;
+            h.distance = f[k].d, h.end = f[k].j, h.strand = f[k].strand ? '-' : '+', h.target = &names.at(f[k].r);
+            if (align_) to_align.push_back({i, rows[i].size(), f[k].strand, f[k].d, f[k].r, f[k].j});
+            rows[i].push_back(std::move(h));
+        }
+        if (!rows[i].empty()) ++n_confirmed_;
+        n_targets_ += rows[i].size();
+    }
+    if (to_align.empty()) return;
+    // --align: the rows that were kept, bin by bin (to_align is in bin order).  One txq_edit_align_device call per bin on pair and
+    // triple arrays built here, after the copy back; what the device declines or cannot reach, on the host.
+    const AlignRoute align = align_route();
+    const size_t stride = align.stride;
+    const auto on_host_later = [&](const ToAlign& x) { return PendingAlign{x.candidate, x.strand, x.d, x.r, x.j, &rows[x.candidate][x.row]}; };
+    std::vector<PendingAlign> pending;
+    std::vector<size_t> sent;
+    for (size_t t = 0; t < to_align.size(); ++t) {
+        const size_t i = to_align[t].candidate;
+        const bool reachable = align.on_device && pattern_of[i] != 0xFFFFFFFFu && lengths[i] >= 1 && lengths[i] <= TXQ_EDIT_LONG_MAX_PATTERN &&
+                               to_align[t].d <= align.device_errors;
+        if (reachable) sent.push_back(t);
+        else pending.push_back(on_host_later(to_align[t]));
+    }
+    if (!sent.empty()) {
+        std::vector<uint32_t> pairs, triples;
+        for (size_t t : sent) {
+            const ToAlign& x = to_align[t];
+            pairs.insert(pairs.end(), {pattern_of[x.candidate] + x.strand, 0u, errors_});
+            triples.insert(triples.end(), {x.d, x.r, x.j});
+        }
+        DeviceBuffer d_pairs(pairs.size() * 4), d_triples(triples.size() * 4), d_align(sent.size() * stride * 4);
+        txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
+        txq_check(txq_memcpy_h2d(d_triples.p, triples.data(), triples.size() * 4), "h2d");
+        for_each_bin_run(0, sent.size(), [&](size_t k) { return candidates[to_align[sent[k]].candidate].bin; }, [&](uint32_t bin, size_t a, size_t b) {
+            ResidentBins::Bin& e = bins_.resident(bin);
+            const uint64_t* d_rec = (const uint64_t*)e.d_rec;
+            txq_check(txq_edit_align_device(patterns.d_letters, patterns.d_offsets, patterns.n_patterns, patterns.bytes, (const uint8_t*)e.d_text, d_rec,
+                                            e.n_records, e.text_bytes, d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * a, b - a,
+                                            (const uint32_t*)d_triples.p + 3 * a, (const uint8_t*)d_codes_, align.device_errors, (uint32_t*)d_align.p + stride * a,
+                                            nullptr, nullptr),
+                      "txq_edit_align_device");
+        });
+        std::vector<uint32_t> words(sent.size() * stride);
+        txq_check(txq_memcpy_d2h(words.data(), d_align.p, words.size() * 4), "d2h");  // (waits for the kernels)
+        for (size_t k = 0; k < sent.size(); ++k) {
+            const uint32_t* w = words.data() + stride * k;
+            const ToAlign& x = to_align[sent[k]];
+            if (w[0] < kEditNotAligned) {
+                rows[x.candidate][x.row].start = w[0];
+                rows[x.candidate][x.row].runs.assign(w + 2, w + 2 + w[1]);
+                ++n_align_device_;
+            } else pending.push_back(on_host_later(x));
+        }
+    }
+    align_rest(pending, candidates, letters);
+}
+
+}  // namespace tetrex

@@ -1,0 +1,165 @@
+// Host side: the records of bins' FASTA files resident on the GPU, and `tetrex search --verify` on them through the C-ABI
+// (include/txq.h).  Product code; requires a gfx950 GPU.
+#pragma once
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <vector>
+
+namespace tetrex {
+
+// what BinVerifier (below) says about one candidate pair
+struct VerifiedHit {
+    uint32_t distance = 0xFFFFFFFFu;  // 0xFFFFFFFF: not within `errors` of any record of the bin
+    uint32_t end = 0;                 // 1-based position of the match's last letter in the target, 0 for an empty match
+    char strand = '+';                // '-': the reverse complement matched better (on equal distance + wins)
+    const std::string* target = nullptr;  // the target record's name (valid as long as the verifier)
+    // with BinVerifier::set_align (include/txq.h at txq_edit_align_device): the letters of the target in front of the match, and
+    // the alignment's runs as (length << 2) | op, op 0 '=', 1 'X', 2 'I', 3 'D', from the pattern's first letter to its last
+    uint32_t start = 0;
+    std::vector<uint32_t> runs;
+};
+
+// The records of bins' FASTA files, resident on the device: what `tetrex search --verify` and `tetrex query --gpu-verify` run
+// their kernels over.  A bin's file (plain or gzip) is read when it is first asked for; its records go to the device once —
+// the bytes back to back, their n + 1 offsets, and behind those the offsets {0, n} of the one group they form — and stay
+// there, at most TETREX_VERIFY_TEXT_MB MiB of them (default 4096; the bin used longest ago leaves first; a fraction is
+// allowed).  Needs txq_init (DeviceIndex::upload).
+class ResidentBins {
+  public:
+    // `who` begins the message of the std::runtime_error that names a bin file which cannot be read
+    ResidentBins(const std::vector<std::string>& bin_paths, std::string who);
+    ResidentBins(const ResidentBins&) = delete;
+    ResidentBins& operator=(const ResidentBins&) = delete;
+    ~ResidentBins();
+    struct Bin {
+        std::vector<std::string> names;  // kept once read
+        void* d_text = nullptr;          // device: the records back to back, their n + 1 offsets, and {0, n}
+        void* d_rec = nullptr;
+        uint64_t n_records = 0, text_bytes = 0, device_bytes = 0, last_use = 0;
+    };
+    // the bin's records as the device gets them (rec: n + 1 offsets)
+    void read(uint32_t bin, std::string& text, std::vector<uint64_t>& rec, std::vector<std::string>& names) const;
+    // the same for a host route: the names stay with the bin unless it has them (they are the same, and hits point into them)
+    void read_keeping_names(uint32_t bin, std::string& text, std::vector<uint64_t>& rec);
+    Bin& resident(uint32_t bin);  // reads and uploads the bin unless it is on the device
+    // the same with the file already read (text, rec, names as read() gives them; names are moved from)
+    Bin& resident(uint32_t bin, const std::string& text, std::vector<uint64_t>& rec, std::vector<std::string>& names);
+    bool is_resident(uint32_t bin) const { return bins_[bin].d_rec != nullptr; }
+    Bin& at(uint32_t bin) { return bins_[bin]; }
+    size_t size() const { return bins_.size(); }
+
+  private:
+    void drop(Bin& b);
+    const std::vector<std::string>& paths_;
+    std::string who_;
+    std::vector<Bin> bins_;
+    uint64_t limit_bytes_, held_bytes_ = 0, clock_ = 0;
+};
+
+// `tetrex search --verify`: candidate (record, bin) pairs confirmed by edit distance on the bins' raw letters
+// (txq_edit_search_device, include/txq.h, where the semantics are).  Comparison is case-insensitive whatever reduction the
+// index uses: on a peptide index every letter is a class of its own, on a nucleotide index A, C, G and T = U are, every
+// other byte matches nothing; a nucleotide record is tried on both strands (its reverse complement is a second pattern, in
+// which an ambiguous byte stays one).  A bin's FASTA is read when it is first a candidate and its records stay on the device
+// (ResidentBins).  Records of up to TXQ_EDIT_MAX_PATTERN letters go to txq_edit_search_device, those of up to
+// TXQ_EDIT_LONG_MAX_PATTERN to txq_edit_search_long_device (TETREX_VERIFY_LONG=0: to the host, as before that kernel
+// existed), one call per candidate bin each, all queued before the one copy back.  Longer records and empty ones are
+// answered on the host (host/edit_distance.hpp), with OpenMP over the pairs.  n_routed() counts the candidate pairs each of
+// the three routes answered.
+// set_align (`--align`): every confirmed pair also gets the start and the runs of its alignment.  Behind each
+// search call txq_edit_align_device is queued on the same stream, reading the triples where the search call left them, and its
+// answers come back in the verifier's one copy; a pair the device declines (more than TXQ_EDIT_ALIGN_MAX_DISTANCE edits), a pair
+// of the host route, and with TETREX_VERIFY_ALIGN=host every pair, is aligned by edit_align of host/edit_distance.hpp on the
+// bin's letters read once more.  n_aligned() counts the pairs each of the two routes aligned.  Needs txq_init (DeviceIndex::upload).
+// `--all-targets` (verify with `rows`): every record of the bin within E edits is a row of its pair, in the
+// order of the bin's file — on a nucleotide index a target's better strand, + on equal distance.  The routes are the same,
+// with txq_edit_targets_device / txq_edit_targets_long_device in place of the search calls and edit_targets_group on the host.
+// A call's slots — its pairs times the bin's records — are bounded by TETREX_VERIFY_TARGET_SLOTS (default 2^20): a bin
+// whose pairs need more is answered in several calls, a bin with more records than that on the host, and the calls are
+// queued in rounds of at most eight times that many slots; a round waits once, for its totals, and copies its rows back — the
+// whole row area in one copy where that is at most 4 MiB, else only the rows written, call by call.  TETREX_VERIFY_TARGETS=host sends every pair
+// to the host.  With set_align the rows that were kept are aligned by one txq_edit_align_device call per bin on pair and triple
+// arrays built after the copy back (one more round trip a batch), the rest on the host as above.
+class BinVerifier {
+  public:
+    BinVerifier(const std::vector<std::string>& bin_paths, bool dna, uint32_t errors);
+    BinVerifier(const BinVerifier&) = delete;
+    BinVerifier& operator=(const BinVerifier&) = delete;
+    ~BinVerifier();
+    struct Candidate { uint32_t query, bin; };
+    using Hit = VerifiedHit;
+    // hits[i] answers candidates[i]; queries[c.query] are the batch's records.  Throws std::runtime_error naming the bin file
+    // that cannot be read.
+    // rows (`--all-targets`, below): rows->at(i) receives every target of candidates[i] instead, and hits stays as assign() left it.
+    void verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits,
+                std::vector<std::vector<Hit>>* rows = nullptr);
+    // The same for patterns that are on the device already (`tetrex search --translate --verify-frames`, DESIGN.md §14: the
+    // frames of txq_translate_frames_device).  Pattern p is d_letters[d_offsets[p] .. d_offsets[p+1]), n_patterns + 1 offsets,
+    // `bytes` letters in all in a buffer with 16 bytes of slack behind them; candidates[i].query names a pattern,
+    // lengths[i] is its length, and letters(p) gives the pattern to the host route (longer than TXQ_EDIT_LONG_MAX_PATTERN).
+    // One strand: a pattern is compared as it stands, whatever the index's molecule.
+    struct DevicePatterns {
+        const uint8_t* d_letters;
+        const uint64_t* d_offsets;
+        size_t n_patterns, bytes;
+    };
+    void verify(const DevicePatterns& patterns, const std::vector<Candidate>& candidates, const std::vector<uint64_t>& lengths,
+                const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows = nullptr);
+    size_t n_candidates() const { return n_candidates_; }
+    size_t n_confirmed() const { return n_confirmed_; }
+    size_t n_targets() const { return n_targets_; }  // `--all-targets`: the rows of all confirmed pairs
+    struct Routed { size_t device, device_long, host; };
+    Routed n_routed() const { return {n_device_, n_device_long_, n_host_}; }
+    void set_align(bool on) { align_ = on; }
+    struct Aligned { size_t device, host; };
+    Aligned n_aligned() const { return {n_align_device_, n_align_host_}; }
+
+  private:
+    using Letters = std::function<std::string(size_t, size_t)>;  // (candidate, strand) -> the pattern, for the host routes
+    // what both entries share: candidate i compares `strands` consecutive patterns from pattern_of[i] (lengths[i] letters each)
+    // with its bin — routing by length, the pairs, one call per bin and kernel, the one copy back, the host route, settle
+    void run(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
+             const std::vector<uint64_t>& lengths, const Letters& letters, std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows);
+    // `--all-targets`: the same routing with txq_edit_targets*_device and edit_targets_group in place of the search calls
+    void run_targets(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
+                     const std::vector<uint64_t>& lengths, const Letters& letters, std::vector<std::vector<Hit>>& rows);
+    // The candidates by bin (`order`), and by route: on_device holds the n_short patterns of up to TXQ_EDIT_MAX_PATTERN letters
+    // and behind them those of up to device_max(), which the long-pattern kernels answer; on_host the empty and the longer
+    // ones, and with all_on_host every one.
+    struct Routes {
+        std::vector<size_t> order, on_device, on_host;
+        size_t n_short = 0;
+    };
+    Routes split_routes(const std::vector<Candidate>& candidates, const std::vector<uint64_t>& lengths, bool all_on_host) const;
+    static size_t device_max();  // the longest pattern the device answers (TETREX_VERIFY_LONG)
+    // --align: on the device unless TETREX_VERIFY_ALIGN=host says otherwise, there with at most device_errors edits (the device
+    // declines more anyway) in `stride` words a pair
+    struct AlignRoute {
+        bool on_device;
+        uint32_t device_errors;
+        size_t stride;
+    };
+    AlignRoute align_route() const;
+    // a confirmed pair the host aligns: distance d, record r of the bin, end j; the answer goes to *into
+    struct PendingAlign {
+        size_t candidate, strand;
+        uint32_t d, r, j;
+        Hit* into;
+    };
+    // n pairs of one bin on its letters, side by side; throws after all of them where one has no alignment
+    void align_on_host(uint32_t bin, const PendingAlign* pairs, size_t n, const std::string& text, const std::vector<uint64_t>& rec, const Letters& letters);
+    // alignments the device did not make: a bin's letters are read once more, its pairs run side by side
+    void align_rest(std::vector<PendingAlign>& pending, const std::vector<Candidate>& candidates, const Letters& letters);
+    ResidentBins bins_;
+    bool dna_;
+    uint32_t errors_;
+    uint8_t codes_[256];
+    void* d_codes_ = nullptr;
+    size_t n_candidates_ = 0, n_confirmed_ = 0, n_device_ = 0, n_device_long_ = 0, n_host_ = 0;
+    bool align_ = false;
+    size_t n_align_device_ = 0, n_align_host_ = 0;
+    size_t n_targets_ = 0;
+};
+
+}  // namespace tetrex
