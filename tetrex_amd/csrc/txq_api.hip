@@ -140,85 +140,24 @@ static int validate_ibf(const txq_ibf_desc& d, bool need_words) {
     return TXQ_OK;
 }
 
-// Allocate one IBF (column slice [w0, w1) of its rows) in HBM; copies from `src` when given.
-int alloc_ibf(const txq_ibf_desc& d, uint64_t w0, uint64_t w1, IbfDev* out, uint64_t* bytes) {
+// Allocate one IBF (column slice [w0, w1) of its rows) in HBM; copies from d.words when given.
+int alloc_ibf(Index& ix, const txq_ibf_desc& d, uint64_t w0, uint64_t w1) {
     IbfDev f = ibf_shape(d, w0, w1);
-    *bytes = 0;
     if (f.shard_words) {
         const size_t nbytes = ibf_bytes(f);
-        TXQ_HIP(hipMalloc((void**)&f.words, nbytes));
-        *bytes = nbytes;
+        DeviceBuffer<uint64_t> words;
+        if (int rc = reserved(words.reserve(exactly(nbytes), free_now()), "hipMalloc((void**)&f.words, nbytes)")) return rc;
+        f.words = words.get();
         hipError_t e = hipSuccess;
         if (f.stride != f.shard_words || !d.words) e = hipMemset(f.words, 0, nbytes);
         if (e == hipSuccess && d.words)
             e = hipMemcpy2D(f.words, (size_t)f.stride * 8, d.words + w0, (size_t)d.bin_words * 8, (size_t)f.shard_words * 8,
                             (size_t)d.bin_size, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(f.words);
-            return fail_hip(e, "uploading IBF words");
-        }
+        if (e != hipSuccess) return fail_hip(e, "uploading IBF words");
+        ix.uploaded.push_back(std::move(words));
+        ix.device_bytes += nbytes;
     }
-    *out = f;
-    return TXQ_OK;
-}
-
-void Index::release() {
-    for (auto& f : ibf) if (f.words) (void)hipFree(f.words);
-    ibf.clear();
-    for (void* p : uploaded) (void)hipFree(p);  // every array of an HIBF upload; the fields that point at them die with the index
-    uploaded.clear();
-    for (int i = 0; i < 2; ++i) {
-        if (host_pipe.stream[i]) (void)hipStreamDestroy(host_pipe.stream[i]);
-        if (host_pipe.done[i]) (void)hipEventDestroy(host_pipe.done[i]);
-        if (host_pipe.d_kmers[i]) (void)hipFree(host_pipe.d_kmers[i]);
-        if (host_pipe.d_masks[i]) (void)hipFree(host_pipe.d_masks[i]);
-        if (host_pipe.bounce[i]) (void)hipHostFree(host_pipe.bounce[i]);
-    }
-    host_pipe = HostPipe{};
-    if (probe_table.rows) (void)hipFree(probe_table.rows);
-    if (probe_table.state) (void)hipFree(probe_table.state);
-    if (probe_table.done) (void)hipEventDestroy(probe_table.done);
-    probe_table.rows = nullptr; probe_table.state = nullptr; probe_table.done = nullptr;
-    probe_table.cap_rows = 0; probe_table.recorded = probe_table.refused = false;
-    probe_table.keep = ProbeKeep{};
-    for (const ArenaChunk& c : session_cache.chunks) (void)hipFree(c.p);
-    for (const ArenaChunk& c : session_cache.block_chunks) (void)hipFree(c.p);
-    for (StagingSet& t : session_cache.set)
-        if (t.done) (void)hipEventDestroy(t.done);
-    if (session_cache.upload) (void)hipStreamDestroy(session_cache.upload);
-    if (session_cache.side) (void)hipStreamDestroy(session_cache.side);
-    for (void* p : {(void*)session_cache.set[0].d_blob, (void*)session_cache.set[0].d_aux, (void*)session_cache.set[1].d_blob, (void*)session_cache.set[1].d_aux,
-                    (void*)session_cache.set[0].d_masks, (void*)session_cache.set[1].d_masks})
-        if (p) (void)hipFree(p);
-    session_cache = SessionCache{};
-    interleaved = IbfDev{};
-    if (scratch_cm) (void)hipFree(scratch_cm);
-    if (scratch_crows) (void)hipFree(scratch_crows);
-    scratch_crows = nullptr; cap_crows = 0;
-    scratch_cm = nullptr; cap_cm = 0;
-    for (void* p : {(void*)scratch_kmers, (void*)scratch_masks, (void*)frontier[0], (void*)frontier[1], (void*)d_counts,
-                    (void*)scratch_blob, (void*)scratch_slots, (void*)scratch_final, (void*)scratch_dense_kmers, (void*)scratch_dense_masks, (void*)kmer_table,
-                    (void*)scratch_count_acc, (void*)scratch_count_io})
-        if (p) (void)hipFree(p);
-    scratch_count_acc = nullptr; cap_count_acc = 0;
-    scratch_count_io = nullptr; cap_count_io = 0;
-    kmer_table = nullptr; kmer_table_bits = 0;
-    scratch_kmers = scratch_masks = nullptr; frontier[0] = frontier[1] = nullptr; d_counts = nullptr;
-    scratch_blob = nullptr; scratch_slots = scratch_final = nullptr;
-    if (host_final) { (void)hipHostFree(host_final); host_final = nullptr; cap_host_final = 0; }
-    scratch_dense_kmers = scratch_dense_masks = nullptr; cap_dense_kmers = cap_dense_masks = 0;
-}
-
-int ensure(void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes && *p) return TXQ_OK;
-    if (*p) {  // kernels in flight may still use the buffer (a session's stages are not waited for one by one)
-        (void)hipDeviceSynchronize();
-        (void)hipFree(*p);
-    }
-    *p = nullptr; *cap = 0;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc(scratch)");
-    *cap = bytes;
+    ix.ibf.push_back(f);
     return TXQ_OK;
 }
 
@@ -314,15 +253,11 @@ static int upload_impl(const txq_index_desc* desc, bool hibf, int device_rank, i
     ix->shard_words = hi - lo;
     int rc = TXQ_OK;
     if (!hibf) {
-        IbfDev f;
-        uint64_t bytes;
-        rc = alloc_ibf(desc->ibf[0], lo, hi, &f, &bytes);
-        if (rc == TXQ_OK) { ix->ibf.push_back(f); ix->device_bytes += bytes; }
+        rc = alloc_ibf(*ix, desc->ibf[0], lo, hi);
     } else {
         rc = hibf_upload(*ix, *desc, cleared_ok);
     }
     if (rc != TXQ_OK) {
-        ix->release();
         delete ix;
         return rc;
     }
@@ -401,12 +336,7 @@ int txq_index_create_ibf(uint64_t bins, uint64_t bin_size, uint64_t hash_funs, i
     shard_range(ix->mask_words, shard_rank, n_shards, &lo, &hi);
     ix->shard_word0 = lo;
     ix->shard_words = hi - lo;
-    IbfDev f;
-    uint64_t bytes;
-    int rc = alloc_ibf(d, lo, hi, &f, &bytes);
-    if (rc != TXQ_OK) { delete ix; return rc; }
-    ix->ibf.push_back(f);
-    ix->device_bytes = bytes;
+    if (int rc = alloc_ibf(*ix, d, lo, hi)) { delete ix; return rc; }
     *out = ix;
     return TXQ_OK;
 }
@@ -440,7 +370,6 @@ int txq_index_free(txq_index* ix) {
     if (ix->open_sessions > 0)
         return fail(TXQ_ERR_STATE, "the index still has %d open session(s): end them first (txq_session_end)", ix->open_sessions);
     if (!g_devices.empty()) (void)bind_device(ix->device);
-    ix->release();
     delete ix;
     return TXQ_OK;
 }
@@ -511,30 +440,23 @@ int txq_probe(txq_index* ix, const uint64_t* kmers, size_t n, uint64_t* masks) {
     if (chunk > n) chunk = n;
     Index::HostPipe& hp = ix->host_pipe;
     for (int i = 0; i < 2; ++i) {
-        if (!hp.stream[i]) TXQ_HIP(hipStreamCreateWithFlags(&hp.stream[i], hipStreamNonBlocking));
-        if (!hp.done[i]) TXQ_HIP(hipEventCreateWithFlags(&hp.done[i], hipEventDisableTiming));
-        if (int rc = ensure((void**)&hp.d_kmers[i], &hp.cap_kmers[i], chunk * 8)) return rc;
-        if (int rc = ensure((void**)&hp.d_masks[i], &hp.cap_masks[i], chunk * W * 8)) return rc;
+        TXQ_HIP(make(hp.stream[i]));
+        TXQ_HIP(make(hp.done[i]));
+        if (int rc = reserved(hp.d_kmers[i].reserve(exactly(chunk * 8), after_device_wait()), "hipMalloc(scratch)")) return rc;
+        if (int rc = reserved(hp.d_masks[i].reserve(exactly(chunk * W * 8), after_device_wait()), "hipMalloc(scratch)")) return rc;
     }
     hipPointerAttribute_t attr{};
     const bool pinned_out = hipPointerGetAttributes(&attr, masks) == hipSuccess && attr.type == hipMemoryTypeHost;
     (void)hipGetLastError();  // an unregistered pointer is reported as an error: not one of ours
     if (!pinned_out) {
-        for (int i = 0; i < 2; ++i) {
-            if (hp.cap_bounce[i] < chunk * W * 8) {
-                if (hp.bounce[i]) (void)hipHostFree(hp.bounce[i]);
-                hp.bounce[i] = nullptr;
-                hp.cap_bounce[i] = 0;
-                TXQ_HIP(hipHostMalloc((void**)&hp.bounce[i], chunk * W * 8, hipHostMallocDefault));
-                hp.cap_bounce[i] = chunk * W * 8;
-            }
-        }
+        for (int i = 0; i < 2; ++i)  // (every chunk of an earlier call was drained before that call returned)
+            if (int rc = reserved(hp.bounce[i].reserve(exactly(chunk * W * 8), free_now()), "hipHostMalloc(bounce buffer)")) return rc;
     }
     size_t pending_off[2] = {0, 0}, pending_m[2] = {0, 0};
     auto drain = [&](int b) -> int {  // wait for buffer b's chunk and hand it to the caller
         if (!pending_m[b]) return TXQ_OK;
-        TXQ_HIP(hipEventSynchronize(hp.done[b]));
-        if (!pinned_out) std::memcpy(masks + pending_off[b] * W, hp.bounce[b], pending_m[b] * W * 8);
+        TXQ_HIP(hipEventSynchronize(hp.done[b].get()));
+        if (!pinned_out) std::memcpy(masks + pending_off[b] * W, hp.bounce[b].get(), pending_m[b] * W * 8);
         pending_m[b] = 0;
         return TXQ_OK;
     };
@@ -543,11 +465,11 @@ int txq_probe(txq_index* ix, const uint64_t* kmers, size_t n, uint64_t* masks) {
         const size_t m = n - off < chunk ? n - off : chunk;
         if (int rc = drain(b)) return rc;  // this buffer's previous chunk
         // the HIBF descent has per-index scratch (frontiers): its chunks share one stream
-        hipStream_t st = hp.stream[ix->is_hibf ? 0 : b];
-        TXQ_HIP(hipMemcpyAsync(hp.d_kmers[b], kmers + off, m * 8, hipMemcpyHostToDevice, st));
-        if (int rc = txq_probe_device(ix, hp.d_kmers[b], m, hp.d_masks[b], nullptr, st)) return rc;
-        TXQ_HIP(hipMemcpyAsync(pinned_out ? (void*)(masks + off * W) : (void*)hp.bounce[b], hp.d_masks[b], m * W * 8, hipMemcpyDeviceToHost, st));
-        TXQ_HIP(hipEventRecord(hp.done[b], st));
+        hipStream_t st = hp.stream[ix->is_hibf ? 0 : b].get();
+        TXQ_HIP(hipMemcpyAsync(hp.d_kmers[b].get(), kmers + off, m * 8, hipMemcpyHostToDevice, st));
+        if (int rc = txq_probe_device(ix, hp.d_kmers[b].get(), m, hp.d_masks[b].get(), nullptr, st)) return rc;
+        TXQ_HIP(hipMemcpyAsync(pinned_out ? (void*)(masks + off * W) : (void*)hp.bounce[b].get(), hp.d_masks[b].get(), m * W * 8, hipMemcpyDeviceToHost, st));
+        TXQ_HIP(hipEventRecord(hp.done[b].get(), st));
         pending_off[b] = off;
         pending_m[b] = m;
     }
@@ -585,8 +507,8 @@ int txq_count(txq_index* ix, const uint64_t* values, const uint64_t* offsets, si
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_val = up(n_values * 8), b_off = up((n_queries + 1) * 8), b_thr = up(n_queries * 4), b_hit = up(n_queries * W * 8);
     const size_t b_cnt = counts ? up(n_queries * W * 64 * 4) : 0;
-    if (int rc = ensure((void**)&ix->scratch_count_io, &ix->cap_count_io, b_val + b_off + b_thr + b_hit + b_cnt)) return rc;
-    unsigned char* base = ix->scratch_count_io;
+    if (int rc = reserved(ix->scratch_count_io.reserve(exactly(b_val + b_off + b_thr + b_hit + b_cnt), after_device_wait()), "hipMalloc(scratch)")) return rc;
+    unsigned char* base = ix->scratch_count_io.get();
     uint64_t* d_val = (uint64_t*)base;
     uint64_t* d_off = (uint64_t*)(base + b_val);
     uint32_t* d_thr = (uint32_t*)(base + b_val + b_off);
@@ -595,8 +517,8 @@ int txq_count(txq_index* ix, const uint64_t* values, const uint64_t* offsets, si
     std::vector<uint64_t> rebased(offsets, offsets + n_queries + 1);
     for (uint64_t& o : rebased) o -= offsets[0];
     Index::HostPipe& hp = ix->host_pipe;
-    if (!hp.stream[0]) TXQ_HIP(hipStreamCreateWithFlags(&hp.stream[0], hipStreamNonBlocking));
-    hipStream_t st = hp.stream[0];
+    TXQ_HIP(make(hp.stream[0]));
+    hipStream_t st = hp.stream[0].get();
     if (n_values) TXQ_HIP(hipMemcpyAsync(d_val, values + offsets[0], n_values * 8, hipMemcpyHostToDevice, st));
     TXQ_HIP(hipMemcpyAsync(d_off, rebased.data(), rebased.size() * 8, hipMemcpyHostToDevice, st));
     TXQ_HIP(hipMemcpyAsync(d_thr, thresholds, n_queries * 4, hipMemcpyHostToDevice, st));
@@ -643,8 +565,8 @@ int txq_count_windows(txq_index* ix, const uint64_t* values, size_t n_values, co
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_val = up(span * 8), b_beg = up(n_windows * 8), b_len = up(n_windows * 4), b_thr = up(n_windows * 4), b_hit = up(n_windows * W * 8);
     const size_t b_cnt = counts ? up(n_windows * W * 64 * 4) : 0;
-    if (int rc = ensure((void**)&ix->scratch_count_io, &ix->cap_count_io, b_val + b_beg + b_len + b_thr + b_hit + b_cnt)) return rc;
-    unsigned char* base = ix->scratch_count_io;
+    if (int rc = reserved(ix->scratch_count_io.reserve(exactly(b_val + b_beg + b_len + b_thr + b_hit + b_cnt), after_device_wait()), "hipMalloc(scratch)")) return rc;
+    unsigned char* base = ix->scratch_count_io.get();
     uint64_t* d_val = (uint64_t*)base;
     uint64_t* d_beg = (uint64_t*)(base + b_val);
     uint32_t* d_len = (uint32_t*)(base + b_val + b_beg);
@@ -654,8 +576,8 @@ int txq_count_windows(txq_index* ix, const uint64_t* values, size_t n_values, co
     std::vector<uint64_t> begins(win_begin, win_begin + n_windows);
     for (uint64_t& b : begins) b -= v0;
     Index::HostPipe& hp = ix->host_pipe;
-    if (!hp.stream[0]) TXQ_HIP(hipStreamCreateWithFlags(&hp.stream[0], hipStreamNonBlocking));
-    hipStream_t st = hp.stream[0];
+    TXQ_HIP(make(hp.stream[0]));
+    hipStream_t st = hp.stream[0].get();
     if (span) TXQ_HIP(hipMemcpyAsync(d_val, values + v0, span * 8, hipMemcpyHostToDevice, st));
     TXQ_HIP(hipMemcpyAsync(d_beg, begins.data(), n_windows * 8, hipMemcpyHostToDevice, st));
     TXQ_HIP(hipMemcpyAsync(d_len, win_len, n_windows * 4, hipMemcpyHostToDevice, st));
@@ -695,8 +617,7 @@ int txq_emplace_device(txq_index* ix, const uint64_t* d_values, const uint32_t* 
         std::lock_guard<std::mutex> lock(ix->table_mutex);
         if (ix->kmer_table) {
             TXQ_HIP(hipDeviceSynchronize());  // (kernels of ended sessions may still be reading it)
-            (void)hipFree(ix->kmer_table);
-            ix->kmer_table = nullptr;
+            ix->kmer_table.reset();
             ix->kmer_table_bits = 0;
         }
         ix->kmer_table_refused = false;
@@ -707,7 +628,7 @@ int txq_emplace_device(txq_index* ix, const uint64_t* d_values, const uint32_t* 
     Index::ProbeTable& pt = ix->probe_table;
     std::lock_guard<std::mutex> lock(pt.mutex);
     ++ix->generation;
-    if (pt.recorded) TXQ_HIP(hipStreamWaitEvent((hipStream_t)stream, pt.done, 0));
+    if (pt.recorded) TXQ_HIP(hipStreamWaitEvent((hipStream_t)stream, pt.done.get(), 0));
     hipError_t e = launch_emplace(ix->ibf[0], d_values, d_bins_of, n, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "emplace kernel launch");
     return TXQ_OK;
@@ -718,7 +639,7 @@ int txq_run_programs_device(txq_index* ix, const void* blob, size_t blob_bytes, 
     if (!ix) return fail(TXQ_ERR_ARG, "null argument");
     if (int rc = bind_index(ix)) return rc;
     if (!ix || !blob || (n_programs && !d_final_masks)) return fail(TXQ_ERR_ARG, "null argument");
-    return run_programs(*ix, blob, blob_bytes, n_programs, d_final_masks, (hipStream_t)stream);
+    return run_programs(*ix, blob, blob_bytes, n_programs, d_final_masks, false, (hipStream_t)stream);
 }
 
 int txq_run_programs(txq_index* ix, const void* blob, size_t blob_bytes, size_t n_programs, uint64_t* final_masks) {
@@ -726,12 +647,8 @@ int txq_run_programs(txq_index* ix, const void* blob, size_t blob_bytes, size_t 
     if (!ix) return fail(TXQ_ERR_ARG, "null argument");
     if (int rc = bind_index(ix)) return rc;
     if (!ix || !blob || (n_programs && !final_masks)) return fail(TXQ_ERR_ARG, "null argument");
-    const size_t bytes = n_programs * ix->shard_words * 8;
-    if (bytes == 0) return TXQ_OK;
-    if (int rc = ensure((void**)&ix->scratch_final, &ix->cap_final, bytes)) return rc;
-    if (int rc = run_programs(*ix, blob, blob_bytes, n_programs, ix->scratch_final, nullptr)) return rc;
-    TXQ_HIP(hipMemcpy(final_masks, ix->scratch_final, bytes, hipMemcpyDeviceToHost));
-    return TXQ_OK;
+    if (n_programs * ix->shard_words == 0) return TXQ_OK;
+    return run_programs(*ix, blob, blob_bytes, n_programs, final_masks, true, nullptr);
 }
 
 int txq_session_begin(txq_index* ix, size_t n_programs, txq_session** out) {
@@ -794,38 +711,9 @@ int txq_session_end(txq_session* s, uint64_t* final_masks) {
         // a stage of this session failed: its slots hold half-executed state, there are no final masks to hand out
         rc = fail(TXQ_ERR_STATE, "a stage of this session failed: it has no final masks");
     } else if (final_masks && s->n_programs && s->W) {
-        Index& ix = *s->ix;
-        const size_t bytes = s->n_programs * (size_t)ix.shard_words * 8;  // (a layout-order session hands out user-bin masks too)
-        if (s->kn.final_pinned && !s->vspace && bytes <= ((size_t)64 << 20)) {  // (layout-order rows are first put back in user-bin order, with atomics: on the device)
-            // The gather kernel writes the masks straight into pinned host memory (kept with the index): no copy engine is
-            // involved.  In a fresh process (`tetrex query`) the device-to-host copy of a session's 25 KB of final masks took
-            // 8 ms with the device idle — pageable or pinned destination, hipMemcpy or hipMemcpyAsync alike —, as much as the
-            // whole batch on the device; the kernel's stores over the link take 0.02 ms (profiles/r4_cold_cli_final_masks.txt).
-            if (ix.cap_host_final < bytes) {
-                if (ix.host_final) (void)hipHostFree(ix.host_final);
-                ix.host_final = nullptr;
-                ix.cap_host_final = 0;
-                const size_t cap = std::max<size_t>(bytes + bytes / 2, (size_t)1 << 20);
-                hipError_t e = hipHostMalloc((void**)&ix.host_final, cap, hipHostMallocDefault);
-                if (e != hipSuccess) rc = fail_hip(e, "pinned buffer for the final masks");
-                else ix.cap_host_final = cap;
-            }
-            if (rc == TXQ_OK) rc = session_finish(*s, ix.host_final, nullptr);
-            t_finish = now();
-            if (rc == TXQ_OK) {
-                hipError_t e = hipStreamSynchronize(nullptr);
-                if (e != hipSuccess) rc = fail_hip(e, "waiting for the final masks");
-                else std::memcpy(final_masks, ix.host_final, bytes);
-            }
-        } else {
-            rc = ensure((void**)&ix.scratch_final, &ix.cap_final, bytes);
-            if (rc == TXQ_OK) rc = session_finish(*s, ix.scratch_final, nullptr);
-            t_finish = now();
-            if (rc == TXQ_OK) {
-                hipError_t e = hipMemcpy(final_masks, ix.scratch_final, bytes, hipMemcpyDeviceToHost);
-                if (e != hipSuccess) rc = fail_hip(e, "copying final masks");
-            }
-        }
+        // (layout-order rows are first put back in user-bin order, with atomics: on the device)
+        const size_t bytes = s->n_programs * (size_t)s->ix->shard_words * 8;  // (a layout-order session hands out user-bin masks too)
+        rc = session_finish_host(*s, final_masks, s->kn.final_pinned && !s->vspace && bytes <= ((size_t)64 << 20), &t_finish);
         t_copy = now();
     }
     (void)hipDeviceSynchronize();

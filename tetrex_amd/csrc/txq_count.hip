@@ -362,7 +362,7 @@ static int count_flat(Index& ix, CountOut o, hipStream_t s) {
     size_t per_call = o.nq;
     if (!o.counts) per_call = std::max<size_t>(1, std::min<size_t>(o.nq, ((size_t)256 << 20) / (row * 4)));
     if (!o.counts)
-        if (int rc = ensure((void**)&ix.scratch_count_acc, &ix.cap_count_acc, per_call * row * 4)) return rc;
+        if (int rc = reserved(ix.scratch_count_acc.reserve(exactly(per_call * row * 4), after_device_wait()), "hipMalloc(scratch)")) return rc;
     for (size_t q0 = 0; q0 < o.nq; q0 += per_call) {
         CountOut c = o;
         c.nq = (uint32_t)std::min(per_call, (size_t)o.nq - q0);
@@ -370,7 +370,7 @@ static int count_flat(Index& ix, CountOut o, hipStream_t s) {
         c.thr = o.thr + q0;
         c.hits = o.hits + q0 * o.W;
         c.counts = o.counts ? o.counts + q0 * row : nullptr;
-        c.acc = o.counts ? c.counts : ix.scratch_count_acc;
+        c.acc = o.counts ? c.counts : ix.scratch_count_acc.get();
         const unsigned qgrid = (unsigned)std::min<size_t>(c.nq, kCountGrid);
         count_zero_long_kernel<<<qgrid, 64, 0, s>>>(c);
         if (!with_hash_funs(f.hash_funs, [&](auto h) { count_flat_kernel<decltype(h)::value><<<kCountGrid, 64 * kFlatWaves, lds, s>>>(f, c, lpk_log2, n_tiles); }))
@@ -400,8 +400,8 @@ static int count_hibf(Index& ix, CountOut o, hipStream_t s) {
     const size_t cap = chunk * ix.max_level_width;
     if (ix.depth > 1)
         for (int i = 0; i < 2; ++i)
-            if (int rc = ensure((void**)&ix.frontier[i], &ix.cap_frontier[i], cap * sizeof(WorkItem))) return rc;
-    if (int rc = ensure((void**)&ix.d_counts, &ix.cap_counts, ((size_t)ix.depth + 2) * 4)) return rc;
+            if (int rc = reserved(ix.frontier[i].reserve(exactly(cap * sizeof(WorkItem)), after_device_wait()), "hipMalloc(scratch)")) return rc;
+    if (int rc = reserved(ix.d_counts.reserve(exactly(((size_t)ix.depth + 2) * 4), after_device_wait()), "hipMalloc(scratch)")) return rc;
     const HibfCountView t{ix.d_ibf, ix.d_next, ix.d_tb_user, ix.d_map_off, ix.d_descend, ix.d_merged_off};
     const uint32_t lds_words = max_chunks * kLdsPitch;
     for (size_t q0 = 0; q0 < o.nq; q0 += chunk) {
@@ -412,15 +412,15 @@ static int count_hibf(Index& ix, CountOut o, hipStream_t s) {
         c.thr = o.thr + q0;
         c.hits = o.hits + q0 * o.W;
         c.counts = o.counts ? o.counts + q0 * row : nullptr;
-        TXQ_HIP(hipMemsetAsync(ix.d_counts, 0, ((size_t)ix.depth + 2) * 4, s));
+        TXQ_HIP(hipMemsetAsync(ix.d_counts.get(), 0, ((size_t)ix.depth + 2) * 4, s));
         for (uint32_t lvl = 0; lvl < ix.depth; ++lvl) {
-            const WorkItem* in = lvl ? ix.frontier[(lvl - 1) & 1] : nullptr;
-            const uint32_t* in_count = lvl ? ix.d_counts + (lvl - 1) : nullptr;
-            WorkItem* out = ix.frontier[lvl & 1];
+            const WorkItem* in = lvl ? ix.frontier[(lvl - 1) & 1].get() : nullptr;
+            const uint32_t* in_count = lvl ? ix.d_counts.get() + (lvl - 1) : nullptr;
+            WorkItem* out = ix.frontier[lvl & 1].get();
             const uint32_t out_cap = ix.depth > 1 && lvl + 1 < ix.depth ? (uint32_t)cap : 0u;
             const unsigned grid = lvl ? kCountGrid : (unsigned)std::min<size_t>(c.nq, kCountGrid);
             if (!with_hash_funs(h_max, [&](auto h) {
-                    count_hibf_level_kernel<decltype(h)::value><<<grid, 64, lds_words * 4, s>>>(t, c, in, in_count, (uint32_t)cap, c.nq, out, ix.d_counts + lvl,
+                    count_hibf_level_kernel<decltype(h)::value><<<grid, 64, lds_words * 4, s>>>(t, c, in, in_count, (uint32_t)cap, c.nq, out, ix.d_counts.get() + lvl,
                                                                                                 out_cap, lds_words);
                 }))
                 return fail(TXQ_ERR_ARG, "hash_funs outside 1..5");

@@ -1540,12 +1540,12 @@ Session::~Session() {
     if (aux) --aux->open_sessions;
     if (ix) --ix->open_sessions;
     for (Index::StagingSet& t : set)  // nothing of the session may still be running when its buffers change hands
-        if (t.pending) { (void)hipEventSynchronize(t.done); t.pending = false; }
+        if (t.pending) { (void)hipEventSynchronize(t.done.get()); t.pending = false; }
     if (d_step_ctr) {
         unsigned long long c[4] = {0, 0, 0, 0};
         (void)hipDeviceSynchronize();
-        (void)hipMemcpy(c, d_step_ctr, sizeof c, hipMemcpyDeviceToHost);
-        (void)hipFree(d_step_ctr);
+        (void)hipMemcpy(c, d_step_ctr.get(), sizeof c, hipMemcpyDeviceToHost);
+        d_step_ctr.reset();
         if (c[0] && ix) {
             // algorithmic bytes of the pushed steps: per live entry its list index and its mask, per item and
             // residue the rows' 16-byte (8-byte) pieces, per non-empty product a 16-byte read-modify-write of the destination
@@ -1558,30 +1558,25 @@ Session::~Session() {
         }
     }
     const double t_retire = now_s();
-    for (void* p : retired) (void)hipFree(p);
-    struct Lap {  // TXQ_TRACE: what releasing the session costs (the members' own destructors come after this)
+    const size_t n_retired = retired.size();
+    retired.clear();
+    struct Lap {  // TXQ_TRACE: what releasing the session costs (the members' own destructors come after this and find nothing to free)
         bool on; double t0; size_t retired;
         ~Lap() { if (on) fprintf(stderr, "[txq]   release: %zu outgrown staging buffers freed, then %.2f ms for buffers and blocks going back to the index\n", retired, (now_s() - t0) * 1e3); }
-    } lap{kn.trace, now_s(), retired.size()};
-    if (kn.trace && !retired.empty()) fprintf(stderr, "[txq]   release: hipFree of outgrown staging buffers %.2f ms\n", (lap.t0 - t_retire) * 1e3);
+    } lap{kn.trace, now_s(), n_retired};
+    if (kn.trace && n_retired) fprintf(stderr, "[txq]   release: hipFree of outgrown staging buffers %.2f ms\n", (lap.t0 - t_retire) * 1e3);
+    Index::SessionBuffers& mine = *this;
     if (owns_cache && ix) {  // hand the buffers back for the next session (SlotBook::hand_back says which chunks and blocks)
         Index::SessionCache& c = ix->session_cache;
-        for (const ArenaChunk& k : book.hand_back(c, W, failed, Index::kArenaKeepBytes)) (void)hipFree(k.p);
-        c.set[0] = set[0];
-        c.set[1] = set[1];
-        c.upload = upload;
-        c.side = side;
+        std::vector<ArenaChunk> dropped = book.hand_back(c, W, failed, Index::kArenaKeepBytes);
+        free_chunks<DeviceMem>(dropped);
+        static_cast<Index::SessionBuffers&>(c) = std::move(mine);
         c.in_use = false;
         return;
     }
-    for (const ArenaChunk& k : book.slots.chunks) (void)hipFree(k.p);
-    for (const ArenaChunk& k : book.block_mem.chunks) (void)hipFree(k.p);
-    for (Index::StagingSet& t : set) {
-        if (t.done) (void)hipEventDestroy(t.done);
-        for (void* p : {(void*)t.d_blob, (void*)t.d_aux, (void*)t.d_masks}) if (p) (void)hipFree(p);
-    }
-    if (upload) (void)hipStreamDestroy(upload);
-    if (side) (void)hipStreamDestroy(side);
+    free_chunks<DeviceMem>(book.slots.chunks);
+    free_chunks<DeviceMem>(book.block_mem.chunks);
+    mine = Index::SessionBuffers{};  // staging sets, streams and the buffers of the final masks: this session made them
 }
 
 int session_begin(Index& ix, size_t n_programs, Session** out) {
@@ -1600,28 +1595,22 @@ int session_begin(Index& ix, size_t n_programs, Session** out) {
         c.in_use = true;
         s->owns_cache = true;
         s->book.adopt(c, s->W);  // (the chunks, and the pooled blocks where they fit this session's masks)
-        s->set[0] = c.set[0];
-        s->set[1] = c.set[1];
-        s->upload = c.upload;
-        s->side = c.side;
-        c = Index::SessionCache{};
-        c.in_use = true;
+        static_cast<Index::SessionBuffers&>(*s) = std::move(static_cast<Index::SessionBuffers&>(c));  // (which leaves the cache's empty)
     }
-    if (s->kn.trace && hipMalloc((void**)&s->d_step_ctr, 4 * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemset(s->d_step_ctr, 0, 4 * sizeof(unsigned long long));
-    else { (void)hipGetLastError(); s->d_step_ctr = nullptr; }
+    if (s->kn.trace && s->d_step_ctr.reserve(exactly(4 * sizeof(unsigned long long)), free_now()) == 0)
+        (void)hipMemset(s->d_step_ctr.get(), 0, 4 * sizeof(unsigned long long));
+    else (void)hipGetLastError();
     const double t_streams = now_s();
-    for (hipStream_t* st : {&s->upload, &s->side})
-        if (!*st && !(*st = take_spare_stream(ix.device))) {
-            hipError_t e = hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-            if (e != hipSuccess) { delete s; return fail_hip(e, "hipStreamCreate(session)"); }
-        }
+    for (Stream* st : {&s->upload, &s->side}) {
+        if (!*st) st->reset(take_spare_stream(ix.device));
+        hipError_t e = make(*st);
+        if (e != hipSuccess) { delete s; return fail_hip(e, "hipStreamCreate(session)"); }
+    }
     const double t_events = now_s();
-    for (Index::StagingSet& t : s->set)
-        if (!t.done) {
-            hipError_t e = hipEventCreateWithFlags(&t.done, hipEventDisableTiming);
-            if (e != hipSuccess) { delete s; return fail_hip(e, "hipEventCreate(session)"); }
-        }
+    for (Index::StagingSet& t : s->set) {
+        hipError_t e = make(t.done);
+        if (e != hipSuccess) { delete s; return fail_hip(e, "hipEventCreate(session)"); }
+    }
     if (s->kn.trace) fprintf(stderr, "[txq] session begin: streams %.3f ms, events %.3f ms\n", (t_events - t_streams) * 1e3, (now_s() - t_events) * 1e3);
     *out = s;
     return TXQ_OK;
@@ -1644,29 +1633,27 @@ static bool ensure_kmer_table(Index& ix, const Knobs& kn, const DenseParams& P, 
     const uint64_t n = 1ULL << vb, bytes = n * (uint64_t)W * 8;
     if (ix.kmer_table_refused || bytes > ((uint64_t)kn.kmer_table_mb << 20)) return false;
     const double t0 = now_s();
-    uint64_t *table = nullptr, *values = nullptr;
-    if (hipMalloc((void**)&table, bytes) != hipSuccess || hipMalloc((void**)&values, n * 8) != hipSuccess) {
+    DeviceBuffer<uint64_t> table, values;  // (freed on every way out; the table moves into the index)
+    if (table.reserve(exactly(bytes), free_now()) || values.reserve(exactly(n * 8), free_now())) {
         (void)hipGetLastError();
-        if (table) (void)hipFree(table);
         ix.kmer_table_refused = true;
         return false;
     }
-    iota_kernel<<<(unsigned)std::min<uint64_t>((n + 255) / 256, 4096), 256, 0, st>>>(values, n);
+    iota_kernel<<<(unsigned)std::min<uint64_t>((n + 255) / 256, 4096), 256, 0, st>>>(values.get(), n);
     hipError_t e = hipSuccess;
     if (ix.is_hibf) {  // membership_for(., 1) of every value, in user-bin order: any tree, whatever its shape
         // the descent keeps its frontiers in the INDEX's scratch: a stage of this or another session that is still descending
         // (hibf_probe on another stream) must have finished before this descent overwrites them — once per index
         e = hipDeviceSynchronize();
-        if (e == hipSuccess && hibf_probe(ix, kn, values, n, table, nullptr, st) != TXQ_OK) e = hipErrorUnknown;
-    } else e = launch_probe(ix.ibf[0], values, n, table, nullptr, st);
+        if (e == hipSuccess && hibf_probe(ix, kn, values.get(), n, table.get(), nullptr, st) != TXQ_OK) e = hipErrorUnknown;
+    } else e = launch_probe(ix.ibf[0], values.get(), n, table.get(), nullptr, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(values);
+    values.reset();
     if (e != hipSuccess) {
-        (void)hipFree(table);
         ix.kmer_table_refused = true;
         return false;
     }
-    ix.kmer_table = table;
+    ix.kmer_table = std::move(table);
     ix.kmer_table_bits = vb;
     if (kn.trace) fprintf(stderr, "[txq] table of all %llu k-mer masks (%u bits per k-mer): %.1f MB, built in %.2f ms\n", (unsigned long long)n, vb, bytes / 1e6, (now_s() - t0) * 1e3);
     return true;
@@ -1754,7 +1741,7 @@ static bool with_rows(const RowSource& rs, const Index& ix, uint32_t W, F&& f) {
         constexpr bool WIDE = decltype(wide)::value;
         if (rs.kind == RowSource::Table) {  // one row per k-mer: H = 1, whatever the index's hash count
             TableRows<1, WIDE> r{};
-            r.table = ix.kmer_table, r.stride = W;
+            r.table = ix.kmer_table.get(), r.stride = W;
             f(r, RowsTag<RowSource::Table, 1, WIDE>{});
             return;
         }
@@ -1830,7 +1817,7 @@ struct Stage {
     const unsigned char* d_blob = nullptr;
     uint64_t* d_masks = nullptr;
     template <class T>
-    T* dev(StageTable t) const { return reinterpret_cast<T*>(set->d_aux + tables.seg[t].at); }
+    T* dev(StageTable t) const { return reinterpret_cast<T*>(set->d_aux.get() + tables.seg[t].at); }
     // stage_prologue
     hipStream_t st = nullptr;
     // the levels: what every launch takes ...
@@ -1899,7 +1886,7 @@ static hipError_t launch_sparse_units(const Stage& g, const SparseGroup* groups,
             using R = std::decay_t<decltype(rows)>;
             auto go = [&](auto u) {
                 sparse_units_kernel<T::H, T::WIDE, decltype(u)::value, R><<<(unsigned)grid, 256, 0, g.st>>>(rows, groups, n_groups, counts, prefix, g.d_dops, g.d_optr,
-                                                                                                           g.s.d_base, g.np, g.W, g.rows.g, P, U, g.s.d_step_ctr);
+                                                                                                           g.s.d_base, g.np, g.W, g.rows.g, P, U, g.s.d_step_ctr.get());
             };
             if constexpr (T::H >= 4) go(std::integral_constant<int, 2>{});
             else with_value<2, 3>(ua, go);
@@ -1930,8 +1917,8 @@ static int stage_decide(Stage& g, bool* empty) {
     // stage, before anything has been laid out.
     // A session of a few queries does not build it (0.4-1 ms: more than a single query's steps cost); it uses one that is there.
     if (g.any_dense && (!ix.is_hibf || s.kn.dense_tree < 0) && (ix.kmer_table || (long long)s.n_programs >= s.kn.kmer_table_min)) {
-        if (!s.vspace) g.table = ensure_kmer_table(ix, s.kn, bv.dense, s.W, s.upload);
-        else if (s.n_stages == 1 && !s.aux && ensure_kmer_table(ix, s.kn, bv.dense, (uint32_t)ix.shard_words, s.upload)) {
+        if (!s.vspace) g.table = ensure_kmer_table(ix, s.kn, bv.dense, s.W, s.upload.get());
+        else if (s.n_stages == 1 && !s.aux && ensure_kmer_table(ix, s.kn, bv.dense, (uint32_t)ix.shard_words, s.upload.get())) {
             s.vspace = false;
             s.W = (uint32_t)ix.shard_words;
             g.table = true;
@@ -2028,12 +2015,12 @@ static int send_tables(Stage& g) {
         s.host_aux.resize(T.bytes);
         for (const StageTables::Segment& t : T.seg)
             if (t.src && t.bytes) std::memcpy(s.host_aux.data() + t.at, t.src, t.bytes);
-        TXQ_HIP(hipMemcpyAsync(S.d_aux, s.host_aux.data(), T.bytes, hipMemcpyHostToDevice, s.upload));
+        TXQ_HIP(hipMemcpyAsync(S.d_aux.get(), s.host_aux.data(), T.bytes, hipMemcpyHostToDevice, s.upload.get()));
         return TXQ_OK;
     }
-    TXQ_HIP(hipMemcpyAsync(S.d_blob, g.blob, g.bytes, hipMemcpyHostToDevice, s.upload));
+    TXQ_HIP(hipMemcpyAsync(S.d_blob.get(), g.blob, g.bytes, hipMemcpyHostToDevice, s.upload.get()));
     for (const StageTables::Segment& t : T.seg)
-        if (t.src && t.bytes) TXQ_HIP(hipMemcpyAsync(S.d_aux + t.at, t.src, t.bytes, hipMemcpyHostToDevice, s.upload));
+        if (t.src && t.bytes) TXQ_HIP(hipMemcpyAsync(S.d_aux.get() + t.at, t.src, t.bytes, hipMemcpyHostToDevice, s.upload.get()));
     return TXQ_OK;
 }
 
@@ -2048,7 +2035,7 @@ static int stage_upload(Stage& g) {
     Index::StagingSet& S = s.set[(s.n_stages - 1) & 1];
     g.set = &S;
     if (S.pending) {
-        TXQ_HIP(hipEventSynchronize(S.done));
+        TXQ_HIP(hipEventSynchronize(S.done.get()));
         S.pending = false;
     }
     s.t_wait += now_s() - t1;
@@ -2059,40 +2046,27 @@ static int stage_upload(Stage& g) {
     // The set's buffers are idle (S.done was waited for), but hipFree drains the WHOLE device — the previous stage, which this
     // stage may want to run beside: a buffer that has to grow (how the queries fall into waves depends on the host's timing, so
     // stage sizes differ from batch to batch) is replaced generously and the old one freed with the session.
-    auto ensure_idle = [&](void** p, size_t* cap, size_t need) -> int {
-        if (*p && *cap >= need) return TXQ_OK;
-        if (*p) s.retired.push_back(*p);
-        *p = nullptr; *cap = 0;
-        const size_t want = std::max(need + need / 2, (size_t)1 << 20);
-        hipError_t e = hipMalloc(p, want);
-        if (e != hipSuccess) return fail_hip(e, "hipMalloc(staging set)");
-        *cap = want;
-        return TXQ_OK;
-    };
+    const size_t MiB = (size_t)1 << 20;
     if (!T.packed)
-        if (int rc = ensure_idle((void**)&S.d_blob, &S.cap_blob, (g.bytes + 7) & ~(size_t)7)) return rc;
-    if (int rc = ensure_idle((void**)&S.d_aux, &S.cap_aux, T.bytes + 16)) return rc;
-    g.d_blob = T.packed ? g.dev<const unsigned char>(kBlob) : S.d_blob;
+        if (int rc = reserved(S.d_blob.reserve(half_more((g.bytes + 7) & ~(size_t)7, MiB), retire_to(s.retired)), "hipMalloc(staging set)")) return rc;
+    if (int rc = reserved(S.d_aux.reserve(half_more(T.bytes + 16, MiB), retire_to(s.retired)), "hipMalloc(staging set)")) return rc;
+    g.d_blob = T.packed ? g.dev<const unsigned char>(kBlob) : S.d_blob.get();
     for (size_t p = 0; p < s.n_programs; ++p)  // (the aux buffer has its final address now)
         s.book.base[s.n_programs + p] = s.book.blocks[p].empty() ? nullptr : reinterpret_cast<uint64_t*>(g.dev<uint64_t*>(kBlockTable) + g.row_of[p]);
     const size_t nk = g.bv.n_kmers;
-    if (int rc = ensure_idle((void**)&S.d_masks, &S.cap_masks, std::max((nk ? nk : 1) * (size_t)g.W * 8, (size_t)16 << 20))) return rc;
-    g.d_masks = S.d_masks;
+    if (int rc = reserved(S.d_masks.reserve(half_more(std::max((nk ? nk : 1) * (size_t)g.W * 8, 16 * MiB), MiB), retire_to(s.retired)), "hipMalloc(staging set)")) return rc;
+    g.d_masks = S.d_masks.get();
     s.t_alloc += now_s() - t1;
     g.t_mark[3] = now_s();
     if (int rc = send_tables(g)) return rc;
     s.d_base = g.dev<uint64_t*>(kBase);
     if (!g.plan.hsteps.empty()) {
-        // scratch of the INDEX that kernels in flight may still use: replacing it drains the device (ensure), so replace it generously
-        auto ensure_scratch = [&](uint64_t** p, size_t* cap, size_t need) -> int {
-            if (*p && *cap >= need) return TXQ_OK;
-            return ensure((void**)p, cap, std::max(need + need / 2, (size_t)64 << 20));
-        };
-        if (int rc = ensure_scratch(&ix.scratch_dense_kmers, &ix.cap_dense_kmers, g.plan.most_pairs * 8)) return rc;
-        if (int rc = ensure_scratch(&ix.scratch_dense_masks, &ix.cap_dense_masks, g.plan.most_pairs * (size_t)g.W * 8)) return rc;
+        // scratch of the INDEX that kernels in flight may still use: replacing it drains the device, so replace it generously
+        if (int rc = reserved(ix.scratch_dense_kmers.reserve(half_more(g.plan.most_pairs * 8, 64 * MiB), after_device_wait()), "hipMalloc(scratch)")) return rc;
+        if (int rc = reserved(ix.scratch_dense_masks.reserve(half_more(g.plan.most_pairs * (size_t)g.W * 8, 64 * MiB), after_device_wait()), "hipMalloc(scratch)")) return rc;
     }
     g.t_mark[4] = now_s();
-    TXQ_HIP(hipStreamSynchronize(s.upload));
+    TXQ_HIP(hipStreamSynchronize(s.upload.get()));
     s.t_upload += now_s() - g.t0;
     g.t0 = now_s();
     g.t_mark[5] = g.t0;
@@ -2112,7 +2086,7 @@ static int stage_prologue(Stage& g) {
     if (s.kn.trace_stages)
         fprintf(stderr, "[txq] stage %zu: continues %d (questions %zu), moves %zu, previous pending %d -> stream %d\n", s.n_stages, (int)g.continues, g.n_q,
                 g.moves.size(), (int)prev.pending, which);
-    hipStream_t st = g.st = which ? s.side : g.caller_stream;
+    hipStream_t st = g.st = which ? s.side.get() : g.caller_stream;
     if (!g.plan.tile_groups.empty()) {
         make_tiles_kernel<<<(unsigned)g.plan.tile_groups.size(), 256, 0, st>>>(g.dev<const TileGroup>(kTileGroups), g.dev<DenseTile>(kTiles));
         TXQ_HIP(hipGetLastError());
@@ -2174,10 +2148,10 @@ static int run_hibf_steps(Stage& g, const LevelPlan& lp) {
         const size_t c0 = g.plan.chunk_first[g.chunk], c1 = g.plan.chunk_first[g.chunk + 1];
         const uint32_t pairs = g.plan.chunk_pairs[g.chunk];
         if (pairs) {
-            dense_hibf_kmers_kernel<<<(unsigned)(c1 - c0), 256, 0, g.st>>>(d_hsteps + c0, d_pair_base + c0, g.d_dops, g.bv.dense, ix.scratch_dense_kmers);
+            dense_hibf_kmers_kernel<<<(unsigned)(c1 - c0), 256, 0, g.st>>>(d_hsteps + c0, d_pair_base + c0, g.d_dops, g.bv.dense, ix.scratch_dense_kmers.get());
             TXQ_HIP(hipGetLastError());
-            if (int rc = hibf_probe(ix, s.kn, ix.scratch_dense_kmers, pairs, ix.scratch_dense_masks, nullptr, g.st)) return rc;
-            dense_hibf_combine_kernel<<<(unsigned)(c1 - c0), 256, 0, g.st>>>(d_hsteps + c0, d_pair_base + c0, g.d_dops, g.d_optr, g.W, g.bv.dense, ix.scratch_dense_masks);
+            if (int rc = hibf_probe(ix, s.kn, ix.scratch_dense_kmers.get(), pairs, ix.scratch_dense_masks.get(), nullptr, g.st)) return rc;
+            dense_hibf_combine_kernel<<<(unsigned)(c1 - c0), 256, 0, g.st>>>(d_hsteps + c0, d_pair_base + c0, g.d_dops, g.d_optr, g.W, g.bv.dense, ix.scratch_dense_masks.get());
             TXQ_HIP(hipGetLastError());
         }
         g.first_hstep = c1;
@@ -2307,7 +2281,7 @@ static int stage_epilogue(Stage& g) {
         TXQ_HIP(hipMemcpyAsync(g.alive, d_alive, g.n_q, hipMemcpyDeviceToHost, g.st));
         TXQ_HIP(hipStreamSynchronize(g.st));
     }
-    TXQ_HIP(hipEventRecord(S.done, g.st));
+    TXQ_HIP(hipEventRecord(S.done.get(), g.st));
     S.pending = true;
     if (s.kn.trace_sync) (void)hipStreamSynchronize(g.st);  // charges the device time to the stage that caused it
     s.t_device += now_s() - g.t0;
@@ -2351,7 +2325,7 @@ int session_finish(Session& s, uint64_t* d_final, hipStream_t st) {
     // (a program that never had an op has no region: its RESULT is the initial one, no bin)
     for (Index::StagingSet& t : s.set)  // stages may have run on two streams: all of them before the results are gathered
         if (t.pending) {
-            hipError_t e = hipEventSynchronize(t.done);
+            hipError_t e = hipEventSynchronize(t.done.get());
             if (e != hipSuccess) return fail_hip(e, "waiting for the last stages");
             t.pending = false;
         }
@@ -2359,8 +2333,8 @@ int session_finish(Session& s, uint64_t* d_final, hipStream_t st) {
     if (blocks > 2048) blocks = 2048;
     uint64_t* gathered = d_final;
     if (s.vspace) {  // RESULT slots are rows in layout order: gathered into scratch, then converted to user-bin order
-        if (int rc = ensure((void**)&s.ix->scratch_slots, &s.ix->cap_slots, s.n_programs * (size_t)W * 8)) return rc;
-        gathered = s.ix->scratch_slots;
+        if (int rc = reserved(s.layout_rows.reserve(exactly(s.n_programs * (size_t)W * 8), after_device_wait()), "hipMalloc(scratch)")) return rc;
+        gathered = s.layout_rows.get();
     }
     gather_result_kernel<<<(unsigned)blocks, 256, 0, st>>>(s.d_base, (uint32_t)s.n_programs, W, gathered);
     hipError_t e = hipGetLastError();
@@ -2375,11 +2349,26 @@ void preload_exec_kernels() {
     (void)hipGetLastError();
 }
 
-int run_programs(Index& ix, const void* blob, size_t bytes, size_t n_programs, uint64_t* d_final, hipStream_t st) {
+// Pinned memory that the gather kernel writes over the link (profiles/r4_cold_cli_final_masks.txt: a device-to-host copy of 25 KB
+// took 8 ms in a fresh process, the kernel's stores 0.02 ms), grown generously; or the device buffer and a copy.
+int session_finish_host(Session& s, uint64_t* final_masks, bool pinned, double* t_finish) {
+    const size_t bytes = s.n_programs * (size_t)s.ix->shard_words * 8;
+    int rc = pinned ? reserved(s.host_final.reserve(half_more(bytes, (size_t)1 << 20), free_now()), "pinned buffer for the final masks")
+                    : reserved(s.dev_final.reserve(exactly(bytes), after_device_wait()), "hipMalloc(scratch)");
+    if (rc == TXQ_OK) rc = session_finish(s, pinned ? s.host_final.get() : s.dev_final.get(), nullptr);
+    if (t_finish) *t_finish = now_s();
+    if (rc != TXQ_OK) return rc;
+    const hipError_t e = pinned ? hipStreamSynchronize(nullptr) : hipMemcpy(final_masks, s.dev_final.get(), bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip(e, pinned ? "waiting for the final masks" : "copying final masks");
+    if (pinned) std::memcpy(final_masks, s.host_final.get(), bytes);
+    return TXQ_OK;
+}
+
+int run_programs(Index& ix, const void* blob, size_t bytes, size_t n_programs, uint64_t* final, bool final_on_host, hipStream_t st) {
     Session* s = nullptr;
     if (int rc = session_begin(ix, n_programs, &s)) return rc;
     int rc = session_stage(*s, blob, bytes, nullptr, nullptr, 0, nullptr, st);
-    if (rc == TXQ_OK) rc = session_finish(*s, d_final, st);
+    if (rc == TXQ_OK) rc = final_on_host ? session_finish_host(*s, final, false) : session_finish(*s, final, st);
     // the slot arena must outlive the kernels that read it
     if (hipStreamSynchronize(st) != hipSuccess && rc == TXQ_OK) rc = fail(TXQ_ERR_HIP, "stream synchronize failed");
     delete s;

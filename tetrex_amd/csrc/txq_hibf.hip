@@ -911,19 +911,18 @@ int hibf_layout_to_user(const Index& ix, const uint64_t* d_rows, size_t n, uint6
 }
 
 // ---- upload: the plans of txq_hibf_plan.hpp go to the device ----------------------------------------------------------------
-// Every array of an upload goes through device_array: allocated (at least one element), copied, recorded in Index::uploaded —
-// which Index::release frees — and, where `counted`, added to device_bytes.
+// Every array of an upload goes through device_array: allocated (at least one element), copied, owned by Index::uploaded
+// and, where `counted`, added to device_bytes.
 // KNOWN GAP: d_merged, d_descend, d_merged_off and d_vgroups are not counted (they never were).  Counting them changes what
 // txq_index_get_info reports, so it is left to a change of its own.
 enum Counted : bool { kUncounted = false, kCounted = true };
 
 static int device_alloc(Index& ix, void** out, size_t bytes, Counted counted) {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-    if (e != hipSuccess) return fail_hip(e, "hipMalloc(index array)");
-    ix.uploaded.push_back(p);
+    DeviceBuffer<void> p;
+    if (int rc = reserved(p.reserve(exactly(bytes ? bytes : 1), free_now()), "hipMalloc(index array)")) return rc;
+    *out = p.get();
+    ix.uploaded.push_back(std::move(p));
     if (counted) ix.device_bytes += bytes;
-    *out = p;
     return TXQ_OK;
 }
 // the first `count` elements of v (all of them by default)
@@ -971,19 +970,16 @@ static int upload_split_bins(Index& ix, const LayoutPlan& p) {
     if (int rc = device_array(ix, &ix.d_vrep, s.rep_pos, kCounted)) return rc;
     if (int rc = device_array(ix, &ix.d_vsplit_range, s.ranges, kCounted)) return rc;
     if (int rc = device_array(ix, &ix.d_vsplits, s.flat, kCounted)) return rc;
-    struct Temporary {  // the entries' side bits: only the kernel below reads them
-        uint32_t* p = nullptr;
-        ~Temporary() { if (p) (void)hipFree(p); }
-    } pos;
-    TXQ_HIP(hipMalloc((void**)&pos.p, std::max<size_t>(s.side_pos.size(), 1) * 4));
-    TXQ_HIP(hipMemcpy(pos.p, s.side_pos.data(), s.side_pos.size() * 4, hipMemcpyHostToDevice));
+    DeviceBuffer<uint32_t> pos;  // the entries' side bits: only the kernel below reads them
+    if (int rc = reserved(pos.reserve(exactly(std::max<size_t>(s.side_pos.size(), 1) * 4), free_now()), "hipMalloc(side bits)")) return rc;
+    TXQ_HIP(hipMemcpy(pos.get(), s.side_pos.data(), s.side_pos.size() * 4, hipMemcpyHostToDevice));
     for (uint64_t i = 0; i < n; ++i) {  // every IBF's entries are consecutive in `flat` (its chunks are)
         if (!s.side_stride[i]) continue;
         const uint32_t e0 = s.ranges[p.chunk0[i]].first;
         const VSplitRange& last = s.ranges[p.chunk0[i] + p.padded[i] / p.cwords - 1];
         const uint32_t e1 = last.first + last.count;
         const IbfDev& f = ix.ibf[i];
-        build_side_matrix_kernel<<<(unsigned)((f.bin_size + 255) / 256), 256>>>(f.words, f.stride, f.bin_size, ix.d_vsplits + e0, pos.p + e0, e1 - e0,
+        build_side_matrix_kernel<<<(unsigned)((f.bin_size + 255) / 256), 256>>>(f.words, f.stride, f.bin_size, ix.d_vsplits + e0, pos.get() + e0, e1 - e0,
                                                                            ix.d_vside + s.side_off[i], s.side_stride[i]);
     }
     hipError_t e = hipDeviceSynchronize();
@@ -1020,13 +1016,9 @@ int hibf_upload(Index& ix, const txq_index_desc& desc, bool cleared_ok) {
     ix.ibf.reserve(n);
     ix.max_stride = 1;
     for (uint64_t i = 0; i < n; ++i) {
-        IbfDev f;
-        uint64_t bytes;
         // every IBF of the tree is kept whole; only the user-bin mask columns are sharded
-        if (int rc = alloc_ibf(desc.ibf[i], 0, desc.ibf[i].bin_words, &f, &bytes)) return rc;
-        ix.ibf.push_back(f);
-        ix.device_bytes += bytes;
-        if (f.stride > ix.max_stride) ix.max_stride = f.stride;
+        if (int rc = alloc_ibf(ix, desc.ibf[i], 0, desc.ibf[i].bin_words)) return rc;
+        ix.max_stride = std::max(ix.max_stride, ix.ibf.back().stride);
     }
     const MapsPlan maps = plan_maps(tree, desc, ix.ibf, ix.shard_word0, ix.shard_words);
     if (int rc = device_array(ix, &ix.d_ibf, ix.ibf, kCounted)) return rc;
@@ -1086,25 +1078,25 @@ static bool hibf_probe_fused(Index& ix, const Knobs& kn, const uint64_t* d_kmers
             if ((size_t)phases * n_tiles * gpp < ((size_t)1 << 31) && n_tiles < ((size_t)1 << 31)) {
                 const IbfDev& root = ix.ibf[0];
                 const uint32_t cm_words = root.stride;
-                if (int e = ensure((void**)&ix.scratch_cm, &ix.cap_cm, n * (size_t)cm_words * 8)) { *rc = e; return true; }
+                if (int e = reserved(ix.scratch_cm.reserve(exactly(n * (size_t)cm_words * 8), after_device_wait()), "hipMalloc(scratch)")) { *rc = e; return true; }
                 size_t rb = (n + 255) / 256;
                 if (rb > 256 * 32) rb = 256 * 32;
                 const bool uniform = ix.children_uniform && !kn.hibf_lane_hash;  // (A/B: per-lane hashing on a uniform tree)
                 uint32_t* d_child_rows = nullptr;
                 const IbfDev& c0 = ix.ibf[1];  // uniform: every child looks like this one
                 if (uniform) {
-                    if (int e = ensure((void**)&ix.scratch_crows, &ix.cap_crows, n * (size_t)c0.hash_funs * 4)) { *rc = e; return true; }
-                    d_child_rows = ix.scratch_crows;
+                    if (int e = reserved(ix.scratch_crows.reserve(exactly(n * (size_t)c0.hash_funs * 4), after_device_wait()), "hipMalloc(scratch)")) { *rc = e; return true; }
+                    d_child_rows = ix.scratch_crows.get();
                     h_max = c0.hash_funs;
                 }
-                hibf_root_kernel<<<(unsigned)rb, 256, 0, s>>>(ix.root_node, d_kmers, n, ix.scratch_cm, cm_words, d_child_rows, (uint32_t)c0.bin_size, c0.hash_shift, c0.hash_funs);
+                hibf_root_kernel<<<(unsigned)rb, 256, 0, s>>>(ix.root_node, d_kmers, n, ix.scratch_cm.get(), cm_words, d_child_rows, (uint32_t)c0.bin_size, c0.hash_shift, c0.hash_funs);
                 if (d_alive) {
                     hipError_t e = hipMemsetAsync(d_alive, 0, ((n + 63) / 64) * 8, s);
                     if (e != hipSuccess) { *rc = fail_hip(e, "hipMemsetAsync(alive)"); return true; }
                 }
                 const unsigned grid = (unsigned)((size_t)phases * n_tiles * gpp);
                 const int unroll = kn.hibf_unroll, store_flavour = kn.hibf_store;
-#define TXQ_CHILDREN(U, UNI) hibf_children_kernel<U, UNI><<<grid, 256, 0, s>>>((const ChildRec*)ix.d_children, ix.n_children, lpc, d_kmers, n, ix.scratch_cm, \
+#define TXQ_CHILDREN(U, UNI) hibf_children_kernel<U, UNI><<<grid, 256, 0, s>>>((const ChildRec*)ix.d_children, ix.n_children, lpc, d_kmers, n, ix.scratch_cm.get(), \
                                                                                 cm_words, d_masks, w_out, n_steps, spg, gpp, (uint32_t)n_tiles, tile, h_max, d_alive, store_flavour, d_child_rows)
                 if (uniform) {
                     if (unroll == 1) TXQ_CHILDREN(1, true);
@@ -1191,10 +1183,10 @@ int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, ui
     const size_t cap = chunk * ix.max_level_width;
     if (ix.depth > 1) {
         for (int i = 0; i < 2; ++i)
-            if (int rc = ensure((void**)&ix.frontier[i], &ix.cap_frontier[i], cap * sizeof(WorkItem))) return rc;
+            if (int rc = reserved(ix.frontier[i].reserve(exactly(cap * sizeof(WorkItem)), after_device_wait()), "hipMalloc(scratch)")) return rc;
     }
-    if (int rc = ensure((void**)&ix.d_counts, &ix.cap_counts, ((size_t)ix.depth + 2) * 4)) return rc;
-    uint32_t* overflow = ix.d_counts + ix.depth + 1;
+    if (int rc = reserved(ix.d_counts.reserve(exactly(((size_t)ix.depth + 2) * 4), after_device_wait()), "hipMalloc(scratch)")) return rc;
+    uint32_t* overflow = ix.d_counts.get() + ix.depth + 1;
     const HibfView t{ix.d_ibf, ix.d_next, ix.d_tb_user, ix.d_map_off, ix.d_merged, ix.d_descend, ix.d_merged_off, (const HibfNode*)ix.d_nodes, (uint32_t)ix.hibf_total_tbs};
     int g = 1;
     while (g < 64 && (uint32_t)g < ix.max_stride) g <<= 1;
@@ -1202,11 +1194,11 @@ int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, ui
 
     for (size_t off = 0; off < n; off += chunk) {
         const size_t m = n - off < chunk ? n - off : chunk;
-        TXQ_HIP(hipMemsetAsync(ix.d_counts, 0, ((size_t)ix.depth + 2) * 4, s));
+        TXQ_HIP(hipMemsetAsync(ix.d_counts.get(), 0, ((size_t)ix.depth + 2) * 4, s));
         for (uint32_t lvl = 0; lvl < ix.depth; ++lvl) {
-            const WorkItem* in = lvl ? ix.frontier[(lvl - 1) & 1] : nullptr;
-            const uint32_t* in_count = lvl ? ix.d_counts + (lvl - 1) : nullptr;
-            WorkItem* out = ix.frontier[lvl & 1];
+            const WorkItem* in = lvl ? ix.frontier[(lvl - 1) & 1].get() : nullptr;
+            const uint32_t* in_count = lvl ? ix.d_counts.get() + (lvl - 1) : nullptr;
+            WorkItem* out = ix.frontier[lvl & 1].get();
             // level 0 is sized by the batch; deeper levels are grid-stride over an unknown count
             size_t groups = lvl ? (size_t)2048 * 256 / g : m;
             size_t blocks = (groups * g + 255) / 256;
@@ -1214,11 +1206,11 @@ int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, ui
             if (blocks == 0) blocks = 1;
             hipError_t e = hipErrorInvalidValue;
             with_value<1, 2, 4, 8, 16, 32, 64>(g, [&](auto G) {  // (g is a power of two)
-                e = launch_level<decltype(G)::value>((unsigned)blocks, s, t, d_kmers + off, in, in_count, (uint32_t)m, out, ix.d_counts + lvl,
+                e = launch_level<decltype(G)::value>((unsigned)blocks, s, t, d_kmers + off, in, in_count, (uint32_t)m, out, ix.d_counts.get() + lvl,
                                                      (uint32_t)(ix.depth > 1 ? cap : 0), overflow, d_masks + off * w_out, w_out, (uint32_t)ix.shard_word0, w_iters);
             });
             if (e != hipSuccess) return fail_hip(e, "hibf level kernel launch");
-            hibf_clamp_kernel<<<1, 64, 0, s>>>(ix.d_counts + lvl, (uint32_t)cap);
+            hibf_clamp_kernel<<<1, 64, 0, s>>>(ix.d_counts.get() + lvl, (uint32_t)cap);
         }
     }
     if (d_alive) {

@@ -4,6 +4,7 @@
 #include "txq_records.hpp"
 #include "txq_exec_plan.hpp"
 #include "txq_probe_plan.hpp"
+#include "txq_buffers.hpp"
 #include "../../include/txq.h"
 #include <cstdlib>
 #include <map>
@@ -83,6 +84,41 @@ struct Knobs {
 Knobs knobs();      // a copy of the snapshot taken at the last entry point (published under a lock: entry points run on several threads)
 void read_knobs();  // take it (txq_api.hip)
 
+// The owners of txq_buffers.hpp on HIP's primitives.  Every allocation libtxq keeps has exactly one of them as its owner, and
+// changes hands by move only; an outgrown buffer is freed by one of four rules, named where it grows: after_device_wait(),
+// after an event the caller names (free_after), retire_to(list), or free_now() where the caller has already waited.
+struct DeviceMem {
+    static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void free(void* p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static int alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void free(void* p) { (void)hipHostFree(p); }
+};
+struct EventKind { static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); } };
+struct StreamKind { static void destroy(hipStream_t s) { (void)hipStreamDestroy(s); } };
+template <class T> using DeviceBuffer = Buffer<T, DeviceMem>;
+template <class T> using PinnedBuffer = Buffer<T, PinnedMem>;
+using Event = Handle<hipEvent_t, EventKind>;    // made by make(): no timing
+using Stream = Handle<hipStream_t, StreamKind>;  // made by make(): non-blocking
+// kernels in flight, on whatever stream, may still use the outgrown buffer
+inline auto after_device_wait() {
+    return free_after([] { (void)hipDeviceSynchronize(); });
+}
+// the event or stream if there is none yet
+inline hipError_t make(Event& e) {
+    hipEvent_t h = nullptr;
+    const hipError_t rc = e ? hipSuccess : hipEventCreateWithFlags(&h, hipEventDisableTiming);
+    if (h) e.reset(h);
+    return rc;
+}
+inline hipError_t make(Stream& s) {
+    hipStream_t h = nullptr;
+    const hipError_t rc = s ? hipSuccess : hipStreamCreateWithFlags(&h, hipStreamNonBlocking);
+    if (h) s.reset(h);
+    return rc;
+}
+
 // (the records an index keeps in HBM — HibfNode, ChildRec, VChunk, VPath, VSplit, VSplitRange — and VLevel: txq_records.hpp)
 
 // One HIBF work item: k-mer `kmer` (index into the batch) must be looked up in IBF `ibf`.
@@ -93,9 +129,10 @@ struct Index {
     bool is_hibf = false;
     uint64_t user_bins = 0, mask_words = 0, shard_word0 = 0, shard_words = 0, device_bytes = 0;
     std::vector<IbfDev> ibf;  // host copies of the device descriptors ([0] = flat IBF / HIBF root)
-    // Every array below that an HIBF upload sends to the device (txq_hibf.hip device_array) is owned through this list: a new one
-    // needs its field here and its call there, release() frees the list.
-    std::vector<void*> uploaded;
+    // The IBFs' words (IbfDev::words: the record goes to kernels by value and owns nothing) and every array below that an HIBF
+    // upload sends to the device (txq_hibf.hip device_array) are owned through this list: a new one needs its field here and its
+    // call there.  The fields that point at them die with the index.
+    std::vector<DeviceBuffer<void>> uploaded;
 
     // HIBF tree in HBM
     IbfDev* d_ibf = nullptr;         // [n_ibf]
@@ -126,8 +163,8 @@ struct Index {
     uint32_t tree_hash_max = 0;      // most hash functions of any IBF of the tree (every HIBF: set at upload)
     bool children_uniform = false;   // same rows / hash shift / hash count in every child: scalar hashing
     uint64_t children_bytes = 0;     // their matrices
-    uint32_t* scratch_crows = nullptr; size_t cap_crows = 0;  // uniform children: per k-mer its row indexes in a child
-    uint64_t* scratch_cm = nullptr; size_t cap_cm = 0;  // root pass output: per k-mer the root row (which children to visit)
+    DeviceBuffer<uint32_t> scratch_crows;  // uniform children: per k-mer its row indexes in a child
+    DeviceBuffer<uint64_t> scratch_cm;  // root pass output: per k-mer the root row (which children to visit)
     // layout order (see VChunk): built at upload for trees that are not regular, one shard, fewer than 2^32 rows per IBF
     VChunk* d_vchunks = nullptr;
     VPath* d_vpaths = nullptr;
@@ -149,22 +186,17 @@ struct Index {
     uint64_t max_level_width = 1;    // max number of IBFs on one level (bounds the frontier)
     uint32_t max_stride = 1;         // widest row over all IBFs (words)
 
-    // grow-only scratch (owned by the index; one host thread at a time)
-    uint64_t* scratch_kmers = nullptr; size_t cap_kmers = 0;
-    uint64_t* scratch_masks = nullptr; size_t cap_masks = 0;
-    WorkItem* frontier[2] = {nullptr, nullptr}; size_t cap_frontier[2] = {0, 0};
-    uint32_t* d_counts = nullptr; size_t cap_counts = 0;
-    unsigned char* scratch_blob = nullptr; size_t cap_blob = 0;
-    uint64_t* scratch_slots = nullptr; size_t cap_slots = 0;
-    uint64_t* scratch_final = nullptr; size_t cap_final = 0;
-    uint64_t* host_final = nullptr; size_t cap_host_final = 0;  // pinned: a session's final masks are gathered straight into host memory
-    uint64_t* scratch_dense_kmers = nullptr; size_t cap_dense_kmers = 0;  // dense steps on an HIBF: the pairs' k-mers ...
-    uint64_t* scratch_dense_masks = nullptr; size_t cap_dense_masks = 0;  // ... and their descended masks
-    uint32_t* scratch_count_acc = nullptr; size_t cap_count_acc = 0;      // txq_count on a flat index: long queries' partial counts
-    unsigned char* scratch_count_io = nullptr; size_t cap_count_io = 0;   // txq_count (host buffers): the call's inputs and results
+    // grow-only scratch of the descent and of txq_count (owned by the index; one host thread at a time).  No buffer of a session
+    // is among them, and none is shared between two sessions of one index: what a session uses it owns (SessionBuffers below).
+    DeviceBuffer<WorkItem> frontier[2];
+    DeviceBuffer<uint32_t> d_counts;
+    DeviceBuffer<uint64_t> scratch_dense_kmers;      // dense steps on an HIBF: the pairs' k-mers ...
+    DeviceBuffer<uint64_t> scratch_dense_masks;      // ... and their descended masks
+    DeviceBuffer<uint32_t> scratch_count_acc;        // txq_count on a flat index: long queries' partial counts
+    DeviceBuffer<unsigned char> scratch_count_io;    // txq_count (host buffers): the call's inputs and results
     // A flat index's masks of ALL k-mers, M[v] at kmer_table + v * shard_words for every packed value v < 2^(bits * k) (txq_exec.hip
     // ensure_kmer_table): where that fits TXQ_KMER_TABLE_MB, a dense step reads ONE row per k-mer instead of gathering hash_funs.
-    uint64_t* kmer_table = nullptr; uint32_t kmer_table_bits = 0;  // bits = bits per residue * k of the table that is built
+    DeviceBuffer<uint64_t> kmer_table; uint32_t kmer_table_bits = 0;  // bits = bits per residue * k of the table that is built
     bool kmer_table_refused = false;                               // (the allocation failed once: not tried again)
     std::mutex table_mutex;                                        // building / dropping the table (sessions of one index may run on several threads)
     // Calls that changed a flat index's bits after it was made: txq_emplace_device, the only writer of ibf[0].words besides upload
@@ -178,10 +210,10 @@ struct Index {
     // whatever stream, waits for it; so does txq_emplace_device before it changes the bits.  Everything here is read and
     // written under `mutex`.
     struct ProbeTable {
-        uint64_t* rows = nullptr; size_t cap_rows = 0;  // [cap_rows][stride]
-        uint32_t* state = nullptr;                      // [kStateWords]: sample accumulators, the valid-rows word twice, statistics (txq_probe_plan.hpp)
+        DeviceBuffer<uint64_t> rows; size_t cap_rows = 0;  // [cap_rows][stride]
+        DeviceBuffer<uint32_t> state;                   // [kStateWords]: sample accumulators, the valid-rows word twice, statistics (txq_probe_plan.hpp)
         ProbeKeep keep;                                 // the generation the rows belong to, the calls so far
-        hipEvent_t done = nullptr;
+        Event done;
         bool recorded = false, refused = false;         // (refused: the allocation failed once, not tried again)
         std::mutex mutex;
     } probe_table;
@@ -193,16 +225,27 @@ struct Index {
     // table of region bases.  A session alternates between two sets, so stage n+1 is uploaded (on its own stream) while
     // the kernels of stage n still read theirs; `done` is recorded behind a stage's last kernel.
     struct StagingSet {
-        unsigned char* d_blob = nullptr; size_t cap_blob = 0;
-        unsigned char* d_aux = nullptr; size_t cap_aux = 0;
-        uint64_t* d_masks = nullptr; size_t cap_masks = 0;  // M[k-mer] of the stage's k-mer table (the probe's output)
-        hipEvent_t done = nullptr;
+        DeviceBuffer<unsigned char> d_blob, d_aux;
+        DeviceBuffer<uint64_t> d_masks;  // M[k-mer] of the stage's k-mer table (the probe's output)
+        Event done;
         bool pending = false;
     };
-    struct SessionCache : BookCache {
-        StagingSet set[2];
-        hipStream_t upload = nullptr, side = nullptr;
+    // The buffers and streams a session works with.  A session that gets the cache takes them over by move and moves them
+    // back at its end; one that does not makes its own and frees them: no two sessions ever share one.
+    struct SessionBuffers {
+        StagingSet set[2];                  // stage n uses set[n & 1]
+        Stream upload;                      // the uploads' stream (non-blocking: independent of the stream the kernels run on)
+        Stream side;                        // a stage that continues nothing of the stage in flight runs beside it, on this stream
+        PinnedBuffer<uint64_t> host_final;  // the final masks are gathered straight into host memory ...
+        DeviceBuffer<uint64_t> dev_final;   // ... or (TXQ_FINAL_PINNED=0, layout order, more than 64 MiB) here and copied
+        DeviceBuffer<uint64_t> layout_rows; // a layout-order session's RESULT rows before they are put in user-bin order
+    };
+    struct SessionCache : BookCache, SessionBuffers {
         bool in_use = false;
+        ~SessionCache() {
+            free_chunks<DeviceMem>(chunks);
+            free_chunks<DeviceMem>(block_chunks);
+        }
     } session_cache;
     static constexpr size_t kArenaKeepBytes = (size_t)64 << 30;
     uint64_t user_tag = 0;  // txq_index_set_tag
@@ -212,14 +255,11 @@ struct Index {
 
     // txq_probe (host buffers): two streams with their device and pinned bounce buffers
     struct HostPipe {
-        hipStream_t stream[2] = {nullptr, nullptr};
-        hipEvent_t done[2] = {nullptr, nullptr};
-        uint64_t* d_kmers[2] = {nullptr, nullptr}; size_t cap_kmers[2] = {0, 0};
-        uint64_t* d_masks[2] = {nullptr, nullptr}; size_t cap_masks[2] = {0, 0};
-        uint64_t* bounce[2] = {nullptr, nullptr}; size_t cap_bounce[2] = {0, 0};
+        Stream stream[2];
+        Event done[2];
+        DeviceBuffer<uint64_t> d_kmers[2], d_masks[2];
+        PinnedBuffer<uint64_t> bounce[2];
     } host_pipe;
-
-    void release();
 };
 
 // Does a session on this index run dense steps fused on the tree (txq_exec.hip TreeRows / InterleavedRows)?  A regular
@@ -234,7 +274,7 @@ inline bool index_fuses_tree_steps(const Index& ix, const Knobs& kn) {
 }
 
 // A batch of programs whose slot masks persist in HBM across stages (txq_exec.hip).
-struct Session {
+struct Session : Index::SessionBuffers {
     Index* ix = nullptr;
     Index* aux = nullptr;  // optional d-gram index (flat IBF, same bins and shard as ix)
     Knobs kn;              // the environment switches as they were when the session began
@@ -245,14 +285,11 @@ struct Session {
     SlotBook book;         // the programs' slot regions and dense blocks (txq_exec_plan.hpp)
     double block_alloc_seconds = 0;  // spent in hipMalloc for block chunks (TXQ_TRACE)
     size_t n_block_memsets = 0, n_sparse_launches = 0, n_sparse_groups = 0;
-    hipStream_t side = nullptr;        // a stage that continues nothing of the stage in flight runs beside it, on the other stream
     int stream_of_last = 0;            // 0: the caller's stream, 1: `side`
     uint64_t** d_base = nullptr;  // device copy of `base` as of the last stage (lives in that stage's staging set)
-    bool owns_cache = false;      // buffers came from / go back to ix->session_cache
-    std::vector<void*> retired;   // staging buffers that were outgrown while another stage was running: freed with the session
-    Index::StagingSet set[2];     // stage n uses set[n & 1]
-    hipStream_t upload = nullptr; // the uploads' stream (non-blocking: independent of the stream the kernels run on)
-    unsigned long long* d_step_ctr = nullptr;  // TXQ_TRACE: what sparse_units_kernel did (entries, units, non-empty products, units that left a bit)
+    bool owns_cache = false;      // the SessionBuffers and the book's chunks came from / go back to ix->session_cache
+    std::vector<DeviceBuffer<void>> retired;  // staging buffers that were outgrown while another stage was running: freed with the session
+    DeviceBuffer<unsigned long long> d_step_ctr;  // TXQ_TRACE: what sparse_units_kernel did (entries, units, non-empty products, units that left a bit)
     std::vector<unsigned char> host_aux;  // a small stage is packed here and sent as one copy
     // where a stage's wall time goes (reported on stderr at session end when TXQ_TRACE is set)
     double t_validate = 0, t_upload = 0, t_device = 0;
@@ -278,8 +315,10 @@ hipStream_t take_spare_stream(int device);  // a non-blocking stream made at txq
 int require_init();  // txq_init has run; binds the calling thread to the first device
 int fail(int code, const char* fmt, ...);
 int fail_hip(hipError_t e, const char* what);
-int ensure(void** p, size_t* cap, size_t bytes);
-int alloc_ibf(const txq_ibf_desc& d, uint64_t w0, uint64_t w1, IbfDev* out, uint64_t* bytes);
+// what Buffer::reserve returned, as a TXQ_* code
+inline int reserved(int e, const char* what) { return e ? fail_hip((hipError_t)e, what) : TXQ_OK; }
+// one IBF (column slice [w0, w1) of its rows) in HBM, appended to ix.ibf and counted in ix.device_bytes (txq_api.hip)
+int alloc_ibf(Index& ix, const txq_ibf_desc& d, uint64_t w0, uint64_t w1);
 
 // An environment variable as a number in [lo, hi]; `def` where it is unset or empty.  For the knobs that are read per call
 // (TXQ_EDIT_CHUNK, TXQ_REGEX_CHUNK, TXQ_REGEX_MAX_SERIAL: tests change them between calls), not at the entry points above.
@@ -359,10 +398,14 @@ int count_windows_device(Index& ix, const uint64_t* d_values, const uint64_t* d_
                          const uint32_t* d_thr, uint64_t* d_hits, uint32_t* d_counts, hipStream_t s);
 
 // txq_exec.hip
-int run_programs(Index& ix, const void* blob, size_t blob_bytes, size_t n_programs, uint64_t* d_final, hipStream_t s);
+// (final_on_host: `final` is host memory, filled through the session's device buffer)
+int run_programs(Index& ix, const void* blob, size_t blob_bytes, size_t n_programs, uint64_t* final, bool final_on_host, hipStream_t s);
 int session_begin(Index& ix, size_t n_programs, Session** out);
 int session_stage(Session& s, const void* blob, size_t bytes, const uint32_t* q_prog, const uint32_t* q_slot, size_t n_q,
                   uint8_t* alive, hipStream_t st);
 int session_finish(Session& s, uint64_t* d_final, hipStream_t st);
+// the final masks in host memory (null stream): gathered straight into the session's pinned buffer, or (pinned == false)
+// into its device buffer and copied; *t_finish (if given): when the last launch was issued
+int session_finish_host(Session& s, uint64_t* final_masks, bool pinned, double* t_finish = nullptr);
 
 }  // namespace txq

@@ -625,17 +625,12 @@ hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* k, size_t n, u
     if (pt.refused) return launch_probe(f, k, n, m, a, s);
     bool reallocated = false;
     if (pt.cap_rows < cap) {
-        if (pt.rows) {  // growing: the kernels of an earlier call may still read the old table
-            if (pt.recorded) (void)hipEventSynchronize(pt.done);
-            (void)hipFree(pt.rows);
-            pt.rows = nullptr;
-            pt.cap_rows = 0;
-        }
-        if (!pt.state && hipMalloc((void**)&pt.state, kStateWords * sizeof(uint32_t)) != hipSuccess) pt.state = nullptr;
-        if (!pt.done && hipEventCreateWithFlags(&pt.done, hipEventDisableTiming) != hipSuccess) pt.done = nullptr;
-        if (!pt.state || !pt.done || hipMalloc((void**)&pt.rows, cap * f.stride * 8) != hipSuccess) {
+        pt.cap_rows = 0;
+        // growing: the kernels of an earlier call may still read the old table
+        const auto after_last_call = free_after([&pt] { if (pt.recorded) (void)hipEventSynchronize(pt.done.get()); });
+        if (pt.state.reserve(exactly(kStateWords * sizeof(uint32_t)), free_now()) || make(pt.done) != hipSuccess ||
+            pt.rows.reserve(exactly(cap * f.stride * 8), after_last_call)) {
             (void)hipGetLastError();  // (out of memory is not an error of this call: the rows are gathered as before)
-            pt.rows = nullptr;
             pt.refused = true;
             return launch_probe(f, k, n, m, a, s);
         }
@@ -643,19 +638,19 @@ hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* k, size_t n, u
         reallocated = true;
     }
     if (pt.recorded) {
-        hipError_t e = hipStreamWaitEvent(s, pt.done, 0);
+        hipError_t e = hipStreamWaitEvent(s, pt.done.get(), 0);
         if (e != hipSuccess) return e;
     }
     const ProbeCall call = plan_probe_call(pt.keep, ix.generation, reallocated, kn.probe_table_keep);
     pt.keep.valid = false;  // until this call's launches are through: a call after a failed one zeroes the state words again
     if (call.zero_state) {  // on this call's stream, like everything else: later calls are ordered behind it by `done`
-        hipError_t e = hipMemsetAsync(pt.state, 0, kStateWords * sizeof(uint32_t), s);
+        hipError_t e = hipMemsetAsync(pt.state.get(), 0, kStateWords * sizeof(uint32_t), s);
         if (e != hipSuccess) return e;
     }
     // a kept call is one launch: the answer counts what it had to gather and builds what the call before counted
     // (TXQ_PROBE_TABLE_FUSED=0: sample, build and answer as in a fresh call, on the rows the table holds)
     const bool sampled = call.fresh || !kn.probe_table_fused;
-    const TableArgs T{pt.rows, pt.state, kn.probe_table == 1 ? 0u : kTableRatio, (uint32_t)pt.cap_rows, (uint32_t)cap, call.fresh ? 1u : 0u,
+    const TableArgs T{pt.rows.get(), pt.state.get(), kn.probe_table == 1 ? 0u : kTableRatio, (uint32_t)pt.cap_rows, (uint32_t)cap, call.fresh ? 1u : 0u,
                       sampled ? 1u : 0u, probe_slots(pt.keep.calls - 1), (uint32_t)kn.probe_experiment, kn.probe_table_tile ? 1u : 0u};
     const uint32_t chunks = f.stride >> 1;
     hipError_t e;
@@ -667,7 +662,7 @@ hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* k, size_t n, u
     else if (chunks <= 32) e = launch_table_lpk<32>(f, k, n, m, a, T, s);
     else e = launch_table_lpk<64>(f, k, n, m, a, T, s);
     if (e != hipSuccess) return e;
-    e = hipEventRecord(pt.done, s);
+    e = hipEventRecord(pt.done.get(), s);
     if (e != hipSuccess) return e;
     pt.recorded = true;
     pt.keep.valid = true;
