@@ -73,7 +73,9 @@ class TreeRef:
         hits = np.zeros((nq, 64 * W), dtype=bool)
         t = np.asarray(thresholds, dtype=np.int64)
         level = {0: np.arange(nq)}  # IBF -> queries that visit it, level by level
+        self.level_pairs = []       # (query, IBF) pairs of this descent on every level
         while level:
+            self.level_pairs.append(sum(len(qs) for qs in level.values()))
             nxt = {}
             for i, qs in level.items():
                 c = count_on(self.ox[i], values, offsets, qs)[:, :self.descs[i]["bins"]]

@@ -3,7 +3,8 @@ out as duplicated disjoint queries go through the numpy restatement of tests/sea
 count of Index.count_windows must equal it bit for bit — on flat IBFs (the sliding kernel), column shards and regular,
 layout-shaped and split-heavy HIBFs (the windows as independent queries).  The window sets are those of
 tests/native/count_windows_sim.cpp, 5000 windows of 64 values at step 1 (many unit boundaries) and 12 windows of 10 000
-values at step 1000 (a window far longer than one pass of the workgroup)."""
+values at step 1000 (a window far longer than one pass of the workgroup); then more units than the kernel has workgroups
+and more windows than an HIBF level has waves, where a workgroup's second item starts on what its first one left in LDS."""
 import numpy as np
 import pytest
 
@@ -80,6 +81,18 @@ WINDOW_SETS = {
 }
 
 
+def mid_unit_resets():
+    """270 000 windows of 16 values: 1000 times 263 windows at step 4, then 4 at step 16 (each begins at the end of the one
+    before) and 3 at step 20 (gaps): the windows that do not slide fall on every position of a unit of 16"""
+    return joined([sliding(16, 4, 263), sliding(16, 16, 4), sliding(16, 20, 3)] * 1000)
+
+
+SCALE_SETS = {  # more units than count_windows_kernel has workgroups (test_flat_more_units_than_workgroups)
+    "units_of_one": lambda: sliding(24, 3, 20000),
+    "mid_unit_resets": mid_unit_resets,
+}
+
+
 def restated(bins, name):
     """The numpy restatement takes 0.14 ms per value of the written-out windows on the 9000-bin index (45 s for the
     simulator's sets, 41 s for the 5000 windows): there it answers the cut sim_small, and the larger sets are held to what
@@ -107,7 +120,7 @@ def flat_case(oracle, capi, bins, h, name):
     key = (bins, h, name)
     if key not in _flat_cache:
         words = random_words(bins, ROWS, 0.5, bins + h)
-        begins, lens = WINDOW_SETS[name]()
+        begins, lens = {**WINDOW_SETS, **SCALE_SETS}[name]()
         n_values = int((begins + lens.astype(np.uint64)).max()) if begins.size else 10
         values = splitmix64(bins * 31 + len(name), n_values + 3)  # (three values behind the last window)
         thr = window_thresholds(lens, shift=bins % 5)
@@ -158,6 +171,40 @@ def test_unit_and_waves_knobs_give_identical_arrays(capi, oracle, monkeypatch, b
     ix.free()
 
 
+COUNT_WINDOWS_GRID = 4096 * 4  # txq_count.hip count_windows_flat: grid = min(cw_units(n, U) * n_tiles, kCountGrid * 4)
+COUNT_WINDOWS_UNIT = 16        # txq_count_windows_plan.hpp kCountWindowsUnitDefault
+
+
+@pytest.mark.parametrize("bins,h,name,unit,waves", [(64, 2, "units_of_one", 1, 1), (64, 2, "units_of_one", 1, 4), (40, 2, "mid_unit_resets", None, None)])
+def test_flat_more_units_than_workgroups(capi, oracle, monkeypatch, bins, h, name, unit, waves):
+    """More units than the 16 384 workgroups of count_windows_kernel: a workgroup's second unit begins on the LDS counters
+    its first one left behind (they are never cleared when read), so its first window must reset them.  20 000 units of one
+    window, with one wave and with four; and 16 875 units of the default 16 windows, with windows that begin at or behind the
+    end of the one before (cw_step: reset) on every position inside a unit."""
+    for knob, value in (("TXQ_COUNT_WINDOWS_UNIT", unit), ("TXQ_COUNT_WINDOWS_WAVES", waves)):
+        if value is None:
+            monkeypatch.delenv(knob, raising=False)
+        else:
+            monkeypatch.setenv(knob, str(value))
+    words, values, begins, lens, thr, want_hits, want_counts = flat_case(oracle, capi, bins, h, name)
+    U = unit or COUNT_WINDOWS_UNIT
+    n_units, n_tiles = -(-begins.size // U), 1  # txq_count_windows_plan.hpp cw_units; one column tile up to 8192 bins
+    assert n_units * n_tiles > COUNT_WINDOWS_GRID, (n_units, n_tiles)  # count_windows_kernel: work < n_units * n_tiles, work += gridDim.x
+    if name == "mid_unit_resets":
+        ends = begins + lens.astype(np.uint64)
+        at = np.flatnonzero(begins[1:] >= ends[:-1]) + 1  # windows that share nothing with the one before
+        assert set((at % U).tolist()) == set(range(U)) and (at % U != 0).sum() > 5000
+    assert want_hits.any() and not (want_hits == np.uint64((1 << bins) - 1)).all() and want_counts.max() > 1
+    ix = capi.Index.upload_ibf(bins, ROWS, h, words)
+    hits, counts = ix.count_windows(values, begins, lens, thr, counts=True)
+    assert np.array_equal(counts, want_counts), (bins, h, name)
+    assert np.array_equal(hits, want_hits), (bins, h, name)
+    assert np.array_equal(ix.count_windows(values, begins, lens, thr), hits)  # without counts: the same hits
+    ix.free()
+    if name == "mid_unit_resets":
+        del _flat_cache[bins, h, name]  # (140 MB of expected counts that no other test asks for)
+
+
 @pytest.mark.parametrize("bins,h,name", [(1000, 3, "sim"), (9000, 5, "sim_small"), (9000, 5, "long")])
 def test_flat_column_shards_join(capi, oracle, bins, h, name):
     words, values, begins, lens, thr, want_hits, want_counts = flat_case(oracle, capi, bins, h, name)
@@ -185,11 +232,11 @@ def make_tree(oracle, name):
     return split_heavy_hibf(oracle, 7)[:3]
 
 
-def tree_windows(values, seed):
+def tree_windows(values, seed, n_values=600):
     """windows of 20 to 40 values sliding at step 5 over a concatenation of user bins' own values"""
     rng = np.random.default_rng(seed)
     parts, total = [], 0
-    while total < 600:  # (bins of a few values each: more of them)
+    while total < n_values:  # (bins of a few values each: more of them)
         parts.append(np.asarray(values[int(rng.integers(0, len(values)))], dtype=np.uint64))
         total += parts[-1].size
     v = np.concatenate(parts)
@@ -229,6 +276,27 @@ def test_hibf_windows_match_restatement(capi, oracle, tree):
                 sh.free()
             assert np.array_equal(np.concatenate(hs, axis=1), want_hits), R
             assert np.array_equal(np.concatenate(cs, axis=1), want_counts), R
+
+
+def test_hibf_more_windows_than_waves(capi, oracle):
+    """5000 windows on the 900-bin layout tree: the windows reach count_hibf as queries with their own lengths (CountOut::lens),
+    level 0 has more than 4096 (window, root) items on 4096 waves, and a deeper level more than 4096 pairs."""
+    ox, descs, values = make_tree(oracle, "layout")
+    user_bins = len(values)
+    ref = TreeRef(oracle, user_bins, descs)
+    v, begins, lens = tree_windows(values, 17, n_values=25_100)
+    assert begins.size > 5000 > 4096  # txq_count.hip count_hibf: grid = lvl ? kCountGrid : min(nq, kCountGrid), kCountGrid = 4096
+    ev, eo = expanded(v, begins, lens)
+    thr = window_thresholds(lens, 2)
+    want_hits, want_counts = ref.search(ev, eo, thr)
+    assert ref.level_pairs[0] == begins.size and max(ref.level_pairs[1:]) > 4096, ref.level_pairs
+    assert want_hits[thr > 1].any() and not want_hits[thr > lens].any()
+    ix = capi.Index.upload_hibf(user_bins, descs)
+    hits, counts = ix.count_windows(v, begins, lens, thr, counts=True)
+    assert np.array_equal(hits, want_hits)
+    assert np.array_equal(counts, want_counts)
+    assert np.array_equal(ix.count_windows(v, begins, lens, thr), hits)
+    ix.free()
 
 
 def test_refusals(capi, oracle):

@@ -146,6 +146,46 @@ def test_one_long_record_hit_from_several_units(capi, host, monkeypatch):
     assert want[:len(ends), 3].tolist() == ends and want.shape[0] >= len(ends) + 1 and (want[:, 2] == 0).all()
 
 
+GRID = 256 * 16  # txq_edit.hip, txq_edit_long.hip, txq_edit_targets.hip: kGridBlocks, the waves of every persistent grid
+
+
+def test_more_units_than_waves(capi, host, monkeypatch):
+    """Chunks and spans of 16 bytes, 120 groups of 2 to 4 KiB, each paired with eight patterns of 5 to 512 letters (every word
+    count of the short kernels) at three caps, pattern after pattern in shuffled order: about 9000 units of 1024 bytes for targets_kernel and
+    edit_kernel and sixteen times as many of 64 bytes for targets_long_kernel<16> and edit_long_kernel<16>, so every wave of
+    the 4096 takes a second and a third unit, and that unit belongs to a pair with another pattern: the pattern's match
+    vectors in LDS are rebuilt between them."""
+    letters = "ACDEFGHIKLMNPQRSTVWY"
+    rng = np.random.default_rng(53)
+    codes = E.letter_codes(letters)
+    patterns = [edit_cases.random_text(rng, letters, m, junk=0) for m in (5, 64, 65, 128, 129, 256, 300, 512)]
+    records, groups, pairs = [], [0], []
+    for g in range(120):
+        n = int(rng.integers(1, 6))
+        recs = [edit_cases.random_text(rng, letters, int(rng.integers(2100, 4000)) // n) for _ in range(n)]
+        for k, p in enumerate((g % 8, (g + 3) % 8, (g + 5) % 8)):  # edited copies of three of the patterns, each inside one record
+            r = int(rng.integers(0, n))
+            at = int(rng.integers(0, len(recs[r]) + 1))
+            recs[r] = np.concatenate([recs[r][:at], edit_cases.edited(rng, letters, patterns[p], (g + k) % 4), recs[r][at:]])
+        records += recs
+        groups.append(len(records))
+        pairs += [(int(p), g, e) for e in (0, 1, 3) for p in rng.permutation(len(patterns))]  # (in an order of its own: no period that 4096 units could fall in step with)
+    size = [sum(len(r) for r in records[groups[g]:groups[g + 1]]) for g in range(120)]
+    for per_unit in (64 * 16, (64 // 16) * 16):  # txq_text.hpp units_of(bytes, 64 lanes, chunk); txq_edit_long_plan.hpp long_units: 64 / G groups of one span, G = 16 up to 1024 letters
+        units = np.array([-(-size[g] // per_unit) for _, g, _ in pairs])
+        total = int(units.sum())
+        assert total > 2 * GRID, (per_unit, total)  # edit_kernel, targets_kernel, ..._long_kernel: u < total, u += gridDim.x
+        pattern_of_unit = np.repeat(np.array([p for p, _, _ in pairs]), units)  # pair_of_unit
+        other = float((pattern_of_unit[GRID:] != pattern_of_unit[:-GRID]).mean())
+        assert other > 0.8, other  # a wave's next unit: another pattern
+    case = ([p.tobytes() for p in patterns], [r.tobytes() for r in records], groups, pairs, codes)
+    want = _both(capi, monkeypatch, host, case, cuts=("16",))
+    counts = T.per_pair_counts(want, len(pairs))
+    assert (counts >= 1).sum() > len(pairs) // 5 and (counts == 0).sum() > len(pairs) // 5, counts
+    late = np.repeat(np.arange(len(pairs)), units)[GRID:]  # (pairs with units that are some wave's second or later one)
+    assert counts[np.unique(late)].sum() > 100
+
+
 def test_records_that_begin_at_a_chunk_start(capi, host, monkeypatch):
     """chunks and spans of 64 bytes, records of 64, 128, 64, 0, 192, 0, 0 and 64 bytes: every record begins where a lane does"""
     rng = np.random.default_rng(43)

@@ -1,6 +1,6 @@
 """GPU parity of the record filter (include/txq.h txq_regex_filter): capi.regex_filter against the host twin
 host.regex_filter — the same automaton blobs through the same inline interpreter — bit for bit, with TXQ_REGEX_CHUNK=16 and
-with the default chunk."""
+with the default chunk; and a call of more units than the persistent grids have workgroups."""
 import numpy as np
 import pytest
 
@@ -164,6 +164,98 @@ def test_text_that_is_not_16_byte_aligned(capi, automata, monkeypatch):
         assert results[at][0].tolist() == results[0][0].tolist() and results[at][1].tolist() == results[0][1].tolist(), at
     assert results[0][1].tolist() == want_status.tolist()
     _same(host.regex_filter_unpack(go, pr, oo, results[0][0], results[0][1]), want)
+
+
+UNIT_LANES, SMALL_GRID, LARGE_GRID = 256, 256 * 8, 256 * 2  # txq_regex.hip: kBlock; regex_kernel<kSmallLds> and <0>: kCus * 8 workgroups, <kLargeLds>: kCus * 2
+
+
+@pytest.fixture(scope="module")
+def many_units(automata):
+    """600 groups of one to three records, 4.2 to 9 KiB each: with chunks of 16 bytes a unit is 4096 bytes and a group two or
+    three units.  Every group is paired with four automata — (LMAEGLYN) and A(C+|G+)T of the small tier, A.{11}C or A.{9}C (by
+    the group's parity) of the 64 KiB tier, A.{12}C above it — pair after pair, so that neighbouring pairs never share a table.
+    Filler letters occur in no motif and a group holds at most one instance: record r matches automaton a exactly if a's
+    instance was planted in it."""
+    rng = np.random.default_rng(7)
+    unit = UNIT_LANES * 16
+    recs, groups, pairs, planted, last_byte = [], [0], [], {}, {}  # planted[record] = automaton, last_byte[group] = the instance's last byte in the group
+    for g in range(600):
+        size = int(rng.integers(4300, 9200))
+        body = bytearray("".join(rng.choice(list("WYQ"), size=size)).encode())
+        autos = (LDS, 3, MIDDLE[1] if g % 2 == 0 else MIDDLE[0], L2)
+        lo = hi = None
+        if g % 4 != 3:  # three groups of four hold an instance
+            a = autos[int(rng.integers(4))]
+            inst = INSTANCE[a].encode()
+            where = g % 3
+            if where == 0:
+                x = unit + len(inst) // 2 - 1           # the boundary between the group's first two units is inside the instance
+            elif where == 1:
+                x = unit * (1 + (size > 2 * unit)) - 1  # the instance's last byte is a unit's last byte
+            else:
+                x = int(rng.integers(len(inst), size))
+            lo, hi = x - len(inst) + 1, x + 1
+            body[lo:hi] = inst
+            last_byte[g] = x
+        cuts = sorted(int(c) for c in rng.integers(1, size, size=int(rng.integers(0, 3))))
+        cuts = [lo if lo is not None and lo < c < hi else c for c in cuts]  # (no cut inside the instance)
+        for b, e in zip([0] + cuts, cuts + [size]):
+            if lo is not None and b <= lo and hi <= e:  # (true of one record: no cut falls inside the instance)
+                planted[len(recs)] = a
+            recs.append(bytes(body[b:e]))
+        groups.append(len(recs))
+        pairs += [(a, g) for a in autos]
+    assert len(planted) == len(last_byte) == 450 and set(planted.values()) == {LDS, 3, MIDDLE[0], MIDDLE[1], L2}
+    want = host.regex_filter(automata, recs, groups, pairs)
+    return recs, groups, pairs, planted, last_byte, want
+
+
+def test_more_units_than_workgroups(capi, automata, many_units, monkeypatch):
+    """About 5300 units: every workgroup of the three persistent grids of regex_kernel walks over two or three units (about
+    ten on the 512-workgroup grid of the 64 KiB tier), and the units it takes one after the other belong to pairs with other
+    automata: the table in LDS is reloaded between them.  Instances planted in units from the 2048th on, some across the
+    boundary between a group's units and some that end on a unit's last byte, are found; no other record is."""
+    monkeypatch.setenv("TXQ_REGEX_CHUNK", "16")
+    recs, groups, pairs, planted, last_byte, want = many_units
+    unit = UNIT_LANES * 16  # txq_text.hpp units_of(bytes, lanes, chunk): per_unit = lanes * chunk
+    group_bytes = [sum(len(r) for r in recs[groups[g]:groups[g + 1]]) for g in range(len(groups) - 1)]
+    units = np.array([-(-group_bytes[g] // unit) for _, g in pairs])
+    assert set(units.tolist()) == {2, 3}
+    pref = np.concatenate([[0], np.cumsum(units)])  # regex_plan_kernel and scan_kernel: pref[i + 1] = units of pairs 0 .. i
+    total = int(pref[-1])
+    assert total > 2 * SMALL_GRID and total > 9 * LARGE_GRID, total  # regex_kernel: u < total, u += gridDim.x
+    owner = np.repeat(np.arange(len(pairs)), units)  # pair_of_unit
+    auto_of_unit = np.array([a for a, _ in pairs])[owner]
+    tier = {LDS: 0, 3: 0, MIDDLE[0]: 1, MIDDLE[1]: 1, L2: 2}
+    tier_of_unit = np.array([tier[a] for a in auto_of_unit.tolist()])
+    for t, grid in ((0, SMALL_GRID), (1, LARGE_GRID)):  # the two kernels that keep the table in LDS
+        changes = 0
+        for block in range(grid):
+            mine = np.arange(block, total, grid)
+            mine = mine[tier_of_unit[mine] == t]  # (a unit of another tier is skipped)
+            changes += int((auto_of_unit[mine][1:] != auto_of_unit[mine][:-1]).any())
+        # workgroups that load one automaton's table over another's.  (A workgroup of the small grid walks over 2.6 units,
+        # half of them of its tier: about one in ten takes two such units, of different automata.)
+        assert changes >= 100, (t, changes)
+    # where the planted instances lie, as (pair, unit) of the pair that looks for them
+    late = straddle = unit_end = found = 0
+    for i, (a, g) in enumerate(pairs):
+        for r in range(groups[g], groups[g + 1]):
+            if planted.get(r) == a:
+                found += 1
+                x = last_byte[g]
+                u = int(pref[i]) + x // unit
+                if u >= SMALL_GRID:
+                    late += 1
+                    straddle += (x - len(INSTANCE[a]) + 1) // unit != x // unit
+                    unit_end += x % unit == unit - 1
+    assert found == len(planted) and 3 * late >= found and straddle >= 20 and unit_end >= 20, (found, late, straddle, unit_end)
+    expect = [np.array([planted.get(r) == a for r in range(groups[g], groups[g + 1])]) for a, g in pairs]
+    _same(want, expect)
+    got, status = capi.regex_filter(automata, recs, groups, pairs, return_status=True)
+    assert status.tolist() == [0] * len(pairs)
+    _same(got, want)
+    _same(got, expect)
 
 
 def test_refused_pairs_leave_their_neighbours_alone(capi, automata, case):

@@ -16,7 +16,8 @@
 //     300-value queries their flushes cost more than the atomics they save;
 //   * at the end of a query the counters are thresholded and written once per (query, word): a hit word by ballot, and the
 //     64 u32 counts of the word as one coalesced 256-byte store.  No per-value mask is written; bytes per value h*W*8 + 8.
-// Flat IBF: the value array is cut into units of `seg` values (seg_len); a unit starts at a query boundary unless the query
+// Flat IBF: the value array is cut into units of `seg` values (seg_len, txq_count_plan.hpp: the unit arithmetic lives there,
+// where tests/native/count_units_sim.cpp runs it on the CPU); a unit starts at a query boundary unless the query
 // is longer than `seg`, so a short query is counted by ONE workgroup (four waves that share its LDS counters) and written
 // directly, and a long one (10^6 values) is spread over many workgroups that add their partial counts to a per-query row of
 // u32 accumulators (one global atomic per non-zero bin and workgroup); count_finish_kernel thresholds those rows and answers
@@ -26,6 +27,7 @@
 // columns and appends (query, child) for merged bins that pass.  Each level reads its item count from HBM: no host
 // synchronisation inside a call.
 #include "txq_internal.hpp"
+#include "txq_count_plan.hpp"
 #include "txq_count_windows_plan.hpp"
 #include <algorithm>
 
@@ -35,32 +37,8 @@ typedef uint32_t cx4 __attribute__((ext_vector_type(4)));
 
 static constexpr uint32_t kLdsPitch = 129;      // u32 counters of chunk c at lds[c * 129 + b], b < 128
 static constexpr uint32_t kTileChunks = 64;     // 16-byte chunks per column tile (8192 bins)
-static constexpr uint64_t kSegMin = 512;        // values per unit of the flat kernel, at least ...
-static constexpr uint64_t kTargetUnits = 8192;  // ... and about this many units per call
 static constexpr int kFlatWaves = 4;            // waves of a flat workgroup: they share one unit and its LDS counters
 static constexpr uint32_t kWindowsWaves = 1;    // waves of a sliding-window workgroup: 1 or 4 (TXQ_COUNT_WINDOWS_WAVES; DESIGN.md §17: one wave won)
-
-__device__ __forceinline__ uint64_t seg_len(uint64_t n) { return max(kSegMin, (n + kTargetUnits - 1) / kTargetUnits); }
-
-// the query that holds value index x (offsets[0] <= x < offsets[nq]): the last q with offsets[q] <= x < offsets[q+1]
-__device__ __forceinline__ uint32_t query_of(const uint64_t* off, uint32_t nq, uint64_t x) {
-    uint32_t lo = 1, hi = nq;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (off[mid] > x) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo - 1;
-}
-
-// where the unit that nominally starts at x really starts: x, unless x falls inside a query of at most `seg` values (that
-// query is left whole to the unit before)
-__device__ __forceinline__ uint64_t unit_start(const uint64_t* off, uint32_t nq, uint64_t end, uint64_t seg, uint64_t x) {
-    if (x >= end) return end;
-    const uint32_t q = query_of(off, nq, x);
-    const uint64_t a = off[q], b = off[q + 1];
-    return a == x || b - a > seg ? x : b;
-}
 
 struct CountOut {
     const uint64_t* values;
@@ -347,8 +325,6 @@ __global__ __launch_bounds__(64) void count_hibf_level_kernel(HibfCountView t, C
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------
 
-static constexpr unsigned kCountGrid = 4096;  // waves of a call (persistent: the work is only known on the device)
-
 static int count_flat(Index& ix, CountOut o, hipStream_t s) {
     const IbfDev& f = ix.ibf[0];
     const uint32_t chunks = f.stride == 1 ? 1u : f.stride >> 1;
@@ -359,8 +335,7 @@ static int count_flat(Index& ix, CountOut o, hipStream_t s) {
     const size_t row = (size_t)o.W * 64;
     // long queries add their partial counts to a row of u32 per query: the caller's counts, or scratch of a bounded number
     // of queries at a time
-    size_t per_call = o.nq;
-    if (!o.counts) per_call = std::max<size_t>(1, std::min<size_t>(o.nq, ((size_t)256 << 20) / (row * 4)));
+    const size_t per_call = o.counts ? o.nq : count_flat_per_call(o.nq, row);
     if (!o.counts)
         if (int rc = reserved(ix.scratch_count_acc.reserve(exactly(per_call * row * 4), after_device_wait()), "hipMalloc(scratch)")) return rc;
     for (size_t q0 = 0; q0 < o.nq; q0 += per_call) {
@@ -394,9 +369,7 @@ static int count_hibf(Index& ix, CountOut o, hipStream_t s) {
     TXQ_HIP(hipMemsetAsync(o.hits, 0, (size_t)o.nq * o.W * 8, s));
     if (o.counts) TXQ_HIP(hipMemsetAsync(o.counts, 0, (size_t)o.nq * row * 4, s));
     // a (query, IBF) pair occurs at most once: level l holds at most chunk * (IBFs on level l) items
-    const size_t cap_items = (size_t)1 << 24;
-    size_t chunk = std::max<size_t>(1, cap_items / ix.max_level_width);
-    chunk = std::min<size_t>(chunk, o.nq);
+    const size_t chunk = count_hibf_chunk(o.nq, ix.max_level_width);
     const size_t cap = chunk * ix.max_level_width;
     if (ix.depth > 1)
         for (int i = 0; i < 2; ++i)
