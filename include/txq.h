@@ -21,6 +21,7 @@
  *   txq_edit_search / _device  (no counterpart: `tetrex search --verify` confirms candidate bins by edit distance)
  *   txq_edit_search_long / _device  (the same for patterns of up to 4096 bytes, the pattern spread over the lanes of a wave)
  *   txq_edit_align / _device  (no counterpart: start and CIGAR of the pairs a search call confirmed, `--verify --align`)
+ *   txq_edit_windows / _device  (no counterpart: txq_edit_search for windows into one letter buffer, `--window --verify-windows`)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every function returns 0 on success or a
  * negative txq_status; txq_last_error() gives the message for the calling thread.  Host buffers are
@@ -63,6 +64,7 @@ extern "C" {
  *   TXQ_PROBE_BLOCKS_PER_CU, TXQ_PROBE_UNROLL, TXQ_PROBE_NT   grid and variant of the flat probe kernel
  *   TXQ_EDIT_CHUNK=<bytes>                            bytes of text per lane of the edit-distance kernel (txq_edit_search, below)
  *   TXQ_EDIT_LONG_SPAN=<bytes>                        bytes of text per lane group of the long-pattern edit-distance kernel (txq_edit_search_long, below)
+ *   TXQ_EDIT_WINDOWS_BUNDLE=1|2|4                     the most (window, bin) pairs that walk a bin's text together (txq_edit_windows, below)
  *   TXQ_COUNT_WINDOWS_UNIT=<n>, TXQ_COUNT_WINDOWS_WAVES=1|4   windows per workgroup of the sliding count and its waves (txq_count_windows, below)
  *   TXQ_PROBE_TABLE=0|1                               a flat probe's table of its batch's k-mer domain: never | whenever it fits
  *                                                     (unset: where the batch repeats its values often enough to pay for it)
@@ -349,6 +351,36 @@ int txq_edit_search_long_device(const uint8_t* d_patterns, const uint64_t* d_pat
 int txq_edit_search_long(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
                          size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs,
                          const uint8_t* codes, uint32_t* out);  /* host buffers, synchronous */
+
+/* The same for patterns that are WINDOWS into one letter buffer (`tetrex search --window --verify-windows`; not
+ * in the reference).  Window p is d_letters[d_win_begin[p] .. d_win_begin[p] + d_win_len[p]) — the array types of
+ * txq_count_windows_device —, n_windows of them in a buffer of letters_bytes bytes.  Windows may overlap, repeat, touch or
+ * leave gaps, in any order: the windows of a record are never written out.  Text, records, groups, the class table, the pairs
+ * (window, group, cap e), d_out = (d*, r, j), the refusal marker (0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFE), the size limits and the
+ * promises of the _device call — nothing allocated, nothing read back, nothing waited for, no load outside a buffer whatever
+ * the arrays say — are those of txq_edit_search / txq_edit_search_device above.  THE RESULT IS DEFINED AS what txq_edit_search
+ * answers with window p written out as pattern p.
+ * Windows of 1 .. TXQ_EDIT_MAX_PATTERN bytes run here.  txq_edit_windows_device marks a pair whose window has no letters, more
+ * than that, leaves letters_bytes, or whose window or group index is out of range, and answers the others; txq_edit_windows
+ * checks its host buffers first as txq_edit_search does (TXQ_ERR_ARG, nothing launched).
+ * Consecutive pairs of one group whose windows have the same number of 64-bit words (1, 2, 4 or 8: up to 64, 128, 256, 512
+ * letters) walk the group's text TOGETHER, up to 4 of them (2 at 4 words, 1 at 8): a lane loads and classifies each byte once
+ * and steps every pair's state.  A caller gains that by putting the windows of a record that go to one group side by side;
+ * the arrangement of the pairs changes speed, never results.
+ * d_workspace: TXQ_EDIT_WINDOWS_WORKSPACE(n_pairs) bytes of device memory, 8-byte aligned (a key and a unit count per pair).
+ *   TXQ_EDIT_CHUNK=<bytes>             as for txq_edit_search above; the lead-in is the largest of the pairs that walk together.
+ *   TXQ_EDIT_WINDOWS_BUNDLE=1|2|4      the most pairs that walk together (read at every call; 1: every pair walks alone, as
+ *                                      in txq_edit_search_device).  Unset: 4, the fastest measured, in a call of at least 8192
+ *                                      pairs, and 1 in a smaller one, where every pair has a wave of its own and walking
+ *                                      together only makes a wave's path longer.  The results do not depend on it. */
+#define TXQ_EDIT_WINDOWS_WORKSPACE(n_pairs) (16 * (size_t)(n_pairs) + 8)
+int txq_edit_windows_device(const uint8_t* d_letters, size_t letters_bytes, const uint64_t* d_win_begin, const uint32_t* d_win_len, size_t n_windows,
+                            const uint8_t* d_text, const uint64_t* d_rec_offsets, size_t n_records, size_t text_bytes,
+                            const uint64_t* d_group_offsets, size_t n_groups, const uint32_t* d_pairs, size_t n_pairs,
+                            const uint8_t* d_codes, uint32_t* d_out, void* d_workspace, void* stream);
+int txq_edit_windows(const uint8_t* letters, size_t letters_bytes, const uint64_t* win_begin, const uint32_t* win_len, size_t n_windows,
+                     const uint8_t* text, const uint64_t* rec_offsets, size_t n_records, const uint64_t* group_offsets, size_t n_groups,
+                     const uint32_t* pairs, size_t n_pairs, const uint8_t* codes, uint32_t* out);  /* host buffers, synchronous */
 
 /* Every record of a group that a pattern matches within its cap (`tetrex search --verify --all-targets`; not in
  * the reference).  Classes, Sellers' D, patterns, records, groups, pairs (pattern, group, cap e) and the refusal rules are

@@ -28,6 +28,7 @@ SYMBOLS = [
     "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
     "txq_edit_search_long", "txq_edit_search_long_device", "txq_edit_align", "txq_edit_align_device",
     "txq_edit_targets", "txq_edit_targets_device", "txq_edit_targets_long", "txq_edit_targets_long_device",
+    "txq_edit_windows", "txq_edit_windows_device",
     "txq_regex_filter", "txq_regex_filter_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
@@ -106,6 +107,10 @@ def lib():
                                       C.c_void_p, C.c_void_p]
         L.txq_edit_search_long_device.argtypes = L.txq_edit_search_device.argtypes
         L.txq_edit_search_long.argtypes = L.txq_edit_search.argtypes
+        L.txq_edit_windows_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.txq_edit_windows.argtypes = [C.c_void_p, C.c_size_t, u64p, u32p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p,
+                                       C.c_size_t, C.c_void_p, C.c_void_p]
         L.txq_edit_align_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
@@ -720,6 +725,39 @@ def edit_search_long(patterns, records, groups, pairs, codes):
     out = np.zeros((pr.shape[0], 3), dtype=np.uint32)
     check(lib().txq_edit_search_long(pat.ctypes.data, po.ctypes.data_as(u64p), po.size - 1, txt.ctypes.data, ro.ctypes.data_as(u64p), ro.size - 1,
                                      go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0], cd.ctypes.data, out.ctypes.data))
+    return out
+
+
+def edit_windows_workspace_bytes(n_pairs):
+    """TXQ_EDIT_WINDOWS_WORKSPACE: the device workspace txq_edit_windows_device needs for n_pairs pairs"""
+    return 16 * int(n_pairs) + 8
+
+
+def edit_windows_arrays(letters, win_begin, win_len, records, groups, pairs, codes):
+    """the arguments of edit_windows as contiguous arrays: (letters, window begins uint64, window lengths uint32, text bytes,
+    record offsets, group offsets, pairs (n, 3) uint32, codes)"""
+    let = np.ascontiguousarray(np.frombuffer(letters.encode() if isinstance(letters, str) else bytes(letters), dtype=np.uint8)
+                               if not isinstance(letters, np.ndarray) else letters, dtype=np.uint8)
+    wb, wl = np.ascontiguousarray(win_begin, dtype=np.uint64), np.ascontiguousarray(win_len, dtype=np.uint32)
+    txt, ro = records if isinstance(records, tuple) else _records(records)
+    txt, ro = np.ascontiguousarray(txt, dtype=np.uint8), np.ascontiguousarray(ro, dtype=np.uint64)
+    go = np.ascontiguousarray(groups, dtype=np.uint64)
+    pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 3)
+    cd = np.ascontiguousarray(codes, dtype=np.uint8)
+    if cd.size != 256 or wb.size != wl.size or ro.size < 1 or go.size < 1 or int(ro[-1]) > txt.size:
+        raise TxqError(-1, "edit_windows: windows, offsets, bytes and class table disagree")
+    return let, wb, wl, txt, ro, go, pr, cd
+
+
+def edit_windows(letters, win_begin, win_len, records, groups, pairs, codes):
+    """edit_search for patterns that are windows into one letter buffer (txq_edit_windows, include/txq.h): window p is
+    letters[win_begin[p] : win_begin[p] + win_len[p]], pairs are rows of (window, group, cap); records, groups, codes and the
+    (n, 3) uint32 result are edit_search's.  The result is what edit_search gives with every window written out."""
+    let, wb, wl, txt, ro, go, pr, cd = edit_windows_arrays(letters, win_begin, win_len, records, groups, pairs, codes)
+    out = np.zeros((pr.shape[0], 3), dtype=np.uint32)
+    check(lib().txq_edit_windows(let.ctypes.data, let.size, wb.ctypes.data_as(u64p), wl.ctypes.data_as(u32p), wb.size, txt.ctypes.data,
+                                 ro.ctypes.data_as(u64p), ro.size - 1, go.ctypes.data_as(u64p), go.size - 1, pr.ctypes.data, pr.shape[0],
+                                 cd.ctypes.data, out.ctypes.data))
     return out
 
 

@@ -114,6 +114,20 @@ size_t BinVerifier::device_max() {
     return long_env && long_env[0] == '0' && !long_env[1] ? TXQ_EDIT_MAX_PATTERN : TXQ_EDIT_LONG_MAX_PATTERN;
 }
 
+namespace {
+std::string reverse_complement(const std::string& s) {
+    std::string out(s.rbegin(), s.rend());
+    for (char& c : out) switch (c & 0xDF) {
+        case 'A': c = 'T'; break;
+        case 'C': c = 'G'; break;
+        case 'G': c = 'C'; break;
+        case 'T': case 'U': c = 'A'; break;
+        default: c = 'N'; break;  // (no class: matches nothing, as the byte it stands for)
+    }
+    return out;
+}
+}  // namespace
+
 void BinVerifier::verify(const std::vector<std::string>& queries, const std::vector<Candidate>& candidates, std::vector<Hit>& hits,
                          std::vector<std::vector<Hit>>* rows) {
     hits.assign(candidates.size(), Hit{});
@@ -125,17 +139,6 @@ void BinVerifier::verify(const std::vector<std::string>& queries, const std::vec
     std::vector<uint32_t> pattern_of(queries.size(), kNoPattern), of_candidate(candidates.size(), kNoPattern);
     std::vector<uint64_t> pat_off{0}, lengths(candidates.size());
     std::string pat;
-    const auto reverse_complement = [](const std::string& s) {
-        std::string out(s.rbegin(), s.rend());
-        for (char& c : out) switch (c & 0xDF) {
-            case 'A': c = 'T'; break;
-            case 'C': c = 'G'; break;
-            case 'G': c = 'C'; break;
-            case 'T': case 'U': c = 'A'; break;
-            default: c = 'N'; break;  // (no class: matches nothing, as the byte it stands for)
-        }
-        return out;
-    };
     const size_t longest = device_max();
     for (size_t i = 0; i < candidates.size(); ++i) {
         const uint32_t q = candidates[i].query;
@@ -344,6 +347,110 @@ void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std:
         align_on_host(bin, confirmed.data(), confirmed.size(), text, rec, letters);
     });
     align_rest(pending, candidates, letters);
+}
+
+// ---- tetrex search --window --verify-windows ---------------------------------------------------------------------------
+
+void BinVerifier::verify_windows(const std::vector<std::string>& queries, const std::vector<Window>& windows, const std::vector<Candidate>& candidates,
+                                 std::vector<Hit>& hits) {
+    hits.assign(candidates.size(), Hit{});
+    if (candidates.empty()) return;
+    const size_t strands = dna_ ? 2 : 1;
+    const char* route_env = std::getenv("TETREX_VERIFY_WINDOWS");
+    const bool all_written = route_env && std::string(route_env) == "written";
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    // by route: what the window kernel takes, and what is written out (longer windows; everything for an A/B run)
+    std::vector<size_t> on_kernel, written;
+    for (size_t i = 0; i < candidates.size(); ++i) {
+        const Window& w = windows.at(candidates[i].query);
+        if (w.begin + w.len > queries.at(w.record).size()) throw std::runtime_error("tetrex search --verify-windows: a window leaves its record");
+        (all_written || w.len == 0 || w.len > TXQ_EDIT_MAX_PATTERN ? written : on_kernel).push_back(i);
+    }
+    if (!written.empty()) {  // each distinct window becomes a string of its own: verify() and its routes, unchanged
+        std::vector<uint32_t> string_of(windows.size(), kNone);
+        std::vector<std::string> strings;
+        std::vector<Candidate> as_records;
+        for (size_t i : written) {
+            const uint32_t q = candidates[i].query;
+            if (string_of[q] == kNone) {
+                string_of[q] = (uint32_t)strings.size();
+                strings.push_back(queries[windows[q].record].substr(windows[q].begin, windows[q].len));
+            }
+            as_records.push_back({string_of[q], candidates[i].bin});
+        }
+        std::vector<Hit> answers;
+        verify(strings, as_records, answers);
+        for (size_t k = 0; k < written.size(); ++k) hits[written[k]] = std::move(answers[k]);
+    }
+    if (on_kernel.empty()) return;
+    n_candidates_ += on_kernel.size();
+    n_windows_ += on_kernel.size();
+    // by bin, and by window within the bin: the windows of a record that hit a bin are consecutive pairs, which walk together
+    std::stable_sort(on_kernel.begin(), on_kernel.end(), [&](size_t x, size_t y) {
+        return std::tie(candidates[x].bin, candidates[x].query) < std::tie(candidates[y].bin, candidates[y].query);
+    });
+    // the letters: every record with a candidate once, on a nucleotide index its reverse complement behind it; the windows
+    // that are candidates as (begin, length) into them, `strands` entries each
+    std::vector<uint64_t> base_of(queries.size(), ~0ull), win_begin;
+    std::vector<uint32_t> entry_of(windows.size(), kNone), win_len;
+    std::string letters;
+    for (size_t i : on_kernel) {
+        const uint32_t q = candidates[i].query;
+        if (entry_of[q] != kNone) continue;
+        const Window& w = windows[q];
+        const std::string& s = queries[w.record];
+        if (base_of[w.record] == ~0ull) {
+            base_of[w.record] = letters.size();
+            letters.append(s);
+            if (dna_) letters.append(reverse_complement(s));
+        }
+        entry_of[q] = (uint32_t)win_begin.size();
+        win_begin.push_back(base_of[w.record] + w.begin);
+        win_len.push_back(w.len);
+        if (dna_) {
+            win_begin.push_back(base_of[w.record] + s.size() + (s.size() - w.begin - w.len));
+            win_len.push_back(w.len);
+        }
+    }
+    std::vector<uint32_t> pairs;
+    pairs.reserve(on_kernel.size() * strands * 3);
+    for (size_t i : on_kernel)
+        for (size_t s = 0; s < strands; ++s) pairs.insert(pairs.end(), {entry_of[candidates[i].query] + (uint32_t)s, 0u, errors_});
+    const size_t n_pairs = pairs.size() / 3;
+    DeviceBuffer d_letters(letters.size() + 16), d_begin(win_begin.size() * 8), d_len(win_len.size() * 4), d_pairs(pairs.size() * 4), d_out(pairs.size() * 4);
+    DeviceBuffer d_work(TXQ_EDIT_WINDOWS_WORKSPACE(n_pairs) + 8 * on_kernel.size());  // (every call its own part: they are all in flight at once)
+    txq_check(txq_memcpy_h2d(d_letters.p, letters.data(), letters.size()), "h2d");
+    txq_check(txq_memcpy_h2d(d_begin.p, win_begin.data(), win_begin.size() * 8), "h2d");
+    txq_check(txq_memcpy_h2d(d_len.p, win_len.data(), win_len.size() * 4), "h2d");
+    txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
+    size_t n_calls = 0;
+    for_each_bin_run(0, on_kernel.size(), [&](size_t k) { return candidates[on_kernel[k]].bin; }, [&](uint32_t bin, size_t a, size_t b) {
+        ResidentBins::Bin& e = bins_.resident(bin);
+        const uint64_t* d_rec = (const uint64_t*)e.d_rec;
+        txq_check(txq_edit_windows_device((const uint8_t*)d_letters.p, letters.size(), (const uint64_t*)d_begin.p, (const uint32_t*)d_len.p, win_begin.size(),
+                                          (const uint8_t*)e.d_text, d_rec, e.n_records, e.text_bytes, d_rec + e.n_records + 1, 1,
+                                          (const uint32_t*)d_pairs.p + 3 * strands * a, (b - a) * strands, (const uint8_t*)d_codes_,
+                                          (uint32_t*)d_out.p + 3 * strands * a, (unsigned char*)d_work.p + 16 * strands * a + 8 * n_calls++, nullptr),
+                  "txq_edit_windows_device");
+    });
+    std::vector<uint32_t> out(pairs.size());
+    txq_check(txq_memcpy_d2h(out.data(), d_out.p, out.size() * 4), "d2h");  // (waits for the kernels)
+    for (size_t k = 0; k < on_kernel.size(); ++k) {  // the better strand; + wins on equal distance
+        const uint32_t* res = out.data() + 3 * strands * k;
+        const size_t i = on_kernel[k];
+        Hit& h = hits[i];
+        const std::vector<std::string>& names = bins_.at(candidates[i].bin).names;
+        for (size_t s = 0; s < strands; ++s) {
+            if (res[3 * s] == kEditNone && res[3 * s + 1] == 0xFFFFFFFEu) throw std::runtime_error("tetrex search --verify-windows: the device refused a pair of bin " + std::to_string(candidates[i].bin));
+            if (res[3 * s] != kEditNone && (h.distance == kEditNone || res[3 * s] < h.distance)) {
+                h.distance = res[3 * s];
+                h.target = &names.at(res[3 * s + 1]);
+                h.end = res[3 * s + 2];
+                h.strand = s ? '-' : '+';
+            }
+        }
+        if (h.distance != kEditNone) ++n_confirmed_;
+    }
 }
 
 // ---- tetrex search --verify --all-targets ------------------------------------------------------------------------------

@@ -81,6 +81,13 @@ class ResidentBins {
 // whole row area in one copy where that is at most 4 MiB, else only the rows written, call by call.  TETREX_VERIFY_TARGETS=host sends every pair
 // to the host.  With set_align the rows that were kept are aligned by one txq_edit_align_device call per bin on pair and triple
 // arrays built after the copy back (one more round trip a batch), the rest on the host as above.
+// `--window --verify-windows` (verify_windows): the patterns are windows of the batch's records.  The letters of
+// the records that have a candidate go up once — on a nucleotide index each record's reverse complement behind it, window
+// [a, a + l) on strand - being [L - a - l, L - a) of it —, the windows as (begin, length) into them, and the candidates, by bin
+// and by window within the bin so that consecutive windows of a record are neighbours, go to txq_edit_windows_device: one
+// call per candidate bin on its resident text, all queued before the one copy back; strands are settled as above.  Windows of
+// more than TXQ_EDIT_MAX_PATTERN letters, and with TETREX_VERIFY_WINDOWS=written every window, are written out as strings and
+// take verify() with its three routes.
 class BinVerifier {
   public:
     BinVerifier(const std::vector<std::string>& bin_paths, bool dna, uint32_t errors);
@@ -106,11 +113,19 @@ class BinVerifier {
     };
     void verify(const DevicePatterns& patterns, const std::vector<Candidate>& candidates, const std::vector<uint64_t>& lengths,
                 const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows = nullptr);
+    // `--verify-windows`: window w is letters [begin, begin + len) of queries[record]; candidates[i].query names a window.
+    struct Window {
+        uint32_t record;
+        uint64_t begin;
+        uint32_t len;
+    };
+    void verify_windows(const std::vector<std::string>& queries, const std::vector<Window>& windows, const std::vector<Candidate>& candidates,
+                        std::vector<Hit>& hits);
     size_t n_candidates() const { return n_candidates_; }
     size_t n_confirmed() const { return n_confirmed_; }
     size_t n_targets() const { return n_targets_; }  // `--all-targets`: the rows of all confirmed pairs
-    struct Routed { size_t device, device_long, host; };
-    Routed n_routed() const { return {n_device_, n_device_long_, n_host_}; }
+    struct Routed { size_t device, device_long, host, windows; };  // (windows: txq_edit_windows_device)
+    Routed n_routed() const { return {n_device_, n_device_long_, n_host_, n_windows_}; }
     void set_align(bool on) { align_ = on; }
     struct Aligned { size_t device, host; };
     Aligned n_aligned() const { return {n_align_device_, n_align_host_}; }
@@ -156,7 +171,7 @@ class BinVerifier {
     uint32_t errors_;
     uint8_t codes_[256];
     void* d_codes_ = nullptr;
-    size_t n_candidates_ = 0, n_confirmed_ = 0, n_device_ = 0, n_device_long_ = 0, n_host_ = 0;
+    size_t n_candidates_ = 0, n_confirmed_ = 0, n_device_ = 0, n_device_long_ = 0, n_host_ = 0, n_windows_ = 0;
     bool align_ = false;
     size_t n_align_device_ = 0, n_align_host_ = 0;
     size_t n_targets_ = 0;

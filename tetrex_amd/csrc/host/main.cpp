@@ -14,6 +14,9 @@
 //   tetrex search --window W [--step S] (-e E | --threshold F) [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (a local search: every record cut into overlapping windows of W letters, S apart, each answered like a record of its own,
 //      slid on the device; the rows say where on the record each bin is hit)
+//   tetrex search --window W [--step S] -e E --verify-windows [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//     (the local search confirmed: only the runs of windows whose letters are within E edits of a record of the bin, each with
+//      the distance, target and end of its nearest window; compared on the device, the windows never written out)
 //   tetrex search --translate --frame-window W [--frame-step S] (-e E | --threshold F) [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (the local search in the six frames of nucleotide records: every frame cut into overlapping windows of W residues, S apart,
 //      translated, cut and slid on the device; the rows say in which frame and where on the record, in nucleotides, each bin is hit)

@@ -32,7 +32,7 @@ struct Search {
     std::ostream* out = &std::cout;
     // --verify / --verify-frames (make_verifier)
     std::unique_ptr<BinVerifier> verifier;
-    bool align = false, all_targets = false;
+    bool align = false, all_targets = false, windows = false;  // windows: --verify-windows, the candidates are windows
 
     Search(const Args& args, const IndexImage& img, unsigned long long errors, double fraction, double started = now())
         : a(args), image(img), verbose(args.has("verbose")), with_counts(args.has("counts")), t_start(started) {
@@ -57,11 +57,14 @@ struct Search {
     }
     void report_verifier() const {
         if (!verifier) return;
-        if (verbose) std::cerr << "Verified: " << verifier->n_confirmed() << " of " << verifier->n_candidates() << " candidate pairs" << std::endl;
+        if (verbose)
+            std::cerr << "Verified: " << verifier->n_confirmed() << " of " << verifier->n_candidates() << " candidate " << (windows ? "windows" : "pairs") << std::endl;
         if (verbose && all_targets) std::cerr << "Targets: " << verifier->n_targets() << std::endl;
         if (!std::getenv("TETREX_TRACE")) return;
         const BinVerifier::Routed n = verifier->n_routed();
-        std::cerr << "[tetrex search] verify routes: device " << n.device << ", device-long " << n.device_long << ", host " << n.host << std::endl;
+        std::cerr << "[tetrex search] verify routes: device " << n.device << ", device-long " << n.device_long << ", host " << n.host;
+        if (windows) std::cerr << ", windows " << n.windows;
+        std::cerr << std::endl;
         if (!align) return;
         const BinVerifier::Aligned al = verifier->n_aligned();
         std::cerr << "[tetrex search] align routes: device " << al.device << ", host " << al.host << std::endl;
@@ -177,6 +180,12 @@ int search_translated(const Args& a, const IndexImage& image, unsigned long long
 // consecutive hit windows is one row, name \t bin path \t begin \t end [\t count/w], begin and end the 1-based inclusive
 // letter positions of the run's union, count/w those of the run's best window (the highest count, the earliest on a tie);
 // by record, bin, begin.
+// -e E --verify-windows: every hit (window, bin) is a candidate; a window is confirmed in a bin when its letters
+// are within E edits of a substring of one record of the bin (BinVerifier::verify_windows: the comparison of --verify, both
+// strands on a nucleotide index).  Rows: one for every maximal run of consecutive CONFIRMED windows of a (record, bin) — on a
+// nucleotide index of a (record, bin, strand) —, name \t bin path \t begin \t end [\t count/w] \t distance \t target \t
+// target_end [\t strand]: count/w of the run's best confirmed window, distance, target and target_end of its window of
+// least distance, the earliest on a tie (plan::confirmed_runs); by record, bin, begin.
 int search_windowed(const Args& a, const IndexImage& image, unsigned long long errors, double fraction, uint64_t window, uint64_t step) {
     Search s(a, image, errors, fraction);
     const KmerEncoder enc = s.dev.encoder();
@@ -190,15 +199,50 @@ int search_windowed(const Args& a, const IndexImage& image, unsigned long long e
     std::vector<Hit> hits, mine;
     std::string row;
     uint64_t n_searched = 0, n_hit = 0, n_rows = 0;
+    const bool dna = enc.molecule() == Molecule::DNA;
+    s.make_verifier(a.has("verify-windows"), dna);
+    const bool verify = s.verifier != nullptr;
+    s.windows = verify;
+    std::vector<std::string> seqs;  // --verify-windows: the batch's records themselves, and their windows as letters
+    std::vector<BinVerifier::Window> win_table;
+    std::vector<BinVerifier::Candidate> candidates;
+    std::vector<VerifiedHit> confirmed;
+    struct Confirmed { uint32_t query, bin, count, distance; char strand; size_t at; };  // at: its place in `confirmed`
+    std::vector<Confirmed> kept;
     auto flush = [&]() {
         if (recs.empty()) return;
         s.dev.search_windows(values, begins, lens, thresholds, s.with_counts, hits);
+        if (verify) {
+            candidates.clear();
+            for (const Hit& x : hits) candidates.push_back({x.query, x.bin});
+            s.verifier->verify_windows(seqs, win_table, candidates, confirmed);
+        }
         size_t h = 0;
         for (const Rec& r : recs) {
             mine.clear();
+            const size_t h0 = h;
             for (; h < hits.size() && hits[h].query < r.w1; ++h) mine.push_back(hits[h]);
             if (s.verbose) {
                 for (size_t i = 0; i < mine.size(); ++i) n_hit += i == 0 || mine[i].query != mine[i - 1].query;
+            }
+            if (verify) {
+                kept.clear();
+                for (size_t i = 0; i < mine.size(); ++i)
+                    if (confirmed[h0 + i].distance != 0xFFFFFFFFu)
+                        kept.push_back({mine[i].query, mine[i].bin, mine[i].count, confirmed[h0 + i].distance, confirmed[h0 + i].strand, h0 + i});
+                std::stable_sort(kept.begin(), kept.end(), [](const Confirmed& x, const Confirmed& y) {
+                    return x.bin != y.bin ? x.bin < y.bin : x.strand != y.strand ? x.strand == '+' : x.query < y.query;
+                });
+                for (const plan::WindowRun& run : plan::confirmed_runs(kept)) {
+                    const Confirmed &first = kept[run.first], &last = kept[run.last], &best = kept[run.best];
+                    row.assign(r.name).append("\t").append(image.bin_paths[first.bin]).append("\t").append(std::to_string(letter_at[first.query] + 1));
+                    row.append("\t").append(std::to_string(letter_at[last.query] + lens[last.query] + k - 1));
+                    s.append_count(row, best.count, lens[best.query]);
+                    s.append_verified(row, confirmed[kept[run.nearest].at], dna);
+                    *s.out << row << '\n';
+                    ++n_rows;
+                }
+                continue;
             }
             std::stable_sort(mine.begin(), mine.end(), [](const Hit& x, const Hit& y) { return x.bin < y.bin; });
             plan::for_each_run(mine, [&](const Hit& first, const Hit& last, const Hit& best) {
@@ -210,6 +254,8 @@ int search_windowed(const Args& a, const IndexImage& image, unsigned long long e
             });
         }
         recs.clear();
+        seqs.clear();
+        win_table.clear();
         values.clear();
         begins.clear();
         letter_at.clear();
@@ -237,11 +283,13 @@ int search_windowed(const Args& a, const IndexImage& image, unsigned long long e
             n_searched += t != 0;
             begins.push_back(base + at.a);
             letter_at.push_back(at.a);
+            if (verify) win_table.push_back({(uint32_t)recs.size(), at.a, (uint32_t)at.len});
             lens.push_back((uint32_t)w);
             thresholds.push_back((uint32_t)std::min<uint64_t>(t, 0xFFFFFFFEull));
         }
         rec.w1 = begins.size();
         recs.push_back(std::move(rec));
+        if (verify) seqs.push_back(r.seq);
         if (unsearched) std::cerr << "[tetrex search] " << r.name << ": a window with threshold 0 is not searched" << std::endl;
     });
     flush();
@@ -398,7 +446,7 @@ int search_plain(const Args& a, const IndexImage& image, unsigned long long erro
 int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
                                        {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false},
-                                       {'\0', "verify-frames", false}, {'\0', "align", false}, {'\0', "all-targets", false},
+                                       {'\0', "verify-frames", false}, {'\0', "verify-windows", false}, {'\0', "align", false}, {'\0', "all-targets", false},
                                        {'\0', "window", true}, {'\0', "step", true}, {'\0', "frame-window", true}, {'\0', "frame-step", true}};
     Args a;
     unsigned long long errors = 0, window = 0, step = 0, frame_window = 0, frame_step = 0;
@@ -413,7 +461,7 @@ int cmd_search(int argc, char** argv) {
             if (!a.has("translate")) throw std::runtime_error("--frame-window cuts the translated frames of --translate into windows: it needs --translate");
             if (a.has("window")) throw std::runtime_error("--frame-window cannot be combined with --window: one counts residues of a translated frame, the other letters of the record");
             if (a.has("step")) throw std::runtime_error("--frame-window cannot be combined with --step: the distance between frame windows is --frame-step");
-            for (const char* o : {"verify-frames", "all-targets", "align", "verify"})
+            for (const char* o : {"verify-windows", "verify-frames", "all-targets", "align", "verify"})
                 if (a.has(o)) throw std::runtime_error(std::string("--frame-window cannot be combined with --") + o + ": frame windows are not verified in this version");
             if (!a.has("errors") && !a.has("threshold")) throw std::runtime_error("--frame-window needs -e E or --threshold F");
             frame_window = parse_count(a.get("frame-window", ""), "--frame-window must be a number of residues >= k", 1, 0x7FFFFFFFull);
@@ -421,11 +469,19 @@ int cmd_search(int argc, char** argv) {
             if (a.has("frame-step"))
                 frame_step = parse_count(a.get("frame-step", ""), "--frame-step must be a number of residues in 1 .. --frame-window", 1, frame_window);
         }
+        if (a.has("verify-windows")) {
+            if (a.has("translate")) throw std::runtime_error("--verify-windows cannot be combined with --translate: it confirms the windows of --window, which --translate does not cut");
+            if (!a.has("window")) throw std::runtime_error("--verify-windows confirms the windows of --window W: it needs --window");
+            if (a.has("threshold")) throw std::runtime_error("--verify-windows confirms the windows of -e E: it cannot be combined with --threshold");
+            if (!a.has("errors")) throw std::runtime_error("--verify-windows needs -e E: the number of edits a confirmed window may be away");
+            for (const char* o : {"verify-frames", "all-targets", "align", "verify"})
+                if (a.has(o)) throw std::runtime_error(std::string("--verify-windows cannot be combined with --") + o + ": a confirmed window gets its distance, target and end, nothing more in this version");
+        }
         if (a.has("window")) {
             if (a.has("translate")) throw std::runtime_error("--window cannot be combined with --translate: translated frames lose their positions where stops are taken out (translated records: --frame-window)");
             if (a.has("verify-frames")) throw std::runtime_error("--window cannot be combined with --verify-frames: it confirms translated frames, which --window does not search");
             for (const char* o : {"all-targets", "align", "verify"})
-                if (a.has(o)) throw std::runtime_error(std::string("--window cannot be combined with --") + o + ": windows are not verified in this version");
+                if (a.has(o)) throw std::runtime_error(std::string("--window cannot be combined with --") + o + ": windows are confirmed with --verify-windows");
             if (!a.has("errors") && !a.has("threshold")) throw std::runtime_error("--window needs -e E or --threshold F");
             window = parse_count(a.get("window", ""), "--window must be a number of letters >= k", 1, 0x7FFFFFFFull);
             step = std::max<unsigned long long>(1, window / 2);

@@ -45,6 +45,35 @@ void for_each_run(const std::vector<Hit>& hits, Each&& each) {
     }
 }
 
+// --verify-windows: the CONFIRMED windows of one record (.query: the window, .bin, .count, .distance, .strand
+// '+' or '-'; a window is there once per bin, on the strand that verification settled), sorted by bin, then strand (+ first),
+// then window.  Every maximal run of consecutive windows of one (bin, strand) is one row: its first and last item, its best
+// one by count (the highest, the earliest window on a tie: for_each_run's rule) and its nearest one (the least distance, the
+// earliest window on a tie), as indexes into the items.  The rows come by bin, then by their first window, + before -.
+struct WindowRun {
+    size_t first, last, best, nearest;
+};
+template <class Item>
+std::vector<WindowRun> confirmed_runs(const std::vector<Item>& items) {
+    std::vector<WindowRun> runs;
+    for (size_t i = 0; i < items.size();) {
+        WindowRun r{i, i, i, i};
+        size_t e = i + 1;
+        while (e < items.size() && items[e].bin == items[i].bin && items[e].strand == items[i].strand && items[e].query == items[e - 1].query + 1) {
+            if (items[e].count > items[r.best].count) r.best = e;
+            if (items[e].distance < items[r.nearest].distance) r.nearest = e;
+            r.last = e++;
+        }
+        runs.push_back(r);
+        i = e;
+    }
+    std::stable_sort(runs.begin(), runs.end(), [&](const WindowRun& x, const WindowRun& y) {
+        if (items[x.first].bin != items[y.first].bin) return items[x.first].bin < items[y.first].bin;
+        return items[x.first].query < items[y.first].query;
+    });
+    return runs;
+}
+
 // Device batches: batch i is the items [cut[i], cut[i + 1]); most_*: the largest batch's, for buffers sized before the first
 // batch runs ("Host")
 struct Cuts {
