@@ -18,7 +18,7 @@ KNOBS = [
     {"TXQ_KMER_TABLE_MIN": "1", "TXQ_KMER_TABLE_MB": "0"}, {"TXQ_KMER_TABLE_MIN": "1", "TXQ_DENSE_SLICES": "1", "TXQ_FUSE_UNITS": "0"},
     {"TXQ_HIBF_INTERLEAVE": "0"}, {"TXQ_HIBF_INTERLEAVE_PROBE": "0"}, {"TXQ_HIBF_LEVELS": "1"}, {"TXQ_HIBF_STATIONARY": "0"},
     {"TXQ_HIBF_SMALL": "0"}, {"TXQ_HIBF_LANE_HASH": "1"}, {"TXQ_HIBF_STEPS_PER_GROUP": "1"}, {"TXQ_HIBF_TILE": "256"},
-    {"TXQ_HIBF_UNROLL": "2"}, {"TXQ_HIBF_UNROLL": "4"}, {"TXQ_HIBF_STORE_KIND": "1"}, {"TXQ_HIBF_STORE_KIND": "2"}, {"TXQ_HIBF_STORE_KIND": "3"},
+    {"TXQ_HIBF_UNROLL": "2"}, {"TXQ_HIBF_UNROLL": "4"}, {"TXQ_HIBF_UNROLL": "1"}, {"TXQ_HIBF_UNROLL": "3"}, {"TXQ_HIBF_UNROLL": "8"}, {"TXQ_HIBF_STORE_KIND": "1"}, {"TXQ_HIBF_STORE_KIND": "2"}, {"TXQ_HIBF_STORE_KIND": "3"},
     {"TXQ_HIBF_STORE": "48"},  # (the removed experiment switch: must change nothing)
     # pushed steps of tracked blocks (TETREX_DENSE_TRACKED=1 is the host's switch for them): by units, in rounds, and the units' knobs
     {"TETREX_DENSE_TRACKED": "1"}, {"TETREX_DENSE_TRACKED": "1", "TXQ_SPARSE_STEPS": "0"}, {"TETREX_DENSE_TRACKED": "1", "TXQ_SPARSE_UNROLL": "2"},

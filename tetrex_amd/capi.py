@@ -235,11 +235,13 @@ class DeviceBuffer:
             check(lib().txq_memcpy_h2d(b.ptr, a.ctypes.data, a.nbytes))
         return b
 
-    def to_numpy(self, dtype, shape):
+    def to_numpy(self, dtype, shape, offset=0):
+        """A copy of the bytes [offset, offset + size of the array) of the allocation."""
         out = np.empty(shape, dtype=dtype)
-        assert out.nbytes <= self.nbytes
+        offset = int(offset)
+        assert offset >= 0 and offset + out.nbytes <= self.nbytes
         if out.nbytes:
-            check(lib().txq_memcpy_d2h(out.ctypes.data, self.ptr, out.nbytes))
+            check(lib().txq_memcpy_d2h(out.ctypes.data, self.ptr + offset, out.nbytes))
         return out
 
     def free(self):

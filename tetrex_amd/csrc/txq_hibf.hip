@@ -11,6 +11,7 @@
 // No host round trip between levels: each level kernel reads its item count from HBM.
 #include "txq_internal.hpp"
 #include "txq_hibf_plan.hpp"
+#include "txq_hibf_descent_plan.hpp"
 #include <cstdlib>
 #include <cstring>
 #include <utility>
@@ -388,7 +389,7 @@ static hipError_t launch_fused(unsigned grid, unsigned threads, size_t lds_bytes
 // one after the other (a k-mer of such a tree visits two or three) and the workgroup writes its 256 rows
 // out together, coalesced.  The tree (about a MB) is L2-resident; 64 independent descents per wave
 // supply the memory-level parallelism that the wave-per-k-mer kernel gets from 64 IBFs per round.
-constexpr uint32_t kSmallThreads = 256, kSmallStack = 32, kSmallPitch = kSmallThreads + 1;
+// (kSmallThreads = 256 lanes, kSmallStack = 32 entries, kSmallPitch = kSmallThreads + 1: txq_hibf_descent_plan.hpp)
 
 __global__ __launch_bounds__(256) void hibf_small_kernel(HibfView t, const uint64_t* __restrict__ kmers, size_t n,
                                                          uint64_t* __restrict__ masks, uint32_t w_out, uint32_t word0,
@@ -774,28 +775,39 @@ __global__ __launch_bounds__(256) void build_side_matrix_kernel(const uint64_t* 
     out[word] = acc;
 }
 
-// Waves per workgroup of hibf_fused_kernel: its waves share nothing (a wave's row and stack are its own piece of the LDS, only
-// wave-level synchronisation), so the block size is free — taken so that the CU's 160 KB of LDS hold the most waves (a 22 KB
-// layout-order row of the 65 536-bin trees: 7 single-wave blocks against 3 blocks of two; an 11 KB user-order row: 14 against 12).
-// Entries of a wave's IBF stack kept in LDS (TXQ_HIBF_STACK_LDS, default 128; even: the stack follows the row's 8-byte words);
-// the whole stack when the output row could not take the rest.
-static uint32_t fused_stack_lds(const Knobs& kn, uint32_t stack_cap, uint32_t w_out) {
-    uint32_t in_lds = (uint32_t)std::max(2LL, kn.hibf_stack_lds) & ~1u;
-    if (in_lds >= stack_cap || (uint64_t)stack_cap - in_lds > 2ull * w_out) in_lds = (stack_cap + 1) & ~1u;
-    return in_lds;
+// What the launchers below know about the index and the switches, as txq_hibf_descent_plan.hpp takes them: the path choice and every
+// grid, LDS size and loop count of the descent are computed there (fused_stack_lds and fused_waves_per_block live there too).
+static DescentShape descent_shape(const Index& ix, const Knobs& kn) {
+    DescentShape sh;
+    sh.shard_words = (uint32_t)ix.shard_words;
+    sh.n_ibf = ix.ibf.size();
+    sh.total_tbs = ix.hibf_total_tbs;
+    sh.max_stride = ix.max_stride;
+    sh.max_level_width = ix.max_level_width;
+    sh.depth = ix.depth;
+    sh.has_nodes = ix.d_nodes != nullptr;
+    sh.n_children = ix.d_children ? ix.n_children : 0;
+    sh.child_row_words = ix.child_row_words;
+    sh.children_bytes = ix.children_bytes;
+    sh.children_uniform = ix.children_uniform;
+    sh.root_stride = ix.ibf.empty() ? 1u : ix.ibf[0].stride;
+    sh.probes_interleaved = ix.probes_interleaved(kn);
+    return sh;
 }
-
-static unsigned fused_waves_per_block(size_t wave_bytes) {
-    constexpr size_t kLdsPerCu = 160u << 10, kGranule = 1280;  // (allocation granule: the larger of the documented ones — a safe count)
-    unsigned best = 1;
-    size_t best_resident = 0;
-    for (unsigned w = 4; w >= 1; w >>= 1) {
-        if (wave_bytes * w > (64u << 10)) continue;
-        const size_t block = (wave_bytes * w + kGranule - 1) / kGranule * kGranule;
-        const size_t resident = std::min<size_t>(kLdsPerCu / block * w, 32);  // (a CU runs at most 8 waves per SIMD: short rows keep blocks of four)
-        if (resident > best_resident) { best_resident = resident; best = w; }  // (ties: the larger block, met first)
-    }
-    return best;
+static DescentKnobs descent_knobs(const Knobs& kn) {
+    DescentKnobs k;
+    k.levels = kn.hibf_levels;
+    k.stationary = kn.hibf_stationary;
+    k.small = kn.hibf_small;
+    k.lane_hash = kn.hibf_lane_hash;
+    k.layout_fused = kn.hibf_layout_fused;
+    k.layout_direct = kn.hibf_layout_direct;
+    k.steps_per_group = kn.hibf_steps_per_group;
+    k.tile = kn.hibf_tile;
+    k.unroll = kn.hibf_unroll;
+    k.waves = kn.hibf_waves;
+    k.stack_lds = kn.hibf_stack_lds;
+    return k;
 }
 
 // The layout-order rows with ONE wave per k-mer (hibf_fused_kernel<G, LAYOUT>): the wave walks the IBFs the k-mer reaches,
@@ -804,31 +816,17 @@ static unsigned fused_waves_per_block(size_t wave_bytes) {
 // does not fit a wave's share of the LDS, or TXQ_HIBF_LAYOUT_FUSED=0, false: the level kernels.
 static bool layout_order_fused(Index& ix, const uint64_t* d_kmers, size_t n, uint64_t* d_rows, hipStream_t s, int* rc) {
     const Knobs kn = knobs();
-    if (!ix.d_vnodes || !kn.hibf_layout_fused) return false;
-    const uint32_t w_out = ix.v_words, stack_cap = (uint32_t)ix.ibf.size();
     // (TXQ_HIBF_LAYOUT_DIRECT=0: the row in LDS, written out when the k-mer is done — the A/B and what the tests compare with)
-    const bool direct = kn.hibf_layout_direct;
-    const uint32_t stack_lds = direct ? ((stack_cap + 1) & ~1u) : fused_stack_lds(kn, stack_cap, w_out);
-    const uint32_t row_lds_words = direct ? 0 : w_out;
-    const size_t wave_words = (size_t)row_lds_words + stack_lds / 2, wave_bytes = wave_words * 8;
-    if (wave_bytes > (64u << 10)) return false;
-    uint32_t h_max = ix.tree_hash_max;
+    const FusedPlan p = plan_fused_layout(ix.v_words, ix.ibf.size(), ix.max_stride, ix.d_vnodes != nullptr, ix.d_vnonrep != nullptr, descent_knobs(kn), n);
+    if (!p.ok) return false;
+    const uint32_t w_out = ix.v_words, h_max = ix.tree_hash_max;
     HibfView t{ix.d_ibf, ix.d_next, ix.d_tb_user, ix.d_map_off, ix.d_merged, ix.d_merged, ix.d_merged_off, (const HibfNode*)ix.d_vnodes, (uint32_t)ix.hibf_total_tbs};
     t.nonrep = ix.d_vnonrep;
     t.rep_pos = ix.d_vrep;
-    const unsigned waves = fused_waves_per_block(wave_bytes);
-    const size_t want_waves = kn.hibf_waves > 0 ? (size_t)kn.hibf_waves : (size_t)256 * 64;
-    const size_t total_waves = n < want_waves ? n : want_waves;
-    const unsigned grid = (unsigned)((total_waves + waves - 1) / waves);
-    const uint32_t quads = (ix.max_stride + 3) / 4;  // a lane owns four row words
-    int g = 1;
-    while (g < 64 && (uint32_t)g < quads) g <<= 1;
-    const uint32_t w_iters = (quads + (uint32_t)g - 1) / (uint32_t)g;
-    if (w_iters > 1 && ix.d_vnonrep) return false;  // (split bins are unified for one pass of words per lane: the level kernels then)
     hipError_t e = hipErrorInvalidValue;
-    with_value<1, 2, 4, 8, 16, 32, 64>(g, [&](auto G) {  // (g is a power of two)
-        e = launch_fused<decltype(G)::value, true>(grid, waves * 64, wave_bytes * waves, s, t, d_kmers, n, d_rows, w_out, 0u, w_iters, stack_cap, (uint32_t)wave_words, h_max,
-                                                   nullptr, stack_lds, row_lds_words);
+    with_value<1, 2, 4, 8, 16, 32, 64>(p.G, [&](auto G) {  // (G is a power of two)
+        e = launch_fused<decltype(G)::value, true>(p.grid, p.waves_per_block * 64, p.wave_bytes * p.waves_per_block, s, t, d_kmers, n, d_rows, w_out, 0u, p.w_iters, p.stack_cap,
+                                                   (uint32_t)p.wave_words, h_max, nullptr, p.stack_lds, p.row_lds_words);
     });
     *rc = e == hipSuccess ? TXQ_OK : fail_hip(e, "layout-order fused kernel launch");
     return true;
@@ -869,26 +867,26 @@ int hibf_probe_layout_order(Index& ix, const uint64_t* d_kmers_all, size_t n_all
         int rc = TXQ_OK;
         if (layout_order_fused(ix, d_kmers_all, n_all, d_rows_all, s, &rc)) return rc;  // (split bins: unified as the rows are written)
     }
-    const uint32_t tile = 2048;
+    const uint32_t tile = kLayoutLevelTile;
     // A level reads the gates the level above it wrote (the words of the IBFs that have children: v_inner_words of a row):
     // a very large batch goes through the levels in pieces whose gates (about 100 MB) are still in the Infinity Cache when
     // the next level asks for them — but never in pieces so small that a level's launch could not fill the device
     // (measured on the 65 536-bin trees of tests/perf_hibf_ragged.py: 1 M k-mers in one piece 28 ms, in pieces of 128 k 47 ms — the
     // launches' tails cost more than the gates' cache misses; pieces are for batches of many millions)
-    size_t piece = std::max<size_t>((size_t)4 << 20, (((size_t)96 << 20) / ((size_t)std::max(ix.v_inner_words, 1u) * 8)) / tile * tile);
+    const size_t piece = layout_level_piece(ix.v_inner_words);
     for (size_t off = 0; off < n_all; off += piece) {
         const size_t n = std::min(piece, n_all - off);
         const uint64_t* d_kmers = d_kmers_all + off;
         uint64_t* d_rows = d_rows_all + off * ix.v_words;
-        const uint32_t n_tiles = (uint32_t)((n + tile - 1) / tile);
+        const uint32_t n_tiles = layout_level_tiles(n);
         for (const VLevel& L : ix.vlevels) {
             const uint32_t at = L.group_first[0], ng = L.group_first[1];
-            const uint32_t phases = (ng + 7) / 8;
-            if ((uint64_t)phases * n_tiles * 8 >= ((uint64_t)1 << 31)) return fail(TXQ_ERR_ARG, "too many k-mers for one layout-order probe");
+            const uint32_t grid = layout_level_grid(ng, n_tiles);
+            if (!grid) return fail(TXQ_ERR_ARG, "too many k-mers for one layout-order probe");
             // (chunks of one or two row words; a hash count outside 1..4 means 5, the most an IBF has)
             with_value<1, 2>(ix.v_chunk_words == 1 ? 1 : 2, [&](auto cw) {
                 with_hash_funs(ix.tree_hash_max >= 1 && ix.tree_hash_max <= 4 ? ix.tree_hash_max : 5u, [&](auto h) {
-                    hibf_layout_level_kernel<decltype(cw)::value, decltype(h)::value><<<phases * n_tiles * 8, 256, 0, s>>>(
+                    hibf_layout_level_kernel<decltype(cw)::value, decltype(h)::value><<<grid, 256, 0, s>>>(
                         ix.d_vchunks, ix.d_vgroups + at, ng, d_kmers, n, d_rows, ix.v_words, n_tiles, tile, (uint32_t)knobs().hibf_store & 112u);
                 });
             });
@@ -1045,110 +1043,66 @@ static hipError_t launch_level(unsigned grid, hipStream_t s, HibfView t, const u
     return hipGetLastError();
 }
 
-// fused descent (hibf_fused_kernel) when a k-mer's row and IBF stack fit the LDS; returns false if not
-// (TXQ_HIBF_LEVELS=1 forces the level-synchronous path, for A/B runs and for testing both)
-static bool hibf_probe_fused(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, uint64_t* d_masks, uint64_t* d_alive, hipStream_t s, int* rc) {
+// The descent kernels that keep a k-mer's row out of HBM until it is finished: child-stationary, small or fused, as
+// descent_path chose (txq_hibf_descent_plan.hpp; TXQ_HIBF_LEVELS=1 forces the level-synchronous path, for A/B runs and for testing both)
+static int hibf_probe_fused(Index& ix, const Knobs& kn, DescentPath path, const DescentShape& sh, const DescentKnobs& dk, const uint64_t* d_kmers, size_t n,
+                            uint64_t* d_masks, uint64_t* d_alive, hipStream_t s) {
     const uint32_t w_out = (uint32_t)ix.shard_words;
-    const uint32_t stack_cap = (uint32_t)ix.ibf.size();
-    const uint32_t stack_lds = fused_stack_lds(kn, stack_cap, w_out);
-    const size_t wave_words = (size_t)w_out + stack_lds / 2;
-    const size_t wave_bytes = wave_words * 8;
-    const size_t lds_budget = 64u << 10;
-    if (!w_out || wave_bytes > lds_budget || !ix.d_nodes || kn.hibf_levels) return false;
     uint32_t h_max = ix.tree_hash_max;
     const HibfView t{ix.d_ibf, ix.d_next, ix.d_tb_user, ix.d_map_off, ix.d_merged, ix.d_descend, ix.d_merged_off, (const HibfNode*)ix.d_nodes, (uint32_t)ix.hibf_total_tbs};
-    *rc = TXQ_OK;
     // regular two-level trees: the children stay put in L2, the k-mers stream past (TXQ_HIBF_STATIONARY=0: A/B against the kernels below)
-    {
-        // (narrow masks, <= 16 words, are better off with one lane per k-mer: hibf_small_kernel)
-        if (ix.d_children && ix.n_children && ix.child_row_words >= 2 && w_out > 16 && kn.hibf_stationary) {
-            const uint32_t wpr = ix.child_row_words, lpc = wpr / 2, cps = 64 / lpc;
-            const uint32_t n_steps = (ix.n_children + cps - 1) / cps;
-            // a group = whole wave steps whose children fit ~2 MB (half an XCD's L2); at least 8 groups when there are 8 steps
-            const uint64_t per_step = ix.children_bytes / n_steps + 1;
-            uint32_t spg = (uint32_t)std::max<uint64_t>(1, ((uint64_t)2 << 20) / per_step);
-            if (n_steps >= 8 && (n_steps + spg - 1) / spg < 8) spg = n_steps / 8;
-            if (kn.hibf_steps_per_group) spg = (uint32_t)kn.hibf_steps_per_group;
-            const uint32_t n_groups = (n_steps + spg - 1) / spg;
-            const uint32_t gpp = n_groups < 8 ? n_groups : 8;
-            const uint32_t phases = (n_groups + gpp - 1) / gpp;
-            uint32_t tile = 2048;
-            if (kn.hibf_tile) tile = (uint32_t)std::max(64, kn.hibf_tile);
-            const size_t n_tiles = (n + tile - 1) / tile;
-            if ((size_t)phases * n_tiles * gpp < ((size_t)1 << 31) && n_tiles < ((size_t)1 << 31)) {
-                const IbfDev& root = ix.ibf[0];
-                const uint32_t cm_words = root.stride;
-                if (int e = reserved(ix.scratch_cm.reserve(exactly(n * (size_t)cm_words * 8), after_device_wait()), "hipMalloc(scratch)")) { *rc = e; return true; }
-                size_t rb = (n + 255) / 256;
-                if (rb > 256 * 32) rb = 256 * 32;
-                const bool uniform = ix.children_uniform && !kn.hibf_lane_hash;  // (A/B: per-lane hashing on a uniform tree)
-                uint32_t* d_child_rows = nullptr;
-                const IbfDev& c0 = ix.ibf[1];  // uniform: every child looks like this one
-                if (uniform) {
-                    if (int e = reserved(ix.scratch_crows.reserve(exactly(n * (size_t)c0.hash_funs * 4), after_device_wait()), "hipMalloc(scratch)")) { *rc = e; return true; }
-                    d_child_rows = ix.scratch_crows.get();
-                    h_max = c0.hash_funs;
-                }
-                hibf_root_kernel<<<(unsigned)rb, 256, 0, s>>>(ix.root_node, d_kmers, n, ix.scratch_cm.get(), cm_words, d_child_rows, (uint32_t)c0.bin_size, c0.hash_shift, c0.hash_funs);
-                if (d_alive) {
-                    hipError_t e = hipMemsetAsync(d_alive, 0, ((n + 63) / 64) * 8, s);
-                    if (e != hipSuccess) { *rc = fail_hip(e, "hipMemsetAsync(alive)"); return true; }
-                }
-                const unsigned grid = (unsigned)((size_t)phases * n_tiles * gpp);
-                const int unroll = kn.hibf_unroll, store_flavour = kn.hibf_store;
-#define TXQ_CHILDREN(U, UNI) hibf_children_kernel<U, UNI><<<grid, 256, 0, s>>>((const ChildRec*)ix.d_children, ix.n_children, lpc, d_kmers, n, ix.scratch_cm.get(), \
-                                                                                cm_words, d_masks, w_out, n_steps, spg, gpp, (uint32_t)n_tiles, tile, h_max, d_alive, store_flavour, d_child_rows)
-                if (uniform) {
-                    if (unroll == 1) TXQ_CHILDREN(1, true);
-                    else if (unroll == 2) TXQ_CHILDREN(2, true);
-                    else if (unroll == 3) TXQ_CHILDREN(3, true);
-                    else if (unroll == 8) TXQ_CHILDREN(8, true);
-                    else TXQ_CHILDREN(4, true);
-                } else {
-                    if (unroll == 1) TXQ_CHILDREN(1, false);
-                    else if (unroll == 2) TXQ_CHILDREN(2, false);
-                    else if (unroll == 8) TXQ_CHILDREN(8, false);
-                    else TXQ_CHILDREN(4, false);
-                }
-#undef TXQ_CHILDREN
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess) *rc = fail_hip(e, "hibf child-stationary kernel launch");
-                return true;
-            }
+    if (path == DescentPath::Stationary) {
+        const StationaryPlan p = plan_stationary(sh, dk, n);
+        const uint32_t cm_words = sh.root_stride;
+        if (int e = reserved(ix.scratch_cm.reserve(exactly(n * (size_t)cm_words * 8), after_device_wait()), "hipMalloc(scratch)")) return e;
+        uint32_t* d_child_rows = nullptr;
+        const IbfDev& c0 = ix.ibf[1];  // uniform: every child looks like this one
+        if (p.uniform) {
+            if (int e = reserved(ix.scratch_crows.reserve(exactly(n * (size_t)c0.hash_funs * 4), after_device_wait()), "hipMalloc(scratch)")) return e;
+            d_child_rows = ix.scratch_crows.get();
+            h_max = c0.hash_funs;
         }
+        hibf_root_kernel<<<p.root_blocks, 256, 0, s>>>(ix.root_node, d_kmers, n, ix.scratch_cm.get(), cm_words, d_child_rows, (uint32_t)c0.bin_size, c0.hash_shift, c0.hash_funs);
+        if (d_alive) {
+            hipError_t e = hipMemsetAsync(d_alive, 0, ((n + 63) / 64) * 8, s);
+            if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(alive)");
+        }
+        const int store_flavour = kn.hibf_store;
+#define TXQ_CHILDREN(U, UNI) hibf_children_kernel<U, UNI><<<p.grid, 256, 0, s>>>((const ChildRec*)ix.d_children, ix.n_children, p.lanes_per_child, d_kmers, n, ix.scratch_cm.get(), \
+                                                                                cm_words, d_masks, w_out, p.n_steps, p.steps_per_group, p.groups_per_phase, (uint32_t)p.n_tiles, p.tile, h_max, d_alive, store_flavour, d_child_rows)
+        if (p.uniform) {
+            if (p.unroll == 1) TXQ_CHILDREN(1, true);
+            else if (p.unroll == 2) TXQ_CHILDREN(2, true);
+            else if (p.unroll == 3) TXQ_CHILDREN(3, true);
+            else if (p.unroll == 8) TXQ_CHILDREN(8, true);
+            else TXQ_CHILDREN(4, true);
+        } else {
+            if (p.unroll == 1) TXQ_CHILDREN(1, false);
+            else if (p.unroll == 2) TXQ_CHILDREN(2, false);
+            else if (p.unroll == 8) TXQ_CHILDREN(8, false);
+            else TXQ_CHILDREN(4, false);
+        }
+#undef TXQ_CHILDREN
+        hipError_t e = hipGetLastError();
+        return e == hipSuccess ? TXQ_OK : fail_hip(e, "hibf child-stationary kernel launch");
     }
     // small trees: one lane per k-mer (TXQ_HIBF_SMALL=0 keeps them on the wave-per-k-mer kernel, for A/B runs)
-    if (ix.max_stride <= 4 && ix.ibf.size() <= kSmallStack && ix.hibf_total_tbs < 0xFFFF && w_out <= 16 && kn.hibf_small) {
-        const size_t lds_bytes = (size_t)w_out * kSmallPitch * 8 + (size_t)kSmallStack * kSmallThreads * 2;
-        size_t blocks = (n + kSmallThreads - 1) / kSmallThreads;
-        if (blocks > 256 * 8) blocks = 256 * 8;
-        hibf_small_kernel<<<(unsigned)blocks, kSmallThreads, lds_bytes, s>>>(t, d_kmers, n, d_masks, w_out, (uint32_t)ix.shard_word0, h_max, d_alive);
+    if (path == DescentPath::Small) {
+        hibf_small_kernel<<<small_blocks(n), kSmallThreads, small_lds_bytes(w_out), s>>>(t, d_kmers, n, d_masks, w_out, (uint32_t)ix.shard_word0, h_max, d_alive);
         hipError_t e = hipGetLastError();
-        if (e != hipSuccess) *rc = fail_hip(e, "hibf small-tree kernel launch");
-        return true;
+        return e == hipSuccess ? TXQ_OK : fail_hip(e, "hibf small-tree kernel launch");
     }
-    const unsigned waves = fused_waves_per_block(wave_bytes);
-    // 64 waves per CU are launched: with an 8 KiB row the LDS keeps 14 of them resident and the rest queue up,
-    // with the short rows of a column shard more are resident and the finer grain is worth 14 % (TXQ_HIBF_WAVES overrides)
-    size_t want_waves = (size_t)256 * 64;
-    if (kn.hibf_waves > 0) want_waves = (size_t)kn.hibf_waves;
-    const size_t total_waves = n < want_waves ? n : want_waves;
-    const unsigned grid = (unsigned)((total_waves + waves - 1) / waves);
-    const uint32_t quads = (ix.max_stride + 3) / 4;  // a lane owns four row words
-    int g = 1;
-    while (g < 64 && (uint32_t)g < quads) g <<= 1;
-    const uint32_t w_iters = (quads + (uint32_t)g - 1) / (uint32_t)g;
+    const FusedPlan p = plan_fused(sh, dk, n);
     if (d_alive) {
         hipError_t e = hipMemsetAsync(d_alive, 0, ((n + 63) / 64) * 8, s);
-        if (e != hipSuccess) { *rc = fail_hip(e, "hipMemsetAsync(alive)"); return true; }
+        if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(alive)");
     }
     hipError_t e = hipErrorInvalidValue;
-    with_value<1, 2, 4, 8, 16, 32, 64>(g, [&](auto G) {  // (g is a power of two)
-        e = launch_fused<decltype(G)::value>(grid, waves * 64, wave_bytes * waves, s, t, d_kmers, n, d_masks, w_out, (uint32_t)ix.shard_word0, w_iters, stack_cap,
-                                             (uint32_t)wave_words, h_max, d_alive, stack_lds, w_out);
+    with_value<1, 2, 4, 8, 16, 32, 64>(p.G, [&](auto G) {  // (G is a power of two)
+        e = launch_fused<decltype(G)::value>(p.grid, p.waves_per_block * 64, p.wave_bytes * p.waves_per_block, s, t, d_kmers, n, d_masks, w_out, (uint32_t)ix.shard_word0, p.w_iters,
+                                             p.stack_cap, (uint32_t)p.wave_words, h_max, d_alive, p.stack_lds, p.row_lds_words);
     });
-    if (e != hipSuccess) *rc = fail_hip(e, "hibf fused kernel launch");
-    return true;
+    return e == hipSuccess ? TXQ_OK : fail_hip(e, "hibf fused kernel launch");
 }
 
 void preload_hibf_kernels() {
@@ -1160,7 +1114,10 @@ void preload_hibf_kernels() {
 int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, uint64_t* d_masks, uint64_t* d_alive, hipStream_t s) {
     const uint32_t w_out = (uint32_t)ix.shard_words;
     if (n == 0) return TXQ_OK;
-    if (ix.probes_interleaved(kn)) {
+    const DescentShape sh = descent_shape(ix, kn);
+    const DescentKnobs dk = descent_knobs(kn);
+    const DescentPath path = descent_path(sh, dk, n);
+    if (path == DescentPath::Interleaved) {
         // a small regular tree of uniform children: its interleaved children are probed like a flat IBF (one row segment per
         // hash function), the root's word clears the words of the children the k-mer cannot be in (txq_probe.hip TreeRoot)
         uint32_t wpr_log2 = 0;
@@ -1169,18 +1126,11 @@ int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, ui
         if (e != hipSuccess) return fail_hip(e, "interleaved probe launch");
         return TXQ_OK;
     }
-    {
-        int rc = TXQ_OK;
-        if (hibf_probe_fused(ix, kn, d_kmers, n, d_masks, d_alive, s, &rc)) return rc;
-    }
+    if (path != DescentPath::Levels) return hibf_probe_fused(ix, kn, path, sh, dk, d_kmers, n, d_masks, d_alive, s);
     if (w_out) TXQ_HIP(hipMemsetAsync(d_masks, 0, n * w_out * 8, s));
-    // Frontier bound: a (k-mer, IBF) pair occurs at most once, so level l holds at most
-    // chunk * (#IBFs on level l) items.  Choose the chunk so that this always fits.
-    const size_t cap_items = (size_t)1 << 24;  // 128 MiB per frontier buffer
-    size_t chunk = cap_items / ix.max_level_width;
-    if (chunk == 0) chunk = 1;
-    if (chunk > n) chunk = n;
-    const size_t cap = chunk * ix.max_level_width;
+    // the batch goes through the levels in chunks whose frontiers fit their buffers (128 MiB each)
+    const LevelsPlan p = plan_levels(sh, n);
+    const size_t chunk = p.chunk, cap = p.cap;
     if (ix.depth > 1) {
         for (int i = 0; i < 2; ++i)
             if (int rc = reserved(ix.frontier[i].reserve(exactly(cap * sizeof(WorkItem)), after_device_wait()), "hipMalloc(scratch)")) return rc;
@@ -1188,9 +1138,6 @@ int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, ui
     if (int rc = reserved(ix.d_counts.reserve(exactly(((size_t)ix.depth + 2) * 4), after_device_wait()), "hipMalloc(scratch)")) return rc;
     uint32_t* overflow = ix.d_counts.get() + ix.depth + 1;
     const HibfView t{ix.d_ibf, ix.d_next, ix.d_tb_user, ix.d_map_off, ix.d_merged, ix.d_descend, ix.d_merged_off, (const HibfNode*)ix.d_nodes, (uint32_t)ix.hibf_total_tbs};
-    int g = 1;
-    while (g < 64 && (uint32_t)g < ix.max_stride) g <<= 1;
-    const uint32_t w_iters = (ix.max_stride + (uint32_t)g - 1) / (uint32_t)g;
 
     for (size_t off = 0; off < n; off += chunk) {
         const size_t m = n - off < chunk ? n - off : chunk;
@@ -1199,24 +1146,18 @@ int hibf_probe(Index& ix, const Knobs& kn, const uint64_t* d_kmers, size_t n, ui
             const WorkItem* in = lvl ? ix.frontier[(lvl - 1) & 1].get() : nullptr;
             const uint32_t* in_count = lvl ? ix.d_counts.get() + (lvl - 1) : nullptr;
             WorkItem* out = ix.frontier[lvl & 1].get();
-            // level 0 is sized by the batch; deeper levels are grid-stride over an unknown count
-            size_t groups = lvl ? (size_t)2048 * 256 / g : m;
-            size_t blocks = (groups * g + 255) / 256;
-            if (blocks > 2048) blocks = 2048;
-            if (blocks == 0) blocks = 1;
+            const unsigned blocks = level_blocks(p.G, lvl, m);
             hipError_t e = hipErrorInvalidValue;
-            with_value<1, 2, 4, 8, 16, 32, 64>(g, [&](auto G) {  // (g is a power of two)
-                e = launch_level<decltype(G)::value>((unsigned)blocks, s, t, d_kmers + off, in, in_count, (uint32_t)m, out, ix.d_counts.get() + lvl,
-                                                     (uint32_t)(ix.depth > 1 ? cap : 0), overflow, d_masks + off * w_out, w_out, (uint32_t)ix.shard_word0, w_iters);
+            with_value<1, 2, 4, 8, 16, 32, 64>(p.G, [&](auto G) {  // (G is a power of two)
+                e = launch_level<decltype(G)::value>(blocks, s, t, d_kmers + off, in, in_count, (uint32_t)m, out, ix.d_counts.get() + lvl,
+                                                     (uint32_t)(ix.depth > 1 ? cap : 0), overflow, d_masks + off * w_out, w_out, (uint32_t)ix.shard_word0, p.w_iters);
             });
             if (e != hipSuccess) return fail_hip(e, "hibf level kernel launch");
             hibf_clamp_kernel<<<1, 64, 0, s>>>(ix.d_counts.get() + lvl, (uint32_t)cap);
         }
     }
     if (d_alive) {
-        size_t blocks = ((n + 63) / 64 * 64 + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        mask_alive_kernel<<<(unsigned)blocks, 256, 0, s>>>(d_masks, n, w_out, d_alive);
+        mask_alive_kernel<<<p.alive_blocks, 256, 0, s>>>(d_masks, n, w_out, d_alive);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail_hip(e, "mask_alive kernel launch");
     }
