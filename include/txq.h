@@ -22,6 +22,7 @@
  *   txq_edit_search_long / _device  (the same for patterns of up to 4096 bytes, the pattern spread over the lanes of a wave)
  *   txq_edit_align / _device  (no counterpart: start and CIGAR of the pairs a search call confirmed, `--verify --align`)
  *   txq_edit_windows / _device  (no counterpart: txq_edit_search for windows into one letter buffer, `--window --verify-windows`)
+ *   txq_frame_window_letters / _device  (no counterpart: the letters, stops and thresholds of translated windows, `--verify-frame-windows`)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every function returns 0 on success or a
  * negative txq_status; txq_last_error() gives the message for the calling thread.  Host buffers are
@@ -291,6 +292,35 @@ int txq_translate_frames_device(const uint8_t* d_seq, const uint64_t* d_rec_offs
                                 uint64_t* d_frame_offsets, void* stream);
 int txq_translate_frames(const uint8_t* seq, const uint64_t* rec_offsets, size_t n_records, uint8_t* frames, size_t frames_bytes,
                          uint64_t* frame_offsets);  /* host buffers, synchronous */
+
+/* Where the letters of every frame window lie, how many stops they hold and the threshold that follows
+ * (`tetrex search --translate --frame-window --verify-frame-windows`; not in the reference).  The step between
+ * the two calls above and txq_count_windows_device / txq_edit_windows_device.  d_rec_offsets, k, window and step are those of
+ * the txq_translate_windows_device call that left d_win_offsets and d_win_len (n_windows entries: the windows' stop-free
+ * k-mers w); d_frames, frames_bytes and d_frame_offsets are as txq_translate_frames_device left them for the same records.
+ * For window j, window j - d_win_offsets[q] of its frame q with residues [a, a + l):
+ *   d_let_begin[j]   d_frame_offsets[q] + a, the index of its first residue letter in d_frames
+ *   d_let_len[j]     l
+ *   d_stops[j]       s, the number of '*' among those letters
+ *   d_thresholds[j]  0xFFFFFFFF ("not searched", what txq_count_windows_device takes for it) where s > edits or
+ *                    w <= k (edits - s), else w - k (edits - s)
+ * The threshold loses nothing: within `edits` edits of anything every stop is an edited column of its own, the edits - s
+ * that remain touch at most k of the w stop-free k-mers each, and the k-mers only stops touch are not among the w.
+ * d_let_begin and d_let_len are the window arrays txq_edit_windows_device takes (letters_bytes = frames_bytes), d_thresholds
+ * what txq_count_windows_device takes: nothing goes to the host between translation and count.  A j at or behind
+ * d_win_offsets[6 n_records] and a window its frame does not have get begin 0 and length 0, a window whose letters leave
+ * frames_bytes keeps its begin and length; all of them get 0 stops and "not searched".  No byte at or behind frames_bytes is read whatever the arrays say, and
+ * d_frames may have any alignment.  The call is deterministic, allocates nothing, reads nothing back and does not
+ * synchronise with the host.  Null pointers, k outside 1..12, window < k and step outside 1..window: TXQ_ERR_ARG, nothing
+ * written; at most 2^32 - 2 windows.  txq_frame_window_letters is the synchronous twin on host buffers: it checks that the
+ * three offset arrays ascend, that the frame and window offsets begin at 0 and that n_windows covers the window offsets. */
+int txq_frame_window_letters_device(const uint64_t* d_rec_offsets, size_t n_records, unsigned k, uint32_t window, uint32_t step,
+                                    const uint8_t* d_frames, size_t frames_bytes, const uint64_t* d_frame_offsets,
+                                    const uint64_t* d_win_offsets, const uint32_t* d_win_len, size_t n_windows, uint32_t edits,
+                                    uint64_t* d_let_begin, uint32_t* d_let_len, uint32_t* d_stops, uint32_t* d_thresholds, void* stream);
+int txq_frame_window_letters(const uint64_t* rec_offsets, size_t n_records, unsigned k, uint32_t window, uint32_t step, const uint8_t* frames,
+                             size_t frames_bytes, const uint64_t* frame_offsets, const uint64_t* win_offsets, const uint32_t* win_len,
+                             size_t n_windows, uint32_t edits, uint64_t* let_begin, uint32_t* let_len, uint32_t* stops, uint32_t* thresholds);
 
 /* Approximate matching of (pattern, bin) pairs by edit distance (`tetrex search --verify`; not in the reference).
  * Classes: d_codes[256] maps a byte to a class 0..30; any other value (255 by convention) is "matches nothing, not even

@@ -25,6 +25,7 @@ SYMBOLS = [
     "txq_count_windows", "txq_count_windows_device",
     "txq_translate_bound", "txq_translate_device", "txq_translate",
     "txq_translate_windows_bound", "txq_translate_windows_device", "txq_translate_windows", "txq_translate_frames_bound", "txq_translate_frames_device", "txq_translate_frames",
+    "txq_frame_window_letters", "txq_frame_window_letters_device",
     "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
     "txq_edit_search_long", "txq_edit_search_long_device", "txq_edit_align", "txq_edit_align_device",
     "txq_edit_targets", "txq_edit_targets_device", "txq_edit_targets_long", "txq_edit_targets_long_device",
@@ -100,6 +101,10 @@ def lib():
         L.txq_translate_frames_bound.argtypes = [u64p, C.c_size_t]
         L.txq_translate_frames_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.txq_translate_frames.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, C.c_size_t, u64p]
+        L.txq_frame_window_letters_device.argtypes = [C.c_void_p, C.c_size_t, C.c_uint, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.txq_frame_window_letters.argtypes = [u64p, C.c_size_t, C.c_uint, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, u64p, u64p, u32p, C.c_size_t,
+                                               C.c_uint32, u64p, u32p, u32p, u32p]
         L.txq_hit_list_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.txq_edit_search_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -673,6 +678,76 @@ def translate_frames_device(records, capacity=None, seq_at=0, frames_at=0, guard
         return buf, d_off.to_numpy(np.uint64, (6 * n + 1,)), bound
     finally:
         for b in (d_seq, d_rec, d_frames, d_off):
+            b.free()
+
+
+NOT_SEARCHED = 0xFFFFFFFF
+
+
+def frame_window_letters(rec_offsets, k, window, step, frames, frame_offsets, win_offsets, win_lens, edits, n_windows=None):
+    """Where the letters of every frame window lie in the frames buffer, their stops and thresholds on the GPU
+    (txq_frame_window_letters, include/txq.h).  rec_offsets, k, window, step: those of translate_windows(); frames and
+    frame_offsets: what translate_frames() returned; win_offsets and win_lens: translate_windows()' window offsets and value
+    counts.  Returns (begins uint64[], lens uint32[], stops uint32[], thresholds uint32[]), NOT_SEARCHED for a window that is
+    not searched under `edits` edits."""
+    rec = np.ascontiguousarray(rec_offsets, dtype=np.uint64)
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    fo = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+    wo = np.ascontiguousarray(win_offsets, dtype=np.uint64)
+    wl = np.ascontiguousarray(win_lens, dtype=np.uint32)
+    n = rec.size - 1
+    if n < 0 or fo.size != 6 * n + 1 or wo.size != 6 * n + 1:
+        raise TxqError(-1, "frame_window_letters: record, frame and window offsets disagree")
+    if not (0 <= int(window) <= 0xFFFFFFFF and 0 <= int(step) <= 0xFFFFFFFF and 0 <= int(edits) <= 0xFFFFFFFF):
+        raise TxqError(-1, "frame_window_letters: window, step and edits must fit 32 bits")
+    nw = wl.size if n_windows is None else int(n_windows)
+    begins, lens = np.zeros(nw, dtype=np.uint64), np.zeros(nw, dtype=np.uint32)
+    stops, thresholds = np.zeros(nw, dtype=np.uint32), np.zeros(nw, dtype=np.uint32)
+    check(lib().txq_frame_window_letters(rec.ctypes.data_as(u64p), n, k, int(window), int(step), frames.ctypes.data, frames.size, fo.ctypes.data_as(u64p),
+                                         wo.ctypes.data_as(u64p), wl.ctypes.data_as(u32p), nw, int(edits), begins.ctypes.data_as(u64p),
+                                         lens.ctypes.data_as(u32p), stops.ctypes.data_as(u32p), thresholds.ctypes.data_as(u32p)))
+    return begins, lens, stops, thresholds
+
+
+def frame_window_letters_device(records, k, codes, window, step, edits, frames_at=0, capacity=None, stream=None):
+    """txq_translate_windows_device, txq_translate_frames_device and txq_frame_window_letters_device queued back to back on
+    `stream` (a hipStream_t as an integer; None: the default stream) with no host wait in between.  The frames buffer begins
+    frames_at bytes behind a 16-byte boundary and is exactly `capacity` bytes long (default: the frames' bound), which is the
+    frames_bytes the calls are given.  Returns (frames uint8[capacity], frame_offsets, win_offsets, win_lens, begins, lens,
+    stops, thresholds)."""
+    seq, rec = records if isinstance(records, tuple) else _records(records)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    rec = np.ascontiguousarray(rec, dtype=np.uint64)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    n = rec.size - 1
+    bound = translate_bound(rec, k)
+    nw = translate_windows_bound(rec, k, window, step)
+    fbytes = translate_frames_bound(rec)
+    capacity = fbytes if capacity is None else int(capacity)
+    m = 6 * n
+    L = lib()
+    bufs = dict(seq=DeviceBuffer.from_numpy(np.concatenate([seq, np.full(16, ord("A"), dtype=np.uint8)])), rec=DeviceBuffer.from_numpy(rec),
+                codes=DeviceBuffer.from_numpy(codes), val=DeviceBuffer(bound * 8 + 8), off=DeviceBuffer((m + 1) * 8), woff=DeviceBuffer((m + 1) * 8),
+                wbeg=DeviceBuffer(nw * 8 + 8), wlen=DeviceBuffer(nw * 4 + 8), frames=DeviceBuffer(capacity + 32), foff=DeviceBuffer((m + 1) * 8),
+                lbeg=DeviceBuffer(nw * 8 + 8), llen=DeviceBuffer(nw * 4 + 8), stops=DeviceBuffer(nw * 4 + 8), thr=DeviceBuffer(nw * 4 + 8))
+    try:
+        # the buffer ends where the allocation ends: [first, first + capacity) with first = frames_at (mod 16)
+        first = bufs["frames"].nbytes - capacity
+        first -= (bufs["frames"].ptr + first - frames_at) % 16
+        assert first >= 0 and (bufs["frames"].ptr + first) % 16 == frames_at % 16
+        d_frames = bufs["frames"].ptr + first
+        check(L.txq_translate_windows_device(bufs["seq"].ptr, bufs["rec"].ptr, n, k, bufs["codes"].ptr, int(window), int(step), bufs["val"].ptr,
+                                             bufs["off"].ptr, bufs["woff"].ptr, bufs["wbeg"].ptr, bufs["wlen"].ptr, stream))
+        check(L.txq_translate_frames_device(bufs["seq"].ptr, bufs["rec"].ptr, n, d_frames, capacity, bufs["foff"].ptr, stream))
+        check(L.txq_frame_window_letters_device(bufs["rec"].ptr, n, k, int(window), int(step), d_frames, capacity, bufs["foff"].ptr, bufs["woff"].ptr,
+                                                bufs["wlen"].ptr, nw, int(edits), bufs["lbeg"].ptr, bufs["llen"].ptr, bufs["stops"].ptr, bufs["thr"].ptr,
+                                                stream))
+        synchronize()
+        return (bufs["frames"].to_numpy(np.uint8, (capacity,), first), bufs["foff"].to_numpy(np.uint64, (m + 1,)), bufs["woff"].to_numpy(np.uint64, (m + 1,)),
+                bufs["wlen"].to_numpy(np.uint32, (nw,)), bufs["lbeg"].to_numpy(np.uint64, (nw,)), bufs["llen"].to_numpy(np.uint32, (nw,)),
+                bufs["stops"].to_numpy(np.uint32, (nw,)), bufs["thr"].to_numpy(np.uint32, (nw,)))
+    finally:
+        for b in bufs.values():
             b.free()
 
 

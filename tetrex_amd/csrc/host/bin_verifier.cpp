@@ -412,24 +412,30 @@ void BinVerifier::verify_windows(const std::vector<std::string>& queries, const 
             win_len.push_back(w.len);
         }
     }
-    std::vector<uint32_t> pairs;
-    pairs.reserve(on_kernel.size() * strands * 3);
-    for (size_t i : on_kernel)
-        for (size_t s = 0; s < strands; ++s) pairs.insert(pairs.end(), {entry_of[candidates[i].query] + (uint32_t)s, 0u, errors_});
-    const size_t n_pairs = pairs.size() / 3;
-    DeviceBuffer d_letters(letters.size() + 16), d_begin(win_begin.size() * 8), d_len(win_len.size() * 4), d_pairs(pairs.size() * 4), d_out(pairs.size() * 4);
-    DeviceBuffer d_work(TXQ_EDIT_WINDOWS_WORKSPACE(n_pairs) + 8 * on_kernel.size());  // (every call its own part: they are all in flight at once)
+    DeviceBuffer d_letters(letters.size() + 16), d_begin(win_begin.size() * 8), d_len(win_len.size() * 4);
     txq_check(txq_memcpy_h2d(d_letters.p, letters.data(), letters.size()), "h2d");
     txq_check(txq_memcpy_h2d(d_begin.p, win_begin.data(), win_begin.size() * 8), "h2d");
     txq_check(txq_memcpy_h2d(d_len.p, win_len.data(), win_len.size() * 4), "h2d");
+    run_windows(DeviceWindows{(const uint8_t*)d_letters.p, letters.size(), (const uint64_t*)d_begin.p, (const uint32_t*)d_len.p, win_begin.size()}, strands,
+                on_kernel, [&](size_t i) { return entry_of[candidates[i].query]; }, candidates, hits);
+}
+
+void BinVerifier::run_windows(const DeviceWindows& w, size_t strands, const std::vector<size_t>& on_kernel, const std::function<uint32_t(size_t)>& entry_of,
+                              const std::vector<Candidate>& candidates, std::vector<Hit>& hits) {
+    std::vector<uint32_t> pairs;
+    pairs.reserve(on_kernel.size() * strands * 3);
+    for (size_t i : on_kernel)
+        for (size_t s = 0; s < strands; ++s) pairs.insert(pairs.end(), {entry_of(i) + (uint32_t)s, 0u, errors_});
+    const size_t n_pairs = pairs.size() / 3;
+    DeviceBuffer d_pairs(pairs.size() * 4), d_out(pairs.size() * 4);
+    DeviceBuffer d_work(TXQ_EDIT_WINDOWS_WORKSPACE(n_pairs) + 8 * on_kernel.size());  // (every call its own part: they are all in flight at once)
     txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
     size_t n_calls = 0;
     for_each_bin_run(0, on_kernel.size(), [&](size_t k) { return candidates[on_kernel[k]].bin; }, [&](uint32_t bin, size_t a, size_t b) {
         ResidentBins::Bin& e = bins_.resident(bin);
         const uint64_t* d_rec = (const uint64_t*)e.d_rec;
-        txq_check(txq_edit_windows_device((const uint8_t*)d_letters.p, letters.size(), (const uint64_t*)d_begin.p, (const uint32_t*)d_len.p, win_begin.size(),
-                                          (const uint8_t*)e.d_text, d_rec, e.n_records, e.text_bytes, d_rec + e.n_records + 1, 1,
-                                          (const uint32_t*)d_pairs.p + 3 * strands * a, (b - a) * strands, (const uint8_t*)d_codes_,
+        txq_check(txq_edit_windows_device(w.d_letters, w.bytes, w.d_begin, w.d_len, w.n_windows, (const uint8_t*)e.d_text, d_rec, e.n_records, e.text_bytes,
+                                          d_rec + e.n_records + 1, 1, (const uint32_t*)d_pairs.p + 3 * strands * a, (b - a) * strands, (const uint8_t*)d_codes_,
                                           (uint32_t*)d_out.p + 3 * strands * a, (unsigned char*)d_work.p + 16 * strands * a + 8 * n_calls++, nullptr),
                   "txq_edit_windows_device");
     });
@@ -441,7 +447,7 @@ void BinVerifier::verify_windows(const std::vector<std::string>& queries, const 
         Hit& h = hits[i];
         const std::vector<std::string>& names = bins_.at(candidates[i].bin).names;
         for (size_t s = 0; s < strands; ++s) {
-            if (res[3 * s] == kEditNone && res[3 * s + 1] == 0xFFFFFFFEu) throw std::runtime_error("tetrex search --verify-windows: the device refused a pair of bin " + std::to_string(candidates[i].bin));
+            if (res[3 * s] == kEditNone && res[3 * s + 1] == 0xFFFFFFFEu) throw std::runtime_error("tetrex search --verify-windows / --verify-frame-windows: the device refused a pair of bin " + std::to_string(candidates[i].bin));
             if (res[3 * s] != kEditNone && (h.distance == kEditNone || res[3 * s] < h.distance)) {
                 h.distance = res[3 * s];
                 h.target = &names.at(res[3 * s + 1]);
@@ -451,6 +457,49 @@ void BinVerifier::verify_windows(const std::vector<std::string>& queries, const 
         }
         if (h.distance != kEditNone) ++n_confirmed_;
     }
+}
+
+// ---- tetrex search --translate --frame-window --verify-frame-windows ------------------------------------------------------
+
+void BinVerifier::verify_windows(const DeviceWindows& windows, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& lengths,
+                                 const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits) {
+    hits.assign(candidates.size(), Hit{});
+    if (candidates.empty()) return;
+    if (lengths.size() != candidates.size()) throw std::runtime_error("tetrex search --verify-frame-windows: candidates and lengths disagree");
+    if (dna_) throw std::runtime_error("tetrex search --verify-frame-windows: translated windows have one strand, the verifier two");
+    const char* route_env = std::getenv("TETREX_VERIFY_FRAME_WINDOWS");
+    const bool all_written = route_env && std::string(route_env) == "written";
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    std::vector<size_t> on_kernel, written;
+    for (size_t i = 0; i < candidates.size(); ++i) {
+        if (candidates[i].query >= windows.n_windows) throw std::runtime_error("tetrex search --verify-frame-windows: a candidate names no window");
+        (all_written || lengths[i] == 0 || lengths[i] > TXQ_EDIT_MAX_PATTERN ? written : on_kernel).push_back(i);
+    }
+    if (!written.empty()) {  // each distinct window becomes a string of its own, in window order: verify() and its routes, unchanged
+        std::vector<size_t> by_window(written);
+        std::stable_sort(by_window.begin(), by_window.end(), [&](size_t x, size_t y) { return candidates[x].query < candidates[y].query; });
+        std::vector<uint32_t> string_of(windows.n_windows, kNone);
+        std::vector<std::string> strings;
+        for (size_t i : by_window) {
+            const uint32_t q = candidates[i].query;
+            if (string_of[q] != kNone) continue;
+            string_of[q] = (uint32_t)strings.size();
+            strings.push_back(letters(q));
+        }
+        std::vector<Candidate> as_records;
+        for (size_t i : written) as_records.push_back({string_of[candidates[i].query], candidates[i].bin});
+        std::vector<Hit> answers;
+        verify(strings, as_records, answers);
+        for (size_t k = 0; k < written.size(); ++k) hits[written[k]] = std::move(answers[k]);
+    }
+    if (on_kernel.empty()) return;
+    n_candidates_ += on_kernel.size();
+    n_windows_ += on_kernel.size();
+    // by bin, and by window within the bin: the windows of a frame that hit a bin are consecutive pairs, which walk together
+    std::stable_sort(on_kernel.begin(), on_kernel.end(), [&](size_t x, size_t y) {
+        return std::tie(candidates[x].bin, candidates[x].query) < std::tie(candidates[y].bin, candidates[y].query);
+    });
+    run_windows(windows, 1, on_kernel, [&](size_t i) { return candidates[i].query; }, candidates, hits);
 }
 
 // ---- tetrex search --verify --all-targets ------------------------------------------------------------------------------

@@ -121,6 +121,23 @@ class BinVerifier {
     };
     void verify_windows(const std::vector<std::string>& queries, const std::vector<Window>& windows, const std::vector<Candidate>& candidates,
                         std::vector<Hit>& hits);
+    // `--translate --frame-window --verify-frame-windows`: the windows' letters are on the device already — the
+    // frames of txq_translate_frames_device, `bytes` of them with 16 bytes of slack behind, window w being
+    // d_letters[d_begin[w] .. d_begin[w] + d_len[w]) as txq_frame_window_letters_device left them.  candidates[i].query names a
+    // window, lengths[i] is its length, letters(w) gives the window as a string to verify()'s routes: windows of more than
+    // TXQ_EDIT_MAX_PATTERN residues, and with TETREX_VERIFY_FRAME_WINDOWS=written every window.  One strand: the frame fixes it
+    // (a verifier made for a nucleotide index is refused).  The others go to txq_edit_windows_device grouped, ordered and
+    // queued exactly as above — by bin and by window within the bin, one call per candidate bin, all queued before the one
+    // copy back — and count towards n_routed().windows.
+    struct DeviceWindows {
+        const uint8_t* d_letters;
+        size_t bytes;
+        const uint64_t* d_begin;
+        const uint32_t* d_len;
+        size_t n_windows;
+    };
+    void verify_windows(const DeviceWindows& windows, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& lengths,
+                        const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits);
     size_t n_candidates() const { return n_candidates_; }
     size_t n_confirmed() const { return n_confirmed_; }
     size_t n_targets() const { return n_targets_; }  // `--all-targets`: the rows of all confirmed pairs
@@ -136,6 +153,11 @@ class BinVerifier {
     // with its bin — routing by length, the pairs, one call per bin and kernel, the one copy back, the host route, settle
     void run(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
              const std::vector<uint64_t>& lengths, const Letters& letters, std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows);
+    // what both verify_windows share: the candidates on_kernel, by bin and by window, as `strands` consecutive entries from
+    // entry_of(candidate) of window arrays on the device — the pairs, one txq_edit_windows_device call per bin, the one copy
+    // back, the better strand (+ on equal distance)
+    void run_windows(const DeviceWindows& w, size_t strands, const std::vector<size_t>& on_kernel, const std::function<uint32_t(size_t)>& entry_of,
+                     const std::vector<Candidate>& candidates, std::vector<Hit>& hits);
     // `--all-targets`: the same routing with txq_edit_targets*_device and edit_targets_group in place of the search calls
     void run_targets(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
                      const std::vector<uint64_t>& lengths, const Letters& letters, std::vector<std::vector<Hit>>& rows);

@@ -132,9 +132,23 @@ class DeviceIndex {
     // most 256 MiB of hit words / counts, and TETREX_SEARCH_BATCH_WINDOWS windows where set (for tests: the hits are the same
     // for every value).  No value is sent twice.  Only the list of (window, bin, count) comes back, in (window, bin) order.
     // One shard only; flat and hierarchical indexes alike.
+    // With `verified` (`--verify-frame-windows`) every hit is a candidate.  Behind the translation of a batch its
+    // frames become letters on the device (txq_translate_frames_device on the same bytes) and txq_frame_window_letters_device
+    // writes, per window, where its letters lie, its stops s and its threshold — not searched where s > edits, else
+    // w - k (edits - s), not searched where that is not above 0 — straight into what the count takes; lens and stops come
+    // back, thresholds[j] is that threshold (0: not searched) and threshold_of is not asked.  TETREX_FRAME_WINDOW_THRESHOLD=plain
+    // (an A/B run): threshold_of as without `verified`, windows of any number of stops searched.  After the batch's counts its
+    // hits go to BinVerifier::verify_windows with the letters where they are; confirmed[i] answers hits[i].
+    struct VerifiedWindows {
+        BinVerifier* verifier = nullptr;
+        uint32_t edits = 0;
+        std::vector<uint32_t> stops;         // out: the stops of every window
+        std::vector<VerifiedHit> confirmed;  // out: confirmed[i] answers hits[i]
+    };
     void search_translated_windows(std::string_view seq, const std::vector<uint64_t>& rec_offsets, uint32_t window, uint32_t step,
                                    const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& win_offsets,
-                                   std::vector<uint32_t>& lens, std::vector<uint32_t>& thresholds, std::vector<TranslatedHit>& hits);
+                                   std::vector<uint32_t>& lens, std::vector<uint32_t>& thresholds, std::vector<TranslatedHit>& hits,
+                                   VerifiedWindows* verified = nullptr);
     // `tetrex query -g`: upload the d-gram index next to the main index (same device, same shard)
     void attach_dgram(const DgramImage& dgram);
     bool has_dgram() const { return aux_ != nullptr; }

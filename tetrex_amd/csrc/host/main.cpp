@@ -20,6 +20,9 @@
 //   tetrex search --translate --frame-window W [--frame-step S] (-e E | --threshold F) [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (the local search in the six frames of nucleotide records: every frame cut into overlapping windows of W residues, S apart,
 //      translated, cut and slid on the device; the rows say in which frame and where on the record, in nucleotides, each bin is hit)
+//   tetrex search --translate --frame-window W [--frame-step S] -e E --verify-frame-windows [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//     (the translated local search confirmed: only the runs of windows whose residues are within E edits of a record of the bin,
+//      stops counted as edits, each with the distance, target and end of its nearest window; the letters never leave the device)
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
 // (`tetrex search` is search_cmd.cpp.)

@@ -309,6 +309,13 @@ int search_windowed(const Args& a, const IndexImage& image, unsigned long long e
 // the 1-based inclusive nucleotide positions of the run's residues on the record as given (begin <= end; the frame carries
 // the strand), count/w those of the run's best window (the highest count, the earliest on a tie); by record, frame
 // (+1 +2 +3 -1 -2 -3), bin, begin.
+// -e E --verify-frame-windows: a window of w stop-free k-mers and s stops is searched with t = w - k (E - s) where
+// s <= E and that is above 0 — every stop costs an edit of its own, so nothing is lost and a window with s > E cannot match —,
+// every hit (window, bin) is a candidate, and a window is confirmed in a bin when its residue letters are within E edits of a
+// substring of one record of the bin (BinVerifier::verify_windows on the frames' letters where txq_translate_frames_device
+// left them: the comparison of --verify-frames, one strand).  Rows: one for every maximal run of consecutive CONFIRMED windows
+// of a (record, frame, bin), name \t bin path \t frame \t begin \t end [\t count/w] \t distance \t target \t target_end as
+// --verify-windows settles them (plan::confirmed_runs); the same order.
 int search_translated_windowed(const Args& a, const IndexImage& image, unsigned long long errors, double fraction, uint32_t window, uint32_t step) {
     Search s(a, image, errors, fraction);
     const uint64_t k = s.k;
@@ -317,9 +324,17 @@ int search_translated_windowed(const Args& a, const IndexImage& image, unsigned 
     std::vector<uint32_t> lens, thresholds;
     std::vector<Hit> hits, mine;
     uint64_t n_searched = 0, n_hit = 0, n_rows = 0;
+    s.make_verifier(a.has("verify-frame-windows"), false);
+    const bool verify = s.verifier != nullptr;
+    s.windows = verify;
+    DeviceIndex::VerifiedWindows verified;
+    verified.verifier = s.verifier.get();
+    verified.edits = (uint32_t)std::min<uint64_t>(errors, 0xFFFFFFFEull);
+    struct Confirmed { uint32_t query, bin, count, distance; char strand; size_t at; };  // at: its place in verified.confirmed
+    std::vector<Confirmed> kept;
     for_each_chunk(a.pos[1], [&](const Chunk& c) {
         s.dev.search_translated_windows(c.seq, c.rec_offsets, window, step, [&](uint64_t n) { return s.threshold.of(n); }, s.with_counts, win_offsets, lens,
-                                        thresholds, hits);
+                                        thresholds, hits, verify ? &verified : nullptr);
         size_t h = 0;
         for (size_t r = 0; r < c.names.size(); ++r) {
             const uint64_t L = c.rec_offsets[r + 1] - c.rec_offsets[r];
@@ -336,16 +351,36 @@ int search_translated_windowed(const Args& a, const IndexImage& image, unsigned 
             for (uint32_t f = 0; f < 6; ++f) {
                 const uint64_t w0 = win_offsets[6 * r + f], w1 = win_offsets[6 * r + f + 1];
                 mine.clear();
+                const size_t h0 = h;
                 for (; h < hits.size() && hits[h].query < w1; ++h) mine.push_back(hits[h]);
                 if (mine.empty()) continue;
                 const txq::fw::Frame layout = txq::fw::frame_plan(txq::tr::frame_len(L, f % 3), (uint32_t)k, window, step);
                 for (size_t i = 0; i < mine.size(); ++i) n_hit += i == 0 || mine[i].query != mine[i - 1].query;
+                const auto begin_row = [&](uint32_t bin, uint32_t first, uint32_t last) {
+                    const txq::fw::Window wf = txq::fw::window_at(layout, first - w0), wl = txq::fw::window_at(layout, last - w0);
+                    const txq::fw::Span at = txq::fw::residues_on_record(L, f, wf.a, wl.a + wl.len);
+                    row.assign(c.names[r]).append("\t").append(image.bin_paths[bin]).append("\t").append(kFrames[f]);
+                    row.append("\t").append(std::to_string(at.begin)).append("\t").append(std::to_string(at.end));
+                };
+                if (verify) {
+                    kept.clear();
+                    for (size_t i = 0; i < mine.size(); ++i)
+                        if (verified.confirmed[h0 + i].distance != 0xFFFFFFFFu)
+                            kept.push_back({mine[i].query, mine[i].bin, mine[i].count, verified.confirmed[h0 + i].distance, '+', h0 + i});
+                    std::stable_sort(kept.begin(), kept.end(), [](const Confirmed& x, const Confirmed& y) { return x.bin != y.bin ? x.bin < y.bin : x.query < y.query; });
+                    for (const plan::WindowRun& run : plan::confirmed_runs(kept)) {
+                        const Confirmed &first = kept[run.first], &last = kept[run.last], &best = kept[run.best];
+                        begin_row(first.bin, first.query, last.query);
+                        s.append_count(row, best.count, lens[best.query]);
+                        s.append_verified(row, verified.confirmed[kept[run.nearest].at], false);
+                        *s.out << row << '\n';
+                        ++n_rows;
+                    }
+                    continue;
+                }
                 std::stable_sort(mine.begin(), mine.end(), [](const Hit& x, const Hit& y) { return x.bin < y.bin; });
                 plan::for_each_run(mine, [&](const Hit& first, const Hit& last, const Hit& best) {
-                    const txq::fw::Window wf = txq::fw::window_at(layout, first.query - w0), wl = txq::fw::window_at(layout, last.query - w0);
-                    const txq::fw::Span at = txq::fw::residues_on_record(L, f, wf.a, wl.a + wl.len);
-                    row.assign(c.names[r]).append("\t").append(image.bin_paths[first.bin]).append("\t").append(kFrames[f]);
-                    row.append("\t").append(std::to_string(at.begin)).append("\t").append(std::to_string(at.end));
+                    begin_row(first.bin, first.query, last.query);
                     s.append_count(row, best.count, lens[best.query]);
                     *s.out << row << '\n';
                     ++n_rows;
@@ -446,7 +481,7 @@ int search_plain(const Args& a, const IndexImage& image, unsigned long long erro
 int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
                                        {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false},
-                                       {'\0', "verify-frames", false}, {'\0', "verify-windows", false}, {'\0', "align", false}, {'\0', "all-targets", false},
+                                       {'\0', "verify-frames", false}, {'\0', "verify-windows", false}, {'\0', "verify-frame-windows", false}, {'\0', "align", false}, {'\0', "all-targets", false},
                                        {'\0', "window", true}, {'\0', "step", true}, {'\0', "frame-window", true}, {'\0', "frame-step", true}};
     Args a;
     unsigned long long errors = 0, window = 0, step = 0, frame_window = 0, frame_step = 0;
@@ -462,12 +497,22 @@ int cmd_search(int argc, char** argv) {
             if (a.has("window")) throw std::runtime_error("--frame-window cannot be combined with --window: one counts residues of a translated frame, the other letters of the record");
             if (a.has("step")) throw std::runtime_error("--frame-window cannot be combined with --step: the distance between frame windows is --frame-step");
             for (const char* o : {"verify-windows", "verify-frames", "all-targets", "align", "verify"})
-                if (a.has(o)) throw std::runtime_error(std::string("--frame-window cannot be combined with --") + o + ": frame windows are not verified in this version");
+                if (a.has(o))
+                    throw std::runtime_error(std::string("--frame-window cannot be combined with --") + o +
+                                             ": frame windows are not verified by it (they are confirmed with --verify-frame-windows, which gives distance, target and end)");
             if (!a.has("errors") && !a.has("threshold")) throw std::runtime_error("--frame-window needs -e E or --threshold F");
             frame_window = parse_count(a.get("frame-window", ""), "--frame-window must be a number of residues >= k", 1, 0x7FFFFFFFull);
             frame_step = std::max<unsigned long long>(1, frame_window / 2);
             if (a.has("frame-step"))
                 frame_step = parse_count(a.get("frame-step", ""), "--frame-step must be a number of residues in 1 .. --frame-window", 1, frame_window);
+        }
+        if (a.has("verify-frame-windows")) {
+            if (!a.has("translate")) throw std::runtime_error("--verify-frame-windows confirms the windows of --translate --frame-window W: it needs --translate");
+            for (const char* o : {"window", "step", "verify-windows", "verify-frames", "all-targets", "align", "verify"})
+                if (a.has(o)) throw std::runtime_error(std::string("--verify-frame-windows cannot be combined with --") + o + ": it confirms the windows of --frame-window, with distance, target and end, nothing more in this version");
+            if (!a.has("frame-window")) throw std::runtime_error("--verify-frame-windows confirms the windows of --frame-window W: it needs --frame-window");
+            if (a.has("threshold")) throw std::runtime_error("--verify-frame-windows confirms the windows of -e E: it cannot be combined with --threshold");
+            if (!a.has("errors")) throw std::runtime_error("--verify-frame-windows needs -e E: the number of residue edits a confirmed window may be away");
         }
         if (a.has("verify-windows")) {
             if (a.has("translate")) throw std::runtime_error("--verify-windows cannot be combined with --translate: it confirms the windows of --window, which --translate does not cut");

@@ -5,6 +5,7 @@
 #include "device_index.hpp"
 #include "search_plan.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
@@ -219,7 +220,7 @@ void DeviceIndex::search_windows(const std::vector<uint64_t>& values, const std:
 void DeviceIndex::search_translated_windows(std::string_view seq, const std::vector<uint64_t>& rec_offsets, uint32_t window, uint32_t step,
                                             const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts,
                                             std::vector<uint64_t>& win_offsets, std::vector<uint32_t>& lens, std::vector<uint32_t>& thresholds,
-                                            std::vector<TranslatedHit>& hits) {
+                                            std::vector<TranslatedHit>& hits, VerifiedWindows* verified) {
     if (!ix_) throw std::runtime_error("index not uploaded");
     if (shards_.size() > 1) throw std::runtime_error("search_translated_windows: one shard only");
     if (enc_.molecule() != Molecule::Peptide) throw std::runtime_error("search_translated_windows: a peptide index is needed");
@@ -239,7 +240,15 @@ void DeviceIndex::search_translated_windows(std::string_view seq, const std::vec
     lens.assign(N, 0);
     thresholds.assign(N, 0);
     hits.clear();
+    if (verified) {
+        if (!verified->verifier) throw std::runtime_error("search_translated_windows: verified windows need a verifier");
+        verified->stops.assign(N, 0);
+        verified->confirmed.clear();
+    }
     if (R == 0 || W == 0 || N == 0) return;
+    // --verify-frame-windows: the threshold follows from a window's stops (fw::stop_threshold) unless the A/B variable asks for §18's
+    const char* thr_env = std::getenv("TETREX_FRAME_WINDOW_THRESHOLD");
+    const bool stop_rule = verified && !(thr_env && std::string(thr_env) == "plain");
     const bool trace = std::getenv("TETREX_TRACE") != nullptr;
     // the record batches [cut[i], cut[i + 1]): at most 2^24 values by their bound, a larger record alone.  The buffers are sized
     // for the largest batch before the first one runs, so that no device memory of the call is freed or allocated between
@@ -253,10 +262,22 @@ void DeviceIndex::search_translated_windows(std::string_view seq, const std::vec
         d_off((6 * most_records + 1) * 8), d_woff((6 * most_records + 1) * 8), d_beg(most_windows * 8 + 8), d_len(most_windows * 4 + 8),
         d_thr(most_windows * 4 + 8), d_hit(sub_windows * W * 8), d_cnt;
     if (with_counts) d_cnt.reserve(sub_windows * W * 64 * 4);
+    // --verify-frame-windows: the frames as letters (six frames of L bytes are below 2 L residues; 16 bytes of slack as
+    // BinVerifier gives its own pattern buffer) and, per window, where its letters lie and its stops
+    DeviceBuffer d_frames, d_foff, d_lbeg, d_llen, d_stops;
+    if (verified) {
+        d_frames.reserve(2 * cuts.most_bytes + 16);
+        d_foff.reserve((6 * most_records + 1) * 8);
+        d_lbeg.reserve(most_windows * 8 + 8);
+        d_llen.reserve(most_windows * 4 + 8);
+        d_stops.reserve(most_windows * 4 + 8);
+    }
     txq_check(txq_memcpy_h2d(d_codes.p, enc_.aa_table().data(), 256), "h2d");
     HitLister lister;
     std::vector<uint64_t> rebased;
-    std::vector<uint32_t> thr;
+    std::vector<uint32_t> thr, lengths;
+    std::vector<BinVerifier::Candidate> candidates;
+    std::vector<VerifiedHit> batch_confirmed;
     const uint32_t bin0 = (uint32_t)(info_.shard_word0 * 64);
     for (size_t c = 0; c + 1 < cut.size(); ++c) {
         const size_t r0 = cut[c], r1 = cut[c + 1], nr = r1 - r0;
@@ -266,16 +287,30 @@ void DeviceIndex::search_translated_windows(std::string_view seq, const std::vec
         txq_check(txq_translate_windows_device((const uint8_t*)d_seq.p, (const uint64_t*)d_rec.p, nr, k, (const uint8_t*)d_codes.p, window, step,
                                                (uint64_t*)d_val.p, (uint64_t*)d_off.p, (uint64_t*)d_woff.p, (uint64_t*)d_beg.p, (uint32_t*)d_len.p, nullptr),
                   "txq_translate_windows_device");
+        uint64_t frames_bytes = 0;
+        if (verified) {  // the frames of the same bytes, then every window's letters, stops and threshold: nothing comes back in between
+            frames_bytes = txq_translate_frames_bound(rebased.data(), nr);
+            if (frames_bytes == UINT64_MAX || frames_bytes > 2 * cuts.most_bytes) txq_check(TXQ_ERR_ARG, "txq_translate_frames_bound");
+            txq_check(txq_translate_frames_device((const uint8_t*)d_seq.p, (const uint64_t*)d_rec.p, nr, (uint8_t*)d_frames.p, frames_bytes,
+                                                  (uint64_t*)d_foff.p, nullptr), "txq_translate_frames_device");
+            txq_check(txq_frame_window_letters_device((const uint64_t*)d_rec.p, nr, k, window, step, (const uint8_t*)d_frames.p, frames_bytes,
+                                                      (const uint64_t*)d_foff.p, (const uint64_t*)d_woff.p, (const uint32_t*)d_len.p, nw, verified->edits,
+                                                      (uint64_t*)d_lbeg.p, (uint32_t*)d_llen.p, (uint32_t*)d_stops.p, (uint32_t*)d_thr.p, nullptr),
+                      "txq_frame_window_letters_device");
+        }
         txq_check(txq_memcpy_d2h(lens.data() + w0, d_len.p, nw * 4), "d2h");
+        if (verified) txq_check(txq_memcpy_d2h(verified->stops.data() + w0, d_stops.p, nw * 4), "d2h");
         thr.resize(nw);
         bool any = false;
         for (uint64_t j = 0; j < nw; ++j) {
-            const uint64_t w = lens[w0 + j], t = w ? threshold_of(w) : 0;
-            thr[j] = device_threshold(t);
-            if (t) thresholds[w0 + j] = thr[j], any = true;
+            const uint64_t w = lens[w0 + j];
+            // (with the stop rule this is what the device wrote into d_thr: the same function of the same two numbers)
+            thr[j] = stop_rule ? txq::fw::stop_threshold((uint32_t)w, verified->stops[w0 + j], k, verified->edits) : device_threshold(w ? threshold_of(w) : 0);
+            if (thr[j] != 0xFFFFFFFFu) thresholds[w0 + j] = thr[j], any = true;
         }
         if (!any) continue;
-        txq_check(txq_memcpy_h2d(d_thr.p, thr.data(), nw * 4), "h2d");
+        if (!stop_rule) txq_check(txq_memcpy_h2d(d_thr.p, thr.data(), nw * 4), "h2d");
+        const size_t h0 = hits.size();
         // sub-ranges of the batch's windows: the begins are absolute in the batch's values, so nothing is sent again
         for (uint64_t j0 = 0; j0 < nw; j0 += sub_windows) {
             const size_t n = (size_t)std::min<uint64_t>(sub_windows, nw - j0);
@@ -290,6 +325,36 @@ void DeviceIndex::search_translated_windows(std::string_view seq, const std::vec
                 std::fprintf(stderr, "[tetrex search] frame window batch: records %zu..%zu, windows %llu..%llu, %llu hits\n", r0, r1,
                              (unsigned long long)(w0 + j0), (unsigned long long)(w0 + j0 + n), (unsigned long long)total);
         }
+        if (!verified) continue;
+        // --verify-frame-windows: the batch's hits are candidates, window index = the window's index within the batch
+        verified->confirmed.resize(hits.size());
+        if (hits.size() == h0) continue;
+        candidates.clear();
+        lengths.clear();
+        const auto frame_of = [&](uint64_t j) { return (size_t)(std::upper_bound(win_offsets.begin(), win_offsets.end(), j) - win_offsets.begin()) - 1; };
+        const auto residues_of = [&](uint64_t j, size_t q) {  // window j of the call, in frame q
+            const uint64_t L = rec_offsets[q / 6 + 1] - rec_offsets[q / 6];
+            return txq::fw::window_at(txq::fw::frame_plan(txq::tr::frame_len(L, (uint32_t)(q % 3)), k, window, step), j - win_offsets[q]);
+        };
+        for (size_t h = h0; h < hits.size(); ++h) {
+            candidates.push_back({(uint32_t)(hits[h].query - w0), hits[h].bin});
+            lengths.push_back((uint32_t)residues_of(hits[h].query, frame_of(hits[h].query)).len);
+        }
+        size_t held = ~(size_t)0;  // the frame translated last: the host routes ask for windows in ascending order
+        std::string held_letters;
+        const auto window_letters = [&](uint32_t j) {
+            const size_t q = frame_of(w0 + j);
+            if (q != held) {
+                held_letters = translate_frame(seq.substr(rec_offsets[q / 6], rec_offsets[q / 6 + 1] - rec_offsets[q / 6]), (unsigned)(q % 6));
+                held = q;
+            }
+            const txq::fw::Window at = residues_of(w0 + j, q);
+            return held_letters.substr(at.a, at.len);
+        };
+        verified->verifier->verify_windows(BinVerifier::DeviceWindows{(const uint8_t*)d_frames.p, frames_bytes, (const uint64_t*)d_lbeg.p,
+                                                                      (const uint32_t*)d_llen.p, (size_t)nw},
+                                           candidates, lengths, window_letters, batch_confirmed);
+        std::move(batch_confirmed.begin(), batch_confirmed.end(), verified->confirmed.begin() + (long)h0);
     }
 }
 
