@@ -22,6 +22,7 @@
  *   txq_edit_search_long / _device  (the same for patterns of up to 4096 bytes, the pattern spread over the lanes of a wave)
  *   txq_edit_align / _device  (no counterpart: start and CIGAR of the pairs a search call confirmed, `--verify --align`)
  *   txq_edit_windows / _device  (no counterpart: txq_edit_search for windows into one letter buffer, `--window --verify-windows`)
+ *   txq_edit_align_windows / _device  (no counterpart: txq_edit_align for windows against a table of text views, `--align-windows`)
  *   txq_frame_window_letters / _device  (no counterpart: the letters, stops and thresholds of translated windows, `--verify-frame-windows`)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every function returns 0 on success or a
@@ -499,6 +500,43 @@ int txq_edit_align_device(const uint8_t* d_patterns, const uint64_t* d_pat_offse
 int txq_edit_align(const uint8_t* patterns, const uint64_t* pat_offsets, size_t n_patterns, const uint8_t* text, const uint64_t* rec_offsets,
                    size_t n_records, const uint64_t* group_offsets, size_t n_groups, const uint32_t* pairs, size_t n_pairs, const uint32_t* results,
                    const uint8_t* codes, uint32_t max_errors, uint32_t* align);  /* host buffers, synchronous */
+
+/* The same for patterns that are WINDOWS into one letter buffer and texts behind a TABLE OF VIEWS (`tetrex search --window
+ * --verify-windows --align-windows` and its frame-window sibling; not in the reference).  Window p is
+ * d_letters[d_win_begin[p] .. d_win_begin[p] + d_win_len[p]), as txq_edit_windows_device takes them: in any order, overlapping,
+ * repeated.  View g is d_views[g]: the records of one bin, wherever the caller keeps them, so ONE call aligns pairs of any number
+ * of bins.  Pair i is d_pairs[3 i ..] = (window, view, cap); the view is ONE group, all its records.  d_results[3 i ..] is the
+ * triple (d, r, j) a search call answered for that window against that view, r an index into the view's offsets; "none" and the
+ * refusal marker pass through as in txq_edit_align_device.  The answers, their stride, the markers and max_errors are
+ * txq_edit_align_device's, word for word.  THE RESULT IS DEFINED AS what txq_edit_align answers with the window written out as
+ * the pattern and the view's records as the one group of a text of its own.
+ * Windows of 1 .. TXQ_EDIT_MAX_PATTERN letters run here; a longer one is declined (start = 0xFFFFFFFE, nothing else written):
+ * the caller takes it to txh_edit_align.  A pair is refused (start = 0xFFFFFFFF, n_runs = 0xFFFFFFFE, zero run words) when its
+ * window index is >= n_windows, its view index >= n_views, its window empty or leaving letters_bytes.  A triple that is not a
+ * cell of the pair's matrix is declined as there: r >= the view's n_records, offsets that leave text_bytes or do not ascend, j
+ * beyond the record, d > m, d > TXQ_EDIT_ALIGN_MAX_DISTANCE, d > max_errors, D[m][j] != d.
+ * The view table's CONTENTS (pointers and sizes) are the caller's word, like any pointer argument; everything read THROUGH them
+ * is device data: no load or store leaves [d_text, d_text + text_bytes), the view's n_records + 1 offsets, letters_bytes or the
+ * pair's own answer words, whatever arrays and triples say.  TXQ_ERR_ARG only for what the call can see: null pointers, more
+ * than 2^31 - 1 pairs, max_errors above TXQ_EDIT_ALIGN_MAX_ERRORS.  One launch, one wave per pair; the call allocates nothing,
+ * reads nothing back and waits for nothing.  d_workspace: TXQ_EDIT_ALIGN_WINDOWS_WORKSPACE(n_pairs) bytes — none, the direction
+ * bits stay in LDS; the argument may be null.
+ * txq_edit_align_windows is the synchronous twin: `views` is a host array of views that hold HOST pointers.  It checks its
+ * buffers first as txq_edit_windows does (TXQ_ERR_ARG, nothing launched; a view's offsets ascend and end within text_bytes; a
+ * window above TXQ_EDIT_MAX_PATTERN passes: it is declined, not refused), stages all texts into one allocation, builds the device
+ * table and copies the answers back.  A declined pair's words behind the marker keep what `align` held. */
+typedef struct txq_text_view {      /* the records of one bin */
+    const uint8_t*  d_text;         /* records back to back */
+    const uint64_t* d_rec_offsets;  /* n_records + 1 ascending offsets into d_text */
+    uint64_t n_records, text_bytes;
+} txq_text_view;
+#define TXQ_EDIT_ALIGN_WINDOWS_WORKSPACE(n_pairs) ((size_t)0)
+int txq_edit_align_windows_device(const uint8_t* d_letters, size_t letters_bytes, const uint64_t* d_win_begin, const uint32_t* d_win_len, size_t n_windows,
+                                  const txq_text_view* d_views, size_t n_views, const uint32_t* d_pairs, size_t n_pairs, const uint32_t* d_results,
+                                  const uint8_t* d_codes, uint32_t max_errors, uint32_t* d_align, void* d_workspace, void* stream);
+int txq_edit_align_windows(const uint8_t* letters, size_t letters_bytes, const uint64_t* win_begin, const uint32_t* win_len, size_t n_windows,
+                           const txq_text_view* views, size_t n_views, const uint32_t* pairs, size_t n_pairs, const uint32_t* results,
+                           const uint8_t* codes, uint32_t max_errors, uint32_t* align);  /* host views, synchronous */
 
 /* Which records of a bin does a regular expression match?  (`tetrex query --gpu-verify`; not in the reference.)
  * An automaton is a blob of include/txq_regex.h, where its layout and the meaning of "matches" are stated (as code: the

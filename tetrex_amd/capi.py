@@ -29,7 +29,7 @@ SYMBOLS = [
     "txq_hit_list_device", "txq_edit_search", "txq_edit_search_device",
     "txq_edit_search_long", "txq_edit_search_long_device", "txq_edit_align", "txq_edit_align_device",
     "txq_edit_targets", "txq_edit_targets_device", "txq_edit_targets_long", "txq_edit_targets_long_device",
-    "txq_edit_windows", "txq_edit_windows_device",
+    "txq_edit_windows", "txq_edit_windows_device", "txq_edit_align_windows", "txq_edit_align_windows_device",
     "txq_regex_filter", "txq_regex_filter_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
@@ -60,6 +60,11 @@ class IndexInfo(C.Structure):
                 ("shard_words", C.c_uint64), ("n_ibf", C.c_uint64), ("device_bytes", C.c_uint64),
                 ("is_hibf", C.c_int), ("device", C.c_int), ("join_or", C.c_int), ("shard_rank", C.c_int), ("n_shards", C.c_int),
                 ("reserved", C.c_int)]
+
+
+class TextView(C.Structure):
+    """txq_text_view: the records of one bin (txq_edit_align_windows, include/txq.h)"""
+    _fields_ = [("text", C.c_void_p), ("rec_offsets", C.c_void_p), ("n_records", C.c_uint64), ("text_bytes", C.c_uint64)]
 
 
 _LIB = None
@@ -121,6 +126,10 @@ def lib():
                                             C.c_void_p]
         L.txq_edit_align.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.txq_edit_align_windows_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.txq_edit_align_windows.argtypes = [C.c_void_p, C.c_size_t, u64p, u32p, C.c_size_t, C.POINTER(TextView), C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.txq_edit_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                               C.c_size_t, C.c_void_p, C.c_void_p]
@@ -979,6 +988,74 @@ def edit_align_device(patterns, records, groups, pairs, codes, max_errors, resul
         return d_res.to_numpy(np.uint32, (n, 3)), d_align.to_numpy(np.uint8, (guard + body + guard,))
     finally:
         for b in bufs + [d_res, d_work, d_align]:
+            b.free()
+
+
+def edit_align_windows_arrays(letters, win_begin, win_len, texts, pairs, results, codes, max_errors):
+    """the arguments of edit_align_windows as contiguous arrays: (letters, window begins uint64, window lengths uint32, a list of
+    (text bytes, record offsets) per view, pairs (n, 3) uint32, results (n, 3) uint32, codes)"""
+    let = np.ascontiguousarray(np.frombuffer(letters.encode() if isinstance(letters, str) else bytes(letters), dtype=np.uint8)
+                               if not isinstance(letters, np.ndarray) else letters, dtype=np.uint8)
+    wb, wl = np.ascontiguousarray(win_begin, dtype=np.uint64), np.ascontiguousarray(win_len, dtype=np.uint32)
+    views = []
+    for t in texts:
+        txt, ro = t if isinstance(t, tuple) else _records(t)
+        views.append((np.ascontiguousarray(txt, dtype=np.uint8), np.ascontiguousarray(ro, dtype=np.uint64)))
+    pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 3)
+    res = np.ascontiguousarray(results, dtype=np.uint32).reshape(-1, 3)
+    cd = np.ascontiguousarray(codes, dtype=np.uint8)
+    if cd.size != 256 or wb.size != wl.size or res.shape != pr.shape or any(ro.size < 1 for _, ro in views) or not 0 <= int(max_errors) <= 1 << 24:
+        raise TxqError(-1, "edit_align_windows: windows, views, one result triple per pair, class table and max_errors (at most 2^24) disagree")
+    return let, wb, wl, views, pr, res, cd
+
+
+def edit_align_windows(letters, win_begin, win_len, texts, pairs, results, codes, max_errors, raw=False):
+    """edit_align for patterns that are windows into one letter buffer and texts behind a table of views (txq_edit_align_windows,
+    include/txq.h): window p is letters[win_begin[p] : win_begin[p] + win_len[p]], texts is a list of record lists (or of (uint8
+    array, uint64 offsets)), one per view, pairs are rows of (window, view, cap), results the (n, 3) triples a search answered
+    for each window against the records of its view as one group.  Returns what edit_align returns."""
+    let, wb, wl, views, pr, res, cd = edit_align_windows_arrays(letters, win_begin, win_len, texts, pairs, results, codes, max_errors)
+    table = (TextView * max(len(views), 1))()
+    for g, (txt, ro) in enumerate(views):
+        table[g] = TextView(txt.ctypes.data, ro.ctypes.data, ro.size - 1, txt.size)
+    out = np.full((pr.shape[0], edit_align_stride(max_errors)), 0xA5A5A5A5, dtype=np.uint32)
+    check(lib().txq_edit_align_windows(let.ctypes.data, let.size, wb.ctypes.data_as(u64p), wl.ctypes.data_as(u32p), wb.size, table, len(views),
+                                       pr.ctypes.data, pr.shape[0], res.ctypes.data, cd.ctypes.data, int(max_errors), out.ctypes.data))
+    return out if raw else decode_alignments(out, max_errors)
+
+
+def edit_align_windows_device(letters, win_begin, win_len, texts, pairs, results, codes, max_errors, letters_at=0, text_at=0, guard=64, fill=0xA5,
+                              stream=None):
+    """txq_edit_align_windows_device on buffers the caller places: the letters begin letters_at bytes behind a 16-byte boundary,
+    every view's text text_at bytes behind one in an allocation of its own — with text_at = 0 at its very start —, the arrays go
+    to the device as they are (the call cannot read them: what they name wrongly is the kernel's to refuse or decline) and the
+    answers lie between `guard` bytes of `fill` on either side.  stream: a hipStream_t as an integer; None: the default stream.
+    Returns the buffer uint8[guard + 4 n stride + guard]: the answers begin at buffer[guard], and what the call did not write
+    still holds `fill`."""
+    let, wb, wl, views, pr, res, cd = edit_align_windows_arrays(letters, win_begin, win_len, texts, pairs, results, codes, max_errors)
+    n, body = pr.shape[0], 4 * pr.shape[0] * edit_align_stride(max_errors)
+
+    def around(a, at):
+        b = np.full(at + a.size + 33, ord("A"), dtype=np.uint8)
+        b[at:at + a.size] = a
+        return b
+
+    pad = lambda a: np.concatenate([a.view(np.uint8).ravel(), np.zeros(16, dtype=np.uint8)])  # (no buffer of no bytes)
+    d_texts = [DeviceBuffer.from_numpy(around(txt, text_at)) for txt, _ in views]
+    d_recs = [DeviceBuffer.from_numpy(pad(ro)) for _, ro in views]
+    table = np.zeros((max(len(views), 1), 4), dtype=np.uint64)
+    for g, (txt, ro) in enumerate(views):
+        table[g] = (d_texts[g].ptr + text_at, d_recs[g].ptr, ro.size - 1, txt.size)
+    bufs = [DeviceBuffer.from_numpy(x) for x in (around(let, letters_at), pad(wb), pad(wl), table, pad(pr), pad(res), cd)]
+    d_align = DeviceBuffer.from_numpy(np.full(guard + body + guard, fill, dtype=np.uint8))
+    try:
+        assert bufs[0].ptr % 16 == 0 and all(b.ptr % 16 == 0 for b in d_texts) and guard % 4 == 0
+        check(lib().txq_edit_align_windows_device(bufs[0].ptr + letters_at, let.size, bufs[1].ptr, bufs[2].ptr, wb.size, bufs[3].ptr, len(views), bufs[4].ptr,
+                                                  n, bufs[5].ptr, bufs[6].ptr, int(max_errors), d_align.ptr + guard, None, stream))
+        synchronize()
+        return d_align.to_numpy(np.uint8, (guard + body + guard,))
+    finally:
+        for b in bufs + d_texts + d_recs + [d_align]:
             b.free()
 
 

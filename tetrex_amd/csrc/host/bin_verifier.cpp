@@ -70,7 +70,7 @@ ResidentBins::Bin& ResidentBins::resident(uint32_t bin, const std::string& text,
     const uint64_t n = rec.size() - 1;
     rec.push_back(0);  // behind the record offsets: the one group's offsets {0, n}
     rec.push_back(n);
-    const uint64_t bytes = text.size() + 16 + rec.size() * 8;
+    const uint64_t bytes = bytes_on_device(text.size(), n);
     while (held_bytes_ && held_bytes_ + bytes > limit_bytes_) {  // the bin used longest ago leaves
         Bin* oldest = nullptr;
         for (Bin& o : bins_)
@@ -354,11 +354,19 @@ void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std:
 void BinVerifier::verify_windows(const std::vector<std::string>& queries, const std::vector<Window>& windows, const std::vector<Candidate>& candidates,
                                  std::vector<Hit>& hits) {
     hits.assign(candidates.size(), Hit{});
-    if (candidates.empty()) return;
     const size_t strands = dna_ ? 2 : 1;
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    kept_.on_device = DeviceWindows{};
+    kept_.strands = strands;
+    kept_.entry_of.assign(candidates.size(), kNone);
+    kept_.letters_of = [&queries, &windows, &candidates](size_t i, size_t strand) {
+        const Window& w = windows[candidates[i].query];
+        const std::string s = queries[w.record].substr(w.begin, w.len);
+        return strand ? reverse_complement(s) : s;
+    };
+    if (candidates.empty()) return;
     const char* route_env = std::getenv("TETREX_VERIFY_WINDOWS");
     const bool all_written = route_env && std::string(route_env) == "written";
-    constexpr uint32_t kNone = 0xFFFFFFFFu;
     // by route: what the window kernel takes, and what is written out (longer windows; everything for an A/B run)
     std::vector<size_t> on_kernel, written;
     for (size_t i = 0; i < candidates.size(); ++i) {
@@ -412,12 +420,17 @@ void BinVerifier::verify_windows(const std::vector<std::string>& queries, const 
             win_len.push_back(w.len);
         }
     }
-    DeviceBuffer d_letters(letters.size() + 16), d_begin(win_begin.size() * 8), d_len(win_len.size() * 4);
+    // (with keep_windows the buffers stay until the next call: align_windows reads the selected windows where they are)
+    DeviceBuffer own_letters, own_begin, own_len;
+    DeviceBuffer &d_letters = keep_windows_ ? kept_.letters : own_letters, &d_begin = keep_windows_ ? kept_.begin : own_begin,
+                 &d_len = keep_windows_ ? kept_.len : own_len;
+    d_letters.reserve(letters.size() + 16), d_begin.reserve(win_begin.size() * 8), d_len.reserve(win_len.size() * 4);
     txq_check(txq_memcpy_h2d(d_letters.p, letters.data(), letters.size()), "h2d");
     txq_check(txq_memcpy_h2d(d_begin.p, win_begin.data(), win_begin.size() * 8), "h2d");
     txq_check(txq_memcpy_h2d(d_len.p, win_len.data(), win_len.size() * 4), "h2d");
-    run_windows(DeviceWindows{(const uint8_t*)d_letters.p, letters.size(), (const uint64_t*)d_begin.p, (const uint32_t*)d_len.p, win_begin.size()}, strands,
-                on_kernel, [&](size_t i) { return entry_of[candidates[i].query]; }, candidates, hits);
+    kept_.on_device = DeviceWindows{(const uint8_t*)d_letters.p, letters.size(), (const uint64_t*)d_begin.p, (const uint32_t*)d_len.p, win_begin.size()};
+    for (size_t i : on_kernel) kept_.entry_of[i] = entry_of[candidates[i].query];
+    run_windows(kept_.on_device, strands, on_kernel, [&](size_t i) { return entry_of[candidates[i].query]; }, candidates, hits);
 }
 
 void BinVerifier::run_windows(const DeviceWindows& w, size_t strands, const std::vector<size_t>& on_kernel, const std::function<uint32_t(size_t)>& entry_of,
@@ -464,12 +477,16 @@ void BinVerifier::run_windows(const DeviceWindows& w, size_t strands, const std:
 void BinVerifier::verify_windows(const DeviceWindows& windows, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& lengths,
                                  const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits) {
     hits.assign(candidates.size(), Hit{});
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    kept_.on_device = windows;
+    kept_.strands = 1;
+    kept_.entry_of.assign(candidates.size(), kNone);
+    kept_.letters_of = [&candidates, letters](size_t i, size_t) { return letters(candidates[i].query); };
     if (candidates.empty()) return;
     if (lengths.size() != candidates.size()) throw std::runtime_error("tetrex search --verify-frame-windows: candidates and lengths disagree");
     if (dna_) throw std::runtime_error("tetrex search --verify-frame-windows: translated windows have one strand, the verifier two");
     const char* route_env = std::getenv("TETREX_VERIFY_FRAME_WINDOWS");
     const bool all_written = route_env && std::string(route_env) == "written";
-    constexpr uint32_t kNone = 0xFFFFFFFFu;
     std::vector<size_t> on_kernel, written;
     for (size_t i = 0; i < candidates.size(); ++i) {
         if (candidates[i].query >= windows.n_windows) throw std::runtime_error("tetrex search --verify-frame-windows: a candidate names no window");
@@ -499,7 +516,116 @@ void BinVerifier::verify_windows(const DeviceWindows& windows, const std::vector
     std::stable_sort(on_kernel.begin(), on_kernel.end(), [&](size_t x, size_t y) {
         return std::tie(candidates[x].bin, candidates[x].query) < std::tie(candidates[y].bin, candidates[y].query);
     });
+    for (size_t i : on_kernel) kept_.entry_of[i] = candidates[i].query;
     run_windows(windows, 1, on_kernel, [&](size_t i) { return candidates[i].query; }, candidates, hits);
+}
+
+// ---- tetrex search --verify-windows / --verify-frame-windows --align-windows ------------------------------------------------
+
+void BinVerifier::align_windows(const std::vector<Candidate>& candidates, const std::vector<Selected>& selection) {
+    if (selection.empty()) return;
+    if (!keep_windows_) throw std::runtime_error("tetrex search --align-windows: verify_windows was not asked to keep its windows");
+    if (kept_.entry_of.size() != candidates.size()) throw std::runtime_error("tetrex search --align-windows: the candidates are not those of the last verify_windows call");
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    const char* align_env = std::getenv("TETREX_VERIFY_ALIGN");
+    const bool on_device = !(align_env && std::string(align_env) == "host");
+    const uint32_t device_errors = std::min<uint32_t>(errors_, TXQ_EDIT_ALIGN_MAX_DISTANCE);
+    const size_t stride = TXQ_EDIT_ALIGN_STRIDE(device_errors);
+    // a selected window as the pair the device aligns: its entry on the kept strand, and the triple (d, r, j) of its hit
+    struct Sent {
+        PendingAlign pair;
+        uint32_t bin, entry;
+    };
+    std::vector<Sent> sent;
+    std::vector<PendingAlign> pending;
+    for (const Selected& x : selection) {
+        if (x.candidate >= candidates.size() || !x.hit || x.hit->distance == kEditNone || !x.hit->target)
+            throw std::runtime_error("tetrex search --align-windows: a selected window is not a confirmed candidate");
+        const uint32_t bin = candidates[x.candidate].bin, entry = kept_.entry_of[x.candidate];
+        const std::vector<std::string>& names = bins_.at(bin).names;
+        const size_t r = (size_t)(x.hit->target - names.data()), strand = x.hit->strand == '-' ? 1 : 0;
+        if (r >= names.size() || strand >= kept_.strands) throw std::runtime_error("tetrex search --align-windows: a hit that its bin did not give");
+        const PendingAlign pair{x.candidate, strand, x.hit->distance, (uint32_t)r, x.hit->end, x.hit};
+        if (on_device && entry != kNone && pair.d <= device_errors) sent.push_back({pair, bin, entry + (uint32_t)strand});
+        else pending.push_back(pair);
+    }
+    std::stable_sort(sent.begin(), sent.end(), [](const Sent& x, const Sent& y) { return x.bin < y.bin; });
+    // one round, sent[a, b) — whole bins, all resident: their views, the pairs and the triples go up, ONE call, one copy back
+    const auto run_round = [&](size_t a, size_t b) {
+        if (a == b) return;
+        std::vector<txq_text_view> views;
+        std::vector<uint32_t> pairs, triples;
+        bool all_resident = true;
+        for (size_t k = a; k < b; ++k) {
+            if (k == a || sent[k].bin != sent[k - 1].bin) {
+                all_resident = all_resident && bins_.is_resident(sent[k].bin);
+                const ResidentBins::Bin& e = bins_.at(sent[k].bin);
+                views.push_back({(const uint8_t*)e.d_text, (const uint64_t*)e.d_rec, e.n_records, e.text_bytes});
+            }
+            pairs.insert(pairs.end(), {sent[k].entry, (uint32_t)(views.size() - 1), errors_});
+            triples.insert(triples.end(), {sent[k].pair.d, sent[k].pair.r, sent[k].pair.j});
+        }
+        if (!all_resident) {  // a bin left while a later one of the round came: the host answers the round
+            for (size_t k = a; k < b; ++k) pending.push_back(sent[k].pair);
+            return;
+        }
+        const size_t n = b - a;
+        DeviceBuffer d_views(views.size() * sizeof(txq_text_view)), d_pairs(pairs.size() * 4), d_triples(triples.size() * 4), d_align(n * stride * 4);
+        txq_check(txq_memcpy_h2d(d_views.p, views.data(), views.size() * sizeof(txq_text_view)), "h2d");
+        txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
+        txq_check(txq_memcpy_h2d(d_triples.p, triples.data(), triples.size() * 4), "h2d");
+        const DeviceWindows& w = kept_.on_device;
+        txq_check(txq_edit_align_windows_device(w.d_letters, w.bytes, w.d_begin, w.d_len, w.n_windows, (const txq_text_view*)d_views.p, views.size(),
+                                                (const uint32_t*)d_pairs.p, n, (const uint32_t*)d_triples.p, (const uint8_t*)d_codes_, device_errors,
+                                                (uint32_t*)d_align.p, nullptr, nullptr),
+                  "txq_edit_align_windows_device");
+        ++n_align_windows_calls_;
+        std::vector<uint32_t> words(n * stride);
+        txq_check(txq_memcpy_d2h(words.data(), d_align.p, words.size() * 4), "d2h");  // (waits for the kernel)
+        for (size_t k = 0; k < n; ++k) {
+            const uint32_t* o = words.data() + stride * k;
+            const PendingAlign& p = sent[a + k].pair;
+            if (o[0] == kEditNone) throw std::runtime_error("tetrex search --align-windows: the device refused a pair of bin " + std::to_string(sent[a + k].bin));
+            if (o[0] < kEditNotAligned) {
+                p.into->start = o[0];
+                p.into->runs.assign(o + 2, o + 2 + o[1]);
+                ++n_align_device_;
+            } else pending.push_back(p);
+        }
+    };
+    // the rounds: bins in order while they fit the cache together.  A bin's bytes are known before it is uploaded (a bin that is
+    // not resident is read first), so a round ends BEFORE the bin that would push one of its own out.
+    size_t round_begin = 0;
+    uint64_t round_bytes = 0;
+    for_each_bin_run(0, sent.size(), [&](size_t k) { return sent[k].bin; }, [&](uint32_t bin, size_t a, size_t) {
+        std::string text;
+        std::vector<uint64_t> rec;
+        std::vector<std::string> names;
+        const bool there = bins_.is_resident(bin);
+        if (!there) bins_.read(bin, text, rec, names);
+        const uint64_t bytes = there ? bins_.at(bin).device_bytes : ResidentBins::bytes_on_device(text.size(), rec.size() - 1);
+        if (a > round_begin && round_bytes + bytes > bins_.limit_bytes()) {
+            run_round(round_begin, a);
+            round_begin = a, round_bytes = 0;
+        }
+        if (there) bins_.resident(bin);
+        else bins_.resident(bin, text, rec, names);
+        round_bytes += bytes;
+    });
+    run_round(round_begin, sent.size());
+    if (pending.empty()) return;
+    // the host route: the windows as strings, made one after the other (the way to a frame window's letters keeps state), then
+    // the pairs of a bin side by side
+    std::stable_sort(pending.begin(), pending.end(), [](const PendingAlign& x, const PendingAlign& y) { return x.candidate < y.candidate; });
+    std::vector<std::string> strings;
+    std::vector<size_t> string_of(candidates.size() * kept_.strands, ~(size_t)0);
+    for (const PendingAlign& p : pending) {
+        size_t& at = string_of[p.candidate * kept_.strands + p.strand];
+        if (at != ~(size_t)0) continue;
+        at = strings.size();
+        strings.push_back(kept_.letters_of(p.candidate, p.strand));
+    }
+    align_rest(pending, candidates, [&](size_t i, size_t strand) { return strings[string_of[i * kept_.strands + strand]]; });
 }
 
 // ---- tetrex search --verify --all-targets ------------------------------------------------------------------------------

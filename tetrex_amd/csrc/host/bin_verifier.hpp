@@ -1,6 +1,8 @@
 // Host side: the records of bins' FASTA files resident on the GPU, and `tetrex search --verify` on them through the C-ABI
 // (include/txq.h).  Product code; requires a gfx950 GPU.
 #pragma once
+#include "device_buffer.hpp"
+
 #include <cstdint>
 #include <functional>
 #include <string>
@@ -46,6 +48,10 @@ class ResidentBins {
     // the same with the file already read (text, rec, names as read() gives them; names are moved from)
     Bin& resident(uint32_t bin, const std::string& text, std::vector<uint64_t>& rec, std::vector<std::string>& names);
     bool is_resident(uint32_t bin) const { return bins_[bin].d_rec != nullptr; }
+    // the device bytes of a bin of n_records records in text_bytes letters, and the most the cache holds (TETREX_VERIFY_TEXT_MB):
+    // what a caller needs to plan several bins that must be resident TOGETHER (BinVerifier::align_windows)
+    static uint64_t bytes_on_device(uint64_t text_bytes, uint64_t n_records) { return text_bytes + 16 + (n_records + 3) * 8; }
+    uint64_t limit_bytes() const { return limit_bytes_; }
     Bin& at(uint32_t bin) { return bins_[bin]; }
     size_t size() const { return bins_.size(); }
 
@@ -88,6 +94,14 @@ class ResidentBins {
 // call per candidate bin on its resident text, all queued before the one copy back; strands are settled as above.  Windows of
 // more than TXQ_EDIT_MAX_PATTERN letters, and with TETREX_VERIFY_WINDOWS=written every window, are written out as strings and
 // take verify() with its three routes.
+// `--align-windows` (align_windows): start and runs of the windows the caller selects after its run merge — one
+// per row.  set_align stays off: nothing is aligned during verification.  After keep_windows(true) verify_windows keeps its
+// letter and window buffers (and the way to a window's string) until its next call; align_windows cuts the selection into rounds of bins that fit
+// TETREX_VERIFY_TEXT_MB together (one bin is always a round), makes a round's bins resident, uploads a table of their views,
+// the pairs and the triples, queues ONE txq_edit_align_windows_device and copies back once.  What that call declines (more than
+// TXQ_EDIT_ALIGN_MAX_DISTANCE edits), windows that did not take the window kernel (longer than TXQ_EDIT_MAX_PATTERN, the
+// `written` routes), a round whose bins did not all stay resident, and with TETREX_VERIFY_ALIGN=host every pair, go to the host
+// twin as above.
 class BinVerifier {
   public:
     BinVerifier(const std::vector<std::string>& bin_paths, bool dna, uint32_t errors);
@@ -138,6 +152,17 @@ class BinVerifier {
     };
     void verify_windows(const DeviceWindows& windows, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& lengths,
                         const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits);
+    // `--align-windows`: selection[k] names a candidate of the LAST verify_windows call (either form) and the confirmed hit that
+    // answers it; the hit gets start and runs (include/txq.h at txq_edit_align_windows_device).  `candidates` are that call's,
+    // and what it was given — queries and windows, or the device buffers and `letters` — must still be there.
+    struct Selected {
+        size_t candidate;
+        Hit* hit;
+    };
+    // (asked for before verify_windows: its first form then keeps its device buffers instead of freeing them on return)
+    void keep_windows(bool on) { keep_windows_ = on; }
+    void align_windows(const std::vector<Candidate>& candidates, const std::vector<Selected>& selection);
+    size_t n_align_windows_calls() const { return n_align_windows_calls_; }  // txq_edit_align_windows_device calls
     size_t n_candidates() const { return n_candidates_; }
     size_t n_confirmed() const { return n_confirmed_; }
     size_t n_targets() const { return n_targets_; }  // `--all-targets`: the rows of all confirmed pairs
@@ -197,6 +222,18 @@ class BinVerifier {
     bool align_ = false;
     size_t n_align_device_ = 0, n_align_host_ = 0;
     size_t n_targets_ = 0;
+    // what the last verify_windows call left for align_windows: where its windows are on the device (the first form's own
+    // buffers, the second form's caller's), `strands` entries from entry_of[candidate] (0xFFFFFFFF: the candidate did not take the
+    // window kernel), and the window of (candidate, strand) as a string
+    struct KeptWindows {
+        DeviceBuffer letters, begin, len;
+        DeviceWindows on_device{};
+        size_t strands = 1;
+        std::vector<uint32_t> entry_of;
+        Letters letters_of;
+    } kept_;
+    size_t n_align_windows_calls_ = 0;
+    bool keep_windows_ = false;
 };
 
 }  // namespace tetrex

@@ -144,6 +144,10 @@ class DeviceIndex {
         uint32_t edits = 0;
         std::vector<uint32_t> stops;         // out: the stops of every window
         std::vector<VerifiedHit> confirmed;  // out: confirmed[i] answers hits[i]
+        // `--align-windows`, optional: called after the verification of every device batch with the batch's range
+        // [h0, h1) of hits — whole records —, it returns the indexes of the confirmed hits to align; those get start and runs
+        // (BinVerifier::align_windows) before the batch's letters are overwritten by the next one
+        std::function<std::vector<size_t>(size_t, size_t)> select;
     };
     void search_translated_windows(std::string_view seq, const std::vector<uint64_t>& rec_offsets, uint32_t window, uint32_t step,
                                    const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& win_offsets,

@@ -33,6 +33,7 @@ struct Search {
     // --verify / --verify-frames (make_verifier)
     std::unique_ptr<BinVerifier> verifier;
     bool align = false, all_targets = false, windows = false;  // windows: --verify-windows, the candidates are windows
+    bool align_windows = false;  // --align-windows: the nearest window of every row is aligned after the run merge
 
     Search(const Args& args, const IndexImage& img, unsigned long long errors, double fraction, double started = now())
         : a(args), image(img), verbose(args.has("verbose")), with_counts(args.has("counts")), t_start(started) {
@@ -54,6 +55,8 @@ struct Search {
         align = a.has("align");
         if (align) verifier->set_align(true);
         all_targets = a.has("all-targets");
+        align_windows = a.has("align-windows");
+        if (align_windows) verifier->keep_windows(true);
     }
     void report_verifier() const {
         if (!verifier) return;
@@ -65,8 +68,10 @@ struct Search {
         std::cerr << "[tetrex search] verify routes: device " << n.device << ", device-long " << n.device_long << ", host " << n.host;
         if (windows) std::cerr << ", windows " << n.windows;
         std::cerr << std::endl;
-        if (!align) return;
         const BinVerifier::Aligned al = verifier->n_aligned();
+        if (align_windows)
+            std::cerr << "[tetrex search] align windows: device " << al.device << ", host " << al.host << ", calls " << verifier->n_align_windows_calls() << std::endl;
+        if (!align) return;
         std::cerr << "[tetrex search] align routes: device " << al.device << ", host " << al.host << std::endl;
     }
     // the verified columns behind a confirmed row: distance \t target \t end [\t strand] and, with --align,
@@ -76,6 +81,13 @@ struct Search {
         row.append("\t").append(std::to_string(h.distance)).append("\t").append(*h.target).append("\t").append(std::to_string(h.end));
         if (with_strand) row.append("\t").append(1, h.strand);
         if (!align) return;
+        row.append("\t").append(std::to_string((uint64_t)h.start + 1)).append("\t");
+        for (const uint32_t run : h.runs) row.append(std::to_string(run >> 2)).append(1, "=XID"[run & 3]);
+    }
+    // --align-windows behind those: \t wbegin \t wend \t start \t cigar — the aligned window, which is the run's
+    // nearest one, as 1-based inclusive positions on the record as given, then start and cigar as --align writes them
+    void append_window_alignment(std::string& row, const VerifiedHit& h, uint64_t wbegin, uint64_t wend) const {
+        row.append("\t").append(std::to_string(wbegin)).append("\t").append(std::to_string(wend));
         row.append("\t").append(std::to_string((uint64_t)h.start + 1)).append("\t");
         for (const uint32_t run : h.runs) row.append(std::to_string(run >> 2)).append(1, "=XID"[run & 3]);
     }
@@ -217,6 +229,26 @@ int search_windowed(const Args& a, const IndexImage& image, unsigned long long e
             for (const Hit& x : hits) candidates.push_back({x.query, x.bin});
             s.verifier->verify_windows(seqs, win_table, candidates, confirmed);
         }
+        // the confirmed windows among hits [h0, h1) — one record's — by bin, strand and window, and their runs
+        const auto merge = [&](size_t h0, size_t h1) {
+            kept.clear();
+            for (size_t i = h0; i < h1; ++i)
+                if (confirmed[i].distance != 0xFFFFFFFFu) kept.push_back({hits[i].query, hits[i].bin, hits[i].count, confirmed[i].distance, confirmed[i].strand, i});
+            std::stable_sort(kept.begin(), kept.end(), [](const Confirmed& x, const Confirmed& y) {
+                return x.bin != y.bin ? x.bin < y.bin : x.strand != y.strand ? x.strand == '+' : x.query < y.query;
+            });
+            return plan::confirmed_runs(kept);
+        };
+        if (s.align_windows) {  // a first pass over the records: the nearest window of every row, all aligned by one call
+            std::vector<BinVerifier::Selected> selection;
+            size_t h = 0;
+            for (const Rec& r : recs) {
+                const size_t h0 = h;
+                while (h < hits.size() && hits[h].query < r.w1) ++h;
+                for (const plan::WindowRun& run : merge(h0, h)) selection.push_back({kept[run.nearest].at, &confirmed[kept[run.nearest].at]});
+            }
+            s.verifier->align_windows(candidates, selection);
+        }
         size_t h = 0;
         for (const Rec& r : recs) {
             mine.clear();
@@ -226,19 +258,14 @@ int search_windowed(const Args& a, const IndexImage& image, unsigned long long e
                 for (size_t i = 0; i < mine.size(); ++i) n_hit += i == 0 || mine[i].query != mine[i - 1].query;
             }
             if (verify) {
-                kept.clear();
-                for (size_t i = 0; i < mine.size(); ++i)
-                    if (confirmed[h0 + i].distance != 0xFFFFFFFFu)
-                        kept.push_back({mine[i].query, mine[i].bin, mine[i].count, confirmed[h0 + i].distance, confirmed[h0 + i].strand, h0 + i});
-                std::stable_sort(kept.begin(), kept.end(), [](const Confirmed& x, const Confirmed& y) {
-                    return x.bin != y.bin ? x.bin < y.bin : x.strand != y.strand ? x.strand == '+' : x.query < y.query;
-                });
-                for (const plan::WindowRun& run : plan::confirmed_runs(kept)) {
-                    const Confirmed &first = kept[run.first], &last = kept[run.last], &best = kept[run.best];
+                for (const plan::WindowRun& run : merge(h0, h)) {
+                    const Confirmed &first = kept[run.first], &last = kept[run.last], &best = kept[run.best], &nearest = kept[run.nearest];
                     row.assign(r.name).append("\t").append(image.bin_paths[first.bin]).append("\t").append(std::to_string(letter_at[first.query] + 1));
                     row.append("\t").append(std::to_string(letter_at[last.query] + lens[last.query] + k - 1));
                     s.append_count(row, best.count, lens[best.query]);
-                    s.append_verified(row, confirmed[kept[run.nearest].at], dna);
+                    s.append_verified(row, confirmed[nearest.at], dna);
+                    if (s.align_windows)
+                        s.append_window_alignment(row, confirmed[nearest.at], letter_at[nearest.query] + 1, letter_at[nearest.query] + lens[nearest.query] + k - 1);
                     *s.out << row << '\n';
                     ++n_rows;
                 }
@@ -332,6 +359,27 @@ int search_translated_windowed(const Args& a, const IndexImage& image, unsigned 
     verified.edits = (uint32_t)std::min<uint64_t>(errors, 0xFFFFFFFEull);
     struct Confirmed { uint32_t query, bin, count, distance; char strand; size_t at; };  // at: its place in verified.confirmed
     std::vector<Confirmed> kept;
+    // the confirmed windows among hits [h0, h1) — one frame's — by bin and window, and their runs: what the rows are written
+    // from and, with --align-windows, what the nearest windows are selected from, batch by batch
+    const auto merge = [&](size_t h0, size_t h1) {
+        kept.clear();
+        for (size_t i = h0; i < h1; ++i)
+            if (verified.confirmed[i].distance != 0xFFFFFFFFu) kept.push_back({hits[i].query, hits[i].bin, hits[i].count, verified.confirmed[i].distance, '+', i});
+        std::stable_sort(kept.begin(), kept.end(), [](const Confirmed& x, const Confirmed& y) { return x.bin != y.bin ? x.bin < y.bin : x.query < y.query; });
+        return plan::confirmed_runs(kept);
+    };
+    if (s.align_windows)
+        verified.select = [&](size_t h0, size_t h1) {  // the hits of a device batch: whole records, so whole frames
+            std::vector<size_t> nearest;
+            for (size_t h = h0; h < h1;) {
+                const uint64_t frame_end = *std::upper_bound(win_offsets.begin(), win_offsets.end(), (uint64_t)hits[h].query);
+                size_t e = h;
+                while (e < h1 && hits[e].query < frame_end) ++e;
+                for (const plan::WindowRun& run : merge(h, e)) nearest.push_back(kept[run.nearest].at);
+                h = e;
+            }
+            return nearest;
+        };
     for_each_chunk(a.pos[1], [&](const Chunk& c) {
         s.dev.search_translated_windows(c.seq, c.rec_offsets, window, step, [&](uint64_t n) { return s.threshold.of(n); }, s.with_counts, win_offsets, lens,
                                         thresholds, hits, verify ? &verified : nullptr);
@@ -363,16 +411,16 @@ int search_translated_windowed(const Args& a, const IndexImage& image, unsigned 
                     row.append("\t").append(std::to_string(at.begin)).append("\t").append(std::to_string(at.end));
                 };
                 if (verify) {
-                    kept.clear();
-                    for (size_t i = 0; i < mine.size(); ++i)
-                        if (verified.confirmed[h0 + i].distance != 0xFFFFFFFFu)
-                            kept.push_back({mine[i].query, mine[i].bin, mine[i].count, verified.confirmed[h0 + i].distance, '+', h0 + i});
-                    std::stable_sort(kept.begin(), kept.end(), [](const Confirmed& x, const Confirmed& y) { return x.bin != y.bin ? x.bin < y.bin : x.query < y.query; });
-                    for (const plan::WindowRun& run : plan::confirmed_runs(kept)) {
-                        const Confirmed &first = kept[run.first], &last = kept[run.last], &best = kept[run.best];
+                    for (const plan::WindowRun& run : merge(h0, h)) {
+                        const Confirmed &first = kept[run.first], &last = kept[run.last], &best = kept[run.best], &nearest = kept[run.nearest];
                         begin_row(first.bin, first.query, last.query);
                         s.append_count(row, best.count, lens[best.query]);
-                        s.append_verified(row, verified.confirmed[kept[run.nearest].at], false);
+                        s.append_verified(row, verified.confirmed[nearest.at], false);
+                        if (s.align_windows) {
+                            const txq::fw::Window wn = txq::fw::window_at(layout, nearest.query - w0);
+                            const txq::fw::Span on = txq::fw::residues_on_record(L, f, wn.a, wn.a + wn.len);
+                            s.append_window_alignment(row, verified.confirmed[nearest.at], on.begin, on.end);
+                        }
                         *s.out << row << '\n';
                         ++n_rows;
                     }
@@ -481,7 +529,7 @@ int search_plain(const Args& a, const IndexImage& image, unsigned long long erro
 int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
                                        {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false},
-                                       {'\0', "verify-frames", false}, {'\0', "verify-windows", false}, {'\0', "verify-frame-windows", false}, {'\0', "align", false}, {'\0', "all-targets", false},
+                                       {'\0', "verify-frames", false}, {'\0', "verify-windows", false}, {'\0', "verify-frame-windows", false}, {'\0', "align", false}, {'\0', "align-windows", false}, {'\0', "all-targets", false},
                                        {'\0', "window", true}, {'\0', "step", true}, {'\0', "frame-window", true}, {'\0', "frame-step", true}};
     Args a;
     unsigned long long errors = 0, window = 0, step = 0, frame_window = 0, frame_step = 0;
@@ -489,6 +537,10 @@ int cmd_search(int argc, char** argv) {
     try {
         a = parse(argc, argv, 2, spec);
         if (a.pos.size() != 2) throw std::runtime_error("expected <index> <queries.fa>");
+        if (a.has("align-windows") && !a.has("verify-windows") && !a.has("verify-frame-windows"))
+            throw std::runtime_error("--align-windows gives start and cigar of confirmed window runs: it needs --window W -e E --verify-windows, or --translate --frame-window W -e E --verify-frame-windows");
+        // (--align is the whole-record flag; next to the window modes its refusal names the flag that is meant)
+        const auto hint = [](const char* o) { return std::string(o) == "align" ? " (the alignment of confirmed window runs is --align-windows)" : ""; };
         if (a.has("step") && !a.has("window")) throw std::runtime_error("--step is the distance between the windows of --window W: it needs --window");
         if (a.has("frame-step") && !a.has("frame-window"))
             throw std::runtime_error("--frame-step is the distance between the windows of --frame-window W: it needs --frame-window");
@@ -499,7 +551,7 @@ int cmd_search(int argc, char** argv) {
             for (const char* o : {"verify-windows", "verify-frames", "all-targets", "align", "verify"})
                 if (a.has(o))
                     throw std::runtime_error(std::string("--frame-window cannot be combined with --") + o +
-                                             ": frame windows are not verified by it (they are confirmed with --verify-frame-windows, which gives distance, target and end)");
+                                             ": frame windows are not verified by it (they are confirmed with --verify-frame-windows, which gives distance, target and end)" + hint(o));
             if (!a.has("errors") && !a.has("threshold")) throw std::runtime_error("--frame-window needs -e E or --threshold F");
             frame_window = parse_count(a.get("frame-window", ""), "--frame-window must be a number of residues >= k", 1, 0x7FFFFFFFull);
             frame_step = std::max<unsigned long long>(1, frame_window / 2);
@@ -509,7 +561,7 @@ int cmd_search(int argc, char** argv) {
         if (a.has("verify-frame-windows")) {
             if (!a.has("translate")) throw std::runtime_error("--verify-frame-windows confirms the windows of --translate --frame-window W: it needs --translate");
             for (const char* o : {"window", "step", "verify-windows", "verify-frames", "all-targets", "align", "verify"})
-                if (a.has(o)) throw std::runtime_error(std::string("--verify-frame-windows cannot be combined with --") + o + ": it confirms the windows of --frame-window, with distance, target and end, nothing more in this version");
+                if (a.has(o)) throw std::runtime_error(std::string("--verify-frame-windows cannot be combined with --") + o + ": it confirms the windows of --frame-window, with distance, target and end" + hint(o));
             if (!a.has("frame-window")) throw std::runtime_error("--verify-frame-windows confirms the windows of --frame-window W: it needs --frame-window");
             if (a.has("threshold")) throw std::runtime_error("--verify-frame-windows confirms the windows of -e E: it cannot be combined with --threshold");
             if (!a.has("errors")) throw std::runtime_error("--verify-frame-windows needs -e E: the number of residue edits a confirmed window may be away");
@@ -520,13 +572,13 @@ int cmd_search(int argc, char** argv) {
             if (a.has("threshold")) throw std::runtime_error("--verify-windows confirms the windows of -e E: it cannot be combined with --threshold");
             if (!a.has("errors")) throw std::runtime_error("--verify-windows needs -e E: the number of edits a confirmed window may be away");
             for (const char* o : {"verify-frames", "all-targets", "align", "verify"})
-                if (a.has(o)) throw std::runtime_error(std::string("--verify-windows cannot be combined with --") + o + ": a confirmed window gets its distance, target and end, nothing more in this version");
+                if (a.has(o)) throw std::runtime_error(std::string("--verify-windows cannot be combined with --") + o + ": a confirmed window gets its distance, target and end" + hint(o));
         }
         if (a.has("window")) {
             if (a.has("translate")) throw std::runtime_error("--window cannot be combined with --translate: translated frames lose their positions where stops are taken out (translated records: --frame-window)");
             if (a.has("verify-frames")) throw std::runtime_error("--window cannot be combined with --verify-frames: it confirms translated frames, which --window does not search");
             for (const char* o : {"all-targets", "align", "verify"})
-                if (a.has(o)) throw std::runtime_error(std::string("--window cannot be combined with --") + o + ": windows are confirmed with --verify-windows");
+                if (a.has(o)) throw std::runtime_error(std::string("--window cannot be combined with --") + o + ": windows are confirmed with --verify-windows" + hint(o));
             if (!a.has("errors") && !a.has("threshold")) throw std::runtime_error("--window needs -e E or --threshold F");
             window = parse_count(a.get("window", ""), "--window must be a number of letters >= k", 1, 0x7FFFFFFFull);
             step = std::max<unsigned long long>(1, window / 2);

@@ -355,6 +355,14 @@ void DeviceIndex::search_translated_windows(std::string_view seq, const std::vec
                                                                       (const uint32_t*)d_llen.p, (size_t)nw},
                                            candidates, lengths, window_letters, batch_confirmed);
         std::move(batch_confirmed.begin(), batch_confirmed.end(), verified->confirmed.begin() + (long)h0);
+        if (verified->select) {  // --align-windows: the selected hits, while the batch's frames are still on the device
+            std::vector<BinVerifier::Selected> selection;
+            for (const size_t h : verified->select(h0, hits.size())) {
+                if (h < h0 || h >= hits.size()) throw std::runtime_error("search_translated_windows: a selected hit is not of the batch");
+                selection.push_back({h - h0, &verified->confirmed[h]});
+            }
+            verified->verifier->align_windows(candidates, selection);
+        }
     }
 }
 

@@ -17,6 +17,12 @@
 //   * the walk back reads one row per step (all lanes the same address: a broadcast) and is the same in every lane; the run
 //     that closes as number q stays in lane q, and at the end lane q stores it to its place, the last-closed run first.
 // Nothing is allocated, nothing read back, and the workspace argument is not touched: the direction bits never leave the CU.
+//
+// txq_edit_align_windows / _device (`tetrex search --verify-windows --align-windows`) is the same kernel behind
+// another admit(): the pattern is a window into one letter buffer, the text a view of a table — one per resident bin —, so one
+// launch aligns pairs of any number of bins.  Windows of up to 512 letters run: the 8 KiB instance only.
+#include <cstddef>
+
 #include "txq_edit_align_plan.hpp"
 #include "txq_edit_common.hpp"
 
@@ -57,8 +63,57 @@ __device__ __forceinline__ uint32_t band_prefix_min(uint32_t x, uint32_t d) {
     return x;
 }
 
-template <uint32_t kRows>
-__global__ __launch_bounds__(64) void edit_align_kernel(AlArgs a) {
+// The kernel's one seam: how a pair finds its pattern bytes, its record and the bounds its triple is checked against.
+// admit() answers what the triple asks for and, for a pair that runs, m, the pattern's m bytes and the record's first byte.
+struct AlignPair {
+    AlignKind kind;
+    uint32_t m;
+    const uint8_t* ptext;  // the pattern: m bytes
+    const uint8_t* rtext;  // the record: bytes [0, j) of it are read
+};
+
+// a pattern of an offset table against a group of the text (txq_edit_align_device)
+__device__ __forceinline__ AlignPair admit(const AlArgs& a, uint64_t pair, uint32_t d, uint32_t r, uint32_t j) {
+    const PairView v = view_pair<0xFFFFFFFFu>(a.e, pair);
+    const AlignKind kind = !v.ok ? AlignKind::Refused : align_kind(d, r, j, v.m, a.max_errors, a.e.t.rec, v.r0, v.r1, v.gs, v.ge);
+    if (kind != AlignKind::Run) return {kind, 0, nullptr, nullptr};
+    return {kind, v.m, a.e.pat + v.p0, a.e.t.text + a.e.t.rec[r]};
+}
+__device__ __forceinline__ const uint8_t* class_table(const AlArgs& a) { return a.e.codes; }
+
+// a window of one letter buffer against a view of a table (txq_edit_align_windows_device): views[g] is read once, uniformly
+struct AwArgs {
+    const uint8_t* letters;
+    uint64_t letters_bytes;
+    const uint64_t* win_begin;
+    const uint32_t* win_len;
+    uint64_t n_win;
+    const AlignTextView* views;
+    uint64_t n_views;
+    const uint32_t* pairs;
+    const uint8_t* codes;
+    const uint32_t* res;  // one triple per pair, as a search call answered it for the window against the view
+    uint32_t* align;
+    uint32_t max_errors;
+};
+static_assert(sizeof(AlignTextView) == sizeof(txq_text_view) && offsetof(AlignTextView, text) == offsetof(txq_text_view, d_text) &&
+                  offsetof(AlignTextView, rec) == offsetof(txq_text_view, d_rec_offsets) && offsetof(AlignTextView, n_rec) == offsetof(txq_text_view, n_records) &&
+                  offsetof(AlignTextView, text_bytes) == offsetof(txq_text_view, text_bytes),
+              "include/txq.h and the plan header agree on a view");
+
+__device__ __forceinline__ AlignPair admit(const AwArgs& a, uint64_t pair, uint32_t d, uint32_t r, uint32_t j) {
+    const uint32_t p = a.pairs[3 * pair], g = a.pairs[3 * pair + 1];
+    if (!align_window_ok(p, g, a.n_win, a.n_views, a.win_begin, a.win_len, a.letters_bytes)) return {AlignKind::Refused, 0, nullptr, nullptr};
+    const AlignTextView v = a.views[g];
+    const uint32_t m = a.win_len[p];
+    const AlignKind kind = align_window_kind(d, r, j, m, a.max_errors, v);
+    if (kind != AlignKind::Run) return {kind, 0, nullptr, nullptr};
+    return {kind, m, a.letters + a.win_begin[p], v.text + v.rec[r]};
+}
+__device__ __forceinline__ const uint8_t* class_table(const AwArgs& a) { return a.codes; }
+
+template <uint32_t kRows, class Args>
+__global__ __launch_bounds__(64) void edit_align_kernel(Args a) {
     __shared__ uint64_t dir[2 * kRows];  // row i: dir[2 (i - 1)] the low bits of its operations, dir[2 (i - 1) + 1] the high bits
     constexpr bool kFirst = kRows == kSmallRows;
     const uint32_t lane = threadIdx.x;
@@ -66,8 +121,8 @@ __global__ __launch_bounds__(64) void edit_align_kernel(AlArgs a) {
     const uint32_t run_words = 2 * a.max_errors + 1;
     uint32_t* const out = a.align + pair * (uint64_t)(run_words + 2);
     const uint32_t d = a.res[3 * pair], r = a.res[3 * pair + 1], j = a.res[3 * pair + 2];
-    const PairView v = view_pair<0xFFFFFFFFu>(a.e, pair);
-    const AlignKind kind = !v.ok ? AlignKind::Refused : align_kind(d, r, j, v.m, a.max_errors, a.e.t.rec, v.r0, v.r1, v.gs, v.ge);
+    const AlignPair v = admit(a, pair, d, r, j);
+    const AlignKind kind = v.kind;
     if (kind != AlignKind::Run) {
         if (!kFirst) return;
         if (kind == AlignKind::Declined) {
@@ -82,16 +137,17 @@ __global__ __launch_bounds__(64) void edit_align_kernel(AlArgs a) {
     if ((m <= kSmallRows) != kFirst) return;  // (uniform over the wave)
 
     const AlignBand b{m, d, j};
-    const uint8_t* const rtext = a.e.t.text + a.e.t.rec[r];  // the record: bytes [0, j) of it are read
-    const uint8_t* const ptext = a.e.pat + v.p0;
+    const uint8_t* const rtext = v.rtext;
+    const uint8_t* const ptext = v.ptext;
+    const uint8_t* const codes = class_table(a);
     const uint32_t k = lane;
     uint32_t prev = align_row0(b, k);
     for (uint32_t i0 = 0; i0 < m; i0 += 64) {
         uint32_t pc = 31, ta = 31, tb = 31;
-        if (i0 + lane < m) pc = a.e.codes[ptext[i0 + lane]];
+        if (i0 + lane < m) pc = codes[ptext[i0 + lane]];
         const int64_t xa = align_text_index(b, i0, lane), xb = xa + 64;
-        if (xa >= 0 && xa < (int64_t)j) ta = a.e.codes[rtext[xa]];
-        if (xb >= 0 && xb < (int64_t)j) tb = a.e.codes[rtext[xb]];
+        if (xa >= 0 && xa < (int64_t)j) ta = codes[rtext[xa]];
+        if (xb >= 0 && xb < (int64_t)j) tb = codes[rtext[xb]];
         const uint32_t rows = m - i0 < 64 ? m - i0 : 64;
         for (uint32_t ii = 0; ii < rows; ++ii) {
             const uint32_t i = i0 + ii + 1;
@@ -164,8 +220,8 @@ int txq_edit_align_device(const uint8_t* d_patterns, const uint64_t* d_pat_offse
     const AlArgs a{{d_patterns, d_pat_offsets, n_patterns, pattern_bytes, {d_text, d_rec_offsets, n_records, text_bytes, d_group_offsets, n_groups},
                     d_pairs, n_pairs, d_codes, nullptr, nullptr, nullptr, 0},
                    d_out, d_align, max_errors};
-    edit_align_kernel<kSmallRows><<<(unsigned)n_pairs, 64, 0, st>>>(a);
-    edit_align_kernel<kLargeRows><<<(unsigned)n_pairs, 64, 0, st>>>(a);
+    edit_align_kernel<kSmallRows, AlArgs><<<(unsigned)n_pairs, 64, 0, st>>>(a);
+    edit_align_kernel<kLargeRows, AlArgs><<<(unsigned)n_pairs, 64, 0, st>>>(a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "edit align kernel launch");
     return TXQ_OK;
@@ -213,6 +269,84 @@ int txq_edit_align(const uint8_t* patterns, const uint64_t* pat_offsets, size_t 
                                    max_errors, d.at<uint32_t>(s_align), nullptr, nullptr);
     if (rc == TXQ_OK) d.download(align, s_align, n_pairs * stride * 4);  // (waits for the kernels)
     if (d.error() != hipSuccess) return fail_hip(d.error(), "txq_edit_align copies");
+    return rc;
+}
+
+int txq_edit_align_windows_device(const uint8_t* d_letters, size_t letters_bytes, const uint64_t* d_win_begin, const uint32_t* d_win_len, size_t n_windows,
+                                  const txq_text_view* d_views, size_t n_views, const uint32_t* d_pairs, size_t n_pairs, const uint32_t* d_results,
+                                  const uint8_t* d_codes, uint32_t max_errors, uint32_t* d_align, void* d_workspace, void* stream) {
+    (void)d_workspace;  // TXQ_EDIT_ALIGN_WINDOWS_WORKSPACE is 0: the direction bits live in LDS
+    if (max_errors > kMaxErrors) return fail(TXQ_ERR_ARG, "max_errors is at most %u", kMaxErrors);
+    if (n_pairs > 0x7FFFFFFFull) return fail(TXQ_ERR_ARG, "at most 2^31 - 1 pairs per call");
+    if (!d_codes || (n_pairs && (!d_pairs || !d_results || !d_align)) || (n_windows && (!d_win_begin || !d_win_len)) || (n_views && !d_views) ||
+        (letters_bytes && !d_letters))
+        return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = require_init()) return rc;
+    if (n_pairs == 0) return TXQ_OK;
+    const AwArgs a{d_letters, letters_bytes, d_win_begin, d_win_len, n_windows, reinterpret_cast<const AlignTextView*>(d_views), n_views, d_pairs, d_codes,
+                   d_results, d_align, max_errors};
+    edit_align_kernel<kSmallRows, AwArgs><<<(unsigned)n_pairs, 64, 0, (hipStream_t)stream>>>(a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "edit align windows kernel launch");
+    return TXQ_OK;
+}
+
+int txq_edit_align_windows(const uint8_t* letters, size_t letters_bytes, const uint64_t* win_begin, const uint32_t* win_len, size_t n_windows,
+                           const txq_text_view* views, size_t n_views, const uint32_t* pairs, size_t n_pairs, const uint32_t* results, const uint8_t* codes,
+                           uint32_t max_errors, uint32_t* align) {
+    if (max_errors > kMaxErrors) return fail(TXQ_ERR_ARG, "max_errors is at most %u", kMaxErrors);
+    if (n_pairs > 0x7FFFFFFFull) return fail(TXQ_ERR_ARG, "at most 2^31 - 1 pairs per call");
+    if (!codes || (n_pairs && (!pairs || !results || !align)) || (n_windows && (!win_begin || !win_len)) || (n_views && !views) || (letters_bytes && !letters))
+        return fail(TXQ_ERR_ARG, "null argument");
+    // every text at a 16-byte boundary of one slice, every view's offsets behind those of the view before
+    std::vector<uint64_t> text_at(n_views), rec_at(n_views);
+    uint64_t texts_bytes = 0, n_offsets = 0;
+    for (size_t g = 0; g < n_views; ++g) {
+        const txq_text_view& v = views[g];
+        if (!v.d_rec_offsets || (v.text_bytes && !v.d_text)) return fail(TXQ_ERR_ARG, "null argument");
+        if (v.n_records >= 0xFFFFFFFEull) return fail(TXQ_ERR_ARG, "at most 2^32 - 2 records per view");
+        if (int rc = check_ascending(v.d_rec_offsets, v.n_records, "record", "text", v.text_bytes)) return rc;
+        text_at[g] = texts_bytes, rec_at[g] = n_offsets;
+        texts_bytes += (v.text_bytes + 15) & ~(uint64_t)15;
+        n_offsets += v.n_records + 1;
+    }
+    for (size_t i = 0; i < n_pairs; ++i) {
+        const uint32_t p = pairs[3 * i], g = pairs[3 * i + 1];
+        if (p >= n_windows || g >= n_views) return fail(TXQ_ERR_ARG, "pair %zu names window %u of %zu, view %u of %zu", i, p, n_windows, g, n_views);
+        const uint64_t m = win_len[p], b = win_begin[p];
+        if (m < 1) return fail(TXQ_ERR_ARG, "pair %zu: an empty window", i);
+        if (b > letters_bytes || m > letters_bytes - b) return fail(TXQ_ERR_ARG, "pair %zu: window %u leaves the %zu letters", i, p, letters_bytes);
+    }
+    if (int rc = require_init()) return rc;
+    if (n_pairs == 0) return TXQ_OK;
+    const size_t stride = TXQ_EDIT_ALIGN_STRIDE(max_errors);
+    DeviceStage d;
+    const size_t s_let = d.add(letters_bytes + 16), s_wb = d.add(n_windows * 8 + 8), s_wl = d.add(n_windows * 4 + 4), s_text = d.add(texts_bytes + 16),
+                 s_rec = d.add(n_offsets * 8 + 8), s_views = d.add(n_views * sizeof(txq_text_view) + 8), s_pairs = d.add(n_pairs * 12), s_codes = d.add(256),
+                 s_res = d.add(n_pairs * 12), s_align = d.add(n_pairs * stride * 4);
+    if (const hipError_t e = d.alloc(); e != hipSuccess) return fail_hip(e, "hipMalloc");
+    std::vector<txq_text_view> table(n_views);
+    for (size_t g = 0; g < n_views; ++g) {
+        const txq_text_view& v = views[g];
+        d.upload(s_text + text_at[g], v.d_text, v.text_bytes);
+        d.upload(s_rec + 8 * rec_at[g], v.d_rec_offsets, (v.n_records + 1) * 8);
+        table[g] = {d.at<uint8_t>(s_text) + text_at[g], d.at<uint64_t>(s_rec) + rec_at[g], v.n_records, v.text_bytes};
+    }
+    d.upload(s_let, letters, letters_bytes);
+    d.upload(s_wb, win_begin, n_windows * 8);
+    d.upload(s_wl, win_len, n_windows * 4);
+    d.upload(s_views, table.data(), n_views * sizeof(txq_text_view));
+    d.upload(s_pairs, pairs, n_pairs * 12);
+    d.upload(s_codes, codes, 256);
+    d.upload(s_res, results, n_pairs * 12);
+    d.upload(s_align, align, n_pairs * stride * 4);  // (a declined pair keeps what the caller had behind its marker)
+    int rc = TXQ_OK;
+    if (d.error() == hipSuccess)
+        rc = txq_edit_align_windows_device(d.at<uint8_t>(s_let), letters_bytes, d.at<uint64_t>(s_wb), d.at<uint32_t>(s_wl), n_windows,
+                                           d.at<txq_text_view>(s_views), n_views, d.at<uint32_t>(s_pairs), n_pairs, d.at<uint32_t>(s_res), d.at<uint8_t>(s_codes),
+                                           max_errors, d.at<uint32_t>(s_align), nullptr, nullptr);
+    if (rc == TXQ_OK) d.download(align, s_align, n_pairs * stride * 4);  // (waits for the kernel)
+    if (d.error() != hipSuccess) return fail_hip(d.error(), "txq_edit_align_windows copies");
     return rc;
 }
 

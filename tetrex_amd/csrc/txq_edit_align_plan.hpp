@@ -38,6 +38,32 @@ TXQ_TEXT_FN AlignKind align_kind(uint32_t d, uint32_t r, uint32_t j, uint64_t m,
     return AlignKind::Run;
 }
 
+// ---- the same for a window against a view (txq_edit_align_windows_device) -------------------------------------
+// The pattern is a window into one letter buffer, the text one entry of a table of views: the records of one bin, all of them
+// the pair's ONE group.  The layout is txq_text_view's of include/txq.h.
+struct AlignTextView {
+    const uint8_t* text;
+    const uint64_t* rec;  // n_rec + 1 offsets into text
+    uint64_t n_rec, text_bytes;
+};
+constexpr uint32_t kAlignMaxWindow = 512;  // rows of the one instance that aligns windows (TXQ_EDIT_MAX_PATTERN)
+// Is pair (window p, view g) one the call answers?  No: its window index or view index is out of range, the window has no
+// letters or leaves the letter buffer (win_begin / win_len are read only for p < n_windows).
+TXQ_TEXT_FN bool align_window_ok(uint32_t p, uint32_t g, uint64_t n_windows, uint64_t n_views, const uint64_t* win_begin, const uint32_t* win_len,
+                                 uint64_t letters_bytes) {
+    if (p >= n_windows || g >= n_views) return false;
+    const uint64_t p0 = win_begin[p], m = win_len[p];
+    return m != 0 && p0 <= letters_bytes && m <= letters_bytes - p0;
+}
+// (d, r, j) for a window of m >= 1 letters against view v, whose table entry is the caller's word and whose offsets are device
+// data: r indexes the view's offsets.  Run: m <= kAlignMaxWindow and what align_kind asks with the view as the group — records
+// [0, n_rec) in bytes [0, text_bytes) —, so rec[r] and rec[r + 1] are among the view's n_rec + 1 offsets and every byte read lies
+// in [text, text + text_bytes).
+TXQ_TEXT_FN AlignKind align_window_kind(uint32_t d, uint32_t r, uint32_t j, uint64_t m, uint32_t max_errors, const AlignTextView& v) {
+    if (d != kAlignNone && m > kAlignMaxWindow) return AlignKind::Declined;
+    return align_kind(d, r, j, m, max_errors, v.rec, 0, v.n_rec, 0, v.text_bytes);
+}
+
 // ---- the band ------------------------------------------------------------------------------------------------------------
 struct AlignBand {
     uint32_t m, d, j;
