@@ -9,7 +9,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-functi
 ifdef EXPERIMENTS
 HIPFLAGS += -DTXQ_EXPERIMENTS $(EXPERIMENT_FLAGS)
 endif
-HIP_SRCS := $(CSRC)/txq_api.hip $(CSRC)/txq_probe.hip $(CSRC)/txq_hibf.hip $(CSRC)/txq_exec.hip $(CSRC)/txq_build.hip $(CSRC)/txq_count.hip $(CSRC)/txq_translate.hip $(CSRC)/txq_frame_letters.hip $(CSRC)/txq_edit.hip $(CSRC)/txq_edit_long.hip $(CSRC)/txq_edit_align.hip $(CSRC)/txq_edit_targets.hip $(CSRC)/txq_edit_windows.hip $(CSRC)/txq_regex.hip
+HIP_SRCS := $(CSRC)/txq_api.hip $(CSRC)/txq_probe.hip $(CSRC)/txq_hibf.hip $(CSRC)/txq_exec.hip $(CSRC)/txq_build.hip $(CSRC)/txq_count.hip $(CSRC)/txq_translate.hip $(CSRC)/txq_frame_letters.hip $(CSRC)/txq_edit.hip $(CSRC)/txq_edit_long.hip $(CSRC)/txq_edit_align.hip $(CSRC)/txq_edit_targets.hip $(CSRC)/txq_edit_windows.hip $(CSRC)/txq_edit_window_targets.hip $(CSRC)/txq_regex.hip
 HIP_OBJS := $(HIP_SRCS:.hip=.o)
 HIP_HDRS := $(wildcard $(CSRC)/*.hpp) include/txq.h include/txq_program.h include/txq_regex.h
 

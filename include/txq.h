@@ -23,6 +23,7 @@
  *   txq_edit_align / _device  (no counterpart: start and CIGAR of the pairs a search call confirmed, `--verify --align`)
  *   txq_edit_windows / _device  (no counterpart: txq_edit_search for windows into one letter buffer, `--window --verify-windows`)
  *   txq_edit_align_windows / _device  (no counterpart: txq_edit_align for windows against a table of text views, `--align-windows`)
+ *   txq_edit_window_targets / _device  (no counterpart: txq_edit_targets for windows against a table of text views, `--window-targets`)
  *   txq_frame_window_letters / _device  (no counterpart: the letters, stops and thresholds of translated windows, `--verify-frame-windows`)
  *
  * Conventions: plain C, no exceptions cross the boundary.  Every function returns 0 on success or a
@@ -537,6 +538,42 @@ int txq_edit_align_windows_device(const uint8_t* d_letters, size_t letters_bytes
 int txq_edit_align_windows(const uint8_t* letters, size_t letters_bytes, const uint64_t* win_begin, const uint32_t* win_len, size_t n_windows,
                            const txq_text_view* views, size_t n_views, const uint32_t* pairs, size_t n_pairs, const uint32_t* results,
                            const uint8_t* codes, uint32_t max_errors, uint32_t* align);  /* host views, synchronous */
+
+/* Every record of a view that a WINDOW matches within its cap, for pairs of any number of bins in ONE call (`tetrex search
+ * --window --verify-windows --window-targets` and its frame-window sibling; not in the reference).  Windows are
+ * taken as txq_edit_windows_device takes them: window p is d_letters[d_win_begin[p] .. d_win_begin[p] + d_win_len[p]), in any
+ * order, overlapping, repeated.  Texts are taken as txq_edit_align_windows_device takes them: view g is d_views[g], the records of
+ * one bin wherever the caller keeps them; pair i is d_pairs[3 i ..] = (window, view, cap e), the view being ONE group of all its
+ * records.  The answers are those of txq_edit_targets_device above, word for word: the hit list (pair, d, r, j) by pair, then by
+ * record — r an index into the view's offsets —, d_total, d_status, and slots in pair order — a pair needs one per record of
+ * its view — with the same rule: a pair whose slots would end beyond n_slots is refused, and so is every pair behind it.
+ * THE RESULT IS DEFINED AS what txq_edit_targets answers with the window written out as the pattern and the view's records as
+ * the one group of a text of its own.
+ * Windows of 1 .. TXQ_EDIT_MAX_PATTERN letters run here.  A pair is refused (status 0xFFFFFFFE, no hit) when its window index is
+ * >= n_windows, its view index >= n_views, its window empty, longer than that or leaving letters_bytes, or when the view's
+ * offsets leave text_bytes or its ends do not ascend (d_rec_offsets[0] <= d_rec_offsets[n_records] <= text_bytes is what is
+ * checked; offsets in between that do not ascend give hits that mean nothing, and no access outside a buffer).  A view of no
+ * records is answered: no slots, no hits.
+ * The promises of the sibling _device calls hold word for word: nothing allocated, nothing read back, nothing waited for, no
+ * atomic append — the order of the rows does not depend on scheduling.  The view table's CONTENTS (pointers and sizes) are the
+ * caller's word, like any pointer argument; everything read THROUGH them is device data: no load or store leaves [d_text,
+ * d_text + text_bytes), the view's n_records + 1 offsets, letters_bytes, the slots or the hit list, whatever arrays and pairs
+ * say.  TXQ_ERR_ARG only for what the call can see: null pointers, a workspace that is not 8-byte aligned, more than 2^31 - 1
+ * pairs, 2^38 slots or rows and more.  d_workspace: TXQ_EDIT_WINDOW_TARGETS_WORKSPACE(n_pairs, n_slots) bytes of device
+ * memory, 8-byte aligned.  Every pair walks its view's text alone (no bundles as in txq_edit_windows_device).
+ * txq_edit_window_targets is the synchronous twin: `views` is a host array of views that hold HOST pointers.  It checks its
+ * buffers first (TXQ_ERR_ARG, nothing launched: every pair's window and view in range, windows of 1 .. TXQ_EDIT_MAX_PATTERN
+ * letters inside letters_bytes, every view's offsets ascending within text_bytes), stages all texts into one allocation, builds
+ * the device table and copies back the total, the status words and the rows written.
+ *   TXQ_EDIT_CHUNK=<bytes>   cuts the text as for txq_edit_search above; the results do not depend on it. */
+#define TXQ_EDIT_WINDOW_TARGETS_WORKSPACE(n_pairs, n_slots) (8 * (2 * (size_t)(n_pairs) + (size_t)(n_slots) + (size_t)(n_slots) / 256 + 4))
+int txq_edit_window_targets_device(const uint8_t* d_letters, size_t letters_bytes, const uint64_t* d_win_begin, const uint32_t* d_win_len, size_t n_windows,
+                                   const txq_text_view* d_views, size_t n_views, const uint32_t* d_pairs, size_t n_pairs, const uint8_t* d_codes,
+                                   uint32_t* d_hits, size_t capacity, uint64_t* d_total, uint32_t* d_status, size_t n_slots, void* d_workspace,
+                                   void* stream);
+int txq_edit_window_targets(const uint8_t* letters, size_t letters_bytes, const uint64_t* win_begin, const uint32_t* win_len, size_t n_windows,
+                            const txq_text_view* views, size_t n_views, const uint32_t* pairs, size_t n_pairs, const uint8_t* codes, uint32_t* hits,
+                            size_t capacity, uint64_t* total, uint32_t* status, size_t n_slots);  /* host views, synchronous */
 
 /* Which records of a bin does a regular expression match?  (`tetrex query --gpu-verify`; not in the reference.)
  * An automaton is a blob of include/txq_regex.h, where its layout and the meaning of "matches" are stated (as code: the

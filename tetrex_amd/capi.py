@@ -30,6 +30,7 @@ SYMBOLS = [
     "txq_edit_search_long", "txq_edit_search_long_device", "txq_edit_align", "txq_edit_align_device",
     "txq_edit_targets", "txq_edit_targets_device", "txq_edit_targets_long", "txq_edit_targets_long_device",
     "txq_edit_windows", "txq_edit_windows_device", "txq_edit_align_windows", "txq_edit_align_windows_device",
+    "txq_edit_window_targets", "txq_edit_window_targets_device",
     "txq_regex_filter", "txq_regex_filter_device",
     "txq_sketch_device", "txq_union_estimates_device", "txq_pair_unions_device", "txq_tree_insert_device",
     "txq_run_programs", "txq_run_programs_device", "txq_session_begin", "txq_session_set_aux_index", "txq_session_stage", "txq_session_end",
@@ -136,6 +137,10 @@ def lib():
         L.txq_edit_targets.argtypes = [C.c_void_p, u64p, C.c_size_t, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_void_p, C.c_size_t, u64p, C.c_void_p, C.c_size_t]
         L.txq_edit_targets_long_device.argtypes = L.txq_edit_targets_device.argtypes
+        L.txq_edit_window_targets_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.txq_edit_window_targets.argtypes = [C.c_void_p, C.c_size_t, u64p, u32p, C.c_size_t, C.POINTER(TextView), C.c_size_t, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_size_t, u64p, C.c_void_p, C.c_size_t]
         L.txq_edit_targets_long.argtypes = L.txq_edit_targets.argtypes
         L.txq_regex_filter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
@@ -1056,6 +1061,98 @@ def edit_align_windows_device(letters, win_begin, win_len, texts, pairs, results
         return d_align.to_numpy(np.uint8, (guard + body + guard,))
     finally:
         for b in bufs + d_texts + d_recs + [d_align]:
+            b.free()
+
+
+def edit_window_targets_workspace(n_pairs, n_slots):
+    """TXQ_EDIT_WINDOW_TARGETS_WORKSPACE: the device workspace txq_edit_window_targets_device needs for n_pairs pairs and n_slots slots"""
+    return 8 * (2 * int(n_pairs) + int(n_slots) + int(n_slots) // 256 + 4)
+
+
+def edit_window_targets_arrays(letters, win_begin, win_len, texts, pairs, codes):
+    """the arguments of edit_window_targets as contiguous arrays: (letters, window begins uint64, window lengths uint32, a list of
+    (text bytes, record offsets) per view, pairs (n, 3) uint32, codes)"""
+    let = np.ascontiguousarray(np.frombuffer(letters.encode() if isinstance(letters, str) else bytes(letters), dtype=np.uint8)
+                               if not isinstance(letters, np.ndarray) else letters, dtype=np.uint8)
+    wb, wl = np.ascontiguousarray(win_begin, dtype=np.uint64), np.ascontiguousarray(win_len, dtype=np.uint32)
+    views = []
+    for t in texts:
+        txt, ro = t if isinstance(t, tuple) else _records(t)
+        views.append((np.ascontiguousarray(txt, dtype=np.uint8), np.ascontiguousarray(ro, dtype=np.uint64)))
+    pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 3)
+    cd = np.ascontiguousarray(codes, dtype=np.uint8)
+    if cd.size != 256 or wb.size != wl.size or any(ro.size < 1 for _, ro in views):
+        raise TxqError(-1, "edit_window_targets: windows, views and class table disagree")
+    return let, wb, wl, views, pr, cd
+
+
+def edit_window_targets_slots(texts, pairs):
+    """the slots a call needs: the sum over the pairs of the records of their views (pairs that name no view count nothing)"""
+    n_rec = np.array([(t[1].size if isinstance(t, tuple) else len(t) + 1) - 1 for t in texts] + [0], dtype=np.int64)
+    g = np.asarray(pairs, dtype=np.int64).reshape(-1, 3)[:, 1]
+    return int(n_rec[np.where((g >= 0) & (g < len(texts)), g, len(texts))].sum())
+
+
+def edit_window_targets(letters, win_begin, win_len, texts, pairs, codes, capacity=None, n_slots=None):
+    """edit_targets for patterns that are windows into one letter buffer and texts behind a table of views
+    (txq_edit_window_targets, include/txq.h): window p is letters[win_begin[p] : win_begin[p] + win_len[p]], texts is a list of
+    record lists (or of (uint8 array, uint64 offsets)), one per view, pairs are rows of (window, view, cap), a view being one
+    group of all its records.  Returns what edit_targets returns: (hits (n, 4) uint32 of (pair, distance, record, end), total,
+    status)."""
+    let, wb, wl, views, pr, cd = edit_window_targets_arrays(letters, win_begin, win_len, texts, pairs, codes)
+    n_slots = edit_window_targets_slots(views, pr) if n_slots is None else int(n_slots)
+    table = (TextView * max(len(views), 1))()
+    for g, (txt, ro) in enumerate(views):
+        table[g] = TextView(txt.ctypes.data, ro.ctypes.data, ro.size - 1, txt.size)
+    room = 1024 if capacity is None else int(capacity)
+    while True:
+        hits, total, status = np.zeros((room, 4), dtype=np.uint32), np.zeros(1, dtype=np.uint64), np.zeros(pr.shape[0], dtype=np.uint32)
+        check(lib().txq_edit_window_targets(let.ctypes.data, let.size, wb.ctypes.data_as(u64p), wl.ctypes.data_as(u32p), wb.size, table, len(views),
+                                            pr.ctypes.data, pr.shape[0], cd.ctypes.data, hits.ctypes.data, room, total.ctypes.data_as(u64p),
+                                            status.ctypes.data, n_slots))
+        if capacity is not None or int(total[0]) <= room:
+            return hits[:min(int(total[0]), room)].copy(), int(total[0]), status
+        room = int(total[0])
+
+
+def edit_window_targets_device(letters, win_begin, win_len, texts, pairs, codes, capacity, n_slots=None, letters_at=0, text_at=0, exact_end=(), guard=64,
+                               fill=0xA5, stream=None):
+    """txq_edit_window_targets_device on buffers the caller places: the letters begin letters_at bytes behind a 16-byte boundary,
+    every view's text text_at bytes behind one in an allocation of its own — the views listed in exact_end in an allocation that
+    ends with the text's last byte —, the arrays go to the device as they are (the call cannot read them: what they name wrongly
+    is the kernels' to refuse), the rows lie between `guard` bytes of `fill` on either side and the workspace is filled with `fill`.
+    texts may hold (text bytes, record offsets, text_bytes) to give a view a size of its own.  stream: a hipStream_t as an
+    integer; None: the default stream.  Returns (buffer uint8[guard + 16 capacity + guard], total, status uint32[n]): the rows begin
+    at buffer[guard], and what the call did not write still holds `fill`."""
+    sizes = [int(t[2]) if isinstance(t, tuple) and len(t) == 3 else None for t in texts]
+    let, wb, wl, views, pr, cd = edit_window_targets_arrays(letters, win_begin, win_len, [t[:2] if isinstance(t, tuple) else t for t in texts], pairs, codes)
+    n, capacity = pr.shape[0], int(capacity)
+    n_slots = edit_window_targets_slots(views, pr) if n_slots is None else int(n_slots)
+
+    def around(a, at, exact):
+        b = np.full(at + a.size + (0 if exact else 33), ord("A"), dtype=np.uint8)
+        b[at:at + a.size] = a
+        return b if b.size else np.zeros(1, dtype=np.uint8)
+
+    pad = lambda a: np.concatenate([a.view(np.uint8).ravel(), np.zeros(16, dtype=np.uint8)])  # (no buffer of no bytes)
+    d_texts = [DeviceBuffer.from_numpy(around(txt, text_at, g in exact_end)) for g, (txt, _) in enumerate(views)]
+    d_recs = [DeviceBuffer.from_numpy(pad(ro)) for _, ro in views]
+    table = np.zeros((max(len(views), 1), 4), dtype=np.uint64)
+    for g, (txt, ro) in enumerate(views):
+        table[g] = (d_texts[g].ptr + text_at, d_recs[g].ptr, ro.size - 1, txt.size if sizes[g] is None else sizes[g])
+    bufs = [DeviceBuffer.from_numpy(x) for x in (around(let, letters_at, False), pad(wb), pad(wl), table, pad(pr), cd)]
+    d_hits = DeviceBuffer.from_numpy(np.full(guard + 16 * capacity + guard, fill, dtype=np.uint8))
+    d_total, d_status = DeviceBuffer.from_numpy(np.full(8, fill, dtype=np.uint8)), DeviceBuffer.from_numpy(np.full(4 * n + 4, fill, dtype=np.uint8))
+    d_work = DeviceBuffer.from_numpy(np.full(edit_window_targets_workspace(n, n_slots), fill, dtype=np.uint8))
+    try:
+        assert bufs[0].ptr % 16 == 0 and all(b.ptr % 16 == 0 for b in d_texts) and guard % 4 == 0
+        check(lib().txq_edit_window_targets_device(bufs[0].ptr + letters_at, let.size, bufs[1].ptr, bufs[2].ptr, wb.size, bufs[3].ptr, len(views), bufs[4].ptr,
+                                                   n, bufs[5].ptr, d_hits.ptr + guard, capacity, d_total.ptr, d_status.ptr, n_slots, d_work.ptr, stream))
+        synchronize()
+        return (d_hits.to_numpy(np.uint8, (guard + 16 * capacity + guard,)), int(d_total.to_numpy(np.uint64, (1,))[0]),
+                d_status.to_numpy(np.uint32, (n,)))
+    finally:
+        for b in bufs + d_texts + d_recs + [d_hits, d_total, d_status, d_work]:
             b.free()
 
 

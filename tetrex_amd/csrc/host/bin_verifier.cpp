@@ -115,6 +115,12 @@ size_t BinVerifier::device_max() {
 }
 
 namespace {
+uint64_t target_slot_budget();  // (defined with run_targets below)
+// TETREX_VERIFY_TARGETS=host: run_targets answers every pair on the host, so every window is written out for it
+bool window_targets_on_host() {
+    const char* e = std::getenv("TETREX_VERIFY_TARGETS");
+    return e && std::string(e) == "host";
+}
 std::string reverse_complement(const std::string& s) {
     std::string out(s.rbegin(), s.rend());
     for (char& c : out) switch (c & 0xDF) {
@@ -352,8 +358,9 @@ void BinVerifier::run(const DevicePatterns& patterns, size_t strands, const std:
 // ---- tetrex search --window --verify-windows ---------------------------------------------------------------------------
 
 void BinVerifier::verify_windows(const std::vector<std::string>& queries, const std::vector<Window>& windows, const std::vector<Candidate>& candidates,
-                                 std::vector<Hit>& hits) {
+                                 std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows) {
     hits.assign(candidates.size(), Hit{});
+    if (rows) rows->assign(candidates.size(), {});
     const size_t strands = dna_ ? 2 : 1;
     constexpr uint32_t kNone = 0xFFFFFFFFu;
     kept_.on_device = DeviceWindows{};
@@ -366,7 +373,7 @@ void BinVerifier::verify_windows(const std::vector<std::string>& queries, const 
     };
     if (candidates.empty()) return;
     const char* route_env = std::getenv("TETREX_VERIFY_WINDOWS");
-    const bool all_written = route_env && std::string(route_env) == "written";
+    const bool all_written = (route_env && std::string(route_env) == "written") || (rows && window_targets_on_host());
     // by route: what the window kernel takes, and what is written out (longer windows; everything for an A/B run)
     std::vector<size_t> on_kernel, written;
     for (size_t i = 0; i < candidates.size(); ++i) {
@@ -374,7 +381,9 @@ void BinVerifier::verify_windows(const std::vector<std::string>& queries, const 
         if (w.begin + w.len > queries.at(w.record).size()) throw std::runtime_error("tetrex search --verify-windows: a window leaves its record");
         (all_written || w.len == 0 || w.len > TXQ_EDIT_MAX_PATTERN ? written : on_kernel).push_back(i);
     }
-    if (!written.empty()) {  // each distinct window becomes a string of its own: verify() and its routes, unchanged
+    const auto window_string = [&](uint32_t q) { return queries[windows[q].record].substr(windows[q].begin, windows[q].len); };
+    if (rows) written_window_targets(written, windows.size(), candidates, window_string, *rows);
+    else if (!written.empty()) {  // each distinct window becomes a string of its own: verify() and its routes, unchanged
         std::vector<uint32_t> string_of(windows.size(), kNone);
         std::vector<std::string> strings;
         std::vector<Candidate> as_records;
@@ -391,8 +400,7 @@ void BinVerifier::verify_windows(const std::vector<std::string>& queries, const 
         for (size_t k = 0; k < written.size(); ++k) hits[written[k]] = std::move(answers[k]);
     }
     if (on_kernel.empty()) return;
-    n_candidates_ += on_kernel.size();
-    n_windows_ += on_kernel.size();
+    if (!rows) n_candidates_ += on_kernel.size(), n_windows_ += on_kernel.size();  // (with rows: run_window_targets counts what it answers)
     // by bin, and by window within the bin: the windows of a record that hit a bin are consecutive pairs, which walk together
     std::stable_sort(on_kernel.begin(), on_kernel.end(), [&](size_t x, size_t y) {
         return std::tie(candidates[x].bin, candidates[x].query) < std::tie(candidates[y].bin, candidates[y].query);
@@ -430,6 +438,7 @@ void BinVerifier::verify_windows(const std::vector<std::string>& queries, const 
     txq_check(txq_memcpy_h2d(d_len.p, win_len.data(), win_len.size() * 4), "h2d");
     kept_.on_device = DeviceWindows{(const uint8_t*)d_letters.p, letters.size(), (const uint64_t*)d_begin.p, (const uint32_t*)d_len.p, win_begin.size()};
     for (size_t i : on_kernel) kept_.entry_of[i] = entry_of[candidates[i].query];
+    if (rows) return run_window_targets(kept_.on_device, strands, on_kernel, [&](size_t i) { return entry_of[candidates[i].query]; }, candidates, windows.size(), window_string, *rows);
     run_windows(kept_.on_device, strands, on_kernel, [&](size_t i) { return entry_of[candidates[i].query]; }, candidates, hits);
 }
 
@@ -475,8 +484,9 @@ void BinVerifier::run_windows(const DeviceWindows& w, size_t strands, const std:
 // ---- tetrex search --translate --frame-window --verify-frame-windows ------------------------------------------------------
 
 void BinVerifier::verify_windows(const DeviceWindows& windows, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& lengths,
-                                 const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits) {
+                                 const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows) {
     hits.assign(candidates.size(), Hit{});
+    if (rows) rows->assign(candidates.size(), {});
     constexpr uint32_t kNone = 0xFFFFFFFFu;
     kept_.on_device = windows;
     kept_.strands = 1;
@@ -486,13 +496,14 @@ void BinVerifier::verify_windows(const DeviceWindows& windows, const std::vector
     if (lengths.size() != candidates.size()) throw std::runtime_error("tetrex search --verify-frame-windows: candidates and lengths disagree");
     if (dna_) throw std::runtime_error("tetrex search --verify-frame-windows: translated windows have one strand, the verifier two");
     const char* route_env = std::getenv("TETREX_VERIFY_FRAME_WINDOWS");
-    const bool all_written = route_env && std::string(route_env) == "written";
+    const bool all_written = (route_env && std::string(route_env) == "written") || (rows && window_targets_on_host());
     std::vector<size_t> on_kernel, written;
     for (size_t i = 0; i < candidates.size(); ++i) {
         if (candidates[i].query >= windows.n_windows) throw std::runtime_error("tetrex search --verify-frame-windows: a candidate names no window");
         (all_written || lengths[i] == 0 || lengths[i] > TXQ_EDIT_MAX_PATTERN ? written : on_kernel).push_back(i);
     }
-    if (!written.empty()) {  // each distinct window becomes a string of its own, in window order: verify() and its routes, unchanged
+    if (rows) written_window_targets(written, windows.n_windows, candidates, letters, *rows);
+    else if (!written.empty()) {  // each distinct window becomes a string of its own, in window order: verify() and its routes, unchanged
         std::vector<size_t> by_window(written);
         std::stable_sort(by_window.begin(), by_window.end(), [&](size_t x, size_t y) { return candidates[x].query < candidates[y].query; });
         std::vector<uint32_t> string_of(windows.n_windows, kNone);
@@ -510,13 +521,13 @@ void BinVerifier::verify_windows(const DeviceWindows& windows, const std::vector
         for (size_t k = 0; k < written.size(); ++k) hits[written[k]] = std::move(answers[k]);
     }
     if (on_kernel.empty()) return;
-    n_candidates_ += on_kernel.size();
-    n_windows_ += on_kernel.size();
+    if (!rows) n_candidates_ += on_kernel.size(), n_windows_ += on_kernel.size();  // (with rows: run_window_targets counts what it answers)
     // by bin, and by window within the bin: the windows of a frame that hit a bin are consecutive pairs, which walk together
     std::stable_sort(on_kernel.begin(), on_kernel.end(), [&](size_t x, size_t y) {
         return std::tie(candidates[x].bin, candidates[x].query) < std::tie(candidates[y].bin, candidates[y].query);
     });
     for (size_t i : on_kernel) kept_.entry_of[i] = candidates[i].query;
+    if (rows) return run_window_targets(windows, 1, on_kernel, [&](size_t i) { return candidates[i].query; }, candidates, windows.n_windows, letters, *rows);
     run_windows(windows, 1, on_kernel, [&](size_t i) { return candidates[i].query; }, candidates, hits);
 }
 
@@ -626,6 +637,140 @@ void BinVerifier::align_windows(const std::vector<Candidate>& candidates, const 
         strings.push_back(kept_.letters_of(p.candidate, p.strand));
     }
     align_rest(pending, candidates, [&](size_t i, size_t strand) { return strings[string_of[i * kept_.strands + strand]]; });
+}
+
+// ---- tetrex search --verify-windows / --verify-frame-windows --window-targets -----------------------------------------------
+
+void BinVerifier::written_window_targets(const std::vector<size_t>& which, size_t n_windows, const std::vector<Candidate>& candidates,
+                                         const std::function<std::string(uint32_t)>& window_string, std::vector<std::vector<Hit>>& rows) {
+    if (which.empty()) return;
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    // each distinct window becomes a string of its own, in window order (the way to a frame window's letters keeps state)
+    std::vector<size_t> by_window(which);
+    std::stable_sort(by_window.begin(), by_window.end(), [&](size_t x, size_t y) { return candidates[x].query < candidates[y].query; });
+    std::vector<uint32_t> string_of(n_windows, kNone);
+    std::vector<std::string> strings;
+    for (size_t i : by_window) {
+        const uint32_t q = candidates[i].query;
+        if (string_of[q] != kNone) continue;
+        string_of[q] = (uint32_t)strings.size();
+        strings.push_back(window_string(q));
+    }
+    std::vector<Candidate> as_records;
+    for (size_t i : which) as_records.push_back({string_of[candidates[i].query], candidates[i].bin});
+    std::vector<Hit> none;
+    std::vector<std::vector<Hit>> answers;
+    verify(strings, as_records, none, &answers);
+    for (size_t k = 0; k < which.size(); ++k) rows[which[k]] = std::move(answers[k]);
+    n_wt_host_ += which.size();
+}
+
+void BinVerifier::run_window_targets(const DeviceWindows& w, size_t strands, const std::vector<size_t>& on_kernel, const std::function<uint32_t(size_t)>& entry_of,
+                                     const std::vector<Candidate>& candidates, size_t n_windows, const std::function<std::string(uint32_t)>& window_string,
+                                     std::vector<std::vector<Hit>>& rows) {
+    const uint64_t budget = target_slot_budget();
+    // what the rounds find: (record, strand, distance, end) of every hit of a candidate; settled below
+    struct Found { uint32_t r, strand, d, j; };
+    std::vector<std::vector<Found>> found(candidates.size());
+    std::vector<size_t> answered, fallback;
+    const auto bin_at = [&](size_t k) { return candidates[on_kernel[k]].bin; };
+    // one round, on_kernel[a, b) — its bins all resident: their views and the pairs go up, ONE call, one wait, the rows written come back
+    const auto run_round = [&](size_t a, size_t b) {
+        if (a == b) return;
+        std::vector<txq_text_view> views;
+        std::vector<uint32_t> pairs;
+        bool all_resident = true;
+        uint64_t n_slots = 0;
+        for (size_t k = a; k < b; ++k) {
+            if (k == a || bin_at(k) != bin_at(k - 1)) {
+                all_resident = all_resident && bins_.is_resident(bin_at(k));
+                const ResidentBins::Bin& e = bins_.at(bin_at(k));
+                views.push_back({(const uint8_t*)e.d_text, (const uint64_t*)e.d_rec, e.n_records, e.text_bytes});
+            }
+            for (size_t s = 0; s < strands; ++s) pairs.insert(pairs.end(), {entry_of(on_kernel[k]) + (uint32_t)s, (uint32_t)(views.size() - 1), errors_});
+            n_slots += strands * views.back().n_records;
+        }
+        if (!all_resident) {  // a bin left while a later one of the round came: verify()'s routes answer the round
+            fallback.insert(fallback.end(), on_kernel.begin() + (long)a, on_kernel.begin() + (long)b);
+            return;
+        }
+        const size_t n_pairs = (b - a) * strands;
+        DeviceBuffer d_views(views.size() * sizeof(txq_text_view)), d_pairs(pairs.size() * 4 + 4), d_hits(n_slots * 16 + 16), d_total(8), d_status(n_pairs * 4 + 4),
+            d_work(TXQ_EDIT_WINDOW_TARGETS_WORKSPACE(n_pairs, n_slots) + 8);
+        txq_check(txq_memcpy_h2d(d_views.p, views.data(), views.size() * sizeof(txq_text_view)), "h2d");
+        txq_check(txq_memcpy_h2d(d_pairs.p, pairs.data(), pairs.size() * 4), "h2d");
+        txq_check(txq_edit_window_targets_device(w.d_letters, w.bytes, w.d_begin, w.d_len, w.n_windows, (const txq_text_view*)d_views.p, views.size(),
+                                                 (const uint32_t*)d_pairs.p, n_pairs, (const uint8_t*)d_codes_, (uint32_t*)d_hits.p, n_slots, (uint64_t*)d_total.p,
+                                                 (uint32_t*)d_status.p, n_slots, d_work.p, nullptr),
+                  "txq_edit_window_targets_device");
+        ++n_wt_calls_;
+        uint64_t total = 0;
+        std::vector<uint32_t> status(n_pairs);
+        txq_check(txq_memcpy_d2h(&total, d_total.p, 8), "d2h");  // (waits for the kernels)
+        txq_check(txq_memcpy_d2h(status.data(), d_status.p, n_pairs * 4), "d2h");
+        for (size_t p = 0; p < n_pairs; ++p)
+            if (status[p] != 0) throw std::runtime_error("tetrex search --window-targets: the device refused a pair of bin " + std::to_string(bin_at(a + p / strands)));
+        if (total > n_slots) throw std::runtime_error("tetrex search --window-targets: more hits than slots");
+        std::vector<uint32_t> hits(4 * total);
+        if (total) txq_check(txq_memcpy_d2h(hits.data(), d_hits.p, total * 16), "d2h");
+        for (uint64_t h = 0; h < total; ++h) {
+            const uint32_t* row = hits.data() + 4 * h;
+            found[on_kernel[a + row[0] / strands]].push_back({row[2], (uint32_t)(row[0] % strands), row[1], row[3]});
+        }
+        answered.insert(answered.end(), on_kernel.begin() + (long)a, on_kernel.begin() + (long)b);
+    };
+    // the rounds: candidates in order while their bins fit the cache together and their slots the bound.  A bin's bytes and
+    // records are known before it is uploaded (a bin that is not resident is read first), so a round ends BEFORE the bin that
+    // would push one of its own out, and a bin of more records than a call's slots is never uploaded.
+    size_t round_begin = 0;
+    uint64_t round_bytes = 0, round_slots = 0;
+    for_each_bin_run(0, on_kernel.size(), bin_at, [&](uint32_t bin, size_t a, size_t b) {
+        std::string text;
+        std::vector<uint64_t> rec;
+        std::vector<std::string> names;
+        const bool there = bins_.is_resident(bin);
+        if (!there) bins_.read(bin, text, rec, names);
+        const uint64_t n_records = there ? bins_.at(bin).n_records : rec.size() - 1;
+        const uint64_t bytes = there ? bins_.at(bin).device_bytes : ResidentBins::bytes_on_device(text.size(), n_records);
+        if (n_records > budget) {  // a single pair above the bound: run_targets sends it to the host
+            run_round(round_begin, a);
+            fallback.insert(fallback.end(), on_kernel.begin() + (long)a, on_kernel.begin() + (long)b);
+            round_begin = b, round_bytes = round_slots = 0;
+            return;
+        }
+        if (a > round_begin && round_bytes + bytes > bins_.limit_bytes()) {
+            run_round(round_begin, a);
+            round_begin = a, round_bytes = round_slots = 0;
+        }
+        if (there) bins_.resident(bin);
+        else bins_.resident(bin, text, rec, names);
+        round_bytes += bytes;
+        for (size_t k = a; k < b; ++k) {  // (the pairs of one candidate stay in one round)
+            if (k > round_begin && round_slots + strands * n_records > 8 * budget) {
+                run_round(round_begin, k);
+                round_begin = k, round_bytes = bytes, round_slots = 0;
+            }
+            round_slots += strands * n_records;
+        }
+    });
+    run_round(round_begin, on_kernel.size());
+    // settle: a target's row is its better strand, + on equal distance; rows in the order of the bin's file
+    n_candidates_ += answered.size();
+    n_wt_device_ += answered.size();
+    for (size_t i : answered) {
+        std::vector<Found>& f = found[i];
+        std::sort(f.begin(), f.end(), [](const Found& x, const Found& y) { return std::tie(x.r, x.d, x.strand) < std::tie(y.r, y.d, y.strand); });
+        const std::vector<std::string>& names = bins_.at(candidates[i].bin).names;
+        for (size_t k = 0; k < f.size(); ++k) {
+            if (k && f[k].r == f[k - 1].r) continue;
+            Hit h;
+            h.distance = f[k].d, h.end = f[k].j, h.strand = f[k].strand ? '-' : '+', h.target = &names.at(f[k].r);
+            rows[i].push_back(std::move(h));
+        }
+        if (!rows[i].empty()) ++n_confirmed_;
+        n_targets_ += rows[i].size();
+    }
+    written_window_targets(fallback, n_windows, candidates, window_string, rows);
 }
 
 // ---- tetrex search --verify --all-targets ------------------------------------------------------------------------------

@@ -102,6 +102,17 @@ class ResidentBins {
 // TXQ_EDIT_ALIGN_MAX_DISTANCE edits), windows that did not take the window kernel (longer than TXQ_EDIT_MAX_PATTERN, the
 // `written` routes), a round whose bins did not all stay resident, and with TETREX_VERIFY_ALIGN=host every pair, go to the host
 // twin as above.
+// `--window-targets` (verify_windows with `rows`): every record of the bin within E edits of a window is a row of
+// its candidate, in the order of the bin's file — on a nucleotide index a target's better strand, + on equal distance.  The
+// candidates, by bin and by window within the bin, are cut into rounds: a round is a maximal prefix whose bins fit
+// TETREX_VERIFY_TEXT_MB together (one bin is always a round) and whose slots — the sum over its pairs of the records of their
+// bins — are at most eight times TETREX_VERIFY_TARGET_SLOTS.  A round's bins are made resident, a table of their views and the
+// pairs go up (the letters went up once per batch, or are the caller's), ONE txq_edit_window_targets_device is queued over all
+// the round's bins, the round waits once, for the total, and copies back the rows written.  Through verify() with rows — the
+// windows written out as strings, run_targets and its routes — go: windows of more than TXQ_EDIT_MAX_PATTERN letters, a bin with
+// more records than TETREX_VERIFY_TARGET_SLOTS, a round whose bins did not all stay resident, and with
+// TETREX_VERIFY_WINDOWS=written / TETREX_VERIFY_FRAME_WINDOWS=written or TETREX_VERIFY_TARGETS=host every candidate.  The rows are
+// the same on every route; align_windows takes a selected row as it takes a hit (its target points into the bin's names).
 class BinVerifier {
   public:
     BinVerifier(const std::vector<std::string>& bin_paths, bool dna, uint32_t errors);
@@ -133,8 +144,9 @@ class BinVerifier {
         uint64_t begin;
         uint32_t len;
     };
+    // rows (`--window-targets`, below): rows->at(i) receives every target of candidates[i] instead, and hits stays as assign() left it.
     void verify_windows(const std::vector<std::string>& queries, const std::vector<Window>& windows, const std::vector<Candidate>& candidates,
-                        std::vector<Hit>& hits);
+                        std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows = nullptr);
     // `--translate --frame-window --verify-frame-windows`: the windows' letters are on the device already — the
     // frames of txq_translate_frames_device, `bytes` of them with 16 bytes of slack behind, window w being
     // d_letters[d_begin[w] .. d_begin[w] + d_len[w]) as txq_frame_window_letters_device left them.  candidates[i].query names a
@@ -151,7 +163,7 @@ class BinVerifier {
         size_t n_windows;
     };
     void verify_windows(const DeviceWindows& windows, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& lengths,
-                        const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits);
+                        const std::function<std::string(uint32_t)>& letters, std::vector<Hit>& hits, std::vector<std::vector<Hit>>* rows = nullptr);
     // `--align-windows`: selection[k] names a candidate of the LAST verify_windows call (either form) and the confirmed hit that
     // answers it; the hit gets start and runs (include/txq.h at txq_edit_align_windows_device).  `candidates` are that call's,
     // and what it was given — queries and windows, or the device buffers and `letters` — must still be there.
@@ -165,7 +177,10 @@ class BinVerifier {
     size_t n_align_windows_calls() const { return n_align_windows_calls_; }  // txq_edit_align_windows_device calls
     size_t n_candidates() const { return n_candidates_; }
     size_t n_confirmed() const { return n_confirmed_; }
-    size_t n_targets() const { return n_targets_; }  // `--all-targets`: the rows of all confirmed pairs
+    size_t n_targets() const { return n_targets_; }  // `--all-targets`, `--window-targets`: the rows of all confirmed pairs
+    // `--window-targets`: the candidates txq_edit_window_targets_device answered, those that took verify()'s routes, and the calls
+    struct WindowTargets { size_t device, host, calls; };
+    WindowTargets n_window_targets() const { return {n_wt_device_, n_wt_host_, n_wt_calls_}; }
     struct Routed { size_t device, device_long, host, windows; };  // (windows: txq_edit_windows_device)
     Routed n_routed() const { return {n_device_, n_device_long_, n_host_, n_windows_}; }
     void set_align(bool on) { align_ = on; }
@@ -183,6 +198,16 @@ class BinVerifier {
     // back, the better strand (+ on equal distance)
     void run_windows(const DeviceWindows& w, size_t strands, const std::vector<size_t>& on_kernel, const std::function<uint32_t(size_t)>& entry_of,
                      const std::vector<Candidate>& candidates, std::vector<Hit>& hits);
+    // `--window-targets`: every target of the candidates on_kernel (by bin and by window), as `strands` consecutive entries from
+    // entry_of(candidate) of window arrays on the device — rounds, ONE txq_edit_window_targets_device call each, the better strand
+    // per target; what a round cannot answer goes to written_window_targets
+    void run_window_targets(const DeviceWindows& w, size_t strands, const std::vector<size_t>& on_kernel, const std::function<uint32_t(size_t)>& entry_of,
+                            const std::vector<Candidate>& candidates, size_t n_windows, const std::function<std::string(uint32_t)>& window_string,
+                            std::vector<std::vector<Hit>>& rows);
+    // the candidates `which` with their windows written out as strings (window_string(window), asked in ascending order): verify()
+    // with rows, so run_targets and its three routes
+    void written_window_targets(const std::vector<size_t>& which, size_t n_windows, const std::vector<Candidate>& candidates,
+                                const std::function<std::string(uint32_t)>& window_string, std::vector<std::vector<Hit>>& rows);
     // `--all-targets`: the same routing with txq_edit_targets*_device and edit_targets_group in place of the search calls
     void run_targets(const DevicePatterns& patterns, size_t strands, const std::vector<Candidate>& candidates, const std::vector<uint32_t>& pattern_of,
                      const std::vector<uint64_t>& lengths, const Letters& letters, std::vector<std::vector<Hit>>& rows);
@@ -222,6 +247,7 @@ class BinVerifier {
     bool align_ = false;
     size_t n_align_device_ = 0, n_align_host_ = 0;
     size_t n_targets_ = 0;
+    size_t n_wt_device_ = 0, n_wt_host_ = 0, n_wt_calls_ = 0;
     // what the last verify_windows call left for align_windows: where its windows are on the device (the first form's own
     // buffers, the second form's caller's), `strands` entries from entry_of[candidate] (0xFFFFFFFF: the candidate did not take the
     // window kernel), and the window of (candidate, strand) as a string

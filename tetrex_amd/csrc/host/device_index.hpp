@@ -148,6 +148,11 @@ class DeviceIndex {
         // [h0, h1) of hits — whole records —, it returns the indexes of the confirmed hits to align; those get start and runs
         // (BinVerifier::align_windows) before the batch's letters are overwritten by the next one
         std::function<std::vector<size_t>(size_t, size_t)> select;
+        // `--window-targets`: targets[i] receives every target of hits[i] (BinVerifier::verify_windows with rows) and
+        // confirmed stays empty of answers; select_rows then takes select's place and returns (hit, row of its targets) pairs
+        bool all_targets = false;
+        std::vector<std::vector<VerifiedHit>> targets;
+        std::function<std::vector<std::pair<size_t, size_t>>(size_t, size_t)> select_rows;
     };
     void search_translated_windows(std::string_view seq, const std::vector<uint64_t>& rec_offsets, uint32_t window, uint32_t step,
                                    const std::function<uint64_t(uint64_t)>& threshold_of, bool with_counts, std::vector<uint64_t>& win_offsets,

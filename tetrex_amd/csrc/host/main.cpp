@@ -14,17 +14,19 @@
 //   tetrex search --window W [--step S] (-e E | --threshold F) [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (a local search: every record cut into overlapping windows of W letters, S apart, each answered like a record of its own,
 //      slid on the device; the rows say where on the record each bin is hit)
-//   tetrex search --window W [--step S] -e E --verify-windows [--align-windows] [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//   tetrex search --window W [--step S] -e E --verify-windows [--window-targets] [--align-windows] [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (the local search confirmed: only the runs of windows whose letters are within E edits of a record of the bin, each with
 //      the distance, target and end of its nearest window; compared on the device, the windows never written out;
-//      --align-windows: which window that is, where its match begins in the target, and its alignment as a CIGAR string)
+//      --align-windows: which window that is, where its match begins in the target, and its alignment as a CIGAR string;
+//      --window-targets: a row for every record of the bin that a run of windows matches, not only the nearest one)
 //   tetrex search --translate --frame-window W [--frame-step S] (-e E | --threshold F) [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (the local search in the six frames of nucleotide records: every frame cut into overlapping windows of W residues, S apart,
 //      translated, cut and slid on the device; the rows say in which frame and where on the record, in nucleotides, each bin is hit)
-//   tetrex search --translate --frame-window W [--frame-step S] -e E --verify-frame-windows [--align-windows] [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
+//   tetrex search --translate --frame-window W [--frame-step S] -e E --verify-frame-windows [--window-targets] [--align-windows] [--counts] [-o dest] [-v] [-D device] <index.ibf> <queries.fa[.gz]>
 //     (the translated local search confirmed: only the runs of windows whose residues are within E edits of a record of the bin,
 //      stops counted as edits, each with the distance, target and end of its nearest window; the letters never leave the device;
-//      --align-windows: the same three columns more, the window in nucleotides, the CIGAR in residues)
+//      --align-windows: the same three columns more, the window in nucleotides, the CIGAR in residues;
+//      --window-targets: as above, a row per (run of windows, target))
 //   tetrex inspect <index.ibf>   (src/inspect_idx.cpp)
 // The candidate-bin masks come from the GPU (libtxq.so); there is no CPU probe path.
 // (`tetrex search` is search_cmd.cpp.)

@@ -34,6 +34,7 @@ struct Search {
     std::unique_ptr<BinVerifier> verifier;
     bool align = false, all_targets = false, windows = false;  // windows: --verify-windows, the candidates are windows
     bool align_windows = false;  // --align-windows: the nearest window of every row is aligned after the run merge
+    bool window_targets = false;  // --window-targets: a row per run of windows that hit one target
 
     Search(const Args& args, const IndexImage& img, unsigned long long errors, double fraction, double started = now())
         : a(args), image(img), verbose(args.has("verbose")), with_counts(args.has("counts")), t_start(started) {
@@ -57,17 +58,22 @@ struct Search {
         all_targets = a.has("all-targets");
         align_windows = a.has("align-windows");
         if (align_windows) verifier->keep_windows(true);
+        window_targets = a.has("window-targets");
     }
     void report_verifier() const {
         if (!verifier) return;
         if (verbose)
             std::cerr << "Verified: " << verifier->n_confirmed() << " of " << verifier->n_candidates() << " candidate " << (windows ? "windows" : "pairs") << std::endl;
-        if (verbose && all_targets) std::cerr << "Targets: " << verifier->n_targets() << std::endl;
+        if (verbose && (all_targets || window_targets)) std::cerr << "Targets: " << verifier->n_targets() << std::endl;
         if (!std::getenv("TETREX_TRACE")) return;
         const BinVerifier::Routed n = verifier->n_routed();
         std::cerr << "[tetrex search] verify routes: device " << n.device << ", device-long " << n.device_long << ", host " << n.host;
         if (windows) std::cerr << ", windows " << n.windows;
         std::cerr << std::endl;
+        if (window_targets) {
+            const BinVerifier::WindowTargets wt = verifier->n_window_targets();
+            std::cerr << "[tetrex search] window targets: device " << wt.device << ", host " << wt.host << ", calls " << wt.calls << std::endl;
+        }
         const BinVerifier::Aligned al = verifier->n_aligned();
         if (align_windows)
             std::cerr << "[tetrex search] align windows: device " << al.device << ", host " << al.host << ", calls " << verifier->n_align_windows_calls() << std::endl;
@@ -219,21 +225,35 @@ int search_windowed(const Args& a, const IndexImage& image, unsigned long long e
     std::vector<BinVerifier::Window> win_table;
     std::vector<BinVerifier::Candidate> candidates;
     std::vector<VerifiedHit> confirmed;
-    struct Confirmed { uint32_t query, bin, count, distance; char strand; size_t at; };  // at: its place in `confirmed`
+    std::vector<std::vector<VerifiedHit>> targets;  // --window-targets: targets[i] are the rows of hits[i]
+    // at: its place in `confirmed`; with --window-targets an item is a target hit: row `row` of targets[at], whose target it names
+    struct Confirmed { uint32_t query, bin, count, distance; char strand; size_t at; const std::string* target; size_t row; };
     std::vector<Confirmed> kept;
+    const auto hit_of = [&](const Confirmed& x) -> VerifiedHit& { return s.window_targets ? targets[x.at][x.row] : confirmed[x.at]; };
     auto flush = [&]() {
         if (recs.empty()) return;
         s.dev.search_windows(values, begins, lens, thresholds, s.with_counts, hits);
         if (verify) {
             candidates.clear();
             for (const Hit& x : hits) candidates.push_back({x.query, x.bin});
-            s.verifier->verify_windows(seqs, win_table, candidates, confirmed);
+            s.verifier->verify_windows(seqs, win_table, candidates, confirmed, s.window_targets ? &targets : nullptr);
         }
         // the confirmed windows among hits [h0, h1) — one record's — by bin, strand and window, and their runs
         const auto merge = [&](size_t h0, size_t h1) {
             kept.clear();
+            if (s.window_targets) {  // the target hits by bin, target, strand and window, and their runs per target
+                for (size_t i = h0; i < h1; ++i)
+                    for (size_t t = 0; t < targets[i].size(); ++t)
+                        kept.push_back({hits[i].query, hits[i].bin, hits[i].count, targets[i][t].distance, targets[i][t].strand, i, targets[i][t].target, t});
+                std::stable_sort(kept.begin(), kept.end(), [](const Confirmed& x, const Confirmed& y) {
+                    if (x.bin != y.bin) return x.bin < y.bin;
+                    if (x.target != y.target) return std::less<const std::string*>()(x.target, y.target);  // (the bin's names: the order of its file)
+                    return x.strand != y.strand ? x.strand == '+' : x.query < y.query;
+                });
+                return plan::target_runs(kept);
+            }
             for (size_t i = h0; i < h1; ++i)
-                if (confirmed[i].distance != 0xFFFFFFFFu) kept.push_back({hits[i].query, hits[i].bin, hits[i].count, confirmed[i].distance, confirmed[i].strand, i});
+                if (confirmed[i].distance != 0xFFFFFFFFu) kept.push_back({hits[i].query, hits[i].bin, hits[i].count, confirmed[i].distance, confirmed[i].strand, i, nullptr, 0});
             std::stable_sort(kept.begin(), kept.end(), [](const Confirmed& x, const Confirmed& y) {
                 return x.bin != y.bin ? x.bin < y.bin : x.strand != y.strand ? x.strand == '+' : x.query < y.query;
             });
@@ -245,7 +265,7 @@ int search_windowed(const Args& a, const IndexImage& image, unsigned long long e
             for (const Rec& r : recs) {
                 const size_t h0 = h;
                 while (h < hits.size() && hits[h].query < r.w1) ++h;
-                for (const plan::WindowRun& run : merge(h0, h)) selection.push_back({kept[run.nearest].at, &confirmed[kept[run.nearest].at]});
+                for (const plan::WindowRun& run : merge(h0, h)) selection.push_back({kept[run.nearest].at, &hit_of(kept[run.nearest])});
             }
             s.verifier->align_windows(candidates, selection);
         }
@@ -263,9 +283,9 @@ int search_windowed(const Args& a, const IndexImage& image, unsigned long long e
                     row.assign(r.name).append("\t").append(image.bin_paths[first.bin]).append("\t").append(std::to_string(letter_at[first.query] + 1));
                     row.append("\t").append(std::to_string(letter_at[last.query] + lens[last.query] + k - 1));
                     s.append_count(row, best.count, lens[best.query]);
-                    s.append_verified(row, confirmed[nearest.at], dna);
+                    s.append_verified(row, hit_of(nearest), dna);
                     if (s.align_windows)
-                        s.append_window_alignment(row, confirmed[nearest.at], letter_at[nearest.query] + 1, letter_at[nearest.query] + lens[nearest.query] + k - 1);
+                        s.append_window_alignment(row, hit_of(nearest), letter_at[nearest.query] + 1, letter_at[nearest.query] + lens[nearest.query] + k - 1);
                     *s.out << row << '\n';
                     ++n_rows;
                 }
@@ -357,18 +377,43 @@ int search_translated_windowed(const Args& a, const IndexImage& image, unsigned 
     DeviceIndex::VerifiedWindows verified;
     verified.verifier = s.verifier.get();
     verified.edits = (uint32_t)std::min<uint64_t>(errors, 0xFFFFFFFEull);
-    struct Confirmed { uint32_t query, bin, count, distance; char strand; size_t at; };  // at: its place in verified.confirmed
+    verified.all_targets = s.window_targets;
+    // at: its place in verified.confirmed; with --window-targets an item is a target hit: row `row` of verified.targets[at]
+    struct Confirmed { uint32_t query, bin, count, distance; char strand; size_t at; const std::string* target; size_t row; };
     std::vector<Confirmed> kept;
+    const auto hit_of = [&](const Confirmed& x) -> VerifiedHit& { return s.window_targets ? verified.targets[x.at][x.row] : verified.confirmed[x.at]; };
     // the confirmed windows among hits [h0, h1) — one frame's — by bin and window, and their runs: what the rows are written
     // from and, with --align-windows, what the nearest windows are selected from, batch by batch
     const auto merge = [&](size_t h0, size_t h1) {
         kept.clear();
+        if (s.window_targets) {  // the target hits by bin, target and window, and their runs per target
+            for (size_t i = h0; i < h1; ++i)
+                for (size_t t = 0; t < verified.targets[i].size(); ++t)
+                    kept.push_back({hits[i].query, hits[i].bin, hits[i].count, verified.targets[i][t].distance, '+', i, verified.targets[i][t].target, t});
+            std::stable_sort(kept.begin(), kept.end(), [](const Confirmed& x, const Confirmed& y) {
+                if (x.bin != y.bin) return x.bin < y.bin;
+                return x.target != y.target ? std::less<const std::string*>()(x.target, y.target) : x.query < y.query;
+            });
+            return plan::target_runs(kept);
+        }
         for (size_t i = h0; i < h1; ++i)
-            if (verified.confirmed[i].distance != 0xFFFFFFFFu) kept.push_back({hits[i].query, hits[i].bin, hits[i].count, verified.confirmed[i].distance, '+', i});
+            if (verified.confirmed[i].distance != 0xFFFFFFFFu) kept.push_back({hits[i].query, hits[i].bin, hits[i].count, verified.confirmed[i].distance, '+', i, nullptr, 0});
         std::stable_sort(kept.begin(), kept.end(), [](const Confirmed& x, const Confirmed& y) { return x.bin != y.bin ? x.bin < y.bin : x.query < y.query; });
         return plan::confirmed_runs(kept);
     };
-    if (s.align_windows)
+    if (s.align_windows && s.window_targets)
+        verified.select_rows = [&](size_t h0, size_t h1) {  // the same over target rows: (hit, row of its targets)
+            std::vector<std::pair<size_t, size_t>> nearest;
+            for (size_t h = h0; h < h1;) {
+                const uint64_t frame_end = *std::upper_bound(win_offsets.begin(), win_offsets.end(), (uint64_t)hits[h].query);
+                size_t e = h;
+                while (e < h1 && hits[e].query < frame_end) ++e;
+                for (const plan::WindowRun& run : merge(h, e)) nearest.push_back({kept[run.nearest].at, kept[run.nearest].row});
+                h = e;
+            }
+            return nearest;
+        };
+    else if (s.align_windows)
         verified.select = [&](size_t h0, size_t h1) {  // the hits of a device batch: whole records, so whole frames
             std::vector<size_t> nearest;
             for (size_t h = h0; h < h1;) {
@@ -415,11 +460,11 @@ int search_translated_windowed(const Args& a, const IndexImage& image, unsigned 
                         const Confirmed &first = kept[run.first], &last = kept[run.last], &best = kept[run.best], &nearest = kept[run.nearest];
                         begin_row(first.bin, first.query, last.query);
                         s.append_count(row, best.count, lens[best.query]);
-                        s.append_verified(row, verified.confirmed[nearest.at], false);
+                        s.append_verified(row, hit_of(nearest), false);
                         if (s.align_windows) {
                             const txq::fw::Window wn = txq::fw::window_at(layout, nearest.query - w0);
                             const txq::fw::Span on = txq::fw::residues_on_record(L, f, wn.a, wn.a + wn.len);
-                            s.append_window_alignment(row, verified.confirmed[nearest.at], on.begin, on.end);
+                            s.append_window_alignment(row, hit_of(nearest), on.begin, on.end);
                         }
                         *s.out << row << '\n';
                         ++n_rows;
@@ -529,7 +574,7 @@ int search_plain(const Args& a, const IndexImage& image, unsigned long long erro
 int cmd_search(int argc, char** argv) {
     const std::vector<OptSpec> spec = {{'e', "errors", true}, {'\0', "threshold", true}, {'\0', "counts", false}, {'o', "output", true},
                                        {'v', "verbose", false}, {'D', "device", true}, {'\0', "translate", false}, {'\0', "verify", false},
-                                       {'\0', "verify-frames", false}, {'\0', "verify-windows", false}, {'\0', "verify-frame-windows", false}, {'\0', "align", false}, {'\0', "align-windows", false}, {'\0', "all-targets", false},
+                                       {'\0', "verify-frames", false}, {'\0', "verify-windows", false}, {'\0', "verify-frame-windows", false}, {'\0', "align", false}, {'\0', "align-windows", false}, {'\0', "all-targets", false}, {'\0', "window-targets", false},
                                        {'\0', "window", true}, {'\0', "step", true}, {'\0', "frame-window", true}, {'\0', "frame-step", true}};
     Args a;
     unsigned long long errors = 0, window = 0, step = 0, frame_window = 0, frame_step = 0;
@@ -540,7 +585,14 @@ int cmd_search(int argc, char** argv) {
         if (a.has("align-windows") && !a.has("verify-windows") && !a.has("verify-frame-windows"))
             throw std::runtime_error("--align-windows gives start and cigar of confirmed window runs: it needs --window W -e E --verify-windows, or --translate --frame-window W -e E --verify-frame-windows");
         // (--align is the whole-record flag; next to the window modes its refusal names the flag that is meant)
-        const auto hint = [](const char* o) { return std::string(o) == "align" ? " (the alignment of confirmed window runs is --align-windows)" : ""; };
+        // (likewise --all-targets: every target of confirmed window runs is --window-targets)
+        if (a.has("window-targets") && !a.has("verify-windows") && !a.has("verify-frame-windows"))
+            throw std::runtime_error("--window-targets gives a row for every target of confirmed window runs: it needs --window W -e E --verify-windows, or --translate --frame-window W -e E --verify-frame-windows");
+        const auto hint = [](const char* o) {
+            return std::string(o) == "align"         ? " (the alignment of confirmed window runs is --align-windows)"
+                   : std::string(o) == "all-targets" ? " (every target of confirmed window runs is --window-targets)"
+                                                     : "";
+        };
         if (a.has("step") && !a.has("window")) throw std::runtime_error("--step is the distance between the windows of --window W: it needs --window");
         if (a.has("frame-step") && !a.has("frame-window"))
             throw std::runtime_error("--frame-step is the distance between the windows of --frame-window W: it needs --frame-window");

@@ -244,6 +244,7 @@ void DeviceIndex::search_translated_windows(std::string_view seq, const std::vec
         if (!verified->verifier) throw std::runtime_error("search_translated_windows: verified windows need a verifier");
         verified->stops.assign(N, 0);
         verified->confirmed.clear();
+        verified->targets.clear();
     }
     if (R == 0 || W == 0 || N == 0) return;
     // --verify-frame-windows: the threshold follows from a window's stops (fw::stop_threshold) unless the A/B variable asks for §18's
@@ -278,6 +279,7 @@ void DeviceIndex::search_translated_windows(std::string_view seq, const std::vec
     std::vector<uint32_t> thr, lengths;
     std::vector<BinVerifier::Candidate> candidates;
     std::vector<VerifiedHit> batch_confirmed;
+    std::vector<std::vector<VerifiedHit>> batch_targets;
     const uint32_t bin0 = (uint32_t)(info_.shard_word0 * 64);
     for (size_t c = 0; c + 1 < cut.size(); ++c) {
         const size_t r0 = cut[c], r1 = cut[c + 1], nr = r1 - r0;
@@ -328,6 +330,7 @@ void DeviceIndex::search_translated_windows(std::string_view seq, const std::vec
         if (!verified) continue;
         // --verify-frame-windows: the batch's hits are candidates, window index = the window's index within the batch
         verified->confirmed.resize(hits.size());
+        if (verified->all_targets) verified->targets.resize(hits.size());
         if (hits.size() == h0) continue;
         candidates.clear();
         lengths.clear();
@@ -353,9 +356,17 @@ void DeviceIndex::search_translated_windows(std::string_view seq, const std::vec
         };
         verified->verifier->verify_windows(BinVerifier::DeviceWindows{(const uint8_t*)d_frames.p, frames_bytes, (const uint64_t*)d_lbeg.p,
                                                                       (const uint32_t*)d_llen.p, (size_t)nw},
-                                           candidates, lengths, window_letters, batch_confirmed);
+                                           candidates, lengths, window_letters, batch_confirmed, verified->all_targets ? &batch_targets : nullptr);
         std::move(batch_confirmed.begin(), batch_confirmed.end(), verified->confirmed.begin() + (long)h0);
-        if (verified->select) {  // --align-windows: the selected hits, while the batch's frames are still on the device
+        if (verified->all_targets) std::move(batch_targets.begin(), batch_targets.end(), verified->targets.begin() + (long)h0);
+        if (verified->all_targets && verified->select_rows) {  // --window-targets --align-windows: the selected rows
+            std::vector<BinVerifier::Selected> selection;
+            for (const auto& [h, t] : verified->select_rows(h0, hits.size())) {
+                if (h < h0 || h >= hits.size() || t >= verified->targets[h].size()) throw std::runtime_error("search_translated_windows: a selected row is not of the batch");
+                selection.push_back({h - h0, &verified->targets[h][t]});
+            }
+            verified->verifier->align_windows(candidates, selection);
+        } else if (verified->select) {  // --align-windows: the selected hits, while the batch's frames are still on the device
             std::vector<BinVerifier::Selected> selection;
             for (const size_t h : verified->select(h0, hits.size())) {
                 if (h < h0 || h >= hits.size()) throw std::runtime_error("search_translated_windows: a selected hit is not of the batch");

@@ -74,6 +74,24 @@ std::vector<WindowRun> confirmed_runs(const std::vector<Item>& items) {
     return runs;
 }
 
+// --window-targets: the TARGET HITS of one record (confirmed_runs' items with .target, the hit record's place
+// in its bin's file; a window is there once per bin and target, on the strand that verification settled for that target),
+// sorted by bin, then target, then strand (+ first), then window.  The items of a (bin, target) are merged by
+// confirmed_runs' rule, so every maximal run of consecutive windows that hit one target on one strand is one row, `nearest`
+// being the run's nearest window to THAT target.  The rows come by bin, then target, then by their first window, + before -.
+template <class Item>
+std::vector<WindowRun> target_runs(const std::vector<Item>& items) {
+    std::vector<WindowRun> runs;
+    for (size_t a = 0; a < items.size();) {
+        size_t b = a + 1;
+        while (b < items.size() && items[b].bin == items[a].bin && items[b].target == items[a].target) ++b;
+        for (const WindowRun& r : confirmed_runs(std::vector<Item>(items.begin() + (long)a, items.begin() + (long)b)))
+            runs.push_back({r.first + a, r.last + a, r.best + a, r.nearest + a});
+        a = b;
+    }
+    return runs;
+}
+
 // Device batches: batch i is the items [cut[i], cut[i + 1]); most_*: the largest batch's, for buffers sized before the first
 // batch runs ("Host")
 struct Cuts {
