@@ -77,6 +77,14 @@ extern "C" {
  *                                                     call, not the one launch that answers, counts and extends the table
  *   TXQ_PROBE_TABLE_TILE=0                            no table-only tile body: a full tile whose 64 k-mers all have a table row
  *                                                     takes the general body like every other tile (A/B and cross-checks)
+ *   TXQ_PROBE_SORT=0|1                                a large one-launch call on kept rows, without d_alive, on rows of 16 or 32 whole
+ *                                                     words: never | answered from its batch in value-bucket order (three small
+ *                                                     launches partition it), so that an XCD's L2 holds the table rows it reads.
+ *                                                     Scratch kept with the index, grow-only: 8 bytes per k-mer of the largest such
+ *                                                     batch and up to 4 MB of counters, at most TXQ_KMER_TABLE_MB MiB (a larger
+ *                                                     batch is answered in batch order)
+ *   TXQ_PROBE_SORT_MIN=<n>                            the smallest such batch (default 8388608)
+ *   TXQ_PROBE_SORT_BUCKET_KB=<n>                      table rows per value bucket, in KiB (default 1024; at most 256 buckets)
  * (tests/test_gpu_knobs.py runs a workload under each of them against the oracle.) */
 
 typedef enum {
@@ -191,6 +199,10 @@ int txq_probe(txq_index* ix, const uint64_t* kmers, size_t n, uint64_t* masks);
  * (bitvector::none() of include/otf_collector.h:383, per shard). */
 int txq_probe_device(txq_index* ix, const uint64_t* d_kmers, size_t n, uint64_t* d_masks, uint64_t* d_alive,
                      void* stream);
+/* A trace of the flat probe's sorted answer (TXQ_PROBE_SORT above), for tests: out[0] = calls that bucketed their batch,
+ * out[1] = answers that then ran in bucket order (a batch with a k-mer at or above the table's valid rows is answered in
+ * batch order), counted since the table's state was last started over.  Waits for the index's last probe call. */
+int txq_index_probe_sorted(txq_index* ix, uint64_t out[2]);
 
 /* Threshold membership of value sets (seqan::hibf membership_for(values, threshold); counting_agent::bulk_count on a
  * flat IBF).  Query q owns d_values[d_offsets[q] .. d_offsets[q+1]) (n_queries + 1 ascending offsets, at most 2^32-1

@@ -21,7 +21,7 @@ TXQ_MERGED_BIN = 0xFFFFFFFFFFFFFFFF
 SYMBOLS = [
     "txq_init", "txq_shutdown", "txq_last_error", "txq_device_count",
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
-    "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_emplace_device", "txq_count", "txq_count_device",
+    "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_index_probe_sorted", "txq_emplace_device", "txq_count", "txq_count_device",
     "txq_count_windows", "txq_count_windows_device",
     "txq_translate_bound", "txq_translate_device", "txq_translate",
     "txq_translate_windows_bound", "txq_translate_windows_device", "txq_translate_windows", "txq_translate_frames_bound", "txq_translate_frames_device", "txq_translate_frames",
@@ -89,6 +89,7 @@ def lib():
         L.txq_index_download_words.argtypes = [C.c_void_p, u64p, C.c_size_t]
         L.txq_probe.argtypes = [C.c_void_p, u64p, C.c_size_t, u64p]
         L.txq_probe_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.txq_index_probe_sorted.argtypes = [C.c_void_p, u64p]
         L.txq_emplace_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.txq_count.argtypes = [C.c_void_p, u64p, u64p, C.c_size_t, u32p, u64p, u32p]
         L.txq_count_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -376,6 +377,12 @@ class Index:
         assert out.dtype == np.uint64 and out.flags.c_contiguous and out.size == k.size * self.shard_words
         check(lib().txq_probe(self._h, k.ctypes.data_as(u64p), k.size, out.ctypes.data_as(u64p)))
         return out
+
+    def probe_sorted(self):
+        """(calls that bucketed their batch, answers that ran in bucket order): txq_index_probe_sorted"""
+        out = (C.c_uint64 * 2)()
+        check(lib().txq_index_probe_sorted(self._h, out))
+        return int(out[0]), int(out[1])
 
     def probe_device(self, d_kmers, n, d_masks, d_alive=None, stream=None):
         check(lib().txq_probe_device(self._h, d_kmers, n, d_masks, d_alive, stream))

@@ -86,6 +86,9 @@ void read_knobs() {
     k.probe_table_keep = !is("TXQ_PROBE_TABLE_KEEP", '0');
     k.probe_table_fused = !is("TXQ_PROBE_TABLE_FUSED", '0');
     k.probe_table_tile = !is("TXQ_PROBE_TABLE_TILE", '0');
+    k.probe_sort = !is("TXQ_PROBE_SORT", '0');
+    k.probe_sort_min = std::max(1LL, num("TXQ_PROBE_SORT_MIN", kSortMinDefault));
+    k.probe_sort_bucket_kb = std::max(1LL, num("TXQ_PROBE_SORT_BUCKET_KB", kSortBucketKbDefault));
 #ifdef TXQ_EXPERIMENTS
     // timing experiment of tools/ab_probe_ceiling.sh: the domain table's answer without its row loads (1) or its mask stores (2) - WRONG masks
     k.probe_experiment = (int)num("TXQ_PROBE_EXPERIMENT", 0) & 3;
@@ -421,6 +424,23 @@ int txq_probe_device(txq_index* ix, const uint64_t* d_kmers, size_t n, uint64_t*
     if (ix->is_hibf) return hibf_probe(*ix, knobs(), d_kmers, n, d_masks, d_alive, s);
     hipError_t e = probe_flat(*ix, knobs(), d_kmers, n, d_masks, d_alive, s);
     if (e != hipSuccess) return fail_hip(e, "probe kernel launch");
+    return TXQ_OK;
+}
+
+// What the flat probe's sorted answer did so far (tests tell its paths apart by it); waits for the index's last table call.
+int txq_index_probe_sorted(txq_index* ix, uint64_t out[2]) {
+    if (!ix || !out) return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = bind_index(ix)) return rc;
+    Index::ProbeTable& pt = ix->probe_table;
+    std::lock_guard<std::mutex> lock(pt.mutex);
+    out[0] = pt.sort_planned;
+    out[1] = 0;
+    if (pt.recorded && pt.state) {
+        uint32_t ran = 0;
+        TXQ_HIP(hipEventSynchronize(pt.done.get()));
+        TXQ_HIP(hipMemcpy(&ran, pt.state.get() + kStateSorted, sizeof ran, hipMemcpyDeviceToHost));
+        out[1] = ran;
+    }
     return TXQ_OK;
 }
 

@@ -79,6 +79,9 @@ struct Knobs {
     bool probe_table_keep = true;  // TXQ_PROBE_TABLE_KEEP=0: the domain table is built from row 0 on every call (A/B and tests)
     bool probe_table_fused = true;  // TXQ_PROBE_TABLE_FUSED=0: a call on kept rows runs sample, build and answer, not the one launch that does all three (A/B and tests)
     bool probe_table_tile = true;   // TXQ_PROBE_TABLE_TILE=0: no table-only tile body, every tile of an answer takes probe_tile (A/B and tests)
+    bool probe_sort = true;         // TXQ_PROBE_SORT=0: a large kept call is never answered from a value-bucketed batch (txq_probe_plan.hpp plan_probe_sort)
+    long long probe_sort_min = kSortMinDefault;             // TXQ_PROBE_SORT_MIN: the smallest batch that is bucketed
+    long long probe_sort_bucket_kb = kSortBucketKbDefault;  // TXQ_PROBE_SORT_BUCKET_KB: table rows per bucket, in KiB
     int probe_experiment = 0;       // TXQ_PROBE_EXPERIMENT, TXQ_EXPERIMENTS builds only: bit 0 the answer loads no rows, bit 1 it stores no masks (timing, wrong masks)
 };
 Knobs knobs();      // a copy of the snapshot taken at the last entry point (published under a lock: entry points run on several threads)
@@ -215,6 +218,12 @@ struct Index {
         ProbeKeep keep;                                 // the generation the rows belong to, the calls so far
         Event done;
         bool recorded = false, refused = false;         // (refused: the allocation failed once, not tried again)
+        // scratch of the sorted answer (plan_probe_sort): the batch's records in bucket order; counts[bucket][chunk] and,
+        // behind them, kSortMaxBuckets bucket totals.  Grown like `rows`; sort_refused: an allocation failed once.
+        DeviceBuffer<uint64_t> sort_records;
+        DeviceBuffer<uint32_t> sort_counts;
+        bool sort_refused = false;
+        uint64_t sort_planned = 0;                      // calls that launched the partition since the state words were last zeroed (txq_index_probe_sorted)
         std::mutex mutex;
     } probe_table;
 

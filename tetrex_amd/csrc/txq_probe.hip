@@ -41,7 +41,17 @@
 // into.  `valid` has two copies, used alternately: a one-launch call writes the rows [V, E) in the launch that publishes E,
 // and a wave that read E there would read rows not yet written.  The statistics have three slots (add, read, zero).  No
 // state word is read by the waves of a launch and written in the same launch (txq_probe_plan.hpp probe_slots).
-// Per probe of the answer: 8 (k-mer) + W*8 (table row) + W*8 (mask); a fresh call n/2 bytes of sample, and per new row
+//   kept, sorted (txq_probe_plan.hpp plan_probe_sort: one launch, no `alive`, rows of 16 or 32 whole words, a batch of at least
+//     TXQ_PROBE_SORT_MIN k-mers; TXQ_PROBE_SORT=0: never): three launches in front of the answer partition the batch into value
+//     buckets v >> shift, a bucket's rows about 1 MB of the table - probe_sort_count_kernel (a histogram per chunk of 4096
+//     k-mers; a k-mer at or above `valid` sets the call's `outside` flag), probe_sort_scan_kernel (offsets per bucket and chunk),
+//     probe_sort_scatter_kernel (records v << 32 | position, in bucket order).  The answer (probe_sorted_answer_kernel: the
+//     same body, an instance of its own so that every other answer keeps its registers) then takes its tiles from the
+//     records: workgroup b the tiles (b % 8) * tiles_per_xcd + (b / 8) * 4 + wave, so that XCD b % 8 walks one contiguous eighth
+//     of them and its L2 holds the rows it reads; a tile stores to the rows its records name.  With `outside` set (and with
+//     valid == 0, where count does not even read the batch) scan and scatter leave at once and the answer runs in batch order.
+//     A sorted answer meets no k-mer at or above `valid`: it adds nothing to the statistics, and builds [V, E) like any other.
+// Per probe of the answer: 8 (k-mer) + W*8 (table row) + W*8 (mask); a sorted call 32 more (k-mer twice, record twice); a fresh call n/2 bytes of sample, and per new row
 // h*W*8 + W*8 to extend the table.
 #include "txq_internal.hpp"
 #include "txq_probe_plan.hpp"
@@ -86,6 +96,11 @@ struct TableArgs {
     ProbeSlots slot;
     uint32_t experiment;      // TXQ_EXPERIMENTS builds only (TXQ_PROBE_EXPERIMENT: timing experiments, wrong masks)
     uint32_t table_tile;      // a full tile whose 64 k-mers all have a row takes table_tile (TXQ_PROBE_TABLE_TILE=0: never)
+    // the sorted answer (txq_probe_plan.hpp plan_probe_sort; records == nullptr: none): the batch's records in bucket order,
+    // the remap of its tiles, and this call's / the next call's `outside` flag
+    const uint64_t* records;
+    uint32_t tiles_per_xcd, sort_blocks;
+    uint32_t outside, outside_zero;
 };
 // the rows of a sampled call: the build writes [lo, rows), its answer reads [0, rows)
 __device__ __forceinline__ ProbeRows table_rows(const TableArgs& T) {
@@ -260,9 +275,13 @@ __device__ __forceinline__ void probe_tile(const IbfDev& f, const uint64_t* __re
 // the path WITHOUT the stores, and would wait for earlier stores of the group.  With one group the loads are therefore waited
 // for as a whole in front of the stores, which then need no wait at all; with several (LPK > 8 and an odd or masked row) the
 // compiler's waits stand.  Requires chunks <= LPK (the caller takes it at LPK <= 16 only).
-template <int LPK, bool WHOLE>
+// SORTED (WHOLE rows, no `alive`): the tile is 64 records of the bucketed batch, lane l: row `row`, written to row `dst` of
+// the masks (a second shuffle per step; the rows of a store instruction are then no longer adjacent), of which the first
+// `count` exist (RAGGED: count < 64, the last tile; its lanes past `count` load row 0 and store nothing).
+template <int LPK, bool WHOLE, bool SORTED = false, bool RAGGED = false>
 __device__ __forceinline__ void table_tile(const IbfDev& f, uint64_t* __restrict__ masks, uint64_t* __restrict__ alive,
-                                           const uint64_t* __restrict__ table, uint32_t row, uint32_t experiment, size_t tile) {
+                                           const uint64_t* __restrict__ table, uint32_t row, uint32_t experiment, size_t tile,
+                                           uint32_t dst = 0, uint32_t count = 64) {
     constexpr int KPS = 64 / LPK;
     constexpr int G = LPK < 8 ? LPK : 8;
     constexpr int GROUPS = LPK / G;
@@ -278,24 +297,24 @@ __device__ __forceinline__ void table_tile(const IbfDev& f, uint64_t* __restrict
 #endif
     bool my_alive = false;
     u32x4 x[2][G];
-    auto load_group = [&](int g, u32x4* dst) {
+    auto load_group = [&](int g, u32x4* out) {
         uint32_t r[G];
 #pragma unroll
         for (int u = 0; u < G; ++u) r[u] = (uint32_t)__shfl((int)row, (g * G + u) * KPS + grp);
         if constexpr (!WHOLE) {
 #pragma unroll
-            for (int u = 0; u < G; ++u) dst[u] = u32x4{0u, 0u, 0u, 0u};
+            for (int u = 0; u < G; ++u) out[u] = u32x4{0u, 0u, 0u, 0u};
         }
 #ifdef TXQ_EXPERIMENTS
         if (experiment & 1u) {  // no row loads: the mask is a constant
 #pragma unroll
-            for (int u = 0; u < G; ++u) dst[u] = u32x4{0x55555555u, 0x33333333u, 0x0f0f0f0fu, 0x00ff00ffu};
+            for (int u = 0; u < G; ++u) out[u] = u32x4{0x55555555u, 0x33333333u, 0x0f0f0f0fu, 0x00ff00ffu};
             return;
         }
 #endif
         if (on) {
 #pragma unroll
-            for (int u = 0; u < G; ++u) dst[u] = ld16(table + (size_t)r[u] * f.stride + 2u * sub);
+            for (int u = 0; u < G; ++u) out[u] = ld16(table + (size_t)r[u] * f.stride + 2u * sub);
         }
     };
     load_group(0, x[0]);
@@ -311,7 +330,15 @@ __device__ __forceinline__ void table_tile(const IbfDev& f, uint64_t* __restrict
             for (int u = 0; u < G; ++u) sink ^= cur[u].x ^ cur[u].y ^ cur[u].z ^ cur[u].w;
         } else
 #endif
-        if constexpr (WHOLE) {
+        if constexpr (SORTED) {
+            // (the destination rows are shuffled here, not with the row indices: a second group's would cost LPK 16 its fourth wave)
+            uint32_t to[G];
+#pragma unroll
+            for (int u = 0; u < G; ++u) to[u] = (uint32_t)__shfl((int)dst, (g * G + u) * KPS + grp);
+#pragma unroll
+            for (int u = 0; u < G; ++u)
+                if (!RAGGED || (uint32_t)((g * G + u) * KPS + grp) < count) st16_stream(masks + (size_t)to[u] * f.shard_words + 2u * sub, cur[u]);
+        } else if constexpr (WHOLE) {
 #pragma unroll
             for (int u = 0; u < G; ++u) st16_stream(masks + (base + (g * G + u) * KPS + grp) * f.shard_words + 2u * sub, cur[u]);
         } else if (on) {
@@ -319,7 +346,7 @@ __device__ __forceinline__ void table_tile(const IbfDev& f, uint64_t* __restrict
             for (int u = 0; u < G; ++u) store_chunk(f, masks, base + (g * G + u) * KPS + grp, sub, cur[u]);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (alive) {
+        if (!SORTED && alive) {
 #pragma unroll
             for (int u = 0; u < G; ++u) {
                 const uint64_t b = __ballot(on && nonzero(cur[u]));
@@ -327,7 +354,7 @@ __device__ __forceinline__ void table_tile(const IbfDev& f, uint64_t* __restrict
             }
         }
     }
-    if (alive) {
+    if (!SORTED && alive) {
         const uint64_t bits = __ballot(my_alive);
         if (lane == 0) alive[tile] = bits;
     }
@@ -339,14 +366,89 @@ __device__ __forceinline__ void table_tile(const IbfDev& f, uint64_t* __restrict
 #endif
 }
 
-// A wave owns the tiles wave, wave + n_waves, ... of the batch.  Requires bin_size < 2^32 and an even stride.
-// MODE kBuild: the tiles are those of the values [lo, rows) of table_rows, written to T.table.
-// MODE kAnswer: the batch's tiles read the table below `valid` - a full tile that lies below it as a whole through table_tile,
-// any other (the ragged last tile, a k-mer at or above `valid`, a tree root) through probe_tile; then the tiles of the values
-// [valid, rows) of answer_rows are built into T.table as a second loop of the same waves (its registers are the larger of the two bodies, not their sum) -
+// The tiles of a sorted answer (answer_body below): workgroup b, b + gridDim.x, ... of the plan's workgroups takes tile
+// (b % 8) * tiles_per_xcd + (b / 8) * 4 + wave of the records.  Every record's value lies below `valid`.
+template <int LPK>
+__device__ __forceinline__ void sorted_tiles(const IbfDev& f, size_t n, uint64_t* __restrict__ masks, const TableArgs& T) {
+    const size_t n_tiles = (n + 63) >> 6;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t b = blockIdx.x; b < T.sort_blocks; b += gridDim.x) {
+        const size_t tile = (size_t)(b % kSortXcds) * T.tiles_per_xcd + (size_t)(b / kSortXcds) * 4u + wave;
+        if (tile >= n_tiles) continue;
+        const size_t mine = (tile << 6) + lane;
+        if ((tile << 6) + 64 <= n) {
+            const uint64_t rec = __builtin_nontemporal_load(T.records + mine);
+            table_tile<LPK, true, true, false>(f, masks, nullptr, T.table, (uint32_t)(rec >> 32), T.experiment, tile, (uint32_t)rec);
+        } else {
+            const uint64_t rec = mine < n ? __builtin_nontemporal_load(T.records + mine) : 0;
+            table_tile<LPK, true, true, true>(f, masks, nullptr, T.table, (uint32_t)(rec >> 32), T.experiment, tile, (uint32_t)rec,
+                                                       (uint32_t)(n - (tile << 6)));
+        }
+    }
+}
+
+// The answer of a table call (probe_kernel<..., kAnswer> and probe_sorted_answer_kernel below): the batch's tiles read the
+// table below `valid` - a full tile that lies below it as a whole through table_tile, any other (the ragged last tile, a
+// k-mer at or above `valid`, a tree root) through probe_tile; then the tiles of the values [valid, rows) of answer_rows are
+// built into T.table as a second loop of the same waves (its registers are the larger of the two bodies, not their sum) -
 // nothing in a sampled call, whose build ran before.  Each wave that met k-mers in [rows, cap) adds them to this call's
 // statistics, and one thread leaves behind what the next call reads: `valid` = rows in the copy this launch does not read,
-// and the next call's statistics and sample words zeroed.
+// and the next call's statistics, sample words and `outside` flag zeroed.
+// SORT: the batch was bucketed in front of this launch (T.records); if none of its k-mers lies at or above `valid` the tiles
+// are those of the records (sorted_tiles), else the in-order loop runs as if nothing had been bucketed.
+template <int LPK, int H, int U, bool NT, class ROOT, bool SORT>
+__device__ __forceinline__ void answer_body(const IbfDev& f, const uint64_t* __restrict__ kmers, size_t n, uint64_t* __restrict__ masks,
+                                            uint64_t* __restrict__ alive, const ROOT& R, const TableArgs& T) {
+    const size_t wave = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const size_t n_waves = (size_t)gridDim.x * (blockDim.x >> 6);
+    WaveStats st;
+    const ProbeExtend ex = answer_rows(T);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        T.state[T.slot.valid_write] = ex.rows;
+        T.state[T.slot.stat_zero] = 0;
+        T.state[T.slot.stat_zero + 1] = 0;
+        T.state[T.slot.acc_zero] = 0;
+        T.state[T.slot.acc_zero + 1] = 0;
+        T.state[T.outside_zero] = 0;
+    }
+    const size_t n_tiles = (n + 63) >> 6;
+    // (rows of up to 32 words only: at LPK 32 and 64 the body's two row buffers cost the kernel 1 to 4 waves/SIMD and
+    // measured no gain, profiles/probe_table_tile_ab.txt)
+    constexpr bool kTableTile = !ROOT::kActive && LPK <= 16;
+    const bool tile_ok = kTableTile && T.table_tile && ex.valid;
+    const bool whole = (f.stride >> 1) == (uint32_t)LPK && !(f.shard_words & 1u);
+    bool sorted = false;
+    if constexpr (SORT) {
+        sorted = T.state[T.outside] == 0;
+        if (sorted) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(T.state + kStateSorted, 1u);
+            sorted_tiles<LPK>(f, n, masks, T);
+        }
+    }
+    for (size_t tile = sorted ? n_tiles : wave; tile < n_tiles; tile += n_waves) {
+        const size_t mine = (tile << 6) + (threadIdx.x & 63);
+        const uint64_t v = mine < n ? __builtin_nontemporal_load(kmers + mine) : 0;
+        if constexpr (kTableTile) {
+            if (tile_ok && (tile << 6) + 64 <= n && __ballot(v < ex.valid) == ~0ULL) {
+                if (whole) table_tile<LPK, true>(f, masks, alive, T.table, (uint32_t)v, T.experiment, tile);
+                else table_tile<LPK, false>(f, masks, alive, T.table, (uint32_t)v, T.experiment, tile);
+                continue;
+            }
+        }
+        probe_tile<LPK, H, U, NT, ROOT, kAnswer>(f, kmers, n, masks, alive, R, T.table, ex.valid, 0, ex.rows, T.cap, st, T.experiment, tile, v);
+    }
+    if (st.count && (threadIdx.x & 63) == 0) {
+        atomicMax(T.state + T.slot.stat_add, st.top);
+        atomicAdd(T.state + T.slot.stat_add + 1, st.count);
+    }
+    const size_t x_tiles = ((size_t)ex.rows + 63) >> 6;
+    for (size_t tile = (ex.valid >> 6) + wave; tile < x_tiles; tile += n_waves)
+        probe_tile<LPK, H, U, NT, ROOT, kBuild>(f, nullptr, ex.rows, T.table, nullptr, R, nullptr, 0, ex.valid, 0, 0, st, 0, tile);
+}
+
+// A wave owns the tiles wave, wave + n_waves, ... of the batch.  Requires bin_size < 2^32 and an even stride.
+// MODE kBuild: the tiles are those of the values [lo, rows) of table_rows, written to T.table.
+// MODE kAnswer: answer_body, in batch order.
 template <int LPK, int H, int U, bool NT, class ROOT = NoRoot, int MODE = kPlain>
 __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __restrict__ kmers, size_t n,
                                                     uint64_t* __restrict__ masks, uint64_t* __restrict__ alive, ROOT R = ROOT{},
@@ -364,40 +466,20 @@ __global__ __launch_bounds__(256) void probe_kernel(IbfDev f, const uint64_t* __
         for (size_t tile = (tr.lo >> 6) + wave; tile < n_tiles; tile += n_waves)
             probe_tile<LPK, H, U, NT, ROOT, kBuild>(f, nullptr, tr.rows, T.table, nullptr, R, nullptr, 0, tr.lo, 0, 0, st, 0, tile);
     } else {
-        const ProbeExtend ex = answer_rows(T);
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            T.state[T.slot.valid_write] = ex.rows;
-            T.state[T.slot.stat_zero] = 0;
-            T.state[T.slot.stat_zero + 1] = 0;
-            T.state[T.slot.acc_zero] = 0;
-            T.state[T.slot.acc_zero + 1] = 0;
-        }
-        const size_t n_tiles = (n + 63) >> 6;
-        // (rows of up to 32 words only: at LPK 32 and 64 the body's two row buffers cost the kernel 1 to 4 waves/SIMD and
-        // measured no gain, profiles/probe_table_tile_ab.txt)
-        constexpr bool kTableTile = !ROOT::kActive && LPK <= 16;
-        const bool tile_ok = kTableTile && T.table_tile && ex.valid;
-        const bool whole = (f.stride >> 1) == (uint32_t)LPK && !(f.shard_words & 1u);
-        for (size_t tile = wave; tile < n_tiles; tile += n_waves) {
-            const size_t mine = (tile << 6) + (threadIdx.x & 63);
-            const uint64_t v = mine < n ? __builtin_nontemporal_load(kmers + mine) : 0;
-            if constexpr (kTableTile) {
-                if (tile_ok && (tile << 6) + 64 <= n && __ballot(v < ex.valid) == ~0ULL) {
-                    if (whole) table_tile<LPK, true>(f, masks, alive, T.table, (uint32_t)v, T.experiment, tile);
-                    else table_tile<LPK, false>(f, masks, alive, T.table, (uint32_t)v, T.experiment, tile);
-                    continue;
-                }
-            }
-            probe_tile<LPK, H, U, NT, ROOT, kAnswer>(f, kmers, n, masks, alive, R, T.table, ex.valid, 0, ex.rows, T.cap, st, T.experiment, tile, v);
-        }
-        if (st.count && (threadIdx.x & 63) == 0) {
-            atomicMax(T.state + T.slot.stat_add, st.top);
-            atomicAdd(T.state + T.slot.stat_add + 1, st.count);
-        }
-        const size_t x_tiles = ((size_t)ex.rows + 63) >> 6;
-        for (size_t tile = (ex.valid >> 6) + wave; tile < x_tiles; tile += n_waves)
-            probe_tile<LPK, H, U, NT, ROOT, kBuild>(f, nullptr, ex.rows, T.table, nullptr, R, nullptr, 0, ex.valid, 0, 0, st, 0, tile);
+        (void)wave, (void)n_waves, (void)st;
+        answer_body<LPK, H, U, NT, ROOT, false>(f, kmers, n, masks, alive, R, T);
     }
+}
+
+// The answer of a call whose batch was bucketed (plan_probe_sort: LPK 8 or 16, no `alive`, no root): the same body with the
+// sorted tiles compiled in - an instance of its own, so that every other answer keeps the registers it had.  It is held to
+// the waves per SIMD of the answer it stands in for (profiles/probe_sorted_resource_usage.txt): left alone, LPK 16 with 3 and
+// 5 hash functions took 130 VGPRs, two more than four waves allow.
+constexpr int sorted_answer_waves(int lpk, int h) { return lpk == 16 && h == 2 ? 2 : (lpk == 8 && h == 5) || (lpk == 16 && h == 4) ? 3 : 4; }
+template <int LPK, int H>
+__global__ __launch_bounds__(256, sorted_answer_waves(LPK, H)) void probe_sorted_answer_kernel(IbfDev f, const uint64_t* __restrict__ kmers, size_t n, uint64_t* __restrict__ masks,
+                                                                  TableArgs T) {
+    answer_body<LPK, H, 2, false, NoRoot, true>(f, kmers, n, masks, nullptr, NoRoot{}, T);
 }
 
 // <= 64 bins in this shard: one 8-byte word per row, one lane per k-mer.
@@ -514,6 +596,116 @@ __global__ __launch_bounds__(256) void probe_domain_kernel(const uint64_t* __res
     }
 }
 
+// The partition in front of a sorted answer (txq_probe_plan.hpp plan_probe_sort): three launches, no answer to the host.
+// A k-mer is in the domain when v < valid, the `valid` the answer will use (answer_rows).
+// counts[bucket * chunks + chunk], and behind them (at buckets * chunks) the buckets' totals.
+struct SortArgs {
+    uint32_t* counts;
+    uint64_t* records;
+    uint32_t shift, buckets, chunks;
+};
+// exclusive scan over the 256 threads of a workgroup (wsum: 4 words of LDS); `total` = the sum over all of them
+__device__ __forceinline__ uint32_t block_scan256(uint32_t x, uint32_t* wsum, uint32_t& total) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t incl = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
+        if ((int)lane >= o) incl += up;
+    }
+    __syncthreads();  // (wsum may still be read from the scan before)
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    total = 0;
+    for (uint32_t w = 0; w < 4; ++w) {
+        if (w < wave) before += wsum[w];
+        total += wsum[w];
+    }
+    return before + incl - x;
+}
+static constexpr int kSortPerThread = kSortChunk / 256;
+
+// workgroup c: the histogram of chunk c over the buckets; a k-mer at or above `valid` sets the call's `outside` flag
+__global__ __launch_bounds__(256) void probe_sort_count_kernel(const uint64_t* __restrict__ kmers, size_t n, SortArgs S, TableArgs T) {
+    __shared__ uint32_t hist[kSortMaxBuckets];
+    const uint32_t valid = answer_rows(T).valid;
+    if (valid == 0) {  // no row to read (a batch whose domain never paid): nothing is bucketed, the batch is not even read
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(T.state + T.outside, 1u);
+        return;
+    }
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * kSortChunk + threadIdx.x;
+    uint64_t v[kSortPerThread];
+#pragma unroll
+    for (int j = 0; j < kSortPerThread; ++j) v[j] = base + j * 256 < n ? __builtin_nontemporal_load(kmers + base + j * 256) : 0;
+    bool out = false;
+#pragma unroll
+    for (int j = 0; j < kSortPerThread; ++j) {
+        if (base + j * 256 >= n) continue;
+        if (v[j] < valid) atomicAdd(&hist[(uint32_t)v[j] >> S.shift], 1u);
+        else out = true;
+    }
+    if (__ballot(out) && (threadIdx.x & 63) == 0) atomicOr(T.state + T.outside, 1u);
+    __syncthreads();
+    if (threadIdx.x < S.buckets) S.counts[(size_t)threadIdx.x * S.chunks + blockIdx.x] = hist[threadIdx.x];
+}
+
+// workgroup b: the exclusive prefix sum of bucket b's counts over the chunks, in place, and the bucket's total
+// (the count kernel found a k-mer outside: the answer will not read the records, scan and scatter leave at once)
+__global__ __launch_bounds__(256) void probe_sort_scan_kernel(SortArgs S, TableArgs T) {
+    __shared__ uint32_t wsum[4];
+    if (T.state[T.outside]) return;
+    uint32_t* row = S.counts + (size_t)blockIdx.x * S.chunks;
+    uint32_t carry = 0;
+    for (uint32_t c0 = 0; c0 < S.chunks; c0 += 256) {
+        const uint32_t c = c0 + threadIdx.x;
+        const uint32_t x = c < S.chunks ? row[c] : 0;
+        uint32_t total;
+        const uint32_t ex = block_scan256(x, wsum, total);
+        if (c < S.chunks) row[c] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) S.counts[(size_t)S.buckets * S.chunks + blockIdx.x] = carry;
+}
+
+// The chunk once more: its records staged in LDS in bucket order, then written so that each bucket's run of the chunk is
+// contiguous in the records (the order inside a bucket: whatever the LDS atomics gave).
+__global__ __launch_bounds__(256) void probe_sort_scatter_kernel(const uint64_t* __restrict__ kmers, size_t n, SortArgs S, TableArgs T) {
+    __shared__ uint32_t hist[kSortMaxBuckets], delta[kSortMaxBuckets], wsum[4];
+    __shared__ uint64_t stage[kSortChunk];
+    if (T.state[T.outside]) return;
+    const uint32_t valid = answer_rows(T).valid;
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * kSortChunk + threadIdx.x;
+    uint64_t v[kSortPerThread];
+    uint32_t rank[kSortPerThread];
+#pragma unroll
+    for (int j = 0; j < kSortPerThread; ++j) v[j] = base + j * 256 < n ? __builtin_nontemporal_load(kmers + base + j * 256) : ~0ULL;
+#pragma unroll
+    for (int j = 0; j < kSortPerThread; ++j) rank[j] = v[j] < valid ? atomicAdd(&hist[(uint32_t)v[j] >> S.shift], 1u) : 0u;
+    __syncthreads();
+    const bool mine = threadIdx.x < S.buckets;
+    uint32_t total;
+    const uint32_t bucket_base = block_scan256(mine ? S.counts[(size_t)S.buckets * S.chunks + threadIdx.x] : 0u, wsum, total);
+    const uint32_t local = block_scan256(hist[threadIdx.x], wsum, total);  // total: the chunk's k-mers in the domain
+    const uint32_t global = mine ? bucket_base + S.counts[(size_t)threadIdx.x * S.chunks + blockIdx.x] : 0u;
+    __syncthreads();
+    hist[threadIdx.x] = local;
+    delta[threadIdx.x] = global - local;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kSortPerThread; ++j)
+        if (v[j] < valid) stage[hist[(uint32_t)v[j] >> S.shift] + rank[j]] = (v[j] << 32) | (uint32_t)(base + j * 256);
+    __syncthreads();
+    for (uint32_t p = threadIdx.x; p < total; p += 256) {
+        const uint64_t rec = stage[p];
+        S.records[(size_t)(uint32_t)(delta[(uint32_t)(rec >> 32) >> S.shift] + p)] = rec;
+    }
+}
+
 // ---- launchers --------------------------------------------------------------------------
 
 static inline unsigned grid_for(size_t work_items, unsigned per_block) {
@@ -589,10 +781,17 @@ hipError_t launch_probe(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* 
 // The domain-table path (header comment).  T.ratio: the table is used when at least ratio * D k-mers of the batch lie below D
 // (0: whenever D fits the table).  The table holds T.cap_rows >= cap rows; the caller keeps other calls off it until the answer ran.
 template <int LPK>
-static hipError_t launch_table_lpk(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* m, uint64_t* a, const TableArgs& T, hipStream_t s) {
+static hipError_t launch_table_lpk(const IbfDev& f, const uint64_t* k, size_t n, uint64_t* m, uint64_t* a, const TableArgs& T, const SortArgs& S,
+                                   hipStream_t s) {
     // a build's grid covers the call's capacity (neither `valid` nor D is known on the host); waves with nothing to do leave at once
     const unsigned bgrid = (unsigned)std::min<size_t>(((size_t)T.cap + 255) / 256, kBuildBlocks);
-    const unsigned grid = grid_for((n + 63) / 64, 4);
+    unsigned grid = grid_for((n + 63) / 64, 4);
+    if (T.records) {  // the sorted answer: the batch bucketed first; a grid of a multiple of 8 workgroups, so that b % 8 stays with a workgroup
+        probe_sort_count_kernel<<<S.chunks, 256, 0, s>>>(k, n, S, T);
+        probe_sort_scan_kernel<<<S.buckets, 256, 0, s>>>(S, T);
+        probe_sort_scatter_kernel<<<S.chunks, 256, 0, s>>>(k, n, S, T);
+        grid = (std::max(std::min<unsigned>(grid, T.sort_blocks), bgrid) + kSortXcds - 1) / kSortXcds * kSortXcds;
+    }
     if (T.sampled) {
         // the sample: the heads of `segs` segments, each shared by as many blocks as give a thread at most kDomainLoads k-mers
         const uint32_t segs = (uint32_t)std::min<size_t>(std::max<size_t>(n / 1024, 1), 512);
@@ -606,6 +805,12 @@ static hipError_t launch_table_lpk(const IbfDev& f, const uint64_t* k, size_t n,
             if constexpr (H >= 2) {
                 if (T.sampled) probe_kernel<LPK, H, 2, false, NoRoot, kBuild><<<bgrid, 256, 0, s>>>(f, nullptr, 0, T.table, nullptr, NoRoot{}, T);
                 // a one-launch call builds too: a small batch that has to build many rows does not do it with a handful of blocks
+                if constexpr (LPK == 8 || LPK == 16) {
+                    if (T.records) {
+                        probe_sorted_answer_kernel<LPK, H><<<grid, 256, 0, s>>>(f, k, n, m, T);
+                        return;
+                    }
+                }
                 probe_kernel<LPK, H, 2, false, NoRoot, kAnswer><<<T.sampled ? grid : std::max(grid, bgrid), 256, 0, s>>>(f, k, n, m, a, NoRoot{}, T);
             }
         }))
@@ -646,21 +851,41 @@ hipError_t probe_flat(Index& ix, const Knobs& kn, const uint64_t* k, size_t n, u
     if (call.zero_state) {  // on this call's stream, like everything else: later calls are ordered behind it by `done`
         hipError_t e = hipMemsetAsync(pt.state.get(), 0, kStateWords * sizeof(uint32_t), s);
         if (e != hipSuccess) return e;
+        pt.sort_planned = 0;  // (counted on the same base as the device's kStateSorted)
     }
     // a kept call is one launch: the answer counts what it had to gather and builds what the call before counted
     // (TXQ_PROBE_TABLE_FUSED=0: sample, build and answer as in a fresh call, on the rows the table holds)
     const bool sampled = call.fresh || !kn.probe_table_fused;
-    const TableArgs T{pt.rows.get(), pt.state.get(), kn.probe_table == 1 ? 0u : kTableRatio, (uint32_t)pt.cap_rows, (uint32_t)cap, call.fresh ? 1u : 0u,
-                      sampled ? 1u : 0u, probe_slots(pt.keep.calls - 1), (uint32_t)kn.probe_experiment, kn.probe_table_tile ? 1u : 0u};
     const uint32_t chunks = f.stride >> 1;
+    const uint32_t lpk = chunks <= 1 ? 1 : chunks <= 2 ? 2 : chunks <= 4 ? 4 : chunks <= 8 ? 8 : chunks <= 16 ? 16 : chunks <= 32 ? 32 : 64;
+    // a large kept call is answered from its batch in value-bucket order (txq_probe_plan.hpp plan_probe_sort); scratch that
+    // cannot be had is no error, the call is answered in batch order as before
+    ProbeSort ps = plan_probe_sort(!sampled && kn.probe_table_tile, a != nullptr, false, lpk, f.stride, f.shard_words, n, pt.cap_rows,
+                                   kn.probe_sort && !pt.sort_refused, kn.probe_sort_min, kn.probe_sort_bucket_kb, kn.kmer_table_mb);
+    if (ps.on) {
+        const auto after_last_call = free_after([&pt] { if (pt.recorded) (void)hipEventSynchronize(pt.done.get()); });
+        if (pt.sort_records.reserve(exactly(n * sizeof(uint64_t)), after_last_call) ||
+            pt.sort_counts.reserve(exactly(((size_t)ps.buckets * ps.chunks + kSortMaxBuckets) * sizeof(uint32_t)), after_last_call)) {
+            (void)hipGetLastError();
+            pt.sort_refused = true;
+            ps = ProbeSort{};
+        }
+    }
+    const uint32_t parity = (uint32_t)((pt.keep.calls - 1) & 1);
+    const TableArgs T{pt.rows.get(), pt.state.get(), kn.probe_table == 1 ? 0u : kTableRatio, (uint32_t)pt.cap_rows, (uint32_t)cap, call.fresh ? 1u : 0u,
+                      sampled ? 1u : 0u, probe_slots(pt.keep.calls - 1), (uint32_t)kn.probe_experiment, kn.probe_table_tile ? 1u : 0u,
+                      ps.on ? pt.sort_records.get() : nullptr, (uint32_t)ps.tiles_per_xcd, (uint32_t)ps.blocks,
+                      kStateOutside + parity, kStateOutside + (parity ^ 1u)};
+    const SortArgs S{pt.sort_counts.get(), pt.sort_records.get(), ps.shift, ps.buckets, ps.chunks};
+    if (ps.on) ++pt.sort_planned;
     hipError_t e;
-    if (chunks <= 1) e = launch_table_lpk<1>(f, k, n, m, a, T, s);
-    else if (chunks <= 2) e = launch_table_lpk<2>(f, k, n, m, a, T, s);
-    else if (chunks <= 4) e = launch_table_lpk<4>(f, k, n, m, a, T, s);
-    else if (chunks <= 8) e = launch_table_lpk<8>(f, k, n, m, a, T, s);
-    else if (chunks <= 16) e = launch_table_lpk<16>(f, k, n, m, a, T, s);
-    else if (chunks <= 32) e = launch_table_lpk<32>(f, k, n, m, a, T, s);
-    else e = launch_table_lpk<64>(f, k, n, m, a, T, s);
+    if (chunks <= 1) e = launch_table_lpk<1>(f, k, n, m, a, T, S, s);
+    else if (chunks <= 2) e = launch_table_lpk<2>(f, k, n, m, a, T, S, s);
+    else if (chunks <= 4) e = launch_table_lpk<4>(f, k, n, m, a, T, S, s);
+    else if (chunks <= 8) e = launch_table_lpk<8>(f, k, n, m, a, T, S, s);
+    else if (chunks <= 16) e = launch_table_lpk<16>(f, k, n, m, a, T, S, s);
+    else if (chunks <= 32) e = launch_table_lpk<32>(f, k, n, m, a, T, S, s);
+    else e = launch_table_lpk<64>(f, k, n, m, a, T, S, s);
     if (e != hipSuccess) return e;
     e = hipEventRecord(pt.done.get(), s);
     if (e != hipSuccess) return e;

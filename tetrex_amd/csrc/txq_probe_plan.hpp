@@ -67,7 +67,10 @@ TXQ_HOST_DEVICE inline ProbeExtend extend_rows(uint32_t valid, uint32_t top, uin
 //   kStateStat   three exact statistics {top, count}: the answer of call c adds into slot c % 3, reads slot (c + 2) % 3 (what
 //                call c - 1 added) and zeroes slot (c + 1) % 3 for call c + 1.
 // No word is read by the waves of a launch and written in the same launch.
-enum : uint32_t { kStateAcc = 0, kStateValid = 4, kStateStat = 6, kStateWords = 12 };
+//   kStateOutside  two flags "a k-mer of the batch lies at or above `valid`" of the sorted answer (plan_probe_sort below): the
+//                count kernel of call c sets flag c & 1, its answer reads it and zeroes flag (c + 1) & 1 (every answer does)
+//   kStateSorted   how many answers ran in sorted mode since the state was zeroed (one thread adds; tests read it)
+enum : uint32_t { kStateAcc = 0, kStateValid = 4, kStateStat = 6, kStateOutside = 12, kStateSorted = 14, kStateWords = 16 };
 struct ProbeSlots {
     uint32_t acc, acc_zero;                  // word offsets of this call's sample accumulator and the next call's
     uint32_t valid_read, valid_write;        // the copy of `valid` this call reads / stores
@@ -78,6 +81,53 @@ inline ProbeSlots probe_slots(uint64_t c) {
     const uint32_t p = (uint32_t)(c & 1), t = (uint32_t)(c % 3);
     return ProbeSlots{kStateAcc + 2u * p, kStateAcc + 2u * (p ^ 1u), kStateValid + p, kStateValid + (p ^ 1u),
                       kStateStat + 2u * t, kStateStat + 2u * ((t + 2u) % 3u), kStateStat + 2u * ((t + 1u) % 3u)};
+}
+
+// The sorted answer of a large kept call: the batch is partitioned into value buckets v >> shift in front of the answer
+// (count, scan, scatter: records (v << 32 | position) in bucket order), and a workgroup on XCD x answers the x-th eighth of
+// the records, so that the table rows an XCD reads at any one time are about one bucket's, which its L2 holds.
+//   shift          a bucket's rows take about bucket_kb KiB (a power of two of rows, at least one), and at most
+//                  kSortMaxBuckets buckets cover the table's cap_rows rows
+//   chunks         workgroups of count and scatter: kSortChunk k-mers each
+//   tiles_per_xcd  workgroup b of the answer (four waves, workgroups are dealt round-robin over the 8 XCDs) takes the tiles
+//                  sort_tile(b, wave): XCD x walks the tiles [x * tiles_per_xcd, (x + 1) * tiles_per_xcd)
+//   blocks         workgroups b the answer has to walk (a multiple of 8; its grid is one too, so b % 8 stays with a workgroup)
+static constexpr uint32_t kSortChunk = 4096, kSortMaxBuckets = 256, kSortXcds = 8;
+// TXQ_PROBE_SORT_MIN unset: the smallest batch that gained at both domains measured, 2^18 and 2^20 values (2^22 k-mers gained 16 us
+// at the one and lost 14 us at the other, 2^20 lost 3 us: profiles/probe_sorted_ab.txt)
+static constexpr long long kSortMinDefault = 1 << 23;
+static constexpr long long kSortBucketKbDefault = 1024;
+struct ProbeSort {
+    bool on = false;
+    uint32_t shift = 0, buckets = 0, chunks = 0;
+    uint64_t n_tiles = 0, tiles_per_xcd = 0, blocks = 0;
+};
+inline uint64_t sort_tile(const ProbeSort& p, uint64_t block, uint32_t wave) {
+    return (block % kSortXcds) * p.tiles_per_xcd + (block / kSortXcds) * 4u + wave;
+}
+// kept_fused: the call is one launch on kept rows; lpk: lanes per k-mer of the kernel instance (pow2 >= stride / 2);
+// sort: TXQ_PROBE_SORT (0 never); sort_min: TXQ_PROBE_SORT_MIN; bucket_kb: TXQ_PROBE_SORT_BUCKET_KB.
+// The scratch (8 bytes of records per k-mer of the largest batch, kept with the index) is bounded twice: rows of 16 or 32
+// words only (LPK 8 and 16, the widths that were measured: at most 1/16 of the caller's masks), and at most scratch_mb MiB
+// (TXQ_KMER_TABLE_MB, the budget of the table itself).
+inline ProbeSort plan_probe_sort(bool kept_fused, bool has_alive, bool has_root, uint32_t lpk, uint32_t stride, uint32_t shard_words, uint64_t n,
+                                 size_t cap_rows, bool sort, long long sort_min, long long bucket_kb, long long scratch_mb) {
+    ProbeSort p;
+    const bool whole = stride / 2 == lpk && !(stride & 1) && !(shard_words & 1) && shard_words == stride;
+    if (!sort || !kept_fused || has_alive || has_root || lpk < 8 || lpk > 16 || !whole || n == 0 || (n >> 32) || cap_rows == 0 || (cap_rows >> 32) ||
+        sort_min < 1 || n < (uint64_t)sort_min || scratch_mb < 0 || n * 8 > ((uint64_t)scratch_mb << 20))
+        return p;
+    const uint64_t row_bytes = (uint64_t)stride * 8;
+    const uint64_t bucket_rows = std::max<uint64_t>(((uint64_t)std::max(bucket_kb, 1LL) << 10) / row_bytes, 1);
+    while ((2ull << p.shift) <= bucket_rows) ++p.shift;
+    while ((((uint64_t)cap_rows - 1) >> p.shift) + 1 > kSortMaxBuckets) ++p.shift;
+    p.buckets = (uint32_t)((((uint64_t)cap_rows - 1) >> p.shift) + 1);
+    p.chunks = (uint32_t)((n + kSortChunk - 1) / kSortChunk);
+    p.n_tiles = (n + 63) >> 6;
+    p.tiles_per_xcd = ((p.n_tiles + kSortXcds - 1) / kSortXcds + 3) & ~(uint64_t)3;
+    p.blocks = kSortXcds * (p.tiles_per_xcd / 4);
+    p.on = true;
+    return p;
 }
 
 // Is the table's content still valid?  Decided by API call order on the host: the index's generation counts the calls that
