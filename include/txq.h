@@ -69,6 +69,8 @@ extern "C" {
  *   TXQ_EDIT_LONG_SPAN=<bytes>                        bytes of text per lane group of the long-pattern edit-distance kernel (txq_edit_search_long, below)
  *   TXQ_EDIT_WINDOWS_BUNDLE=1|2|4                     the most (window, bin) pairs that walk a bin's text together (txq_edit_windows, below)
  *   TXQ_COUNT_WINDOWS_UNIT=<n>, TXQ_COUNT_WINDOWS_WAVES=1|4   windows per workgroup of the sliding count and its waves (txq_count_windows, below)
+ *   TXQ_COUNT_WINDOWS_TREE=0|1                        on an HIBF: every (window, IBF) pair counted in full | the count slides down the tree
+ *                                                     (txq_count_windows, below)
  *   TXQ_PROBE_TABLE=0|1                               a flat probe's table of its batch's k-mer domain: never | whenever it fits
  *                                                     (unset: where the batch repeats its values often enough to pay for it)
  *   TXQ_PROBE_TABLE_KEEP=0                            that table is built from its first row on every call, not kept with the
@@ -232,18 +234,30 @@ int txq_count(txq_index* ix, const uint64_t* values, const uint64_t* offsets, si
  * its predecessor: the values that enter are added to the counters, those that leave are subtracted (their rows were read a
  * window ago and come from L2), so a window costs the rows of two steps, not of its whole length.  A window is counted by ONE
  * workgroup: a window of 10^5 values is exact, but slow (txq_count_device spreads such a query over many workgroups).
- * HIBF: the windows run as independent queries, each (window, IBF) pair counted in full by one wave — exact, no sliding; every
- * IBF may have at most 8192 technical bins, as for txq_count.
+ * HIBF: the count slides down the tree.  A wave takes a unit of min(TXQ_COUNT_WINDOWS_UNIT, 32) consecutive windows on ONE IBF
+ * and slides over those windows of the unit that visit the IBF — a subsequence of a sliding sequence still slides —, then hands
+ * every child the windows of the unit that descend into it, as one work item of the next level.  With TXQ_COUNT_WINDOWS_TREE=0
+ * the windows run as independent queries, each (window, IBF) pair counted in full by one wave, no sliding.  Every IBF may have
+ * at most 8192 technical bins, as for txq_count.
  * txq_count_windows checks before anything is launched that the windows slide, that each ends within n_values and that no
  * pointer it needs is NULL (TXQ_ERR_ARG); txq_count_windows_device trusts the device arrays it is given.  It allocates nothing
  * outside the index's scratch and does not synchronise with the host.
  *   TXQ_COUNT_WINDOWS_UNIT=<n>    windows per workgroup on a flat IBF (default 16, 1 .. 2^20; read at every call)
  *   TXQ_COUNT_WINDOWS_WAVES=1|4   waves of that workgroup (default 1; read at every call)
- * The results are the same for every value of either. */
+ *   TXQ_COUNT_WINDOWS_TREE=0|1    on an HIBF: independent queries | sliding in units of min(TXQ_COUNT_WINDOWS_UNIT, 32) windows
+ *                                 (default 1: on 2*10^5 windows sliding by 16 values it takes 0.25 to 0.63 of the other route's
+ *                                 time; read at every call)
+ * The results are the same for every value of each. */
 int txq_count_windows_device(txq_index* ix, const uint64_t* d_values, const uint64_t* d_win_begin, const uint32_t* d_win_len,
                              size_t n_windows, const uint32_t* d_thresholds, uint64_t* d_hits, uint32_t* d_counts, void* stream);
 int txq_count_windows(txq_index* ix, const uint64_t* values, size_t n_values, const uint64_t* win_begin, const uint32_t* win_len,
                       size_t n_windows, const uint32_t* thresholds, uint64_t* hits, uint32_t* counts);  /* host buffers, synchronous */
+/* A trace of the index's last txq_count_windows / txq_count_windows_device call on an HIBF, for tests and measurements:
+ * out[0] = (window, IBF) visits, out[1] = values added to counters, out[2] = values subtracted from them, out[3] = work items
+ * (one wave each).  With TXQ_COUNT_WINDOWS_TREE=0 that is visits, the summed lengths of the visiting windows, 0 and visits.
+ * All zero on a flat IBF, before the first call, and after a call of no windows or one that failed.  Waits for the index's
+ * last such call. */
+int txq_count_windows_trace(txq_index* ix, uint64_t out[4]);
 
 /* Six-frame translation of nucleotide records into the k-mer values of a peptide index (`tetrex search --translate`; not in
  * the reference).  Record r is the bytes d_seq[d_rec_offsets[r] .. d_rec_offsets[r+1]) (n_records + 1 ascending offsets).

@@ -22,7 +22,7 @@ SYMBOLS = [
     "txq_init", "txq_shutdown", "txq_last_error", "txq_device_count",
     "txq_index_upload", "txq_index_upload_subtrees", "txq_index_get_info", "txq_index_free", "txq_index_supports_dense", "txq_index_memory", "txq_index_set_tag", "txq_index_get_tag", "txq_index_create_ibf",
     "txq_index_download_words", "txq_probe", "txq_probe_device", "txq_index_probe_sorted", "txq_emplace_device", "txq_count", "txq_count_device",
-    "txq_count_windows", "txq_count_windows_device",
+    "txq_count_windows", "txq_count_windows_device", "txq_count_windows_trace",
     "txq_translate_bound", "txq_translate_device", "txq_translate",
     "txq_translate_windows_bound", "txq_translate_windows_device", "txq_translate_windows", "txq_translate_frames_bound", "txq_translate_frames_device", "txq_translate_frames",
     "txq_frame_window_letters", "txq_frame_window_letters_device",
@@ -95,6 +95,7 @@ def lib():
         L.txq_count_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.txq_count_windows.argtypes = [C.c_void_p, u64p, C.c_size_t, u64p, u32p, C.c_size_t, u32p, u64p, u32p]
         L.txq_count_windows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.txq_count_windows_trace.argtypes = [C.c_void_p, u64p]
         L.txq_translate_bound.restype = C.c_uint64
         L.txq_translate_bound.argtypes = [u64p, C.c_size_t, C.c_uint]
         L.txq_translate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -428,6 +429,12 @@ class Index:
 
     def count_windows_device(self, d_values, d_begins, d_lens, n_windows, d_thresholds, d_hits, d_counts=None, stream=None):
         check(lib().txq_count_windows_device(self._h, d_values, d_begins, d_lens, n_windows, d_thresholds, d_hits, d_counts, stream))
+
+    def count_windows_trace(self):
+        """(visits, values added, values subtracted, items) of the last count_windows call on an HIBF: txq_count_windows_trace"""
+        out = (C.c_uint64 * 4)()
+        check(lib().txq_count_windows_trace(self._h, out))
+        return tuple(int(x) for x in out)
 
     def emplace_device(self, d_values, d_bins_of, n, stream=None):
         check(lib().txq_emplace_device(self._h, d_values, d_bins_of, n, stream))

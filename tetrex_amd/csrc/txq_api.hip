@@ -3,6 +3,7 @@
 // that needs one fails with TXQ_ERR_STATE.
 #include "../../include/txq.h"
 #include "txq_internal.hpp"
+#include "txq_count_windows_tree_plan.hpp"
 #include "txq_hibf_plan.hpp"
 
 #include <algorithm>
@@ -578,7 +579,10 @@ int txq_count_windows(txq_index* ix, const uint64_t* values, size_t n_values, co
         if (j && win_begin[j] + win_len[j] < win_begin[j - 1] + win_len[j - 1]) return fail(TXQ_ERR_ARG, "window ends are not ascending at window %zu", j);
     }
     const size_t W = ix->shard_words;
-    if (n_windows == 0 || W == 0) return TXQ_OK;
+    if (n_windows == 0 || W == 0) {
+        ix->count_windows_trace.recorded = false;  // (txq_count_windows_trace: nothing of the call before)
+        return TXQ_OK;
+    }
     const uint64_t v0 = win_begin[0], span = win_begin[n_windows - 1] + win_len[n_windows - 1] - v0;
     if (span >> 32) return fail(TXQ_ERR_ARG, "%llu values: at most 2^32-1 per call", (unsigned long long)span);
     if (span && !values) return fail(TXQ_ERR_ARG, "null argument");
@@ -609,6 +613,21 @@ int txq_count_windows(txq_index* ix, const uint64_t* values, size_t n_values, co
     TXQ_HIP(hipMemcpyAsync(hits, d_hit, n_windows * W * 8, hipMemcpyDeviceToHost, st));
     if (counts) TXQ_HIP(hipMemcpyAsync(counts, d_cnt, n_windows * W * 64 * 4, hipMemcpyDeviceToHost, st));
     TXQ_HIP(hipStreamSynchronize(st));
+    return TXQ_OK;
+}
+
+// What the index's last txq_count_windows* call on an HIBF did (tests and measurements tell its routes apart by it); waits for that call.
+int txq_count_windows_trace(txq_index* ix, uint64_t out[4]) {
+    if (!ix || !out) return fail(TXQ_ERR_ARG, "null argument");
+    if (int rc = bind_index(ix)) return rc;
+    Index::CountWindowsTrace& tr = ix->count_windows_trace;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (tr.recorded && tr.totals) {
+        unsigned long long totals[kCwTraceSlots * kCwTraceWords];  // (the waves add to kCwTraceSlots sets of totals)
+        TXQ_HIP(hipEventSynchronize(tr.done.get()));
+        TXQ_HIP(hipMemcpy(totals, tr.totals.get(), sizeof totals, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < kCwTraceSlots * kCwTraceWords; ++i) out[i % kCwTraceWords] += totals[i];
+    }
     return TXQ_OK;
 }
 

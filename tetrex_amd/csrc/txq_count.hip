@@ -29,6 +29,7 @@
 #include "txq_internal.hpp"
 #include "txq_count_plan.hpp"
 #include "txq_count_windows_plan.hpp"
+#include "txq_count_windows_tree_plan.hpp"
 #include <algorithm>
 
 namespace txq {
@@ -48,6 +49,7 @@ struct CountOut {
     uint64_t* hits;           // [nq][W]
     uint32_t* counts;         // [nq][64 W] or null
     uint32_t* acc;            // flat: long queries' accumulators [nq][64 W] (== counts when counts are asked for)
+    unsigned long long* trace;  // null, or [kCwTraceSlots][kCwTraceWords] totals of txq_count_windows on an HIBF (txq_count_windows_trace)
     uint64_t user_bins;       // bits of a full mask (t = 0 selects only these)
     uint32_t nq, W, word0;
 };
@@ -279,6 +281,7 @@ __global__ __launch_bounds__(64) void count_hibf_level_kernel(HibfCountView t, C
     __syncthreads();
     const uint32_t count = in ? min(*in_count, in_cap) : n_level0;
     const size_t W = o.W;
+    unsigned long long t_items = 0, t_added = 0;  // this wave's part of txq_count_windows_trace (o.trace), added once at its end
     for (uint32_t item = blockIdx.x; item < count; item += gridDim.x) {
         const uint32_t q = in ? in[item].kmer : item;
         const uint32_t id = in ? in[item].ibf : 0u;
@@ -317,9 +320,130 @@ __global__ __launch_bounds__(64) void count_hibf_level_kernel(HibfCountView t, C
                 }
             }
         }
+        ++t_items, t_added += q_hi - q_lo;
         __syncthreads();
         for (uint32_t i = lane; i < chunks * kLdsPitch; i += 64) lds[i] = 0;
         __syncthreads();
+    }
+    if (o.trace && lane == 0 && t_items) {  // (windows as independent queries: a visit is an item, counted in full)
+        unsigned long long* tr = o.trace + (size_t)(blockIdx.x % kCwTraceSlots) * kCwTraceWords;
+        atomicAdd(tr + kCwTraceVisits, t_items);
+        atomicAdd(tr + kCwTraceAdded, t_added);
+        atomicAdd(tr + kCwTraceItems, t_items);
+    }
+}
+
+// ---- HIBF, sliding windows (txq_count_windows) --------------------------------------------------------------------------------
+//
+// One level: work item (unit, IBF, mask) per wave (txq_count_windows_tree_plan.hpp).  Level 0 (in == null): (u, root, all
+// windows of unit u) for u < n_level0.  The wave walks the item's windows in order and keeps the CURRENT window's counters
+// on this IBF in LDS: cw_step between two VISITED windows says which values enter and which leave, or that the counters
+// start from zero — always so at the item's first window, since they hold what the wave's last item left.  After each
+// window the technical-bin pass of count_hibf_level_kernel runs on the counters; a merged bin that passes appends nothing,
+// its lane ORs the window's bit into the bin's mask word (LDS, behind the counters: one lane owns a bin in a pass).  After
+// the last window every non-zero mask word becomes the child's item, and is zeroed for the wave's next item.
+// LDS: max chunks * 129 u32 counters, then one u32 mask word per technical bin of the widest IBF.
+
+struct WindowsTreeOut {
+    const uint64_t* values;
+    const uint64_t* begin;       // n (of this device call: it starts at a unit boundary)
+    const uint32_t* len;         // n
+    const uint32_t* thr;         // n
+    uint64_t* hits;              // [n][W]
+    uint32_t* counts;            // [n][64 W] or null
+    unsigned long long* trace;   // [kCwTraceSlots][kCwTraceWords]: txq_count_windows_trace
+    uint64_t user_bins;
+    uint64_t n;
+    uint32_t W, word0, U;
+};
+
+template <int H>
+__global__ __launch_bounds__(64) void count_windows_tree_kernel(HibfCountView t, WindowsTreeOut o, const CwTreeItem* __restrict__ in,
+                                                                const uint32_t* __restrict__ in_count, uint32_t in_cap, uint32_t n_level0,
+                                                                CwTreeItem* __restrict__ out, uint32_t* __restrict__ out_count, uint32_t out_cap,
+                                                                uint32_t cnt_words, uint32_t mask_words) {
+    extern __shared__ uint32_t lds[];
+    uint32_t* kid_mask = lds + cnt_words;
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t i = lane; i < mask_words; i += 64) kid_mask[i] = 0;
+    __syncthreads();
+    const uint32_t count = in ? min(*in_count, in_cap) : n_level0;
+    const size_t W = o.W;
+    // This wave's part of txq_count_windows_trace, over all of its items: added once, at the wave's end, to one of kCwTraceSlots
+    // sets of totals.  (One set that every item adds to costs 10 ns an item on 3 * 10^5 items: the adds to one address queue up.)
+    unsigned long long t_visits = 0, t_added = 0, t_subtracted = 0, t_items = 0;
+    for (uint32_t item = blockIdx.x; item < count; item += gridDim.x) {
+        const uint32_t unit = in ? in[item].unit : item;
+        const uint32_t id = in ? in[item].ibf : 0u;
+        const uint32_t mask = in ? in[item].mask : cwt_level0_mask(unit, o.U, o.n);
+        const IbfDev f = t.ibf[id];
+        const uint64_t off = t.map_off[id], moff = t.merged_off[id];
+        const uint32_t chunks = f.stride == 1 ? 1u : f.stride >> 1;
+        uint32_t lpk_log2 = 0;
+        while ((1u << lpk_log2) < chunks) ++lpk_log2;
+        const uint64_t j0 = cw_unit_first(unit, o.U);
+        uint64_t added = 0, subtracted = 0;
+        for (CwTreeWalk wk = cwt_walk(mask); cwt_more(wk);) {
+            const uint32_t wi = cwt_window(wk);
+            const uint64_t j = j0 + wi;
+            const uint64_t b = o.begin[j], e = b + o.len[j];
+            const CwStep st = cwt_advance(wk, b, e);
+            if (st.reset) {  // (the reads of the window before are behind the barrier that ended it)
+                for (uint32_t i = lane; i < chunks * kLdsPitch; i += 64) lds[i] = 0;
+                __syncthreads();
+            }
+            count_values<H, false>(f, lpk_log2, 0, chunks, o.values, st.add_lo, st.add_hi, lds);
+            if (st.add_lo < st.add_hi) added += st.add_hi - st.add_lo;
+            if (st.sub_lo < st.sub_hi) {
+                count_values<H, true>(f, lpk_log2, 0, chunks, o.values, st.sub_lo, st.sub_hi, lds);
+                subtracted += st.sub_hi - st.sub_lo;
+            }
+            __syncthreads();
+            const uint32_t thr = o.thr[j];
+            for (uint32_t b0 = 0; b0 < f.bins; b0 += 64) {
+                const uint32_t tb = b0 + lane;
+                const bool live = tb < f.bins;
+                const uint32_t n = live ? lds[(tb >> 7) * kLdsPitch + (tb & 127u)] : 0u;
+                const uint64_t ub = live ? t.tb_user[off + tb] : 0;
+                const bool merged = live && ub == TXQ_MERGED_BIN;
+                if (merged && n >= thr && ((t.descend[moff + (tb >> 6)] >> (tb & 63u)) & 1ULL)) kid_mask[tb] |= 1u << wi;
+                if (live && !merged && (tb + 1 == f.bins || t.tb_user[off + tb + 1] != ub)) {  // the last technical bin of a user bin's run
+                    uint32_t sum = n;
+                    for (uint32_t s = tb; s > 0 && t.tb_user[off + s - 1] == ub; --s) sum += lds[((s - 1) >> 7) * kLdsPitch + ((s - 1) & 127u)];
+                    const uint64_t w = ub >> 6;
+                    if (ub < o.user_bins && w >= o.word0 && w < (uint64_t)o.word0 + o.W) {
+                        const size_t wl = (size_t)(w - o.word0);
+                        // (a user bin whose parts are not adjacent has several runs: a hit if any passes, its count the largest)
+                        if (o.counts) atomicMax(o.counts + ((size_t)j * W + wl) * 64 + (ub & 63), sum);
+                        if (sum >= thr) atomicOr((unsigned long long*)(o.hits + (size_t)j * W + wl), 1ULL << (ub & 63));
+                    }
+                }
+            }
+            __syncthreads();  // (the next window changes the counters the run sums read)
+        }
+        for (uint32_t b0 = 0; b0 < f.bins; b0 += 64) {  // (unit, child, windows that descend) -> next level, one atomic per wave and 64 bins
+            const uint32_t tb = b0 + lane;
+            const uint32_t m = tb < f.bins ? kid_mask[tb] : 0u;
+            const uint64_t kids = __ballot(m != 0);
+            if (kids) {
+                uint32_t at = 0;
+                if (lane == 0) at = atomicAdd(out_count, (uint32_t)__builtin_popcountll(kids));
+                at = __shfl(at, 0) + (uint32_t)__builtin_popcountll(kids & ((1ULL << lane) - 1ULL));
+                if (m) {
+                    if (at < out_cap) out[at] = CwTreeItem{unit, (uint32_t)t.next[off + tb], m};
+                    kid_mask[tb] = 0;
+                }
+            }
+        }
+        t_visits += (unsigned long long)__builtin_popcount(mask), t_added += added, t_subtracted += subtracted, ++t_items;  // the item's totals, once
+        __syncthreads();
+    }
+    if (lane == 0 && t_items) {
+        unsigned long long* tr = o.trace + (size_t)(blockIdx.x % kCwTraceSlots) * kCwTraceWords;
+        atomicAdd(tr + kCwTraceVisits, t_visits);
+        atomicAdd(tr + kCwTraceAdded, t_added);
+        atomicAdd(tr + kCwTraceSubtracted, t_subtracted);
+        atomicAdd(tr + kCwTraceItems, t_items);
     }
 }
 
@@ -441,23 +565,116 @@ static int count_windows_flat(Index& ix, WindowsOut o, hipStream_t s) {
     return TXQ_OK;
 }
 
+// The totals of txq_count_windows_trace start from zero on the call's stream; `done` is recorded behind the call's last kernel.
+static int count_windows_trace_begin(Index& ix, hipStream_t s) {
+    Index::CountWindowsTrace& tr = ix.count_windows_trace;
+    if (int rc = reserved(tr.totals.reserve(exactly(kCwTraceSlots * kCwTraceWords * sizeof(unsigned long long)), after_device_wait()), "hipMalloc(scratch)")) return rc;
+    TXQ_HIP(make(tr.done));
+    TXQ_HIP(hipMemsetAsync(tr.totals.get(), 0, kCwTraceSlots * kCwTraceWords * sizeof(unsigned long long), s));
+    return TXQ_OK;
+}
+
+static int count_windows_tree(Index& ix, WindowsTreeOut o, hipStream_t s) {
+    uint32_t max_chunks = 1, h_max = 1, max_bins = 1;
+    for (const IbfDev& f : ix.ibf) {
+        const uint32_t chunks = f.stride == 1 ? 1u : f.stride >> 1;
+        if (chunks > kTileChunks) return fail(TXQ_ERR_ARG, "txq_count: an IBF of the tree has more than %u technical bins", kTileChunks * 128);
+        max_chunks = std::max(max_chunks, chunks);
+        max_bins = std::max(max_bins, (uint32_t)f.bins);
+        h_max = std::max(h_max, f.hash_funs);
+    }
+    o.U = cwt_unit(env_u32("TXQ_COUNT_WINDOWS_UNIT", kCountWindowsUnitDefault, 1, kCountWindowsUnitMax));
+    const size_t row = (size_t)o.W * 64;
+    TXQ_HIP(hipMemsetAsync(o.hits, 0, (size_t)o.n * o.W * 8, s));
+    if (o.counts) TXQ_HIP(hipMemsetAsync(o.counts, 0, (size_t)o.n * row * 4, s));
+    const size_t n_units = (size_t)cw_units(o.n, o.U);
+    const size_t per_call = cwt_units_per_call(n_units, ix.max_level_width, kHibfCapItems);
+    const size_t cap = cwt_frontier_items(per_call, ix.max_level_width);
+    if (ix.depth > 1)
+        for (int i = 0; i < 2; ++i)
+            if (int rc = reserved(ix.frontier[i].reserve(exactly(cap * sizeof(CwTreeItem)), after_device_wait()), "hipMalloc(scratch)")) return rc;
+    if (int rc = reserved(ix.d_counts.reserve(exactly(((size_t)ix.depth + 2) * 4), after_device_wait()), "hipMalloc(scratch)")) return rc;
+    const HibfCountView t{ix.d_ibf, ix.d_next, ix.d_tb_user, ix.d_map_off, ix.d_descend, ix.d_merged_off};
+    const uint32_t cnt_words = max_chunks * kLdsPitch, mask_words = (max_bins + 63u) / 64u * 64u;
+    const size_t lds_bytes = ((size_t)cnt_words + mask_words) * 4;
+    if (lds_bytes > (48u << 10)) {  // (more dynamic LDS than the default limit: ask for it, once per call)
+        hipError_t e = hipSuccess;
+        if (!with_hash_funs(h_max, [&](auto h) {
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&count_windows_tree_kernel<decltype(h)::value>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            }))
+            return fail(TXQ_ERR_ARG, "hash_funs outside 1..5");
+        if (e != hipSuccess) return fail_hip(e, "hipFuncSetAttribute");
+    }
+    for (size_t u0 = 0; u0 < n_units; u0 += per_call) {  // device calls are cut at unit boundaries
+        const size_t j0 = (size_t)cw_unit_first(u0, o.U), nu = std::min(per_call, n_units - u0);
+        WindowsTreeOut c = o;
+        c.n = std::min<uint64_t>((uint64_t)nu * o.U, o.n - j0);
+        c.begin = o.begin + j0;
+        c.len = o.len + j0;
+        c.thr = o.thr + j0;
+        c.hits = o.hits + j0 * o.W;
+        c.counts = o.counts ? o.counts + j0 * row : nullptr;
+        TXQ_HIP(hipMemsetAsync(ix.d_counts.get(), 0, ((size_t)ix.depth + 2) * 4, s));
+        for (uint32_t lvl = 0; lvl < ix.depth; ++lvl) {
+            const CwTreeItem* in = lvl ? reinterpret_cast<const CwTreeItem*>(ix.frontier[(lvl - 1) & 1].get()) : nullptr;
+            const uint32_t* in_count = lvl ? ix.d_counts.get() + (lvl - 1) : nullptr;
+            CwTreeItem* out = reinterpret_cast<CwTreeItem*>(ix.frontier[lvl & 1].get());
+            const uint32_t out_cap = ix.depth > 1 && lvl + 1 < ix.depth ? (uint32_t)cap : 0u;
+            const unsigned grid = lvl ? kCountGrid : (unsigned)std::min<size_t>(nu, kCountGrid);
+            if (!with_hash_funs(h_max, [&](auto h) {
+                    count_windows_tree_kernel<decltype(h)::value><<<grid, 64, lds_bytes, s>>>(t, c, in, in_count, (uint32_t)cap, (uint32_t)nu, out, ix.d_counts.get() + lvl,
+                                                                                              out_cap, cnt_words, mask_words);
+                }))
+                return fail(TXQ_ERR_ARG, "hash_funs outside 1..5");
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return fail_hip(e, "hibf count windows kernel launch");
+        }
+    }
+    return TXQ_OK;
+}
+
 int count_windows_device(Index& ix, const uint64_t* d_values, const uint64_t* d_begin, const uint32_t* d_len, size_t n_windows,
                          const uint32_t* d_thr, uint64_t* d_hits, uint32_t* d_counts, hipStream_t s) {
+    if (ix.is_hibf) ix.count_windows_trace.recorded = false;  // (a call of no windows, or one that fails: txq_count_windows_trace reports zeros, not the call before)
     if (n_windows == 0 || ix.shard_words == 0) return TXQ_OK;
-    if (ix.is_hibf) {  // the windows as independent queries: each (window, IBF) pair counted in full by one wave, no sliding
-        CountOut o{};
-        o.values = d_values;
-        o.offsets = d_begin;
-        o.lens = d_len;
-        o.thr = d_thr;
-        o.hits = d_hits;
-        o.counts = d_counts;
-        o.acc = d_counts;
-        o.user_bins = ix.user_bins;
-        o.nq = (uint32_t)n_windows;
-        o.W = (uint32_t)ix.shard_words;
-        o.word0 = (uint32_t)ix.shard_word0;
-        return count_hibf(ix, o, s);
+    if (ix.is_hibf) {
+        if (int rc = count_windows_trace_begin(ix, s)) return rc;
+        Index::CountWindowsTrace& tr = ix.count_windows_trace;
+        int rc = TXQ_OK;
+        if (env_u32("TXQ_COUNT_WINDOWS_TREE", kCountWindowsTreeDefault, 0, 1)) {  // sliding: a wave per (unit of windows, IBF)
+            WindowsTreeOut o{};
+            o.values = d_values;
+            o.begin = d_begin;
+            o.len = d_len;
+            o.thr = d_thr;
+            o.hits = d_hits;
+            o.counts = d_counts;
+            o.trace = tr.totals.get();
+            o.user_bins = ix.user_bins;
+            o.n = n_windows;
+            o.W = (uint32_t)ix.shard_words;
+            o.word0 = (uint32_t)ix.shard_word0;
+            rc = count_windows_tree(ix, o, s);
+        } else {  // the windows as independent queries: each (window, IBF) pair counted in full by one wave, no sliding
+            CountOut o{};
+            o.values = d_values;
+            o.offsets = d_begin;
+            o.lens = d_len;
+            o.thr = d_thr;
+            o.hits = d_hits;
+            o.counts = d_counts;
+            o.acc = d_counts;
+            o.trace = tr.totals.get();
+            o.user_bins = ix.user_bins;
+            o.nq = (uint32_t)n_windows;
+            o.W = (uint32_t)ix.shard_words;
+            o.word0 = (uint32_t)ix.shard_word0;
+            rc = count_hibf(ix, o, s);
+        }
+        if (rc) return rc;
+        TXQ_HIP(hipEventRecord(tr.done.get(), s));
+        tr.recorded = true;
+        return TXQ_OK;
     }
     WindowsOut o{};
     o.values = d_values;

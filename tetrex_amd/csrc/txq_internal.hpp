@@ -195,6 +195,12 @@ struct Index {
     DeviceBuffer<uint32_t> d_counts;
     DeviceBuffer<uint64_t> scratch_dense_kmers;      // dense steps on an HIBF: the pairs' k-mers ...
     DeviceBuffer<uint64_t> scratch_dense_masks;      // ... and their descended masks
+    // txq_count_windows on an HIBF: what the last call did (txq_count_windows_trace), kCwTraceSlots sets of four u64 totals the waves add to
+    struct CountWindowsTrace {
+        DeviceBuffer<unsigned long long> totals;
+        Event done;             // behind the last call's last kernel
+        bool recorded = false;
+    } count_windows_trace;
     DeviceBuffer<uint32_t> scratch_count_acc;        // txq_count on a flat index: long queries' partial counts
     DeviceBuffer<unsigned char> scratch_count_io;    // txq_count (host buffers): the call's inputs and results
     // A flat index's masks of ALL k-mers, M[v] at kmer_table + v * shard_words for every packed value v < 2^(bits * k) (txq_exec.hip
